@@ -9,7 +9,11 @@ threefry tie-break noise, Gumbel sampling from the key).  Inputs are synthetic a
 HBM when the timed region starts.  For N>1 every rank owns 4096 more roots of one global batch (weak
 scaling, no collective on the data path; RCCL is used only for the barrier and the max-over-ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the line
+has carried: the un-settled and back-to-back runs, the roofline, the api / config 3-5 legs and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (rank 0's roots) as DIR/<name>.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -151,10 +155,12 @@ def grow_signal_pool():
 
 
 def fused_run(workload, B, rank, world, dev, steps, warmup, tiebreak, dist=None, backend="nccl", settle_ms=30.0,
-              unsettled_first=False):
+              unsettled_first=False, full=True, keep_outputs=False):
     """`steps` timed acts of the fused act() kernel on this rank's B roots of the global batch (inputs resident in
-    HBM; every act followed by the host synchronisation; barrier + max over ranks for N > 1), then the same number of
-    launches back to back with one synchronisation at the end (`pipelined`).
+    HBM; every act followed by the host synchronisation; barrier + max over ranks for N > 1), then (`full`) the same
+    number of launches back to back with one synchronisation at the end (`pipelined`).  Without `full` the timed
+    region holds no events and nothing runs after it.  `keep_outputs`: host copies of what the last timed act
+    computed, as `outputs`.
 
     Before the `warmup` untimed steps the GPU is brought to its working clocks: the MI355X ramps them over ~10 ms of
     continuous work (the same 20 timed steps measure 36.9 M env-steps/s after 5 warm-up launches = 0.5 ms, 37.6 M after
@@ -168,7 +174,9 @@ def fused_run(workload, B, rank, world, dev, steps, warmup, tiebreak, dist=None,
     weights = haiku_style_weights(0, obs_dim, E, A, F)
     g = torch.Generator().manual_seed(1000 + rank)
     obs = torch.rand(B, obs_dim, generator=g) * 2 - 1
-    noise = torch.distributions.Dirichlet(torch.full((A,), 0.3)).sample((B,)) if A > 1 else torch.ones(B, 1)
+    # seeded like obs, so that runs with the same arguments see the same inputs (--dump-outputs compares them)
+    noise = (torch.from_numpy(np.random.default_rng(2000 + rank).dirichlet([0.3] * A, B).astype(np.float32)) if A > 1
+             else torch.ones(B, 1))
     search = MuZeroSearch(B, SearchConfig(A, S, E, tiebreak=tiebreak, global_batch=B * world, root_offset=B * rank), dev)
     search.set_mlp_weights(weights, obs_dim, support, 0.99)
     d_obs, d_noise = obs.to(dev), noise.to(dev)
@@ -182,7 +190,7 @@ def fused_run(workload, B, rank, world, dev, steps, warmup, tiebreak, dist=None,
     # has to grow stalls the host for tens of milliseconds -- once, but inside a 24 ms timed region that is the whole
     # measurement (seen on this pool: one 45 ms step among 200 steps of 0.118 ms).
     ev_every = 10 if steps >= 20 else 1
-    sampled = [i for i in range(steps) if i % ev_every == ev_every // 2]
+    sampled = [i for i in range(steps) if i % ev_every == ev_every // 2] if full else []
     ev_sets = []
     for _ in range(3):
         evs = {i: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for i in sampled}
@@ -223,7 +231,7 @@ def fused_run(workload, B, rank, world, dev, steps, warmup, tiebreak, dist=None,
         if dist:
             dist.barrier()  # closing bracket: no rank leaves the timed region's neighbourhood before all are done
             torch.cuda.synchronize()
-        return reduce_max(dt), float(np.mean([evs[i][0].elapsed_time(evs[i][1]) for i in sampled]))
+        return reduce_max(dt), (float(np.mean([evs[i][0].elapsed_time(evs[i][1]) for i in sampled])) if sampled else None)
 
     # THE TIMED REGION ("B / wall_time(act), host sync at the end included"): every act is followed by
     # the host synchronisation the reference's np.asarray / .item() imply -- the next act of an RL loop needs this
@@ -247,19 +255,45 @@ def fused_run(workload, B, rank, world, dev, steps, warmup, tiebreak, dist=None,
             step(i)
             torch.cuda.synchronize()
     elapsed, kernel_ms = timed(True, ev_sets[0])
-    for i in range(max(10, warmup)):  # (the secondary figure gets its own untimed warm-up: a different submission pattern)
-        step(i)
-    # (the median of three runs: with 200 launches in flight the runtime sometimes stalls the host once for ~17 ms --
-    # its queue / signal bookkeeping, box dependent -- which would double this secondary figure; `value` is one run)
-    runs = sorted(timed(False, ev_sets[1]) for _ in range(3))
-    pipelined, kernel_ms_pipelined = runs[1]
-    depth_total = int(search.depth_sum.sum().item())  # last act's D (the same every act up to the key)
-    actions = search.action.cpu()
-    assert int(actions.min()) >= 0 and int(actions.max()) < A
+    outputs = None
+    if keep_outputs:  # copied before any later launch overwrites the buffers
+        outputs = {name: getattr(search, name).cpu().numpy()
+                   for name in ("action", "action_weights", "root_value", "search_value", "depth_sum")}
+    pipelined = kernel_ms_pipelined = depth_total = None
+    if full:
+        for i in range(max(10, warmup)):  # (the secondary figure gets its own untimed warm-up: a different submission pattern)
+            step(i)
+        # (the median of three runs: with 200 launches in flight the runtime sometimes stalls the host once for ~17 ms --
+        # its queue / signal bookkeeping, box dependent -- which would double this secondary figure; `value` is one run)
+        runs = sorted(timed(False, ev_sets[1]) for _ in range(3))
+        pipelined, kernel_ms_pipelined = runs[1]
+        depth_total = int(search.depth_sum.sum().item())  # last act's D (the same every act up to the key)
+        actions = search.action.cpu()
+        assert int(actions.min()) >= 0 and int(actions.max()) < A
     search.close()
     return {"elapsed": elapsed, "elapsed_unsettled": elapsed_unsettled, "kernel_ms": kernel_ms, "depth_total": depth_total,
             "weights": weights, "obs": obs,
-            "noise": noise, "pipelined": pipelined, "kernel_ms_pipelined": kernel_ms_pipelined}
+            "noise": noise, "pipelined": pipelined, "kernel_ms_pipelined": kernel_ms_pipelined, "outputs": outputs}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES):
+    """`outputs` (arrays with one row per root) -> out_dir/<name>.npy: floating arrays as float32, integer ones as
+    float64 (exact).  When they would pass `limit` bytes in all, every array keeps the same fixed, seeded sample of
+    rows, whose indices are written as rows.npy."""
+    arrs = {k: v.astype(np.float32 if v.dtype.kind == "f" else np.float64) for k, v in outputs.items()}
+    B = len(next(iter(arrs.values())))
+    row_bytes = sum(a.nbytes for a in arrs.values()) / B
+    if row_bytes * B > limit:
+        n = int((limit - 4096 * (len(arrs) + 1)) // (row_bytes + 8))  # (+ 8: the row index; 4096: .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def roofline(workload, B, kernel_ms, depth_total, kernel_ms_timed_region=None):
@@ -600,9 +634,16 @@ def main():
     ap.add_argument("--cfg4-sims", type=int, default=200, help="num_simulations of the config-4 leg (200 = BASELINE's; dry runs lower it)")
     ap.add_argument("--cfg4-acts", type=int, default=3)
     ap.add_argument("--cfg5-iters", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="also the un-settled and back-to-back runs, roofline, api, configs 3-5 and the CPU baseline "
+                         "(the --no-* switches above prune this)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0's roots) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)  # does not return
@@ -644,7 +685,8 @@ def main():
     F = 2 * support + 1
     dev = torch.device("cuda", local_rank)
     run = fused_run(args.workload, B, rank, world, dev, args.steps, args.warmup, not args.no_tiebreak, dist, backend,
-                    args.settle_ms, unsettled_first=not args.no_unsettled)
+                    args.settle_ms, unsettled_first=args.full and not args.no_unsettled, full=args.full,
+                    keep_outputs=bool(args.dump_outputs) and rank == 0)
     unsettled = None if run["elapsed_unsettled"] is None else B * world * args.steps / run["elapsed_unsettled"]
     elapsed, kernel_ms, depth_total, weights, obs, noise = (run[k] for k in ("elapsed", "kernel_ms", "depth_total",
                                                                                "weights", "obs", "noise"))
@@ -667,12 +709,6 @@ def main():
             # the pipelined rate here and this one as `value_synced`)
             "value": round(B * world * args.steps / elapsed, 1),
             "unit": "env-steps/s",
-            # the same launches enqueued back to back, one synchronisation after the last
-            # the same steps timed FIRST, right after the warm-up steps and before the clock-settling launches
-            # (BASELINE.md section 3's protocol as written)
-            "value_unsettled": None if unsettled is None else round(unsettled, 1),
-            "value_pipelined": round(B * world * args.steps / run["pipelined"], 1),
-            "ms_per_step_pipelined": round(run["pipelined"] / args.steps * 1e3, 4),
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -686,8 +722,19 @@ def main():
                        "backend": rk.describe()["backend"],
                        "launcher": os.environ.get("MUAX_BENCH_LAUNCHER", "torch.distributed.run" if world > 1 else "none"),
                        "ranks": placement},
-            "roofline": roofline(args.workload, B, run["kernel_ms_pipelined"], depth_total, kernel_ms),
         }
+        if args.full:
+            line.update({
+                # the same steps timed FIRST, right after the warm-up steps and before the clock-settling launches
+                # (BASELINE.md section 3's protocol as written)
+                "value_unsettled": None if unsettled is None else round(unsettled, 1),
+                # the same launches enqueued back to back, one synchronisation after the last
+                "value_pipelined": round(B * world * args.steps / run["pipelined"], 1),
+                "ms_per_step_pipelined": round(run["pipelined"] / args.steps * 1e3, 4),
+                "roofline": roofline(args.workload, B, run["kernel_ms_pipelined"], depth_total, kernel_ms),
+            })
+        if args.dump_outputs:
+            dump_outputs(run["outputs"], args.dump_outputs)
 
     def guarded(name, fn):
         # a secondary measurement must never cost the headline line: its failure is reported in its own slot.  With
@@ -702,8 +749,8 @@ def main():
         if rank == 0:
             line[name] = res
 
-    extras = not args.no_extras and args.workload == "cartpole" and not args.roots
-    if rank == 0 and world == 1 and not args.no_extras:
+    extras = args.full and not args.no_extras and args.workload == "cartpole" and not args.roots
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         # the reference's own entry point on the same workload
         guarded("api", lambda: api_numbers(args.workload, B, weights, obs, dev))
     if extras and world == 1:
@@ -722,7 +769,7 @@ def main():
         # BASELINE configs[3] and [4] are multi-GPU configurations: every rank runs its shard / its replica
         guarded("config4_atari", lambda: config4_atari(rk, S=args.cfg4_sims, acts=args.cfg4_acts))
         guarded("config5_gumbel_train", lambda: config5_gumbel_train(rk, iters=args.cfg5_iters))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         guarded("cpu_baseline", lambda: cpu_baseline(weights, obs.numpy(), noise.numpy(), A, E, F, S, support))
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -103,7 +103,7 @@ def test_bench_launcher_contract_with_two_ranks_on_one_gpu():
     port = 29400 + os.getpid() % 500
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "10", "--warmup", "3", "--no-config45"], env=env, cwd=ROOT,
+                          "--gpus", "2", "--steps", "10", "--warmup", "3", "--full", "--no-config45"], env=env, cwd=ROOT,
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -125,7 +125,7 @@ def test_bench_plain_invocation_launches_its_own_ranks():
     env["MUAX_BENCH_SINGLE_DEVICE"] = "1"
     env["MZS_TOWER_PAIR"] = "0"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3",
-                          "--cfg4-sims", "16", "--cfg4-acts", "1", "--cfg5-iters", "5"],
+                          "--full", "--cfg4-sims", "16", "--cfg4-acts", "1", "--cfg5-iters", "5"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -177,7 +177,7 @@ def test_bench_eight_ranks_under_torch_distributed_run_on_one_gpu():
     env["MUAX_BENCH_SINGLE_DEVICE"] = "1"
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                          "--gpus", "8", "--steps", "5", "--warmup", "2", "--cfg4-sims", "10", "--cfg4-acts", "1",
+                          "--gpus", "8", "--steps", "5", "--warmup", "2", "--full", "--cfg4-sims", "10", "--cfg4-acts", "1",
                           "--cfg5-iters", "3", "--no-cpu-baseline"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -200,7 +200,7 @@ def test_bench_eight_rank_dry_run_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MZS_TOWER_PAIR")}
     env["MUAX_BENCH_SINGLE_DEVICE"] = "1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "10", "--warmup", "3",
-                          "--cfg4-sims", "20", "--cfg4-acts", "1", "--cfg5-iters", "5"],
+                          "--full", "--cfg4-sims", "20", "--cfg4-acts", "1", "--cfg5-iters", "5"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -225,10 +225,11 @@ def test_bench_refuses_more_gpus_than_the_box_has():
 
 
 def test_bench_line_schema_at_one_gpu():
-    """The driver's N = 1 command: the line carries roofline, cpu_baseline, api, config 3/4/5 sub-objects, and
+    """The N = 1 command with --full: the line carries roofline, cpu_baseline, api, config 3/4/5 sub-objects, and
     roofline.frac is algorithmic bytes / kernel time / 8 TB/s recomputed from its own fields."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--full"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -268,6 +269,34 @@ def test_bench_line_schema_at_one_gpu():
     assert r["kernel_ms"] <= line["ms_per_step"]
 
 
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """The plain N = 1 command: the headline fields and nothing that needs runs of its own; --dump-outputs writes the
+    last timed act's outputs, and two runs with the same arguments write the same arrays."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                              "--dump-outputs", str(tmp_path / run)],
+                             env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        line = json.loads(lines[0])
+        assert line["metric"] == "batched act() env-steps/sec at num_simulations=50" and line["unit"] == "env-steps/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 7
+        assert abs(line["value"] - 4096 * 7 / (line["ms_per_step"] * 7e-3)) < 0.01 * line["value"]
+        for key in ("roofline", "cpu_baseline", "api", "value_pipelined", "value_unsettled", "config3_lunarlander",
+                    "config4_atari", "config5_gumbel_train"):
+            assert key not in line, key
+        d = {f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)}
+        assert set(d) == {"action", "action_weights", "root_value", "search_value", "depth_sum"}
+        assert all(a.dtype in (np.float32, np.float64) and len(a) == 4096 for a in d.values())
+        assert d["action"].min() >= 0 and d["action"].max() < 2 and np.allclose(d["action_weights"].sum(1), 1, atol=1e-5)
+        dumps.append(d)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
 def _rccl_worker(q, port):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -303,7 +332,7 @@ def test_bench_rccl_branch_with_one_rank():
     all_reduce(MAX) on a device tensor and all_gather_object all run through RCCL."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(MUAX_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--full",
                           "--no-cpu-baseline", "--cfg4-sims", "16", "--cfg4-acts", "1", "--cfg5-iters", "5"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]

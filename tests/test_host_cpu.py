@@ -435,6 +435,29 @@ def test_bench_refuses_to_run_without_the_devices_it_was_asked_for():
         assert "ROCm" in out.stderr
 
 
+def test_bench_dump_outputs_types_and_size_cap(tmp_path):
+    """bench.dump_outputs: floating arrays as float32, integer ones as float64 (exact); over the byte cap every array
+    keeps the same fixed, seeded sample of rows and rows.npy names them."""
+    import bench
+    rng = np.random.default_rng(1)
+    B = 1000
+    outs = {"action": rng.integers(0, 2, B).astype(np.int32), "action_weights": rng.random((B, 2)).astype(F32),
+            "depth_sum": rng.integers(0, 3000, B).astype(np.int32)}
+    bench.dump_outputs(outs, str(tmp_path / "all"))
+    d = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in outs}
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(f"{k}.npy" for k in outs)
+    assert d["action"].dtype == np.float64 and d["depth_sum"].dtype == np.float64 and d["action_weights"].dtype == F32
+    assert all(np.array_equal(d[k], outs[k]) for k in outs)
+    limit = 4096 * 4 + 6000
+    for run in ("s1", "s2"):
+        bench.dump_outputs(outs, str(tmp_path / run), limit=limit)
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= limit
+    rows = np.load(tmp_path / "s1" / "rows.npy").astype(np.int64)
+    assert 0 < len(rows) < B and np.array_equal(rows, np.load(tmp_path / "s2" / "rows.npy"))
+    for k in outs:
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{k}.npy"), outs[k][rows])
+
+
 def test_jit_planner_agrees_with_the_kernels_own_limits(tmp_path):
     """muax_amd/_jit.py::plan restates FusedCfg's LDS arithmetic in Python; a disagreement would make an on-demand build
     fail its static_asserts on the user's machine (act() would then fall to the generic route: silent, 5x slower).  The

@@ -116,7 +116,7 @@ for wl, fn in (("cartpole", "prof_cartpole.txt"), ("lunarlander", "prof_lunarlan
     if fs and ws:
         pj[wl].update({"hbm_bytes_per_launch": int((2 * fs + ws) * 1024), "fetch_size_kb_raw": fs, "write_size_kb_raw": ws,
                        "source": f"profiles/{tag}_rocprofv3_cartpole4096.txt (tools/rocprof_passes.sh: separate --pmc passes of "
-                                 f"`python bench.py --workload {wl}`)"})
+                                 f"`python bench.py --full --workload {wl}`)"})
 json.dump(pj, open(os.path.join(P, "pmc_traffic.json"), "w"), indent=1)
 print("pmc_traffic.json refreshed")
 

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
-B="python $REPO/bench.py --no-cpu-baseline $@"
+B="python $REPO/bench.py --full --no-cpu-baseline $@"
 BX="$B --no-extras"   # counter passes: the main loop only
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $B > $OUT/bench_trace.log 2>&1   # the default run of bench.py (200 steps, 20 warm-up)
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY -d $OUT/pmc1 -o pmc1 -- $BX --steps 5 --warmup 1 > $OUT/bench_pmc1.log 2>&1

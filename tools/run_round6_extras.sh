@@ -31,4 +31,4 @@ timeout 300 python tools/bench_cfg5.py 2>&1 | grep -v amdgpu.ids > $OUT/cfg5.txt
 timeout 300 python tools/bench_atari.py 128 200 2>&1 | grep -v amdgpu.ids > $OUT/atari_bench.txt
 timeout 300 python tools/bench_atari.py 1024 200 2>&1 | grep -v amdgpu.ids >> $OUT/atari_bench.txt
 (timeout 400 python tools/stress_round5.py 400 2026; timeout 400 python tools/stress_round5.py 400 8; timeout 300 python tools/stress_parity.py 400 33; timeout 300 python tools/stress_parity.py 40 34 compact; timeout 400 python tools/stress_stepwise.py 300 35) 2>&1 | grep -v amdgpu.ids > $OUT/stress_round5.txt
-MUAX_BENCH_SINGLE_DEVICE=1 timeout 600 python bench.py --gpus 2 --steps 20 --warmup 5 --cfg4-sims 200 --cfg4-acts 2 > $OUT/bench_2ranks_1gpu.json 2>> $OUT/bench.err
+MUAX_BENCH_SINGLE_DEVICE=1 timeout 600 python bench.py --gpus 2 --full --steps 20 --warmup 5 --cfg4-sims 200 --cfg4-acts 2 > $OUT/bench_2ranks_1gpu.json 2>> $OUT/bench.err

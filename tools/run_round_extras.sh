@@ -30,4 +30,4 @@ python tools/bench_repr_conv.py 2>&1 | grep -v amdgpu.ids > $OUT/repr_conv.txt
 bash tools/ab_fused.sh tools/bin/libmzsearch_split.so > $OUT/ab_split.log 2>&1
 python tools/diag_stall.py 4000 0 0 2>&1 | grep -v amdgpu.ids > $OUT/stall.txt
 python tools/diag_stall.py 4000 0 2048 2>&1 | grep -v amdgpu.ids >> $OUT/stall.txt
-MUAX_BENCH_SINGLE_DEVICE=1 python bench.py --gpus 2 --steps 20 --warmup 5 --cfg4-sims 200 --cfg4-acts 2 > $OUT/bench_2ranks_1gpu.json 2>> $OUT/bench.err
+MUAX_BENCH_SINGLE_DEVICE=1 python bench.py --gpus 2 --full --steps 20 --warmup 5 --cfg4-sims 200 --cfg4-acts 2 > $OUT/bench_2ranks_1gpu.json 2>> $OUT/bench.err
