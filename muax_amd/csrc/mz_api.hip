@@ -175,8 +175,12 @@ static void mlp_offsets(int obs_dim, int E, int A, int F, int off[19]) {
 
 template <class C>
 static int launch_train(const mz::TrainParams& p, hipStream_t stream) {
+  if (p.L > C::MAX_UNROLL) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "unroll_steps %d too large for the LDS (at most %d for this (A, E, F))", p.L, C::MAX_UNROLL);
+    return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_mlp_loss_grad: %s", msg);
+  }
   const size_t lds = sizeof(float) * ((size_t)C::WEIGHT_WORDS + (size_t)p.L * C::CK_WORDS_PER_STEP);
-  if (lds > 160 * 1024) return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_mlp_loss_grad: unroll_steps too large for the LDS");
   auto kern = mz::mz_train_kernel<C>;
   static mzh::LdsGrant granted;  // (per device and instance: the attribute call is not free, update() runs every step)
   int dev = 0;

@@ -44,6 +44,8 @@ struct TrainParams {
   int waves;
 };
 
+constexpr int TRAIN_LDS_BYTES = 160 * 1024;  // one workgroup may take all of a CU's LDS
+
 template <int A_, int E_, int F_>
 struct TrainCfg {
   static constexpr int A = A_, E = E_, F = F_, H = 16, X = E_ + A_;
@@ -62,6 +64,8 @@ struct TrainCfg {
   static constexpr int DN2 = DN1 + blk(X, H);
   static constexpr int WEIGHT_WORDS = ((DN2 + blk(H, E) + 3) / 4) * 4;
   static constexpr int CK_WORDS_PER_STEP = 16 * 16 * ES;  // 16 samples per workgroup
+  // dynamic LDS of a workgroup (weights + L kept states) is at most TRAIN_LDS_BYTES: the longest unroll it admits
+  static constexpr int MAX_UNROLL = (TRAIN_LDS_BYTES / 4 - WEIGHT_WORDS) / CK_WORDS_PER_STEP;
 };
 
 // ---- row-distributed linear layers on LDS weights ----

@@ -30,11 +30,12 @@ extern "C" int mzs_jit_train_launch(const void* params, void* stream_, char* err
   using C = mz::TrainCfg<MZ_TRAIN_A, MZ_TRAIN_E, MZ_TRAIN_F>;
   const mz::TrainParams& p = *static_cast<const mz::TrainParams*>(params);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const size_t lds = sizeof(float) * ((size_t)C::WEIGHT_WORDS + (size_t)p.L * C::CK_WORDS_PER_STEP);
-  if (lds > 160 * 1024) {
-    if (err && errlen > 0) snprintf(err, (size_t)errlen, "unroll_steps too large for the LDS");
+  if (p.L > C::MAX_UNROLL) {
+    if (err && errlen > 0)
+      snprintf(err, (size_t)errlen, "unroll_steps %d too large for the LDS (at most %d for this (A, E, F))", p.L, C::MAX_UNROLL);
     return MZS_E_UNSUPPORTED;
   }
+  const size_t lds = sizeof(float) * ((size_t)C::WEIGHT_WORDS + (size_t)p.L * C::CK_WORDS_PER_STEP);
   auto kern = mz::mz_train_kernel<C>;
   // (per device, as the built-in launcher does: the attribute call is not free and update() runs every step)
   static mzh::LdsGrant granted;

@@ -556,7 +556,9 @@ class MuZero:
                 for p, g in zip(self._fused_train.params, self._fused_train.views):
                     p.grad = g
             except ValueError as e:
-                if backend == "hip" or "no kernel instance" not in str(e):
+                # shapes the kernel cannot serve (no instance, or an unroll longer than its LDS keeps) take the
+                # torch route under backend="auto"; the kernel refuses them on the host, before any launch
+                if backend == "hip" or not any(m in str(e) for m in ("no kernel instance", "too large for the LDS")):
                     raise
                 fused = False
         if not fused:

@@ -32,9 +32,10 @@ class MZNetwork(NamedTuple):
 
 
 def min_max_normalize(s: torch.Tensor) -> torch.Tensor:
-    """muax/nn.py:37-44."""
-    s_min = s.min(dim=1, keepdim=True).values
-    s_max = s.max(dim=1, keepdim=True).values
+    """muax/nn.py:37-44.  Tied minima / maxima share their gradient evenly, jax's reduce_min / reduce_max rule
+    (amin / amax; min(dim) / max(dim) would hand all of it to one index), as the fused kernels do."""
+    s_min = s.amin(dim=1, keepdim=True)
+    s_max = s.amax(dim=1, keepdim=True)
     s_scale = s_max - s_min
     s_scale = torch.where(s_scale < 1e-5, s_scale + 1e-5, s_scale)
     return (s - s_min) / s_scale

@@ -7,68 +7,9 @@ import pytest
 import torch
 
 import muax_amd as mx
+from helpers import train_autograd as _autograd, train_batch as _batch, train_model as _model
 
 pytestmark = pytest.mark.gpu
-F32 = np.float32
-
-
-def _model(A, E, obs_dim, seed, support=10):
-    g = torch.Generator().manual_seed(seed)
-    F = 2 * support + 1
-    net = mx.nn.MZNetwork(mx.nn.Representation(E, generator=g), mx.nn.Prediction(A, F, generator=g),
-                          mx.nn.Dynamic(E, A, F, generator=g))
-    m = mx.MuZero(net, optimizer=mx.optimizers.create_optimizer("adam", 1e-2), support_size=support)
-    m.init(0, np.zeros((1, obs_dim)))
-    with torch.no_grad():  # non-zero biases so that every gradient path is exercised
-        for p in [p for mod in m.network for p in mod.parameters()]:
-            if p.dim() == 1:
-                p.add_(0.1 * torch.randn(p.shape, generator=g).to(p.device))
-    return m
-
-
-def _batch(B, L, A, obs_dim, seed):
-    rng = np.random.default_rng(seed)
-    return mx.Transition(obs=rng.uniform(-1, 1, (B, L, obs_dim)).astype(F32), a=rng.integers(0, A, (B, L)),
-                         r=rng.uniform(-2, 3, (B, L)).astype(F32), Rn=rng.uniform(-30, 60, (B, L)).astype(F32),
-                         pi=rng.dirichlet(np.ones(A), (B, L)).astype(F32).reshape(B, L, 1, A))
-
-
-def _autograd(m, b, dtype, device, **kw):
-    import copy
-    mods = [copy.deepcopy(x).to(device=device, dtype=dtype) for x in m.network]
-    m2 = mx.MuZero(mx.nn.MZNetwork(*mods), device=device)
-    m2._params, m2._support_size = True, m._support_size
-    bb = mx.Transition(**{k: (torch.as_tensor(v).to(dtype) if isinstance(v, np.ndarray) and v.dtype == F32 else v)
-                          for k, v in b.__dict__.items()})
-    orig = mx.loss.default_loss_fn
-
-    def loss64(inst, batch, **k2):  # the restated loss casts to float32; redo it in `dtype`
-        dev = inst.device
-        t = lambda x, dt=dtype: torch.as_tensor(x, device=dev).to(dt)  # noqa: E731
-        a = t(batch.a, torch.long)
-        B, L = a.shape[:2]
-        S = inst._support_size
-        r_t = mx.utils.scalar_to_support(t(batch.r).reshape(B, L), S)
-        Rn_t = mx.utils.scalar_to_support(t(batch.Rn).reshape(B, L), S)
-        pi = t(batch.pi).reshape(B, L, -1)
-        s = inst.repr_func(t(batch.obs)[:, 0])
-        loss = 0
-        for i in range(L):
-            v, lg = inst.pred_func(s)
-            s = mx.utils.scale_gradient(s, 0.5)
-            r, ns = inst.dy_func(s, a[:, i])
-            ce = mx.loss.softmax_cross_entropy
-            loss = loss + ce(r, r_t[:, i]).mean() + ce(v, Rn_t[:, i]).mean() + ce(lg, pi[:, i]).mean()
-            s = ns
-        if k2.get("divide_by_length"):
-            loss = loss / L
-        return loss + 1e-4 * 0.5 * sum((p ** 2).sum() for mod in inst.network for p in mod.parameters())
-
-    loss = (loss64 if dtype == torch.float64 else orig)(m2, bb if dtype == torch.float64 else b, **kw)
-    loss.backward()
-    w = mx.nn.mlp_trio_weights(m2.network)
-    from muax_amd._lib import MLP_WEIGHT_NAMES
-    return float(loss.detach()), [w[n].grad.detach().cpu().double().numpy() for n in MLP_WEIGHT_NAMES]
 
 
 @pytest.mark.parametrize("A,E,obs_dim,B,L,kw", [

@@ -115,6 +115,21 @@ def test_codec_matches_reference_formulas(oracle):
     g = torch.ones(3, requires_grad=True)
     (mx.utils.scale_gradient(g, 0.5) * 2).sum().backward()
     assert torch.allclose(g.grad, torch.ones(3))
+    # the two-hot target at its edges -- 0, negative values, h(x) on an integer or one ulp off it, the clip and far
+    # beyond it -- against oracle/mz_numpy.py's restatement (the target codec of the training step's fp64 reference)
+    from helpers import support_edge_scalars
+    for support in (10, 15, 20):
+        x = support_edge_scalars(support)
+        p = mx.utils.scalar_to_support(torch.from_numpy(x), support).numpy()
+        assert np.array_equal(p, mn.scalar_to_support(x, support)), support
+        assert np.allclose(p.sum(-1), 1.0, rtol=0, atol=2e-7) and (p >= 0).all()
+        hx = mn.scaling(x)
+        on = hx == np.round(hx)  # h(x) on an integer (or clipped): one bin holds all the mass
+        assert on.sum() >= 6 and np.array_equal(p[on].max(-1), np.ones(on.sum(), F32))
+        assert np.array_equal(p[on].argmax(-1), np.clip(np.round(hx[on]), -support, support).astype(int) + support)
+        out = np.abs(hx) >= support  # at or beyond the clip: all the mass on the end bin
+        assert out.sum() >= 8 and np.array_equal(p[out].argmax(-1), np.where(x[out] > 0, 2 * support, 0))
+        assert np.array_equal(p[out].max(-1), np.ones(out.sum(), F32))
 
 
 def test_model_constructor_shapes_and_errors():

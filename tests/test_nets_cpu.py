@@ -114,3 +114,39 @@ def test_ez_trio_contract_and_factories():
     m = mx.MuZero(rep, pred, dyn, device="cpu")
     m.init(0, np.zeros((1, 84, 84, 4), np.float32))
     assert m.representation(obs.numpy()).shape == (2, 6, 6, 16)
+
+
+def _minmax_grad_jax_rule(u, g):
+    """d/du of sum(g * (u - min u) / c) over one set of entries, c = max u - min u (+1e-5 when below 1e-5), with tied
+    minima / maxima sharing their gradient evenly (jax's reduce_min / reduce_max rule, muax/nn.py:37-56), in float64."""
+    u, g = np.asarray(u, np.float64), np.asarray(g, np.float64)
+    mn, mx_ = u.min(), u.max()
+    c = mx_ - mn
+    c = c + 1e-5 if c < 1e-5 else c
+    s = (u - mn) / c
+    at_min, at_max = u == mn, u == mx_
+    return (g / c + at_min * ((g * s).sum() - g.sum()) / (c * at_min.sum())
+            + at_max * (-(g * s).sum()) / (c * at_max.sum()))
+
+
+def test_min_max_normalize_shares_tied_gradients_evenly():
+    """Rows with one tie at the min, one at the max, both, none, and all entries equal (the c < 1e-5 branch): the input
+    gradient of min_max_normalize / min_max_normalize2d is the explicit jax-rule formula (min(dim) / max(dim) would send
+    a tie's whole share to one index)."""
+    rows = np.array([[1, 1, 3, 3, 2], [0.5, -1, 2, -1, 0.25], [0.5, 2, 2, -1, 0.25], [0.75] * 5,
+                     [0.125, -0.5, 1.5, 0.25, 1.0], [2, 2, 2, 2, -3]], np.float64)
+    g = np.random.default_rng(0).normal(size=rows.shape)
+    u = torch.tensor(rows, requires_grad=True)
+    y = mx.nn.min_max_normalize(u)
+    (y * torch.from_numpy(g)).sum().backward()
+    ref = np.stack([_minmax_grad_jax_rule(r, gr) for r, gr in zip(rows, g)])
+    assert np.allclose(u.grad.numpy(), ref, rtol=1e-12, atol=1e-9), (u.grad.numpy(), ref)
+    assert torch.equal(y.detach()[3], torch.zeros(5))
+    # NHWC planes: per (sample, channel) over H * W, the same rows laid out as 1 x 5 planes of two channels
+    p = np.stack([rows[:3], rows[3:]], axis=-1).reshape(3, 1, 5, 2)
+    gp = np.stack([g[:3], g[3:]], axis=-1).reshape(3, 1, 5, 2)
+    u2 = torch.tensor(p, requires_grad=True)
+    (mx.nn.min_max_normalize2d(u2) * torch.from_numpy(gp)).sum().backward()
+    ref2 = np.stack([np.stack([_minmax_grad_jax_rule(p[b, 0, :, ch], gp[b, 0, :, ch]) for ch in range(2)], -1)
+                     for b in range(3)])
+    assert np.allclose(u2.grad.numpy()[:, 0], ref2, rtol=1e-12, atol=1e-9)
