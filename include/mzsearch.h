@@ -461,6 +461,19 @@ int mzs_train_jit_abi(void);
  * arithmetic spec, same results bit for bit as an instance would give; several times slower per simulation than a
  * tuned instance, an order of magnitude faster than per-simulation launches with the caller's own nets. */
 int mzs_mlp_allow_generic(mzs_handle *h, int32_t allow);
+/* 17..64 actions under the MuZero policy: allow != 0 lets mzs_act_mlp / mzs_act_mlp_host serve them with the wide-action
+ * kernel (mz_wide.cuh) -- the whole act() in ONE launch like a fused instance, one root per wavefront, one lane per action,
+ * the root's tree in LDS, shapes at run time (embed_dim <= 64, support_size 8..31, num_simulations <= 255).  It is tried
+ * after the fused instances and before the generic route, and DECLINES (the call goes on as if it were not allowed: the
+ * generic route when that is allowed, else MZS_E_UNSUPPORTED) a Gumbel handle, num_actions <= 16, support_size outside
+ * 8..31, num_simulations > 255 and a shape whose single root does not fit a CU's LDS.  Same results bit for bit as the
+ * generic route.  Off by default: a handle that never calls this behaves as before. */
+int mzs_mlp_allow_wide(mzs_handle *h, int32_t allow);
+/* The wide kernel's LDS plan for a shape (host arithmetic, no device): out = {roots (wavefronts) per workgroup, LDS
+ * bytes per workgroup, resident roots per CU, 1 when the embeddings are kept in LDS}; MZS_E_UNSUPPORTED when the kernel
+ * declines the shape.  Per root (num_simulations + 1) x (4 + 4 num_actions [+ embed_dim] + 1) words, per workgroup the
+ * four nets' weights and num_simulations + 2 words; the workgroup size 1..4 that keeps most roots within 160 KiB. */
+int mzs_mlp_wide_plan(int32_t num_actions, int32_t embed_dim, int32_t support_size, int32_t num_simulations, int32_t out[4]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * The simulation loop of a search with the ResNet nets in ONE launch (mz_search_conv.hip).

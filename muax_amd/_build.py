@@ -2,8 +2,8 @@
 
 The library is several translation units compiled in parallel (each `hipcc -c`, objects under muax_amd/lib/obj/)
 and linked into one shared object: the C-ABI and the step-wise / training / Dirichlet kernels (mz_api.hip), the
-fused act() kernel instances in five groups (mz_fused_g*.hip, listed in mz_instances.def) and the ResNet
-recurrent kernel (mz_conv.hip).  Only the units whose sources changed are recompiled."""
+fused act() kernel instances in five groups (mz_fused_g*.hip, listed in mz_instances.def), the wide-action act()
+kernel (mz_wide.hip) and the ResNet recurrent kernel (mz_conv.hip).  Only the units whose sources changed are recompiled."""
 from __future__ import annotations
 
 import os
@@ -20,12 +20,13 @@ _FUSED = ["mz_fused_group.inc", "mz_fused_launch.h", "mz_fused.cuh", "mz_spec.cu
 # translation unit -> the headers it is rebuilt for
 UNITS = {
     "mz_api.hip": ["mz_host.h", "mz_fused_launch.h", "mz_fused.cuh", "mz_spec.cuh", "mz_step.cuh", "mz_step_jump.cuh",
-                   "mz_mlp_generic.cuh", "mz_train.cuh", "mz_dirichlet.cuh", _ABI],
+                   "mz_mlp_generic.cuh", "mz_train.cuh", "mz_dirichlet.cuh", "mz_wide_launch.h", _ABI],
     "mz_fused_g0.hip": _FUSED,
     "mz_fused_g1.hip": _FUSED,
     "mz_fused_g2.hip": _FUSED,
     "mz_fused_g3.hip": _FUSED,
     "mz_fused_g4.hip": _FUSED,
+    "mz_wide.hip": ["mz_wide.cuh", "mz_wide_launch.h", "mz_fused_launch.h", "mz_fused.cuh", "mz_spec.cuh", "mz_host.h", _ABI],
     "mz_conv.hip": ["mz_host.h", "mz_conv_host.h", "mz_conv.cuh", "mz_spec.cuh", _ABI],
     "mz_search_conv.hip": ["mz_host.h", "mz_conv_host.h", "mz_conv.cuh", "mz_step.cuh", "mz_step_jump.cuh", "mz_spec.cuh", _ABI],
     "mz_norm.hip": ["mz_host.h", "mz_norm.cuh", "mz_repr.cuh", "mz_repr_host.h", "mz_spec.cuh", _ABI],

@@ -12,6 +12,7 @@
 #include "../../include/mzsearch.h"
 #include "mz_host.h"
 #include "mz_fused_launch.h"
+#include "mz_wide_launch.h"
 #include "mz_step.cuh"
 #include "mz_step_jump.cuh"
 #include "mz_mlp_generic.cuh"
@@ -95,6 +96,7 @@ struct mzs_handle {
                                    // B N^2 path words exceed the budget -- the chunk of roots act() searches at a time
   bool allow_generic = false;      // mzs_mlp_allow_generic: shapes without a fused instance take the generic one-launch search
   float* gen_scratch = nullptr;    // generic route: prior logits [B, A] | embeddings [B, E] | actions [B]
+  bool allow_wide = false;         // mzs_mlp_allow_wide: 17..64 actions under the MuZero policy take the wide one-launch kernel
 };
 
 namespace {
@@ -254,6 +256,12 @@ int mzs_create(const mzs_config* cfg, mzs_handle** out) {
 int mzs_mlp_allow_generic(mzs_handle* h, int32_t allow) {
   if (!h) return MZS_E_INVALID;
   h->allow_generic = allow != 0;
+  return MZS_OK;
+}
+
+int mzs_mlp_allow_wide(mzs_handle* h, int32_t allow) {
+  if (!h) return MZS_E_INVALID;
+  h->allow_wide = allow != 0;
   return MZS_OK;
 }
 
@@ -550,6 +558,17 @@ int mzs_act_mlp(mzs_handle* h, const mzs_act_args* a, void* stream_) {
       if (rc != MZS_OK) return fail(h, rc, "mzs_act_mlp: %s", err.c_str());
       return MZS_OK;
     }
+  }
+  if (h->allow_wide) {  // 17..64 actions, MuZero policy: the lane-per-action kernel with the tree in LDS (mz_wide.cuh)
+    std::string err;
+    int rc = mz::wide_dispatch(mode, c.device, p, stream, A, E, F, &err);
+    if (rc == mz::kNeedEmbScratch) {  // (a shape whose embeddings it keeps in HBM, first launch without a tree export)
+      MZS_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->fused_emb), (size_t)c.batch * N * c.embed_dim * sizeof(float)));
+      p.emb_scratch = h->fused_emb;
+      rc = mz::wide_dispatch(mode, c.device, p, stream, A, E, F, &err);
+    }
+    if (rc == MZS_OK) return MZS_OK;
+    if (rc != mz::kNoFusedInstance) return fail(h, rc, "mzs_act_mlp: %s", err.c_str());
   }
   if (h->allow_generic) return act_mlp_generic(h, a, stream_);
   return fail(h, MZS_E_UNSUPPORTED,

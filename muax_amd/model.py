@@ -245,7 +245,8 @@ class MuZero:
         """call() -- a fused act(); when the library has no instance of the kernel for this shape, build one on demand
         (muax_amd/_jit.py: one translation unit, cached on disk, planned for the policy class `gumbel` names) and call
         again; a shape outside the kernel's limits (more than 16 actions, more than 255 simulations, embeddings wider than
-        64) switches `handle` to the library's generic one-launch search (mzs_mlp_allow_generic).  Re-raises the
+        64) switches `handle` to the library's wide-action kernel (17..64 actions, MuZero policy: mzs_mlp_allow_wide,
+        MUAX_AMD_WIDE=0 skips it) or its generic one-launch search (mzs_mlp_allow_generic).  Re-raises the
         ValueError when neither applies: the caller then runs the step-wise path with the torch modules."""
         try:
             return call()
@@ -262,11 +263,17 @@ class MuZero:
                 warnings.warn(f"muax_amd: the on-demand build of a fused act() instance for num_actions={A}, embedding_dim="
                               f"{E}, num_simulations={S} failed; compiler log {_jit.last_build_log}:\n{tail}",
                               RuntimeWarning, stacklevel=3)
-            # outside the fused kernel's limits (or no compiler): the generic one-launch search of the library
-            if os.environ.get("MUAX_AMD_GENERIC", "1") == "0" or handle is None:
+            # outside the fused kernel's limits (or no compiler): the wide-action kernel of the library (17..64 actions,
+            # MuZero policy; tried first) and its generic one-launch search, which takes what the wide kernel declines
+            wide = os.environ.get("MUAX_AMD_WIDE", "1") != "0" and not gumbel
+            generic = os.environ.get("MUAX_AMD_GENERIC", "1") != "0"
+            if handle is None or not (wide or generic):
                 raise
-            handle.allow_generic()
-            return call()
+            if wide:
+                handle.allow_wide()
+            if generic:
+                handle.allow_generic()
+            return call()  # (a ValueError of this call -- both routes declined -- sends the caller to the step-wise path)
 
     def _native_loop(self, root):
         """The one-launch simulation loop, when the nets are ones the library evaluates itself (the reference's ResNet
@@ -404,8 +411,9 @@ class MuZero:
 
     def _warn_stepwise(self, A, E, S, err):
         """Loud, once per shape: the default MLP trio normally runs inside the library (a fused instance, one built on
-        demand, or the generic one-launch search); a shape none of them takes (support_size outside 8..31, more than 64
-        actions, MUAX_AMD_JIT=0 and MUAX_AMD_GENERIC=0) drops to the step-wise kernels + torch modules."""
+        demand, the wide-action kernel for 17..64 actions, or the generic one-launch search); a shape none of them takes
+        (support_size outside 8..31, more than 64 actions, MUAX_AMD_JIT=0 with MUAX_AMD_WIDE=0 and MUAX_AMD_GENERIC=0)
+        drops to the step-wise kernels + torch modules."""
         key = (A, E, self._support_size, S)
         if key not in MuZero._warned_stepwise:
             MuZero._warned_stepwise.add(key)
@@ -413,7 +421,7 @@ class MuZero:
             warnings.warn(f"muax_amd: no in-library act() route for num_actions={A}, embedding_dim={E}, support_size="
                           f"{self._support_size}, num_simulations={S} ({err}); falling back to the step-wise search "
                           f"with torch modules, which is far slower (about 70x a tuned instance at 4096 roots x 50 "
-                          f"simulations; the generic one-launch route is about 16x)"
+                          f"simulations; the generic one-launch route is about 16x, the wide-action kernel for 17..64 actions less)"
                           + (f"; last failed on-demand build: {_jit_tail()}" if _jit_tail() else ""),
                           RuntimeWarning, stacklevel=4)
 

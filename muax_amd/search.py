@@ -85,6 +85,17 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def wide_plan(num_actions: int, embed_dim: int, support_size: int, num_simulations: int):
+    """The wide-action kernel's LDS plan for a shape (mzs_mlp_wide_plan; host arithmetic, no device needed): a dict of
+    `waves` (roots per workgroup), `lds_bytes` (per workgroup), `roots_per_cu` and `emb_lds` (embeddings in LDS), or
+    None when the kernel declines the shape (outside 17..64 actions, support_size outside 8..31, more than 255
+    simulations, or one root's tree beyond a CU's 160 KiB)."""
+    out = (C.c_int32 * 4)()
+    if _lib.load().mzs_mlp_wide_plan(num_actions, embed_dim, support_size, num_simulations, C.byref(out)) != 0:
+        return None
+    return dict(waves=out[0], lds_bytes=out[1], roots_per_cu=out[2], emb_lds=bool(out[3]))
+
+
 class MuZeroSearch:
     """One handle = one (device, batch shard, search configuration).
 
@@ -260,6 +271,13 @@ class MuZeroSearch:
         """Let act_mlp / act_mlp_host serve default-trio shapes without a fused-kernel instance through the library's
         generic one-launch search (mzs_mlp_allow_generic) instead of raising "no fused kernel instance"."""
         _lib.check(self._L.mzs_mlp_allow_generic(self._h, int(bool(allow))), self._h)
+
+    def allow_wide(self, allow: bool = True):
+        """Let act_mlp / act_mlp_host serve 17..64 actions under the MuZero policy through the wide-action one-launch
+        kernel (mzs_mlp_allow_wide: one root per wavefront, one lane per action, tree in LDS).  Tried after the fused
+        instances and before the generic route; a shape it declines (Gumbel policy, a root that does not fit the LDS:
+        `wide_plan`) goes on to the generic route if that is allowed, else raises "no fused kernel instance"."""
+        _lib.check(self._L.mzs_mlp_allow_wide(self._h, int(bool(allow))), self._h)
 
     def act_mlp(self, obs, key, dirichlet_noise=None, dirichlet_fraction: float = 0.25,
                 invalid_actions=None, temperature: float = 1.0, gumbel=None,

@@ -1,6 +1,8 @@
 """Per-act time of the three routes a default-trio act() can take, on one shape: the tuned fused instance, the generic
 one-launch search (MZS_FORCE_GENERIC=1 on a handle with allow_generic), and -- for shapes without an instance -- the
-generic route alone.   python tools/bench_generic.py"""
+generic route alone.   python tools/bench_generic.py
+--wide: 17..64 actions at 4096 roots x 50 simulations, the wide-action kernel (allow_wide) beside the generic route and
+the metric's listed instance, alternated, medians of the alternations."""
 import os
 import sys
 import time
@@ -16,11 +18,13 @@ from muax_amd.utils import warm_runtime  # noqa: E402
 warm_runtime()  # (the runtime's signal pool grown before anything is timed: tools/diag_stall.py)
 
 
-def run(B, obs_dim, E, A, S, force_generic):
+def run(B, obs_dim, E, A, S, force_generic, wide=False):
     w = haiku_style_weights(0, obs_dim, E, A, 21)
     s = MuZeroSearch(B, SearchConfig(A, S, E, tiebreak=True))
     s.set_mlp_weights(w, obs_dim, 10, 0.99)
     s.allow_generic()
+    if wide:
+        s.allow_wide()  # (tried before the generic route)
     if force_generic:
         os.environ["MZS_FORCE_GENERIC"] = "1"
     else:
@@ -62,7 +66,40 @@ def guarded(label, fn):
         return None
 
 
+def wide_table(rounds=5):
+    """Wide-action kernel | generic route | the metric's listed instance, one after the other `rounds` times on one box
+    (each run: 5 settling acts, the median of 20 timed ones); the table gives the medians over the rounds."""
+    from muax_amd.search import wide_plan
+    shapes = ((4096, 4, 8, 18, 50), (4096, 4, 8, 32, 50), (4096, 4, 8, 64, 50), (4096, 8, 32, 18, 50), (1024, 4, 8, 18, 50))
+    t = {k: [] for k in [("ref",)] + [(sh, r) for sh in shapes for r in ("wide", "generic")]}
+    depth = {}
+    for _ in range(rounds):
+        t[("ref",)].append(run(4096, 4, 8, 2, 50, False)[0])
+        for sh in shapes:
+            for route in ("wide", "generic"):
+                r = guarded(f"{sh} {route}", lambda: run(*sh, False, wide=route == "wide"))
+                if r:
+                    t[(sh, route)].append(r[0])
+                    depth[sh] = r[1]
+    med = lambda v: sorted(v)[len(v) // 2] if v else float("nan")  # noqa: E731
+    t_ref = med(t[("ref",)])
+    print(f"reference: 4096 roots, A=2, E=8, S=50, listed instance {t_ref * 1e3:.3f} ms = {t_ref / 50 * 1e6:.2f} us/sim "
+          f"(median of {rounds} alternations; min {min(t[('ref',)]) * 1e3:.3f}, max {max(t[('ref',)]) * 1e3:.3f})")
+    for sh in shapes:
+        B, od, E, A, S = sh
+        pl = wide_plan(A, E, 10, S)
+        tw, tg = med(t[(sh, "wide")]), med(t[(sh, "generic")])
+        per = lambda x: (x / S) / (t_ref / 50) * 4096 / B  # noqa: E731
+        print(f"{B} roots, A={A}, E={E}, S={S} (mean depth {depth.get(sh, float('nan')):.1f}): wide {tw * 1e3:8.3f} ms = "
+              f"{tw / S * 1e6:6.2f} us/sim = x{per(tw):.1f} | generic route {tg * 1e3:8.3f} ms = {tg / S * 1e6:6.2f} us/sim = "
+              f"x{per(tg):.1f} | wide is x{tg / tw:.2f} faster | plan: {pl['waves']} roots/workgroup, {pl['lds_bytes']} B LDS, "
+              f"{pl['roots_per_cu']} roots/CU, embeddings in {'LDS' if pl['emb_lds'] else 'HBM'}")
+
+
 if __name__ == "__main__":
+    if "--wide" in sys.argv:
+        wide_table(int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 5)
+        sys.exit(0)
     if "--round6" in sys.argv:
         # round 6: (a) instances planned per policy (the MuZero policy's four-word children: more roots per workgroup),
         # per simulation against the metric's listed instance; (b) the generic route where B (S + 1)^2 path words used to
