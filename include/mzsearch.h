@@ -465,15 +465,26 @@ int mzs_mlp_allow_generic(mzs_handle *h, int32_t allow);
  * kernel (mz_wide.cuh) -- the whole act() in ONE launch like a fused instance, one root per wavefront, one lane per action,
  * the root's tree in LDS, shapes at run time (embed_dim <= 64, support_size 8..31, num_simulations <= 255).  It is tried
  * after the fused instances and before the generic route, and DECLINES (the call goes on as if it were not allowed: the
- * generic route when that is allowed, else MZS_E_UNSUPPORTED) a Gumbel handle, num_actions <= 16, support_size outside
- * 8..31, num_simulations > 255 and a shape whose single root does not fit a CU's LDS.  Same results bit for bit as the
- * generic route.  Off by default: a handle that never calls this behaves as before. */
+ * generic route when that is allowed, else MZS_E_UNSUPPORTED) a Gumbel handle (see mzs_mlp_allow_wide_gumbel),
+ * num_actions <= 16, support_size outside 8..31, num_simulations > 255 and a shape whose single root does not fit a CU's
+ * LDS.  Same results bit for bit as the generic route.  Off by default: a handle that never calls this behaves as before. */
 int mzs_mlp_allow_wide(mzs_handle *h, int32_t allow);
+/* The same for a handle of the Gumbel policy (both qtransforms, any max_num_considered_actions, root Gumbel noise given or
+ * drawn from the key): allow != 0 lets the wide-action kernel serve its 17..64-action shapes -- sequential halving at the
+ * root, the deterministic interior selection and the completed-Q transform one lane per action.  A separate switch:
+ * mzs_mlp_allow_wide alone leaves a Gumbel handle where it was (generic route or MZS_E_UNSUPPORTED), and this one has no
+ * effect on a handle of the MuZero policy.  The record holds the prior logits as well (5 fields per action), so the plan
+ * is mzs_mlp_wide_plan_policy(..., 1, ...): fewer resident roots, a smaller largest num_simulations. */
+int mzs_mlp_allow_wide_gumbel(mzs_handle *h, int32_t allow);
 /* The wide kernel's LDS plan for a shape (host arithmetic, no device): out = {roots (wavefronts) per workgroup, LDS
  * bytes per workgroup, resident roots per CU, 1 when the embeddings are kept in LDS}; MZS_E_UNSUPPORTED when the kernel
  * declines the shape.  Per root (num_simulations + 1) x (4 + 4 num_actions [+ embed_dim] + 1) words, per workgroup the
  * four nets' weights and num_simulations + 2 words; the workgroup size 1..4 that keeps most roots within 160 KiB. */
 int mzs_mlp_wide_plan(int32_t num_actions, int32_t embed_dim, int32_t support_size, int32_t num_simulations, int32_t out[4]);
+/* ... for a policy: 0 MuZero (what mzs_mlp_wide_plan answers), 1 Gumbel (4 + 5 num_actions words per record);
+ * MZS_E_INVALID for another policy or a null `out`. */
+int mzs_mlp_wide_plan_policy(int32_t num_actions, int32_t embed_dim, int32_t support_size, int32_t num_simulations,
+                             int32_t policy, int32_t out[4]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * The simulation loop of a search with the ResNet nets in ONE launch (mz_search_conv.hip).

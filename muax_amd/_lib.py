@@ -135,7 +135,8 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_register_fused_dispatch", "mzs_register_fused_dispatch_muzero", "mzs_fused_jit_abi", "mzs_mlp_allow_generic", "mzs_conv3x3_nhwc",
                     "mzs_resblock_v1", "mzs_resblock_workspace_bytes", "mzs_conv3x3_stride2_nhwc", "mzs_resnet_root_tail",
                     "mzs_resblock_v2", "mzs_resblock_v2_workspace_bytes", "mzs_register_train_dispatch", "mzs_train_jit_abi",
-                    "mzs_mlp_allow_wide", "mzs_mlp_wide_plan"]
+                    "mzs_mlp_allow_wide", "mzs_mlp_wide_plan",
+                    "mzs_mlp_allow_wide_gumbel", "mzs_mlp_wide_plan_policy"]
 
 _lib = None
 
@@ -176,6 +177,8 @@ def load(build_if_missing: bool = True):
     L.mzs_mlp_allow_generic.argtypes = [_vp, C.c_int32]
     L.mzs_mlp_allow_wide.argtypes = [_vp, C.c_int32]
     L.mzs_mlp_wide_plan.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_int32 * 4)]
+    L.mzs_mlp_allow_wide_gumbel.argtypes = [_vp, C.c_int32]
+    L.mzs_mlp_wide_plan_policy.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_int32 * 4)]
     L.mzs_conv3x3_nhwc.argtypes = [C.POINTER(MzsConv3x3Args), _vp]
     L.mzs_resblock_v1.argtypes = [C.POINTER(MzsResblockArgs), _vp]
     L.mzs_conv3x3_stride2_nhwc.argtypes = [C.POINTER(MzsConv3x3sArgs), _vp]

@@ -97,6 +97,7 @@ struct mzs_handle {
   bool allow_generic = false;      // mzs_mlp_allow_generic: shapes without a fused instance take the generic one-launch search
   float* gen_scratch = nullptr;    // generic route: prior logits [B, A] | embeddings [B, E] | actions [B]
   bool allow_wide = false;         // mzs_mlp_allow_wide: 17..64 actions under the MuZero policy take the wide one-launch kernel
+  bool allow_wide_gumbel = false;  // mzs_mlp_allow_wide_gumbel: ... and under the Gumbel policy (a handle opts in separately)
 };
 
 namespace {
@@ -262,6 +263,12 @@ int mzs_mlp_allow_generic(mzs_handle* h, int32_t allow) {
 int mzs_mlp_allow_wide(mzs_handle* h, int32_t allow) {
   if (!h) return MZS_E_INVALID;
   h->allow_wide = allow != 0;
+  return MZS_OK;
+}
+
+int mzs_mlp_allow_wide_gumbel(mzs_handle* h, int32_t allow) {
+  if (!h) return MZS_E_INVALID;
+  h->allow_wide_gumbel = allow != 0;
   return MZS_OK;
 }
 
@@ -559,13 +566,14 @@ int mzs_act_mlp(mzs_handle* h, const mzs_act_args* a, void* stream_) {
       return MZS_OK;
     }
   }
-  if (h->allow_wide) {  // 17..64 actions, MuZero policy: the lane-per-action kernel with the tree in LDS (mz_wide.cuh)
+  // 17..64 actions: the lane-per-action kernel with the tree in LDS (mz_wide.cuh), each policy by its own opt-in
+  if (mode >= 2 ? h->allow_wide_gumbel : h->allow_wide) {
     std::string err;
-    int rc = mz::wide_dispatch(mode, c.device, p, stream, A, E, F, &err);
+    int rc = mz::wide_dispatch(mode, h->allow_wide_gumbel, c.device, p, stream, A, E, F, &err);
     if (rc == mz::kNeedEmbScratch) {  // (a shape whose embeddings it keeps in HBM, first launch without a tree export)
       MZS_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->fused_emb), (size_t)c.batch * N * c.embed_dim * sizeof(float)));
       p.emb_scratch = h->fused_emb;
-      rc = mz::wide_dispatch(mode, c.device, p, stream, A, E, F, &err);
+      rc = mz::wide_dispatch(mode, h->allow_wide_gumbel, c.device, p, stream, A, E, F, &err);
     }
     if (rc == MZS_OK) return MZS_OK;
     if (rc != mz::kNoFusedInstance) return fail(h, rc, "mzs_act_mlp: %s", err.c_str());

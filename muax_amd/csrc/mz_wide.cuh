@@ -1,4 +1,4 @@
-// mz_wide.cuh -- act() of the default MLP trio (muax/nn.py:59-115) under the MuZero policy for 17..64 actions in ONE launch,
+// mz_wide.cuh -- act() of the default MLP trio (muax/nn.py:59-115) under either policy for 17..64 actions in ONE launch,
 // the root's tree in LDS: root inference, every simulation, the summary and the sampling, like mz_fused.cuh, but mapped
 // for wide action sets.  mz_fused.cuh keeps all scores of a node in one lane (A <= 16); here
 //
@@ -13,8 +13,14 @@
 //     lanes evaluate a hidden layer, two hidden layers (reward | next state, value | policy) side by side; an output
 //     layer has one lane per output (F <= 63 support bins, E <= 64 state elements, A <= 64 prior logits).
 //
-// Shapes (A, E, F, S, obs_dim, max_depth, pred_on_parent) are run-time parameters: one kernel per tie-break mode serves
-// A in 17..64, E <= 64, support_size 8..31 and every S the LDS admits (mz_wide_launch.h, wide_plan).
+// Shapes (A, E, F, S, obs_dim, max_depth, pred_on_parent) are run-time parameters: one kernel per mode of the fused
+// dispatchers (0 / 1: MuZero policy without / with tie-break noise, 2 / 3: Gumbel MuZero with
+// qtransform_by_parent_and_siblings / qtransform_completed_by_mix_value) serves A in 17..64, E <= 64, support_size 8..31
+// and every S the LDS admits (mz_wide_launch.h, wide_plan).  The Gumbel modes share the nets, the expansion and the
+// backup; their decisions (mctx gumbel_muzero_{root,interior}_action_selection, seq_halving) are lane-parallel as well:
+// the completed Q of a level is computed by all lanes at once, the root Gumbel noise of action a lives in lane a's
+// register for the whole act, and any max_num_considered_actions up to A is served (the top-k of sequential halving is
+// the visit-count test of score_considered: nothing is sorted).
 //
 // Arithmetic: MZ-F32 as the oracle states it (oracle/mz_oracle.c): a linear layer is a k-ordered fma chain
 // from 0 with the bias added last, ELU / exp / log / inv_scaling from mz_spec.cuh, every float sum over actions or
@@ -49,6 +55,8 @@ MZ_DEV int wave_sum_i(int x) {
   x = row_sum_i(x);
   return (w_rdl_i(x, 0) + w_rdl_i(x, 16)) + (w_rdl_i(x, 32) + w_rdl_i(x, 48));
 }
+// maximum of small non-negative integers (visit counts: exact as floats)
+MZ_DEV int wave_max_count(int x) { return (int)wave_max((float)x); }
 // first lane that holds the maximum (mctx argmax: first of equals); every lane past the action count holds -inf
 MZ_DEV int wave_first_max(float sc) {
   const float m = wave_max(sc);
@@ -116,8 +124,42 @@ struct WideNets {
   const float *dr_w1, *dr_b1, *dr_w2, *dr_b2, *dn_w1, *dn_b1, *dn_w2, *dn_b2;
 };
 
-template <bool TIEBREAK>
+// mctx qtransforms on the wide mapping (oracle/mz_oracle.c mzo_qtransform), this lane's child: QT 0
+// qtransform_by_parent_and_siblings, QT 1 qtransform_completed_by_mix_value(value_scale 0.1, maxvisit_init 50).
+// prob = softmax(prior logits) of the node; cvis = the child's visits (0 in lanes past A), sum_visits their sum (QT 1)
+template <int QT>
+MZ_DEV float wide_qtransform(bool ok, bool seen, float q, float nval, float raw, float prob, int cvis, int sum_visits, int A,
+                             int lane) {
+  if constexpr (QT == 0) {
+    const float safe = seen ? q : nval;
+    const float lo = fminf(nval, wave_min(safe)), hi = fmaxf(nval, wave_max(safe));
+    const float span = fmaxf(hi - lo, 1e-8f);
+    return ((seen ? q : lo) - lo) / span;
+  } else {
+    const float prior = fmaxf(prob, kFltTiny);
+    const float sum_probs = wave_sum16(seen ? prior : 0.0f, A, lane);
+    const float weighted_q = wave_sum16(seen ? (prior * q) / sum_probs : 0.0f, A, lane);
+    const float mixed = (raw + (float)sum_visits * weighted_q) / (float)(sum_visits + 1);
+    const float out = seen ? q : mixed;
+    const float lo = wave_min(ok ? out : INFINITY), hi = wave_max(ok ? out : -INFINITY);
+    const float span = fmaxf(hi - lo, 1e-8f);
+    const float scale = (50.0f + (float)wave_max_count(cvis)) * 0.1f;
+    return scale * ((out - lo) / span);
+  }
+}
+// seq_halving.score_considered + the root's invalid-action mask (oracle gumbel_argmax), this lane's action
+MZ_DEV float wide_score_considered(bool ok, bool inv, float gum, float logit, float qv, int cvis, int considered_visit) {
+  const float mx = wave_max(ok ? logit : -INFINITY);
+  float sc = fmaxf((gum + (logit - mx)) + qv, -1e9f);
+  sc = sc + (cvis == considered_visit ? 0.0f : -INFINITY);
+  return (!ok || inv) ? -INFINITY : sc;
+}
+
+template <int MODE>
 __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_act_wide_kernel(const FusedParams p, const WideShape sh) {
+  static_assert(MODE >= 0 && MODE <= 3, "mode of the fused dispatchers");
+  constexpr bool TIEBREAK = MODE == 1, GUMBEL = MODE >= 2;
+  constexpr int QT = MODE == 3 ? 1 : 0;
   extern __shared__ int wide_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int A = sh.A, E = sh.E, F = sh.F, H = kHidden, X = E + A;
@@ -156,7 +198,7 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_act_wide_kernel(const F
 
   // ---- this root's block: records [N][REC] | path [N] | embeddings [N][E] (or in HBM) ----
   // record: visits, value, raw value, (parent + 1) | (action + 1) << 16, then per action: (child + 1) | visits << 16,
-  // prior probability, child value, reward -- all zero is mctx's empty tree
+  // prior probability, child value, reward[, prior logit (Gumbel modes)] -- all zero is mctx's empty tree
   int* tree = wide_lds + sh.wg_words + wave * sh.root_words;
   int* path = tree + N * REC;
   {
@@ -176,7 +218,13 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_act_wide_kernel(const F
     value = wave_decode(vl, F, p.support, lane);
   };
 
-  // ---- root inference (muax/model.py:251-263) and the muzero_policy prelude (Dirichlet mix, mask) ----
+  // Gumbel modes: this lane's root Gumbel noise, the number of root actions sequential halving considers, and whether
+  // the root's mask has an invalid action (mctx masks the completed logits only then)
+  [[maybe_unused]] float gum = 0.0f;
+  [[maybe_unused]] int ncons = 0;
+  [[maybe_unused]] bool any_inv = false;
+
+  // ---- root inference (muax/model.py:251-263) and the policy's prelude (MuZero: Dirichlet mix, mask; Gumbel: mask) ----
   {
     const float* ob = p.obs + (size_t)r * p.obs_dim;
     float acc = 0.0f;
@@ -200,17 +248,41 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_act_wide_kernel(const F
     if (lane < E) emb[lane] = s;
     float logit, value;
     prediction(s, logit, value);
-    const float pr = wave_softmax(logit, A, lane);
-    const float nz = (p.dirichlet_noise != nullptr && ok) ? p.dirichlet_noise[(size_t)r * A + ac] : 0.0f;
-    const float noisy = (1.0f - p.dirichlet_fraction) * pr + p.dirichlet_fraction * nz;
-    float lg = log_pos(fmaxf(noisy, kFltTiny));
-    if (p.invalid != nullptr) {
-      const float top = wave_max(ok ? lg : -INFINITY);
-      lg = inv ? kFltLowest : lg - top;
+    float lg;
+    if constexpr (!GUMBEL) {
+      const float pr = wave_softmax(logit, A, lane);
+      const float nz = (p.dirichlet_noise != nullptr && ok) ? p.dirichlet_noise[(size_t)r * A + ac] : 0.0f;
+      const float noisy = (1.0f - p.dirichlet_fraction) * pr + p.dirichlet_fraction * nz;
+      lg = log_pos(fmaxf(noisy, kFltTiny));
+      if (p.invalid != nullptr) {
+        const float top = wave_max(ok ? lg : -INFINITY);
+        lg = inv ? kFltLowest : lg - top;
+      }
+    } else {
+      // mctx gumbel_muzero_policy prelude: the logits only pass through _mask_invalid_actions; root Gumbel noise
+      lg = logit;
+      const unsigned long long inv_lanes = __builtin_amdgcn_ballot_w64(inv);
+      any_inv = inv_lanes != 0;
+      if (any_inv) {
+        const float top = wave_max(ok ? lg : -INFINITY);
+        lg = inv ? kFltLowest : lg - top;
+      }
+      ncons = min(p.max_considered, A - (int)__builtin_popcountll(inv_lanes));
+      if (p.gumbel != nullptr) {
+        gum = ok ? p.gumbel[(size_t)r * A + ac] : 0.0f;
+      } else {
+        uint32_t x0, x1;
+        bool second;
+        bits_block(p.global_batch * (uint64_t)A, rg * (uint64_t)A + (uint64_t)ac, x0, x1, second);
+        threefry2x32(p.k_gumbel[0], p.k_gumbel[1], x0, x1);
+        gum = p.gumbel_scale * gumbel_from_bits(second ? x1 : x0);
+      }
     }
-    const float prob = wave_softmax(lg, A, lane);
+    float prob = 0.0f;  // (qtransform_by_parent_and_siblings under the Gumbel policy never reads a prior probability)
+    if constexpr (MODE != 2) prob = wave_softmax(lg, A, lane);
     if (ok) {
       tree[4 + A + ac] = __float_as_int(prob);
+      if constexpr (GUMBEL) tree[4 + 4 * A + ac] = __float_as_int(lg);
       if (ex) p.t_children_prior_logits[tn0 * A + ac] = lg;
     }
     if (lane == 0) {
@@ -240,13 +312,28 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_act_wide_kernel(const F
       const int cvis = iv >> 16, cidx = (iv & 0xffff) - 1;
       const bool seen = ok && cvis > 0;
       const float q = crew + disc * cval;
-      const float safe = seen ? q : nval;
-      const float lo = fminf(nval, wave_min(safe)), hi = fmaxf(nval, wave_max(safe));
-      const float span = fmaxf(hi - lo, 1e-8f);
-      const float value_score = ((seen ? q : lo) - lo) / span;
-      const float policy_score = (tbl[nvis] * prob) / (float)(cvis + 1);
-      float sc = value_score + policy_score;
-      if (!ok || (depth == 0 && inv)) sc = -INFINITY;
+      float sc;
+      if constexpr (!GUMBEL) {
+        const float safe = seen ? q : nval;
+        const float lo = fminf(nval, wave_min(safe)), hi = fmaxf(nval, wave_max(safe));
+        const float span = fmaxf(hi - lo, 1e-8f);
+        const float value_score = ((seen ? q : lo) - lo) / span;
+        const float policy_score = (tbl[nvis] * prob) / (float)(cvis + 1);
+        sc = value_score + policy_score;
+        if (!ok || (depth == 0 && inv)) sc = -INFINITY;
+      } else {
+        // mctx gumbel_muzero_root_action_selection / gumbel_muzero_interior_action_selection (no tie-break noise)
+        const float lgt = __int_as_float(rec[4 + 4 * A + ac]);
+        const int vis = ok ? cvis : 0;
+        const int sumv = (QT == 1 || depth != 0) ? wave_sum_i(vis) : 0;
+        const float qv = wide_qtransform<QT>(ok, seen, q, nval, __int_as_float(rec[2]), prob, vis, sumv, A, lane);
+        if (depth == 0) {
+          sc = wide_score_considered(ok, inv, gum, lgt, qv, vis, p.visit_table[(size_t)ncons * S + sim]);
+        } else {
+          const float pr = wave_softmax(lgt + qv, A, lane);
+          sc = ok ? pr - (float)vis / (float)(1 + sumv) : -INFINITY;
+        }
+      }
       float top = wave_max(sc);
       unsigned long long at = __builtin_amdgcn_ballot_w64(sc == top);
       int best = at ? __builtin_ctzll(at) : 0;
@@ -315,13 +402,15 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_act_wide_kernel(const F
       reward = wave_decode(rl, F, p.support, lane);
       prediction(p.pred_on_parent ? s_par : ns, logit, value);
     }
-    const float prob = wave_softmax(logit, A, lane);
+    float prob = 0.0f;
+    if constexpr (MODE != 2) prob = wave_softmax(logit, A, lane);
 
     // expand (update_tree_node + the edge); a node met again at max_depth keeps its children
     {
       int* nrec = tree + newn * REC;
       if (ok) {
         nrec[4 + A + ac] = __float_as_int(prob);
+        if constexpr (GUMBEL) nrec[4 + 4 * A + ac] = __float_as_int(logit);
         if (ex) p.t_children_prior_logits[(tn0 + newn) * A + ac] = logit;
       }
       if (lane == 0) {
@@ -369,8 +458,28 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_act_wide_kernel(const F
     }
   }
 
-  // ---- mctx Tree.summary + _apply_temperature + jax.random.categorical ----
-  {
+  if constexpr (GUMBEL) {
+    // ---- tail of mctx gumbel_muzero_policy (oracle mzo_gumbel_finish): the best of the most visited actions by
+    // gumbel + logits + completed Q, action_weights = softmax(logits + completed Q) under the root's mask ----
+    const int vis = ok ? (tree[4 + ac] >> 16) : 0;
+    const float q = __int_as_float(tree[4 + 3 * A + ac]) + disc * __int_as_float(tree[4 + 2 * A + ac]);
+    const float lgt = __int_as_float(tree[4 + 4 * A + ac]);
+    const float nval = __int_as_float(tree[1]);
+    const float qv = wide_qtransform<QT>(ok, vis > 0, q, nval, __int_as_float(tree[2]), __int_as_float(tree[4 + A + ac]), vis,
+                                         wave_sum_i(vis), A, lane);
+    const int best = wave_first_max(wide_score_considered(ok, inv, gum, lgt, qv, vis, wave_max_count(vis)));
+    float x = lgt + qv;
+    const float mx = wave_max(ok ? x : -INFINITY);
+    if (any_inv) x = inv ? kFltLowest : x - mx;
+    const float w = wave_softmax(x, A, lane);
+    if (ok) p.action_weights[(size_t)r * A + ac] = w;
+    if (lane == 0) {
+      p.action[r] = best;
+      if (p.search_value) p.search_value[r] = nval;
+      if (p.depth_sum) p.depth_sum[r] = depth_sum;
+    }
+  } else {
+    // ---- mctx Tree.summary + _apply_temperature + jax.random.categorical ----
     const int vc = ok ? (tree[4 + ac] >> 16) : 0;
     const float total = (float)wave_sum_i(vc);
     const float denom = fmaxf(total, 1.0f);

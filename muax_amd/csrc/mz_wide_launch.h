@@ -11,8 +11,8 @@ constexpr int kWideMaxWaves = 4;           // roots (= wavefronts) per workgroup
 
 // LDS budget of the wide kernel, in 4-byte words (all blocks rounded to 16 bytes):
 //   workgroup: the four nets' weights (the representation's stay in HBM: read once per root) + the pUCT table [S + 2]
-//   root:      (S + 1) records of 4 header words + 4 child fields x A, the path [S + 1], and -- when it costs no
-//              resident root -- the embeddings [S + 1][E]
+//   root:      (S + 1) records of 4 header words + 4 child fields x A (5 under the Gumbel policy: the prior logits as
+//              well), the path [S + 1], and -- when it costs no resident root -- the embeddings [S + 1][E]
 struct WidePlan {
   int waves, emb_lds, rec_words, root_words, wg_words, weight_words, roots_per_cu;
   int lds_bytes;
@@ -23,10 +23,11 @@ inline int wide_weight_words(int A, int E, int F) {
   return (E * H + H + H * F + F) + (E * H + H + H * A + A) + (X * H + H + H * F + F) + (X * H + H + H * E + E);
 }
 // false: the wide kernel declines the shape (also when one root does not fit a CU's LDS)
-inline bool wide_plan(int A, int E, int F, int S, WidePlan* out) {
+// gumbel: the plan of the Gumbel MuZero modes (the larger record: fewer resident roots, a smaller largest S)
+inline bool wide_plan(int A, int E, int F, int S, bool gumbel, WidePlan* out) {
   if (A < 17 || A > 64 || E < 1 || E > 64 || F < 17 || F > 63 || S < 1 || S > 255) return false;
   WidePlan best{};
-  const int N = S + 1, rec = 4 + 4 * A;
+  const int N = S + 1, rec = 4 + (gumbel ? 5 : 4) * A;
   const int wgt = wide_round4(wide_weight_words(A, E, F)), wg = wgt + wide_round4(S + 2);
   for (int emb = 1; emb >= 0; --emb)
     for (int w = 1; w <= kWideMaxWaves; ++w) {
@@ -42,9 +43,11 @@ inline bool wide_plan(int A, int E, int F, int S, WidePlan* out) {
   return true;
 }
 
-// MuZero policy only (mode 0 / 1 of the fused dispatchers).  MZS_OK after the launch, kNoFusedInstance when the kernel
-// declines the shape or the policy, kNeedEmbScratch when it keeps this shape's embeddings in HBM and neither a tree
-// export nor p.emb_scratch is there, or a negative MZS_E_* with *err set.
-int wide_dispatch(int mode, int device, const FusedParams& p, hipStream_t stream, int A, int E, int F, std::string* err);
+// mode: that of the fused dispatchers (0 / 1 MuZero policy, 2 / 3 Gumbel policy); the Gumbel modes are served only with
+// `gumbel_ok` (mzs_mlp_allow_wide_gumbel).  MZS_OK after the launch, kNoFusedInstance when the kernel declines the
+// shape or the policy, kNeedEmbScratch when it keeps this shape's embeddings in HBM and neither a tree export nor
+// p.emb_scratch is there, or a negative MZS_E_* with *err set.
+int wide_dispatch(int mode, bool gumbel_ok, int device, const FusedParams& p, hipStream_t stream, int A, int E, int F,
+                  std::string* err);
 
 }  // namespace mz

@@ -245,8 +245,9 @@ class MuZero:
         """call() -- a fused act(); when the library has no instance of the kernel for this shape, build one on demand
         (muax_amd/_jit.py: one translation unit, cached on disk, planned for the policy class `gumbel` names) and call
         again; a shape outside the kernel's limits (more than 16 actions, more than 255 simulations, embeddings wider than
-        64) switches `handle` to the library's wide-action kernel (17..64 actions, MuZero policy: mzs_mlp_allow_wide,
-        MUAX_AMD_WIDE=0 skips it) or its generic one-launch search (mzs_mlp_allow_generic).  Re-raises the
+        64) switches `handle` to the library's wide-action kernel (17..64 actions: mzs_mlp_allow_wide for the MuZero
+        policy, mzs_mlp_allow_wide_gumbel for the Gumbel policy; MUAX_AMD_WIDE=0 skips both) or its generic one-launch
+        search (mzs_mlp_allow_generic).  Re-raises the
         ValueError when neither applies: the caller then runs the step-wise path with the torch modules."""
         try:
             return call()
@@ -264,13 +265,13 @@ class MuZero:
                               f"{E}, num_simulations={S} failed; compiler log {_jit.last_build_log}:\n{tail}",
                               RuntimeWarning, stacklevel=3)
             # outside the fused kernel's limits (or no compiler): the wide-action kernel of the library (17..64 actions,
-            # MuZero policy; tried first) and its generic one-launch search, which takes what the wide kernel declines
-            wide = os.environ.get("MUAX_AMD_WIDE", "1") != "0" and not gumbel
+            # either policy; tried first) and its generic one-launch search, which takes what the wide kernel declines
+            wide = os.environ.get("MUAX_AMD_WIDE", "1") != "0"
             generic = os.environ.get("MUAX_AMD_GENERIC", "1") != "0"
             if handle is None or not (wide or generic):
                 raise
             if wide:
-                handle.allow_wide()
+                handle.allow_wide(gumbel=gumbel)
             if generic:
                 handle.allow_generic()
             return call()  # (a ValueError of this call -- both routes declined -- sends the caller to the step-wise path)
@@ -421,7 +422,8 @@ class MuZero:
             warnings.warn(f"muax_amd: no in-library act() route for num_actions={A}, embedding_dim={E}, support_size="
                           f"{self._support_size}, num_simulations={S} ({err}); falling back to the step-wise search "
                           f"with torch modules, which is far slower (about 70x a tuned instance at 4096 roots x 50 "
-                          f"simulations; the generic one-launch route is about 16x, the wide-action kernel for 17..64 actions less)"
+                          f"simulations; the generic one-launch route is about 16x, the wide-action kernel for 17..64 actions, "
+                          f"MuZero or Gumbel policy, less)"
                           + (f"; last failed on-demand build: {_jit_tail()}" if _jit_tail() else ""),
                           RuntimeWarning, stacklevel=4)
 

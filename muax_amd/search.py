@@ -85,13 +85,18 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def wide_plan(num_actions: int, embed_dim: int, support_size: int, num_simulations: int):
-    """The wide-action kernel's LDS plan for a shape (mzs_mlp_wide_plan; host arithmetic, no device needed): a dict of
-    `waves` (roots per workgroup), `lds_bytes` (per workgroup), `roots_per_cu` and `emb_lds` (embeddings in LDS), or
-    None when the kernel declines the shape (outside 17..64 actions, support_size outside 8..31, more than 255
-    simulations, or one root's tree beyond a CU's 160 KiB)."""
+def wide_plan(num_actions: int, embed_dim: int, support_size: int, num_simulations: int, policy: str = "muzero"):
+    """The wide-action kernel's LDS plan for a shape (mzs_mlp_wide_plan_policy; host arithmetic, no device needed): a
+    dict of `waves` (roots per workgroup), `lds_bytes` (per workgroup), `roots_per_cu` and `emb_lds` (embeddings in LDS),
+    or None when the kernel declines the shape (outside 17..64 actions, support_size outside 8..31, more than 255
+    simulations, or one root's tree beyond a CU's 160 KiB).  `policy` "gumbel": the plan of the Gumbel modes, whose
+    record holds a fifth field per action (the prior logits)."""
+    try:
+        pol = {"muzero": 0, "gumbel": 1}[policy]
+    except KeyError:
+        raise ValueError(f"unknown policy: {policy!r}") from None
     out = (C.c_int32 * 4)()
-    if _lib.load().mzs_mlp_wide_plan(num_actions, embed_dim, support_size, num_simulations, C.byref(out)) != 0:
+    if _lib.load().mzs_mlp_wide_plan_policy(num_actions, embed_dim, support_size, num_simulations, pol, C.byref(out)) != 0:
         return None
     return dict(waves=out[0], lds_bytes=out[1], roots_per_cu=out[2], emb_lds=bool(out[3]))
 
@@ -272,12 +277,15 @@ class MuZeroSearch:
         generic one-launch search (mzs_mlp_allow_generic) instead of raising "no fused kernel instance"."""
         _lib.check(self._L.mzs_mlp_allow_generic(self._h, int(bool(allow))), self._h)
 
-    def allow_wide(self, allow: bool = True):
+    def allow_wide(self, allow: bool = True, gumbel: bool = False):
         """Let act_mlp / act_mlp_host serve 17..64 actions under the MuZero policy through the wide-action one-launch
         kernel (mzs_mlp_allow_wide: one root per wavefront, one lane per action, tree in LDS).  Tried after the fused
         instances and before the generic route; a shape it declines (Gumbel policy, a root that does not fit the LDS:
-        `wide_plan`) goes on to the generic route if that is allowed, else raises "no fused kernel instance"."""
-        _lib.check(self._L.mzs_mlp_allow_wide(self._h, int(bool(allow))), self._h)
+        `wide_plan`) goes on to the generic route if that is allowed, else raises "no fused kernel instance".
+        `gumbel=True` sets the switch of the Gumbel policy instead (mzs_mlp_allow_wide_gumbel; the two are separate: a
+        Gumbel handle is served by the wide kernel only after allow_wide(gumbel=True), plan `wide_plan(..., policy="gumbel")`)."""
+        fn = self._L.mzs_mlp_allow_wide_gumbel if gumbel else self._L.mzs_mlp_allow_wide
+        _lib.check(fn(self._h, int(bool(allow))), self._h)
 
     def act_mlp(self, obs, key, dirichlet_noise=None, dirichlet_fraction: float = 0.25,
                 invalid_actions=None, temperature: float = 1.0, gumbel=None,

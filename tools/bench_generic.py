@@ -1,8 +1,9 @@
 """Per-act time of the three routes a default-trio act() can take, on one shape: the tuned fused instance, the generic
 one-launch search (MZS_FORCE_GENERIC=1 on a handle with allow_generic), and -- for shapes without an instance -- the
 generic route alone.   python tools/bench_generic.py
---wide: 17..64 actions at 4096 roots x 50 simulations, the wide-action kernel (allow_wide) beside the generic route and
-the metric's listed instance, alternated, medians of the alternations."""
+--wide: 17..64 actions at 4096 roots x 50 simulations under the MuZero and the Gumbel policy, the wide-action kernel (its
+opt-in ONLY) beside the generic route (allow_generic ONLY) and the metric's listed instance, alternated, medians and spread
+of the alternations; --wide-one POLICY: one run of the A = 18 wide launch (25 acts), the target of a rocprofv3 trace."""
 import os
 import sys
 import time
@@ -18,19 +19,24 @@ from muax_amd.utils import warm_runtime  # noqa: E402
 warm_runtime()  # (the runtime's signal pool grown before anything is timed: tools/diag_stall.py)
 
 
-def run(B, obs_dim, E, A, S, force_generic, wide=False):
+def run(B, obs_dim, E, A, S, force_generic, wide=False, gumbel=False):
+    """wide: the wide-action kernel's opt-in of the policy and NOT the generic route (a decline raises, nothing is timed on
+    another route by accident); gumbel: the Gumbel policy with mctx's defaults (completed_by_mix_value, 16 considered)."""
     w = haiku_style_weights(0, obs_dim, E, A, 21)
-    s = MuZeroSearch(B, SearchConfig(A, S, E, tiebreak=True))
+    cfg = SearchConfig(A, S, E, tiebreak=False, policy="gumbel", qtransform="qtransform_completed_by_mix_value",
+                       max_num_considered_actions=16) if gumbel else SearchConfig(A, S, E, tiebreak=True)
+    s = MuZeroSearch(B, cfg)
     s.set_mlp_weights(w, obs_dim, 10, 0.99)
-    s.allow_generic()
     if wide:
-        s.allow_wide()  # (tried before the generic route)
+        s.allow_wide(gumbel=gumbel)
+    else:
+        s.allow_generic()
     if force_generic:
         os.environ["MZS_FORCE_GENERIC"] = "1"
     else:
         os.environ.pop("MZS_FORCE_GENERIC", None)
     obs = (torch.rand(B, obs_dim) * 2 - 1).cuda()
-    noise = torch.distributions.Dirichlet(torch.full((A,), 0.3)).sample((B,)).cuda()
+    noise = None if gumbel else torch.distributions.Dirichlet(torch.full((A,), 0.3)).sample((B,)).cuda()
     for i in range(5):
         s.act_mlp(obs, (0, i), dirichlet_noise=noise)
     torch.cuda.synchronize()
@@ -67,36 +73,46 @@ def guarded(label, fn):
 
 
 def wide_table(rounds=5):
-    """Wide-action kernel | generic route | the metric's listed instance, one after the other `rounds` times on one box
-    (each run: 5 settling acts, the median of 20 timed ones); the table gives the medians over the rounds."""
+    """Wide-action kernel | generic route | the metric's listed instance, under both policies, one after the other `rounds`
+    times on one box (each run: 5 settling acts, the median of 20 timed ones); the table gives the medians over the rounds
+    and their spread (min .. max)."""
     from muax_amd.search import wide_plan
-    shapes = ((4096, 4, 8, 18, 50), (4096, 4, 8, 32, 50), (4096, 4, 8, 64, 50), (4096, 8, 32, 18, 50), (1024, 4, 8, 18, 50))
+    shapes = tuple(sh + (pol,) for pol in ("muzero", "gumbel")
+                   for sh in ((4096, 4, 8, 18, 50), (4096, 4, 8, 32, 50), (4096, 4, 8, 64, 50), (4096, 8, 32, 18, 50)))
     t = {k: [] for k in [("ref",)] + [(sh, r) for sh in shapes for r in ("wide", "generic")]}
     depth = {}
     for _ in range(rounds):
         t[("ref",)].append(run(4096, 4, 8, 2, 50, False)[0])
         for sh in shapes:
             for route in ("wide", "generic"):
-                r = guarded(f"{sh} {route}", lambda: run(*sh, False, wide=route == "wide"))
+                r = guarded(f"{sh} {route}", lambda: run(*sh[:5], False, wide=route == "wide", gumbel=sh[5] == "gumbel"))
                 if r:
                     t[(sh, route)].append(r[0])
                     depth[sh] = r[1]
     med = lambda v: sorted(v)[len(v) // 2] if v else float("nan")  # noqa: E731
+    rng = lambda v: f"{min(v) * 1e3:.3f} .. {max(v) * 1e3:.3f}" if v else "-"  # noqa: E731
     t_ref = med(t[("ref",)])
     print(f"reference: 4096 roots, A=2, E=8, S=50, listed instance {t_ref * 1e3:.3f} ms = {t_ref / 50 * 1e6:.2f} us/sim "
           f"(median of {rounds} alternations; min {min(t[('ref',)]) * 1e3:.3f}, max {max(t[('ref',)]) * 1e3:.3f})")
     for sh in shapes:
-        B, od, E, A, S = sh
-        pl = wide_plan(A, E, 10, S)
+        B, od, E, A, S, pol = sh
+        pl = wide_plan(A, E, 10, S, policy=pol)
         tw, tg = med(t[(sh, "wide")]), med(t[(sh, "generic")])
         per = lambda x: (x / S) / (t_ref / 50) * 4096 / B  # noqa: E731
-        print(f"{B} roots, A={A}, E={E}, S={S} (mean depth {depth.get(sh, float('nan')):.1f}): wide {tw * 1e3:8.3f} ms = "
-              f"{tw / S * 1e6:6.2f} us/sim = x{per(tw):.1f} | generic route {tg * 1e3:8.3f} ms = {tg / S * 1e6:6.2f} us/sim = "
-              f"x{per(tg):.1f} | wide is x{tg / tw:.2f} faster | plan: {pl['waves']} roots/workgroup, {pl['lds_bytes']} B LDS, "
-              f"{pl['roots_per_cu']} roots/CU, embeddings in {'LDS' if pl['emb_lds'] else 'HBM'}")
+        plan = (f"{pl['waves']} roots/workgroup, {pl['lds_bytes']} B LDS, {pl['roots_per_cu']} roots/CU, embeddings in "
+                f"{'LDS' if pl['emb_lds'] else 'HBM'}") if pl else "declined"
+        print(f"{pol:6s} {B} roots, A={A}, E={E}, S={S} (mean depth {depth.get(sh, float('nan')):.1f}): wide {tw * 1e3:8.3f} ms "
+              f"({rng(t[(sh, 'wide')])}) = {tw / S * 1e6:6.2f} us/sim = x{per(tw):.1f} | generic route {tg * 1e3:8.3f} ms "
+              f"({rng(t[(sh, 'generic')])}) = {tg / S * 1e6:6.2f} us/sim = x{per(tg):.1f} | wide is x{tg / tw:.2f} faster | "
+              f"plan: {plan}", flush=True)
 
 
 if __name__ == "__main__":
+    if "--wide-one" in sys.argv:  # one wide-route run of 4096 x (A = 18, E = 8) x 50, for a profiler: --wide-one muzero|gumbel
+        pol = sys.argv[sys.argv.index("--wide-one") + 1]
+        dt, d = run(4096, 4, 8, 18, 50, False, wide=True, gumbel=pol == "gumbel")
+        print(f"{pol} 4096 roots, A=18, E=8, S=50 (mean depth {d:.1f}): wide {dt * 1e3:.3f} ms per act")
+        sys.exit(0)
     if "--wide" in sys.argv:
         wide_table(int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 5)
         sys.exit(0)
