@@ -265,7 +265,11 @@ int mzs_dirichlet(int32_t device, const uint32_t key[2], float alpha, int32_t ba
  * gradient of every one of the 18 weight arrays, concatenated in the member order of mzs_mlp_weights
  * (repr_w, repr_b, pv_w1, ... dn_b2), each in its own haiku layout.  One fused forward+backward kernel
  * and a fixed-order reduction: bit-reproducible run to run.  The optimiser (muax/optimizers.py) and the
- * optional data-parallel gradient mean (one flat all-reduce over `grads`) stay with the caller. */
+ * optional data-parallel gradient mean (one flat all-reduce over `grads`) stay with the caller.
+ * Limits: obs_dim 1..128 (MZS_E_UNSUPPORTED above, the limit named); the (num_actions, embed_dim, 2 support_size + 1)
+ * triple must have a kernel instance, a listed one (num_actions <= 16) or one registered through
+ * mzs_register_train_dispatch (num_actions <= 64), else MZS_E_UNSUPPORTED "no kernel instance for this (A, E, F)";
+ * unroll_steps beyond what the instance's LDS keeps is refused on the host, before any launch, the limit named. */
 typedef struct mzs_train_args {
   int32_t struct_size;      /* = sizeof(mzs_train_args) */
   int32_t device;
@@ -451,7 +455,10 @@ int mzs_fused_jit_abi(void);
  * the missing triple gives a side library whose `mzs_jit_train_launch` is passed here together with its
  * `mzs_jit_train_shape` values and the value of its `mzs_jit_train_abi` (must equal mzs_train_jit_abi(): same argument
  * layout); later
- * mzs_mlp_loss_grad calls of that triple take it. */
+ * mzs_mlp_loss_grad calls of that triple take it.  The kernel's own limits bound what can be built: embed_dim 1..64,
+ * 2 support_size + 1 in 17..63, num_actions 1..16, or 17..64 when the translation unit is compiled with
+ * -DMZ_TRAIN_WIDE=1 (policy head over ceil(num_actions / 16) lane slots; muax_amd/_jit.py::ensure_wide_train_instance).
+ * Wide shapes exist as on-demand instances only: the library lists none. */
 int mzs_register_train_dispatch(void *launch, int32_t num_actions, int32_t embed_dim, int32_t full_support_size, int32_t jit_abi);
 int mzs_train_jit_abi(void);
 /* Shapes the fused kernel cannot be instantiated for at all (more than 16 actions, more than 255 simulations, embeddings

@@ -217,18 +217,12 @@ def _train_hash() -> str:
     return h.hexdigest()[:12]
 
 
-def ensure_train_instance(A: int, E: int, F: int, verbose: bool = False) -> bool:
-    """Make sure mzs_mlp_loss_grad can serve (num_actions, embedding_dim, F = 2 support_size + 1): True when an on-demand
-    instance of the fused training-step kernel (muax_amd/csrc/mz_train_jit.hip) is registered -- built now (one
-    translation unit, cached as muax_amd/lib/jit/mztrain_<shape>-<source hash>.so) or earlier --, False when the shape is
-    outside the kernel's limits (more than 16 actions, embeddings wider than 64, F outside 17..63), there is no compiler,
-    the build fails, or MUAX_AMD_JIT=0.  Round 5: a model whose act() runs on an on-demand instance keeps the fused
-    update() too (the reference's update() takes any widths, muax/model.py:181-201)."""
-    if os.environ.get("MUAX_AMD_JIT", "1") == "0":
-        return False
-    if not (1 <= A <= 16 and 1 <= E <= 64 and 17 <= F <= 63):
-        return False
-    shape = ("train", A, E, F)
+def _ensure_train(kind: str, prefix: str, defines, A: int, E: int, F: int, verbose: bool) -> bool:
+    """Build (once: cached as muax_amd/lib/jit/<prefix>_<shape>-<source hash>.so), load and register one instance of the
+    fused training-step kernel, muax_amd/csrc/mz_train_jit.hip compiled with `defines` on top of the shape's; the
+    caller has checked the shape against its limits.  False when there is no compiler, no writable cache directory, or
+    the build fails (compiler output in the .log beside the file, see build_log_tail())."""
+    shape = (kind, A, E, F)  # key in _loaded / _failed: ("train", ...) narrow, ("train_wide", ...) wide
     if shape in _loaded:
         return True
     if shape in _failed:
@@ -237,7 +231,7 @@ def ensure_train_instance(A: int, E: int, F: int, verbose: bool = False) -> bool
         cc = _build.hipcc()
     except RuntimeError:
         return False
-    so = os.path.join(JIT_DIR, f"mztrain_a{A}_e{E}_f{F}-{_train_hash()}.so")
+    so = os.path.join(JIT_DIR, f"{prefix}_a{A}_e{E}_f{F}-{_train_hash()}.so")
     try:
         os.makedirs(JIT_DIR, exist_ok=True)
         if not os.path.exists(so):
@@ -246,8 +240,8 @@ def ensure_train_instance(A: int, E: int, F: int, verbose: bool = False) -> bool
                 fcntl.flock(lock, fcntl.LOCK_EX)  # ranks that miss the same shape build it once
                 if not os.path.exists(so):
                     tmp = so + f".tmp{os.getpid()}"
-                    cmd = [cc] + _build.FLAGS + [f"-DMZ_TRAIN_A={A}", f"-DMZ_TRAIN_E={E}", f"-DMZ_TRAIN_F={F}", "-shared",
-                                                 os.path.join(_build.CSRC, "mz_train_jit.hip"), "-o", tmp]
+                    cmd = [cc] + _build.FLAGS + [f"-DMZ_TRAIN_A={A}", f"-DMZ_TRAIN_E={E}", f"-DMZ_TRAIN_F={F}"] + \
+                        list(defines) + ["-shared", os.path.join(_build.CSRC, "mz_train_jit.hip"), "-o", tmp]
                     try:
                         if not _run_compiler(cmd, so[:-3] + ".log", verbose):
                             _failed.add(shape)
@@ -271,3 +265,34 @@ def ensure_train_instance(A: int, E: int, F: int, verbose: bool = False) -> bool
     _lib.check(L.mzs_register_train_dispatch(fn, A, E, F, side.mzs_jit_train_abi()))
     _loaded[shape] = side
     return True
+
+
+def ensure_train_instance(A: int, E: int, F: int, verbose: bool = False) -> bool:
+    """Make sure mzs_mlp_loss_grad can serve (num_actions, embedding_dim, F = 2 support_size + 1): True when an on-demand
+    instance of the fused training-step kernel (muax_amd/csrc/mz_train_jit.hip) is registered -- built now (one
+    translation unit, cached as muax_amd/lib/jit/mztrain_<shape>-<source hash>.so) or earlier --, False when the shape is
+    outside the kernel's limits (more than 16 actions, embeddings wider than 64, F outside 17..63), there is no compiler,
+    the build fails, or MUAX_AMD_JIT=0.  Round 5: a model whose act() runs on an on-demand instance keeps the fused
+    update() too (the reference's update() takes any widths, muax/model.py:181-201).  17 to 64 actions:
+    ensure_wide_train_instance."""
+    if os.environ.get("MUAX_AMD_JIT", "1") == "0":
+        return False
+    if not (1 <= A <= 16 and 1 <= E <= 64 and 17 <= F <= 63):
+        return False
+    return _ensure_train("train", "mztrain", (), A, E, F, verbose)
+
+
+WIDE_TRAIN_DEFINES = ("-DMZ_TRAIN_WIDE=1",)
+
+
+def ensure_wide_train_instance(A: int, E: int, F: int, verbose: bool = False) -> bool:
+    """ensure_train_instance for 17 <= num_actions <= 64 (1 <= E <= 64, 17 <= F <= 63 as there): the same translation
+    unit compiled with -DMZ_TRAIN_WIDE=1, which spreads the policy head over ceil(A / 16) lane slots and re-reads the
+    weights from LDS in every unroll step (mz_train.cuh); cached as muax_amd/lib/jit/mztrainwide_<shape>-<source
+    hash>.so.  False outside those limits, without a compiler, when the build fails, under MUAX_AMD_JIT=0, and under
+    MUAX_AMD_WIDE=0 (the switch that also keeps act() off the wide-action kernel)."""
+    if os.environ.get("MUAX_AMD_JIT", "1") == "0" or os.environ.get("MUAX_AMD_WIDE", "1") == "0":
+        return False
+    if not (17 <= A <= 64 and 1 <= E <= 64 and 17 <= F <= 63):
+        return False
+    return _ensure_train("train_wide", "mztrainwide", WIDE_TRAIN_DEFINES, A, E, F, verbose)

@@ -930,7 +930,7 @@ int mzs_mlp_loss_grad(const mzs_mlp_weights* w, const mzs_train_args* a, void* s
   if (a->batch <= 0 || a->unroll_steps <= 0) return fail(nullptr, MZS_E_INVALID, "mzs_mlp_loss_grad: batch and unroll_steps must be positive");
   if (!a->obs || !a->actions || !a->rewards || !a->returns || !a->policy || !a->loss || !a->grads || !a->workspace)
     return fail(nullptr, MZS_E_INVALID, "mzs_mlp_loss_grad: null batch / output / workspace pointer");
-  if (w->obs_dim <= 0 || w->obs_dim > 16) return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_mlp_loss_grad: obs_dim must be 1..16");
+  if (w->obs_dim <= 0 || w->obs_dim > 128) return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_mlp_loss_grad: obs_dim must be 1..128");
   const int A = a->num_actions, E = a->embed_dim, F = 2 * w->support_size + 1;
   if (a->workspace_bytes < mzs_mlp_train_workspace_bytes(a->batch, w->obs_dim, E, A, w->support_size))
     return fail(nullptr, MZS_E_INVALID, "mzs_mlp_loss_grad: workspace too small");

@@ -49,8 +49,16 @@ constexpr int TRAIN_LDS_BYTES = 160 * 1024;  // one workgroup may take all of a 
 template <int A_, int E_, int F_>
 struct TrainCfg {
   static constexpr int A = A_, E = E_, F = F_, H = 16, X = E_ + A_;
-  static constexpr int ES = (E + 15) / 16, FS = (F + 15) / 16, XS = (X + 15) / 16;
+  static constexpr int ES = (E + 15) / 16, FS = (F + 15) / 16, XS = (X + 15) / 16, AS = (A + 15) / 16;
+  // The listed instances and the narrow on-demand ones keep the policy head in one slot; a translation unit built
+  // with -DMZ_TRAIN_WIDE=1 (muax_amd/_jit.py::ensure_wide_train_instance) spreads it over AS <= 4 slots.
+#if defined(MZ_TRAIN_WIDE) && MZ_TRAIN_WIDE
+  static constexpr bool WIDE = true;
+  static_assert(A <= 64, "policy head in at most four slots");
+#else
+  static constexpr bool WIDE = false;
   static_assert(A <= 16, "policy head in one slot");
+#endif
   static constexpr int ld(int n) { return 16 * ((n + 15) / 16) + 1; }  // odd, zero padded
   // LDS weight blocks: [K][ld(N)] then the bias padded to a multiple of 16
   static constexpr int blk(int k, int n) { return k * ld(n) + 16 * ((n + 15) / 16); }
@@ -261,7 +269,7 @@ MZ_DEV void minmax_bwd(const float (&g)[(E + 15) / 16], const float (&u)[(E + 15
 template <class C>
 __global__ __launch_bounds__(256) void mz_train_kernel(const TrainParams p) {
   constexpr int A = C::A, E = C::E, F = C::F, H = C::H, X = C::X;
-  constexpr int ES = C::ES, FS = C::FS, XS = C::XS;
+  constexpr int ES = C::ES, FS = C::FS, XS = C::XS, AS = C::AS;
   extern __shared__ float lds[];
   const int tid = threadIdx.x, lane = tid & 63, j = tid & 15;
   const int row = tid >> 4;
@@ -282,10 +290,23 @@ __global__ __launch_bounds__(256) void mz_train_kernel(const TrainParams p) {
     }
   }
   __syncthreads();
-  const float* Wpv1 = lds + C::PV1; const float* Wpv2 = lds + C::PV2;
-  const float* Wpp1 = lds + C::PP1; const float* Wpp2 = lds + C::PP2;
-  const float* Wdr1 = lds + C::DR1; const float* Wdr2 = lds + C::DR2;
-  const float* Wdn1 = lds + C::DN1; const float* Wdn2 = lds + C::DN2;
+  // The weights do not change after the barrier, so the compiler is free to lift their LDS reads out of the unroll
+  // loops and keep them in registers.  The narrow instances gain from that.  A wide instance has up to 40 accumulator
+  // tiles and 8-slot layer inputs, the lifted reads would push it into scratch (AMD clang 22.0.0git of ROCm 7.2,
+  // 256 VGPRs + 256 AGPRs each: 2412 bytes per lane at (64, 64, 63), 944 at (18, 32, 63), 316 at (18, 8, 63); with the
+  // re-reads 256 + 81, 256 + 62 and 256 + 34 registers and no scratch), so it takes the base of the weights through an
+  // opaque register once per step: every step re-reads what it needs from LDS, at a VGPR base plus a constant offset.
+  // profiles/wide_train.txt has the figures per shape; tools/bench_train.py --wide times a narrow and a wide instance of
+  // almost the same work (A = 16 / 17, E = 8) to show what the re-reads cost.
+  auto weights = [&]() -> const float* {
+    if constexpr (C::WIDE) {
+      int z = 0;
+      asm volatile("" : "+v"(z));
+      return lds + z;
+    } else {
+      return lds;
+    }
+  };
   float* ck = lds + C::WEIGHT_WORDS + row * 16 * ES;  // + step * CK_WORDS_PER_STEP
 
   const int L = p.L;
@@ -323,6 +344,8 @@ __global__ __launch_bounds__(256) void mz_train_kernel(const TrainParams p) {
 #pragma unroll
     for (int t = 0; t < ES; ++t) ck[j + 16 * t] = s[t];
     for (int i = 0; i + 1 < L; ++i) {
+      const float* Wl = weights();
+      const float* Wdn1 = Wl + C::DN1; const float* Wdn2 = Wl + C::DN2;
       float x[XS], hn[1], u[ES], mn, mx, c;
       make_x(s, p.act[(size_t)r * L + i], x);
       lin_fwd<X, H>(x, Wdn1, j, hn);
@@ -335,21 +358,28 @@ __global__ __launch_bounds__(256) void mz_train_kernel(const TrainParams p) {
   }
 
   // ---- sweep 2: heads, loss and gradients, last step first ----
-  f32x4 g_pv1[ES][1], g_pv2[1][FS], g_pp1[ES][1], g_pp2[1][1], g_dr1[XS][1], g_dr2[1][FS], g_dn1[XS][1], g_dn2[1][ES];
+  f32x4 g_pv1[ES][1], g_pv2[1][FS], g_pp1[ES][1], g_pp2[1][AS], g_dr1[XS][1], g_dr2[1][FS], g_dn1[XS][1], g_dn2[1][ES];
   zero_tiles(g_pv1); zero_tiles(g_pv2); zero_tiles(g_pp1); zero_tiles(g_pp2);
   zero_tiles(g_dr1); zero_tiles(g_dr2); zero_tiles(g_dn1); zero_tiles(g_dn2);
-  float b_pv1[1] = {0.0f}, b_pp1[1] = {0.0f}, b_pp2[1] = {0.0f}, b_dr1[1] = {0.0f}, b_dn1[1] = {0.0f};
-  float b_pv2[FS], b_dr2[FS], b_dn2[ES];
+  float b_pv1[1] = {0.0f}, b_pp1[1] = {0.0f}, b_dr1[1] = {0.0f}, b_dn1[1] = {0.0f};
+  float b_pv2[FS], b_dr2[FS], b_dn2[ES], b_pp2[AS];
 #pragma unroll
   for (int t = 0; t < FS; ++t) b_pv2[t] = b_dr2[t] = 0.0f;
 #pragma unroll
   for (int t = 0; t < ES; ++t) b_dn2[t] = 0.0f;
+#pragma unroll
+  for (int t = 0; t < AS; ++t) b_pp2[t] = 0.0f;
   float loss = 0.0f;
   float ds_next[ES];
 #pragma unroll
   for (int t = 0; t < ES; ++t) ds_next[t] = 0.0f;
 
   for (int i = L - 1; i >= 0; --i) {
+    const float* Wl = weights();
+    const float* Wpv1 = Wl + C::PV1; const float* Wpv2 = Wl + C::PV2;
+    const float* Wpp1 = Wl + C::PP1; const float* Wpp2 = Wl + C::PP2;
+    const float* Wdr1 = Wl + C::DR1; const float* Wdr2 = Wl + C::DR2;
+    const float* Wdn1 = Wl + C::DN1; const float* Wdn2 = Wl + C::DN2;
     float s[ES], x[XS];
 #pragma unroll
     for (int t = 0; t < ES; ++t) s[t] = ck[i * C::CK_WORDS_PER_STEP + j + 16 * t];
@@ -423,14 +453,16 @@ __global__ __launch_bounds__(256) void mz_train_kernel(const TrainParams p) {
       for (int t = 0; t < ES; ++t) ds[t] = ds[t] + dsv[t];
     }
     {
-      float ap[1], lp[1], tp[1], dlp[1], dap[1], dsp[ES];
+      float ap[1], lp[AS], tp[AS], dlp[AS], dap[1], dsp[ES];
       lin_fwd<E, H>(s, Wpp1, j, ap);
       elu_vec(ap);
       lin_fwd<H, A>(ap, Wpp2, j, lp);
-      tp[0] = j < A ? p.pi[((size_t)r * L + i) * A + j] : 0.0f;
+#pragma unroll
+      for (int t = 0; t < AS; ++t) tp[t] = (j + 16 * t < A) ? p.pi[((size_t)r * L + i) * A + j + 16 * t] : 0.0f;
       loss = loss + ce_and_grad<A>(lp, tp, j, scale, dlp);
       grad_tiles(ap, dlp, g_pp2);
-      b_pp2[0] = b_pp2[0] + dlp[0];
+#pragma unroll
+      for (int t = 0; t < AS; ++t) b_pp2[t] = b_pp2[t] + dlp[t];
       lin_bwd<H, A>(dlp, Wpp2, j, dap);
       dap[0] = dap[0] * elu_grad(ap[0]);
       grad_tiles(s, dap, g_pp1);
@@ -451,17 +483,19 @@ __global__ __launch_bounds__(256) void mz_train_kernel(const TrainParams p) {
     for (int t = 0; t < ES; ++t) s[t] = ck[j + 16 * t];
     minmax_bwd<E>(ds_next, u0, s, s0mn, s0mx, s0c, j, du0);
   }
-  f32x4 g_rep[1][ES];
-  zero_tiles(g_rep);
-  {
-    float ob[1];
-    ob[0] = j < p.obs_dim ? p.obs[(size_t)r * p.obs_dim + j] : 0.0f;
-    grad_tiles(ob, du0, g_rep);
-  }
 
   // ---- this wavefront's partial gradient -> its workspace row ----
   float* dst = p.ws + (size_t)(blockIdx.x * 4 + (tid >> 6)) * (p.off[18] + 1);
-  store_tiles(g_rep, dst + p.off[0], p.obs_dim, E, lane);
+  // obs^T du0, one tile row per 16 observation features (once per sample: the row lives only between its MFMAs and
+  // its store, whatever obs_dim is)
+  for (int o = 0; o < p.obs_dim; o += 16) {
+    f32x4 g_rep[1][ES];
+    zero_tiles(g_rep);
+    float ob[1];
+    ob[0] = o + j < p.obs_dim ? p.obs[(size_t)r * p.obs_dim + o + j] : 0.0f;
+    grad_tiles(ob, du0, g_rep);
+    store_tiles(g_rep, dst + p.off[0] + o * E, p.obs_dim - o, E, lane);
+  }
   store_bias(du0, dst + p.off[1], E, lane);
   store_tiles(g_pv1, dst + p.off[2], E, H, lane);  store_bias(b_pv1, dst + p.off[3], H, lane);
   store_tiles(g_pv2, dst + p.off[4], H, F, lane);  store_bias(b_pv2, dst + p.off[5], F, lane);

@@ -6,7 +6,8 @@
 // built on demand (mz_fused_jit.hip); this is the same for the training step, so that such a model's update() does not
 // drop to framework autograd (14 - 22 ms against 0.06 ms at 4096 x 10).  The host side (muax_amd/_jit.py) compiles THIS
 // translation unit with -DMZ_TRAIN_A=.. -DMZ_TRAIN_E=.. -DMZ_TRAIN_F=.., loads it and hands mzs_jit_train_launch to
-// mzs_register_train_dispatch(): same kernel source, same arithmetic.
+// mzs_register_train_dispatch(): same kernel source, same arithmetic.  With -DMZ_TRAIN_WIDE=1 on top
+// (_jit.ensure_wide_train_instance) the same unit serves 17 to 64 actions: mz_train.cuh lifts its one-slot assertion.
 #if !defined(MZ_TRAIN_A) || !defined(MZ_TRAIN_E) || !defined(MZ_TRAIN_F)
 #error "build through muax_amd/_jit.py"
 #endif

@@ -543,7 +543,7 @@ class MuZero:
                 self._optimizer.load_state_dict(loaded)
                 self._loaded_opt_state = None
         fused = backend != "torch" and self.loss_fn is None and self.device.type == "cuda" \
-            and mz_nn.is_default_mlp_trio(self.network) and (self.repr_func.obs_dim or 99) <= 16 \
+            and mz_nn.is_default_mlp_trio(self.network) and (self.repr_func.obs_dim or 999) <= 128 \
             and not kwargs.get("pi_all_pairs", False)
         if backend == "hip" and not fused:
             raise ValueError("backend='hip' needs the default MLP trio on a GPU and the default loss")
@@ -555,10 +555,13 @@ class MuZero:
                     loss, flat = self._fused_train(batch, divide_by_length=kwargs.get("divide_by_length", False))
                 except ValueError as e:
                     # a shape of the default trio the library lists no training instance for: build one on demand
-                    # (muax_amd/_jit.py::ensure_train_instance, once per shape, cached on disk) and call again
+                    # (muax_amd/_jit.py::ensure_train_instance, or ensure_wide_train_instance for 17 to 64 actions; once
+                    # per shape, cached on disk) and call again
                     from . import _jit
                     ft = self._fused_train
-                    if "no kernel instance" not in str(e) or not _jit.ensure_train_instance(ft.A, ft.E, 2 * ft.S + 1):
+                    shape = (ft.A, ft.E, 2 * ft.S + 1)
+                    if "no kernel instance" not in str(e) or not (_jit.ensure_train_instance(*shape)
+                                                                  or _jit.ensure_wide_train_instance(*shape)):
                         raise
                     loss, flat = ft(batch, divide_by_length=kwargs.get("divide_by_length", False))
                 if dp_mean:
