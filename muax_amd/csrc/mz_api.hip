@@ -975,6 +975,9 @@ int mzs_mlp_loss_grad(const mzs_mlp_weights* w, const mzs_train_args* a, void* s
       return rc == MZS_OK ? MZS_OK : fail(nullptr, rc, "mzs_mlp_loss_grad (on-demand instance): %s", msg);
     }
   }
+  if (F < 17 || F > 63)  // no instance can exist: name the limit (callers still match "no kernel instance")
+    return fail(nullptr, MZS_E_UNSUPPORTED,
+                "mzs_mlp_loss_grad: no kernel instance for this (A, E, F): support_size must be 8..31");
   return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_mlp_loss_grad: no kernel instance for this (A, E, F)");
 }
 
