@@ -514,6 +514,89 @@ int mzs_mlp_wide_plan_policy(int32_t num_actions, int32_t embed_dim, int32_t sup
 int mzs_resnet_search(mzs_handle *h, const mzs_tower_args *a, float discount, int32_t sim_begin, int32_t sim_end,
                       void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Device-resident trajectory replay (mz_replay.cuh): the buffer of muax/replay_buffer.py:161-262 with
+ * its storage on the GPU and a k-step batch sampled in ONE launch, in the layout mzs_mlp_loss_grad reads.
+ *
+ * Whole episodes lie contiguous in per-field arenas of `max_steps` transitions (caller-owned device memory, as are the
+ * two episode tables of `capacity` rows); WHERE an episode goes and which ones are evicted is the caller's bookkeeping
+ * (muax_amd/replay_device.py).  No entry point synchronises or copies to the host; errors: mzs_last_error(NULL). */
+typedef struct mzs_replay_arena {
+  int32_t struct_size;     /* = sizeof(mzs_replay_arena) */
+  int32_t device;
+  int64_t max_steps;       /* transitions per arena, < 2^31 */
+  int32_t capacity;        /* episode table rows */
+  int32_t obs_dim, num_actions, reserved0;
+  float *obs;              /* [max_steps, obs_dim] */
+  int32_t *a;              /* [max_steps] */
+  float *r, *Rn, *v;       /* [max_steps] */
+  uint8_t *done;           /* [max_steps] */
+  float *pi;               /* [max_steps, num_actions] */
+  double *w, *cw;          /* [max_steps]: priority weight; its inclusive prefix sum inside the episode */
+  int32_t *t_start, *t_len; double *t_w; int64_t *t_serial;   /* [capacity] by table slot: written by the store */
+  int32_t *c_start, *c_len; double *c_CW; int64_t *c_serial;  /* [capacity] oldest first: written by the refresh */
+} mzs_replay_arena;
+
+/* One add: `episodes` complete episodes, given as one flat stream of `stream_steps` transitions, are copied to their
+ * places, the prefix sums `cw` and the table rows written -- one launch, one wavefront per episode.
+ *   desc[e] = {first transition in the stream, first transition in the arena, length, table slot}; the HOST copy is
+ *   checked here (ranges inside the stream / the arena, slot < capacity), the DEVICE copy is what the kernel reads.
+ *   The caller keeps the episodes of one call disjoint in the arena and in the table.
+ * raw == 0: r, v are float[stream_steps]; Rn, done, w are given; the episode weights are ep_w (weight_mode 0).
+ * raw == 1: r, v are DOUBLE[stream_steps]; Rn, done and w are computed as muax_amd/vector.py:25-52 defines them, in
+ *   fp64 and in its operation order: Rn = sum_{i < n_step} gpow[i] * r[t + i] (i ascending, 0 past the end), then
+ *   + v[t + n_step] * gpow[n_step] where that step exists (else done = 1); w = |v - Rn| ** alpha, or 1 with
+ *   has_alpha == 0.  gpow: device table of the n_step + 1 powers gamma ** i the host computed.
+ *   weight_mode 1 / 2: the episode weight is the mean / the sum of its w (0: ep_w, as with raw == 0). */
+typedef struct mzs_replay_store_args {
+  int32_t struct_size;     /* = sizeof(mzs_replay_store_args) */
+  int32_t episodes;
+  int64_t stream_steps;
+  int32_t raw, n_step, weight_mode, has_alpha;
+  double alpha;
+  const int32_t *desc_host;  /* HOST [episodes][4] */
+  const int32_t *desc;       /* [episodes][4] */
+  const int64_t *serial;     /* [episodes]: running number of the add that stores the episode */
+  const double *ep_w;        /* [episodes], or NULL with weight_mode != 0 */
+  const double *gpow;        /* [n_step + 1] (raw) */
+  const float *obs;          /* [stream_steps, obs_dim] */
+  const int32_t *a;          /* [stream_steps] */
+  const float *pi;           /* [stream_steps, num_actions] */
+  const void *r, *v;         /* [stream_steps] float (raw == 0) or double (raw == 1) */
+  const float *Rn; const uint8_t *done; const double *w;   /* [stream_steps] (raw == 0) */
+} mzs_replay_store_args;
+int mzs_replay_store(const mzs_replay_arena *arena, const mzs_replay_store_args *a, void *stream);
+
+/* The `count` live episodes from table slot `head` on (slots wrap at capacity), oldest first, into the compact table,
+ * with CW = the inclusive fp64 prefix sum, in that order, of the weights of the episodes LONGER than k_steps (the others
+ * carry no probability).  One launch; needed after adds / evictions and when k_steps changes. */
+int mzs_replay_refresh(const mzs_replay_arena *arena, int32_t head, int32_t count, int32_t k_steps, void *stream);
+
+/* A batch of `batch` k-step windows in one launch, one wavefront per row.  Row j:
+ *   u(x0, x1) = ((y0 << 32 | y1) >> 11) * 2^-53 in fp64 with (y0, y1) = threefry2x32(key, x0, x1);
+ *   u0 = u(j / sample_per_trajectory, 0), u1 = u(j, 1);
+ *   episode e = the first with CW[e] > u0 * CW[count - 1];   m = length(e) - k_steps;
+ *   start i = the first i < m with cw[i] > u1 * cw[m - 1], or floor(u1 * m) when cw[m - 1] == 0;
+ *   the outputs are transitions i .. i + k_steps - 1 of that episode (obs: transition i alone).
+ * With every weight zero (CW[count - 1] == 0: the caller's error) the draw lands on the newest episode; a row whose
+ * episode is no longer than k_steps is zero-filled, serial and start -1. */
+typedef struct mzs_replay_sample_args {
+  int32_t struct_size;     /* = sizeof(mzs_replay_sample_args) */
+  int32_t count;           /* rows of the compact table */
+  int32_t batch, k_steps, sample_per_trajectory;
+  uint32_t key[2];         /* HOST values */
+  int32_t reserved0;
+  float *obs;              /* out [batch, obs_dim] */
+  int32_t *a;              /* out [batch, k_steps] */
+  float *r, *Rn, *v;       /* out [batch, k_steps] */
+  uint8_t *done;           /* out [batch, k_steps], 0 / 1 */
+  float *pi;               /* out [batch, k_steps, num_actions] */
+  float *w;                /* out [batch, k_steps] */
+  int64_t *serial;         /* out [batch] */
+  int32_t *start;          /* out [batch] */
+} mzs_replay_sample_args;
+int mzs_replay_sample(const mzs_replay_arena *arena, const mzs_replay_sample_args *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ mctx.muzero_policy loop as hand-written gfx950 HIP kernels behind a C-ABI
 from . import checkpoint, episode_tracer, loss, nn, optimizers, prng, replay_buffer, utils  # noqa: F401
 from .episode_tracer import NStep, PNStep  # noqa: F401
 from .replay_buffer import Trajectory, TrajectoryReplayBuffer  # noqa: F401
+from .replay_device import DeviceReplayBuffer  # noqa: F401
 from .loss import Transition, default_loss_fn  # noqa: F401
 from .model import MuZero  # noqa: F401
 from .nn import MZNetwork, MZNetworkParams, create_muzero_network  # noqa: F401

@@ -3,7 +3,7 @@
 The library is several translation units compiled in parallel (each `hipcc -c`, objects under muax_amd/lib/obj/)
 and linked into one shared object: the C-ABI and the step-wise / training / Dirichlet kernels (mz_api.hip), the
 fused act() kernel instances in five groups (mz_fused_g*.hip, listed in mz_instances.def), the wide-action act()
-kernel (mz_wide.hip) and the ResNet recurrent kernel (mz_conv.hip).  Only the units whose sources changed are recompiled."""
+kernel (mz_wide.hip), the ResNet recurrent kernel (mz_conv.hip) and the device-resident replay (mz_replay.hip).  Only the units whose sources changed are recompiled."""
 from __future__ import annotations
 
 import os
@@ -32,6 +32,7 @@ UNITS = {
     "mz_norm.hip": ["mz_host.h", "mz_norm.cuh", "mz_repr.cuh", "mz_repr_host.h", "mz_spec.cuh", _ABI],
     "mz_repr.hip": ["mz_host.h", "mz_repr.cuh", "mz_repr_host.h", "mz_norm.cuh", "mz_spec.cuh", _ABI],
     "mz_ez.hip": ["mz_host.h", "mz_ez.cuh", "mz_spec.cuh", _ABI],
+    "mz_replay.hip": ["mz_host.h", "mz_replay.cuh", "mz_spec.cuh", _ABI],
 }
 SOURCES = list(UNITS)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-honor-nans",

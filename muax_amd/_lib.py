@@ -125,6 +125,26 @@ class MzsResblockArgs(C.Structure):
                 ("workspace", _vp), ("workspace_bytes", C.c_int64)]
 
 
+class MzsReplayArena(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("device", C.c_int32), ("max_steps", C.c_int64), ("capacity", C.c_int32),
+                 ("obs_dim", C.c_int32), ("num_actions", C.c_int32), ("reserved0", C.c_int32)]
+                + [(n, _vp) for n in ("obs", "a", "r", "Rn", "v", "done", "pi", "w", "cw", "t_start", "t_len", "t_w",
+                                      "t_serial", "c_start", "c_len", "c_CW", "c_serial")])
+
+
+class MzsReplayStoreArgs(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("episodes", C.c_int32), ("stream_steps", C.c_int64), ("raw", C.c_int32),
+                 ("n_step", C.c_int32), ("weight_mode", C.c_int32), ("has_alpha", C.c_int32), ("alpha", C.c_double)]
+                + [(n, _vp) for n in ("desc_host", "desc", "serial", "ep_w", "gpow", "obs", "a", "pi", "r", "v", "Rn",
+                                      "done", "w")])
+
+
+class MzsReplaySampleArgs(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("count", C.c_int32), ("batch", C.c_int32), ("k_steps", C.c_int32),
+                 ("sample_per_trajectory", C.c_int32), ("key", C.c_uint32 * 2), ("reserved0", C.c_int32)]
+                + [(n, _vp) for n in ("obs", "a", "r", "Rn", "v", "done", "pi", "w", "serial", "start")])
+
+
 EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_destroy",
                     "mzs_mlp_set_weights", "mzs_act_mlp", "mzs_root", "mzs_root_gumbel", "mzs_select",
                     "mzs_expand_backup", "mzs_expand_backup_select",
@@ -136,7 +156,8 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_resblock_v1", "mzs_resblock_workspace_bytes", "mzs_conv3x3_stride2_nhwc", "mzs_resnet_root_tail",
                     "mzs_resblock_v2", "mzs_resblock_v2_workspace_bytes", "mzs_register_train_dispatch", "mzs_train_jit_abi",
                     "mzs_mlp_allow_wide", "mzs_mlp_wide_plan",
-                    "mzs_mlp_allow_wide_gumbel", "mzs_mlp_wide_plan_policy"]
+                    "mzs_mlp_allow_wide_gumbel", "mzs_mlp_wide_plan_policy",
+                    "mzs_replay_store", "mzs_replay_refresh", "mzs_replay_sample"]
 
 _lib = None
 
@@ -202,6 +223,9 @@ def load(build_if_missing: bool = True):
     L.mzs_resblock_workspace_bytes.restype = C.c_int64
     L.mzs_resblock_v2_workspace_bytes.restype = C.c_int64
     L.mzs_tower_pair_scratch_bytes.argtypes = [C.c_int32]
+    L.mzs_replay_store.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayStoreArgs), _vp]
+    L.mzs_replay_refresh.argtypes = [C.POINTER(MzsReplayArena), C.c_int32, C.c_int32, C.c_int32, _vp]
+    L.mzs_replay_sample.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplaySampleArgs), _vp]
     L.mzs_tower_pair_scratch_bytes.restype = C.c_int64
     if L.mzs_abi_version() != 1:
         raise RuntimeError("libmzsearch.so ABI version mismatch")

@@ -1,0 +1,207 @@
+// mz_replay.cuh -- device-resident trajectory replay (muax/replay_buffer.py:161-262 on the GPU).
+//
+// Whole episodes lie contiguous in per-field arenas of `max_steps` transitions, so a k-step training window is one
+// contiguous range of every field.  Three kernels, one wavefront per episode / per batch row, vector stores only:
+//   replay_store_kernel    copies the episodes of one add into the arenas; with `raw` it first computes the n-step
+//                          returns, `done` and the priority weights (muax_amd/vector.py:25-52) in fp64; then the
+//                          inclusive prefix sum `cw` of the transition weights and the episode's row of the table
+//   replay_refresh_kernel  the live episodes, oldest first, as a compact table with the inclusive prefix sum CW of the
+//                          weights of those longer than k_steps (one wavefront; after adds or a change of k_steps)
+//   replay_sample_kernel   per batch row: two threefry draws, the episode and the start by binary search in CW / cw,
+//                          then 64 lanes copy the window
+// Every prefix sum is the SEQUENTIAL fp64 sum (np.cumsum's order), one addition per element on a wave-uniform carry:
+// monotone, so the searches are well defined, and equal to the host's bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mz_spec.cuh"
+
+#pragma clang fp contract(off)
+
+namespace mz {
+
+constexpr int kReplayWaves = 4;  // wavefronts (episodes / batch rows) per workgroup
+
+struct ReplayArena {
+  long long max_steps;
+  int capacity, obs_dim, A;
+  float* obs; int32_t* a; float* r; float* Rn; float* v; uint8_t* done; float* pi; double* w; double* cw;
+  int32_t* t_start; int32_t* t_len; double* t_w; long long* t_serial;          // [capacity], by slot
+  int32_t* c_start; int32_t* c_len; double* c_CW; long long* c_serial;         // [capacity], oldest first
+};
+
+struct ReplayStoreArgs {
+  ReplayArena ar;
+  int episodes, raw, n_step, weight_mode, has_alpha;
+  double alpha;
+  const int32_t* desc;        // [episodes][4]: first transition in the stream, first in the arena, length, table slot
+  const long long* serial;    // [episodes]
+  const double* ep_w;         // [episodes] (weight_mode 0)
+  const double* gpow;         // [n_step + 1]: gamma ** i (raw)
+  const float* obs; const int32_t* a; const float* pi;
+  const float* r32; const float* v32; const double* r64; const double* v64;  // raw reads the fp64 pair
+  const float* Rn; const uint8_t* done; const double* w;
+};
+
+struct ReplaySampleArgs {
+  ReplayArena ar;
+  int count, B, k, spt;
+  uint32_t key0, key1;
+  float* obs; int32_t* a; float* r; float* Rn; float* v; uint8_t* done; float* pi; float* w;
+  long long* serial; int32_t* start;
+};
+
+MZ_DEV double lane_bcast(double x, int j) {  // j wave-uniform
+  const int lo = __builtin_amdgcn_readlane(__double2loint(x), j);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), j);
+  return __hiloint2double(hi, lo);
+}
+
+// inclusive sequential prefix sum over the first `valid` lanes, continued from the wave-uniform `carry`
+MZ_DEV double seq_scan(double x, int valid, int lane, double& carry) {
+  double mine = 0.0;
+  for (int j = 0; j < valid; ++j) {
+    carry = carry + lane_bcast(x, j);
+    if (lane == j) mine = carry;
+  }
+  return mine;
+}
+
+// (y0 << 32 | y1) >> 11 of one threefry block, as a double in [0, 1)
+MZ_DEV double uniform53(uint32_t k0, uint32_t k1, uint32_t x0, uint32_t x1) {
+  threefry2x32(k0, k1, x0, x1);
+  const unsigned long long bits = (((unsigned long long)x0 << 32) | x1) >> 11;
+  return (double)bits * 0x1p-53;
+}
+
+// first i in [0, n) with c[i] > t, n when there is none (c ascending)
+MZ_DEV int upper_bound(const double* c, int n, double t) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (c[mid] > t) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+__global__ void __launch_bounds__(64 * kReplayWaves) replay_store_kernel(ReplayStoreArgs p) {
+  const int lane = threadIdx.x & 63;
+  const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  if (e >= p.episodes) return;
+  const ReplayArena& ar = p.ar;
+  const size_t src = (size_t)p.desc[4 * e], dst = (size_t)p.desc[4 * e + 1];
+  const int T = p.desc[4 * e + 2], slot = p.desc[4 * e + 3];
+  const size_t no = (size_t)T * ar.obs_dim, np_ = (size_t)T * ar.A;
+  for (size_t i = lane; i < no; i += 64) ar.obs[dst * ar.obs_dim + i] = p.obs[src * ar.obs_dim + i];
+  for (size_t i = lane; i < np_; i += 64) ar.pi[dst * ar.A + i] = p.pi[src * ar.A + i];
+  double carry = 0.0;
+  for (int base = 0; base < T; base += 64) {
+    const int t = base + lane;
+    const bool in = t < T;
+    double w = 0.0;
+    if (in) {
+      ar.a[dst + t] = p.a[src + t];
+      if (p.raw) {
+        // vector.nstep_returns, its operation order: i ascending (terms past the end are + gamma^i * 0), then the bootstrap
+        const double* r = p.r64 + src;
+        double Rn = 0.0;
+        for (int i = 0; i < p.n_step; ++i) Rn = Rn + p.gpow[i] * (t + i < T ? r[t + i] : 0.0);
+        const bool boot = t + p.n_step < T;
+        Rn = Rn + (boot ? p.v64[src + t + p.n_step] * p.gpow[p.n_step] : 0.0);
+        const double v = p.v64[src + t];
+        w = p.has_alpha ? pow(fabs(v - Rn), p.alpha) : 1.0;
+        ar.r[dst + t] = (float)r[t];
+        ar.v[dst + t] = (float)v;
+        ar.Rn[dst + t] = (float)Rn;
+        ar.done[dst + t] = boot ? 0 : 1;
+      } else {
+        w = p.w[src + t];
+        ar.r[dst + t] = p.r32[src + t];
+        ar.v[dst + t] = p.v32[src + t];
+        ar.Rn[dst + t] = p.Rn[src + t];
+        ar.done[dst + t] = p.done[src + t] ? 1 : 0;
+      }
+      ar.w[dst + t] = w;
+    }
+    const int valid = T - base < 64 ? T - base : 64;
+    const double c = seq_scan(w, valid, lane, carry);
+    if (in) ar.cw[dst + t] = c;
+  }
+  if (lane == 0) {
+    ar.t_start[slot] = (int32_t)dst;
+    ar.t_len[slot] = T;
+    ar.t_w[slot] = p.weight_mode == 0 ? p.ep_w[e] : p.weight_mode == 1 ? carry / (double)T : carry;
+    ar.t_serial[slot] = p.serial[e];
+  }
+}
+
+__global__ void __launch_bounds__(64) replay_refresh_kernel(ReplayArena ar, int head, int count, int k) {
+  const int lane = threadIdx.x;
+  double carry = 0.0;
+  for (int base = 0; base < count; base += 64) {
+    const int i = base + lane;
+    const bool in = i < count;
+    int slot = in ? head + i : head;
+    if (slot >= ar.capacity) slot -= ar.capacity;
+    const int len = ar.t_len[slot];
+    const double w = in && len > k ? ar.t_w[slot] : 0.0;
+    const int valid = count - base < 64 ? count - base : 64;
+    const double c = seq_scan(w, valid, lane, carry);
+    if (in) {
+      ar.c_start[i] = ar.t_start[slot];
+      ar.c_len[i] = len;
+      ar.c_serial[i] = ar.t_serial[slot];
+      ar.c_CW[i] = c;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64 * kReplayWaves) replay_sample_kernel(ReplaySampleArgs p) {
+  const int lane = threadIdx.x & 63;
+  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  if (row >= p.B) return;
+  const ReplayArena& ar = p.ar;
+  const int k = p.k, A = ar.A, od = ar.obs_dim;
+  // the draws and the two searches are wave-uniform: scalar loads, done once per row
+  const double u0 = uniform53(p.key0, p.key1, (uint32_t)(row / p.spt), 0u);
+  const double u1 = uniform53(p.key0, p.key1, (uint32_t)row, 1u);
+  const double total = ar.c_CW[p.count - 1];
+  int e = upper_bound(ar.c_CW, p.count, u0 * total);
+  if (e > p.count - 1) e = p.count - 1;  // (only when every weight is zero)
+  const int T = ar.c_len[e], m = T - k;
+  const size_t first = (size_t)ar.c_start[e];
+  const size_t ok = (size_t)row * k;
+  if (m <= 0) {  // nothing to draw from (the host refuses such a buffer; all-zero weights can still lead here): zeros
+    for (int i = lane; i < k * A; i += 64) p.pi[ok * A + i] = 0.f;
+    for (int i = lane; i < od; i += 64) p.obs[(size_t)row * od + i] = 0.f;
+    for (int i = lane; i < k; i += 64) {
+      p.a[ok + i] = 0; p.r[ok + i] = 0.f; p.Rn[ok + i] = 0.f; p.v[ok + i] = 0.f; p.done[ok + i] = 0; p.w[ok + i] = 0.f;
+    }
+    if (lane == 0) { p.serial[row] = -1; p.start[row] = -1; }
+    return;
+  }
+  const double* cw = ar.cw + first;
+  const double tot = cw[m - 1];
+  int s;
+  if (tot == 0.0) {
+    s = (int)floor(u1 * (double)m);
+  } else {
+    s = upper_bound(cw, m, u1 * tot);
+  }
+  if (s > m - 1) s = m - 1;
+  const size_t at = first + (size_t)s;
+  for (int i = lane; i < k * A; i += 64) p.pi[ok * A + i] = ar.pi[at * A + i];
+  for (int i = lane; i < k; i += 64) {
+    p.a[ok + i] = ar.a[at + i];
+    p.r[ok + i] = ar.r[at + i];
+    p.Rn[ok + i] = ar.Rn[at + i];
+    p.v[ok + i] = ar.v[at + i];
+    p.done[ok + i] = ar.done[at + i];
+    p.w[ok + i] = (float)ar.w[at + i];
+  }
+  for (int i = lane; i < od; i += 64) p.obs[(size_t)row * od + i] = ar.obs[at * od + i];
+  if (lane == 0) { p.serial[row] = ar.c_serial[e]; p.start[row] = s; }
+}
+
+}  // namespace mz

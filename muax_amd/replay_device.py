@@ -1,0 +1,335 @@
+"""Device-resident trajectory replay: `TrajectoryReplayBuffer`'s interface (muax/replay_buffer.py:161-262) with the
+storage on the GPU and `sample()` as ONE launch that leaves a `Transition` of device tensors in the layout
+`MuZero.update(backend="hip")` reads in place (kernels: muax_amd/csrc/mz_replay.cuh; the arithmetic
+spec, the arena and the eviction rule: DESIGN.md 4.7).
+
+The Python here keeps the bookkeeping -- where an episode goes, which ones are evicted, the running key -- and never
+reads the device: `sample()` makes no device-to-host copy and no synchronisation, so it can be captured in a graph.
+There is no CPU fallback: without a GPU the first add raises."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from collections import deque, namedtuple
+
+import numpy as np
+import torch
+
+from . import _lib, prng
+from .episode_tracer import Transition
+from .replay_buffer import BaseReplayBuffer
+
+_Episode = namedtuple("_Episode", "slot start length serial")
+_ARENA_FIELDS = (("obs", torch.float32), ("a", torch.int32), ("r", torch.float32), ("Rn", torch.float32),
+                 ("v", torch.float32), ("done", torch.uint8), ("pi", torch.float32), ("w", torch.float64),
+                 ("cw", torch.float64))
+_TABLE_FIELDS = (("t_start", torch.int32), ("t_len", torch.int32), ("t_w", torch.float64), ("t_serial", torch.int64),
+                 ("c_start", torch.int32), ("c_len", torch.int32), ("c_CW", torch.float64), ("c_serial", torch.int64))
+_WEIGHT_MODES = {"mean": 1, "sum": 2}
+
+
+def _columns(trajectory):
+    """(obs [T, obs_dim] f32, a [T] i32, r, Rn, v [T] f32, done [T] u8, pi [T, A] f32, w [T] f64) of a Trajectory,
+    array-backed or filled step by step."""
+    if getattr(trajectory, "_rows", None) is not None:
+        cols = trajectory._rows
+    else:
+        if trajectory.batched_transitions is None:
+            trajectory.finalize()
+        cols = [np.asarray(x)[0] for x in trajectory.batched_transitions]
+    obs, a, r, done, Rn, v, pi, w = (np.asarray(x) for x in cols)
+    T = len(trajectory)
+    if T == 0:
+        raise ValueError("an empty trajectory cannot be stored")
+
+    def col(x, dt):
+        x = x.reshape(T, -1)[:, 0] if x.ndim else np.full(T, x)
+        return np.ascontiguousarray(x, dtype=dt)
+    return (np.ascontiguousarray(obs.reshape(T, -1), dtype=np.float32), col(a, np.int32), col(r, np.float32),
+            col(Rn, np.float32), col(v, np.float32), col(done, np.uint8),
+            np.ascontiguousarray(pi.reshape(T, -1), dtype=np.float32), col(w, np.float64))
+
+
+class DeviceReplayBuffer(BaseReplayBuffer):
+    """Ring buffer of whole episodes on the GPU.
+
+    `capacity` episodes at most, `max_steps` transitions at most: every field has an arena of `max_steps` rows in
+    which an episode is one contiguous range (never split across the wrap).  A new episode evicts the oldest ones
+    while the episode count would exceed `capacity` or the arena has no contiguous room for it; one longer than
+    `max_steps` is a ValueError.  `obs_dim` / `num_actions` default to those of the first episode added.
+
+    `sample()` differs from the host buffer in two documented ways: the batch size is FIXED (episodes no longer than
+    `k_steps` carry no probability instead of shortening the batch), and the random stream is a threefry key
+    (`random_seed`, split on every call, or `key=`) instead of Python's `random`.  `obs` comes out as [B, 1, obs_dim],
+    the window's first observation -- all the losses read."""
+
+    def __init__(self, capacity, max_steps, obs_dim=None, num_actions=None, random_seed=None, device=None,
+                 transition_class=Transition):
+        self._capacity, self._max_steps = int(capacity), int(max_steps)
+        if self._capacity <= 0 or not 0 < self._max_steps < 2 ** 31:
+            raise ValueError("capacity and max_steps must be positive (max_steps below 2^31)")
+        self.obs_dim = None if obs_dim is None else int(obs_dim)
+        self.num_actions = None if num_actions is None else int(num_actions)
+        self.transition_class = transition_class
+        self._device = None if device is None else torch.device(device)
+        seed = int.from_bytes(os.urandom(4), "little") if random_seed is None else random_seed
+        self._key = prng.PRNGKey(seed)
+        self._arena = self._t = None
+        self._serial = 0
+        self.clear()
+
+    # ------------------------------------------------------------------ bookkeeping (host)
+    @property
+    def capacity(self):
+        return self._capacity
+
+    @property
+    def max_steps(self):
+        return self._max_steps
+
+    @property
+    def steps(self):
+        """Transitions held."""
+        return self._steps
+
+    @property
+    def serials(self):
+        """Serial numbers of the episodes held, oldest first."""
+        return [e.serial for e in self._eps]
+
+    def episode(self, serial):
+        """The stored episode with that serial as a Transition of views [T, ...] into the arenas (w: float64)."""
+        for e in self._eps:
+            if e.serial == serial:
+                rows = slice(e.start, e.start + e.length)
+                return self.transition_class(**{n: self._t[n][rows] for n in ("obs", "a", "r", "done", "Rn", "v", "pi", "w")})
+        raise KeyError(f"no episode with serial {serial} in the buffer")
+
+    def clear(self):
+        self._eps = deque()
+        self._head = self._tail = self._steps = 0
+        self._dirty, self._table_k, self._eligible = True, None, False
+
+    def __len__(self):
+        return len(self._eps)
+
+    def __bool__(self):
+        return bool(self._eps)
+
+    def _evict(self):
+        e = self._eps.popleft()
+        self._steps -= e.length
+        self._head = (self._head + 1) % self._capacity
+
+    def _place_all(self, lengths):
+        """[(first transition in the stream, _Episode)] for consecutive episodes of a stream."""
+        for T in lengths:
+            if T > self._max_steps:
+                raise ValueError(f"an episode of {T} steps does not fit max_steps = {self._max_steps}")
+        placed, src = [], 0
+        for T in lengths:
+            placed.append((src, self._place(T)))
+            src += T
+        return placed
+
+    def _place(self, T):
+        """Make room for an episode of T transitions and enter it."""
+        while len(self._eps) >= self._capacity:
+            self._evict()
+        while True:
+            if not self._eps:
+                dst = 0
+                break
+            lo = self._eps[0].start
+            if lo < self._tail:  # the episodes are one stretch [lo, tail): room after it, or before it from row 0
+                if self._tail + T <= self._max_steps:
+                    dst = self._tail
+                    break
+                if T <= lo:
+                    dst = 0
+                    break
+            elif self._tail + T <= lo:  # wrapped: [lo, end) and [0, tail), room in between
+                dst = self._tail
+                break
+            self._evict()
+        slot = (self._head + len(self._eps)) % self._capacity
+        self._eps.append(_Episode(slot, dst, T, self._serial))
+        self._serial += 1
+        self._tail = dst + T
+        self._steps += T
+        self._dirty = True
+        return self._eps[-1]
+
+    # ------------------------------------------------------------------ device side
+    def _alloc(self, obs_dim, num_actions):
+        if not torch.cuda.is_available():
+            raise RuntimeError("muax_amd needs a ROCm GPU (gfx950); there is no CPU fallback")
+        if self._device is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+        self.obs_dim = int(obs_dim) if self.obs_dim is None else self.obs_dim
+        self.num_actions = int(num_actions) if self.num_actions is None else self.num_actions
+        self._L = _lib.load()
+        dev, S = self._device, self._max_steps
+        shapes = {"obs": (S, self.obs_dim), "pi": (S, self.num_actions)}
+        self._t = {n: torch.zeros(shapes.get(n, (S,)), dtype=dt, device=dev) for n, dt in _ARENA_FIELDS}
+        self._t.update({n: torch.zeros(self._capacity, dtype=dt, device=dev) for n, dt in _TABLE_FIELDS})
+        ar = _lib.MzsReplayArena()
+        ar.struct_size = C.sizeof(_lib.MzsReplayArena)
+        ar.device = dev.index if dev.index is not None else torch.cuda.current_device()
+        ar.max_steps, ar.capacity, ar.obs_dim, ar.num_actions = S, self._capacity, self.obs_dim, self.num_actions
+        for n, x in self._t.items():
+            setattr(ar, n, x.data_ptr())
+        self._arena = ar
+
+    def _stream(self):
+        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+        idx = self._arena.device
+        return C.c_void_p(raw(idx) if raw is not None else torch.cuda.current_stream(self._device).cuda_stream)
+
+    def _check_dims(self, obs_dim, num_actions):
+        if self._arena is None:
+            self._alloc(obs_dim, num_actions)
+        if obs_dim != self.obs_dim or num_actions != self.num_actions:
+            raise ValueError(f"episode has obs_dim {obs_dim}, {num_actions} actions; the buffer holds "
+                             f"obs_dim {self.obs_dim}, {self.num_actions} actions")
+
+    def _store(self, placed, host, device, raw=False, n=0, alpha=None, weight_mode=0, stream_steps=0):
+        """One upload (the arrays of `host`, by name, in one staging buffer) and one launch.  `placed`:
+        [(first transition in the stream, _Episode)] of the episodes that are still held; `device`: fields that
+        already are device tensors."""
+        live = {e.serial for e in self._eps}
+        placed = [(src, e) for src, e in placed if e.serial in live]
+        if not placed:
+            return
+        desc = np.array([[src, e.start, e.length, e.slot] for src, e in placed], np.int32)
+        host = dict(host, serial=np.array([e.serial for _, e in placed], np.int64), desc=desc)
+        # widest element type first, every block starting on a multiple of 16 bytes
+        names = sorted(host, key=lambda k: -host[k].dtype.itemsize)
+        offs, total = {}, 0
+        for k in names:
+            offs[k] = total
+            total += -(-host[k].nbytes // 16) * 16
+        stage = np.empty(total, np.uint8)
+        for k in names:
+            stage[offs[k]:offs[k] + host[k].nbytes] = host[k].reshape(-1).view(np.uint8)
+        dstage = torch.from_numpy(stage).to(self._device)
+        base = dstage.data_ptr()
+        a = _lib.MzsReplayStoreArgs()
+        a.struct_size = C.sizeof(_lib.MzsReplayStoreArgs)
+        a.episodes, a.stream_steps = len(placed), stream_steps
+        a.raw, a.n_step, a.weight_mode = int(raw), int(n), weight_mode
+        a.has_alpha, a.alpha = int(alpha is not None), float(alpha if alpha is not None else 0.0)
+        a.desc_host = desc.ctypes.data
+        for k in names:
+            setattr(a, k, base + offs[k])
+        for k, x in device.items():
+            setattr(a, k, x.data_ptr())
+        _lib.check(self._L.mzs_replay_store(C.byref(self._arena), C.byref(a), self._stream()))
+        self._keep = (dstage, device)
+
+    def add(self, trajectory, w=1.):
+        """Store one finished episode (a `Trajectory`, array-backed or filled step by step) with the buffer weight `w`."""
+        self.add_many([trajectory], [w])
+
+    def add_many(self, trajectories, weights):
+        """`add` for a whole collection with one upload and one launch."""
+        cols = [_columns(t) for t in trajectories]
+        weights = [float(np.asarray(w).reshape(-1)[0]) for w in weights]
+        if len(cols) != len(weights):
+            raise ValueError("add_many: one weight per trajectory")
+        if not cols:
+            return
+        for c in cols:
+            self._check_dims(c[0].shape[1], c[6].shape[1])
+        placed = self._place_all([len(c[0]) for c in cols])
+        live = {e.serial for e in self._eps}
+        keep = [i for i, (_, e) in enumerate(placed) if e.serial in live]
+        # the stream holds the surviving episodes only (a collection larger than the buffer evicts its own head)
+        src, kept = 0, []
+        for i in keep:
+            kept.append((src, placed[i][1]))
+            src += placed[i][1].length
+        host = {k: np.concatenate([cols[i][j] for i in keep])
+                for j, k in enumerate(("obs", "a", "r", "Rn", "v", "done", "pi", "w"))}
+        host["ep_w"] = np.array([weights[i] for i in keep], np.float64)
+        self._store(kept, host, {}, stream_steps=src)
+
+    def add_raw(self, obs, a, r, v, pi, lengths, n, gamma, alpha=None, weight="mean"):
+        """Complete episodes as one flat stream (NumPy arrays or device tensors, [M, ...] with M = sum(lengths)):
+        the n-step returns, `done` and the priority weights of `vector.nstep_returns` / `episode_trajectory`
+        (w = |v - Rn| ** alpha, 1 when alpha is None) are computed on the device in fp64, in NumPy's operation
+        order; the buffer weight of an episode is the `weight` ("mean" or "sum") of its transition weights."""
+        if weight not in _WEIGHT_MODES:
+            raise ValueError("weight must be 'mean' or 'sum'")
+        lengths = [int(x) for x in np.asarray(lengths).reshape(-1)]
+        M = sum(lengths)
+        if not lengths or min(lengths) <= 0:
+            raise ValueError("add_raw: episode lengths must be positive")
+        if int(n) < 1:
+            raise ValueError("add_raw: n must be at least 1")
+        host, device = {}, {}
+        for k, x, np_dt, t_dt in (("obs", obs, np.float32, torch.float32), ("a", a, np.int32, torch.int32),
+                                  ("r", r, np.float64, torch.float64), ("v", v, np.float64, torch.float64),
+                                  ("pi", pi, np.float32, torch.float32)):
+            if len(x) != M:
+                raise ValueError(f"add_raw: {k} has {len(x)} rows, the lengths sum to {M}")
+            if isinstance(x, torch.Tensor):
+                if self._device is None:
+                    self._device = x.device
+                device[k] = x.to(device=self._device, dtype=t_dt).reshape(M, -1).contiguous()
+            else:
+                host[k] = np.ascontiguousarray(np.asarray(x).reshape(M, -1), dtype=np_dt)
+        dims = {**host, **device}
+        if dims["a"].shape[1] != 1 or dims["r"].shape[1] != 1 or dims["v"].shape[1] != 1:
+            raise ValueError("add_raw: a, r and v are one scalar per transition")
+        self._check_dims(dims["obs"].shape[1], dims["pi"].shape[1])
+        placed = self._place_all(lengths)
+        host["gpow"] = np.array([float(gamma) ** i for i in range(int(n) + 1)], np.float64)
+        self._store(placed, host, device, raw=True, n=n, alpha=alpha, weight_mode=_WEIGHT_MODES[weight], stream_steps=M)
+
+    def sample(self, batch_size=32, num_trajectory: int = None, k_steps: int = 5, sample_per_trajectory: int = 1,
+               key=None, with_indices: bool = False):
+        """A batch of `num_trajectory * sample_per_trajectory` windows of `k_steps` transitions (the arguments of
+        muax/replay_buffer.py:192-240; `batch_size` alone means that many trajectories, one window each) as a
+        Transition of device tensors: obs [B, 1, obs_dim], a [B, k] int32, r / Rn / v / w [B, k] float32, done
+        [B, k] bool, pi [B, k, A] float32.  Episodes are drawn with their buffer weights, the start inside an
+        episode with the transition weights, the rows of one trajectory sharing their episode.  The batch size is
+        fixed: an episode no longer than `k_steps` is never drawn (the reference returns a shorter batch).
+        `key`: an int seed or two uint32 words fix the draws; default: the buffer's own key, split on every call.
+        `with_indices=True` returns (batch, (episode serial [B] int64, start [B] int32))."""
+        if batch_size is None and num_trajectory is None:
+            raise ValueError("Either num_trajectory or batch_size need to be given.")
+        elif batch_size is not None and num_trajectory is None:
+            num_trajectory, sample_per_trajectory = batch_size, 1
+        if not self._eps:
+            raise ValueError("cannot sample from an empty buffer")
+        k, spt = int(k_steps), int(sample_per_trajectory)
+        B = int(num_trajectory) * spt
+        stream = self._stream()
+        if self._dirty or self._table_k != k:
+            self._eligible = any(e.length > k for e in self._eps)
+            _lib.check(self._L.mzs_replay_refresh(C.byref(self._arena), self._head, len(self._eps), k, stream))
+            self._dirty, self._table_k = False, k
+        if not self._eligible:
+            raise ValueError(f"no episode in the buffer is longer than k_steps = {k}")
+        if key is None:
+            self._key, key = prng.split(self._key)
+        else:
+            key = prng.as_key(key)
+        dev, f32 = self._device, torch.float32
+        obs = torch.empty((B, 1, self.obs_dim), dtype=f32, device=dev)
+        a = torch.empty((B, k), dtype=torch.int32, device=dev)
+        r, Rn, v, w = (torch.empty((B, k), dtype=f32, device=dev) for _ in range(4))
+        done = torch.empty((B, k), dtype=torch.bool, device=dev)
+        pi = torch.empty((B, k, self.num_actions), dtype=f32, device=dev)
+        serial = torch.empty(B, dtype=torch.int64, device=dev)
+        start = torch.empty(B, dtype=torch.int32, device=dev)
+        s = _lib.MzsReplaySampleArgs()
+        s.struct_size = C.sizeof(_lib.MzsReplaySampleArgs)
+        s.count, s.batch, s.k_steps, s.sample_per_trajectory = len(self._eps), B, k, spt
+        s.key[0], s.key[1] = int(key[0]), int(key[1])
+        s.obs, s.a, s.r, s.Rn, s.v, s.done = (x.data_ptr() for x in (obs, a, r, Rn, v, done))
+        s.pi, s.w, s.serial, s.start = pi.data_ptr(), w.data_ptr(), serial.data_ptr(), start.data_ptr()
+        _lib.check(self._L.mzs_replay_sample(C.byref(self._arena), C.byref(s), stream))
+        batch = self.transition_class(obs=obs, a=a, r=r, done=done, Rn=Rn, v=v, pi=pi, w=w)
+        return (batch, (serial, start)) if with_indices else batch

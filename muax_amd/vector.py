@@ -176,9 +176,13 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
         t0 = time.perf_counter()
         trajs, key, env_steps = collector.collect(model, key, steps_per_iteration, num_simulations, temperature)
         collect_s = time.perf_counter() - t0
-        for tr in trajs:
-            if len(tr) >= k_steps:
-                buffer.add(tr, tr.weights.mean() if trajectory_weight == "mean" else tr.weights.sum())
+        keep = [tr for tr in trajs if len(tr) >= k_steps]
+        weights = [tr.weights.mean() if trajectory_weight == "mean" else tr.weights.sum() for tr in keep]
+        if hasattr(buffer, "add_many"):  # (the device buffer: one upload and one launch for the collection)
+            buffer.add_many(keep, weights)
+        else:
+            for tr, w in zip(keep, weights):
+                buffer.add(tr, w)
         row = {"iteration": it, "env_steps": env_steps, "episodes": len(trajs), "collect_s": collect_s,
                "G": float(np.mean([float(np.sum(t.rewards)) for t in trajs])) if trajs else float("nan")}
         if len(buffer):

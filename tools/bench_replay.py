@@ -1,0 +1,96 @@
+"""Replay sampling beside the training step: `TrajectoryReplayBuffer.sample` + `update()` (host lists and NumPy
+slices, five uploads per batch) against `DeviceReplayBuffer.sample` + `update()` (one launch, the batch read in place),
+and each `sample` on its own.  Default MLP trio on CartPole shapes, 500 stored episodes of about 200 steps.
+
+    python tools/bench_replay.py [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
+
+Every figure is the median of `--iters` iterations, each ending in a device synchronise, after 30 ms of untimed
+iterations of the same work (clocks settled).  The two routes alternate shape by shape in one process."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import muax_amd as mx  # noqa: E402
+from muax_amd.utils import warm_runtime  # noqa: E402
+
+A, E, OBS, SUPPORT = 2, 8, 4, 10
+
+
+def median_ms(fn, iters, settle_ms=30.0):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    while (time.perf_counter() - t0) * 1e3 < settle_ms:
+        fn()
+        torch.cuda.synchronize()
+    out = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(out))
+
+
+def model():
+    g = torch.Generator().manual_seed(0)
+    net = mx.nn.MZNetwork(mx.nn.Representation(E, generator=g), mx.nn.Prediction(A, 2 * SUPPORT + 1, generator=g),
+                          mx.nn.Dynamic(E, A, 2 * SUPPORT + 1, generator=g))
+    m = mx.MuZero(net, support_size=SUPPORT)
+    m.init(0, np.zeros((1, OBS)))
+    return m
+
+
+def episodes(n, rng):
+    out = []
+    for T in rng.integers(150, 251, n):
+        w = np.abs(rng.standard_normal(T)) ** 0.5
+        out.append(mx.Trajectory.from_arrays(rng.uniform(-1, 1, (T, OBS)).astype(np.float32), rng.integers(0, A, T),
+                                             np.ones(T), rng.uniform(size=T) < 0.05, rng.uniform(0, 20, T),
+                                             rng.uniform(0, 20, T), rng.dirichlet(np.ones(A), T).astype(np.float32)[:, None],
+                                             w))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--episodes", type=int, default=500)
+    ap.add_argument("--shape", action="append", default=[], metavar="NUM_TRAJECTORY,K")
+    a = ap.parse_args()
+    shapes = [tuple(int(x) for x in s.split(",")) for s in a.shape] or [(32, 10), (4096, 10)]
+    warm_runtime()
+    eps = episodes(a.episodes, np.random.default_rng(0))
+    host = mx.TrajectoryReplayBuffer(a.episodes, random_seed=0)
+    dev = mx.DeviceReplayBuffer(a.episodes, sum(len(t) for t in eps), random_seed=0)
+    for t in eps:
+        host.add(t, t.weights.mean())
+    t0 = time.perf_counter()
+    dev.add_many(eps, [t.weights.mean() for t in eps])
+    torch.cuda.synchronize()
+    print(f"{a.episodes} episodes, {dev.steps} transitions; add_many: {(time.perf_counter() - t0) * 1e3:.1f} ms "
+          f"(one upload, one launch); median of {a.iters} synchronised iterations, ms")
+    print(f"{'num_trajectory x k':>18} | {'host sample':>11} {'host s+upd':>10} | {'dev sample':>10} {'dev s+upd':>9} | "
+          f"{'update':>7} | {'s+upd host/dev':>14} {'sample host/dev':>15}")
+    for n, k in shapes:
+        m_host, m_dev = model(), model()
+        fixed = dev.sample(num_trajectory=n, k_steps=k)
+        res = {
+            "hs": median_ms(lambda: host.sample(num_trajectory=n, k_steps=k), a.iters),
+            "hu": median_ms(lambda: m_host.update(host.sample(num_trajectory=n, k_steps=k), backend="hip"), a.iters),
+            "ds": median_ms(lambda: dev.sample(num_trajectory=n, k_steps=k), a.iters),
+            "du": median_ms(lambda: m_dev.update(dev.sample(num_trajectory=n, k_steps=k), backend="hip"), a.iters),
+            "u": median_ms(lambda: m_dev.update(fixed, backend="hip"), a.iters),
+        }
+        print(f"{n:>13} x {k:<2} | {res['hs']:11.3f} {res['hu']:10.3f} | {res['ds']:10.3f} {res['du']:9.3f} | "
+              f"{res['u']:7.3f} | {res['hu'] / res['du']:13.1f}x {res['hs'] / res['ds']:14.1f}x", flush=True)
+
+
+if __name__ == "__main__":
+    main()
