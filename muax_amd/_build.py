@@ -1,7 +1,9 @@
 """Builds the HIP extension in-tree (muax_amd/lib/libmzsearch.so) for gfx950.
 
 The library is several translation units compiled in parallel (each `hipcc -c`, objects under muax_amd/lib/obj/)
-and linked into one shared object: the C-ABI and the step-wise / training / Dirichlet kernels (mz_api.hip), the
+and linked into one shared object: the C-ABI's handle and registries (mz_api.hip) and one unit per route -- the fused
+act() dispatch (mz_act.hip), the step-wise path and the generic one-launch search with the step kernels
+(mz_stepwise.hip), the training step (mz_train.hip), the self-test and Dirichlet kernels (mz_selftest.hip) --, the
 fused act() kernel instances in five groups (mz_fused_g*.hip, listed in mz_instances.def), the wide-action act()
 kernel (mz_wide.hip), the ResNet recurrent kernel (mz_conv.hip) and the device-resident replay (mz_replay.hip).  Only the units whose sources changed are recompiled."""
 from __future__ import annotations
@@ -17,10 +19,14 @@ OBJ_DIR = os.path.join(LIB_DIR, "obj")
 LIB_PATH = os.path.join(LIB_DIR, "libmzsearch.so")
 _ABI = os.path.join("..", "..", "include", "mzsearch.h")
 _FUSED = ["mz_fused_group.inc", "mz_fused_launch.h", "mz_fused.cuh", "mz_spec.cuh", "mz_instances.def", "mz_host.h", _ABI]
+_HANDLE = ["mz_handle.h", "mz_host.h", "mz_keys.h", "mz_step.cuh", "mz_step_jump.cuh", "mz_spec.cuh", _ABI]
 # translation unit -> the headers it is rebuilt for
 UNITS = {
-    "mz_api.hip": ["mz_host.h", "mz_fused_launch.h", "mz_fused.cuh", "mz_spec.cuh", "mz_step.cuh", "mz_step_jump.cuh",
-                   "mz_mlp_generic.cuh", "mz_train.cuh", "mz_dirichlet.cuh", "mz_wide_launch.h", _ABI],
+    "mz_api.hip": _HANDLE + ["mz_fused_launch.h", "mz_fused.cuh"],
+    "mz_act.hip": _HANDLE + ["mz_fused_launch.h", "mz_fused.cuh", "mz_wide_launch.h"],
+    "mz_stepwise.hip": _HANDLE + ["mz_mlp_generic.cuh"],
+    "mz_train.hip": ["mz_host.h", "mz_train_launch.h", "mz_train.cuh", "mz_spec.cuh", _ABI],
+    "mz_selftest.hip": ["mz_host.h", "mz_dirichlet.cuh", "mz_spec.cuh", _ABI],
     "mz_fused_g0.hip": _FUSED,
     "mz_fused_g1.hip": _FUSED,
     "mz_fused_g2.hip": _FUSED,

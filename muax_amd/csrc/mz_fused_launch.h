@@ -2,6 +2,7 @@
 // in parallel); each group exports one dispatcher.  Instances are listed in mz_instances.def.
 #pragma once
 #include <string>
+#include <vector>
 
 #include "mz_fused.cuh"
 
@@ -23,4 +24,7 @@ int fused_dispatch_g1(int mode, int device, const FusedParams& p, hipStream_t st
 int fused_dispatch_g2(int mode, int device, const FusedParams& p, hipStream_t stream, int A, int E, int F, int N, bool compact, std::string* err);
 int fused_dispatch_g3(int mode, int device, const FusedParams& p, hipStream_t stream, int A, int E, int F, int N, bool compact, std::string* err);
 int fused_dispatch_g4(int mode, int device, const FusedParams& p, hipStream_t stream, int A, int E, int F, int N, bool compact, std::string* err);
+// appends the instances built on demand that serve `mode` (mzs_register_fused_dispatch[_muzero]; the registry is in
+// mz_api.hip): the MuZero-policy-only ones first
+void jit_dispatchers(int mode, std::vector<FusedDispatch>* out);
 }  // namespace mz

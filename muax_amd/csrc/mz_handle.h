@@ -1,0 +1,56 @@
+// mz_handle.h -- the handle behind the C-ABI and the host helpers its routes share (not part of the ABI): mz_api.hip,
+// mz_act.hip, mz_stepwise.hip.  Every includer but mz_stepwise.hip defines MZ_NO_STEP_KERNELS first: the non-template
+// kernels of mz_step.cuh are emitted by that unit alone.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "mz_host.h"
+#include "mz_keys.h"
+#include "mz_step_jump.cuh"
+
+struct mzs_handle {
+  mzs_config cfg;
+  std::string err;
+  bool have_weights = false;
+  mzs_mlp_weights w;
+  mz::StepState step;  // device buffers of the step-wise path (lazily allocated)
+  uint32_t k_sample[2] = {0, 0};
+  std::vector<uint32_t> sim_keys;  // [num_simulations][2], sized at create: simulate_key of every simulation
+  uint64_t* prof = nullptr;        // MZ_PROFILE builds only
+  int32_t* fused_table = nullptr;  // gumbel policy, fused path: seq_halving table on the device
+  float* fused_emb = nullptr;      // fused path, embed_dim > 16: [B][S+1][E] embeddings in HBM
+  int32_t* fused_path = nullptr;   // fused path, instances with the root paths in HBM: [B][S+1][fused_path_words]
+  int fused_path_words = 0;
+  int cu_count = 0;
+  // mzs_act_mlp_host: pinned staging (in: obs | noise | invalid, out: action | weights | value) and their device twins
+  void* host_in = nullptr; void* host_out = nullptr; void* dev_noise = nullptr;  // dev_noise: [B, A] drawn root noise
+  size_t host_in_bytes = 0;
+  mz::JumpArgs jump = {nullptr, nullptr, nullptr, nullptr};  // step-wise path with cached decisions
+  void* jump_slab = nullptr;
+  bool use_jump = false;
+  int jump_roots = 0;              // roots the cached-decision slab holds: the batch (use_jump), or -- generic route of trees whose
+                                   // B N^2 path words exceed the budget -- the chunk of roots act() searches at a time
+  bool allow_generic = false;      // mzs_mlp_allow_generic: shapes without a fused instance take the generic one-launch search
+  float* gen_scratch = nullptr;    // generic route: prior logits [B, A] | embeddings [B, E] | actions [B]
+  bool allow_wide = false;         // mzs_mlp_allow_wide: 17..64 actions under the MuZero policy take the wide one-launch kernel
+  bool allow_wide_gumbel = false;  // mzs_mlp_allow_wide_gumbel: ... and under the Gumbel policy (a handle opts in separately)
+};
+
+namespace mzh {
+
+// the 18 weight pointers of the default MLP trio into a kernel argument block with the same member names
+template <class D>
+void copy_weights(const mzs_mlp_weights& w, D& d) {
+  d.repr_w = w.repr_w; d.repr_b = w.repr_b;
+  d.pv_w1 = w.pv_w1; d.pv_b1 = w.pv_b1; d.pv_w2 = w.pv_w2; d.pv_b2 = w.pv_b2;
+  d.pp_w1 = w.pp_w1; d.pp_b1 = w.pp_b1; d.pp_w2 = w.pp_w2; d.pp_b2 = w.pp_b2;
+  d.dr_w1 = w.dr_w1; d.dr_b1 = w.dr_b1; d.dr_w2 = w.dr_w2; d.dr_b2 = w.dr_b2;
+  d.dn_w1 = w.dn_w1; d.dn_b1 = w.dn_b1; d.dn_w2 = w.dn_w2; d.dn_b2 = w.dn_b2;
+}
+
+// act() of the default MLP trio on the step-wise tree with ONE search launch (mz_stepwise.hip): what mzs_act_mlp falls
+// back to, with mzs_mlp_allow_generic, for shapes no fused or wide instance serves
+int act_mlp_generic(mzs_handle* h, const mzs_act_args* a, void* stream);
+
+}  // namespace mzh

@@ -8,24 +8,28 @@
 
 #include "../../include/mzsearch.h"
 
+#define MZS_HIP(h, call)                                                                            \
+  do {                                                                                              \
+    hipError_t e_ = (call);                                                                         \
+    if (e_ != hipSuccess) return mzh::fail(h, MZS_E_RUNTIME, #call ": %s", hipGetErrorString(e_));  \
+  } while (0)
+
 namespace mz {
 struct StepArgs;
 struct JumpArgs;
 }  // namespace mz
 namespace mzh {
 // internals of a handle for the translation units that launch their own kernels on its step-wise tree (defined in
-// mz_api.hip): MZS_OK and the kernel argument blocks of the rooted tree with cached decisions, or an error (message set
-// on the handle) when the handle has no such tree
+// mz_stepwise.hip): MZS_OK and the kernel argument blocks of the rooted tree with cached decisions, or an error (message
+// set on the handle) when the handle has no such tree
 int step_view(mzs_handle* h, mz::StepArgs* sa, mz::JumpArgs* ja, int* policy, const char* who, int* device = nullptr);
-int fail_handle(mzs_handle* h, int code, const char* msg);
-// message of the last failure of an entry point that has no handle (mzs_last_error(NULL)); defined in mz_api.hip
-extern thread_local std::string g_create_error;
-inline int fail_global(int code, const char* fmt, const char* a = "") {
-  char buf[512];
-  snprintf(buf, sizeof buf, fmt, a);
-  g_create_error = buf;
-  return code;
-}
+// THE error helper: formats the message onto the handle, or -- h == nullptr, an entry point without one -- into the
+// thread's handle-less slot (mzs_last_error(NULL)), and returns `code`.  Defined in mz_api.hip
+int fail(mzs_handle* h, int code, const char* fmt, const char* a = "");
+// launcher of one training-step instance built on demand (mz_train_jit.hip; registered with mzs_register_train_dispatch,
+// kept in mz_api.hip): the instance for (A, E, F = 2 support + 1), or nullptr
+using JitTrainLaunch = int (*)(const void* train_params, void* stream, char* err, int errlen);
+JitTrainLaunch jit_train_instance(int A, int E, int F);
 // per-device record of what hipFuncSetAttribute(MaxDynamicSharedMemorySize) has already granted ONE kernel (one static
 // LdsGrant per kernel instance).  Atomic: host threads that race can at worst both set the attribute (idempotent);
 // device ordinals beyond the table are never recorded, so the attribute is then set on every call (no aliasing)
@@ -41,10 +45,18 @@ struct LdsGrant {
     }
   }
 };
+// `device` names a device this process can use, or the handle-less error is set: MZS_E_NODEVICE, then MZS_E_INVALID
+inline int check_device(int device, const char* who) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(nullptr, MZS_E_NODEVICE, "%s: no HIP device (this library has no CPU fallback)", who);
+  if (device < 0 || device >= ndev) return fail(nullptr, MZS_E_INVALID, "%s: bad device ordinal", who);
+  return MZS_OK;
+}
+// ... and makes it the calling thread's current device
+inline int select_device(int device, const char* who) {
+  if (int rc = check_device(device, who)) return rc;
+  MZS_HIP(nullptr, hipSetDevice(device));
+  return MZS_OK;
+}
 }  // namespace mzh
-
-#define MZS_HIPG(call)                                                                             \
-  do {                                                                                             \
-    hipError_t e_ = (call);                                                                        \
-    if (e_ != hipSuccess) return mzh::fail_global(MZS_E_RUNTIME, #call ": %s", hipGetErrorString(e_)); \
-  } while (0)

@@ -217,7 +217,7 @@ MZ_DEV void mlp_search_body(const StepArgs& s, const JumpArgs& g, const MlpGen& 
 // simulation 18.6 us at 1024 roots, 21.7 at 2048, 41.9 at 4096).  _occ4: the same body held to 128 registers (four
 // wavefronts per SIMD; ~25 loop invariants spilled to scratch) for launches of more roots than two wavefronts per SIMD
 // hold whose workgroups fit sixteen to a CU's LDS -- 1.2 - 1.3x there, slower everywhere else (the host chooses:
-// mz_api.hip, launch_mlp_search; both measured in profiles/r06_generic_notes.txt).
+// mz_stepwise.hip, launch_mlp_search; both measured in profiles/r06_generic_notes.txt).
 template <bool GUMBEL, int AS = 0, bool TBL = false>
 __global__ __launch_bounds__(64) void mz_mlp_search_kernel(const StepArgs s, const JumpArgs g, const MlpGen w, int sim_begin,
                                                            int sim_end) {

@@ -17,22 +17,18 @@ int64_t mzs_layernorm_workspace_bytes(int32_t batch, int32_t n) {
 
 int mzs_layernorm_act(const mzs_layernorm_args* a, void* stream_) {
   if (!a || a->struct_size != (int32_t)sizeof(mzs_layernorm_args))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_layernorm_act: null arguments or size mismatch (ABI)");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_layernorm_act: null arguments or size mismatch (ABI)");
   if (a->batch <= 0 || a->n <= 0 || a->channels <= 0)
-    return mzh::fail_global(MZS_E_INVALID, "mzs_layernorm_act: batch, n and channels must be positive");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_layernorm_act: batch, n and channels must be positive");
   if (a->n % 4 || a->channels % 4 || a->n % a->channels)
-    return mzh::fail_global(MZS_E_UNSUPPORTED, "mzs_layernorm_act: n and channels must be multiples of 4, n of channels");
+    return mzh::fail(nullptr, MZS_E_UNSUPPORTED, "mzs_layernorm_act: n and channels must be multiples of 4, n of channels");
   if (!a->x || !a->scale || !a->offset || !a->y || !a->workspace)
-    return mzh::fail_global(MZS_E_INVALID, "mzs_layernorm_act: null tensor pointer");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_layernorm_act: null tensor pointer");
   if (a->x2 && (!a->scale2 || !a->offset2))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_layernorm_act: the second tensor needs its scale and offset");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_layernorm_act: the second tensor needs its scale and offset");
   if (a->workspace_bytes < mzs_layernorm_workspace_bytes(a->batch, a->n))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_layernorm_act: workspace too small");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return mzh::fail_global(MZS_E_NODEVICE, "mzs_layernorm_act: no HIP device (this library has no CPU fallback)");
-  if (a->device < 0 || a->device >= ndev) return mzh::fail_global(MZS_E_INVALID, "mzs_layernorm_act: bad device ordinal");
-  MZS_HIPG(hipSetDevice(a->device));
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_layernorm_act: workspace too small");
+  if (int rc = mzh::select_device(a->device, "mzs_layernorm_act")) return rc;
   mz::NormParams p;
   memset(&p, 0, sizeof p);
   p.x = a->x; p.scale = a->scale; p.offset = a->offset;
@@ -47,7 +43,7 @@ int mzs_layernorm_act(const mzs_layernorm_args* a, void* stream_) {
   int slices = (a->n + per_block - 1) / per_block;
   if (slices > 65535) slices = 65535;  // (grid y; the kernel strides over the sample)
   hipLaunchKernelGGL(mz::ln_apply_kernel, dim3(a->batch, slices), dim3(mz::kNormThreads), 0, stream, p);
-  MZS_HIPG(hipGetLastError());
+  MZS_HIP(nullptr, hipGetLastError());
   return MZS_OK;
 }
 
@@ -68,23 +64,19 @@ int64_t mzs_resblock_workspace_bytes(int32_t batch, int32_t height, int32_t widt
 
 int mzs_resblock_v1(const mzs_resblock_args* a, void* stream_) {
   if (!a || a->struct_size != (int32_t)sizeof(mzs_resblock_args))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_resblock_v1: null arguments or size mismatch (ABI)");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_resblock_v1: null arguments or size mismatch (ABI)");
   if (a->batch <= 0 || a->height <= 0 || a->width <= 0 || !a->x || !a->w0 || !a->w1 || !a->y || !a->workspace)
-    return mzh::fail_global(MZS_E_INVALID, "mzs_resblock_v1: batch / height / width / pointers");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_resblock_v1: batch / height / width / pointers");
   if (!a->ln0_scale || !a->ln0_offset || !a->ln1_scale || !a->ln1_offset || (a->w_proj && (!a->proj_scale || !a->proj_offset)))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_resblock_v1: every LayerNorm needs its scale and offset");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_resblock_v1: every LayerNorm needs its scale and offset");
   if (a->channels != 32 && a->channels != 64)
-    return mzh::fail_global(MZS_E_UNSUPPORTED, "mzs_resblock_v1: channels must be 32 or 64 (in == out)");
+    return mzh::fail(nullptr, MZS_E_UNSUPPORTED, "mzs_resblock_v1: channels must be 32 or 64 (in == out)");
   if (a->workspace_bytes < mzs_resblock_workspace_bytes(a->batch, a->height, a->width, a->channels))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_resblock_v1: workspace too small");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return mzh::fail_global(MZS_E_NODEVICE, "mzs_resblock_v1: no HIP device (this library has no CPU fallback)");
-  if (a->device < 0 || a->device >= ndev) return mzh::fail_global(MZS_E_INVALID, "mzs_resblock_v1: bad device ordinal");
-  MZS_HIPG(hipSetDevice(a->device));
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_resblock_v1: workspace too small");
+  if (int rc = mzh::select_device(a->device, "mzs_resblock_v1")) return rc;
   const int C = a->channels, n1 = a->height * a->width * C;
   const mzr::Geometry g = mzr::geometry(a->height, a->width, C);
-  if (g.lds > 160 * 1024) return mzh::fail_global(MZS_E_UNSUPPORTED, "mzs_resblock_v1: image too wide for the LDS of a CU");
+  if (g.lds > 160 * 1024) return mzh::fail(nullptr, MZS_E_UNSUPPORTED, "mzs_resblock_v1: image too wide for the LDS of a CU");
   const size_t n = (size_t)a->batch * n1, bk2 = (size_t)a->batch * g.blocks * 2;
   float* c0 = static_cast<float*>(a->workspace);
   float* out = c0 + n;
@@ -117,7 +109,7 @@ int mzs_resblock_v1(const mzs_resblock_args* a, void* stream_) {
   int slices = (n1 + per_block - 1) / per_block;
   if (slices > 65535) slices = 65535;
   hipLaunchKernelGGL(mz::ln_apply_kernel, dim3(a->batch, slices), dim3(mz::kNormThreads), 0, stream, q);
-  MZS_HIPG(hipGetLastError());
+  MZS_HIP(nullptr, hipGetLastError());
   return MZS_OK;
 }
 
@@ -137,26 +129,22 @@ int64_t mzs_resblock_v2_workspace_bytes(int32_t batch, int32_t height, int32_t w
 
 int mzs_resblock_v2(const mzs_resblock_args* a, void* stream_) {
   if (!a || a->struct_size != (int32_t)sizeof(mzs_resblock_args))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_resblock_v2: null arguments or size mismatch (ABI)");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_resblock_v2: null arguments or size mismatch (ABI)");
   if (a->batch <= 0 || a->height <= 0 || a->width <= 0 || !a->x || !a->w0 || !a->w1 || !a->y || !a->workspace)
-    return mzh::fail_global(MZS_E_INVALID, "mzs_resblock_v2: batch / height / width / pointers");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_resblock_v2: batch / height / width / pointers");
   if (!a->ln0_scale || !a->ln0_offset || !a->ln1_scale || !a->ln1_offset)
-    return mzh::fail_global(MZS_E_INVALID, "mzs_resblock_v2: every LayerNorm needs its scale and offset");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_resblock_v2: every LayerNorm needs its scale and offset");
   if (a->w_proj || a->proj_scale || a->proj_offset)
-    return mzh::fail_global(MZS_E_UNSUPPORTED, "mzs_resblock_v2: identity shortcut only (the projection block is strided: single calls)");
+    return mzh::fail(nullptr, MZS_E_UNSUPPORTED, "mzs_resblock_v2: identity shortcut only (the projection block is strided: single calls)");
   if (a->channels != 16 && a->channels != 32 && a->channels != 64)
-    return mzh::fail_global(MZS_E_UNSUPPORTED, "mzs_resblock_v2: channels must be 16, 32 or 64 (in == out)");
-  if (a->y == a->x) return mzh::fail_global(MZS_E_INVALID, "mzs_resblock_v2: y must not alias x");
+    return mzh::fail(nullptr, MZS_E_UNSUPPORTED, "mzs_resblock_v2: channels must be 16, 32 or 64 (in == out)");
+  if (a->y == a->x) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_resblock_v2: y must not alias x");
   if (a->workspace_bytes < mzs_resblock_v2_workspace_bytes(a->batch, a->height, a->width, a->channels))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_resblock_v2: workspace too small");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return mzh::fail_global(MZS_E_NODEVICE, "mzs_resblock_v2: no HIP device (this library has no CPU fallback)");
-  if (a->device < 0 || a->device >= ndev) return mzh::fail_global(MZS_E_INVALID, "mzs_resblock_v2: bad device ordinal");
-  MZS_HIPG(hipSetDevice(a->device));
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_resblock_v2: workspace too small");
+  if (int rc = mzh::select_device(a->device, "mzs_resblock_v2")) return rc;
   const int C = a->channels, n1 = a->height * a->width * C;
   const mzr::Geometry g = mzr::geometry(a->height, a->width, C);
-  if (g.lds > 160 * 1024) return mzh::fail_global(MZS_E_UNSUPPORTED, "mzs_resblock_v2: image too wide for the LDS of a CU");
+  if (g.lds > 160 * 1024) return mzh::fail(nullptr, MZS_E_UNSUPPORTED, "mzs_resblock_v2: image too wide for the LDS of a CU");
   float* c0 = static_cast<float*>(a->workspace);
   double* m_x = reinterpret_cast<double*>(c0 + (size_t)a->batch * n1);  // [B][Kx][2]
   const int Kx = mz::norm_chunks(n1);
@@ -167,7 +155,7 @@ int mzs_resblock_v2(const mzs_resblock_args* a, void* stream_) {
   q.x = a->x; q.ws = m_x; q.B = a->batch; q.n = n1; q.C = C; q.K = Kx; q.eps = a->eps;
   q.chunk = ((n1 / 4 + Kx - 1) / Kx) * 4;
   hipLaunchKernelGGL(mz::ln_moments_kernel, dim3(a->batch, Kx, 1), dim3(mz::kNormThreads), 0, stream, q);
-  MZS_HIPG(hipGetLastError());
+  MZS_HIP(nullptr, hipGetLastError());
   mz::ReprConvParams p;
   memset(&p, 0, sizeof p);
   p.B = a->batch; p.H = a->height; p.W = a->width; p.eps = a->eps;

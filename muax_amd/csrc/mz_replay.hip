@@ -9,17 +9,14 @@ namespace {
 
 int check_arena(const mzs_replay_arena* ar, const char* who, mz::ReplayArena* out) {
   if (!ar || ar->struct_size != (int32_t)sizeof(mzs_replay_arena))
-    return mzh::fail_global(MZS_E_INVALID, "%s: null arena or size mismatch (ABI)", who);
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: null arena or size mismatch (ABI)", who);
   if (ar->max_steps <= 0 || ar->max_steps >= ((int64_t)1 << 31) || ar->capacity <= 0 || ar->obs_dim <= 0 ||
       ar->num_actions <= 0)
-    return mzh::fail_global(MZS_E_INVALID, "%s: max_steps (< 2^31), capacity, obs_dim and num_actions must be positive", who);
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: max_steps (< 2^31), capacity, obs_dim and num_actions must be positive", who);
   if (!ar->obs || !ar->a || !ar->r || !ar->Rn || !ar->v || !ar->done || !ar->pi || !ar->w || !ar->cw || !ar->t_start ||
       !ar->t_len || !ar->t_w || !ar->t_serial || !ar->c_start || !ar->c_len || !ar->c_CW || !ar->c_serial)
-    return mzh::fail_global(MZS_E_INVALID, "%s: null arena pointer", who);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return mzh::fail_global(MZS_E_NODEVICE, "%s: no HIP device (this library has no CPU fallback)", who);
-  if (ar->device < 0 || ar->device >= ndev) return mzh::fail_global(MZS_E_INVALID, "%s: bad device ordinal", who);
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: null arena pointer", who);
+  if (int rc = mzh::check_device(ar->device, who)) return rc;  // (selected after the entry point's own checks)
   out->max_steps = ar->max_steps; out->capacity = ar->capacity; out->obs_dim = ar->obs_dim; out->A = ar->num_actions;
   out->obs = ar->obs; out->a = ar->a; out->r = ar->r; out->Rn = ar->Rn; out->v = ar->v; out->done = ar->done;
   out->pi = ar->pi; out->w = ar->w; out->cw = ar->cw;
@@ -38,26 +35,26 @@ int mzs_replay_store(const mzs_replay_arena* arena, const mzs_replay_store_args*
   mz::ReplayStoreArgs p{};
   if (int rc = check_arena(arena, "mzs_replay_store", &p.ar)) return rc;
   if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_store_args))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_replay_store: null arguments or size mismatch (ABI)");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: null arguments or size mismatch (ABI)");
   if (a->episodes <= 0 || a->episodes > arena->capacity || a->stream_steps <= 0 || a->stream_steps >= ((int64_t)1 << 31))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_replay_store: episodes must be 1..capacity, stream_steps 1..2^31 - 1");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: episodes must be 1..capacity, stream_steps 1..2^31 - 1");
   if (!a->desc_host || !a->desc || !a->serial || !a->obs || !a->a || !a->pi || !a->r || !a->v)
-    return mzh::fail_global(MZS_E_INVALID, "mzs_replay_store: null pointer");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: null pointer");
   if (a->weight_mode < 0 || a->weight_mode > 2 || (a->weight_mode == 0 && !a->ep_w))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_replay_store: weight_mode must be 0 (with ep_w), 1 or 2");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: weight_mode must be 0 (with ep_w), 1 or 2");
   if (a->raw) {
-    if (a->n_step <= 0 || !a->gpow) return mzh::fail_global(MZS_E_INVALID, "mzs_replay_store: raw needs n_step >= 1 and gpow");
+    if (a->n_step <= 0 || !a->gpow) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: raw needs n_step >= 1 and gpow");
   } else if (!a->Rn || !a->done || !a->w || a->weight_mode != 0) {
-    return mzh::fail_global(MZS_E_INVALID, "mzs_replay_store: without raw, Rn, done, w and ep_w must be given");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: without raw, Rn, done, w and ep_w must be given");
   }
   for (int e = 0; e < a->episodes; ++e) {
     const int32_t* d = a->desc_host + 4 * e;
     const int64_t src = d[0], dst = d[1], len = d[2];
     if (len <= 0 || src < 0 || src + len > a->stream_steps || dst < 0 || dst + len > arena->max_steps || d[3] < 0 ||
         d[3] >= arena->capacity)
-      return mzh::fail_global(MZS_E_INVALID, "mzs_replay_store: an episode's range leaves the stream, the arena or the table");
+      return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: an episode's range leaves the stream, the arena or the table");
   }
-  MZS_HIPG(hipSetDevice(arena->device));
+  MZS_HIP(nullptr, hipSetDevice(arena->device));
   p.episodes = a->episodes; p.raw = a->raw ? 1 : 0; p.n_step = a->n_step; p.weight_mode = a->weight_mode;
   p.has_alpha = a->has_alpha ? 1 : 0; p.alpha = a->alpha;
   p.desc = a->desc; p.serial = (const long long*)a->serial; p.ep_w = a->ep_w; p.gpow = a->gpow;
@@ -67,7 +64,7 @@ int mzs_replay_store(const mzs_replay_arena* arena, const mzs_replay_store_args*
   p.Rn = a->Rn; p.done = a->done; p.w = a->w;
   hipLaunchKernelGGL(mz::replay_store_kernel, dim3(waves_grid(a->episodes)), dim3(64 * mz::kReplayWaves), 0,
                      static_cast<hipStream_t>(stream_), p);
-  MZS_HIPG(hipGetLastError());
+  MZS_HIP(nullptr, hipGetLastError());
   return MZS_OK;
 }
 
@@ -75,11 +72,11 @@ int mzs_replay_refresh(const mzs_replay_arena* arena, int32_t head, int32_t coun
   mz::ReplayArena ar{};
   if (int rc = check_arena(arena, "mzs_replay_refresh", &ar)) return rc;
   if (count <= 0 || count > arena->capacity || head < 0 || head >= arena->capacity || k_steps <= 0)
-    return mzh::fail_global(MZS_E_INVALID, "mzs_replay_refresh: head in 0..capacity - 1, count in 1..capacity, k_steps >= 1");
-  MZS_HIPG(hipSetDevice(arena->device));
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_refresh: head in 0..capacity - 1, count in 1..capacity, k_steps >= 1");
+  MZS_HIP(nullptr, hipSetDevice(arena->device));
   hipLaunchKernelGGL(mz::replay_refresh_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream_), ar, (int)head,
                      (int)count, (int)k_steps);
-  MZS_HIPG(hipGetLastError());
+  MZS_HIP(nullptr, hipGetLastError());
   return MZS_OK;
 }
 
@@ -87,21 +84,21 @@ int mzs_replay_sample(const mzs_replay_arena* arena, const mzs_replay_sample_arg
   mz::ReplaySampleArgs p{};
   if (int rc = check_arena(arena, "mzs_replay_sample", &p.ar)) return rc;
   if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_sample_args))
-    return mzh::fail_global(MZS_E_INVALID, "mzs_replay_sample: null arguments or size mismatch (ABI)");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample: null arguments or size mismatch (ABI)");
   if (a->count <= 0 || a->count > arena->capacity || a->batch <= 0 || a->k_steps <= 0 || a->sample_per_trajectory <= 0)
-    return mzh::fail_global(MZS_E_INVALID, "mzs_replay_sample: count in 1..capacity; batch, k_steps, sample_per_trajectory >= 1");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample: count in 1..capacity; batch, k_steps, sample_per_trajectory >= 1");
   if ((int64_t)a->k_steps * arena->num_actions >= ((int64_t)1 << 31) || a->k_steps >= arena->max_steps)
-    return mzh::fail_global(MZS_E_INVALID, "mzs_replay_sample: k_steps too large");
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample: k_steps too large");
   if (!a->obs || !a->a || !a->r || !a->Rn || !a->v || !a->done || !a->pi || !a->w || !a->serial || !a->start)
-    return mzh::fail_global(MZS_E_INVALID, "mzs_replay_sample: null output pointer");
-  MZS_HIPG(hipSetDevice(arena->device));
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample: null output pointer");
+  MZS_HIP(nullptr, hipSetDevice(arena->device));
   p.count = a->count; p.B = a->batch; p.k = a->k_steps; p.spt = a->sample_per_trajectory;
   p.key0 = a->key[0]; p.key1 = a->key[1];
   p.obs = a->obs; p.a = a->a; p.r = a->r; p.Rn = a->Rn; p.v = a->v; p.done = a->done; p.pi = a->pi; p.w = a->w;
   p.serial = (long long*)a->serial; p.start = a->start;
   hipLaunchKernelGGL(mz::replay_sample_kernel, dim3(waves_grid(a->batch)), dim3(64 * mz::kReplayWaves), 0,
                      static_cast<hipStream_t>(stream_), p);
-  MZS_HIPG(hipGetLastError());
+  MZS_HIP(nullptr, hipGetLastError());
   return MZS_OK;
 }
 

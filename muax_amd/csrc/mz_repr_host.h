@@ -46,9 +46,9 @@ template <int C, int TPW, int NW, bool LNIN, bool MOM, int CIN = C, int STRIDE =
 int launch(const mz::ReprConvParams& p, int blocks, size_t lds, hipStream_t stream) {
   static mzh::LdsGrant granted;
   int dev = 0;
-  MZS_HIPG(hipGetDevice(&dev));
+  MZS_HIP(nullptr, hipGetDevice(&dev));
   if (!granted.covers(dev, lds)) {
-    MZS_HIPG(hipFuncSetAttribute(reinterpret_cast<const void*>(mz::mz_repr_conv3x3_kernel<C, TPW, NW, LNIN, MOM, CIN, STRIDE>),
+    MZS_HIP(nullptr, hipFuncSetAttribute(reinterpret_cast<const void*>(mz::mz_repr_conv3x3_kernel<C, TPW, NW, LNIN, MOM, CIN, STRIDE>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     granted.note(dev, lds);
   }
@@ -64,7 +64,7 @@ int launch(const mz::ReprConvParams& p, int blocks, size_t lds, hipStream_t stre
     if (p.y2) q.y2 = p.y2 + off;
     q.b0 = b0;
     hipLaunchKernelGGL((mz::mz_repr_conv3x3_kernel<C, TPW, NW, LNIN, MOM, CIN, STRIDE>), dim3(blocks, nb), dim3(256), lds, stream, q);
-    MZS_HIPG(hipGetLastError());
+    MZS_HIP(nullptr, hipGetLastError());
   }
   return MZS_OK;
 }

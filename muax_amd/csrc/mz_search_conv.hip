@@ -23,7 +23,7 @@
 
 #include <cstdlib>
 
-#define MZ_NO_STEP_KERNELS   // device functions and types of the step-wise path only: its kernels live in mz_api.hip,
+#define MZ_NO_STEP_KERNELS   // device functions and types of the step-wise path only: its kernels live in mz_stepwise.hip,
 #define MZ_NO_TOWER_KERNELS  // the recurrent kernel's in mz_conv.hip
 #include "mz_conv_host.h"
 #include "mz_step_jump.cuh"
@@ -321,18 +321,18 @@ int mzs_resnet_search(mzs_handle* h, const mzs_tower_args* a, float discount, in
   if (int rc = mzh::step_view(h, &sa, &ja, &policy, "mzs_resnet_search", &tree_device)) return rc;
   // the tree belongs to the handle's device; the nets' arrays are named by a->device -- one launch cannot serve two
   if (a && a->struct_size == (int32_t)sizeof(mzs_tower_args) && a->device != tree_device)
-    return mzh::fail_handle(h, MZS_E_INVALID, "mzs_resnet_search: the nets' device differs from the handle's");
+    return mzh::fail(h, MZS_E_INVALID, "mzs_resnet_search: the nets' device differs from the handle's");
   mz::TowerParams p;
-  if (int rc = tower_params_from_args(a, p, true)) return mzh::fail_handle(h, rc, mzs_last_error(nullptr));
-  if (!p.heads) return mzh::fail_handle(h, MZS_E_INVALID, "mzs_resnet_search: needs the heads (the whole recurrent_fn)");
+  if (int rc = tower_params_from_args(a, p, true)) return mzh::fail(h, rc, "%s", mzs_last_error(nullptr));
+  if (!p.heads) return mzh::fail(h, MZS_E_INVALID, "mzs_resnet_search: needs the heads (the whole recurrent_fn)");
   if (a->batch != sa.B || a->num_actions != sa.A || sa.E != mz::kTowerPix * mz::kTowerC)
-    return mzh::fail_handle(h, MZS_E_INVALID, "mzs_resnet_search: batch / num_actions / embedding (6x6x64) do not match the handle");
+    return mzh::fail(h, MZS_E_INVALID, "mzs_resnet_search: batch / num_actions / embedding (6x6x64) do not match the handle");
   if (sim_begin < 0 || sim_end > sa.S || sim_begin >= sim_end)
-    return mzh::fail_handle(h, MZS_E_INVALID, "mzs_resnet_search: simulation range");
+    return mzh::fail(h, MZS_E_INVALID, "mzs_resnet_search: simulation range");
   if (2 * a->blocks + 3 > mz::kPairMsgs)
-    return mzh::fail_handle(h, MZS_E_UNSUPPORTED, "mzs_resnet_search: too many blocks");
+    return mzh::fail(h, MZS_E_UNSUPPORTED, "mzs_resnet_search: too many blocks");
   size_t lds = sizeof(float) * (2 * (size_t)mz::kBufWords + mz::kHeadWords) + sizeof(int32_t) * 17 * ((size_t)sa.S + 2);  // (15 arrays of the tree step + the score table)
-  if (lds > 160 * 1024) return mzh::fail_handle(h, MZS_E_UNSUPPORTED, "mzs_resnet_search: num_simulations too large for the LDS of a CU");
+  if (lds > 160 * 1024) return mzh::fail(h, MZS_E_UNSUPPORTED, "mzs_resnet_search: num_simulations too large for the LDS of a CU");
   // the tree's statistics in LDS as well when they fit next to that (MuZero policy; MZS_SEARCH_LDS_TREE=0: A/B, tests)
   const size_t lds_tree = lds + sizeof(int32_t) * (5 * (size_t)sa.N * sa.A + 4 * (size_t)sa.N + 2 * mz::kTowerC * 16 + 2);  // (+ the heads' 1x1 weights, reward, value)
   const char* lt = getenv("MZS_SEARCH_LDS_TREE");
@@ -340,7 +340,7 @@ int mzs_resnet_search(mzs_handle* h, const mzs_tower_args* a, float discount, in
   const bool wide = sa.A > 16;  // (LDS-tree instances: one or two 16-lane slots of actions)
   if (ldstree) lds = lds_tree;
   if (sa.S + 1 > 4096 || sa.A > 255)
-    return mzh::fail_handle(h, MZS_E_UNSUPPORTED, "mzs_resnet_search: message T packs (node, action, node) as 12 + 8 + 12 bits");
+    return mzh::fail(h, MZS_E_UNSUPPORTED, "mzs_resnet_search: message T packs (node, action, node) as 12 + 8 + 12 bits");
   const mz::SearchLoop loop = {sim_begin, sim_end, discount};
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const bool gumbel = policy == 1;
@@ -348,8 +348,8 @@ int mzs_resnet_search(mzs_handle* h, const mzs_tower_args* a, float discount, in
   dim3 grid;
   if (a->pair_scratch) {
     const int64_t need = mzs_tower_pair_scratch_bytes(a->batch);
-    if (need == 0) return mzh::fail_handle(h, MZS_E_UNSUPPORTED, "mzs_resnet_search: pair mode needs batch <= 128");
-    if (a->pair_scratch_bytes < need) return mzh::fail_handle(h, MZS_E_INVALID, "mzs_resnet_search: pair_scratch too small");
+    if (need == 0) return mzh::fail(h, MZS_E_UNSUPPORTED, "mzs_resnet_search: pair mode needs batch <= 128");
+    if (a->pair_scratch_bytes < need) return mzh::fail(h, MZS_E_INVALID, "mzs_resnet_search: pair_scratch too small");
     p.pair_f = static_cast<float*>(a->pair_scratch);
     p.pair_u = reinterpret_cast<unsigned*>(p.pair_f + (size_t)a->batch * 4 * mz::kPairSlot * 2);  // (8-byte words)
     fn = gumbel ? reinterpret_cast<const void*>(mz::mz_resnet_search_kernel<true, true, false>)
@@ -370,13 +370,13 @@ int mzs_resnet_search(mzs_handle* h, const mzs_tower_args* a, float discount, in
     mzh::LdsGrant& have = granted[(gumbel ? 6 : (ldstree ? (wide ? 4 : 2) : 0)) + (a->pair_scratch ? 1 : 0)];
     if (!have.covers(a->device, lds)) {
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return mzh::fail_handle(h, MZS_E_RUNTIME, "mzs_resnet_search: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+        return mzh::fail(h, MZS_E_RUNTIME, "mzs_resnet_search: hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
       have.note(a->device, lds);
     }
   }
   void* args[] = {&p, &sa, &ja, const_cast<mz::SearchLoop*>(&loop)};
   if (hipLaunchKernel(fn, grid, dim3(256), args, lds, stream) != hipSuccess || hipGetLastError() != hipSuccess)
-    return mzh::fail_handle(h, MZS_E_RUNTIME, "mzs_resnet_search: launch failed");
+    return mzh::fail(h, MZS_E_RUNTIME, "mzs_resnet_search: launch failed");
   return MZS_OK;
 }
 

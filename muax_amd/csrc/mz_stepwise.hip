@@ -1,0 +1,399 @@
+// mz_stepwise.hip -- the routes on the HBM tree of mz_step.cuh, whose kernels THIS unit emits: the step-wise entry points
+// for plugin nets (mzs_root .. mzs_finish, mzs_tree_export) and the generic one-launch act() (mz_mlp_generic.cuh).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+
+#include "mz_handle.h"
+#include "mz_mlp_generic.cuh"
+
+using mzh::fail;
+
+// Small batches run one wavefront (4 roots) per workgroup: the tree of a root is then always walked from the
+// same XCD, all 8 L2s share the trees, and the dependent per-level loads hit L2 instead of HBM.
+static int step_block(int batch) { return batch >= 4096 ? 256 : 64; }
+static int step_grid(int batch) { const int per = step_block(batch) / 16; return (batch + per - 1) / per; }
+
+static void emb_xfer(const mz::StepArgs& sa, float* rows, int dir, hipStream_t stream) {
+  hipLaunchKernelGGL(mz::emb_xfer_kernel, dim3(sa.B, (sa.E + 1023) / 1024), dim3(256), 0, stream, sa, rows, dir);
+}
+
+// What roots a tree: the root inference's outputs and, by policy, the Dirichlet noise (MuZero) or the Gumbel noise -- null:
+// drawn from the key gk -- (Gumbel); the other policy's members are null / 0
+struct RootInputs {
+  const float *prior_logits, *value, *embedding;
+  const uint8_t* invalid_actions;
+  const float* dirichlet_noise;
+  float dirichlet_fraction;
+  const float* gumbel;
+  uint32_t gk[2];
+};
+// roots the trees of sa's rows by the handle's policy; `jump`: ... and their cached decisions (the slab holds these rows)
+static void launch_root(mzs_handle* h, const mz::StepArgs& sa, const RootInputs& in, bool jump, hipStream_t stream) {
+  const dim3 grid(step_grid(sa.B)), blk(step_block(sa.B));
+  const int gumbel = h->cfg.policy == 1;
+  hipLaunchKernelGGL(mz::step_root_kernel, grid, blk, 0, stream, sa, in.prior_logits, in.value, in.embedding, in.invalid_actions,
+                     in.dirichlet_noise, in.dirichlet_fraction, gumbel, in.gumbel, in.gk[0], in.gk[1]);
+  if (jump && gumbel) hipLaunchKernelGGL(mz::jump_root_kernel<true>, grid, blk, 0, stream, sa, h->jump);
+  else if (jump) hipLaunchKernelGGL(mz::jump_root_kernel<false>, grid, blk, 0, stream, sa, h->jump);
+}
+// the policy's action choice over sa's rows (gumbel: the MuZero policy's optional sampling noise; k_sample from the key walk)
+static void launch_finish(mzs_handle* h, const mz::StepArgs& sa, float temperature, const float* gumbel, int32_t* action_out,
+                          float* action_weights_out, float* search_value_out, int32_t* depth_sum_out, hipStream_t stream) {
+  const dim3 grid(step_grid(sa.B)), blk(step_block(sa.B));
+  if (h->cfg.policy == 1)
+    hipLaunchKernelGGL(mz::step_finish_gumbel_kernel, grid, blk, 0, stream, sa, action_out, action_weights_out,
+                       search_value_out, depth_sum_out);
+  else
+    hipLaunchKernelGGL(mz::step_finish_kernel, grid, blk, 0, stream, sa, temperature, gumbel, h->k_sample[0], h->k_sample[1],
+                       action_out, action_weights_out, search_value_out, depth_sum_out);
+}
+
+static int ensure_step_state(mzs_handle* h) {
+  const mzs_config& c = h->cfg;
+  if (h->step.allocated) return MZS_OK;
+  const int rows = c.policy == 1 ? c.max_num_considered_actions + 1 : 0;
+  const int table_words = rows * c.num_simulations;
+  hipError_t e = h->step.allocate(c.batch, c.num_simulations + 1, c.num_actions, c.embed_dim, table_words);
+  if (e != hipSuccess) return fail(h, MZS_E_RUNTIME, "tree allocation: %s", hipGetErrorString(e));
+  // cached-decision kernels (mz_step_jump.cuh): bounded tree, B N^2 path words within the slab budget (8 GiB of the
+  // 288 GB: 4096 roots x 300 simulations are 1.5 GB; MZS_JUMP_BUDGET_MB overrides); MZS_STEP_WALK=1 keeps the
+  // level-by-level kernels (A/B testing).  A tree beyond the budget gets a slab for a CHUNK of roots: the step-wise
+  // entry points then walk level by level (they address the whole batch), the generic one-launch search of mzs_act_mlp
+  // runs the batch chunk by chunk (roots never interact; muax/model.py:222-243 takes any num_simulations).
+  const size_t B = (size_t)c.batch, N = (size_t)c.num_simulations + 1;
+  const char* walk = getenv("MZS_STEP_WALK");
+  const char* mb = getenv("MZS_JUMP_BUDGET_MB");
+  const size_t budget = mb && atoll(mb) > 0 ? (size_t)atoll(mb) << 20 : (size_t)8 << 30;
+  const size_t per_root = (3 * N + N * N) * 4;
+  if (N <= (size_t)mz::kJumpMaxNodes && !(walk && walk[0] == '1')) {
+    const bool whole = B * per_root <= budget;
+    size_t roots = whole ? B : budget / per_root;
+    if (roots > B) roots = B;
+    if (roots >= 1 && hipMalloc(&h->jump_slab, roots * per_root) == hipSuccess) {
+      int32_t* w = static_cast<int32_t*>(h->jump_slab);
+      h->jump.jump_pa = w; h->jump.jump_lv = w + roots * N; h->jump.node_depth = w + 2 * roots * N;
+      h->jump.node_path = reinterpret_cast<uint32_t*>(w + 3 * roots * N);
+      h->use_jump = whole;
+      h->jump_roots = (int)roots;
+    }
+  }
+  if (table_words) {
+    const std::vector<int32_t> table = mzh::visit_table(c.max_num_considered_actions, c.num_simulations);
+    MZS_HIP(h, hipMemcpy(h->step.visit_table, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice));
+  }
+  return MZS_OK;
+}
+
+int mzh::step_view(mzs_handle* h, mz::StepArgs* sa, mz::JumpArgs* ja, int* policy, const char* who, int* device) {
+  if (!h) return MZS_E_INVALID;
+  if (!h->step.rooted) return fail(h, MZS_E_INVALID, "%s: call mzs_root first", who);
+  if (!h->use_jump) return fail(h, MZS_E_UNSUPPORTED, "%s: this handle's tree has no cached decisions (too large, or MZS_STEP_WALK=1)", who);
+  *sa = h->step.args(h->cfg);
+  *ja = h->jump;
+  *policy = h->cfg.policy;
+  if (device) *device = h->cfg.device;
+  return MZS_OK;
+}
+
+extern "C" {
+
+int mzs_root(mzs_handle* h, const float* prior_logits, const float* value, const float* embedding, const uint8_t* invalid_actions,
+             const float* dirichlet_noise, float dirichlet_fraction, const uint32_t key[2], void* stream_) {
+  if (!h) return MZS_E_INVALID;
+  if (!prior_logits || !value || !embedding) return fail(h, MZS_E_INVALID, "mzs_root: null input");
+  if (!dirichlet_noise && dirichlet_fraction != 0.0f)
+    return fail(h, MZS_E_INVALID, "mzs_root: dirichlet_fraction != 0 needs dirichlet_noise");
+  const mzs_config& c = h->cfg;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MZS_HIP(h, hipSetDevice(c.device));
+  if (c.policy != 0) return fail(h, MZS_E_INVALID, "mzs_root: this handle runs the gumbel policy; use mzs_root_gumbel");
+  if (int rc = ensure_step_state(h)) return rc;
+  uint32_t zero[2] = {0, 0};
+  mzh::derive_keys(key ? key : zero, h->cfg.num_simulations, h->k_sample, h->sim_keys.data());
+  if (c.tiebreak) {
+    // pageable source: the runtime stages it before the call returns, so the next act() may rewrite sim_keys
+    MZS_HIP(h, hipMemcpyAsync(h->step.sim_keys, h->sim_keys.data(), sizeof(uint32_t) * 2 * (size_t)c.num_simulations,
+                              hipMemcpyHostToDevice, stream));
+  }
+  mz::StepArgs sa = h->step.args(c);
+  if (sa.wide) MZS_HIP(h, hipMemsetAsync(sa.embeddings, 0, sizeof(float) * (size_t)sa.B * sa.N * sa.E, stream));
+  launch_root(h, sa, {prior_logits, value, embedding, invalid_actions, dirichlet_noise, dirichlet_fraction, nullptr, {0, 0}},
+              h->use_jump, stream);
+  if (sa.wide) emb_xfer(sa, const_cast<float*>(embedding), 1, stream);
+  MZS_HIP(h, hipGetLastError());
+  h->step.rooted = true;
+  return MZS_OK;
+}
+
+int mzs_root_gumbel(mzs_handle* h, const float* prior_logits, const float* value, const float* embedding,
+                    const uint8_t* invalid_actions, const float* gumbel, const uint32_t key[2], void* stream_) {
+  if (!h) return MZS_E_INVALID;
+  if (!prior_logits || !value || !embedding) return fail(h, MZS_E_INVALID, "mzs_root_gumbel: null input");
+  const mzs_config& c = h->cfg;
+  if (c.policy != 1) return fail(h, MZS_E_INVALID, "mzs_root_gumbel: handle was created with policy 0 (muzero)");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MZS_HIP(h, hipSetDevice(c.device));
+  if (int rc = ensure_step_state(h)) return rc;
+  // mctx gumbel_muzero_policy: rng_key, gumbel_rng = jax.random.split(rng_key)
+  uint32_t zero[2] = {0, 0}, gk[2];
+  mzh::h_split(key ? key : zero, 2, 1, gk);
+  mz::StepArgs sa = h->step.args(c);
+  if (sa.wide) MZS_HIP(h, hipMemsetAsync(sa.embeddings, 0, sizeof(float) * (size_t)sa.B * sa.N * sa.E, stream));
+  launch_root(h, sa, {prior_logits, value, embedding, invalid_actions, nullptr, 0.0f, gumbel, {gk[0], gk[1]}}, h->use_jump,
+              stream);
+  if (sa.wide) emb_xfer(sa, const_cast<float*>(embedding), 1, stream);
+  MZS_HIP(h, hipGetLastError());
+  h->step.rooted = true;
+  return MZS_OK;
+}
+
+int mzs_select(mzs_handle* h, int32_t sim, int32_t* action_out, float* parent_embedding_out, void* stream_) {
+  if (!h) return MZS_E_INVALID;
+  if (!h->step.rooted) return fail(h, MZS_E_INVALID, "mzs_select: call mzs_root first");
+  if (sim < 0 || sim >= h->cfg.num_simulations) return fail(h, MZS_E_INVALID, "mzs_select: sim out of range");
+  if (!action_out || !parent_embedding_out) return fail(h, MZS_E_INVALID, "mzs_select: null output");
+  const mzs_config& c = h->cfg;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MZS_HIP(h, hipSetDevice(c.device));
+  mz::StepArgs sa = h->step.args(c);
+  const dim3 grid(step_grid(c.batch)), blk(step_block(c.batch));
+  const bool gathers = h->use_jump && sa.wide;  // one workgroup per root: selection + the gather of the wide embedding row
+  if (gathers)
+    hipLaunchKernelGGL(mz::jump_select_kernel<true>, dim3(c.batch), dim3(256), 0, stream, sa, h->jump, sim, action_out,
+                       parent_embedding_out);
+  else if (h->use_jump)
+    hipLaunchKernelGGL(mz::jump_select_kernel<false>, grid, blk, 0, stream, sa, h->jump, sim, action_out, parent_embedding_out);
+  else if (c.policy == 1)
+    hipLaunchKernelGGL(mz::step_select_gumbel_kernel, grid, blk, 0, stream, sa, sim, action_out, parent_embedding_out);
+  else
+    hipLaunchKernelGGL(mz::step_select_kernel, grid, blk, 0, stream, sa, sim, action_out, parent_embedding_out);
+  if (sa.wide && !gathers) emb_xfer(sa, parent_embedding_out, 0, stream);
+  MZS_HIP(h, hipGetLastError());
+  return MZS_OK;
+}
+
+static int expand_backup_impl(mzs_handle* h, int32_t sim, const float* reward, const float* discount, const float* prior_logits,
+                              const float* value, const float* next_embedding, int32_t* next_action_out,
+                              float* next_parent_embedding_out, void* stream_, const char* who) {
+  if (!h) return MZS_E_INVALID;
+  if (!h->step.rooted) return fail(h, MZS_E_INVALID, "%s: call mzs_root first", who);
+  if (sim < 0 || sim >= h->cfg.num_simulations) return fail(h, MZS_E_INVALID, "%s: sim out of range", who);
+  if (!reward || !discount || !prior_logits || !value || !next_embedding)
+    return fail(h, MZS_E_INVALID, "%s: null input", who);
+  const mzs_config& c = h->cfg;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MZS_HIP(h, hipSetDevice(c.device));
+  mz::StepArgs sa = h->step.args(c);
+  const bool want_next = next_action_out != nullptr && sim + 1 < c.num_simulations;
+  if (h->use_jump) {
+    // small batches: 16 levels in flight per root; large ones: one wavefront per root keeps the launch small;
+    // few roots and long searches (deep paths): 64 levels in flight
+    const dim3 blk(c.batch <= 256 && c.num_simulations >= 64 ? 1024 : (c.batch <= 1024 ? 256 : 64));
+    const size_t lds = sizeof(int32_t) * 15 * ((size_t)c.num_simulations + 2);
+    if (c.policy == 1)
+      hipLaunchKernelGGL(mz::jump_expand_backup_kernel<true>, dim3(c.batch), blk, lds, stream, sa, h->jump, sim, reward,
+                         discount, prior_logits, value, next_embedding, next_action_out, next_parent_embedding_out);
+    else
+      hipLaunchKernelGGL(mz::jump_expand_backup_kernel<false>, dim3(c.batch), blk, lds, stream, sa, h->jump, sim, reward,
+                         discount, prior_logits, value, next_embedding, next_action_out, next_parent_embedding_out);
+  } else
+    hipLaunchKernelGGL(mz::step_expand_backup_kernel, dim3(step_grid(c.batch)), dim3(step_block(c.batch)), 0, stream, sa, sim,
+                       reward, discount, prior_logits, value, next_embedding);
+  if (sa.wide && !h->use_jump) emb_xfer(sa, const_cast<float*>(next_embedding), 1, stream);
+  MZS_HIP(h, hipGetLastError());
+  // the walking kernels (trees beyond the cached-decision budget, MZS_STEP_WALK=1) select in a launch of their own
+  if (want_next && !h->use_jump) return mzs_select(h, sim + 1, next_action_out, next_parent_embedding_out, stream_);
+  return MZS_OK;
+}
+
+int mzs_expand_backup(mzs_handle* h, int32_t sim, const float* reward, const float* discount, const float* prior_logits,
+                      const float* value, const float* next_embedding, void* stream_) {
+  return expand_backup_impl(h, sim, reward, discount, prior_logits, value, next_embedding, nullptr, nullptr, stream_,
+                            "mzs_expand_backup");
+}
+
+int mzs_expand_backup_select(mzs_handle* h, int32_t sim, const float* reward, const float* discount, const float* prior_logits,
+                             const float* value, const float* next_embedding, int32_t* next_action_out,
+                             float* next_parent_embedding_out, void* stream_) {
+  if (h && (!next_action_out || !next_parent_embedding_out))
+    return fail(h, MZS_E_INVALID, "mzs_expand_backup_select: null output");
+  return expand_backup_impl(h, sim, reward, discount, prior_logits, value, next_embedding, next_action_out,
+                            next_parent_embedding_out, stream_, "mzs_expand_backup_select");
+}
+
+int mzs_finish(mzs_handle* h, float temperature, const float* gumbel, int32_t* action_out,
+               float* action_weights_out, float* search_value_out, int32_t* depth_sum_out, void* stream_) {
+  if (!h) return MZS_E_INVALID;
+  if (!h->step.rooted) return fail(h, MZS_E_INVALID, "mzs_finish: call mzs_root first");
+  if (!action_out || !action_weights_out) return fail(h, MZS_E_INVALID, "mzs_finish: null output");
+  const mzs_config& c = h->cfg;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MZS_HIP(h, hipSetDevice(c.device));
+  launch_finish(h, h->step.args(c), temperature, gumbel, action_out, action_weights_out, search_value_out, depth_sum_out, stream);
+  MZS_HIP(h, hipGetLastError());
+  return MZS_OK;
+}
+
+int mzs_tree_export(mzs_handle* h, const mzs_tree_view* out, void* stream_) {
+  if (!h) return MZS_E_INVALID;
+  if (!h->step.rooted) return fail(h, MZS_E_INVALID, "mzs_tree_export: no step-wise tree (call mzs_root first)");
+  if (!out) return fail(h, MZS_E_INVALID, "mzs_tree_export: null view");
+  const void* const* tp = reinterpret_cast<const void* const*>(out);
+  for (int i = 0; i < 12; ++i)
+    if (!tp[i]) return fail(h, MZS_E_INVALID, "mzs_tree_export: tree view has a null array");
+  const mzs_config& c = h->cfg;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MZS_HIP(h, hipSetDevice(c.device));
+  const size_t BN = (size_t)c.batch * (c.num_simulations + 1);
+  const mz::StepState& s = h->step;
+#define CP(dst, src, n) MZS_HIP(h, hipMemcpyAsync(dst, src, (n) * 4, hipMemcpyDeviceToDevice, stream))
+  CP(out->node_visits, s.node_visits, BN); CP(out->raw_values, s.raw_values, BN);
+  CP(out->node_values, s.node_values, BN); CP(out->parents, s.parents, BN);
+  CP(out->action_from_parent, s.action_from_parent, BN);
+  CP(out->children_index, s.children_index, BN * c.num_actions);
+  CP(out->children_prior_logits, s.children_prior_logits, BN * c.num_actions);
+  CP(out->children_values, s.children_values, BN * c.num_actions);
+  CP(out->children_visits, s.children_visits, BN * c.num_actions);
+  CP(out->children_rewards, s.children_rewards, BN * c.num_actions);
+  CP(out->children_discounts, s.children_discounts, BN * c.num_actions);
+  CP(out->embeddings, s.embeddings, BN * c.embed_dim);
+#undef CP
+  return MZS_OK;
+}
+
+}  // extern "C"
+
+// the generic route's ONE search launch over `n` roots (round 6: MuZero-policy instances specialised on the 16-lane slots
+// the action count fills, with the pUCT table in LDS while it fits the workgroup's 64 KB)
+static void launch_mlp_search(const mzs_config& c, const mz::StepArgs& sa, const mz::JumpArgs& ja, const mz::MlpGen& g, int n,
+                              size_t lds_search, hipStream_t stream) {
+  const size_t lds_tbl = lds_search + sizeof(float) * 2 * ((size_t)sa.S + 2);
+  const bool tbl = sa.S + 2 <= 1030 && lds_tbl <= 64 * 1024;  // (Markstein's sequence is checked for every divisor up to 1030)
+  // the 128-register build (four wavefronts per SIMD, mz_mlp_generic.cuh) where it puts MORE roots on the chip: more roots
+  // than two wavefronts per SIMD hold, and workgroups small enough that sixteen share a CU's LDS
+  const size_t lds = (c.policy != 1 && tbl && sa.A <= 32) ? lds_tbl : lds_search;
+  const bool occ4 = n > 2 * 4 * 256 && 16 * lds <= 160 * 1024;
+#define MZ_GEN_LAUNCH(...)                                                                                            \
+  do {                                                                                                                \
+    if (occ4) hipLaunchKernelGGL((mz::mz_mlp_search_kernel_occ4<__VA_ARGS__>), dim3(n), dim3(64), lds, stream, sa, ja, g, 0, sa.S); \
+    else hipLaunchKernelGGL((mz::mz_mlp_search_kernel<__VA_ARGS__>), dim3(n), dim3(64), lds, stream, sa, ja, g, 0, sa.S);           \
+  } while (0)
+  if (c.policy == 1) MZ_GEN_LAUNCH(true);
+  else if (tbl && sa.A <= 16) MZ_GEN_LAUNCH(false, 1, true);
+  else if (tbl && sa.A <= 32) MZ_GEN_LAUNCH(false, 2, true);
+  else MZ_GEN_LAUNCH(false);
+#undef MZ_GEN_LAUNCH
+}
+// rows [rb, rb + n) of the step-wise tree as a batch of their own: every per-root array starts at row rb, the PRNG streams
+// stay those of the global root index (root_offset + rb)
+static mz::StepArgs slice_rows(mz::StepArgs s, size_t rb, int n) {
+  const size_t N = (size_t)s.N, A = (size_t)s.A, E = (size_t)s.E;
+  s.B = n;
+  s.root_offset += rb;
+  s.node_visits += rb * N; s.raw_values += rb * N; s.node_values += rb * N; s.parents += rb * N;
+  s.action_from_parent += rb * N; s.path += rb * N;
+  s.children_index += rb * N * A; s.children_prior_logits += rb * N * A; s.children_prior_probs += rb * N * A;
+  s.children_values += rb * N * A; s.children_visits += rb * N * A; s.children_rewards += rb * N * A;
+  s.children_discounts += rb * N * A; s.embeddings += rb * N * E;
+  s.root_invalid += rb * A; s.root_gumbel += rb * A;
+  s.sel_parent += rb; s.sel_action += rb; s.sel_depth += rb; s.depth_sum += rb; s.xfer_node += rb;
+  return s;
+}
+// The generic route for a tree whose B N^2 cached path words exceed the slab budget (4096 roots x 1000 simulations would
+// be 16 GB): the handle's slab holds `jump_roots` roots and the batch is searched in chunks of that many -- root /
+// select(0) / ONE search launch / finish per chunk on the caller's stream, the slab reused chunk after chunk (stream order),
+// the tree arrays those of the whole batch (an export copies them as ever).  Same kernels, same per-root PRNG streams
+// (root_offset + row), hence the same bits as the undivided launch.
+static int act_mlp_generic_chunks(mzs_handle* h, const mzs_act_args* a, const mz::MlpGen& g, float* pl, float* emb,
+                                  int32_t* act0, size_t lds_search, hipStream_t stream) {
+  const mzs_config& c = h->cfg;
+  const size_t A = (size_t)c.num_actions, E = (size_t)c.embed_dim;
+  uint32_t gk[2] = {0, 0};
+  if (c.policy == 1) {
+    mzh::h_split(a->key, 2, 1, gk);  // mctx gumbel_muzero_policy: rng_key, gumbel_rng = split(rng_key)
+  } else {
+    mzh::derive_keys(a->key, h->cfg.num_simulations, h->k_sample, h->sim_keys.data());
+    if (c.tiebreak)
+      MZS_HIP(h, hipMemcpyAsync(h->step.sim_keys, h->sim_keys.data(), sizeof(uint32_t) * 2 * (size_t)c.num_simulations,
+                                hipMemcpyHostToDevice, stream));
+  }
+  const mz::StepArgs whole = h->step.args(c);
+  const bool gum = c.policy == 1;
+  for (size_t rb = 0; rb < (size_t)c.batch; rb += (size_t)h->jump_roots) {
+    const int n = (int)std::min((size_t)h->jump_roots, (size_t)c.batch - rb);
+    const mz::StepArgs sa = slice_rows(whole, rb, n);
+    auto rows = [&](auto* p, size_t stride) { return p ? p + rb * stride : nullptr; };  // row rb of an optional [B, stride] array
+    launch_root(h, sa, {pl + rb * A, a->root_value + rb, emb + rb * E, rows(a->invalid_actions, A),
+                        gum ? nullptr : rows(a->dirichlet_noise, A), gum ? 0.0f : a->dirichlet_fraction,
+                        gum ? rows(a->gumbel, A) : nullptr, {gk[0], gk[1]}}, true, stream);
+    hipLaunchKernelGGL(mz::jump_select_kernel<false>, dim3(step_grid(n)), dim3(step_block(n)), 0, stream, sa, h->jump, 0,
+                       act0 + rb, emb + rb * E);
+    launch_mlp_search(c, sa, h->jump, g, n, lds_search, stream);
+    launch_finish(h, sa, a->temperature, rows(a->gumbel, A), a->action + rb, a->action_weights + rb * A,
+                  rows(a->search_value, 1), rows(a->depth_sum, 1), stream);
+    MZS_HIP(h, hipGetLastError());
+  }
+  h->step.rooted = true;
+  if (a->tree) return mzs_tree_export(h, a->tree, stream);
+  return MZS_OK;
+}
+// act() of the default MLP trio for shapes the fused kernel has no instance for (mz_mlp_generic.cuh): root inference,
+// mzs_root, mzs_select(0), ONE launch for all simulations, mzs_finish -- five launches per act instead of two per
+// simulation, the nets evaluated by the library to the project's arithmetic spec (== the oracle for any shape).
+int mzh::act_mlp_generic(mzs_handle* h, const mzs_act_args* a, void* stream_) {
+  const mzs_config& c = h->cfg;
+  const mzs_mlp_weights& w = h->w;
+  const int A = c.num_actions, E = c.embed_dim, F = 2 * w.support_size + 1, S = c.num_simulations;
+  if (F < 17 || F > 64 || A > 64)
+    return fail(h, MZS_E_UNSUPPORTED, "mzs_act_mlp (generic route): support_size must be 8..31 and num_actions <= 64");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MZS_HIP(h, hipSetDevice(c.device));  // (reached before mzs_act_mlp's own hipSetDevice when num_simulations > kMaxSims)
+  if (int rc = ensure_step_state(h)) return rc;
+  if (h->jump_roots < 1 || (!h->use_jump && E >= mz::kWideEmb))
+    return fail(h, MZS_E_UNSUPPORTED, "mzs_act_mlp (generic route): no cached-decision slab for this tree (more than 1023 "
+                                      "simulations, MZS_STEP_WALK=1, or out of device memory); use the step-wise path");
+  const size_t B = (size_t)c.batch;
+  if (!h->gen_scratch) MZS_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->gen_scratch), (B * A + B * E + B) * sizeof(float)));
+  float* pl = h->gen_scratch;
+  float* emb = pl + B * A;
+  int32_t* act0 = reinterpret_cast<int32_t*>(emb + B * E);
+  mz::MlpGen g;
+  mzh::copy_weights(w, g);
+  g.obs_dim = w.obs_dim; g.E = E; g.A = A; g.F = F; g.support = w.support_size; g.pred_on_parent = w.recurrent_pred_on;
+  g.discount = w.discount;
+  const int ew = E > w.obs_dim ? E : w.obs_dim;
+  const size_t lds_root = sizeof(float) * (size_t)mz::gen_scratch_words(ew, A);
+  const size_t lds_search = sizeof(int32_t) * 15 * ((size_t)S + 2) + sizeof(float) * (size_t)mz::gen_scratch_words(E, A);
+  if (lds_root > 64 * 1024 || lds_search > 64 * 1024)
+    return fail(h, MZS_E_UNSUPPORTED, "mzs_act_mlp (generic route): num_simulations / embedding too large for the LDS of a workgroup");
+  hipLaunchKernelGGL(mz::mz_mlp_root_kernel, dim3(c.batch), dim3(64), lds_root, stream, g, c.batch, a->obs, pl, a->root_value, emb);
+  MZS_HIP(h, hipGetLastError());
+  if (!h->use_jump) return act_mlp_generic_chunks(h, a, g, pl, emb, act0, lds_search, stream);
+  int rc = c.policy == 1 ? mzs_root_gumbel(h, pl, a->root_value, emb, a->invalid_actions, a->gumbel, a->key, stream_)
+                         : mzs_root(h, pl, a->root_value, emb, a->invalid_actions, a->dirichlet_noise, a->dirichlet_fraction,
+                                    a->key, stream_);
+  if (rc) return rc;
+  if ((rc = mzs_select(h, 0, act0, emb, stream_))) return rc;  // simulate() of simulation 0 (emb: consumed by mzs_root, reused)
+  mz::StepArgs sa = h->step.args(c);
+  launch_mlp_search(c, sa, h->jump, g, c.batch, lds_search, stream);
+  MZS_HIP(h, hipGetLastError());
+  if ((rc = mzs_finish(h, a->temperature, c.policy == 1 ? nullptr : a->gumbel, a->action, a->action_weights, a->search_value,
+                       a->depth_sum, stream_)))
+    return rc;
+  if (a->tree) return mzs_tree_export(h, a->tree, stream_);
+  return MZS_OK;
+}
+
+#ifdef MZ_PROFILE
+// tools-only entry point (not part of the ABI): the tree-step phase counters of THIS translation unit's kernels (the
+// generic one-launch search, the step-wise launches): read and clear (tools/profile_generic.py)
+extern "C" int mzs_debug_generic_jump_profile(uint64_t* host_out, int32_t words) {
+  static unsigned long long zero[1024 * 8];
+  if (words > 1024 * 8) words = 1024 * 8;
+  if (hipMemcpyFromSymbol(host_out, HIP_SYMBOL(mz::g_jump_prof), sizeof(uint64_t) * (size_t)words) != hipSuccess) return MZS_E_RUNTIME;
+  if (hipMemcpyToSymbol(HIP_SYMBOL(mz::g_jump_prof), zero, sizeof(zero)) != hipSuccess) return MZS_E_RUNTIME;
+  return MZS_OK;
+}
+#endif
