@@ -597,6 +597,50 @@ typedef struct mzs_replay_sample_args {
 } mzs_replay_sample_args;
 int mzs_replay_sample(const mzs_replay_arena *arena, const mzs_replay_sample_args *a, void *stream);
 
+/* Reanalysis: fresh search results for episodes the arenas already hold, without the host.  Between
+ * the two calls the caller runs its searches on the gathered observations.  Both take the descriptors of
+ * mzs_replay_store -- desc[e] = {first row in the dense stream, first row in the arena, length, table slot}, the HOST
+ * copy checked here (every range inside the stream, the arena and the table, else MZS_E_INVALID), the DEVICE copy read
+ * by the kernel -- one wavefront per episode, one launch each; neither synchronises or copies to the host.  The caller
+ * keeps the episodes of one call disjoint and back to back in the stream (rows [0, stream_rows) all covered).
+ *
+ * mzs_replay_gather_obs: obs[src + t] = arena.obs[dst + t] for every selected episode; rows stream_rows ..
+ *   rows_padded - 1 of `obs` are written as zeros (whole chunks for a fixed-batch search). */
+typedef struct mzs_replay_gather_args {
+  int32_t struct_size;     /* = sizeof(mzs_replay_gather_args) */
+  int32_t episodes;
+  int64_t stream_rows;     /* sum of the lengths */
+  int64_t rows_padded;     /* >= stream_rows, < 2^31 */
+  const int32_t *desc;       /* [episodes][4] */
+  const int32_t *desc_host;  /* HOST [episodes][4] */
+  float *obs;                /* out [rows_padded, obs_dim] */
+} mzs_replay_gather_args;
+int mzs_replay_gather_obs(const mzs_replay_arena *arena, const mzs_replay_gather_args *a, void *stream);
+
+/* mzs_replay_reanalyse: for an episode of length T at stream row src, arena row dst:
+ *   arena.pi[dst + t] = pi[src + t], arena.v[dst + t] = v[src + t];
+ *   Rn, done, w by the arithmetic of mzs_replay_store's raw == 1, in fp64 and in its operation order, on
+ *   r[t] = (double)arena.r[dst + t] (the STORED float reward) and v[t] = (double)v[src + t] (the bootstrap value is
+ *   read from the stream as well); cw = the sequential inclusive prefix sum of w; the episode's table weight t_w =
+ *   the mean (weight_mode 1) or the sum (weight_mode 2) of its w.
+ * obs, a, r and the table's start / length / serial are not written.  The compact table is stale afterwards
+ * (mzs_replay_refresh).  pi / v may have rows_padded rows; rows from stream_rows on are not read. */
+typedef struct mzs_replay_reanalyse_args {
+  int32_t struct_size;     /* = sizeof(mzs_replay_reanalyse_args) */
+  int32_t episodes;
+  int64_t stream_rows, rows_padded;
+  const int32_t *desc;       /* [episodes][4] */
+  const int32_t *desc_host;  /* HOST [episodes][4] */
+  int32_t n_step;          /* >= 1 */
+  int32_t weight_mode;     /* 1: mean, 2: sum */
+  int32_t has_alpha, reserved0;
+  double alpha;
+  const double *gpow;        /* [n_step + 1]: gamma ** i */
+  const float *pi;           /* [stream_rows, num_actions] */
+  const float *v;            /* [stream_rows] */
+} mzs_replay_reanalyse_args;
+int mzs_replay_reanalyse(const mzs_replay_arena *arena, const mzs_replay_reanalyse_args *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,18 @@ class MzsReplaySampleArgs(C.Structure):
                 + [(n, _vp) for n in ("obs", "a", "r", "Rn", "v", "done", "pi", "w", "serial", "start")])
 
 
+class MzsReplayGatherArgs(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("episodes", C.c_int32), ("stream_rows", C.c_int64),
+                 ("rows_padded", C.c_int64)] + [(n, _vp) for n in ("desc", "desc_host", "obs")])
+
+
+class MzsReplayReanalyseArgs(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("episodes", C.c_int32), ("stream_rows", C.c_int64),
+                 ("rows_padded", C.c_int64), ("desc", _vp), ("desc_host", _vp), ("n_step", C.c_int32),
+                 ("weight_mode", C.c_int32), ("has_alpha", C.c_int32), ("reserved0", C.c_int32), ("alpha", C.c_double)]
+                + [(n, _vp) for n in ("gpow", "pi", "v")])
+
+
 EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_destroy",
                     "mzs_mlp_set_weights", "mzs_act_mlp", "mzs_root", "mzs_root_gumbel", "mzs_select",
                     "mzs_expand_backup", "mzs_expand_backup_select",
@@ -157,7 +169,8 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_resblock_v2", "mzs_resblock_v2_workspace_bytes", "mzs_register_train_dispatch", "mzs_train_jit_abi",
                     "mzs_mlp_allow_wide", "mzs_mlp_wide_plan",
                     "mzs_mlp_allow_wide_gumbel", "mzs_mlp_wide_plan_policy",
-                    "mzs_replay_store", "mzs_replay_refresh", "mzs_replay_sample"]
+                    "mzs_replay_store", "mzs_replay_refresh", "mzs_replay_sample",
+                    "mzs_replay_gather_obs", "mzs_replay_reanalyse"]
 
 _lib = None
 
@@ -226,6 +239,8 @@ def load(build_if_missing: bool = True):
     L.mzs_replay_store.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayStoreArgs), _vp]
     L.mzs_replay_refresh.argtypes = [C.POINTER(MzsReplayArena), C.c_int32, C.c_int32, C.c_int32, _vp]
     L.mzs_replay_sample.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplaySampleArgs), _vp]
+    L.mzs_replay_gather_obs.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayGatherArgs), _vp]
+    L.mzs_replay_reanalyse.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayReanalyseArgs), _vp]
     L.mzs_tower_pair_scratch_bytes.restype = C.c_int64
     if L.mzs_abi_version() != 1:
         raise RuntimeError("libmzsearch.so ABI version mismatch")

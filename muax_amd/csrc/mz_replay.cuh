@@ -9,6 +9,10 @@
 //                          weights of those longer than k_steps (one wavefront; after adds or a change of k_steps)
 //   replay_sample_kernel   per batch row: two threefry draws, the episode and the start by binary search in CW / cw,
 //                          then 64 lanes copy the window
+// and the two of reanalysis (fresh search results for episodes already held), again one wavefront per episode:
+//   replay_gather_obs_kernel  the observations of the selected episodes as one dense stream, zero-padded to whole chunks
+//   replay_reanalyse_kernel   new pi and v in place; Rn, done, w from the STORED rewards and the new values by the store
+//                             kernel's arithmetic (nstep_transition); then cw and the episode's table weight
 // Every prefix sum is the SEQUENTIAL fp64 sum (np.cumsum's order), one addition per element on a wave-uniform carry:
 // monotone, so the searches are well defined, and equal to the host's bit for bit.
 #pragma once
@@ -42,6 +46,24 @@ struct ReplayStoreArgs {
   const float* obs; const int32_t* a; const float* pi;
   const float* r32; const float* v32; const double* r64; const double* v64;  // raw reads the fp64 pair
   const float* Rn; const uint8_t* done; const double* w;
+};
+
+struct ReplayGatherArgs {
+  ReplayArena ar;
+  int episodes, pad_waves;    // wavefronts e >= episodes (pad_waves of them) zero the padding
+  long long stream_rows, rows_padded;
+  const int32_t* desc;        // [episodes][4], as ReplayStoreArgs
+  float* obs;                 // out [rows_padded, obs_dim]
+};
+
+struct ReplayReanalyseArgs {
+  ReplayArena ar;
+  int episodes, n_step, weight_mode, has_alpha;
+  double alpha;
+  const int32_t* desc;        // [episodes][4], as ReplayStoreArgs
+  const double* gpow;         // [n_step + 1]
+  const float* pi;            // [stream_rows, A]
+  const float* v;             // [stream_rows]
 };
 
 struct ReplaySampleArgs {
@@ -85,6 +107,19 @@ MZ_DEV int upper_bound(const double* c, int n, double t) {
   return lo;
 }
 
+// Transition t of an episode of T steps with rewards r[0..T) and values v[0..T) (double, or float widened):
+// vector.nstep_returns in its operation order -- i ascending (terms past the end are + gamma^i * 0), then the bootstrap --
+// and episode_trajectory's priority weight.  Returns w; Rn and boot (false: `done`) by reference.
+template <typename TR, typename TV>
+MZ_DEV double nstep_transition(const TR* r, const TV* v, int t, int T, int n_step, const double* gpow, int has_alpha,
+                               double alpha, double& Rn, bool& boot) {
+  Rn = 0.0;
+  for (int i = 0; i < n_step; ++i) Rn = Rn + gpow[i] * (t + i < T ? (double)r[t + i] : 0.0);
+  boot = t + n_step < T;
+  Rn = Rn + (boot ? (double)v[t + n_step] * gpow[n_step] : 0.0);
+  return has_alpha ? pow(fabs((double)v[t] - Rn), alpha) : 1.0;
+}
+
 __global__ void __launch_bounds__(64 * kReplayWaves) replay_store_kernel(ReplayStoreArgs p) {
   const int lane = threadIdx.x & 63;
   const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
@@ -103,16 +138,12 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_store_kernel(ReplayS
     if (in) {
       ar.a[dst + t] = p.a[src + t];
       if (p.raw) {
-        // vector.nstep_returns, its operation order: i ascending (terms past the end are + gamma^i * 0), then the bootstrap
         const double* r = p.r64 + src;
-        double Rn = 0.0;
-        for (int i = 0; i < p.n_step; ++i) Rn = Rn + p.gpow[i] * (t + i < T ? r[t + i] : 0.0);
-        const bool boot = t + p.n_step < T;
-        Rn = Rn + (boot ? p.v64[src + t + p.n_step] * p.gpow[p.n_step] : 0.0);
-        const double v = p.v64[src + t];
-        w = p.has_alpha ? pow(fabs(v - Rn), p.alpha) : 1.0;
+        double Rn;
+        bool boot;
+        w = nstep_transition(r, p.v64 + src, t, T, p.n_step, p.gpow, p.has_alpha, p.alpha, Rn, boot);
         ar.r[dst + t] = (float)r[t];
-        ar.v[dst + t] = (float)v;
+        ar.v[dst + t] = (float)p.v64[src + t];
         ar.Rn[dst + t] = (float)Rn;
         ar.done[dst + t] = boot ? 0 : 1;
       } else {
@@ -134,6 +165,56 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_store_kernel(ReplayS
     ar.t_w[slot] = p.weight_mode == 0 ? p.ep_w[e] : p.weight_mode == 1 ? carry / (double)T : carry;
     ar.t_serial[slot] = p.serial[e];
   }
+}
+
+__global__ void __launch_bounds__(64 * kReplayWaves) replay_gather_obs_kernel(ReplayGatherArgs p) {
+  const int lane = threadIdx.x & 63;
+  const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  const size_t od = (size_t)p.ar.obs_dim;
+  if (e < p.episodes) {
+    const size_t src = (size_t)p.desc[4 * e], dst = (size_t)p.desc[4 * e + 1];
+    const size_t no = (size_t)p.desc[4 * e + 2] * od;
+    for (size_t i = lane; i < no; i += 64) p.obs[src * od + i] = p.ar.obs[dst * od + i];
+    return;
+  }
+  const int j = e - p.episodes;  // the padding rows, strided over the pad_waves tail wavefronts
+  if (j >= p.pad_waves) return;
+  const size_t first = (size_t)p.stream_rows * od, end = (size_t)p.rows_padded * od;
+  for (size_t i = first + (size_t)j * 64 + lane; i < end; i += (size_t)p.pad_waves * 64) p.obs[i] = 0.f;
+}
+
+__global__ void __launch_bounds__(64 * kReplayWaves) replay_reanalyse_kernel(ReplayReanalyseArgs p) {
+  const int lane = threadIdx.x & 63;
+  const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  if (e >= p.episodes) return;
+  const ReplayArena& ar = p.ar;
+  const size_t src = (size_t)p.desc[4 * e], dst = (size_t)p.desc[4 * e + 1];
+  const int T = p.desc[4 * e + 2], slot = p.desc[4 * e + 3];
+  const size_t np_ = (size_t)T * ar.A;
+  for (size_t i = lane; i < np_; i += 64) ar.pi[dst * ar.A + i] = p.pi[src * ar.A + i];
+  // rewards: the arena's (never written here); values, the bootstrap's included: the stream's, so no lane reads what
+  // another lane of the wave writes
+  const float* r = ar.r + dst;
+  const float* v = p.v + src;
+  double carry = 0.0;
+  for (int base = 0; base < T; base += 64) {
+    const int t = base + lane;
+    const bool in = t < T;
+    double w = 0.0;
+    if (in) {
+      double Rn;
+      bool boot;
+      w = nstep_transition(r, v, t, T, p.n_step, p.gpow, p.has_alpha, p.alpha, Rn, boot);
+      ar.v[dst + t] = v[t];
+      ar.Rn[dst + t] = (float)Rn;
+      ar.done[dst + t] = boot ? 0 : 1;
+      ar.w[dst + t] = w;
+    }
+    const int valid = T - base < 64 ? T - base : 64;
+    const double c = seq_scan(w, valid, lane, carry);
+    if (in) ar.cw[dst + t] = c;
+  }
+  if (lane == 0) ar.t_w[slot] = p.weight_mode == 1 ? carry / (double)T : carry;
 }
 
 __global__ void __launch_bounds__(64) replay_refresh_kernel(ReplayArena ar, int head, int count, int k) {

@@ -1,5 +1,5 @@
 // mz_replay.hip -- translation unit of the device-resident trajectory replay (mz_replay.cuh): argument checks and
-// launches of mzs_replay_store / mzs_replay_refresh / mzs_replay_sample.
+// launches of mzs_replay_store / mzs_replay_refresh / mzs_replay_sample / mzs_replay_gather_obs / mzs_replay_reanalyse.
 #include <hip/hip_runtime.h>
 
 #include "mz_host.h"
@@ -26,6 +26,23 @@ int check_arena(const mzs_replay_arena* ar, const char* who, mz::ReplayArena* ou
 }
 
 int waves_grid(int n) { return (n + mz::kReplayWaves - 1) / mz::kReplayWaves; }
+
+// the episode descriptors of a reanalysis call (host copy): every range inside the stream, the arena and the table
+int check_stream_desc(const mzs_replay_arena* ar, const char* who, int32_t episodes, int64_t stream_rows,
+                      int64_t rows_padded, const int32_t* desc, const int32_t* desc_host) {
+  if (episodes <= 0 || episodes > ar->capacity || stream_rows <= 0 || rows_padded < stream_rows ||
+      rows_padded >= ((int64_t)1 << 31))
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: episodes must be 1..capacity, 1 <= stream_rows <= rows_padded < 2^31", who);
+  if (!desc || !desc_host) return mzh::fail(nullptr, MZS_E_INVALID, "%s: null descriptor pointer", who);
+  for (int e = 0; e < episodes; ++e) {
+    const int32_t* d = desc_host + 4 * e;
+    const int64_t src = d[0], dst = d[1], len = d[2];
+    if (len <= 0 || src < 0 || src + len > stream_rows || dst < 0 || dst + len > ar->max_steps || d[3] < 0 ||
+        d[3] >= ar->capacity)
+      return mzh::fail(nullptr, MZS_E_INVALID, "%s: an episode's range leaves the stream, the arena or the table", who);
+  }
+  return MZS_OK;
+}
 
 }  // namespace
 
@@ -97,6 +114,49 @@ int mzs_replay_sample(const mzs_replay_arena* arena, const mzs_replay_sample_arg
   p.obs = a->obs; p.a = a->a; p.r = a->r; p.Rn = a->Rn; p.v = a->v; p.done = a->done; p.pi = a->pi; p.w = a->w;
   p.serial = (long long*)a->serial; p.start = a->start;
   hipLaunchKernelGGL(mz::replay_sample_kernel, dim3(waves_grid(a->batch)), dim3(64 * mz::kReplayWaves), 0,
+                     static_cast<hipStream_t>(stream_), p);
+  MZS_HIP(nullptr, hipGetLastError());
+  return MZS_OK;
+}
+
+int mzs_replay_gather_obs(const mzs_replay_arena* arena, const mzs_replay_gather_args* a, void* stream_) {
+  mz::ReplayGatherArgs p{};
+  if (int rc = check_arena(arena, "mzs_replay_gather_obs", &p.ar)) return rc;
+  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_gather_args))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_gather_obs: null arguments or size mismatch (ABI)");
+  if (int rc = check_stream_desc(arena, "mzs_replay_gather_obs", a->episodes, a->stream_rows, a->rows_padded, a->desc,
+                                 a->desc_host))
+    return rc;
+  if (!a->obs) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_gather_obs: null output pointer");
+  MZS_HIP(nullptr, hipSetDevice(arena->device));
+  p.episodes = a->episodes; p.stream_rows = a->stream_rows; p.rows_padded = a->rows_padded;
+  p.desc = a->desc; p.obs = a->obs;
+  // one tail wavefront per 1024 padding floats, 64 at the most (they stride)
+  const int64_t pad = (a->rows_padded - a->stream_rows) * (int64_t)arena->obs_dim;
+  p.pad_waves = (int)(pad <= 0 ? 0 : (pad + 1023) / 1024 < 64 ? (pad + 1023) / 1024 : 64);
+  hipLaunchKernelGGL(mz::replay_gather_obs_kernel, dim3(waves_grid(a->episodes + p.pad_waves)),
+                     dim3(64 * mz::kReplayWaves), 0, static_cast<hipStream_t>(stream_), p);
+  MZS_HIP(nullptr, hipGetLastError());
+  return MZS_OK;
+}
+
+int mzs_replay_reanalyse(const mzs_replay_arena* arena, const mzs_replay_reanalyse_args* a, void* stream_) {
+  mz::ReplayReanalyseArgs p{};
+  if (int rc = check_arena(arena, "mzs_replay_reanalyse", &p.ar)) return rc;
+  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_reanalyse_args))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_reanalyse: null arguments or size mismatch (ABI)");
+  if (int rc = check_stream_desc(arena, "mzs_replay_reanalyse", a->episodes, a->stream_rows, a->rows_padded, a->desc,
+                                 a->desc_host))
+    return rc;
+  if (a->n_step <= 0 || !a->gpow) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_reanalyse: needs n_step >= 1 and gpow");
+  if (a->weight_mode != 1 && a->weight_mode != 2)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_reanalyse: weight_mode must be 1 (mean) or 2 (sum)");
+  if (!a->pi || !a->v) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_reanalyse: null pi or v");
+  MZS_HIP(nullptr, hipSetDevice(arena->device));
+  p.episodes = a->episodes; p.n_step = a->n_step; p.weight_mode = a->weight_mode;
+  p.has_alpha = a->has_alpha ? 1 : 0; p.alpha = a->alpha;
+  p.desc = a->desc; p.gpow = a->gpow; p.pi = a->pi; p.v = a->v;
+  hipLaunchKernelGGL(mz::replay_reanalyse_kernel, dim3(waves_grid(a->episodes)), dim3(64 * mz::kReplayWaves), 0,
                      static_cast<hipStream_t>(stream_), p);
   MZS_HIP(nullptr, hipGetLastError());
   return MZS_OK;

@@ -26,6 +26,25 @@ _ARENA_FIELDS = (("obs", torch.float32), ("a", torch.int32), ("r", torch.float32
 _TABLE_FIELDS = (("t_start", torch.int32), ("t_len", torch.int32), ("t_w", torch.float64), ("t_serial", torch.int64),
                  ("c_start", torch.int32), ("c_len", torch.int32), ("c_CW", torch.float64), ("c_serial", torch.int64))
 _WEIGHT_MODES = {"mean": 1, "sum": 2}
+ReanalysePlan = namedtuple("ReanalysePlan", "offsets stream_rows n_chunks rows_padded")
+
+
+def reanalyse_plan(lengths, chunk_rows):
+    """Where the episodes of a reanalysis lie in its dense stream: `offsets` (the first row of every episode, the
+    episodes back to back in the order given), `stream_rows` = sum(lengths), `n_chunks` = ceil(stream_rows /
+    chunk_rows) searches of exactly `chunk_rows` roots, and `rows_padded` = n_chunks * chunk_rows."""
+    lengths = [int(x) for x in lengths]
+    chunk_rows = int(chunk_rows)
+    if not lengths or min(lengths) <= 0:
+        raise ValueError("reanalyse_plan: episode lengths must be positive")
+    if chunk_rows <= 0:
+        raise ValueError("reanalyse_plan: chunk_rows must be positive")
+    offsets, rows = [], 0
+    for T in lengths:
+        offsets.append(rows)
+        rows += T
+    n_chunks = -(-rows // chunk_rows)
+    return ReanalysePlan(offsets, rows, n_chunks, n_chunks * chunk_rows)
 
 
 def _columns(trajectory):
@@ -107,6 +126,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
 
     def clear(self):
         self._eps = deque()
+        self._touched, self._clock = {}, 0  # serial -> count of the add / reanalysis that last wrote its targets
         self._head = self._tail = self._steps = 0
         self._dirty, self._table_k, self._eligible = True, None, False
 
@@ -118,6 +138,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
 
     def _evict(self):
         e = self._eps.popleft()
+        self._touched.pop(e.serial, None)
         self._steps -= e.length
         self._head = (self._head + 1) % self._capacity
 
@@ -154,6 +175,8 @@ class DeviceReplayBuffer(BaseReplayBuffer):
             self._evict()
         slot = (self._head + len(self._eps)) % self._capacity
         self._eps.append(_Episode(slot, dst, T, self._serial))
+        self._clock += 1
+        self._touched[self._serial] = self._clock
         self._serial += 1
         self._tail = dst + T
         self._steps += T
@@ -286,6 +309,84 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         placed = self._place_all(lengths)
         host["gpow"] = np.array([float(gamma) ** i for i in range(int(n) + 1)], np.float64)
         self._store(placed, host, device, raw=True, n=n, alpha=alpha, weight_mode=_WEIGHT_MODES[weight], stream_steps=M)
+
+    def stalest(self, count):
+        """Serials of up to `count` held episodes whose targets are the oldest: ordered by when they were last stored
+        or reanalysed, earliest first (the episodes of one reanalysis tie; ties go by serial)."""
+        order = sorted((e.serial for e in self._eps), key=lambda s: (self._touched[s], s))
+        return order[:max(int(count), 0)]
+
+    def reanalyse(self, model, key, n, gamma, alpha=None, weight="mean", serials=None, chunk_rows=4096, **act_kwargs):
+        """MuZero Reanalyse on the device: search the stored observations of the episodes `serials` (default: all
+        held, oldest first; otherwise in the order given) again with `model` and overwrite, in place, their `pi`
+        (search policy) and `v` (root value) and what follows from them -- `Rn`, `done`, `w = |v - Rn| ** alpha`
+        (1 with alpha None), the prefix sums and the episode's buffer weight (`weight`: "mean" or "sum" of w), with
+        the arithmetic of `add_raw` on the STORED float32 rewards.  Observations, actions, rewards, serials and
+        the placement stay as they are, so nothing is evicted.
+
+        The observations are gathered into one dense stream, zero-padded to `n_chunks = ceil(rows / chunk_rows)`
+        chunks, and chunk c is searched as `model.act(keys[c], chunk, with_pi=True, with_value=True,
+        obs_from_batch=True, device_outputs=True, **act_kwargs)` with `keys = prng.split(key, n_chunks)` (always
+        split, also for one chunk); every call has exactly `chunk_rows` roots, so one search handle serves them all.
+        `act_kwargs` reach act() untouched: its own defaults hold unless given here -- `num_simulations=5`,
+        `temperature=1`, and the Dirichlet root noise `dirichlet_fraction=0.25` of acting; pass
+        `dirichlet_fraction=0.0` for noise-free targets.  The actions act() returns are discarded.
+
+        One upload (descriptors and discount powers), two launches around the searches; no device-to-host copy and
+        no synchronisation beyond what act() does on its route.  A serial that is not held is a KeyError, a
+        repeated one a ValueError, both before anything is launched.  Returns the number of transitions refreshed."""
+        if weight not in _WEIGHT_MODES:
+            raise ValueError("weight must be 'mean' or 'sum'")
+        if int(n) < 1:
+            raise ValueError("reanalyse: n must be at least 1")
+        held = {e.serial: e for e in self._eps}
+        serials = list(held) if serials is None else [int(s) for s in serials]
+        if len(set(serials)) != len(serials):
+            raise ValueError("reanalyse: a serial is given more than once")
+        for s in serials:
+            if s not in held:
+                raise KeyError(f"no episode with serial {s} in the buffer")
+        if not serials:
+            return 0
+        eps = [held[s] for s in serials]
+        R = int(chunk_rows)
+        plan = reanalyse_plan([e.length for e in eps], R)
+        desc = np.array([[src, e.start, e.length, e.slot] for src, e in zip(plan.offsets, eps)], np.int32)
+        gpow = np.array([float(gamma) ** i for i in range(int(n) + 1)], np.float64)
+        stage = np.empty(gpow.nbytes + desc.nbytes, np.uint8)  # gpow (8-byte elements) first
+        stage[:gpow.nbytes] = gpow.view(np.uint8)
+        stage[gpow.nbytes:] = desc.reshape(-1).view(np.uint8)
+        dstage = torch.from_numpy(stage).to(self._device)
+        dev, f32, stream = self._device, torch.float32, self._stream()
+        obs = torch.empty((plan.rows_padded, self.obs_dim), dtype=f32, device=dev)
+        pi = torch.empty((plan.rows_padded, self.num_actions), dtype=f32, device=dev)
+        v = torch.empty(plan.rows_padded, dtype=f32, device=dev)
+        g = _lib.MzsReplayGatherArgs()
+        g.struct_size = C.sizeof(_lib.MzsReplayGatherArgs)
+        g.episodes, g.stream_rows, g.rows_padded = len(eps), plan.stream_rows, plan.rows_padded
+        g.desc, g.desc_host, g.obs = dstage.data_ptr() + gpow.nbytes, desc.ctypes.data, obs.data_ptr()
+        _lib.check(self._L.mzs_replay_gather_obs(C.byref(self._arena), C.byref(g), stream))
+        keys = prng.split(prng.as_key(key), plan.n_chunks)
+        for c in range(plan.n_chunks):
+            rows = slice(c * R, (c + 1) * R)
+            _, pi_c, v_c = model.act(keys[c], obs[rows], with_pi=True, with_value=True, obs_from_batch=True,
+                                     device_outputs=True, **act_kwargs)
+            pi[rows].copy_(pi_c)
+            v[rows].copy_(v_c)
+        a = _lib.MzsReplayReanalyseArgs()
+        a.struct_size = C.sizeof(_lib.MzsReplayReanalyseArgs)
+        a.episodes, a.stream_rows, a.rows_padded = len(eps), plan.stream_rows, plan.rows_padded
+        a.desc, a.desc_host = g.desc, g.desc_host
+        a.n_step, a.weight_mode = int(n), _WEIGHT_MODES[weight]
+        a.has_alpha, a.alpha = int(alpha is not None), float(alpha if alpha is not None else 0.0)
+        a.gpow, a.pi, a.v = dstage.data_ptr(), pi.data_ptr(), v.data_ptr()
+        _lib.check(self._L.mzs_replay_reanalyse(C.byref(self._arena), C.byref(a), self._stream()))
+        self._keep = (dstage, obs, pi, v)
+        self._clock += 1
+        for s in serials:
+            self._touched[s] = self._clock
+        self._dirty = True
+        return plan.stream_rows
 
     def sample(self, batch_size=32, num_trajectory: int = None, k_steps: int = 5, sample_per_trajectory: int = 1,
                key=None, with_indices: bool = False):

@@ -153,13 +153,18 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                iterations: int = 100, steps_per_iteration: int = 64, num_simulations: int = 50, k_steps: int = 10,
                num_trajectory: int = 32, sample_per_trajectory: int = 1, num_update_per_iteration: int = 50,
                max_training_steps: int = 10000, test_interval: int = 10, num_test_episodes: int = 10,
-               random_seed: int = 42, temperature_fn=None, metrics=None, trajectory_weight: str = "mean"):
+               random_seed: int = 42, temperature_fn=None, metrics=None, trajectory_weight: str = "mean",
+               reanalyse_every: int = 0, reanalyse_episodes=None):
     """The reference's fit() loop (muax/train.py:175-241: temperature schedule, buffer sampling, update,
     greedy test) with the acting half on a vector environment: per iteration `steps_per_iteration`
     batched act() calls -> finished episodes -> buffer, then `num_update_per_iteration` updates.
     `trajectory_weight`: "mean" is the reference's buffer weight (mean priority of the episode,
     muax/train.py:171,203); "sum" weights an episode by its total priority, which undoes the bias of a
-    fixed collection window towards short episodes (many short episodes finish while one long one runs)."""
+    fixed collection window towards short episodes (many short episodes finish while one long one runs).
+    `reanalyse_every` > 0 (a buffer with `reanalyse`, i.e. the device buffer): before the updates of every
+    `reanalyse_every`-th iteration the `reanalyse_episodes` episodes (default: all) whose targets are the oldest are
+    searched again with the current network (`DeviceReplayBuffer.reanalyse`, `num_simulations` simulations, act()'s
+    other defaults), its key one extra split of the running key; 0: the key stream and every result are unchanged."""
     if trajectory_weight not in ("mean", "sum"):
         raise ValueError("trajectory_weight must be 'mean' or 'sum'")
     from .replay_buffer import TrajectoryReplayBuffer
@@ -185,6 +190,10 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                 buffer.add(tr, w)
         row = {"iteration": it, "env_steps": env_steps, "episodes": len(trajs), "collect_s": collect_s,
                "G": float(np.mean([float(np.sum(t.rewards)) for t in trajs])) if trajs else float("nan")}
+        if reanalyse_every > 0 and hasattr(buffer, "reanalyse") and len(buffer) and (it + 1) % reanalyse_every == 0:
+            key, subkey = prng.split(key)
+            buffer.reanalyse(model, subkey, n_step, gamma, alpha, weight=trajectory_weight,
+                             serials=buffer.stalest(reanalyse_episodes or len(buffer)), num_simulations=num_simulations)
         if len(buffer):
             loss = 0.0
             for _ in range(num_update_per_iteration):

@@ -3,6 +3,11 @@ slices, five uploads per batch) against `DeviceReplayBuffer.sample` + `update()`
 and each `sample` on its own.  Default MLP trio on CartPole shapes, 500 stored episodes of about 200 steps.
 
     python tools/bench_replay.py [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
+    python tools/bench_replay.py --reanalyse [--iters 200] [--episodes 500]
+
+`--reanalyse` times, on the same device buffer and with 50 simulations, (a) `DeviceReplayBuffer.reanalyse()` of the
+whole buffer, (b) the same work through the host -- `episode().obs` downloaded, `act` NumPy in / out in the same
+chunks, `vector.episode_trajectory`, `add_many` into a second buffer -- and (c) the `act()` chunks of (a) alone.
 
 Every figure is the median of `--iters` iterations, each ending in a device synchronise, after 30 ms of untimed
 iterations of the same work (clocks settled).  The two routes alternate shape by shape in one process."""
@@ -58,8 +63,56 @@ def episodes(n, rng):
     return out
 
 
+def reanalyse_figures(dev, iters, simulations=50, chunk_rows=4096, n=10, gamma=0.997, alpha=0.5):
+    from muax_amd import prng, vector
+    from muax_amd.replay_device import reanalyse_plan
+    m = model()
+    serials = dev.serials
+    lengths = [len(dev.episode(s).a) for s in serials]
+    plan = reanalyse_plan(lengths, chunk_rows)
+    keys = prng.split(prng.PRNGKey(0), plan.n_chunks)
+    act_kw = dict(with_pi=True, with_value=True, obs_from_batch=True, num_simulations=simulations)
+    stream = torch.zeros((plan.rows_padded, OBS), device="cuda")
+    stream[:plan.stream_rows] = torch.cat([dev.episode(s).obs for s in serials])
+
+    def on_device():
+        dev.reanalyse(m, 0, n, gamma, alpha, chunk_rows=chunk_rows, num_simulations=simulations)
+
+    def acts_alone():
+        for c in range(plan.n_chunks):
+            m.act(keys[c], stream[c * chunk_rows:(c + 1) * chunk_rows], device_outputs=True, **act_kw)
+
+    def through_the_host():
+        eps = [dev.episode(s) for s in serials]
+        obs = [e.obs.cpu().numpy() for e in eps]
+        flat = np.concatenate(obs + [np.zeros((plan.rows_padded - plan.stream_rows, OBS), np.float32)])
+        pi, v = [], []
+        for c in range(plan.n_chunks):
+            _, p, x = m.act(keys[c], flat[c * chunk_rows:(c + 1) * chunk_rows], **act_kw)
+            pi.append(p), v.append(x)
+        pi, v = np.concatenate(pi), np.concatenate(v)
+        trs = []
+        for e, o, first, T in zip(eps, obs, plan.offsets, lengths):
+            trs.append(vector.episode_trajectory(o, e.a.cpu().numpy(), e.r.cpu().numpy(), v[first:first + T],
+                                                 pi[first:first + T], n, gamma, alpha))
+        second = mx.DeviceReplayBuffer(len(eps), plan.stream_rows)
+        second.add_many(trs, [t.weights.mean() for t in trs])
+
+    ta = median_ms(on_device, iters)
+    tc = median_ms(acts_alone, iters)
+    tb = median_ms(through_the_host, max(3, iters // 20), settle_ms=0.0)
+    print(f"reanalysis of {len(serials)} episodes, {plan.stream_rows} transitions: {plan.n_chunks} act() chunks of "
+          f"{chunk_rows} roots, {simulations} simulations; median of {iters} synchronised iterations "
+          f"({max(3, iters // 20)} for the host route), ms")
+    print(f"(a) reanalyse() on the device          {ta:9.3f}")
+    print(f"(b) through the host and a second buffer {tb:7.3f}   ({tb / ta:.1f}x (a))")
+    print(f"(c) the act() chunks alone             {tc:9.3f}   ({tc / plan.n_chunks:.3f} per chunk)")
+    print(f"(a) - (c): gather, copies, write-back  {ta - tc:9.3f}   ({100 * (ta - tc) / ta:.1f} % of (a))", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--reanalyse", action="store_true", help="time reanalysis instead of sampling")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--episodes", type=int, default=500)
     ap.add_argument("--shape", action="append", default=[], metavar="NUM_TRAJECTORY,K")
@@ -76,6 +129,9 @@ def main():
     torch.cuda.synchronize()
     print(f"{a.episodes} episodes, {dev.steps} transitions; add_many: {(time.perf_counter() - t0) * 1e3:.1f} ms "
           f"(one upload, one launch); median of {a.iters} synchronised iterations, ms")
+    if a.reanalyse:
+        reanalyse_figures(dev, a.iters)
+        return
     print(f"{'num_trajectory x k':>18} | {'host sample':>11} {'host s+upd':>10} | {'dev sample':>10} {'dev s+upd':>9} | "
           f"{'update':>7} | {'s+upd host/dev':>14} {'sample host/dev':>15}")
     for n, k in shapes:
