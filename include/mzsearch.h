@@ -641,6 +641,43 @@ typedef struct mzs_replay_reanalyse_args {
 } mzs_replay_reanalyse_args;
 int mzs_replay_reanalyse(const mzs_replay_arena *arena, const mzs_replay_reanalyse_args *a, void *stream);
 
+/* Priorities from training written back (prioritised replay): `batch` rows (serial[j], start[j]) as mzs_replay_sample
+ * returns them, each with k_prio priorities; row j addresses transitions start[j] + i, i < k_prio, of the live episode
+ * whose t_serial equals serial[j].  Two launches (one wavefront per row, then one per live episode); no synchronisation,
+ * no copy to the host.
+ * PRECONDITION (mzs_replay_refresh's): the live episodes are the `count` table slots from `head` on, wrapping at
+ *   capacity, and their serials ascend along that ring -- the store's running number guarantees it.  The episode is
+ *   found by binary search over t_serial on the ring; t_start / t_len give its rows.
+ * Skipped silently, writing nothing: a row whose serial is not live (evicted since the sample, or the -1 of a
+ *   zero-filled sample row); a row with start < 0; an element with start + i >= the episode's length; an element whose
+ *   priority is NaN or +-inf.
+ * New weight: w = (|p| + eps) ** alpha in fp64 on the widened float; with alpha == 1.0 no pow is executed, so w is
+ *   exactly (double)|p| + eps.  Where several rows address one transition, the HIGHEST row index whose element is valid
+ *   wins (NumPy's last assignment among the valid ones): deterministic; a skipped element never shadows a valid one.
+ * Of every episode with at least one valid element: the new w, cw = the sequential inclusive prefix sum of the whole
+ *   episode's w, t_w = the mean (weight_mode 1) or the sum (weight_mode 2) of its w.  Of every other episode not one
+ *   byte is written (an ep_w given to the store survives until one of the episode's transitions is updated).  obs, a,
+ *   r, Rn, v, done, pi, t_start, t_len, t_serial and the compact table are never written; the compact table is stale
+ *   afterwards (mzs_replay_refresh).
+ * Scratch (caller-owned): owner all -1 and touched all 0 on entry; both are left that way on exit.
+ * batch == 0 or count == 0: MZS_OK without a launch.  MZS_E_INVALID, the message naming the field, before any launch
+ *   for: struct sizes; head outside 0..capacity - 1; count outside 0..capacity; batch < 0; k_prio < 1 (or batch * k_prio
+ *   >= 2^31); weight_mode other than 1 / 2; alpha outside 0..1; eps negative or not finite; a null pointer with
+ *   batch > 0. */
+typedef struct mzs_replay_update_args {
+  int32_t struct_size;     /* = sizeof(mzs_replay_update_args) */
+  int32_t head, count;     /* the live ring of the episode table */
+  int32_t batch, k_prio;
+  int32_t weight_mode;     /* 1: mean, 2: sum */
+  double alpha, eps;
+  const int64_t *serial;   /* [batch] */
+  const int32_t *start;    /* [batch] */
+  const float *prio;       /* [batch, k_prio] */
+  int32_t *owner;          /* scratch [max_steps] */
+  int32_t *touched;        /* scratch [capacity] */
+} mzs_replay_update_args;
+int mzs_replay_update_priorities(const mzs_replay_arena *arena, const mzs_replay_update_args *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,12 @@ class MzsReplayReanalyseArgs(C.Structure):
                 + [(n, _vp) for n in ("gpow", "pi", "v")])
 
 
+class MzsReplayUpdateArgs(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("head", C.c_int32), ("count", C.c_int32), ("batch", C.c_int32),
+                 ("k_prio", C.c_int32), ("weight_mode", C.c_int32), ("alpha", C.c_double), ("eps", C.c_double)]
+                + [(n, _vp) for n in ("serial", "start", "prio", "owner", "touched")])
+
+
 EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_destroy",
                     "mzs_mlp_set_weights", "mzs_act_mlp", "mzs_root", "mzs_root_gumbel", "mzs_select",
                     "mzs_expand_backup", "mzs_expand_backup_select",
@@ -170,7 +176,7 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_mlp_allow_wide", "mzs_mlp_wide_plan",
                     "mzs_mlp_allow_wide_gumbel", "mzs_mlp_wide_plan_policy",
                     "mzs_replay_store", "mzs_replay_refresh", "mzs_replay_sample",
-                    "mzs_replay_gather_obs", "mzs_replay_reanalyse"]
+                    "mzs_replay_gather_obs", "mzs_replay_reanalyse", "mzs_replay_update_priorities"]
 
 _lib = None
 
@@ -241,6 +247,7 @@ def load(build_if_missing: bool = True):
     L.mzs_replay_sample.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplaySampleArgs), _vp]
     L.mzs_replay_gather_obs.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayGatherArgs), _vp]
     L.mzs_replay_reanalyse.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayReanalyseArgs), _vp]
+    L.mzs_replay_update_priorities.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayUpdateArgs), _vp]
     L.mzs_tower_pair_scratch_bytes.restype = C.c_int64
     if L.mzs_abi_version() != 1:
         raise RuntimeError("libmzsearch.so ABI version mismatch")

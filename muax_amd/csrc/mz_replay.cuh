@@ -13,6 +13,12 @@
 //   replay_gather_obs_kernel  the observations of the selected episodes as one dense stream, zero-padded to whole chunks
 //   replay_reanalyse_kernel   new pi and v in place; Rn, done, w from the STORED rewards and the new values by the store
 //                             kernel's arithmetic (nstep_transition); then cw and the episode's table weight
+// and the two that write training priorities back (rows (serial, start) as the sample kernel returns them), one
+// wavefront per batch row, then one per live episode:
+//   replay_prio_mark_kernel   finds the row's episode by its serial and enters the row's index, by atomic max, as the
+//                             owner of every transition it validly addresses; flags the episode
+//   replay_prio_apply_kernel  flagged episodes only: w = (|p| + eps) ** alpha from the owner's priority, then cw and
+//                             the table weight; clears the owners and the flag
 // Every prefix sum is the SEQUENTIAL fp64 sum (np.cumsum's order), one addition per element on a wave-uniform carry:
 // monotone, so the searches are well defined, and equal to the host's bit for bit.
 #pragma once
@@ -72,6 +78,17 @@ struct ReplaySampleArgs {
   uint32_t key0, key1;
   float* obs; int32_t* a; float* r; float* Rn; float* v; uint8_t* done; float* pi; float* w;
   long long* serial; int32_t* start;
+};
+
+struct ReplayUpdateArgs {
+  ReplayArena ar;
+  int head, count, B, kp, weight_mode;
+  double alpha, eps;
+  const long long* serial;    // [B]
+  const int32_t* start;       // [B]
+  const float* prio;          // [B][kp]
+  int32_t* owner;             // [max_steps] scratch: -1 on entry and on exit
+  int32_t* touched;           // [capacity] scratch: 0 on entry and on exit
 };
 
 MZ_DEV double lane_bcast(double x, int j) {  // j wave-uniform
@@ -283,6 +300,84 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_sample_kernel(Replay
   }
   for (int i = lane; i < od; i += 64) p.obs[(size_t)row * od + i] = ar.obs[at * od + i];
   if (lane == 0) { p.serial[row] = ar.c_serial[e]; p.start[row] = s; }
+}
+
+// table slot of the i-th live episode, oldest first
+MZ_DEV int ring_slot(const ReplayArena& ar, int head, int i) {
+  const int slot = head + i;
+  return slot >= ar.capacity ? slot - ar.capacity : slot;
+}
+
+// PRECONDITION of both priority kernels (mzs_replay_refresh's): the live episodes are the `count` table slots from
+// `head` on, wrapping at capacity, and their serials ascend along that ring (the store's running number).
+__global__ void __launch_bounds__(64 * kReplayWaves) replay_prio_mark_kernel(ReplayUpdateArgs p) {
+  const int lane = threadIdx.x & 63;
+  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  if (row >= p.B) return;
+  const ReplayArena& ar = p.ar;
+  // wave-uniform: the row's serial, the binary search for it along the ring, the episode's place
+  const long long serial = p.serial[row];
+  const int start = p.start[row];
+  if (start < 0) return;
+  int lo = 0, hi = p.count;
+  while (lo < hi) {  // first live episode whose serial is not below the row's
+    const int mid = (lo + hi) >> 1;
+    if (ar.t_serial[ring_slot(ar, p.head, mid)] < serial) lo = mid + 1; else hi = mid;
+  }
+  if (lo >= p.count) return;
+  const int slot = ring_slot(ar, p.head, lo);
+  if (ar.t_serial[slot] != serial) return;  // evicted since the sample, or the -1 of a zero-filled row
+  const long long first = ar.t_start[slot];
+  const int T = ar.t_len[slot];
+  if (first < 0 || T <= 0 || first + T > ar.max_steps) return;  // (no live episode; never index outside the arena)
+  // the priorities as bits: NaN and +-inf (exponent all ones) are tested so, whatever the unit's floating-point flags
+  const uint32_t* prio = reinterpret_cast<const uint32_t*>(p.prio) + (size_t)row * p.kp;
+  bool any = false;
+  for (int i = lane; i < p.kp && i < T - start; i += 64) {
+    if ((prio[i] & 0x7F800000u) == 0x7F800000u) continue;
+    atomicMax(p.owner + first + start + i, row);  // the highest row with a VALID element wins
+    any = true;
+  }
+  if (any) p.touched[slot] = 1;
+}
+
+__global__ void __launch_bounds__(64 * kReplayWaves) replay_prio_apply_kernel(ReplayUpdateArgs p) {
+  const int lane = threadIdx.x & 63;
+  const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  if (e >= p.count) return;
+  const ReplayArena& ar = p.ar;
+  const int slot = ring_slot(ar, p.head, e);
+  if (!p.touched[slot]) return;  // nothing of an episode that no valid element addresses is written
+  const long long first = ar.t_start[slot];
+  const int T = ar.t_len[slot];
+  if (first < 0 || T <= 0 || first + T > ar.max_steps) return;  // (the mark pass flags no such slot)
+  const size_t dst = (size_t)first;
+  double carry = 0.0;
+  for (int base = 0; base < T; base += 64) {
+    const int t = base + lane;
+    const bool in = t < T;
+    double w = 0.0;
+    if (in) {
+      w = ar.w[dst + t];
+      const int o = p.owner[dst + t];
+      if (o >= 0) {
+        p.owner[dst + t] = -1;
+        const int i = o < p.B ? t - p.start[o] : -1;
+        if (i >= 0 && i < p.kp) {  // (always, with the scratch as the mark pass left it)
+          const double x = fabs((double)p.prio[(size_t)o * p.kp + i]) + p.eps;
+          w = p.alpha == 1.0 ? x : pow(x, p.alpha);
+          ar.w[dst + t] = w;
+        }
+      }
+    }
+    const int valid = T - base < 64 ? T - base : 64;
+    const double c = seq_scan(w, valid, lane, carry);
+    if (in) ar.cw[dst + t] = c;
+  }
+  if (lane == 0) {
+    ar.t_w[slot] = p.weight_mode == 1 ? carry / (double)T : carry;
+    p.touched[slot] = 0;
+  }
 }
 
 }  // namespace mz

@@ -1,6 +1,9 @@
 // mz_replay.hip -- translation unit of the device-resident trajectory replay (mz_replay.cuh): argument checks and
-// launches of mzs_replay_store / mzs_replay_refresh / mzs_replay_sample / mzs_replay_gather_obs / mzs_replay_reanalyse.
+// launches of mzs_replay_store / mzs_replay_refresh / mzs_replay_sample / mzs_replay_gather_obs / mzs_replay_reanalyse /
+// mzs_replay_update_priorities.
 #include <hip/hip_runtime.h>
+
+#include <cstring>
 
 #include "mz_host.h"
 #include "mz_replay.cuh"
@@ -23,6 +26,14 @@ int check_arena(const mzs_replay_arena* ar, const char* who, mz::ReplayArena* ou
   out->t_start = ar->t_start; out->t_len = ar->t_len; out->t_w = ar->t_w; out->t_serial = (long long*)ar->t_serial;
   out->c_start = ar->c_start; out->c_len = ar->c_len; out->c_CW = ar->c_CW; out->c_serial = (long long*)ar->c_serial;
   return MZS_OK;
+}
+
+// finite, tested on the bits: the units are built with -fno-honor-nans, under which a comparison or std::isfinite may
+// be compiled as if no NaN could reach it
+bool finite_bits(double x) {
+  uint64_t u;
+  std::memcpy(&u, &x, sizeof u);
+  return (u & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
 }
 
 int waves_grid(int n) { return (n + mz::kReplayWaves - 1) / mz::kReplayWaves; }
@@ -158,6 +169,42 @@ int mzs_replay_reanalyse(const mzs_replay_arena* arena, const mzs_replay_reanaly
   p.desc = a->desc; p.gpow = a->gpow; p.pi = a->pi; p.v = a->v;
   hipLaunchKernelGGL(mz::replay_reanalyse_kernel, dim3(waves_grid(a->episodes)), dim3(64 * mz::kReplayWaves), 0,
                      static_cast<hipStream_t>(stream_), p);
+  MZS_HIP(nullptr, hipGetLastError());
+  return MZS_OK;
+}
+
+int mzs_replay_update_priorities(const mzs_replay_arena* arena, const mzs_replay_update_args* a, void* stream_) {
+  mz::ReplayUpdateArgs p{};
+  if (int rc = check_arena(arena, "mzs_replay_update_priorities", &p.ar)) return rc;
+  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_update_args))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: null arguments or size mismatch (ABI)");
+  if (a->head < 0 || a->head >= arena->capacity)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: head must be in 0..capacity - 1");
+  if (a->count < 0 || a->count > arena->capacity)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: count must be in 0..capacity");
+  if (a->batch < 0) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: batch must not be negative");
+  if (a->k_prio < 1 || (int64_t)a->batch * a->k_prio >= ((int64_t)1 << 31))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: k_prio must be >= 1, batch * k_prio < 2^31");
+  if (a->weight_mode != 1 && a->weight_mode != 2)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: weight_mode must be 1 (mean) or 2 (sum)");
+  if (!finite_bits(a->alpha) || a->alpha < 0.0 || a->alpha > 1.0)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: alpha must be in 0..1");
+  if (!finite_bits(a->eps) || a->eps < 0.0)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: eps must be finite and not negative");
+  if (a->batch > 0 && (!a->serial || !a->start || !a->prio))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: null serial, start or prio");
+  if (a->batch > 0 && (!a->owner || !a->touched))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: null owner or touched scratch");
+  if (a->batch == 0 || a->count == 0) return MZS_OK;
+  MZS_HIP(nullptr, hipSetDevice(arena->device));
+  p.head = a->head; p.count = a->count; p.B = a->batch; p.kp = a->k_prio; p.weight_mode = a->weight_mode;
+  p.alpha = a->alpha; p.eps = a->eps;
+  p.serial = (const long long*)a->serial; p.start = a->start; p.prio = a->prio;
+  p.owner = a->owner; p.touched = a->touched;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(mz::replay_prio_mark_kernel, dim3(waves_grid(a->batch)), dim3(64 * mz::kReplayWaves), 0, stream, p);
+  MZS_HIP(nullptr, hipGetLastError());
+  hipLaunchKernelGGL(mz::replay_prio_apply_kernel, dim3(waves_grid(a->count)), dim3(64 * mz::kReplayWaves), 0, stream, p);
   MZS_HIP(nullptr, hipGetLastError());
   return MZS_OK;
 }

@@ -9,6 +9,7 @@ There is no CPU fallback: without a GPU the first add raises."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from collections import deque, namedtuple
 
@@ -93,7 +94,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         self._device = None if device is None else torch.device(device)
         seed = int.from_bytes(os.urandom(4), "little") if random_seed is None else random_seed
         self._key = prng.PRNGKey(seed)
-        self._arena = self._t = None
+        self._arena = self._t = self._prio_scratch = None
         self._serial = 0
         self.clear()
 
@@ -387,6 +388,59 @@ class DeviceReplayBuffer(BaseReplayBuffer):
             self._touched[s] = self._clock
         self._dirty = True
         return plan.stream_rows
+
+    def update_priorities(self, indices, priorities, alpha=1.0, eps=0.0, weight="mean"):
+        """Priorities from training written back on the device: `indices` is the (serial [B], start [B]) pair of
+        `sample(with_indices=True)`, `priorities` a device tensor or an array, [B, kp] for the first kp transitions
+        of every window or [B] for the first one alone (the one whose weight decided the draw of the start).  The
+        addressed transitions get w = (|p| + eps) ** alpha in fp64 (alpha in 0..1; exactly |p| + eps with alpha 1),
+        their episodes new prefix sums and the buffer weight `weight` ("mean" or "sum") of their w; an episode no
+        row addresses keeps every byte, the weight given to `add` included.  Where rows address one transition the
+        last row wins, as in NumPy's w[idx] = p.  Skipped silently: a row whose episode has been evicted since the
+        sample (or a zero-filled row, serial -1), a negative start, a transition past the episode's end, a NaN or
+        infinite priority.  The search targets are not rewritten, so `stalest()` is unaffected.
+
+        Two launches on caller-invisible scratch; no device-to-host copy and no synchronisation.  ValueError before
+        anything is launched: indices and priorities that disagree in shape, alpha / eps / weight out of range, an
+        empty buffer.  Returns None."""
+        if weight not in _WEIGHT_MODES:
+            raise ValueError("weight must be 'mean' or 'sum'")
+        alpha, eps = float(alpha), float(eps)
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError("update_priorities: alpha must be in 0..1")
+        if not (eps >= 0.0 and math.isfinite(eps)):
+            raise ValueError("update_priorities: eps must be finite and not negative")
+        try:
+            serial, start = indices
+        except (TypeError, ValueError):
+            raise ValueError("update_priorities: indices must be the (serial, start) pair of sample(with_indices=True)")
+        serial, start, prio = (x if isinstance(x, torch.Tensor) else np.asarray(x) for x in (serial, start, priorities))
+        B = serial.shape[0] if serial.ndim == 1 else -1
+        if B < 0 or tuple(start.shape) != (B,):
+            raise ValueError(f"update_priorities: serial and start must be [B], got {tuple(serial.shape)} and "
+                             f"{tuple(start.shape)}")
+        if prio.ndim not in (1, 2) or prio.shape[0] != B or (prio.ndim == 2 and prio.shape[1] < 1):
+            raise ValueError(f"update_priorities: priorities must be [B] or [B, kp >= 1] with B = {B}, got "
+                             f"{tuple(prio.shape)}")
+        if not self._eps:
+            raise ValueError("cannot update the priorities of an empty buffer")
+        if B == 0:
+            return
+        dev = self._device
+        serial, start, prio = (torch.as_tensor(x).to(device=dev, dtype=dt).contiguous() for x, dt in
+                               ((serial, torch.int64), (start, torch.int32), (prio, torch.float32)))
+        if self._prio_scratch is None:  # owner [max_steps] = -1, touched [capacity] = 0; the kernels leave them so
+            self._prio_scratch = (torch.full((self._max_steps,), -1, dtype=torch.int32, device=dev),
+                                  torch.zeros(self._capacity, dtype=torch.int32, device=dev))
+        u = _lib.MzsReplayUpdateArgs()
+        u.struct_size = C.sizeof(_lib.MzsReplayUpdateArgs)
+        u.head, u.count, u.batch, u.k_prio = self._head, len(self._eps), B, prio.shape[1] if prio.ndim == 2 else 1
+        u.weight_mode, u.alpha, u.eps = _WEIGHT_MODES[weight], alpha, eps
+        u.serial, u.start, u.prio = serial.data_ptr(), start.data_ptr(), prio.data_ptr()
+        u.owner, u.touched = (x.data_ptr() for x in self._prio_scratch)
+        _lib.check(self._L.mzs_replay_update_priorities(C.byref(self._arena), C.byref(u), self._stream()))
+        self._keep = (serial, start, prio)
+        self._dirty = True
 
     def sample(self, batch_size=32, num_trajectory: int = None, k_steps: int = 5, sample_per_trajectory: int = 1,
                key=None, with_indices: bool = False):

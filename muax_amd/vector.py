@@ -149,12 +149,29 @@ def test_vector(model, venv, key, num_simulations: int, max_steps=None):
     return float(G.mean())
 
 
+def value_priorities(model, batch):
+    """New priorities of a sampled batch from the CURRENT network: |value(repr(obs[:, 0])) - Rn[:, 0]| as [B] float32
+    on the model's device -- the value error of every window's first transition, the one whose weight decided the
+    draw of the start.  The model's torch modules under no_grad, the scalar value decoded from the support logits as
+    in root inference; no synchronisation."""
+    import torch
+
+    from . import utils as mx_utils
+    dev = model.device
+    with torch.no_grad():
+        obs = torch.as_tensor(batch.obs, dtype=torch.float32, device=dev)
+        Rn = torch.as_tensor(batch.Rn, dtype=torch.float32, device=dev)
+        v_logits, _ = model.pred_func(model.repr_func(obs[:, 0]))
+        v = mx_utils.support_to_scalar(torch.softmax(v_logits, dim=-1), model._support_size).flatten()
+        return (v - Rn.reshape(Rn.shape[0], -1)[:, 0]).abs()
+
+
 def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, alpha=0.5, buffer=None,
                iterations: int = 100, steps_per_iteration: int = 64, num_simulations: int = 50, k_steps: int = 10,
                num_trajectory: int = 32, sample_per_trajectory: int = 1, num_update_per_iteration: int = 50,
                max_training_steps: int = 10000, test_interval: int = 10, num_test_episodes: int = 10,
                random_seed: int = 42, temperature_fn=None, metrics=None, trajectory_weight: str = "mean",
-               reanalyse_every: int = 0, reanalyse_episodes=None):
+               reanalyse_every: int = 0, reanalyse_episodes=None, priority_update: bool = False):
     """The reference's fit() loop (muax/train.py:175-241: temperature schedule, buffer sampling, update,
     greedy test) with the acting half on a vector environment: per iteration `steps_per_iteration`
     batched act() calls -> finished episodes -> buffer, then `num_update_per_iteration` updates.
@@ -164,7 +181,11 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     `reanalyse_every` > 0 (a buffer with `reanalyse`, i.e. the device buffer): before the updates of every
     `reanalyse_every`-th iteration the `reanalyse_episodes` episodes (default: all) whose targets are the oldest are
     searched again with the current network (`DeviceReplayBuffer.reanalyse`, `num_simulations` simulations, act()'s
-    other defaults), its key one extra split of the running key; 0: the key stream and every result are unchanged."""
+    other defaults), its key one extra split of the running key; 0: the key stream and every result are unchanged.
+    `priority_update` (a buffer with `update_priorities`, i.e. the device buffer): every batch is sampled with its
+    indices and, after its `update()`, `value_priorities` of the updated network are written back to the window starts
+    with the loop's `alpha` (exponent 1 when `alpha` is None) and `weight=trajectory_weight`.  False, or a buffer
+    without the method: the key stream and every result are unchanged."""
     if trajectory_weight not in ("mean", "sum"):
         raise ValueError("trajectory_weight must be 'mean' or 'sum'")
     from .replay_buffer import TrajectoryReplayBuffer
@@ -172,6 +193,7 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     temperature_fn = temperature_fn or _temperature_fn
     buffer = buffer if buffer is not None else TrajectoryReplayBuffer(500)
     collector = VectorCollector(venv, n_step, gamma, alpha)
+    prioritise = bool(priority_update) and hasattr(buffer, "update_priorities")
     key = prng.PRNGKey(random_seed)
     key, test_key, subkey = prng.split(key, 3)
     model.init(subkey, np.asarray(venv.reset())[:1].astype(float))
@@ -197,8 +219,16 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
         if len(buffer):
             loss = 0.0
             for _ in range(num_update_per_iteration):
-                loss += model.update(buffer.sample(num_trajectory=num_trajectory,
-                                                   sample_per_trajectory=sample_per_trajectory, k_steps=k_steps))["loss"]
+                if prioritise:
+                    batch, indices = buffer.sample(num_trajectory=num_trajectory, k_steps=k_steps,
+                                                   sample_per_trajectory=sample_per_trajectory, with_indices=True)
+                else:
+                    batch = buffer.sample(num_trajectory=num_trajectory,
+                                          sample_per_trajectory=sample_per_trajectory, k_steps=k_steps)
+                loss += model.update(batch)["loss"]
+                if prioritise:
+                    buffer.update_priorities(indices, value_priorities(model, batch),
+                                             alpha=1.0 if alpha is None else alpha, weight=trajectory_weight)
                 training_step += 1
             row["loss"] = loss / num_update_per_iteration
         row["training_step"] = training_step

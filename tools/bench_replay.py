@@ -4,10 +4,15 @@ and each `sample` on its own.  Default MLP trio on CartPole shapes, 500 stored e
 
     python tools/bench_replay.py [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
     python tools/bench_replay.py --reanalyse [--iters 200] [--episodes 500]
+    python tools/bench_replay.py --priorities [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
 
 `--reanalyse` times, on the same device buffer and with 50 simulations, (a) `DeviceReplayBuffer.reanalyse()` of the
 whole buffer, (b) the same work through the host -- `episode().obs` downloaded, `act` NumPy in / out in the same
 chunks, `vector.episode_trajectory`, `add_many` into a second buffer -- and (c) the `act()` chunks of (a) alone.
+
+`--priorities` times, on the device buffer alone, the training step with the priority write-back --
+`sample(with_indices=True)` + `update()` + `vector.value_priorities` + `update_priorities` -- beside `sample`,
+`sample` + `update()` and `update()` as the default mode times them, and the two new parts on their own.
 
 Every figure is the median of `--iters` iterations, each ending in a device synchronise, after 30 ms of untimed
 iterations of the same work (clocks settled).  The two routes alternate shape by shape in one process."""
@@ -110,9 +115,36 @@ def reanalyse_figures(dev, iters, simulations=50, chunk_rows=4096, n=10, gamma=0
     print(f"(a) - (c): gather, copies, write-back  {ta - tc:9.3f}   ({100 * (ta - tc) / ta:.1f} % of (a))", flush=True)
 
 
+def priority_figures(dev, shapes, iters, alpha=0.5):
+    from muax_amd.vector import value_priorities
+    print(f"{'num_trajectory x k':>18} | {'dev sample':>10} {'dev s+upd':>9} {'update':>7} | {'value_prio':>10} "
+          f"{'update_prio':>11} | {'s+upd+prio':>10} | {'s+upd+prio / s+upd':>18}")
+    for n, k in shapes:
+        m_dev, m_pri = model(), model()
+        fixed, indices = dev.sample(num_trajectory=n, k_steps=k, with_indices=True)
+        prio = value_priorities(m_pri, fixed)
+
+        def step_with_priorities():
+            batch, idx = dev.sample(num_trajectory=n, k_steps=k, with_indices=True)
+            m_pri.update(batch, backend="hip")
+            dev.update_priorities(idx, value_priorities(m_pri, batch), alpha=alpha)
+
+        res = {
+            "ds": median_ms(lambda: dev.sample(num_trajectory=n, k_steps=k), iters),
+            "du": median_ms(lambda: m_dev.update(dev.sample(num_trajectory=n, k_steps=k), backend="hip"), iters),
+            "u": median_ms(lambda: m_dev.update(fixed, backend="hip"), iters),
+            "vp": median_ms(lambda: value_priorities(m_pri, fixed), iters),
+            "up": median_ms(lambda: dev.update_priorities(indices, prio, alpha=alpha), iters),
+            "dp": median_ms(step_with_priorities, iters),
+        }
+        print(f"{n:>13} x {k:<2} | {res['ds']:10.3f} {res['du']:9.3f} {res['u']:7.3f} | {res['vp']:10.3f} "
+              f"{res['up']:11.3f} | {res['dp']:10.3f} | {res['dp'] / res['du']:17.2f}x", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reanalyse", action="store_true", help="time reanalysis instead of sampling")
+    ap.add_argument("--priorities", action="store_true", help="time the training step with the priority write-back")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--episodes", type=int, default=500)
     ap.add_argument("--shape", action="append", default=[], metavar="NUM_TRAJECTORY,K")
@@ -131,6 +163,9 @@ def main():
           f"(one upload, one launch); median of {a.iters} synchronised iterations, ms")
     if a.reanalyse:
         reanalyse_figures(dev, a.iters)
+        return
+    if a.priorities:
+        priority_figures(dev, shapes, a.iters)
         return
     print(f"{'num_trajectory x k':>18} | {'host sample':>11} {'host s+upd':>10} | {'dev sample':>10} {'dev s+upd':>9} | "
           f"{'update':>7} | {'s+upd host/dev':>14} {'sample host/dev':>15}")
