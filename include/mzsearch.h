@@ -678,6 +678,37 @@ typedef struct mzs_replay_update_args {
 } mzs_replay_update_args;
 int mzs_replay_update_priorities(const mzs_replay_arena *arena, const mzs_replay_update_args *a, void *stream);
 
+/* ---- forward value unroll of the default MLP trio: the priorities mzs_replay_update_priorities takes ----
+ * For every window j < batch and step i < k_prio, with s_0 = Representation(obs[j]) and s_{i+1} = the next state of
+ * Dynamic(s_i, actions[j][i]) (muax/nn.py:59-115):
+ *   values[j][i] = support_to_scalar(softmax(value head(s_i)))     prio[j][i] = |values[j][i] - returns[j][i]|
+ * One launch, one wavefront per window; the policy head and the reward head are not evaluated.  The arithmetic is the
+ * spec's ("MZ-F32"): values has the bits of the oracle's root_inference / recurrent_inference chain for any widths, prio
+ * is one fp32 subtraction with the sign cleared (a NaN or infinite return gives a NaN or infinite priority, which
+ * mzs_replay_update_priorities skips).  No atomics: the same bits on every run.  No allocation, no synchronisation, no
+ * copy to the host.  `actions` and `returns` are read with the row stride row_steps, of which the first k_prio columns
+ * are used; an action outside 0..num_actions - 1 is the all-zero one-hot (nothing is indexed by it).
+ * Limits, checked before any launch, the message naming the limit: MZS_E_UNSUPPORTED for obs_dim outside 1..128,
+ * embed_dim outside 1..64, num_actions outside 1..64, support_size outside 8..31; MZS_E_INVALID for struct sizes, a
+ * null weight / input pointer, batch < 1, k_prio outside 1..row_steps, values and prio both NULL.
+ * errors: mzs_last_error(NULL) */
+typedef struct mzs_unroll_args {
+  int32_t struct_size;      /* = sizeof(mzs_unroll_args) */
+  int32_t device;
+  int32_t batch;            /* B windows */
+  int32_t row_steps;        /* L: row stride of actions and returns */
+  int32_t k_prio;           /* kp <= L steps evaluated */
+  int32_t num_actions;
+  int32_t embed_dim;
+  int32_t reserved0;
+  const float *obs;         /* [B, obs_dim] */
+  const int32_t *actions;   /* [B, L] */
+  const float *returns;     /* [B, L] */
+  float *values;            /* out [B, kp] or NULL */
+  float *prio;              /* out [B, kp] or NULL */
+} mzs_unroll_args;
+int mzs_mlp_unroll_values(const mzs_mlp_weights *w, const mzs_unroll_args *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,12 @@ class MzsReplayUpdateArgs(C.Structure):
                 + [(n, _vp) for n in ("serial", "start", "prio", "owner", "touched")])
 
 
+class MzsUnrollArgs(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("device", C.c_int32), ("batch", C.c_int32), ("row_steps", C.c_int32),
+                 ("k_prio", C.c_int32), ("num_actions", C.c_int32), ("embed_dim", C.c_int32), ("reserved0", C.c_int32)]
+                + [(n, _vp) for n in ("obs", "actions", "returns", "values", "prio")])
+
+
 EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_destroy",
                     "mzs_mlp_set_weights", "mzs_act_mlp", "mzs_root", "mzs_root_gumbel", "mzs_select",
                     "mzs_expand_backup", "mzs_expand_backup_select",
@@ -176,7 +182,8 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_mlp_allow_wide", "mzs_mlp_wide_plan",
                     "mzs_mlp_allow_wide_gumbel", "mzs_mlp_wide_plan_policy",
                     "mzs_replay_store", "mzs_replay_refresh", "mzs_replay_sample",
-                    "mzs_replay_gather_obs", "mzs_replay_reanalyse", "mzs_replay_update_priorities"]
+                    "mzs_replay_gather_obs", "mzs_replay_reanalyse", "mzs_replay_update_priorities",
+                    "mzs_mlp_unroll_values"]
 
 _lib = None
 
@@ -248,6 +255,7 @@ def load(build_if_missing: bool = True):
     L.mzs_replay_gather_obs.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayGatherArgs), _vp]
     L.mzs_replay_reanalyse.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayReanalyseArgs), _vp]
     L.mzs_replay_update_priorities.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayUpdateArgs), _vp]
+    L.mzs_mlp_unroll_values.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsUnrollArgs), _vp]
     L.mzs_tower_pair_scratch_bytes.restype = C.c_int64
     if L.mzs_abi_version() != 1:
         raise RuntimeError("libmzsearch.so ABI version mismatch")

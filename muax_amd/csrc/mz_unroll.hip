@@ -1,0 +1,54 @@
+// mz_unroll.hip -- translation unit of the forward value unroll (mz_unroll.cuh): argument checks and the one launch of
+// mzs_mlp_unroll_values.  Built like the other units of the arithmetic spec (-ffp-contract=off).
+#include <hip/hip_runtime.h>
+
+#include "mz_host.h"
+#include "mz_unroll.cuh"
+
+using mzh::fail;
+
+extern "C" {
+
+int mzs_mlp_unroll_values(const mzs_mlp_weights* w, const mzs_unroll_args* a, void* stream_) {
+  if (!w || w->struct_size != (int32_t)sizeof(mzs_mlp_weights))
+    return fail(nullptr, MZS_E_INVALID, "mzs_mlp_unroll_values: null weights or size mismatch (ABI)");
+  if (!a || a->struct_size != (int32_t)sizeof(mzs_unroll_args))
+    return fail(nullptr, MZS_E_INVALID, "mzs_mlp_unroll_values: null arguments or size mismatch (ABI)");
+  const float* const* ptrs = &w->repr_w;
+  for (int i = 0; i < 18; ++i)
+    if (!ptrs[i]) return fail(nullptr, MZS_E_INVALID, "mzs_mlp_unroll_values: null weight pointer");
+  if (a->batch < 1) return fail(nullptr, MZS_E_INVALID, "mzs_mlp_unroll_values: batch must be >= 1");
+  if (a->row_steps < 1 || a->k_prio < 1 || a->k_prio > a->row_steps)
+    return fail(nullptr, MZS_E_INVALID, "mzs_mlp_unroll_values: k_prio must be in 1..row_steps");
+  if (!a->obs || !a->actions || !a->returns)
+    return fail(nullptr, MZS_E_INVALID, "mzs_mlp_unroll_values: null obs, actions or returns");
+  if (!a->values && !a->prio)
+    return fail(nullptr, MZS_E_INVALID, "mzs_mlp_unroll_values: at least one of values and prio must be given");
+  if (w->obs_dim < 1 || w->obs_dim > 128) return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_mlp_unroll_values: obs_dim must be 1..128");
+  if (a->embed_dim < 1 || a->embed_dim > 64)
+    return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_mlp_unroll_values: embed_dim must be 1..64");
+  if (a->num_actions < 1 || a->num_actions > 64)
+    return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_mlp_unroll_values: num_actions must be 1..64");
+  if (w->support_size < 8 || w->support_size > 31)
+    return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_mlp_unroll_values: support_size must be 8..31");
+  if (int rc = mzh::select_device(a->device, "mzs_mlp_unroll_values")) return rc;
+  mz::UnrollArgs p{};
+  mz::MlpGen& g = p.w;
+  g.repr_w = w->repr_w; g.repr_b = w->repr_b;
+  g.pv_w1 = w->pv_w1; g.pv_b1 = w->pv_b1; g.pv_w2 = w->pv_w2; g.pv_b2 = w->pv_b2;
+  g.pp_w1 = w->pp_w1; g.pp_b1 = w->pp_b1; g.pp_w2 = w->pp_w2; g.pp_b2 = w->pp_b2;
+  g.dr_w1 = w->dr_w1; g.dr_b1 = w->dr_b1; g.dr_w2 = w->dr_w2; g.dr_b2 = w->dr_b2;
+  g.dn_w1 = w->dn_w1; g.dn_b1 = w->dn_b1; g.dn_w2 = w->dn_w2; g.dn_b2 = w->dn_b2;
+  g.obs_dim = w->obs_dim; g.E = a->embed_dim; g.A = a->num_actions; g.F = 2 * w->support_size + 1;
+  g.support = w->support_size; g.pred_on_parent = 0; g.discount = w->discount;
+  p.B = a->batch; p.L = a->row_steps; p.kp = a->k_prio;
+  p.obs = a->obs; p.act = a->actions; p.Rn = a->returns; p.values = a->values; p.prio = a->prio;
+  // the trio's scratch with the observation in the place of [s, onehot]: 2.2 KiB at the widest shape
+  const int ew = g.E > g.obs_dim ? g.E : g.obs_dim;
+  const size_t lds = sizeof(float) * (size_t)mz::gen_scratch_words(ew, g.A);
+  hipLaunchKernelGGL(mz::mz_mlp_unroll_kernel, dim3(a->batch), dim3(64), lds, static_cast<hipStream_t>(stream_), p);
+  MZS_HIP(nullptr, hipGetLastError());
+  return MZS_OK;
+}
+
+}  // extern "C"

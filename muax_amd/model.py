@@ -103,6 +103,7 @@ class MuZero:
         self._loaded_opt_state = None
         self._param_list = None
         self._fused_train = None
+        self._fused_unroll = None
         self._disc_const = None
         self._fused = {}
         self._root_graphs = {}
@@ -129,6 +130,7 @@ class MuZero:
                                          for m in self.network])
         self._weights_version += 1
         self._fused_train = None
+        self._fused_unroll = None
         return self._params
 
     @property
@@ -583,6 +585,30 @@ class MuZero:
         self._optimizer.step()
         self._weights_version += 1
         return {"loss": float(loss.item())}
+
+    def unroll_values(self, batch, k_prio=None, backend: str = "auto"):
+        """The forward unroll of a sampled batch with the CURRENT network: `(values, priorities)`, both [B, kp] float32
+        on the model's device, with v_i = value(s_i), s_0 = repr(obs[:, 0]), s_{i+1} = dynamics(s_i, a[:, i]) and
+        priorities = |v_i - Rn[:, i]| -- what `DeviceReplayBuffer.update_priorities` takes for the first `kp` steps of
+        every window.  `k_prio` defaults to the window length L and must be in 1..L.  backend "hip": ONE launch
+        (mzs_mlp_unroll_values, muax_amd/csrc/mz_unroll.cuh) for the default MLP trio on a GPU, obs_dim 1..128,
+        embedding 1..64, 1..64 actions, support_size 8..31; values then have the bits of act()'s root value.  "torch": the
+        model's modules under no_grad, any nets, any device.  "auto": the kernel where it applies, else torch.  No
+        synchronisation either way."""
+        from . import unroll as mz_unroll
+        if backend not in ("auto", "hip", "torch"):
+            raise ValueError(f"backend must be 'auto', 'hip' or 'torch', got {backend!r}")
+        if self._params is None:
+            raise ValueError("call init() first")
+        _, _, kp = mz_unroll.batch_window(batch, k_prio)
+        trio = self.device.type == "cuda" and mz_nn.is_default_mlp_trio(self.network)
+        if backend == "hip" and not trio:
+            raise ValueError("backend='hip' needs the default MLP trio on a GPU")
+        if backend == "torch" or not trio or (backend == "auto" and not mz_unroll.within_limits(self)):
+            return mz_unroll.torch_unroll_values(self, batch, kp)
+        if self._fused_unroll is None:
+            self._fused_unroll = mz_unroll.FusedUnrollValues(self)
+        return self._fused_unroll(batch, kp)  # (backend="hip" beyond the limits: the library's error, the limit named)
 
     def save_load(self, file, save=True):
         """muax/model.py:203-212, on torch state dicts (the reference pickles haiku params)."""

@@ -166,12 +166,21 @@ def value_priorities(model, batch):
         return (v - Rn.reshape(Rn.shape[0], -1)[:, 0]).abs()
 
 
+def unroll_value_priorities(model, batch, k_prio=None, backend: str = "auto"):
+    """The [B, kp] sibling of `value_priorities`: |v_i - Rn[:, i]| for the first `kp` steps of every window (default: all
+    of them), v_i the value of the state the CURRENT network unrolls to along the window's actions --
+    `MuZero.unroll_values(batch, k_prio, backend)[1]`: one kernel launch for the default MLP trio on a GPU, else the
+    model's torch modules.  float32 on the model's device, no synchronisation."""
+    return model.unroll_values(batch, k_prio=k_prio, backend=backend)[1]
+
+
 def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, alpha=0.5, buffer=None,
                iterations: int = 100, steps_per_iteration: int = 64, num_simulations: int = 50, k_steps: int = 10,
                num_trajectory: int = 32, sample_per_trajectory: int = 1, num_update_per_iteration: int = 50,
                max_training_steps: int = 10000, test_interval: int = 10, num_test_episodes: int = 10,
                random_seed: int = 42, temperature_fn=None, metrics=None, trajectory_weight: str = "mean",
-               reanalyse_every: int = 0, reanalyse_episodes=None, priority_update: bool = False):
+               reanalyse_every: int = 0, reanalyse_episodes=None, priority_update: bool = False,
+               priority_steps=None):
     """The reference's fit() loop (muax/train.py:175-241: temperature schedule, buffer sampling, update,
     greedy test) with the acting half on a vector environment: per iteration `steps_per_iteration`
     batched act() calls -> finished episodes -> buffer, then `num_update_per_iteration` updates.
@@ -185,7 +194,12 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     `priority_update` (a buffer with `update_priorities`, i.e. the device buffer): every batch is sampled with its
     indices and, after its `update()`, `value_priorities` of the updated network are written back to the window starts
     with the loop's `alpha` (exponent 1 when `alpha` is None) and `weight=trajectory_weight`.  False, or a buffer
-    without the method: the key stream and every result are unchanged."""
+    without the method: the key stream and every result are unchanged.
+    `priority_steps`: None writes `value_priorities` back (one transition per window); an integer kp >= 1 writes
+    `unroll_value_priorities(model, batch, min(kp, k_steps))` instead, one priority for each of the first kp transitions
+    of every window.  Ignored where `priority_update` is off or the buffer has no `update_priorities`."""
+    if priority_steps is not None and int(priority_steps) < 1:
+        raise ValueError("priority_steps must be None or >= 1")
     if trajectory_weight not in ("mean", "sum"):
         raise ValueError("trajectory_weight must be 'mean' or 'sum'")
     from .replay_buffer import TrajectoryReplayBuffer
@@ -227,7 +241,9 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                                           sample_per_trajectory=sample_per_trajectory, k_steps=k_steps)
                 loss += model.update(batch)["loss"]
                 if prioritise:
-                    buffer.update_priorities(indices, value_priorities(model, batch),
+                    prio = value_priorities(model, batch) if priority_steps is None else \
+                        unroll_value_priorities(model, batch, min(int(priority_steps), k_steps))
+                    buffer.update_priorities(indices, prio,
                                              alpha=1.0 if alpha is None else alpha, weight=trajectory_weight)
                 training_step += 1
             row["loss"] = loss / num_update_per_iteration

@@ -4,7 +4,7 @@ and each `sample` on its own.  Default MLP trio on CartPole shapes, 500 stored e
 
     python tools/bench_replay.py [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
     python tools/bench_replay.py --reanalyse [--iters 200] [--episodes 500]
-    python tools/bench_replay.py --priorities [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
+    python tools/bench_replay.py --priorities [--prio-steps KP] [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
 
 `--reanalyse` times, on the same device buffer and with 50 simulations, (a) `DeviceReplayBuffer.reanalyse()` of the
 whole buffer, (b) the same work through the host -- `episode().obs` downloaded, `act` NumPy in / out in the same
@@ -12,7 +12,9 @@ chunks, `vector.episode_trajectory`, `add_many` into a second buffer -- and (c) 
 
 `--priorities` times, on the device buffer alone, the training step with the priority write-back --
 `sample(with_indices=True)` + `update()` + `vector.value_priorities` + `update_priorities` -- beside `sample`,
-`sample` + `update()` and `update()` as the default mode times them, and the two new parts on their own.
+`sample` + `update()` and `update()` as the default mode times them, and the two new parts on their own.  Side by side
+with it, for `--prio-steps` kp (default: k) priorities per window: `MuZero.unroll_values` on the torch modules and as one
+kernel launch (`backend="torch"` / `"hip"`), the write-back of [B, kp] priorities, and the whole step with each.
 
 Every figure is the median of `--iters` iterations, each ending in a device synchronise, after 30 ms of untimed
 iterations of the same work (clocks settled).  The two routes alternate shape by shape in one process."""
@@ -115,19 +117,29 @@ def reanalyse_figures(dev, iters, simulations=50, chunk_rows=4096, n=10, gamma=0
     print(f"(a) - (c): gather, copies, write-back  {ta - tc:9.3f}   ({100 * (ta - tc) / ta:.1f} % of (a))", flush=True)
 
 
-def priority_figures(dev, shapes, iters, alpha=0.5):
-    from muax_amd.vector import value_priorities
+def priority_figures(dev, shapes, iters, prio_steps=None, alpha=0.5):
+    from muax_amd.vector import unroll_value_priorities, value_priorities
     print(f"{'num_trajectory x k':>18} | {'dev sample':>10} {'dev s+upd':>9} {'update':>7} | {'value_prio':>10} "
           f"{'update_prio':>11} | {'s+upd+prio':>10} | {'s+upd+prio / s+upd':>18}")
+    unrolled = []
     for n, k in shapes:
         m_dev, m_pri = model(), model()
         fixed, indices = dev.sample(num_trajectory=n, k_steps=k, with_indices=True)
         prio = value_priorities(m_pri, fixed)
+        kp = min(prio_steps or k, k)
+        prio_kp = unroll_value_priorities(m_pri, fixed, kp, backend="hip")
 
         def step_with_priorities():
             batch, idx = dev.sample(num_trajectory=n, k_steps=k, with_indices=True)
             m_pri.update(batch, backend="hip")
             dev.update_priorities(idx, value_priorities(m_pri, batch), alpha=alpha)
+
+        def step_unrolled(backend):
+            def step():
+                batch, idx = dev.sample(num_trajectory=n, k_steps=k, with_indices=True)
+                m_pri.update(batch, backend="hip")
+                dev.update_priorities(idx, unroll_value_priorities(m_pri, batch, kp, backend=backend), alpha=alpha)
+            return step
 
         res = {
             "ds": median_ms(lambda: dev.sample(num_trajectory=n, k_steps=k), iters),
@@ -139,12 +151,26 @@ def priority_figures(dev, shapes, iters, alpha=0.5):
         }
         print(f"{n:>13} x {k:<2} | {res['ds']:10.3f} {res['du']:9.3f} {res['u']:7.3f} | {res['vp']:10.3f} "
               f"{res['up']:11.3f} | {res['dp']:10.3f} | {res['dp'] / res['du']:17.2f}x", flush=True)
+        unrolled.append((n, k, kp, res["vp"], res["dp"], res["du"], {
+            "ut": median_ms(lambda: m_pri.unroll_values(fixed, kp, backend="torch"), iters),
+            "uh": median_ms(lambda: m_pri.unroll_values(fixed, kp, backend="hip"), iters),
+            "upk": median_ms(lambda: dev.update_priorities(indices, prio_kp, alpha=alpha), iters),
+            "st": median_ms(step_unrolled("torch"), iters),
+            "sh": median_ms(step_unrolled("hip"), iters),
+        }))
+    print(f"\n{'num_trajectory x k':>18} | {'kp':>2} | {'value_prio [B]':>14} {'unroll torch':>12} {'unroll hip':>10} | "
+          f"{'update_prio kp':>14} | {'step [B]':>8} {'step torch':>10} {'step hip':>8} | {'step hip / s+upd':>16}")
+    for n, k, kp, vp, dp, du, r in unrolled:
+        print(f"{n:>13} x {k:<2} | {kp:>2} | {vp:14.3f} {r['ut']:12.3f} {r['uh']:10.3f} | {r['upk']:14.3f} | "
+              f"{dp:8.3f} {r['st']:10.3f} {r['sh']:8.3f} | {r['sh'] / du:15.2f}x", flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reanalyse", action="store_true", help="time reanalysis instead of sampling")
     ap.add_argument("--priorities", action="store_true", help="time the training step with the priority write-back")
+    ap.add_argument("--prio-steps", type=int, default=None, metavar="KP",
+                    help="with --priorities: priorities per window of the unrolled routes (default: k)")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--episodes", type=int, default=500)
     ap.add_argument("--shape", action="append", default=[], metavar="NUM_TRAJECTORY,K")
@@ -165,7 +191,7 @@ def main():
         reanalyse_figures(dev, a.iters)
         return
     if a.priorities:
-        priority_figures(dev, shapes, a.iters)
+        priority_figures(dev, shapes, a.iters, a.prio_steps)
         return
     print(f"{'num_trajectory x k':>18} | {'host sample':>11} {'host s+upd':>10} | {'dev sample':>10} {'dev s+upd':>9} | "
           f"{'update':>7} | {'s+upd host/dev':>14} {'sample host/dev':>15}")
