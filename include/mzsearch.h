@@ -294,6 +294,15 @@ int64_t mzs_mlp_train_workspace_bytes(int32_t batch, int32_t obs_dim, int32_t em
                                       int32_t num_actions, int32_t support_size);
 /* errors: mzs_last_error(NULL) */
 int mzs_mlp_loss_grad(const mzs_mlp_weights *w, const mzs_train_args *a, void *stream);
+/* The same step with a weight per batch row (importance sampling of prioritised replay):
+ * sample_weight [B] float32 on the device multiplies the three cross entropies of row j at EVERY unroll step --
+ *   loss = sum_j loss_scale * sample_weight[j] * sum_i (CE_r + CE_v + CE_pi)(j, i)  +  l2_coeff * 0.5 * sum ||w||^2
+ * -- and with them the row's whole gradient; the L2 term is not weighted.  Same kernels, same instances (listed or
+ * registered), same workspace, same limits and errors as the unweighted entry, reported under its name; weights of 1
+ * give its bits.  The values are not inspected: a weight of 0 makes the row contribute exact zeros while its data is
+ * finite.  A null sample_weight is MZS_E_INVALID.  errors: mzs_last_error(NULL) */
+int mzs_mlp_loss_grad_weighted(const mzs_mlp_weights *w, const mzs_train_args *a, const float *sample_weight,
+                               void *stream);
 
 /* ---- next-state tower of the ResNet dynamics net ----
  * mzs_resnet_tower evaluates, for a batch of 6x6x64 hidden states (NHWC, the reference's embedding
@@ -596,6 +605,30 @@ typedef struct mzs_replay_sample_args {
   int32_t *start;          /* out [batch] */
 } mzs_replay_sample_args;
 int mzs_replay_sample(const mzs_replay_arena *arena, const mzs_replay_sample_args *a, void *stream);
+
+/* The same batch -- every output of mzs_replay_sample for the same key, bit for bit -- and the importance-sampling
+ * weight of every row (Schaul et al. 2016, 3.4; MuZero Appendix G is beta = 1), in fp64, in this operation order:
+ *   p_e = (CW[e] - CW[e - 1]) / CW[count - 1]   (CW[-1] = 0; 1 when CW[count - 1] == 0: the draw is deterministic)
+ *   p_s = (cw[i] - cw[i - 1]) / cw[m - 1]       (cw[-1] = 0; 1 / (double)m when cw[m - 1] == 0: the uniform start)
+ *   q   = p_e * p_s        the probability that a row is window (e, i), whatever rows share its episode
+ *   raw = 1.0 / (num_windows * q) with beta == 1.0, pow(num_windows * q, -beta) otherwise (exactly 1 with beta == 0);
+ *         0 for a zero-filled row (serial -1), which therefore does not train
+ *   isw = (float)raw, or with normalize != 0 (float)(raw / the largest raw of the batch), the maximum taken in fp64;
+ *         a batch of zero-filled rows alone gives zeros.
+ * num_windows is the caller's count of eligible windows: the sum of length - k_steps over the live episodes longer than
+ * k_steps.  One launch, and with normalize a second one of a single workgroup over `scratch`; deterministic; neither
+ * synchronises or copies to the host.  MZS_E_INVALID before any launch for what mzs_replay_sample refuses, a struct
+ * size, beta outside 0..1 or not finite, num_windows below 1 or not finite, a null isw, normalize with a null scratch. */
+typedef struct mzs_replay_is_args {
+  int32_t struct_size;     /* = sizeof(mzs_replay_is_args) */
+  int32_t normalize;       /* != 0: divide by the batch maximum */
+  double beta;             /* 0..1 */
+  double num_windows;      /* N >= 1 */
+  float *isw;              /* out [batch] */
+  double *scratch;         /* [batch], or NULL with normalize == 0 */
+} mzs_replay_is_args;
+int mzs_replay_sample_is(const mzs_replay_arena *arena, const mzs_replay_sample_args *a, const mzs_replay_is_args *w,
+                         void *stream);
 
 /* Reanalysis: fresh search results for episodes the arenas already hold, without the host.  Between
  * the two calls the caller runs its searches on the gathered observations.  Both take the descriptors of

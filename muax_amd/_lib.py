@@ -145,6 +145,11 @@ class MzsReplaySampleArgs(C.Structure):
                 + [(n, _vp) for n in ("obs", "a", "r", "Rn", "v", "done", "pi", "w", "serial", "start")])
 
 
+class MzsReplayIsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("normalize", C.c_int32), ("beta", C.c_double), ("num_windows", C.c_double),
+                ("isw", _vp), ("scratch", _vp)]
+
+
 class MzsReplayGatherArgs(C.Structure):
     _fields_ = ([("struct_size", C.c_int32), ("episodes", C.c_int32), ("stream_rows", C.c_int64),
                  ("rows_padded", C.c_int64)] + [(n, _vp) for n in ("desc", "desc_host", "obs")])
@@ -183,7 +188,7 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_mlp_allow_wide_gumbel", "mzs_mlp_wide_plan_policy",
                     "mzs_replay_store", "mzs_replay_refresh", "mzs_replay_sample",
                     "mzs_replay_gather_obs", "mzs_replay_reanalyse", "mzs_replay_update_priorities",
-                    "mzs_mlp_unroll_values"]
+                    "mzs_mlp_unroll_values", "mzs_replay_sample_is", "mzs_mlp_loss_grad_weighted"]
 
 _lib = None
 
@@ -252,6 +257,9 @@ def load(build_if_missing: bool = True):
     L.mzs_replay_store.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayStoreArgs), _vp]
     L.mzs_replay_refresh.argtypes = [C.POINTER(MzsReplayArena), C.c_int32, C.c_int32, C.c_int32, _vp]
     L.mzs_replay_sample.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplaySampleArgs), _vp]
+    L.mzs_replay_sample_is.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplaySampleArgs),
+                                       C.POINTER(MzsReplayIsArgs), _vp]
+    L.mzs_mlp_loss_grad_weighted.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsTrainArgs), _vp, _vp]
     L.mzs_replay_gather_obs.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayGatherArgs), _vp]
     L.mzs_replay_reanalyse.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayReanalyseArgs), _vp]
     L.mzs_replay_update_priorities.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayUpdateArgs), _vp]

@@ -8,7 +8,8 @@
 //   replay_refresh_kernel  the live episodes, oldest first, as a compact table with the inclusive prefix sum CW of the
 //                          weights of those longer than k_steps (one wavefront; after adds or a change of k_steps)
 //   replay_sample_kernel   per batch row: two threefry draws, the episode and the start by binary search in CW / cw,
-//                          then 64 lanes copy the window
+//                          then 64 lanes copy the window; replay_sample_is_kernel, the same rows, adds the row's
+//                          importance-sampling weight, which replay_is_normalise_kernel scales by the batch maximum
 // and the two of reanalysis (fresh search results for episodes already held), again one wavefront per episode:
 //   replay_gather_obs_kernel  the observations of the selected episodes as one dense stream, zero-padded to whole chunks
 //   replay_reanalyse_kernel   new pi and v in place; Rn, done, w from the STORED rewards and the new values by the store
@@ -78,6 +79,12 @@ struct ReplaySampleArgs {
   uint32_t key0, key1;
   float* obs; int32_t* a; float* r; float* Rn; float* v; uint8_t* done; float* pi; float* w;
   long long* serial; int32_t* start;
+};
+
+struct ReplayIsArgs {
+  double beta, N;             // exponent in 0..1; eligible windows: the sum of len - k over the live episodes with len > k
+  double* raw;                // [B] scratch of the normalisation pass, or null: isw is written by the sample kernel
+  float* isw;                 // [B]
 };
 
 struct ReplayUpdateArgs {
@@ -255,7 +262,11 @@ __global__ void __launch_bounds__(64) replay_refresh_kernel(ReplayArena ar, int 
   }
 }
 
-__global__ void __launch_bounds__(64 * kReplayWaves) replay_sample_kernel(ReplaySampleArgs p) {
+// One batch row of a sample; with IS also the row's importance-sampling weight: raw = (N q) ** -beta
+// in fp64 from the very sums the two searches read, 0 for a zero-filled row; to q.raw for the normalisation pass, or,
+// without one, rounded to q.isw.  The draws, the searches and every copy are the same code with and without IS.
+template <bool IS>
+MZ_DEV void replay_sample_row(const ReplaySampleArgs& p, const ReplayIsArgs& q) {
   const int lane = threadIdx.x & 63;
   const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
   if (row >= p.B) return;
@@ -277,6 +288,11 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_sample_kernel(Replay
       p.a[ok + i] = 0; p.r[ok + i] = 0.f; p.Rn[ok + i] = 0.f; p.v[ok + i] = 0.f; p.done[ok + i] = 0; p.w[ok + i] = 0.f;
     }
     if (lane == 0) { p.serial[row] = -1; p.start[row] = -1; }
+    if constexpr (IS) {
+      if (lane == 0) {
+        if (q.raw) q.raw[row] = 0.0; else q.isw[row] = 0.f;
+      }
+    }
     return;
   }
   const double* cw = ar.cw + first;
@@ -300,6 +316,48 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_sample_kernel(Replay
   }
   for (int i = lane; i < od; i += 64) p.obs[(size_t)row * od + i] = ar.obs[at * od + i];
   if (lane == 0) { p.serial[row] = ar.c_serial[e]; p.start[row] = s; }
+  if constexpr (IS) {
+    // wave-uniform: the marginal probability of window (e, s), the same for every row whatever shares its episode
+    const double p_e = total == 0.0 ? 1.0 : (ar.c_CW[e] - (e > 0 ? ar.c_CW[e - 1] : 0.0)) / total;
+    const double p_s = tot == 0.0 ? 1.0 / (double)m : (cw[s] - (s > 0 ? cw[s - 1] : 0.0)) / tot;
+    const double x = q.N * (p_e * p_s);
+    const double raw = q.beta == 1.0 ? 1.0 / x : q.beta == 0.0 ? 1.0 : pow(x, -q.beta);
+    if (lane == 0) {
+      if (q.raw) q.raw[row] = raw; else q.isw[row] = (float)raw;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64 * kReplayWaves) replay_sample_kernel(ReplaySampleArgs p) {
+  replay_sample_row<false>(p, ReplayIsArgs{});
+}
+
+__global__ void __launch_bounds__(64 * kReplayWaves) replay_sample_is_kernel(ReplaySampleArgs p, ReplayIsArgs q) {
+  replay_sample_row<true>(p, q);
+}
+
+// isw = raw / max(raw) over the batch, the maximum in fp64 (exact whatever the order, so the same bits on every run);
+// an all-zero batch stays zero.  ONE workgroup: the pass is a few kilobytes.
+constexpr int kIsNormThreads = 1024;
+__global__ void __launch_bounds__(kIsNormThreads) replay_is_normalise_kernel(ReplayIsArgs q, int B) {
+  __shared__ double red[kIsNormThreads];
+  const int tid = threadIdx.x;
+  double top = 0.0;
+  for (int i = tid; i < B; i += kIsNormThreads) {
+    const double x = q.raw[i];
+    top = x > top ? x : top;
+  }
+  red[tid] = top;
+  __syncthreads();
+  for (int s = kIsNormThreads / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+      const double a = red[tid], b = red[tid + s];
+      red[tid] = b > a ? b : a;
+    }
+    __syncthreads();
+  }
+  top = red[0];
+  for (int i = tid; i < B; i += kIsNormThreads) q.isw[i] = top > 0.0 ? (float)(q.raw[i] / top) : 0.f;
 }
 
 // table slot of the i-th live episode, oldest first

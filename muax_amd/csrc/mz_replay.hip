@@ -1,6 +1,6 @@
 // mz_replay.hip -- translation unit of the device-resident trajectory replay (mz_replay.cuh): argument checks and
-// launches of mzs_replay_store / mzs_replay_refresh / mzs_replay_sample / mzs_replay_gather_obs / mzs_replay_reanalyse /
-// mzs_replay_update_priorities.
+// launches of mzs_replay_store / mzs_replay_refresh / mzs_replay_sample / mzs_replay_sample_is / mzs_replay_gather_obs /
+// mzs_replay_reanalyse / mzs_replay_update_priorities.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -52,6 +52,24 @@ int check_stream_desc(const mzs_replay_arena* ar, const char* who, int32_t episo
         d[3] >= ar->capacity)
       return mzh::fail(nullptr, MZS_E_INVALID, "%s: an episode's range leaves the stream, the arena or the table", who);
   }
+  return MZS_OK;
+}
+
+// the checks and the kernel arguments both sample entries share (the device is selected by the caller afterwards)
+int check_sample(const mzs_replay_arena* arena, const mzs_replay_sample_args* a, const char* who, mz::ReplaySampleArgs* p) {
+  if (int rc = check_arena(arena, who, &p->ar)) return rc;
+  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_sample_args))
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: null arguments or size mismatch (ABI)", who);
+  if (a->count <= 0 || a->count > arena->capacity || a->batch <= 0 || a->k_steps <= 0 || a->sample_per_trajectory <= 0)
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: count in 1..capacity; batch, k_steps, sample_per_trajectory >= 1", who);
+  if ((int64_t)a->k_steps * arena->num_actions >= ((int64_t)1 << 31) || a->k_steps >= arena->max_steps)
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: k_steps too large", who);
+  if (!a->obs || !a->a || !a->r || !a->Rn || !a->v || !a->done || !a->pi || !a->w || !a->serial || !a->start)
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: null output pointer", who);
+  p->count = a->count; p->B = a->batch; p->k = a->k_steps; p->spt = a->sample_per_trajectory;
+  p->key0 = a->key[0]; p->key1 = a->key[1];
+  p->obs = a->obs; p->a = a->a; p->r = a->r; p->Rn = a->Rn; p->v = a->v; p->done = a->done; p->pi = a->pi; p->w = a->w;
+  p->serial = (long long*)a->serial; p->start = a->start;
   return MZS_OK;
 }
 
@@ -110,23 +128,36 @@ int mzs_replay_refresh(const mzs_replay_arena* arena, int32_t head, int32_t coun
 
 int mzs_replay_sample(const mzs_replay_arena* arena, const mzs_replay_sample_args* a, void* stream_) {
   mz::ReplaySampleArgs p{};
-  if (int rc = check_arena(arena, "mzs_replay_sample", &p.ar)) return rc;
-  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_sample_args))
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample: null arguments or size mismatch (ABI)");
-  if (a->count <= 0 || a->count > arena->capacity || a->batch <= 0 || a->k_steps <= 0 || a->sample_per_trajectory <= 0)
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample: count in 1..capacity; batch, k_steps, sample_per_trajectory >= 1");
-  if ((int64_t)a->k_steps * arena->num_actions >= ((int64_t)1 << 31) || a->k_steps >= arena->max_steps)
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample: k_steps too large");
-  if (!a->obs || !a->a || !a->r || !a->Rn || !a->v || !a->done || !a->pi || !a->w || !a->serial || !a->start)
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample: null output pointer");
+  if (int rc = check_sample(arena, a, "mzs_replay_sample", &p)) return rc;
   MZS_HIP(nullptr, hipSetDevice(arena->device));
-  p.count = a->count; p.B = a->batch; p.k = a->k_steps; p.spt = a->sample_per_trajectory;
-  p.key0 = a->key[0]; p.key1 = a->key[1];
-  p.obs = a->obs; p.a = a->a; p.r = a->r; p.Rn = a->Rn; p.v = a->v; p.done = a->done; p.pi = a->pi; p.w = a->w;
-  p.serial = (long long*)a->serial; p.start = a->start;
   hipLaunchKernelGGL(mz::replay_sample_kernel, dim3(waves_grid(a->batch)), dim3(64 * mz::kReplayWaves), 0,
                      static_cast<hipStream_t>(stream_), p);
   MZS_HIP(nullptr, hipGetLastError());
+  return MZS_OK;
+}
+
+int mzs_replay_sample_is(const mzs_replay_arena* arena, const mzs_replay_sample_args* a, const mzs_replay_is_args* w,
+                         void* stream_) {
+  mz::ReplaySampleArgs p{};
+  if (int rc = check_sample(arena, a, "mzs_replay_sample_is", &p)) return rc;
+  if (!w || w->struct_size != (int32_t)sizeof(mzs_replay_is_args))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample_is: null weight arguments or size mismatch (ABI)");
+  if (!finite_bits(w->beta) || w->beta < 0.0 || w->beta > 1.0)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample_is: beta must be in 0..1");
+  if (!finite_bits(w->num_windows) || w->num_windows < 1.0)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample_is: num_windows must be finite and at least 1");
+  if (!w->isw || (w->normalize && !w->scratch))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample_is: null isw, or normalize without scratch");
+  MZS_HIP(nullptr, hipSetDevice(arena->device));
+  mz::ReplayIsArgs q{};
+  q.beta = w->beta; q.N = w->num_windows; q.raw = w->normalize ? w->scratch : nullptr; q.isw = w->isw;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(mz::replay_sample_is_kernel, dim3(waves_grid(a->batch)), dim3(64 * mz::kReplayWaves), 0, stream, p, q);
+  MZS_HIP(nullptr, hipGetLastError());
+  if (w->normalize) {
+    hipLaunchKernelGGL(mz::replay_is_normalise_kernel, dim3(1), dim3(mz::kIsNormThreads), 0, stream, q, (int)a->batch);
+    MZS_HIP(nullptr, hipGetLastError());
+  }
   return MZS_OK;
 }
 

@@ -42,6 +42,7 @@ struct TrainParams {
   float* grads;         // [off[18]]
   float* loss;          // [1]
   int waves;
+  const float* row_w;   // [B] per-row weight of the three cross entropies (importance sampling), or null: all 1
 };
 
 constexpr int TRAIN_LDS_BYTES = 160 * 1024;  // one workgroup may take all of a CU's LDS
@@ -313,7 +314,9 @@ __global__ __launch_bounds__(256) void mz_train_kernel(const TrainParams p) {
   const int r_raw = blockIdx.x * 16 + row;
   const bool live = r_raw < p.B;
   const int r = live ? r_raw : p.B - 1;
-  const float scale = live ? p.loss_scale : 0.0f;  // rows past the batch contribute exact zeros
+  // rows past the batch contribute exact zeros; a row's weight (indexed by the GLOBAL row) scales its loss and, through
+  // the three logit gradients, everything it back-propagates, at every unroll step; the L2 term is the reduction's
+  const float scale = live ? (p.row_w ? p.loss_scale * p.row_w[r] : p.loss_scale) : 0.0f;
 
   // x = [s, onehot(a)] as a row-distributed vector of X elements
   auto make_x = [&](const float (&s)[ES], int a, float (&x)[XS]) {

@@ -1,5 +1,5 @@
-// mz_train.hip -- training step of the default MLP trio (mzs_mlp_loss_grad): the instances of mz_train.cuh built into the
-// library, and the hand-over to the ones built on demand (mz_train_jit.hip through mzs_register_train_dispatch).
+// mz_train.hip -- training step of the default MLP trio (mzs_mlp_loss_grad, and mzs_mlp_loss_grad_weighted with a weight
+// per batch row): the instances of mz_train.cuh built into the library, and the hand-over to the ones built on demand (mz_train_jit.hip through mzs_register_train_dispatch).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -31,7 +31,11 @@ int64_t mzs_mlp_train_workspace_bytes(int32_t batch, int32_t obs_dim, int32_t em
   return waves * (mzs_mlp_num_params(obs_dim, embed_dim, num_actions, support_size) + 1) * (int64_t)sizeof(float);
 }
 
-int mzs_mlp_loss_grad(const mzs_mlp_weights* w, const mzs_train_args* a, void* stream_) {
+}  // extern "C"
+
+// THE training step behind mzs_mlp_loss_grad (row_w null) and mzs_mlp_loss_grad_weighted: checks, argument block, the
+// instance's two launches.  Both entries report under the first one's name.
+static int loss_grad(const mzs_mlp_weights* w, const mzs_train_args* a, const float* row_w, void* stream_) {
   if (!w || w->struct_size != (int32_t)sizeof(mzs_mlp_weights))
     return fail(nullptr, MZS_E_INVALID, "mzs_mlp_loss_grad: null weights or size mismatch (ABI)");
   if (!a || a->struct_size != (int32_t)sizeof(mzs_train_args))
@@ -56,6 +60,7 @@ int mzs_mlp_loss_grad(const mzs_mlp_weights* w, const mzs_train_args* a, void* s
   p.loss_scale = a->loss_scale; p.l2 = a->l2_coeff;
   p.ws = static_cast<float*>(a->workspace); p.grads = a->grads; p.loss = a->loss;
   p.waves = 4 * ((a->batch + 15) / 16);
+  p.row_w = row_w;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   char msg[256] = "";
   auto filed = [&](int rc, const char* fmt) { return rc == MZS_OK ? MZS_OK : fail(nullptr, rc, fmt, msg); };
@@ -75,6 +80,18 @@ int mzs_mlp_loss_grad(const mzs_mlp_weights* w, const mzs_train_args* a, void* s
     return fail(nullptr, MZS_E_UNSUPPORTED,
                 "mzs_mlp_loss_grad: no kernel instance for this (A, E, F): support_size must be 8..31");
   return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_mlp_loss_grad: no kernel instance for this (A, E, F)");
+}
+
+extern "C" {
+
+int mzs_mlp_loss_grad(const mzs_mlp_weights* w, const mzs_train_args* a, void* stream_) {
+  return loss_grad(w, a, nullptr, stream_);
+}
+
+int mzs_mlp_loss_grad_weighted(const mzs_mlp_weights* w, const mzs_train_args* a, const float* sample_weight,
+                               void* stream_) {
+  if (!sample_weight) return fail(nullptr, MZS_E_INVALID, "mzs_mlp_loss_grad_weighted: null sample_weight");
+  return loss_grad(w, a, sample_weight, stream_);
 }
 
 }  // extern "C"

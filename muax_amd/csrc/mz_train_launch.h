@@ -11,7 +11,10 @@
 
 namespace mz {
 
-// what mzs_train_jit_abi() and a side library's mzs_jit_train_abi() must agree on: the layout of the argument block
+// what mzs_train_jit_abi() and a side library's mzs_jit_train_abi() must agree on: the layout of the argument block.
+// Its size is in the number, so a field added to TrainParams (row_w: 320 -> 328 bytes, 1320 -> 1328) moves it, and a side
+// library built against the earlier block is refused at registration; its cached file is never loaded in the first
+// place, since the file name carries the hash of mz_train.cuh (muax_amd/_jit.py::_train_hash).
 inline int train_jit_abi() { return MZS_ABI_VERSION * 1000 + (int)(sizeof(TrainParams) % 1000); }
 // Both launches of one training step for instance C; the caller has validated `p` and selected the device.  MZS_OK, or an
 // error code with its message in err[errlen], if given (a side library cannot reach the library's error slot: the caller files it)

@@ -15,6 +15,10 @@ muax/loss.py:60-61).  Reference quirks handled explicitly:
   * muax stores pi per step as [1, A] (muax/model.py:176), so batch.pi[:, i] is [B, 1, A] against logits
     [B, A] and optax broadcasts to an all-pairs [B, B] cross entropy.  Here pi is squeezed to [B, L, A]
     (the intended per-sample target); `pi_all_pairs=True` reproduces the broadcast.
+
+Beyond the reference: `sample_weight` [B], the importance-sampling weights of prioritised replay
+(`DeviceReplayBuffer.sample(is_beta=)`), turns every mean_B CE(...) into mean_B (sample_weight * CE(...)) on both
+routes; the L2 term is not weighted.
 """
 from __future__ import annotations
 
@@ -30,10 +34,16 @@ def softmax_cross_entropy(logits, labels):
 
 
 def default_loss_fn(muzero_instance, batch: Transition, divide_by_length: bool = False,
-                    pi_all_pairs: bool = False):
-    """muax/loss.py:10-88.  `batch` fields are tensors/arrays of shape [B, L, ...]."""
+                    pi_all_pairs: bool = False, sample_weight=None):
+    """muax/loss.py:10-88.  `batch` fields are tensors/arrays of shape [B, L, ...].  `sample_weight` [B]: row b's three
+    cross entropies count sample_weight[b] times at every step (no gradient flows into the weights)."""
     dev = muzero_instance.device
-    t = lambda x, dt=torch.float32: torch.as_tensor(x, dtype=dt, device=dev)  # noqa: E731
+    if sample_weight is not None and pi_all_pairs:
+        raise ValueError("sample_weight cannot be combined with pi_all_pairs: a [B, B] cross entropy has no per-row weight")
+    # the nets' own floating-point type: float32 in the product, float64 where a test evaluates the formula so
+    fdt = next((p.dtype for m in muzero_instance.network if isinstance(m, torch.nn.Module) for p in m.parameters()),
+               torch.float32)
+    t = lambda x, dt=fdt: torch.as_tensor(x, dtype=dt, device=dev)  # noqa: E731
     a = t(batch.a, torch.long)
     B, L = a.shape[:2]
     a = a.reshape(B, L)
@@ -44,14 +54,22 @@ def default_loss_fn(muzero_instance, batch: Transition, divide_by_length: bool =
     pi = pi.reshape(B, L, 1, -1) if pi_all_pairs else pi.reshape(B, L, -1)
     obs = t(batch.obs)
     s = muzero_instance.repr_func(obs[:, 0])
-    loss = torch.zeros((), device=dev)
+    loss = torch.zeros((), dtype=fdt, device=dev)
+    sw = None
+    if sample_weight is not None:
+        sw = torch.as_tensor(sample_weight, device=dev).detach().to(s.dtype)
+        if tuple(sw.shape) != (B,):
+            raise ValueError(f"sample_weight must be [B] with B = {B}, got {tuple(sw.shape)}")
     for i in range(L):
         v, logits = muzero_instance.pred_func(s)
         s = mx_utils.scale_gradient(s, 0.5)  # Appendix G
         r, ns = muzero_instance.dy_func(s, a[:, i])
-        loss = loss + softmax_cross_entropy(r, r_t[:, i]).mean() \
-            + softmax_cross_entropy(v, Rn_t[:, i]).mean() \
-            + softmax_cross_entropy(logits, pi[:, i].detach()).mean()
+        ce_r, ce_v = softmax_cross_entropy(r, r_t[:, i]), softmax_cross_entropy(v, Rn_t[:, i])
+        ce_p = softmax_cross_entropy(logits, pi[:, i].detach())
+        if sw is None:
+            loss = loss + ce_r.mean() + ce_v.mean() + ce_p.mean()
+        else:
+            loss = loss + (ce_r * sw).mean() + (ce_v * sw).mean() + (ce_p * sw).mean()
         s = ns
     if divide_by_length:
         loss = loss / L
@@ -97,7 +115,9 @@ class FusedLossGrad:
         self._ws = None
         self._w = self._w_keep = self._w_ptrs = None
 
-    def __call__(self, batch: Transition, divide_by_length: bool = False):
+    def __call__(self, batch: Transition, divide_by_length: bool = False, sample_weight=None):
+        """(loss [1], flat gradient) of the batch.  `sample_weight` [B] (float32 on the device is read in place): the
+        weighted entry mzs_mlp_loss_grad_weighted, each row's cross entropies and gradient scaled by its weight."""
         C, _lib, dev = self._C, self._lib, self.grads.device
 
         def t(x, dt):  # (tensors that already are what the kernel reads pass through untouched)
@@ -112,6 +132,12 @@ class FusedLossGrad:
         pi = t(batch.pi, torch.float32).reshape(B, L, self.A)
         if obs.shape[1] != self.obs_dim:
             raise ValueError(f"batch.obs has {obs.shape[1]} features, the network takes {self.obs_dim}")
+        sw = None
+        if sample_weight is not None:  # (the shape alone: looking at the values would synchronise)
+            if tuple(getattr(sample_weight, "shape", ())) != (B,):
+                raise ValueError(f"sample_weight must be [B] with B = {B}, got "
+                                 f"{tuple(getattr(sample_weight, 'shape', ()))}")
+            sw = t(sample_weight.detach() if isinstance(sample_weight, torch.Tensor) else sample_weight, torch.float32)
         need = int(self._L.mzs_mlp_train_workspace_bytes(B, self.obs_dim, self.E, self.A, self.S))
         if self._ws is None or self._ws.numel() * 4 < need:
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
@@ -141,6 +167,9 @@ class FusedLossGrad:
         raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
         idx = dev.index if dev.index is not None else torch.cuda.current_device()
         stream = C.c_void_p(raw(idx) if raw is not None else torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(self._L.mzs_mlp_loss_grad(C.byref(w), C.byref(args), stream))
-        self._keep = (obs, a, r, Rn, pi, keep)
+        if sw is None:
+            _lib.check(self._L.mzs_mlp_loss_grad(C.byref(w), C.byref(args), stream))
+        else:
+            _lib.check(self._L.mzs_mlp_loss_grad_weighted(C.byref(w), C.byref(args), sw.data_ptr(), stream))
+        self._keep, self._keep_w = (obs, a, r, Rn, pi, keep), sw
         return self.loss, self.grads

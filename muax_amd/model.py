@@ -518,7 +518,7 @@ class MuZero:
         return action
 
     # ------------------------------------------------------------------ next tier
-    def update(self, batch, *args, backend: str = "auto", dp_mean: bool = True, **kwargs):
+    def update(self, batch, *args, sample_weight=None, backend: str = "auto", dp_mean: bool = True, **kwargs):
         """muax/model.py:181-201: one gradient step on a batch of k-step trajectories; returns
         {'loss': float}.  With the default MLP trio and the default loss the loss and all gradients come from
         ONE fused forward+backward HIP kernel (mzs_mlp_loss_grad, muax_amd/csrc/mz_train.cuh) into a flat
@@ -526,12 +526,23 @@ class MuZero:
         optimiser (muax/optimizers.py mirror on torch.optim) consumes views of it.  Plugin nets or a custom
         loss_fn take the torch autograd route (backend="torch" forces it; "hip" refuses to fall back).
         `dp_mean=False` skips the gradient mean over the ranks of an initialised process group (a rank-local step:
-        bench.py times update() with and without its collective)."""
+        bench.py times update() with and without its collective).
+        `sample_weight` [B]: importance-sampling weights (`DeviceReplayBuffer.sample(is_beta=)`); row b's cross
+        entropies and gradient count sample_weight[b] times, the L2 term once.  They reach whichever route serves the
+        step -- the fused kernel (mzs_mlp_loss_grad_weighted), its on-demand retry, the torch route -- and a custom
+        loss_fn as the keyword `sample_weight`, only when given.  A shape other than [B] is a ValueError before any
+        launch; the values are not inspected (that would synchronise)."""
         from . import loss as mz_loss
         from . import optimizers as mz_opt
         from .sharding import allreduce_mean_flat
         if self._params is None:
             raise ValueError("call init() first")
+        if sample_weight is not None:
+            B = int(np.shape(batch.a)[0]) if not isinstance(batch.a, torch.Tensor) else int(batch.a.shape[0])
+            if tuple(getattr(sample_weight, "shape", ())) != (B,):
+                raise ValueError(f"sample_weight must be [B] with B = {B}, got "
+                                 f"{tuple(getattr(sample_weight, 'shape', ()))}")
+            kwargs["sample_weight"] = sample_weight
         def all_params():
             return [p for m in self.network if isinstance(m, torch.nn.Module) for p in m.parameters()]
         if self._optimizer is None:
@@ -554,7 +565,8 @@ class MuZero:
                 if self._fused_train is None:
                     self._fused_train = mz_loss.FusedLossGrad(self)
                 try:
-                    loss, flat = self._fused_train(batch, divide_by_length=kwargs.get("divide_by_length", False))
+                    loss, flat = self._fused_train(batch, divide_by_length=kwargs.get("divide_by_length", False),
+                                                   sample_weight=sample_weight)
                 except ValueError as e:
                     # a shape of the default trio the library lists no training instance for: build one on demand
                     # (muax_amd/_jit.py::ensure_train_instance, or ensure_wide_train_instance for 17 to 64 actions; once
@@ -565,7 +577,8 @@ class MuZero:
                     if "no kernel instance" not in str(e) or not (_jit.ensure_train_instance(*shape)
                                                                   or _jit.ensure_wide_train_instance(*shape)):
                         raise
-                    loss, flat = ft(batch, divide_by_length=kwargs.get("divide_by_length", False))
+                    loss, flat = ft(batch, divide_by_length=kwargs.get("divide_by_length", False),
+                                    sample_weight=sample_weight)
                 if dp_mean:
                     allreduce_mean_flat([flat])
                 for p, g in zip(self._fused_train.params, self._fused_train.views):

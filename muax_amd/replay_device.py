@@ -94,7 +94,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         self._device = None if device is None else torch.device(device)
         seed = int.from_bytes(os.urandom(4), "little") if random_seed is None else random_seed
         self._key = prng.PRNGKey(seed)
-        self._arena = self._t = self._prio_scratch = None
+        self._arena = self._t = self._prio_scratch = self._is_scratch = None
         self._serial = 0
         self.clear()
 
@@ -117,6 +117,12 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         """Serial numbers of the episodes held, oldest first."""
         return [e.serial for e in self._eps]
 
+    def eligible_windows(self, k_steps):
+        """Number of windows of `k_steps` transitions `sample()` can draw: the sum of length - k_steps over the held
+        episodes longer than k_steps (the N of the importance-sampling weights).  Host bookkeeping."""
+        k = int(k_steps)
+        return sum(e.length - k for e in self._eps if e.length > k)
+
     def episode(self, serial):
         """The stored episode with that serial as a Transition of views [T, ...] into the arenas (w: float64)."""
         for e in self._eps:
@@ -129,7 +135,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         self._eps = deque()
         self._touched, self._clock = {}, 0  # serial -> count of the add / reanalysis that last wrote its targets
         self._head = self._tail = self._steps = 0
-        self._dirty, self._table_k, self._eligible = True, None, False
+        self._dirty, self._table_k, self._eligible, self._windows = True, None, False, 0
 
     def __len__(self):
         return len(self._eps)
@@ -443,7 +449,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         self._dirty = True
 
     def sample(self, batch_size=32, num_trajectory: int = None, k_steps: int = 5, sample_per_trajectory: int = 1,
-               key=None, with_indices: bool = False):
+               key=None, with_indices: bool = False, is_beta=None, is_normalize: bool = True):
         """A batch of `num_trajectory * sample_per_trajectory` windows of `k_steps` transitions (the arguments of
         muax/replay_buffer.py:192-240; `batch_size` alone means that many trajectories, one window each) as a
         Transition of device tensors: obs [B, 1, obs_dim], a [B, k] int32, r / Rn / v / w [B, k] float32, done
@@ -451,7 +457,21 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         episode with the transition weights, the rows of one trajectory sharing their episode.  The batch size is
         fixed: an episode no longer than `k_steps` is never drawn (the reference returns a shorter batch).
         `key`: an int seed or two uint32 words fix the draws; default: the buffer's own key, split on every call.
-        `with_indices=True` returns (batch, (episode serial [B] int64, start [B] int32))."""
+        `with_indices=True` returns (batch, (episode serial [B] int64, start [B] int32)).
+
+        `is_beta`, a float in 0..1, adds the importance-sampling weights of the rows as a trailing `isw` [B] float32
+        device tensor -- (batch, isw), or (batch, (serial, start), isw) with the indices -- for
+        `MuZero.update(batch, sample_weight=isw)`: isw = (N q) ** -is_beta in fp64, q the probability with which the
+        row's window was drawn (episode times start), N the number of windows the buffer could have drawn (the sum
+        of length - k_steps over the episodes longer than k_steps); `is_normalize` (default) divides by the largest
+        weight of the batch, so that the weights only ever scale a step down.  A zero-filled row gets 0.  The draws
+        and every field are those of the call without `is_beta`, bit for bit, and nothing is copied to the host or
+        synchronised: one more small launch for the normalisation.  Outside 0..1 or not finite: ValueError before
+        any launch.  None: no weights, today's return value."""
+        if is_beta is not None:
+            is_beta = float(is_beta)
+            if not 0.0 <= is_beta <= 1.0:  # (False for NaN)
+                raise ValueError("sample: is_beta must be None or a number in 0..1")
         if batch_size is None and num_trajectory is None:
             raise ValueError("Either num_trajectory or batch_size need to be given.")
         elif batch_size is not None and num_trajectory is None:
@@ -462,7 +482,8 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         B = int(num_trajectory) * spt
         stream = self._stream()
         if self._dirty or self._table_k != k:
-            self._eligible = any(e.length > k for e in self._eps)
+            self._windows = self.eligible_windows(k)  # (isw's N)
+            self._eligible = self._windows > 0
             _lib.check(self._L.mzs_replay_refresh(C.byref(self._arena), self._head, len(self._eps), k, stream))
             self._dirty, self._table_k = False, k
         if not self._eligible:
@@ -485,6 +506,16 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         s.key[0], s.key[1] = int(key[0]), int(key[1])
         s.obs, s.a, s.r, s.Rn, s.v, s.done = (x.data_ptr() for x in (obs, a, r, Rn, v, done))
         s.pi, s.w, s.serial, s.start = pi.data_ptr(), w.data_ptr(), serial.data_ptr(), start.data_ptr()
-        _lib.check(self._L.mzs_replay_sample(C.byref(self._arena), C.byref(s), stream))
         batch = self.transition_class(obs=obs, a=a, r=r, done=done, Rn=Rn, v=v, pi=pi, w=w)
-        return (batch, (serial, start)) if with_indices else batch
+        if is_beta is None:
+            _lib.check(self._L.mzs_replay_sample(C.byref(self._arena), C.byref(s), stream))
+            return (batch, (serial, start)) if with_indices else batch
+        isw = torch.empty(B, dtype=f32, device=dev)
+        if is_normalize and (self._is_scratch is None or self._is_scratch.numel() < B):
+            self._is_scratch = torch.empty(B, dtype=torch.float64, device=dev)  # raw weights; grows with the batch
+        q = _lib.MzsReplayIsArgs()
+        q.struct_size = C.sizeof(_lib.MzsReplayIsArgs)
+        q.normalize, q.beta, q.num_windows = int(bool(is_normalize)), is_beta, float(self._windows)
+        q.isw, q.scratch = isw.data_ptr(), self._is_scratch.data_ptr() if is_normalize else None
+        _lib.check(self._L.mzs_replay_sample_is(C.byref(self._arena), C.byref(s), C.byref(q), stream))
+        return (batch, (serial, start), isw) if with_indices else (batch, isw)

@@ -180,7 +180,7 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                max_training_steps: int = 10000, test_interval: int = 10, num_test_episodes: int = 10,
                random_seed: int = 42, temperature_fn=None, metrics=None, trajectory_weight: str = "mean",
                reanalyse_every: int = 0, reanalyse_episodes=None, priority_update: bool = False,
-               priority_steps=None):
+               priority_steps=None, is_beta=None):
     """The reference's fit() loop (muax/train.py:175-241: temperature schedule, buffer sampling, update,
     greedy test) with the acting half on a vector environment: per iteration `steps_per_iteration`
     batched act() calls -> finished episodes -> buffer, then `num_update_per_iteration` updates.
@@ -197,7 +197,14 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     without the method: the key stream and every result are unchanged.
     `priority_steps`: None writes `value_priorities` back (one transition per window); an integer kp >= 1 writes
     `unroll_value_priorities(model, batch, min(kp, k_steps))` instead, one priority for each of the first kp transitions
-    of every window.  Ignored where `priority_update` is off or the buffer has no `update_priorities`."""
+    of every window.  Ignored where `priority_update` is off or the buffer has no `update_priorities`.
+    `is_beta`: importance-sampling correction of the prioritised draws -- a float in 0..1, or a schedule called as
+    `is_beta(training_steps=, max_training_steps=)` before every batch (as `temperature_fn` is) -- every batch is
+    sampled with `sample(is_beta=)` and its `update()` takes the returned weights as `sample_weight`; composes with
+    `priority_update` / `priority_steps`.  The weights are normalised by the largest one of the batch, so under data
+    parallelism by each rank's own batch maximum, not a global one.  A buffer whose `sample` takes no `is_beta` (the
+    host `TrajectoryReplayBuffer`) is a ValueError: dropping a correction that was asked for would change what is
+    learned.  None: the key stream and every result are unchanged."""
     if priority_steps is not None and int(priority_steps) < 1:
         raise ValueError("priority_steps must be None or >= 1")
     if trajectory_weight not in ("mean", "sum"):
@@ -206,6 +213,13 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     from .train import _temperature_fn, test
     temperature_fn = temperature_fn or _temperature_fn
     buffer = buffer if buffer is not None else TrajectoryReplayBuffer(500)
+    if is_beta is not None:
+        import inspect
+        if "is_beta" not in inspect.signature(buffer.sample).parameters:
+            raise ValueError(f"fit_vector: is_beta needs a buffer whose sample() takes is_beta (DeviceReplayBuffer); "
+                             f"{type(buffer).__name__}.sample does not")
+        if not callable(is_beta) and not 0.0 <= float(is_beta) <= 1.0:
+            raise ValueError("fit_vector: is_beta must be None, a number in 0..1 or a callable")
     collector = VectorCollector(venv, n_step, gamma, alpha)
     prioritise = bool(priority_update) and hasattr(buffer, "update_priorities")
     key = prng.PRNGKey(random_seed)
@@ -233,13 +247,23 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
         if len(buffer):
             loss = 0.0
             for _ in range(num_update_per_iteration):
-                if prioritise:
-                    batch, indices = buffer.sample(num_trajectory=num_trajectory, k_steps=k_steps,
-                                                   sample_per_trajectory=sample_per_trajectory, with_indices=True)
+                if is_beta is not None:
+                    beta = is_beta(training_steps=training_step, max_training_steps=max_training_steps) \
+                        if callable(is_beta) else is_beta
+                    got = buffer.sample(num_trajectory=num_trajectory, k_steps=k_steps,
+                                        sample_per_trajectory=sample_per_trajectory, with_indices=prioritise,
+                                        is_beta=float(beta))
+                    batch, isw = got[0], got[-1]
+                    indices = got[1] if prioritise else None
+                    loss += model.update(batch, sample_weight=isw)["loss"]
                 else:
-                    batch = buffer.sample(num_trajectory=num_trajectory,
-                                          sample_per_trajectory=sample_per_trajectory, k_steps=k_steps)
-                loss += model.update(batch)["loss"]
+                    if prioritise:
+                        batch, indices = buffer.sample(num_trajectory=num_trajectory, k_steps=k_steps,
+                                                       sample_per_trajectory=sample_per_trajectory, with_indices=True)
+                    else:
+                        batch = buffer.sample(num_trajectory=num_trajectory,
+                                              sample_per_trajectory=sample_per_trajectory, k_steps=k_steps)
+                    loss += model.update(batch)["loss"]
                 if prioritise:
                     prio = value_priorities(model, batch) if priority_steps is None else \
                         unroll_value_priorities(model, batch, min(int(priority_steps), k_steps))

@@ -5,6 +5,7 @@ and each `sample` on its own.  Default MLP trio on CartPole shapes, 500 stored e
     python tools/bench_replay.py [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
     python tools/bench_replay.py --reanalyse [--iters 200] [--episodes 500]
     python tools/bench_replay.py --priorities [--prio-steps KP] [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
+    python tools/bench_replay.py --is-weights [--is-beta 0.4] [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
 
 `--reanalyse` times, on the same device buffer and with 50 simulations, (a) `DeviceReplayBuffer.reanalyse()` of the
 whole buffer, (b) the same work through the host -- `episode().obs` downloaded, `act` NumPy in / out in the same
@@ -15,6 +16,9 @@ chunks, `vector.episode_trajectory`, `add_many` into a second buffer -- and (c) 
 `sample` + `update()` and `update()` as the default mode times them, and the two new parts on their own.  Side by side
 with it, for `--prio-steps` kp (default: k) priorities per window: `MuZero.unroll_values` on the torch modules and as one
 kernel launch (`backend="torch"` / `"hip"`), the write-back of [B, kp] priorities, and the whole step with each.
+
+`--is-weights` times, on the device buffer alone, `sample(is_beta=)` (the sample launch and the normalisation pass)
+beside `sample()`, and `update(sample_weight=)` beside `update()` on one fixed batch, both on the fused kernel.
 
 Every figure is the median of `--iters` iterations, each ending in a device synchronise, after 30 ms of untimed
 iterations of the same work (clocks settled).  The two routes alternate shape by shape in one process."""
@@ -165,12 +169,32 @@ def priority_figures(dev, shapes, iters, prio_steps=None, alpha=0.5):
               f"{dp:8.3f} {r['st']:10.3f} {r['sh']:8.3f} | {r['sh'] / du:15.2f}x", flush=True)
 
 
+def is_weight_figures(dev, shapes, iters, beta):
+    print(f"{'num_trajectory x k':>18} | {'sample':>8} {'sample is':>9} {'is, raw':>8} | {'update':>8} {'update w':>8} | "
+          f"{'sample is - sample':>18} {'update w - update':>17}")
+    for n, k in shapes:
+        m_plain, m_w = model(), model()
+        fixed, isw = dev.sample(num_trajectory=n, k_steps=k, is_beta=beta)
+        res = {
+            "s": median_ms(lambda: dev.sample(num_trajectory=n, k_steps=k), iters),
+            "si": median_ms(lambda: dev.sample(num_trajectory=n, k_steps=k, is_beta=beta), iters),
+            "sr": median_ms(lambda: dev.sample(num_trajectory=n, k_steps=k, is_beta=beta, is_normalize=False), iters),
+            "u": median_ms(lambda: m_plain.update(fixed, backend="hip"), iters),
+            "uw": median_ms(lambda: m_w.update(fixed, sample_weight=isw, backend="hip"), iters),
+        }
+        print(f"{n:>13} x {k:<2} | {res['s']:8.3f} {res['si']:9.3f} {res['sr']:8.3f} | {res['u']:8.3f} {res['uw']:8.3f} | "
+              f"{res['si'] - res['s']:18.3f} {res['uw'] - res['u']:17.3f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reanalyse", action="store_true", help="time reanalysis instead of sampling")
     ap.add_argument("--priorities", action="store_true", help="time the training step with the priority write-back")
     ap.add_argument("--prio-steps", type=int, default=None, metavar="KP",
                     help="with --priorities: priorities per window of the unrolled routes (default: k)")
+    ap.add_argument("--is-weights", action="store_true",
+                    help="time sample(is_beta=) beside sample() and update(sample_weight=) beside update()")
+    ap.add_argument("--is-beta", type=float, default=0.4, help="with --is-weights: the exponent (default 0.4)")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--episodes", type=int, default=500)
     ap.add_argument("--shape", action="append", default=[], metavar="NUM_TRAJECTORY,K")
@@ -192,6 +216,9 @@ def main():
         return
     if a.priorities:
         priority_figures(dev, shapes, a.iters, a.prio_steps)
+        return
+    if a.is_weights:
+        is_weight_figures(dev, shapes, a.iters, a.is_beta)
         return
     print(f"{'num_trajectory x k':>18} | {'host sample':>11} {'host s+upd':>10} | {'dev sample':>10} {'dev s+upd':>9} | "
           f"{'update':>7} | {'s+upd host/dev':>14} {'sample host/dev':>15}")
