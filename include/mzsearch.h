@@ -555,7 +555,8 @@ typedef struct mzs_replay_arena {
  * raw == 1: r, v are DOUBLE[stream_steps]; Rn, done and w are computed as muax_amd/vector.py:25-52 defines them, in
  *   fp64 and in its operation order: Rn = sum_{i < n_step} gpow[i] * r[t + i] (i ascending, 0 past the end), then
  *   + v[t + n_step] * gpow[n_step] where that step exists (else done = 1); w = |v - Rn| ** alpha, or 1 with
- *   has_alpha == 0.  gpow: device table of the n_step + 1 powers gamma ** i the host computed.
+ *   has_alpha == 0; with alpha == 1.0 no pow is executed, so w is exactly |v - Rn| (as in
+ *   mzs_replay_update_priorities).  gpow: device table of the n_step + 1 powers gamma ** i the host computed.
  *   weight_mode 1 / 2: the episode weight is the mean / the sum of its w (0: ep_w, as with raw == 0). */
 typedef struct mzs_replay_store_args {
   int32_t struct_size;     /* = sizeof(mzs_replay_store_args) */
@@ -710,6 +711,63 @@ typedef struct mzs_replay_update_args {
   int32_t *touched;        /* scratch [capacity] */
 } mzs_replay_update_args;
 int mzs_replay_update_priorities(const mzs_replay_arena *arena, const mzs_replay_update_args *a, void *stream);
+
+/* ---- collection on the device: a vector environment's steps staged in a ring, episodes cut in the store launch ----
+ * The ring is caller-owned device memory, STEP-major: row s holds step s of all `num_envs` environments, so the
+ * transitions of one episode lie num_envs rows apart and wrap at the ring's end.  r is double because the
+ * environments' rewards are and mzs_replay_store's raw route reads double; v is act()'s float, widened (exactly)
+ * inside the kernel.  The caller writes r itself (one or two copies per collection). */
+typedef struct mzs_replay_ring {
+  int32_t struct_size;     /* = sizeof(mzs_replay_ring) */
+  int32_t device;
+  int32_t ring_steps;      /* rows; ring_steps * max(obs_dim, num_actions) < 2^31 */
+  int32_t num_envs;        /* N */
+  int32_t obs_dim, num_actions;
+  float *obs;              /* [ring_steps, N, obs_dim] */
+  int32_t *a;              /* [ring_steps, N] */
+  double *r;               /* [ring_steps, N] */
+  float *v;                /* [ring_steps, N] */
+  float *pi;               /* [ring_steps, N, num_actions] */
+} mzs_replay_ring;
+
+/* One step: obs [N, obs_dim], a [N], v [N], pi [N, num_actions] (device memory) into ring row `row`, in one launch;
+ * r is not touched.  No copy to the host, no synchronisation.  MZS_E_INVALID before any launch for a struct size, a
+ * null pointer, non-positive ring dimensions, or a row outside 0 .. ring_steps - 1. */
+typedef struct mzs_replay_stage_args {
+  int32_t struct_size;     /* = sizeof(mzs_replay_stage_args) */
+  int32_t row;
+  const float *obs;
+  const int32_t *a;
+  const float *v;
+  const float *pi;
+} mzs_replay_stage_args;
+int mzs_replay_stage(const mzs_replay_ring *ring, const mzs_replay_stage_args *a, void *stream);
+
+/* The finished episodes of a collection from the ring into the arenas: mzs_replay_store with raw == 1 reading a
+ * strided, wrapping source -- one launch, one wavefront per episode.
+ *   desc[e] = {environment, first ring row, length, first transition in the arena, table slot}; the HOST copy is
+ *   checked here, the DEVICE copy is what the kernel reads.  Transition t of the episode is ring row
+ *   (first + t) % ring_steps, column `environment`.
+ * Written: obs, a, r (rounded to float), v, pi copied; Rn, done, w by the raw store's arithmetic in its operation
+ * order; cw the sequential prefix sum; the table row with the mean (weight_mode 1) or the sum (2) of w -- bit for bit
+ * what mzs_replay_store (raw == 1) writes for the same episodes given as a dense stream with v widened to double.
+ * The cost of the strided reads against the dense store's has not been measured.
+ * MZS_E_INVALID before any launch for: struct sizes; a null pointer; ring and arena that disagree in obs_dim,
+ * num_actions or device; episodes outside 1..capacity; environment outside 0..num_envs - 1; length < 1 or
+ * > ring_steps; a first row outside the ring; an arena range or a slot out of bounds; n_step < 1; weight_mode other
+ * than 1 / 2. */
+typedef struct mzs_replay_store_steps_args {
+  int32_t struct_size;     /* = sizeof(mzs_replay_store_steps_args) */
+  int32_t episodes;
+  int32_t n_step, weight_mode, has_alpha, reserved0;
+  double alpha;
+  const int32_t *desc_host;  /* HOST [episodes][5] */
+  const int32_t *desc;       /* [episodes][5] */
+  const int64_t *serial;     /* [episodes] */
+  const double *gpow;        /* [n_step + 1]: gamma ** i */
+} mzs_replay_store_steps_args;
+int mzs_replay_store_steps(const mzs_replay_arena *arena, const mzs_replay_ring *ring,
+                           const mzs_replay_store_steps_args *a, void *stream);
 
 /* ---- forward value unroll of the default MLP trio: the priorities mzs_replay_update_priorities takes ----
  * For every window j < batch and step i < k_prio, with s_0 = Representation(obs[j]) and s_{i+1} = the next state of

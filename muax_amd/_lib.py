@@ -168,6 +168,21 @@ class MzsReplayUpdateArgs(C.Structure):
                 + [(n, _vp) for n in ("serial", "start", "prio", "owner", "touched")])
 
 
+class MzsReplayRing(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("device", C.c_int32), ("ring_steps", C.c_int32), ("num_envs", C.c_int32),
+                 ("obs_dim", C.c_int32), ("num_actions", C.c_int32)] + [(n, _vp) for n in ("obs", "a", "r", "v", "pi")])
+
+
+class MzsReplayStageArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("row", C.c_int32)] + [(n, _vp) for n in ("obs", "a", "v", "pi")]
+
+
+class MzsReplayStoreStepsArgs(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("episodes", C.c_int32), ("n_step", C.c_int32), ("weight_mode", C.c_int32),
+                 ("has_alpha", C.c_int32), ("reserved0", C.c_int32), ("alpha", C.c_double)]
+                + [(n, _vp) for n in ("desc_host", "desc", "serial", "gpow")])
+
+
 class MzsUnrollArgs(C.Structure):
     _fields_ = ([("struct_size", C.c_int32), ("device", C.c_int32), ("batch", C.c_int32), ("row_steps", C.c_int32),
                  ("k_prio", C.c_int32), ("num_actions", C.c_int32), ("embed_dim", C.c_int32), ("reserved0", C.c_int32)]
@@ -188,7 +203,8 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_mlp_allow_wide_gumbel", "mzs_mlp_wide_plan_policy",
                     "mzs_replay_store", "mzs_replay_refresh", "mzs_replay_sample",
                     "mzs_replay_gather_obs", "mzs_replay_reanalyse", "mzs_replay_update_priorities",
-                    "mzs_mlp_unroll_values", "mzs_replay_sample_is", "mzs_mlp_loss_grad_weighted"]
+                    "mzs_mlp_unroll_values", "mzs_replay_sample_is", "mzs_mlp_loss_grad_weighted",
+                    "mzs_replay_stage", "mzs_replay_store_steps"]
 
 _lib = None
 
@@ -263,6 +279,9 @@ def load(build_if_missing: bool = True):
     L.mzs_replay_gather_obs.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayGatherArgs), _vp]
     L.mzs_replay_reanalyse.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayReanalyseArgs), _vp]
     L.mzs_replay_update_priorities.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayUpdateArgs), _vp]
+    L.mzs_replay_stage.argtypes = [C.POINTER(MzsReplayRing), C.POINTER(MzsReplayStageArgs), _vp]
+    L.mzs_replay_store_steps.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayRing),
+                                         C.POINTER(MzsReplayStoreStepsArgs), _vp]
     L.mzs_mlp_unroll_values.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsUnrollArgs), _vp]
     L.mzs_tower_pair_scratch_bytes.restype = C.c_int64
     if L.mzs_abi_version() != 1:

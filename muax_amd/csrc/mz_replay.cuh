@@ -20,6 +20,12 @@
 //                             owner of every transition it validly addresses; flags the episode
 //   replay_prio_apply_kernel  flagged episodes only: w = (|p| + eps) ** alpha from the owner's priority, then cw and
 //                             the table weight; clears the owners and the flag
+// and the two of collection on the device (a vector environment's steps staged in a caller-owned STEP-MAJOR ring of
+// ring_steps x num_envs rows, so an episode's transitions lie num_envs rows apart and may wrap at the ring's end):
+//   replay_stage_kernel        one step's obs, a, v, pi of every environment into one ring row (rewards come later)
+//   replay_store_steps_kernel  the raw store reading that strided source: one wavefront per finished episode, the
+//                              same copies, nstep_transition, seq_scan and table row, so the same bits as the dense
+//                              store.  The strided reads have NOT been measured against the dense ones.
 // Every prefix sum is the SEQUENTIAL fp64 sum (np.cumsum's order), one addition per element on a wave-uniform carry:
 // monotone, so the searches are well defined, and equal to the host's bit for bit.
 #pragma once
@@ -98,6 +104,42 @@ struct ReplayUpdateArgs {
   int32_t* touched;           // [capacity] scratch: 0 on entry and on exit
 };
 
+struct ReplayRing {
+  int steps, N;               // ring rows (environment steps), environments
+  float* obs; int32_t* a; double* r; float* v; float* pi;  // [steps, N, obs_dim], [steps, N] x 3, [steps, N, A]
+};
+
+struct ReplayStageArgs {
+  ReplayRing ring;
+  int row, obs_dim, A;
+  const float* obs; const int32_t* a; const float* v; const float* pi;
+};
+
+struct ReplayStoreStepsArgs {
+  ReplayArena ar;
+  ReplayRing ring;
+  int episodes, n_step, weight_mode, has_alpha;
+  double alpha;
+  const int32_t* desc;        // [episodes][5]: environment, first ring row, length, first in the arena, table slot
+  const long long* serial;    // [episodes]
+  const double* gpow;         // [n_step + 1]: gamma ** i
+};
+
+// ring row of transition t of an episode that began in row `first` (t < steps: one wrap at the most)
+MZ_DEV int ring_row(int first, int t, int steps) {
+  const int row = first + t;
+  return row >= steps ? row - steps : row;
+}
+
+// One environment's column of a [steps, N] ring field, indexed by the transition inside an episode: what
+// nstep_transition reads where the dense store has a pointer.
+template <typename T>
+struct RingColumn {
+  const T* col;               // field + environment
+  int first, steps, N;
+  MZ_DEV T operator[](int t) const { return col[(size_t)ring_row(first, t, steps) * N]; }
+};
+
 MZ_DEV double lane_bcast(double x, int j) {  // j wave-uniform
   const int lo = __builtin_amdgcn_readlane(__double2loint(x), j);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(x), j);
@@ -134,14 +176,30 @@ MZ_DEV int upper_bound(const double* c, int n, double t) {
 // Transition t of an episode of T steps with rewards r[0..T) and values v[0..T) (double, or float widened):
 // vector.nstep_returns in its operation order -- i ascending (terms past the end are + gamma^i * 0), then the bootstrap --
 // and episode_trajectory's priority weight.  Returns w; Rn and boot (false: `done`) by reference.
-template <typename TR, typename TV>
-MZ_DEV double nstep_transition(const TR* r, const TV* v, int t, int T, int n_step, const double* gpow, int has_alpha,
-                               double alpha, double& Rn, bool& boot) {
+template <typename R, typename V>
+MZ_DEV double nstep_transition_of(R r, V v, int t, int T, int n_step, const double* gpow, int has_alpha, double alpha,
+                                  double& Rn, bool& boot) {
   Rn = 0.0;
   for (int i = 0; i < n_step; ++i) Rn = Rn + gpow[i] * (t + i < T ? (double)r[t + i] : 0.0);
   boot = t + n_step < T;
   Rn = Rn + (boot ? (double)v[t + n_step] * gpow[n_step] : 0.0);
-  return has_alpha ? pow(fabs((double)v[t] - Rn), alpha) : 1.0;
+  // alpha == 1.0: no pow is executed (the device pow does not return x exactly for y == 1: measured 2.1e-16 relative),
+  // so w is exactly |v - Rn|, NumPy's x ** 1.0 -- as replay_prio_apply_kernel does
+  const double d = fabs((double)v[t] - Rn);
+  return has_alpha ? (alpha == 1.0 ? d : pow(d, alpha)) : 1.0;
+}
+
+// r, v dense (pointers), or columns of the collection ring: the same statements either way
+template <typename TR, typename TV>
+MZ_DEV double nstep_transition(const TR* r, const TV* v, int t, int T, int n_step, const double* gpow, int has_alpha,
+                               double alpha, double& Rn, bool& boot) {
+  return nstep_transition_of(r, v, t, T, n_step, gpow, has_alpha, alpha, Rn, boot);
+}
+
+template <typename TR, typename TV>
+MZ_DEV double nstep_transition(RingColumn<TR> r, RingColumn<TV> v, int t, int T, int n_step, const double* gpow,
+                               int has_alpha, double alpha, double& Rn, bool& boot) {
+  return nstep_transition_of(r, v, t, T, n_step, gpow, has_alpha, alpha, Rn, boot);
 }
 
 __global__ void __launch_bounds__(64 * kReplayWaves) replay_store_kernel(ReplayStoreArgs p) {
@@ -187,6 +245,73 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_store_kernel(ReplayS
     ar.t_start[slot] = (int32_t)dst;
     ar.t_len[slot] = T;
     ar.t_w[slot] = p.weight_mode == 0 ? p.ep_w[e] : p.weight_mode == 1 ? carry / (double)T : carry;
+    ar.t_serial[slot] = p.serial[e];
+  }
+}
+
+// One step of a vector environment into ring row p.row: four dense copies, consecutive lanes on consecutive elements.
+constexpr int kStageThreads = 256;
+__global__ void __launch_bounds__(kStageThreads) replay_stage_kernel(ReplayStageArgs p) {
+  const ReplayRing& g = p.ring;
+  const size_t N = (size_t)g.N, row = (size_t)p.row;
+  const size_t first = (size_t)blockIdx.x * kStageThreads + threadIdx.x, step = (size_t)gridDim.x * kStageThreads;
+  const size_t no = N * p.obs_dim, np_ = N * p.A;
+  for (size_t i = first; i < no; i += step) g.obs[row * no + i] = p.obs[i];
+  for (size_t i = first; i < np_; i += step) g.pi[row * np_ + i] = p.pi[i];
+  for (size_t i = first; i < N; i += step) {
+    g.a[row * N + i] = p.a[i];
+    g.v[row * N + i] = p.v[i];
+  }
+}
+
+// replay_store_kernel with raw == 1 whose source is the ring: transition t of the episode is ring row
+// (first + t) % steps, column env.  The 64 lanes run over the ELEMENTS of consecutive transitions, as the dense copy
+// does: a wavefront reads whole rows of obs_dim (A) floats, each contiguous, N rows apart (the host keeps
+// steps * obs_dim and steps * A below 2^31, so the element index is an int).  How much these strided reads cost
+// against the dense store's has not been measured.
+__global__ void __launch_bounds__(64 * kReplayWaves) replay_store_steps_kernel(ReplayStoreStepsArgs p) {
+  const int lane = threadIdx.x & 63;
+  const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  if (e >= p.episodes) return;
+  const ReplayArena& ar = p.ar;
+  const ReplayRing& g = p.ring;
+  const int env = p.desc[5 * e], first = p.desc[5 * e + 1], T = p.desc[5 * e + 2], slot = p.desc[5 * e + 4];
+  const size_t dst = (size_t)p.desc[5 * e + 3], N = (size_t)g.N;
+  const int od = ar.obs_dim, A = ar.A;
+  for (int i = lane; i < T * od; i += 64) {
+    const int t = i / od, c = i - t * od;
+    ar.obs[dst * od + i] = g.obs[((size_t)ring_row(first, t, g.steps) * N + env) * od + c];
+  }
+  for (int i = lane; i < T * A; i += 64) {
+    const int t = i / A, c = i - t * A;
+    ar.pi[dst * A + i] = g.pi[((size_t)ring_row(first, t, g.steps) * N + env) * A + c];
+  }
+  const RingColumn<double> r{g.r + env, first, g.steps, g.N};
+  const RingColumn<float> v{g.v + env, first, g.steps, g.N};
+  double carry = 0.0;
+  for (int base = 0; base < T; base += 64) {
+    const int t = base + lane;
+    const bool in = t < T;
+    double w = 0.0;
+    if (in) {
+      ar.a[dst + t] = g.a[(size_t)ring_row(first, t, g.steps) * N + env];
+      double Rn;
+      bool boot;
+      w = nstep_transition(r, v, t, T, p.n_step, p.gpow, p.has_alpha, p.alpha, Rn, boot);
+      ar.r[dst + t] = (float)r[t];
+      ar.v[dst + t] = v[t];  // (the dense store's (float)(double)v: the widening is exact)
+      ar.Rn[dst + t] = (float)Rn;
+      ar.done[dst + t] = boot ? 0 : 1;
+      ar.w[dst + t] = w;
+    }
+    const int valid = T - base < 64 ? T - base : 64;
+    const double c = seq_scan(w, valid, lane, carry);
+    if (in) ar.cw[dst + t] = c;
+  }
+  if (lane == 0) {
+    ar.t_start[slot] = (int32_t)dst;
+    ar.t_len[slot] = T;
+    ar.t_w[slot] = p.weight_mode == 1 ? carry / (double)T : carry;
     ar.t_serial[slot] = p.serial[e];
   }
 }

@@ -1,6 +1,6 @@
 // mz_replay.hip -- translation unit of the device-resident trajectory replay (mz_replay.cuh): argument checks and
 // launches of mzs_replay_store / mzs_replay_refresh / mzs_replay_sample / mzs_replay_sample_is / mzs_replay_gather_obs /
-// mzs_replay_reanalyse / mzs_replay_update_priorities.
+// mzs_replay_reanalyse / mzs_replay_update_priorities / mzs_replay_stage / mzs_replay_store_steps.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -70,6 +70,21 @@ int check_sample(const mzs_replay_arena* arena, const mzs_replay_sample_args* a,
   p->key0 = a->key[0]; p->key1 = a->key[1];
   p->obs = a->obs; p->a = a->a; p->r = a->r; p->Rn = a->Rn; p->v = a->v; p->done = a->done; p->pi = a->pi; p->w = a->w;
   p->serial = (long long*)a->serial; p->start = a->start;
+  return MZS_OK;
+}
+
+int check_ring(const mzs_replay_ring* g, const char* who, mz::ReplayRing* out) {
+  if (!g || g->struct_size != (int32_t)sizeof(mzs_replay_ring))
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: null ring or size mismatch (ABI)", who);
+  if (g->ring_steps <= 0 || g->num_envs <= 0 || g->obs_dim <= 0 || g->num_actions <= 0)
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: ring_steps, num_envs, obs_dim and num_actions must be positive", who);
+  const int64_t widest = g->obs_dim > g->num_actions ? g->obs_dim : g->num_actions;
+  if ((int64_t)g->ring_steps * widest >= ((int64_t)1 << 31))
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: ring_steps * max(obs_dim, num_actions) must be below 2^31", who);
+  if (!g->obs || !g->a || !g->r || !g->v || !g->pi) return mzh::fail(nullptr, MZS_E_INVALID, "%s: null ring pointer", who);
+  if (int rc = mzh::check_device(g->device, who)) return rc;
+  out->steps = g->ring_steps; out->N = g->num_envs;
+  out->obs = g->obs; out->a = g->a; out->r = g->r; out->v = g->v; out->pi = g->pi;
   return MZS_OK;
 }
 
@@ -236,6 +251,61 @@ int mzs_replay_update_priorities(const mzs_replay_arena* arena, const mzs_replay
   hipLaunchKernelGGL(mz::replay_prio_mark_kernel, dim3(waves_grid(a->batch)), dim3(64 * mz::kReplayWaves), 0, stream, p);
   MZS_HIP(nullptr, hipGetLastError());
   hipLaunchKernelGGL(mz::replay_prio_apply_kernel, dim3(waves_grid(a->count)), dim3(64 * mz::kReplayWaves), 0, stream, p);
+  MZS_HIP(nullptr, hipGetLastError());
+  return MZS_OK;
+}
+
+int mzs_replay_stage(const mzs_replay_ring* ring, const mzs_replay_stage_args* a, void* stream_) {
+  mz::ReplayStageArgs p{};
+  if (int rc = check_ring(ring, "mzs_replay_stage", &p.ring)) return rc;
+  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_stage_args))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_stage: null arguments or size mismatch (ABI)");
+  if (a->row < 0 || a->row >= ring->ring_steps)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_stage: row must be in 0..ring_steps - 1");
+  if (!a->obs || !a->a || !a->v || !a->pi) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_stage: null pointer");
+  MZS_HIP(nullptr, hipSetDevice(ring->device));
+  p.row = a->row; p.obs_dim = ring->obs_dim; p.A = ring->num_actions;
+  p.obs = a->obs; p.a = a->a; p.v = a->v; p.pi = a->pi;
+  const int64_t widest = (int64_t)ring->num_envs * (ring->obs_dim > ring->num_actions ? ring->obs_dim : ring->num_actions);
+  const int64_t blocks = (widest + mz::kStageThreads - 1) / mz::kStageThreads;
+  hipLaunchKernelGGL(mz::replay_stage_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(mz::kStageThreads), 0,
+                     static_cast<hipStream_t>(stream_), p);
+  MZS_HIP(nullptr, hipGetLastError());
+  return MZS_OK;
+}
+
+int mzs_replay_store_steps(const mzs_replay_arena* arena, const mzs_replay_ring* ring,
+                           const mzs_replay_store_steps_args* a, void* stream_) {
+  mz::ReplayStoreStepsArgs p{};
+  if (int rc = check_arena(arena, "mzs_replay_store_steps", &p.ar)) return rc;
+  if (int rc = check_ring(ring, "mzs_replay_store_steps", &p.ring)) return rc;
+  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_store_steps_args))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: null arguments or size mismatch (ABI)");
+  if (ring->obs_dim != arena->obs_dim || ring->num_actions != arena->num_actions || ring->device != arena->device)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: ring and arena disagree in obs_dim, num_actions or device");
+  if (a->episodes <= 0 || a->episodes > arena->capacity)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: episodes must be 1..capacity");
+  if (!a->desc_host || !a->desc || !a->serial || !a->gpow)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: null pointer");
+  if (a->n_step < 1) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: n_step must be >= 1");
+  if (a->weight_mode != 1 && a->weight_mode != 2)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: weight_mode must be 1 (mean) or 2 (sum)");
+  for (int e = 0; e < a->episodes; ++e) {
+    const int32_t* d = a->desc_host + 5 * e;
+    const int64_t len = d[2], dst = d[3];
+    if (d[0] < 0 || d[0] >= ring->num_envs)
+      return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: an episode's environment is outside 0..num_envs - 1");
+    if (len < 1 || len > ring->ring_steps || d[1] < 0 || d[1] >= ring->ring_steps)
+      return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: an episode's first row or length leaves the ring");
+    if (dst < 0 || dst + len > arena->max_steps || d[4] < 0 || d[4] >= arena->capacity)
+      return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: an episode's range leaves the arena or the table");
+  }
+  MZS_HIP(nullptr, hipSetDevice(arena->device));
+  p.episodes = a->episodes; p.n_step = a->n_step; p.weight_mode = a->weight_mode;
+  p.has_alpha = a->has_alpha ? 1 : 0; p.alpha = a->alpha;
+  p.desc = a->desc; p.serial = (const long long*)a->serial; p.gpow = a->gpow;
+  hipLaunchKernelGGL(mz::replay_store_steps_kernel, dim3(waves_grid(a->episodes)), dim3(64 * mz::kReplayWaves), 0,
+                     static_cast<hipStream_t>(stream_), p);
   MZS_HIP(nullptr, hipGetLastError());
   return MZS_OK;
 }

@@ -317,6 +317,47 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         host["gpow"] = np.array([float(gamma) ** i for i in range(int(n) + 1)], np.float64)
         self._store(placed, host, device, raw=True, n=n, alpha=alpha, weight_mode=_WEIGHT_MODES[weight], stream_steps=M)
 
+    def add_steps(self, ring, episodes, n, gamma, alpha=None, weight="mean"):
+        """Complete episodes straight from a step-major collection ring on the device (`DeviceVectorCollector`'s;
+        `ring` is its `_lib.MzsReplayRing`): `episodes` is [(environment, first ring row, length)], transition t of an
+        episode being ring row (first + t) % ring_steps of that environment.  What `add_raw` does for a dense stream
+        -- the same placement, evictions and serials, and on the device the same copies and the same fp64 arithmetic
+        for Rn, done, w, cw and the episode weight, bit for bit -- with one small upload (descriptors, serials, discount
+        powers) and one launch; no observation, policy or value crosses the host.  The strided reads of that launch
+        have not been timed against `add_raw`'s dense ones.  An episode longer than `max_steps` is add_raw's
+        ValueError, before anything is placed.  Returns the serial given to every episode, in order (an episode the
+        collection itself evicts again has one, but is not stored)."""
+        if weight not in _WEIGHT_MODES:
+            raise ValueError("weight must be 'mean' or 'sum'")
+        if int(n) < 1:
+            raise ValueError("add_steps: n must be at least 1")
+        episodes = [(int(env), int(first), int(T)) for env, first, T in episodes]
+        if not episodes:
+            return []
+        if min(T for _, _, T in episodes) <= 0:
+            raise ValueError("add_steps: episode lengths must be positive")
+        self._check_dims(int(ring.obs_dim), int(ring.num_actions))
+        placed = self._place_all([T for _, _, T in episodes])
+        serials = [e.serial for _, e in placed]
+        live = {e.serial for e in self._eps}
+        kept = [(env, first, e) for (env, first, _), (_, e) in zip(episodes, placed) if e.serial in live]
+        desc = np.array([[env, first, e.length, e.start, e.slot] for env, first, e in kept], np.int32)
+        head = np.concatenate([np.array([e.serial for _, _, e in kept], np.int64).view(np.float64),
+                               np.array([float(gamma) ** i for i in range(int(n) + 1)], np.float64)])
+        stage = np.empty(head.nbytes + desc.nbytes, np.uint8)  # the 8-byte elements first
+        stage[:head.nbytes] = head.view(np.uint8)
+        stage[head.nbytes:] = desc.reshape(-1).view(np.uint8)
+        dstage = torch.from_numpy(stage).to(self._device)
+        a = _lib.MzsReplayStoreStepsArgs()
+        a.struct_size = C.sizeof(_lib.MzsReplayStoreStepsArgs)
+        a.episodes, a.n_step, a.weight_mode = len(kept), int(n), _WEIGHT_MODES[weight]
+        a.has_alpha, a.alpha = int(alpha is not None), float(alpha if alpha is not None else 0.0)
+        a.desc_host, a.desc = desc.ctypes.data, dstage.data_ptr() + head.nbytes
+        a.serial, a.gpow = dstage.data_ptr(), dstage.data_ptr() + 8 * len(kept)
+        _lib.check(self._L.mzs_replay_store_steps(C.byref(self._arena), C.byref(ring), C.byref(a), self._stream()))
+        self._keep = (dstage,)
+        return serials
+
     def stalest(self, count):
         """Serials of up to `count` held episodes whose targets are the oldest: ordered by when they were last stored
         or reanalysed, earliest first (the episodes of one reanalysis tie; ties go by serial)."""

@@ -130,6 +130,158 @@ class VectorCollector:
         return out, key, steps * N
 
 
+def ring_plan(done, open_start, step0, min_length=1):
+    """The episodes a call of lock-step collection finishes, from its `done` flags alone (host arithmetic, no GPU).
+    done [T, N]: the flags of the call's T steps; open_start [N]: the ABSOLUTE step at which every environment's open
+    episode began; step0: the absolute index of the call's first step.  Returns (finished, dropped, new open_start):
+    the finished episodes of at least `min_length` steps as (environment, first absolute step, length) in the order in
+    which `VectorCollector.collect` hands out its trajectories (environment-major, then time), those shorter than
+    `min_length` in the same form and order, and the start of every environment's episode still open afterwards."""
+    D = np.asarray(done, bool)
+    if D.ndim != 2:
+        raise ValueError("ring_plan: done must be [T, N]")
+    open_start = np.asarray(open_start, np.int64).reshape(-1)
+    if open_start.shape[0] != D.shape[1]:
+        raise ValueError("ring_plan: one open_start per environment")
+    env, t = np.nonzero(D.T)  # environment-major, time ascending
+    end = int(step0) + t.astype(np.int64)
+    same = np.concatenate([[False], env[1:] == env[:-1]])
+    first = np.where(same, np.concatenate([[0], end[:-1] + 1]), open_start[env])
+    length = end - first + 1
+    new_open = open_start.copy()
+    new_open[env] = end + 1  # ends ascend inside an environment, so its last one stays
+    rows = list(zip(env.tolist(), first.tolist(), length.tolist()))
+    m = int(min_length)
+    return [x for x in rows if x[2] >= m], [x for x in rows if x[2] < m], new_open
+
+
+class DeviceVectorCollector:
+    """`VectorCollector` for a `DeviceReplayBuffer`, with the search results kept on the device: every step's
+    observations, actions, root values and search policies are staged in a step-major ring of `ring_steps` x N rows
+    (one launch per step, `mzs_replay_stage`), only the ACTIONS come to the host (for `venv.step`), and at the end of
+    `collect()` the rewards go up (at most two copies) and the finished episodes are cut out of the ring into the
+    buffer's arenas in one launch (`DeviceReplayBuffer.add_steps`), which computes the n-step returns, `done`, the
+    priority weights and the episode weight (`weight`: "mean" or "sum") as `add_raw` does, bit for bit.  Episodes
+    shorter than `min_length` are dropped and get no serial.  The key stream is `VectorCollector.collect`'s, and so are
+    the order of the episodes and therefore their serials.  `ring_steps` defaults to `venv.spec.max_episode_steps` plus
+    the steps of the first `collect` call: an open episode must fit the ring together with the call's steps.
+    How the strided reads of the store launch compare with `add_raw`'s dense ones has not been measured."""
+
+    def __init__(self, venv, buffer, n: int, gamma: float, alpha=0.5, weight: str = "mean", min_length: int = 1,
+                 ring_steps=None):
+        if not hasattr(buffer, "add_steps"):
+            raise ValueError(f"DeviceVectorCollector needs a buffer with the device store (DeviceReplayBuffer); "
+                             f"{type(buffer).__name__} has none")
+        if weight not in ("mean", "sum"):
+            raise ValueError("weight must be 'mean' or 'sum'")
+        if int(n) < 1:
+            raise ValueError("n must be at least 1")
+        if ring_steps is not None and int(ring_steps) < 1:
+            raise ValueError("ring_steps must be positive")
+        self.venv, self.buffer, self.n, self.gamma, self.alpha = venv, buffer, int(n), float(gamma), alpha
+        self.weight, self.min_length = weight, int(min_length)
+        self.ring_steps = None if ring_steps is None else int(ring_steps)
+        self._obs = self._ring = self._fields = None
+        self._step0 = 0          # absolute index of the next step
+        self._open_start = None  # [N] absolute first step of every open episode
+        self._open_r = None      # per environment: the host rewards of its open episode so far
+
+    def _alloc(self, N, obs_dim, A):
+        import ctypes as C
+
+        import torch
+
+        from . import _lib
+        buf = self.buffer
+        buf._check_dims(obs_dim, A)  # (allocates the arenas on first use; a mismatch is the buffer's ValueError)
+        dev, S = buf._device, self.ring_steps
+        shapes = {"obs": ((S, N, obs_dim), torch.float32), "a": ((S, N), torch.int32), "r": ((S, N), torch.float64),
+                  "v": ((S, N), torch.float32), "pi": ((S, N, A), torch.float32)}
+        self._fields = {k: torch.zeros(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+        ring = _lib.MzsReplayRing()
+        ring.struct_size = C.sizeof(_lib.MzsReplayRing)
+        ring.device = buf._arena.device
+        ring.ring_steps, ring.num_envs, ring.obs_dim, ring.num_actions = S, N, obs_dim, A
+        for k, x in self._fields.items():
+            setattr(ring, k, x.data_ptr())
+        self._ring = ring
+
+    def collect(self, model, key, steps: int, num_simulations: int = 50, temperature: float = 1.0, **act_kwargs):
+        """`steps` lock-step environment steps.  Returns (finished, advanced key, env steps): `finished` lists, in
+        `VectorCollector.collect`'s order, (length, undiscounted return, serial) of every episode that ended, the
+        return summed from the host's rewards and the serial None for one dropped as shorter than `min_length`.
+        ValueError before the first step when an open episode could outgrow the ring (its steps so far plus `steps`
+        exceed `ring_steps`): nothing is overwritten and a call with fewer steps still works."""
+        import ctypes as C
+
+        import torch
+
+        from . import _lib
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("collect: steps must be at least 1")
+        if self.ring_steps is None:
+            self.ring_steps = int(self.venv.spec.max_episode_steps) + steps
+        S = self.ring_steps
+        held = 0 if self._open_start is None else self._step0 - int(self._open_start.min())
+        if held + steps > S:
+            raise ValueError(f"collect: an open episode of {held} steps plus {steps} more does not fit the ring of "
+                             f"{S} steps (ring_steps)")
+        if self._obs is None:
+            self._obs = np.asarray(self.venv.reset())
+            N = self._obs.shape[0]
+            self._open_start, self._open_r = np.zeros(N, np.int64), [[] for _ in range(N)]
+        obs = self._obs
+        N = obs.shape[0]
+        dev = self.buffer._device if self.buffer._device is not None else model.device
+        r_l, d_l = [], []
+        for i in range(steps):
+            key, subkey = prng.split(key)
+            obs_d = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).to(dev)
+            a, pi, v = model.act(subkey, obs_d, with_pi=True, with_value=True, obs_from_batch=True, device_outputs=True,
+                                 num_simulations=num_simulations, temperature=temperature, **act_kwargs)
+            if self._ring is None:
+                self._alloc(N, int(obs_d.numel() // N), int(pi.shape[-1]))
+            flat = obs_d.reshape(N, -1).contiguous()
+            a32 = a.to(torch.int32).contiguous()
+            pi32, v32 = pi.to(torch.float32).reshape(N, -1).contiguous(), v.to(torch.float32).reshape(N).contiguous()
+            s = _lib.MzsReplayStageArgs()
+            s.struct_size = C.sizeof(_lib.MzsReplayStageArgs)
+            s.row = (self._step0 + i) % S
+            s.obs, s.a, s.v, s.pi = flat.data_ptr(), a32.data_ptr(), v32.data_ptr(), pi32.data_ptr()
+            _lib.check(self.buffer._L.mzs_replay_stage(C.byref(self._ring), C.byref(s), self.buffer._stream()))
+            nxt, r, done = self.venv.step(a32.cpu().numpy())  # the one device-to-host copy of the step
+            r_l.append(np.asarray(r, np.float64)), d_l.append(np.asarray(done, bool))
+            obs = np.asarray(nxt)
+        self._obs = obs
+        R, D = np.stack(r_l), np.stack(d_l)  # [T, N]
+        step0, row0 = self._step0, self._step0 % S
+        k = min(steps, S - row0)
+        self._fields["r"][row0:row0 + k].copy_(torch.from_numpy(R[:k]))
+        if k < steps:  # the call's rows wrap past the ring's end
+            self._fields["r"][:steps - k].copy_(torch.from_numpy(R[k:]))
+        finished, dropped, new_open = ring_plan(D, self._open_start, step0, self.min_length)
+        # the returns, from the host's rewards: the carried part of an episode, then the call's
+        Rt = np.ascontiguousarray(R.T)
+        stored = set(finished)
+        every = sorted(finished + dropped, key=lambda x: (x[0], x[1])) if dropped else finished
+        G = []
+        for env, first, T in every:
+            seg = Rt[env, max(first - step0, 0):first + T - step0]
+            G.append(float(np.sum(np.concatenate(self._open_r[env] + [seg]) if first < step0 else seg)))
+        for env in range(N):
+            if new_open[env] <= step0:  # no episode of this environment ended: the open one grows
+                self._open_r[env].append(Rt[env].copy())
+            else:
+                tail = Rt[env, new_open[env] - step0:]
+                self._open_r[env] = [tail.copy()] if len(tail) else []
+        self._open_start, self._step0 = new_open, step0 + steps
+        serials = iter(self.buffer.add_steps(self._ring, [(env, first % S, T) for env, first, T in finished], self.n,
+                                             self.gamma, self.alpha, weight=self.weight))
+        out = [(T, g, next(serials) if (env, first, T) in stored else None) for (env, first, T), g in zip(every, G)]
+        return out, key, steps * N
+
+
 def test_vector(model, venv, key, num_simulations: int, max_steps=None):
     """Greedy evaluation (muax/test.py:5-48: temperature 0, mean undiscounted return) on a vector
     environment: the FIRST episode of each of its N environments, one batched act() per step."""
@@ -180,7 +332,7 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                max_training_steps: int = 10000, test_interval: int = 10, num_test_episodes: int = 10,
                random_seed: int = 42, temperature_fn=None, metrics=None, trajectory_weight: str = "mean",
                reanalyse_every: int = 0, reanalyse_episodes=None, priority_update: bool = False,
-               priority_steps=None, is_beta=None):
+               priority_steps=None, is_beta=None, device_collect: bool = False):
     """The reference's fit() loop (muax/train.py:175-241: temperature schedule, buffer sampling, update,
     greedy test) with the acting half on a vector environment: per iteration `steps_per_iteration`
     batched act() calls -> finished episodes -> buffer, then `num_update_per_iteration` updates.
@@ -204,7 +356,12 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     `priority_update` / `priority_steps`.  The weights are normalised by the largest one of the batch, so under data
     parallelism by each rank's own batch maximum, not a global one.  A buffer whose `sample` takes no `is_beta` (the
     host `TrajectoryReplayBuffer`) is a ValueError: dropping a correction that was asked for would change what is
-    learned.  None: the key stream and every result are unchanged."""
+    learned.  None: the key stream and every result are unchanged.
+    `device_collect=True` (a buffer with the device store, `DeviceReplayBuffer`; any other is a ValueError) collects
+    with `DeviceVectorCollector` (`min_length=k_steps`, `weight=trajectory_weight`): the search results stay on the
+    device and the episodes are cut into the buffer in one launch; `episodes` and `G` of the metrics row come from the
+    host's rewards.  The same key stream and the same episodes as the host collector.  False: the key stream and every
+    result are unchanged."""
     if priority_steps is not None and int(priority_steps) < 1:
         raise ValueError("priority_steps must be None or >= 1")
     if trajectory_weight not in ("mean", "sum"):
@@ -220,7 +377,14 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                              f"{type(buffer).__name__}.sample does not")
         if not callable(is_beta) and not 0.0 <= float(is_beta) <= 1.0:
             raise ValueError("fit_vector: is_beta must be None, a number in 0..1 or a callable")
-    collector = VectorCollector(venv, n_step, gamma, alpha)
+    if device_collect:
+        if not hasattr(buffer, "add_steps"):
+            raise ValueError(f"fit_vector: device_collect needs a buffer with the device store (DeviceReplayBuffer); "
+                             f"{type(buffer).__name__} has none")
+        collector = DeviceVectorCollector(venv, buffer, n_step, gamma, alpha, weight=trajectory_weight,
+                                          min_length=k_steps)
+    else:
+        collector = VectorCollector(venv, n_step, gamma, alpha)
     prioritise = bool(priority_update) and hasattr(buffer, "update_priorities")
     key = prng.PRNGKey(random_seed)
     key, test_key, subkey = prng.split(key, 3)
@@ -229,17 +393,23 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     for it in range(iterations):
         temperature = temperature_fn(max_training_steps=max_training_steps, training_steps=training_step)
         t0 = time.perf_counter()
-        trajs, key, env_steps = collector.collect(model, key, steps_per_iteration, num_simulations, temperature)
-        collect_s = time.perf_counter() - t0
-        keep = [tr for tr in trajs if len(tr) >= k_steps]
-        weights = [tr.weights.mean() if trajectory_weight == "mean" else tr.weights.sum() for tr in keep]
-        if hasattr(buffer, "add_many"):  # (the device buffer: one upload and one launch for the collection)
-            buffer.add_many(keep, weights)
+        if device_collect:  # the episodes are in the buffer when collect() returns
+            finished, key, env_steps = collector.collect(model, key, steps_per_iteration, num_simulations, temperature)
+            row = {"iteration": it, "env_steps": env_steps, "episodes": len(finished),
+                   "collect_s": time.perf_counter() - t0,
+                   "G": float(np.mean([g for _, g, _ in finished])) if finished else float("nan")}
         else:
-            for tr, w in zip(keep, weights):
-                buffer.add(tr, w)
-        row = {"iteration": it, "env_steps": env_steps, "episodes": len(trajs), "collect_s": collect_s,
-               "G": float(np.mean([float(np.sum(t.rewards)) for t in trajs])) if trajs else float("nan")}
+            trajs, key, env_steps = collector.collect(model, key, steps_per_iteration, num_simulations, temperature)
+            collect_s = time.perf_counter() - t0
+            keep = [tr for tr in trajs if len(tr) >= k_steps]
+            weights = [tr.weights.mean() if trajectory_weight == "mean" else tr.weights.sum() for tr in keep]
+            if hasattr(buffer, "add_many"):  # (the device buffer: one upload and one launch for the collection)
+                buffer.add_many(keep, weights)
+            else:
+                for tr, w in zip(keep, weights):
+                    buffer.add(tr, w)
+            row = {"iteration": it, "env_steps": env_steps, "episodes": len(trajs), "collect_s": collect_s,
+                   "G": float(np.mean([float(np.sum(t.rewards)) for t in trajs])) if trajs else float("nan")}
         if reanalyse_every > 0 and hasattr(buffer, "reanalyse") and len(buffer) and (it + 1) % reanalyse_every == 0:
             key, subkey = prng.split(key)
             buffer.reanalyse(model, subkey, n_step, gamma, alpha, weight=trajectory_weight,

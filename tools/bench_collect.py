@@ -1,0 +1,93 @@
+"""Collection on the host against collection on the device, on the vector CartPole of examples/ with the default MLP
+trio and 50 simulations per step:
+
+  host    `VectorCollector.collect` (act() NumPy in / out at every step, episodes cut and n-step returns in NumPy)
+          followed by `DeviceReplayBuffer.add_many` of the episodes of at least k steps, as `fit_vector` does;
+  device  `DeviceVectorCollector.collect` (act() on device tensors, one staging launch per step, only the actions
+          come down; the rewards go up once and the episodes are cut into the arenas in one launch).
+
+    python tools/bench_collect.py [--iters 20] [--shape ENVS,STEPS ...] [--simulations 50]
+
+Every figure is the median of `--iters` repetitions of one whole collect (+ add), each ending in a device synchronise,
+after three untimed ones.  The two routes alternate shape by shape in one process; each keeps its own environment,
+collector and buffer, so episodes run on from one repetition to the next as they do in training."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "examples"))
+import muax_amd as mx  # noqa: E402
+from cartpole_env import VectorCartPole  # noqa: E402
+from muax_amd.utils import warm_runtime  # noqa: E402
+
+A, E, OBS, SUPPORT, N_STEP, GAMMA, ALPHA, K = 2, 8, 4, 10, 10, 0.997, 0.5, 10
+
+
+def model():
+    g = torch.Generator().manual_seed(0)
+    net = mx.nn.MZNetwork(mx.nn.Representation(E, generator=g), mx.nn.Prediction(A, 2 * SUPPORT + 1, generator=g),
+                          mx.nn.Dynamic(E, A, 2 * SUPPORT + 1, generator=g))
+    m = mx.MuZero(net, support_size=SUPPORT)
+    m.init(0, np.zeros((1, OBS)))
+    return m
+
+
+def median_ms(fn, iters, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(out))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--simulations", type=int, default=50)
+    ap.add_argument("--shape", action="append", default=[], metavar="ENVS,STEPS")
+    a = ap.parse_args()
+    shapes = [tuple(int(x) for x in s.split(",")) for s in a.shape] or [(64, 64), (1024, 64)]
+    warm_runtime()
+    print(f"vector CartPole, {a.simulations} simulations, n_step {N_STEP}, episodes of at least {K} steps stored; "
+          f"median of {a.iters} synchronised repetitions, ms")
+    print(f"{'envs x steps':>12} | {'host collect':>12} {'host collect+add_many':>21} | {'device collect (incl. add)':>26} | "
+          f"{'host / device':>13}")
+    for envs, steps in shapes:
+        m = model()
+        state = {"hk": mx.prng.PRNGKey(0), "dk": mx.prng.PRNGKey(0)}
+        cap, rows = 8 * envs, 8 * envs * steps + 4096
+        host_buf, dev_buf = mx.DeviceReplayBuffer(cap, rows), mx.DeviceReplayBuffer(cap, rows)
+        host = mx.VectorCollector(VectorCartPole(envs, seed=0), N_STEP, GAMMA, ALPHA)
+        host_only = mx.VectorCollector(VectorCartPole(envs, seed=0), N_STEP, GAMMA, ALPHA)
+        dev = mx.DeviceVectorCollector(VectorCartPole(envs, seed=0), dev_buf, N_STEP, GAMMA, ALPHA, min_length=K)
+
+        def host_collect():
+            _, state["hk"], _ = host_only.collect(m, state["hk"], steps, a.simulations)
+
+        def host_route():
+            trajs, state["hk"], _ = host.collect(m, state["hk"], steps, a.simulations)
+            keep = [t for t in trajs if len(t) >= K]
+            host_buf.add_many(keep, [t.weights.mean() for t in keep])
+
+        def device_route():
+            _, state["dk"], _ = dev.collect(m, state["dk"], steps, a.simulations)
+
+        hc = median_ms(host_collect, a.iters)
+        hr = median_ms(host_route, a.iters)
+        dr = median_ms(device_route, a.iters)
+        print(f"{envs:>7} x {steps:<2} | {hc:12.3f} {hr:21.3f} | {dr:26.3f} | {hr / dr:12.2f}x", flush=True)
+
+
+if __name__ == "__main__":
+    main()
