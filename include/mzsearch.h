@@ -769,6 +769,47 @@ typedef struct mzs_replay_store_steps_args {
 int mzs_replay_store_steps(const mzs_replay_arena *arena, const mzs_replay_ring *ring,
                            const mzs_replay_store_steps_args *a, void *stream);
 
+/* ---- vector environments stepped on the device: the cart-pole ----
+ * N cart-poles (Barto, Sutton, Anderson 1983: explicit Euler at 50 Hz, force +-10 N, reward 1 per step; an episode ends
+ * when |x| > 2.4, |theta| > 12 * 2 * pi / 360 or after max_episode_steps steps) with auto-reset.  The descriptor and
+ * its three arrays are the caller's (device memory, state 16-byte aligned); zeroed arrays are a valid start.
+ * The start state of environment e, its d-th draw (d = draws[e]), component c:
+ *   state[c] = -0.05 + 0.1 * u53(key, e, 4 d + c),  u53 = ((y0 << 32 | y1) >> 11) * 2^-53 of threefry2x32(key, x0, x1)
+ * (the uniform of mzs_replay_sample), after which draws[e] grows by one: no math-library call, so the same bits as the
+ * host's restatement.  4 d + c is taken modulo 2^32.
+ * Both entries: one launch, one thread per environment, on the caller's stream; no allocation, no copy to the host, no
+ * synchronisation.  MZS_E_INVALID before any launch for a struct size, a null pointer, num_envs < 1,
+ * max_episode_steps < 1, or a state / obs_out that is not 16-byte aligned.  errors: mzs_last_error(NULL) */
+typedef struct mzs_env_cartpole {
+  int32_t struct_size;       /* = sizeof(mzs_env_cartpole) */
+  int32_t device;
+  int32_t num_envs;          /* N */
+  int32_t max_episode_steps;
+  uint32_t key[2];
+  double *state;             /* [N, 4]: x, x_dot, theta, theta_dot */
+  int32_t *t;                /* [N] steps of the open episode */
+  int32_t *draws;            /* [N] start states drawn so far */
+} mzs_env_cartpole;
+
+/* Every environment draws a fresh start state; t = 0; obs_out [N, 4] = (float)state. */
+int mzs_env_cartpole_reset(const mzs_env_cartpole *env, float *obs_out, void *stream);
+
+/* One step of every environment in fp64, in the operation order of the host's VectorCartPole.step (no fused
+ * multiply-add): force +10 where a == 1, -10 for any other value; r_out = 1.0; done_out = 1 where the NEW state has
+ * |x| > 2.4 or |theta| > the angle limit, or t + 1 >= max_episode_steps, else 0.  A finished environment draws its next
+ * start state and sets t = 0 in the same launch, so obs_out = (float)state is already the first observation of its
+ * next episode.  sin and cos are the device library's: the new state equals a host libm's to a few units in the last
+ * place, not bit for bit.  r_out and done_out are plain [N] pointers (a row of a larger array will do). */
+typedef struct mzs_env_step_args {
+  int32_t struct_size;       /* = sizeof(mzs_env_step_args) */
+  int32_t reserved0;
+  const int32_t *a;          /* [N] */
+  float *obs_out;            /* [N, 4] */
+  double *r_out;             /* [N] */
+  uint8_t *done_out;         /* [N] */
+} mzs_env_step_args;
+int mzs_env_cartpole_step(const mzs_env_cartpole *env, const mzs_env_step_args *a, void *stream);
+
 /* ---- forward value unroll of the default MLP trio: the priorities mzs_replay_update_priorities takes ----
  * For every window j < batch and step i < k_prio, with s_0 = Representation(obs[j]) and s_{i+1} = the next state of
  * Dynamic(s_i, actions[j][i]) (muax/nn.py:59-115):

@@ -5,8 +5,8 @@ and linked into one shared object: the C-ABI's handle and registries (mz_api.hip
 act() dispatch (mz_act.hip), the step-wise path and the generic one-launch search with the step kernels
 (mz_stepwise.hip), the training step (mz_train.hip), the self-test and Dirichlet kernels (mz_selftest.hip) --, the
 fused act() kernel instances in five groups (mz_fused_g*.hip, listed in mz_instances.def), the wide-action act()
-kernel (mz_wide.hip), the ResNet recurrent kernel (mz_conv.hip), the device-resident replay (mz_replay.hip) and the
-forward value unroll behind its priorities (mz_unroll.hip).  Only the units whose sources changed are recompiled."""
+kernel (mz_wide.hip), the ResNet recurrent kernel (mz_conv.hip), the device-resident replay (mz_replay.hip), the
+forward value unroll behind its priorities (mz_unroll.hip) and the device vector environments (mz_env.hip).  Only the units whose sources changed are recompiled."""
 from __future__ import annotations
 
 import os
@@ -40,6 +40,7 @@ UNITS = {
     "mz_repr.hip": ["mz_host.h", "mz_repr.cuh", "mz_repr_host.h", "mz_norm.cuh", "mz_spec.cuh", _ABI],
     "mz_ez.hip": ["mz_host.h", "mz_ez.cuh", "mz_spec.cuh", _ABI],
     "mz_replay.hip": ["mz_host.h", "mz_replay.cuh", "mz_spec.cuh", _ABI],
+    "mz_env.hip": ["mz_host.h", "mz_env.cuh", "mz_spec.cuh", _ABI],
     "mz_unroll.hip": ["mz_host.h", "mz_unroll.cuh", "mz_mlp_generic.cuh", "mz_step_jump.cuh", "mz_step.cuh", "mz_spec.cuh", _ABI],
 }
 SOURCES = list(UNITS)

@@ -1,0 +1,101 @@
+"""Vector environments stepped on the device ("Device environments").
+
+The device-environment protocol is duck-typed, as `add_steps` and `update_priorities` are.  An object implements it
+when it has
+
+    reset_device() -> obs                    float32 [N, obs_dim] device tensor
+    step_device(a, r_out, done_out) -> obs   a: int32 [N] device tensor; r_out: float64 [N] and done_out: uint8 [N]
+                                             device views the step writes; obs: the next observations, device tensor
+    n, spec.max_episode_steps, device
+
+with the conventions of the host protocol (muax_amd/vector.py): `done` marks the LAST step of an episode and the
+returned observation of a finished environment is already the first one of its next episode.  Neither call may
+synchronise; both run on the current stream of `device`.  The returned tensor may be the environment's own and be
+overwritten by its next call: `DeviceVectorCollector` stages it in its ring before it steps again.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from types import SimpleNamespace
+
+import numpy as np
+
+from . import prng
+
+
+class DeviceCartPole:
+    """`examples/cartpole_env.VectorCartPole` on the device: N cart-poles, one launch per step
+    (`mzs_env_cartpole_step`: the same fp64 arithmetic in the same order, the device's sin / cos), auto-reset inside
+    that launch.  The start states are NOT NumPy's: environment e's d-th draw of component c is
+    `-0.05 + 0.1 * u53(PRNGKey(seed), e, 4 d + c)`, the replay sampler's threefry uniform, so the state stream is a
+    function of the seed and the actions alone.  Also offers the host protocol (`reset()` / `step(actions)` return NumPy
+    copies, each a synchronisation), so it can be handed to `test_vector`; which of the two is called does not change
+    the stream."""
+
+    def __init__(self, n, max_episode_steps=500, seed=0, device=None):
+        import torch
+
+        from . import _lib
+        self.n = int(n)
+        if self.n < 1 or int(max_episode_steps) < 1:
+            raise ValueError("DeviceCartPole: n and max_episode_steps must be at least 1")
+        self.spec = SimpleNamespace(id="CartPole-v1", max_episode_steps=int(max_episode_steps))
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("DeviceCartPole: needs a GPU device (use examples/cartpole_env.VectorCartPole on the host)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._L = _lib.load()
+        dev = self.device
+        self._state = torch.zeros((self.n, 4), dtype=torch.float64, device=dev)
+        self._t = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self._draws = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self._obs = torch.zeros((self.n, 4), dtype=torch.float32, device=dev)
+        self._r = torch.zeros(self.n, dtype=torch.float64, device=dev)      # the host protocol's outputs
+        self._done = torch.zeros(self.n, dtype=torch.uint8, device=dev)
+        key = prng.PRNGKey(seed)
+        env = _lib.MzsEnvCartPole()
+        env.struct_size = C.sizeof(_lib.MzsEnvCartPole)
+        env.device, env.num_envs, env.max_episode_steps = dev.index, self.n, self.spec.max_episode_steps
+        env.key[0], env.key[1] = int(key[0]), int(key[1])
+        env.state, env.t, env.draws = self._state.data_ptr(), self._t.data_ptr(), self._draws.data_ptr()
+        self._env = env
+
+    def _stream(self):
+        import torch
+        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+        return C.c_void_p(raw(self.device.index) if raw is not None
+                          else torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _view(self, x, dtype, name):
+        if x.dtype != dtype or x.device != self.device or tuple(x.shape) != (self.n,) or not x.is_contiguous():
+            raise ValueError(f"step_device: {name} must be a contiguous {dtype} [{self.n}] tensor on {self.device}")
+        return x.data_ptr()
+
+    # ---- the device protocol
+    def reset_device(self):
+        from . import _lib
+        _lib.check(self._L.mzs_env_cartpole_reset(C.byref(self._env), self._obs.data_ptr(), self._stream()))
+        return self._obs
+
+    def step_device(self, a, r_out, done_out):
+        import torch
+
+        from . import _lib
+        s = _lib.MzsEnvStepArgs()
+        s.struct_size = C.sizeof(_lib.MzsEnvStepArgs)
+        s.a = self._view(a, torch.int32, "a")
+        s.r_out, s.done_out = self._view(r_out, torch.float64, "r_out"), self._view(done_out, torch.uint8, "done_out")
+        s.obs_out = self._obs.data_ptr()
+        _lib.check(self._L.mzs_env_cartpole_step(C.byref(self._env), C.byref(s), self._stream()))
+        return self._obs
+
+    # ---- the host protocol
+    def reset(self):
+        return self.reset_device().cpu().numpy()
+
+    def step(self, actions):
+        import torch
+        a = torch.from_numpy(np.ascontiguousarray(np.asarray(actions).reshape(-1), dtype=np.int32)).to(self.device)
+        obs = self.step_device(a, self._r, self._done)
+        return obs.cpu().numpy(), self._r.cpu().numpy(), self._done.cpu().numpy().astype(bool)

@@ -165,7 +165,13 @@ class DeviceVectorCollector:
     shorter than `min_length` are dropped and get no serial.  The key stream is `VectorCollector.collect`'s, and so are
     the order of the episodes and therefore their serials.  `ring_steps` defaults to `venv.spec.max_episode_steps` plus
     the steps of the first `collect` call: an open episode must fit the ring together with the call's steps.
-    How the strided reads of the store launch compare with `add_raw`'s dense ones has not been measured."""
+    How the strided reads of the store launch compare with `add_raw`'s dense ones has not been measured.
+    A `venv` with `step_device` (the device-environment protocol of muax_amd/envs.py, e.g. `DeviceCartPole`) is stepped
+    on the device: its observation tensor goes into act() and the staging launch as it is, `step_device` writes the
+    step's rewards straight into the ring's `r` row and its `done` flags into the same row of a uint8
+    [ring_steps, N] tensor, nothing inside the step loop copies to the host or synchronises, and per `collect()` the
+    call's `r` and `done` rows come down once (at most two copies each) for `ring_plan` and the returns; there is no
+    reward upload.  A host `venv` takes the path it always took."""
 
     def __init__(self, venv, buffer, n: int, gamma: float, alpha=0.5, weight: str = "mean", min_length: int = 1,
                  ring_steps=None):
@@ -181,7 +187,7 @@ class DeviceVectorCollector:
         self.venv, self.buffer, self.n, self.gamma, self.alpha = venv, buffer, int(n), float(gamma), alpha
         self.weight, self.min_length = weight, int(min_length)
         self.ring_steps = None if ring_steps is None else int(ring_steps)
-        self._obs = self._ring = self._fields = None
+        self._obs = self._ring = self._fields = self._done_rows = None
         self._step0 = 0          # absolute index of the next step
         self._open_start = None  # [N] absolute first step of every open episode
         self._open_r = None      # per environment: the host rewards of its open episode so far
@@ -206,17 +212,66 @@ class DeviceVectorCollector:
             setattr(ring, k, x.data_ptr())
         self._ring = ring
 
+    def _stage(self, i, obs_d, a, pi, v):
+        """One `mzs_replay_stage`: step i of the call into its ring row.  Returns the actions as int32 on the device."""
+        import ctypes as C
+
+        import torch
+
+        from . import _lib
+        N = self._ring.num_envs
+        flat = obs_d.reshape(N, -1).contiguous()
+        a32 = a.to(torch.int32).contiguous()
+        pi32, v32 = pi.to(torch.float32).reshape(N, -1).contiguous(), v.to(torch.float32).reshape(N).contiguous()
+        s = _lib.MzsReplayStageArgs()
+        s.struct_size = C.sizeof(_lib.MzsReplayStageArgs)
+        s.row = (self._step0 + i) % self.ring_steps
+        s.obs, s.a, s.v, s.pi = flat.data_ptr(), a32.data_ptr(), v32.data_ptr(), pi32.data_ptr()
+        _lib.check(self.buffer._L.mzs_replay_stage(C.byref(self._ring), C.byref(s), self.buffer._stream()))
+        return a32
+
+    def _steps_device_env(self, model, key, steps, num_simulations, temperature, act_kwargs):
+        """The step loop for a device environment (muax_amd/envs.py): the observations never leave the device, the
+        environment writes every step's rewards into the ring's `r` row and its flags into the same row of
+        `self._done_rows` (uint8 [ring_steps, N], beside the ring fields), and nothing in the loop copies to the host
+        or synchronises; all launches go on the one stream the staging launch uses, which orders the environment's
+        overwrite of its observation tensor after the staging launch that read it.  Afterwards the call's rows of `r`
+        and of the flags come down, in at most two copies each.  Returns (key, R [T, N] float64, D [T, N] bool)."""
+        import torch
+        venv, S = self.venv, self.ring_steps
+        N = int(venv.n)
+        if self._obs is None:
+            dev = self.buffer._device
+            if dev is not None and dev.index is not None and torch.device(venv.device) != dev:
+                raise ValueError(f"collect: the environment is on {venv.device}, the buffer on {dev}")
+            self._obs = venv.reset_device()
+            self._open_start, self._open_r = np.zeros(N, np.int64), [[] for _ in range(N)]
+        obs_d = self._obs
+        for i in range(steps):
+            key, subkey = prng.split(key)
+            a, pi, v = model.act(subkey, obs_d, with_pi=True, with_value=True, obs_from_batch=True, device_outputs=True,
+                                 num_simulations=num_simulations, temperature=temperature, **act_kwargs)
+            if self._ring is None:
+                self._alloc(N, int(obs_d.numel() // N), int(pi.shape[-1]))
+                self._done_rows = torch.zeros((S, N), dtype=torch.uint8, device=self._fields["r"].device)
+            a32 = self._stage(i, obs_d, a, pi, v)
+            row = (self._step0 + i) % S
+            obs_d = venv.step_device(a32, self._fields["r"][row], self._done_rows[row])
+        self._obs = obs_d
+        row0 = self._step0 % S
+        k = min(steps, S - row0)
+        parts = [(row0, row0 + k)] + ([(0, steps - k)] if k < steps else [])
+        R = np.concatenate([self._fields["r"][lo:hi].cpu().numpy() for lo, hi in parts])
+        D = np.concatenate([self._done_rows[lo:hi].cpu().numpy() for lo, hi in parts]).astype(bool)
+        return key, R, D
+
     def collect(self, model, key, steps: int, num_simulations: int = 50, temperature: float = 1.0, **act_kwargs):
         """`steps` lock-step environment steps.  Returns (finished, advanced key, env steps): `finished` lists, in
         `VectorCollector.collect`'s order, (length, undiscounted return, serial) of every episode that ended, the
         return summed from the host's rewards and the serial None for one dropped as shorter than `min_length`.
         ValueError before the first step when an open episode could outgrow the ring (its steps so far plus `steps`
         exceed `ring_steps`): nothing is overwritten and a call with fewer steps still works."""
-        import ctypes as C
-
         import torch
-
-        from . import _lib
         steps = int(steps)
         if steps < 1:
             raise ValueError("collect: steps must be at least 1")
@@ -227,39 +282,37 @@ class DeviceVectorCollector:
         if held + steps > S:
             raise ValueError(f"collect: an open episode of {held} steps plus {steps} more does not fit the ring of "
                              f"{S} steps (ring_steps)")
-        if self._obs is None:
-            self._obs = np.asarray(self.venv.reset())
-            N = self._obs.shape[0]
-            self._open_start, self._open_r = np.zeros(N, np.int64), [[] for _ in range(N)]
-        obs = self._obs
-        N = obs.shape[0]
-        dev = self.buffer._device if self.buffer._device is not None else model.device
-        r_l, d_l = [], []
-        for i in range(steps):
-            key, subkey = prng.split(key)
-            obs_d = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).to(dev)
-            a, pi, v = model.act(subkey, obs_d, with_pi=True, with_value=True, obs_from_batch=True, device_outputs=True,
-                                 num_simulations=num_simulations, temperature=temperature, **act_kwargs)
-            if self._ring is None:
-                self._alloc(N, int(obs_d.numel() // N), int(pi.shape[-1]))
-            flat = obs_d.reshape(N, -1).contiguous()
-            a32 = a.to(torch.int32).contiguous()
-            pi32, v32 = pi.to(torch.float32).reshape(N, -1).contiguous(), v.to(torch.float32).reshape(N).contiguous()
-            s = _lib.MzsReplayStageArgs()
-            s.struct_size = C.sizeof(_lib.MzsReplayStageArgs)
-            s.row = (self._step0 + i) % S
-            s.obs, s.a, s.v, s.pi = flat.data_ptr(), a32.data_ptr(), v32.data_ptr(), pi32.data_ptr()
-            _lib.check(self.buffer._L.mzs_replay_stage(C.byref(self._ring), C.byref(s), self.buffer._stream()))
-            nxt, r, done = self.venv.step(a32.cpu().numpy())  # the one device-to-host copy of the step
-            r_l.append(np.asarray(r, np.float64)), d_l.append(np.asarray(done, bool))
-            obs = np.asarray(nxt)
-        self._obs = obs
-        R, D = np.stack(r_l), np.stack(d_l)  # [T, N]
         step0, row0 = self._step0, self._step0 % S
-        k = min(steps, S - row0)
-        self._fields["r"][row0:row0 + k].copy_(torch.from_numpy(R[:k]))
-        if k < steps:  # the call's rows wrap past the ring's end
-            self._fields["r"][:steps - k].copy_(torch.from_numpy(R[k:]))
+        k = min(steps, S - row0)  # the call's rows wrap past the ring's end when k < steps
+        if hasattr(self.venv, "step_device"):
+            key, R, D = self._steps_device_env(model, key, steps, num_simulations, temperature, act_kwargs)
+            N = R.shape[1]
+        else:
+            if self._obs is None:
+                self._obs = np.asarray(self.venv.reset())
+                N = self._obs.shape[0]
+                self._open_start, self._open_r = np.zeros(N, np.int64), [[] for _ in range(N)]
+            obs = self._obs
+            N = obs.shape[0]
+            dev = self.buffer._device if self.buffer._device is not None else model.device
+            r_l, d_l = [], []
+            for i in range(steps):
+                key, subkey = prng.split(key)
+                obs_d = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).to(dev)
+                a, pi, v = model.act(subkey, obs_d, with_pi=True, with_value=True, obs_from_batch=True,
+                                     device_outputs=True, num_simulations=num_simulations, temperature=temperature,
+                                     **act_kwargs)
+                if self._ring is None:
+                    self._alloc(N, int(obs_d.numel() // N), int(pi.shape[-1]))
+                a32 = self._stage(i, obs_d, a, pi, v)
+                nxt, r, done = self.venv.step(a32.cpu().numpy())  # the one device-to-host copy of the step
+                r_l.append(np.asarray(r, np.float64)), d_l.append(np.asarray(done, bool))
+                obs = np.asarray(nxt)
+            self._obs = obs
+            R, D = np.stack(r_l), np.stack(d_l)  # [T, N]
+            self._fields["r"][row0:row0 + k].copy_(torch.from_numpy(R[:k]))
+            if k < steps:
+                self._fields["r"][:steps - k].copy_(torch.from_numpy(R[k:]))
         finished, dropped, new_open = ring_plan(D, self._open_start, step0, self.min_length)
         # the returns, from the host's rewards: the carried part of an episode, then the call's
         Rt = np.ascontiguousarray(R.T)
@@ -361,7 +414,10 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     with `DeviceVectorCollector` (`min_length=k_steps`, `weight=trajectory_weight`): the search results stay on the
     device and the episodes are cut into the buffer in one launch; `episodes` and `G` of the metrics row come from the
     host's rewards.  The same key stream and the same episodes as the host collector.  False: the key stream and every
-    result are unchanged."""
+    result are unchanged.
+    A `venv` with `step_device` (a device environment, muax_amd/envs.py) is stepped on the device by that collector;
+    it needs `device_collect=True` and a buffer with the device store, and is a ValueError otherwise: stepping it
+    through host copies would hide the cost it exists to avoid.  `test_env` stays a host-protocol environment."""
     if priority_steps is not None and int(priority_steps) < 1:
         raise ValueError("priority_steps must be None or >= 1")
     if trajectory_weight not in ("mean", "sum"):
@@ -377,6 +433,14 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                              f"{type(buffer).__name__}.sample does not")
         if not callable(is_beta) and not 0.0 <= float(is_beta) <= 1.0:
             raise ValueError("fit_vector: is_beta must be None, a number in 0..1 or a callable")
+    if hasattr(venv, "step_device"):
+        if not device_collect:
+            raise ValueError(f"fit_vector: {type(venv).__name__} is a device environment (it has step_device) and needs "
+                             f"device_collect=True; device_collect is False")
+        if not hasattr(buffer, "add_steps"):
+            raise ValueError(f"fit_vector: {type(venv).__name__} is a device environment (it has step_device) and needs "
+                             f"a buffer with the device store, add_steps (DeviceReplayBuffer); "
+                             f"{type(buffer).__name__} has none")
     if device_collect:
         if not hasattr(buffer, "add_steps"):
             raise ValueError(f"fit_vector: device_collect needs a buffer with the device store (DeviceReplayBuffer); "

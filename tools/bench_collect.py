@@ -6,7 +6,15 @@ trio and 50 simulations per step:
   device  `DeviceVectorCollector.collect` (act() on device tensors, one staging launch per step, only the actions
           come down; the rewards go up once and the episodes are cut into the arenas in one launch).
 
-    python tools/bench_collect.py [--iters 20] [--shape ENVS,STEPS ...] [--simulations 50]
+  with --device-env, two more columns:
+  dev env `DeviceVectorCollector.collect` on `muax_amd.DeviceCartPole`: the environment is stepped on the device too
+          (act() on its observation tensor, the staging launch, one environment launch per step; the rewards and the
+          `done` flags come down once per collect).  Its start states are its own threefry draws, so its episodes are
+          not the other routes' episodes;
+  act()   STEPS x act() alone on a fixed device tensor with device outputs, one synchronise at the end: the search
+          launches every route pays.
+
+    python tools/bench_collect.py [--iters 20] [--shape ENVS,STEPS ...] [--simulations 50] [--device-env]
 
 Every figure is the median of `--iters` repetitions of one whole collect (+ add), each ending in a device synchronise,
 after three untimed ones.  The two routes alternate shape by shape in one process; each keeps its own environment,
@@ -51,18 +59,53 @@ def median_ms(fn, iters, warm=3):
     return float(np.median(out))
 
 
+def split_ms(collector, fn, iters):
+    """Where one collect() of the device-environment route spends its time: the step loop up to and including the
+    download of the call's rewards and flags (which waits for the device), `add_steps` (upload, store launch, then a
+    synchronise added here) and the rest (ring_plan, the returns and the bookkeeping, on the host).  Medians, ms."""
+    spent = {"loop": [], "add_steps": []}
+
+    def timed(obj, name, key, sync):
+        inner = getattr(obj, name)
+
+        def outer(*args, **kw):
+            t0 = time.perf_counter()
+            out = inner(*args, **kw)
+            if sync:
+                torch.cuda.synchronize()
+            spent[key][-1] += (time.perf_counter() - t0) * 1e3
+            return out
+        setattr(obj, name, outer)
+        return lambda: setattr(obj, name, inner)
+
+    undo = [timed(collector, "_steps_device_env", "loop", False), timed(collector.buffer, "add_steps", "add_steps", True)]
+    total = []
+    for _ in range(iters):
+        for v in spent.values():
+            v.append(0.0)
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        total.append((time.perf_counter() - t0) * 1e3)
+    for u in undo:
+        u()
+    loop, add = float(np.median(spent["loop"])), float(np.median(spent["add_steps"]))
+    return float(np.median(total)), loop, add
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--simulations", type=int, default=50)
     ap.add_argument("--shape", action="append", default=[], metavar="ENVS,STEPS")
+    ap.add_argument("--device-env", action="store_true", help="also time collection on DeviceCartPole and act() alone")
     a = ap.parse_args()
     shapes = [tuple(int(x) for x in s.split(",")) for s in a.shape] or [(64, 64), (1024, 64)]
     warm_runtime()
     print(f"vector CartPole, {a.simulations} simulations, n_step {N_STEP}, episodes of at least {K} steps stored; "
           f"median of {a.iters} synchronised repetitions, ms")
     print(f"{'envs x steps':>12} | {'host collect':>12} {'host collect+add_many':>21} | {'device collect (incl. add)':>26} | "
-          f"{'host / device':>13}")
+          f"{'host / device':>13}" + (f" | {'dev env collect (incl. add)':>27} {'steps x act()':>13}" if a.device_env else ""))
     for envs, steps in shapes:
         m = model()
         state = {"hk": mx.prng.PRNGKey(0), "dk": mx.prng.PRNGKey(0)}
@@ -86,7 +129,28 @@ def main():
         hc = median_ms(host_collect, a.iters)
         hr = median_ms(host_route, a.iters)
         dr = median_ms(device_route, a.iters)
-        print(f"{envs:>7} x {steps:<2} | {hc:12.3f} {hr:21.3f} | {dr:26.3f} | {hr / dr:12.2f}x", flush=True)
+        line = f"{envs:>7} x {steps:<2} | {hc:12.3f} {hr:21.3f} | {dr:26.3f} | {hr / dr:12.2f}x"
+        if a.device_env:
+            env_buf = mx.DeviceReplayBuffer(cap, rows)
+            env_dev = mx.DeviceVectorCollector(mx.DeviceCartPole(envs, seed=0), env_buf, N_STEP, GAMMA, ALPHA, min_length=K)
+            state["ek"] = state["ak"] = mx.prng.PRNGKey(0)
+            fixed = torch.from_numpy(VectorCartPole(envs, seed=0).reset()).to(m.device)
+
+            def env_route():
+                _, state["ek"], _ = env_dev.collect(m, state["ek"], steps, a.simulations)
+
+            def act_alone():
+                for _ in range(steps):
+                    state["ak"], sub = mx.prng.split(state["ak"])
+                    m.act(sub, fixed, with_pi=True, with_value=True, obs_from_batch=True, device_outputs=True,
+                          num_simulations=a.simulations)
+
+            line += f" | {median_ms(env_route, a.iters):27.3f} {median_ms(act_alone, a.iters):13.3f}"
+        print(line, flush=True)
+        if a.device_env:
+            total, loop, add = split_ms(env_dev, env_route, a.iters)
+            print(f"{'':>12}   dev env collect, split: {total:.3f} = step loop and download {loop:.3f} + add_steps "
+                  f"{add:.3f} + host tail {total - loop - add:.3f}", flush=True)
 
 
 if __name__ == "__main__":
