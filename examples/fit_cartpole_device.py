@@ -4,9 +4,10 @@ lock-step environment step nothing crosses the host: act() on the environment's 
 one environment launch; per iteration the rewards and `done` flags come down once and the finished episodes are cut
 into the buffer in one launch.  The start states are the device environment's own threefry draws, not NumPy's, so the
 curves are not those of fit_cartpole_vector.py seed for seed.  The greedy test steps a second DeviceCartPole through its
-host protocol.
+host protocol.  With --device-plan the episodes are also cut and their returns summed on the device
+(`fit_vector(device_plan=True)`): per iteration only the counts and one row per finished episode come down.
 
-    python examples/fit_cartpole_device.py [--envs 1024] [--steps 128] [--iterations 100] [--updates 300]
+    python examples/fit_cartpole_device.py [--envs 1024] [--steps 128] [--iterations 100] [--updates 300] [--device-plan]
 """
 import argparse
 import json
@@ -30,6 +31,7 @@ def main():
     ap.add_argument("--rows", type=int, default=1 << 20, help="transitions kept (the arenas' rows)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--traj-weight", default="sum", choices=["mean", "sum"])
+    ap.add_argument("--device-plan", action="store_true", help="cut the episodes and sum their returns on the device")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -51,7 +53,7 @@ def main():
     metrics = Timed()
     muax.fit_vector(model, muax.DeviceCartPole(args.envs, seed=args.seed), muax.DeviceCartPole(16, seed=10_000 + args.seed),
                     n_step=10, gamma=discount, alpha=0.5, buffer=muax.DeviceReplayBuffer(args.buffer, args.rows),
-                    device_collect=True, num_simulations=50,
+                    device_collect=True, device_plan=args.device_plan, num_simulations=50,
                     iterations=args.iterations, steps_per_iteration=args.steps, k_steps=10, num_trajectory=32,
                     sample_per_trajectory=1, num_update_per_iteration=args.updates, max_training_steps=total,
                     test_interval=5, random_seed=args.seed, metrics=metrics, trajectory_weight=args.traj_weight)
@@ -61,7 +63,7 @@ def main():
               f"loss {r.get('loss', float('nan')):.4f}  updates {r['training_step']:6d}"
               + (f"  test_G {r['test_G']:.1f}" if "test_G" in r else ""), flush=True)
     env_steps = int(sum(r["env_steps"] for r in metrics))
-    summary = {"recipe": f"fit_vector(device_collect), {args.envs} cart-poles on the device, {args.steps} steps/iteration, S=50, k_steps=10, "
+    summary = {"recipe": f"fit_vector(device_collect{', device_plan' if args.device_plan else ''}), {args.envs} cart-poles on the device, {args.steps} steps/iteration, S=50, k_steps=10, "
                          f"buffer {args.buffer}, trajectory weight {args.traj_weight}",
                "iterations": len(metrics), "updates": metrics[-1]["training_step"], "env_steps": env_steps,
                "wall_s": round(wall, 1), "env_steps_per_s_whole_loop": round(env_steps / wall),

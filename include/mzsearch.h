@@ -769,6 +769,42 @@ typedef struct mzs_replay_store_steps_args {
 int mzs_replay_store_steps(const mzs_replay_arena *arena, const mzs_replay_ring *ring,
                            const mzs_replay_store_steps_args *a, void *stream);
 
+/* The episodes a collection call finishes, cut and summed on the device: what the host otherwise works out from the
+ * downloaded [steps, N] rewards and flags.  The rewards are ring->r; `done` is a uint8 [ring_steps, N] plane beside the
+ * ring (the flags mzs_env_cartpole_step wrote); step t of the call is ring row (row0 + t) % ring_steps.
+ * Environment e walks t = 0 .. steps - 1 in time order with len = open_len[e], g = open_ret[e]: every step does
+ * len += 1 and g = g + r (a plain fp64 add in time order: no fused multiply-add, no reassociation -- NOT a pairwise
+ * sum); where done != 0 the episode (e, first, len, g) ends, first = ((row0 - open_len[e] % ring_steps) + ring_steps) %
+ * ring_steps for the environment's first episode of the call and the row after the previous end (modulo ring_steps)
+ * for later ones, and len = 0, g = 0.0 start the next.  At the end len and g go back to open_len[e], open_ret[e].
+ * Output: dense, environment-major then time: episode i of that order is ep[i] = {environment, first ring row, length,
+ * stored = (length >= min_length)} and ret[i] = g.  counts = {episodes, stored episodes, max open_len afterwards, 0}.
+ * Rows at or beyond counts[0] are not written; rows at or beyond max_out are never written and counts[0], counts[1]
+ * still report the true totals (the caller compares counts[0] with max_out).
+ * scratch: num_envs + (num_envs + 255) / 256 int32 of device memory, the call's to overwrite; nothing is kept in it
+ * between calls.
+ * Two launches on the caller's stream (a count, then a scan-and-emit that walks again; one thread per environment);
+ * deterministic; no allocation, no copy to the host, no synchronisation.  counts[1] and counts[2] are integer atomics.
+ * MZS_E_INVALID before any launch, the field named, for: struct sizes; a null pointer; non-positive ring dimensions;
+ * row0 outside 0 .. ring_steps - 1; steps outside 1 .. ring_steps; num_envs * steps >= 2^31; min_length < 1;
+ * max_out < 1. */
+typedef struct mzs_replay_plan_args {
+  int32_t struct_size;     /* = sizeof(mzs_replay_plan_args) */
+  int32_t row0;            /* ring row of the call's first step */
+  int32_t steps;           /* T */
+  int32_t min_length;
+  int32_t max_out;         /* rows of ep / ret */
+  int32_t reserved0;
+  const uint8_t *done;     /* [ring_steps, N] */
+  int32_t *open_len;       /* [N] in/out: steps of each environment's open episode */
+  double *open_ret;        /* [N] in/out: sum of that open episode's rewards so far */
+  int32_t *ep;             /* out [max_out][4] */
+  double *ret;             /* out [max_out] */
+  int32_t *counts;         /* out [4] */
+  int32_t *scratch;        /* [num_envs + (num_envs + 255) / 256] */
+} mzs_replay_plan_args;
+int mzs_replay_plan_steps(const mzs_replay_ring *ring, const mzs_replay_plan_args *a, void *stream);
+
 /* ---- vector environments stepped on the device: the cart-pole ----
  * N cart-poles (Barto, Sutton, Anderson 1983: explicit Euler at 50 Hz, force +-10 N, reward 1 per step; an episode ends
  * when |x| > 2.4, |theta| > 12 * 2 * pi / 360 or after max_episode_steps steps) with auto-reset.  The descriptor and

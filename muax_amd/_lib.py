@@ -183,6 +183,17 @@ class MzsReplayStoreStepsArgs(C.Structure):
                 + [(n, _vp) for n in ("desc_host", "desc", "serial", "gpow")])
 
 
+class MzsReplayPlanArgs(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("row0", C.c_int32), ("steps", C.c_int32), ("min_length", C.c_int32),
+                 ("max_out", C.c_int32), ("reserved0", C.c_int32)]
+                + [(n, _vp) for n in ("done", "open_len", "open_ret", "ep", "ret", "counts", "scratch")])
+
+
+def replay_plan_scratch(num_envs: int) -> int:
+    """int32 elements of `scratch` that mzs_replay_plan_steps needs for `num_envs` environments (include/mzsearch.h)."""
+    return int(num_envs) + (int(num_envs) + 255) // 256
+
+
 class MzsEnvCartPole(C.Structure):
     _fields_ = ([("struct_size", C.c_int32), ("device", C.c_int32), ("num_envs", C.c_int32),
                  ("max_episode_steps", C.c_int32), ("key", C.c_uint32 * 2)]
@@ -215,7 +226,7 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_replay_store", "mzs_replay_refresh", "mzs_replay_sample",
                     "mzs_replay_gather_obs", "mzs_replay_reanalyse", "mzs_replay_update_priorities",
                     "mzs_mlp_unroll_values", "mzs_replay_sample_is", "mzs_mlp_loss_grad_weighted",
-                    "mzs_replay_stage", "mzs_replay_store_steps",
+                    "mzs_replay_stage", "mzs_replay_store_steps", "mzs_replay_plan_steps",
                     "mzs_env_cartpole_reset", "mzs_env_cartpole_step"]
 
 _lib = None
@@ -294,6 +305,7 @@ def load(build_if_missing: bool = True):
     L.mzs_replay_stage.argtypes = [C.POINTER(MzsReplayRing), C.POINTER(MzsReplayStageArgs), _vp]
     L.mzs_replay_store_steps.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayRing),
                                          C.POINTER(MzsReplayStoreStepsArgs), _vp]
+    L.mzs_replay_plan_steps.argtypes = [C.POINTER(MzsReplayRing), C.POINTER(MzsReplayPlanArgs), _vp]
     L.mzs_env_cartpole_reset.argtypes = [C.POINTER(MzsEnvCartPole), _vp, _vp]
     L.mzs_env_cartpole_step.argtypes = [C.POINTER(MzsEnvCartPole), C.POINTER(MzsEnvStepArgs), _vp]
     L.mzs_mlp_unroll_values.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsUnrollArgs), _vp]

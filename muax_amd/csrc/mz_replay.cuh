@@ -125,6 +125,18 @@ struct ReplayStoreStepsArgs {
   const double* gpow;         // [n_step + 1]: gamma ** i
 };
 
+struct ReplayPlanArgs {
+  ReplayRing ring;
+  int row0, T, min_length, max_out;
+  const uint8_t* done;        // [steps, N]
+  int32_t* open_len;          // [N] in/out
+  double* open_ret;           // [N] in/out
+  int32_t* ep;                // out [max_out][4]: environment, first ring row, length, stored
+  double* ret;                // out [max_out]
+  int32_t* counts;            // out [4]: episodes, stored episodes, max open_len afterwards, 0
+  int32_t* scratch;           // [ceil(N / kPlanThreads) + N]: the workgroups' episode counts, then the environments'
+};
+
 // ring row of transition t of an episode that began in row `first` (t < steps: one wrap at the most)
 MZ_DEV int ring_row(int first, int t, int steps) {
   const int row = first + t;
@@ -313,6 +325,113 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_store_steps_kernel(R
     ar.t_len[slot] = T;
     ar.t_w[slot] = p.weight_mode == 1 ? carry / (double)T : carry;
     ar.t_serial[slot] = p.serial[e];
+  }
+}
+
+// The episode plan of a collection call (vector.ring_plan and collect()'s returns, muax_amd/vector.py) on the device.
+// One THREAD per environment walks the call's T ring rows in time order, so a wavefront reads 64 consecutive flag
+// bytes and 64 consecutive doubles of every row.  Two launches on one stream:
+//   replay_plan_count_kernel  every environment's number of episode ends into scratch[blocks + e], every workgroup's
+//                             total into scratch[block]; clears counts
+//   replay_plan_emit_kernel   the exclusive prefix of those counts (the earlier workgroups' totals summed, then a scan
+//                             inside the workgroup) is the environment's first output row; it walks again, with the
+//                             length and the fp64 return `g = g + r` carried in open_len / open_ret, and writes one
+//                             (environment, first ring row, length, stored) row and one return per episode end
+// so the output is dense, environment-major then time, and does not depend on the order in which workgroups run.
+// counts[1] and counts[2] are integer atomics (a sum and a maximum: any order gives the same value); the last workgroup
+// writes counts[0].  Rows at or beyond max_out are counted, not written.
+// Scale: every emit workgroup sums the totals of ALL workgroups in front of it from global memory, blocks^2 / 2 reads
+// in all -- 10 at 1024 environments, 8 M at a million (4096 workgroups), where a third launch that scans the totals
+// once would be the better structure.
+constexpr int kPlanThreads = 256;
+
+MZ_DEV int plan_next_row(int row, int steps) { return row + 1 == steps ? 0 : row + 1; }
+
+// sum (MAX == false) or maximum of x over the workgroup, for every thread; s is kPlanThreads ints of LDS
+template <bool MAX>
+MZ_DEV int plan_reduce(int x, int* s) {
+  const int tid = threadIdx.x;
+  s[tid] = x;
+  __syncthreads();
+  for (int h = kPlanThreads / 2; h > 0; h >>= 1) {
+    if (tid < h) s[tid] = MAX ? (s[tid] > s[tid + h] ? s[tid] : s[tid + h]) : s[tid] + s[tid + h];
+    __syncthreads();
+  }
+  const int out = s[0];
+  __syncthreads();
+  return out;
+}
+
+__global__ void __launch_bounds__(kPlanThreads) replay_plan_count_kernel(ReplayPlanArgs p) {
+  __shared__ int s[kPlanThreads];
+  const size_t N = (size_t)p.ring.N, e = (size_t)blockIdx.x * kPlanThreads + threadIdx.x;
+  int c = 0;
+  if (e < N) {
+    int row = p.row0;
+    for (int t = 0; t < p.T; ++t) {
+      c += p.done[(size_t)row * N + e] != 0;
+      row = plan_next_row(row, p.ring.steps);
+    }
+    p.scratch[gridDim.x + e] = c;
+  }
+  const int total = plan_reduce<false>(c, s);
+  if (threadIdx.x == 0) {
+    p.scratch[blockIdx.x] = total;
+    if (blockIdx.x == 0) p.counts[0] = p.counts[1] = p.counts[2] = p.counts[3] = 0;
+  }
+}
+
+__global__ void __launch_bounds__(kPlanThreads) replay_plan_emit_kernel(ReplayPlanArgs p) {
+  __shared__ int s[kPlanThreads];
+  const int tid = threadIdx.x, S = p.ring.steps;
+  const size_t N = (size_t)p.ring.N, e = (size_t)blockIdx.x * kPlanThreads + tid;
+  int mine = 0;
+  for (unsigned b = tid; b < blockIdx.x; b += kPlanThreads) mine += p.scratch[b];
+  const int before = plan_reduce<false>(mine, s);  // episodes of the workgroups in front of this one
+  const int c = e < N ? p.scratch[gridDim.x + e] : 0;
+  s[tid] = c;
+  __syncthreads();
+  for (int d = 1; d < kPlanThreads; d <<= 1) {  // inclusive scan of the workgroup's counts
+    const int left = tid >= d ? s[tid - d] : 0;
+    __syncthreads();
+    s[tid] += left;
+    __syncthreads();
+  }
+  int at = before + s[tid] - c;
+  const int through = before + s[kPlanThreads - 1];
+  __syncthreads();
+  int stored = 0, len = 0;
+  if (e < N) {
+    len = p.open_len[e];
+    double g = p.open_ret[e];
+    int first = ((p.row0 - len % S) + S) % S, row = p.row0;
+    for (int t = 0; t < p.T; ++t) {
+      const size_t i = (size_t)row * N + e;
+      len += 1;
+      g = g + p.ring.r[i];
+      row = plan_next_row(row, S);
+      if (p.done[i] != 0) {
+        const int keep = len >= p.min_length ? 1 : 0;
+        if (at < p.max_out) {
+          int32_t* o = p.ep + 4 * (size_t)at;
+          o[0] = (int32_t)e; o[1] = first; o[2] = len; o[3] = keep;
+          p.ret[at] = g;
+        }
+        stored += keep;
+        ++at;
+        first = row;
+        len = 0;
+        g = 0.0;
+      }
+    }
+    p.open_len[e] = len;
+    p.open_ret[e] = g;
+  }
+  const int kept = plan_reduce<false>(stored, s), longest = plan_reduce<true>(len, s);
+  if (tid == 0) {
+    if (kept) atomicAdd(&p.counts[1], kept);
+    if (longest > 0) atomicMax(&p.counts[2], longest);
+    if (blockIdx.x == gridDim.x - 1) p.counts[0] = through;
   }
 }
 

@@ -1,6 +1,7 @@
 // mz_replay.hip -- translation unit of the device-resident trajectory replay (mz_replay.cuh): argument checks and
 // launches of mzs_replay_store / mzs_replay_refresh / mzs_replay_sample / mzs_replay_sample_is / mzs_replay_gather_obs /
-// mzs_replay_reanalyse / mzs_replay_update_priorities / mzs_replay_stage / mzs_replay_store_steps.
+// mzs_replay_reanalyse / mzs_replay_update_priorities / mzs_replay_stage / mzs_replay_store_steps /
+// mzs_replay_plan_steps.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -306,6 +307,36 @@ int mzs_replay_store_steps(const mzs_replay_arena* arena, const mzs_replay_ring*
   p.desc = a->desc; p.serial = (const long long*)a->serial; p.gpow = a->gpow;
   hipLaunchKernelGGL(mz::replay_store_steps_kernel, dim3(waves_grid(a->episodes)), dim3(64 * mz::kReplayWaves), 0,
                      static_cast<hipStream_t>(stream_), p);
+  MZS_HIP(nullptr, hipGetLastError());
+  return MZS_OK;
+}
+
+int mzs_replay_plan_steps(const mzs_replay_ring* ring, const mzs_replay_plan_args* a, void* stream_) {
+  mz::ReplayPlanArgs p{};
+  if (int rc = check_ring(ring, "mzs_replay_plan_steps", &p.ring)) return rc;
+  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_plan_args))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_plan_steps: null arguments or size mismatch (ABI)");
+  if (a->row0 < 0 || a->row0 >= ring->ring_steps)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_plan_steps: row0 must be in 0..ring_steps - 1");
+  if (a->steps < 1 || a->steps > ring->ring_steps)
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_plan_steps: steps must be in 1..ring_steps");
+  if ((int64_t)ring->num_envs * a->steps >= ((int64_t)1 << 31))
+    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_plan_steps: num_envs * steps must be below 2^31");
+  if (a->min_length < 1) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_plan_steps: min_length must be >= 1");
+  if (a->max_out < 1) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_plan_steps: max_out must be >= 1");
+  const void* ptrs[] = {a->done, a->open_len, a->open_ret, a->ep, a->ret, a->counts, a->scratch};
+  const char* names[] = {"done", "open_len", "open_ret", "ep", "ret", "counts", "scratch"};
+  for (int i = 0; i < 7; ++i)
+    if (!ptrs[i]) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_plan_steps: null %s", names[i]);
+  MZS_HIP(nullptr, hipSetDevice(ring->device));
+  p.row0 = a->row0; p.T = a->steps; p.min_length = a->min_length; p.max_out = a->max_out;
+  p.done = a->done; p.open_len = a->open_len; p.open_ret = a->open_ret; p.ep = a->ep; p.ret = a->ret;
+  p.counts = a->counts; p.scratch = a->scratch;
+  const unsigned blocks = (unsigned)(((int64_t)ring->num_envs + mz::kPlanThreads - 1) / mz::kPlanThreads);
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(mz::replay_plan_count_kernel, dim3(blocks), dim3(mz::kPlanThreads), 0, stream, p);
+  MZS_HIP(nullptr, hipGetLastError());
+  hipLaunchKernelGGL(mz::replay_plan_emit_kernel, dim3(blocks), dim3(mz::kPlanThreads), 0, stream, p);
   MZS_HIP(nullptr, hipGetLastError());
   return MZS_OK;
 }

@@ -171,10 +171,18 @@ class DeviceVectorCollector:
     step's rewards straight into the ring's `r` row and its `done` flags into the same row of a uint8
     [ring_steps, N] tensor, nothing inside the step loop copies to the host or synchronises, and per `collect()` the
     call's `r` and `done` rows come down once (at most two copies each) for `ring_plan` and the returns; there is no
-    reward upload.  A host `venv` takes the path it always took."""
+    reward upload.  A host `venv` takes the path it always took.
+    `device_plan=True` (a `venv` with `step_device`; any other is a ValueError) also cuts the episodes and sums their
+    returns on the device (`mzs_replay_plan_steps`, two launches after the step loop): the [T, N] rewards and flags stay
+    where they are, no per-environment state is kept on the host, and per `collect()` three small copies come down --
+    the counts (the call's first synchronisation), then one (environment, first ring row, length, stored) row and one
+    return per finished episode.  The episodes, their order, their serials and what the buffer stores are the default
+    route's.  An episode's return on this route is the SEQUENTIAL fp64 sum of its rewards in time order, not
+    `np.sum`'s pairwise sum; for rewards that are small integers (every environment of the project) the two are equal
+    bit for bit, for other rewards they may differ in the last bits."""
 
     def __init__(self, venv, buffer, n: int, gamma: float, alpha=0.5, weight: str = "mean", min_length: int = 1,
-                 ring_steps=None):
+                 ring_steps=None, device_plan: bool = False):
         if not hasattr(buffer, "add_steps"):
             raise ValueError(f"DeviceVectorCollector needs a buffer with the device store (DeviceReplayBuffer); "
                              f"{type(buffer).__name__} has none")
@@ -184,6 +192,12 @@ class DeviceVectorCollector:
             raise ValueError("n must be at least 1")
         if ring_steps is not None and int(ring_steps) < 1:
             raise ValueError("ring_steps must be positive")
+        if device_plan and not hasattr(venv, "step_device"):
+            raise ValueError(f"DeviceVectorCollector: device_plan needs a device environment (one with step_device, "
+                             f"e.g. DeviceCartPole): the plan kernel reads the rewards and flags the environment wrote "
+                             f"on the device; {type(venv).__name__} has no step_device")
+        if device_plan and int(min_length) < 1:
+            raise ValueError("DeviceVectorCollector: device_plan needs min_length >= 1")
         self.venv, self.buffer, self.n, self.gamma, self.alpha = venv, buffer, int(n), float(gamma), alpha
         self.weight, self.min_length = weight, int(min_length)
         self.ring_steps = None if ring_steps is None else int(ring_steps)
@@ -191,6 +205,9 @@ class DeviceVectorCollector:
         self._step0 = 0          # absolute index of the next step
         self._open_start = None  # [N] absolute first step of every open episode
         self._open_r = None      # per environment: the host rewards of its open episode so far
+        self.device_plan = bool(device_plan)
+        self._plan = None        # device_plan: the plan kernel's device tensors, allocated once
+        self._plan_held = 0      # device_plan: the longest open episode after the previous call (counts[2])
 
     def _alloc(self, N, obs_dim, A):
         import ctypes as C
@@ -230,13 +247,14 @@ class DeviceVectorCollector:
         _lib.check(self.buffer._L.mzs_replay_stage(C.byref(self._ring), C.byref(s), self.buffer._stream()))
         return a32
 
-    def _steps_device_env(self, model, key, steps, num_simulations, temperature, act_kwargs):
+    def _steps_device_env(self, model, key, steps, num_simulations, temperature, act_kwargs, download=True):
         """The step loop for a device environment (muax_amd/envs.py): the observations never leave the device, the
         environment writes every step's rewards into the ring's `r` row and its flags into the same row of
         `self._done_rows` (uint8 [ring_steps, N], beside the ring fields), and nothing in the loop copies to the host
         or synchronises; all launches go on the one stream the staging launch uses, which orders the environment's
         overwrite of its observation tensor after the staging launch that read it.  Afterwards the call's rows of `r`
-        and of the flags come down, in at most two copies each.  Returns (key, R [T, N] float64, D [T, N] bool)."""
+        and of the flags come down, in at most two copies each.  Returns (key, R [T, N] float64, D [T, N] bool);
+        with `download=False` (the device plan) nothing comes down and R, D are None."""
         import torch
         venv, S = self.venv, self.ring_steps
         N = int(venv.n)
@@ -245,7 +263,8 @@ class DeviceVectorCollector:
             if dev is not None and dev.index is not None and torch.device(venv.device) != dev:
                 raise ValueError(f"collect: the environment is on {venv.device}, the buffer on {dev}")
             self._obs = venv.reset_device()
-            self._open_start, self._open_r = np.zeros(N, np.int64), [[] for _ in range(N)]
+            if download:
+                self._open_start, self._open_r = np.zeros(N, np.int64), [[] for _ in range(N)]
         obs_d = self._obs
         for i in range(steps):
             key, subkey = prng.split(key)
@@ -258,6 +277,8 @@ class DeviceVectorCollector:
             row = (self._step0 + i) % S
             obs_d = venv.step_device(a32, self._fields["r"][row], self._done_rows[row])
         self._obs = obs_d
+        if not download:
+            return key, None, None
         row0 = self._step0 % S
         k = min(steps, S - row0)
         parts = [(row0, row0 + k)] + ([(0, steps - k)] if k < steps else [])
@@ -265,10 +286,56 @@ class DeviceVectorCollector:
         D = np.concatenate([self._done_rows[lo:hi].cpu().numpy() for lo, hi in parts]).astype(bool)
         return key, R, D
 
+    def _collect_device_plan(self, model, key, steps, num_simulations, temperature, act_kwargs):
+        """collect() with the plan on the device: the step loop without its download, `mzs_replay_plan_steps` on the
+        call's rows, then the counts (the first synchronisation) and the episode rows come down."""
+        import ctypes as C
+
+        import torch
+
+        from . import _lib
+        if int(self.venv.n) * steps >= 2 ** 31:
+            raise ValueError("collect: device_plan needs num_envs * steps below 2^31")
+        key, _, _ = self._steps_device_env(model, key, steps, num_simulations, temperature, act_kwargs, download=False)
+        N, S = int(self._ring.num_envs), self.ring_steps
+        dev = self._fields["r"].device
+        if self._plan is None:
+            self._plan = {"open_len": torch.zeros(N, dtype=torch.int32, device=dev),
+                          "open_ret": torch.zeros(N, dtype=torch.float64, device=dev),
+                          "counts": torch.zeros(4, dtype=torch.int32, device=dev),
+                          "scratch": torch.zeros(_lib.replay_plan_scratch(N), dtype=torch.int32, device=dev)}
+        pl = self._plan
+        if "ep" not in pl or pl["ep"].shape[0] < N * steps:  # N * steps episodes at the most; grows with `steps`
+            pl["ep"] = torch.zeros((N * steps, 4), dtype=torch.int32, device=dev)
+            pl["ret"] = torch.zeros(N * steps, dtype=torch.float64, device=dev)
+        max_out = int(pl["ep"].shape[0])
+        a = _lib.MzsReplayPlanArgs()
+        a.struct_size = C.sizeof(_lib.MzsReplayPlanArgs)
+        a.row0, a.steps, a.min_length, a.max_out = self._step0 % S, steps, self.min_length, max_out
+        a.done = self._done_rows.data_ptr()
+        for k, x in pl.items():
+            setattr(a, k, x.data_ptr())
+        _lib.check(self.buffer._L.mzs_replay_plan_steps(C.byref(self._ring), C.byref(a), self.buffer._stream()))
+        counts = pl["counts"].cpu().numpy()
+        episodes = int(counts[0])
+        if episodes > max_out:
+            raise RuntimeError(f"collect: the plan reports {episodes} episodes, more than its {max_out} output rows")
+        rows = pl["ep"][:episodes].cpu().numpy().tolist() if episodes else []
+        G = pl["ret"][:episodes].cpu().numpy().tolist() if episodes else []
+        # (as on the default route the collector's state moves on before add_steps: the launch has already advanced
+        # open_len / open_ret, so if add_steps raises -- an episode longer than the buffer's max_steps -- the call's
+        # episodes are lost, not collected twice)
+        self._plan_held, self._step0 = int(counts[2]), self._step0 + steps
+        serials = iter(self.buffer.add_steps(self._ring, [(env, first, T) for env, first, T, kept in rows if kept],
+                                             self.n, self.gamma, self.alpha, weight=self.weight))
+        out = [(T, g, next(serials) if kept else None) for (_, _, T, kept), g in zip(rows, G)]
+        return out, key, steps * N
+
     def collect(self, model, key, steps: int, num_simulations: int = 50, temperature: float = 1.0, **act_kwargs):
         """`steps` lock-step environment steps.  Returns (finished, advanced key, env steps): `finished` lists, in
         `VectorCollector.collect`'s order, (length, undiscounted return, serial) of every episode that ended, the
-        return summed from the host's rewards and the serial None for one dropped as shorter than `min_length`.
+        return summed from the host's rewards (with `device_plan`: summed on the device, sequentially in time order)
+        and the serial None for one dropped as shorter than `min_length`.
         ValueError before the first step when an open episode could outgrow the ring (its steps so far plus `steps`
         exceed `ring_steps`): nothing is overwritten and a call with fewer steps still works."""
         import torch
@@ -278,10 +345,15 @@ class DeviceVectorCollector:
         if self.ring_steps is None:
             self.ring_steps = int(self.venv.spec.max_episode_steps) + steps
         S = self.ring_steps
-        held = 0 if self._open_start is None else self._step0 - int(self._open_start.min())
+        if self.device_plan:
+            held = self._plan_held
+        else:
+            held = 0 if self._open_start is None else self._step0 - int(self._open_start.min())
         if held + steps > S:
             raise ValueError(f"collect: an open episode of {held} steps plus {steps} more does not fit the ring of "
                              f"{S} steps (ring_steps)")
+        if self.device_plan:
+            return self._collect_device_plan(model, key, steps, num_simulations, temperature, act_kwargs)
         step0, row0 = self._step0, self._step0 % S
         k = min(steps, S - row0)  # the call's rows wrap past the ring's end when k < steps
         if hasattr(self.venv, "step_device"):
@@ -385,7 +457,7 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                max_training_steps: int = 10000, test_interval: int = 10, num_test_episodes: int = 10,
                random_seed: int = 42, temperature_fn=None, metrics=None, trajectory_weight: str = "mean",
                reanalyse_every: int = 0, reanalyse_episodes=None, priority_update: bool = False,
-               priority_steps=None, is_beta=None, device_collect: bool = False):
+               priority_steps=None, is_beta=None, device_collect: bool = False, device_plan: bool = False):
     """The reference's fit() loop (muax/train.py:175-241: temperature schedule, buffer sampling, update,
     greedy test) with the acting half on a vector environment: per iteration `steps_per_iteration`
     batched act() calls -> finished episodes -> buffer, then `num_update_per_iteration` updates.
@@ -417,11 +489,19 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     result are unchanged.
     A `venv` with `step_device` (a device environment, muax_amd/envs.py) is stepped on the device by that collector;
     it needs `device_collect=True` and a buffer with the device store, and is a ValueError otherwise: stepping it
-    through host copies would hide the cost it exists to avoid.  `test_env` stays a host-protocol environment."""
+    through host copies would hide the cost it exists to avoid.  `test_env` stays a host-protocol environment.
+    `device_plan=True` (needs `device_collect=True` and a device environment; a ValueError otherwise) hands the flag to
+    that collector: the episodes are cut and their returns summed on the device (`DeviceVectorCollector`), `G` of the
+    metrics row is then the mean of sequential fp64 sums -- equal to the host's for integer rewards.  False: the key
+    stream and every result are unchanged."""
     if priority_steps is not None and int(priority_steps) < 1:
         raise ValueError("priority_steps must be None or >= 1")
     if trajectory_weight not in ("mean", "sum"):
         raise ValueError("trajectory_weight must be 'mean' or 'sum'")
+    if device_plan and not (device_collect and hasattr(venv, "step_device")):
+        raise ValueError(f"fit_vector: device_plan needs device_collect=True and a device environment (one with "
+                         f"step_device); device_collect is {bool(device_collect)} and {type(venv).__name__} has "
+                         f"{'a' if hasattr(venv, 'step_device') else 'no'} step_device")
     from .replay_buffer import TrajectoryReplayBuffer
     from .train import _temperature_fn, test
     temperature_fn = temperature_fn or _temperature_fn
@@ -446,7 +526,7 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
             raise ValueError(f"fit_vector: device_collect needs a buffer with the device store (DeviceReplayBuffer); "
                              f"{type(buffer).__name__} has none")
         collector = DeviceVectorCollector(venv, buffer, n_step, gamma, alpha, weight=trajectory_weight,
-                                          min_length=k_steps)
+                                          min_length=k_steps, device_plan=device_plan)
     else:
         collector = VectorCollector(venv, n_step, gamma, alpha)
     prioritise = bool(priority_update) and hasattr(buffer, "update_priorities")

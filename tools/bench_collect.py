@@ -14,7 +14,11 @@ trio and 50 simulations per step:
   act()   STEPS x act() alone on a fixed device tensor with device outputs, one synchronise at the end: the search
           launches every route pays.
 
-    python tools/bench_collect.py [--iters 20] [--shape ENVS,STEPS ...] [--simulations 50] [--device-env]
+  with --device-plan, one more column and one more split line:
+  dev plan the same collector with `device_plan=True`: the episodes are cut and their returns summed on the device
+          (`mzs_replay_plan_steps`); per collect the counts and one row per finished episode come down.
+
+    python tools/bench_collect.py [--iters 20] [--shape ENVS,STEPS ...] [--simulations 50] [--device-env] [--device-plan]
 
 Every figure is the median of `--iters` repetitions of one whole collect (+ add), each ending in a device synchronise,
 after three untimed ones.  The two routes alternate shape by shape in one process; each keeps its own environment,
@@ -59,11 +63,14 @@ def median_ms(fn, iters, warm=3):
     return float(np.median(out))
 
 
-def split_ms(collector, fn, iters):
+def split_ms(collector, fn, iters, plan=False):
     """Where one collect() of the device-environment route spends its time: the step loop up to and including the
     download of the call's rewards and flags (which waits for the device), `add_steps` (upload, store launch, then a
-    synchronise added here) and the rest (ring_plan, the returns and the bookkeeping, on the host).  Medians, ms."""
-    spent = {"loop": [], "add_steps": []}
+    synchronise added here) and the rest (ring_plan, the returns and the bookkeeping, on the host).  Medians, ms.
+    `plan` (a collector with device_plan): the step loop downloads nothing and does not wait; the plan launches and the
+    downloads of the counts and the episode rows (which wait for the device) are timed as a fourth part, and the rest
+    is the two list comprehensions that build the episode list.  Returns (total, loop, add_steps[, plan])."""
+    spent = {"loop": [], "add_steps": [], "plan": []}
 
     def timed(obj, name, key, sync):
         inner = getattr(obj, name)
@@ -79,17 +86,43 @@ def split_ms(collector, fn, iters):
         return lambda: setattr(obj, name, inner)
 
     undo = [timed(collector, "_steps_device_env", "loop", False), timed(collector.buffer, "add_steps", "add_steps", True)]
+    if plan:  # from the plan call to the end of the collector's downloads: counts, then (if any episode ended) ep, ret
+        L, cpu = collector.buffer._L, torch.Tensor.cpu
+        inner_plan, mark = L.mzs_replay_plan_steps, {}
+
+        def plan_call(*args):
+            mark["t0"], mark["left"] = time.perf_counter(), 1  # (the counts come first and say whether more follows)
+            return inner_plan(*args)
+
+        def plan_cpu(t, *args, **kw):
+            out = cpu(t, *args, **kw)
+            if mark.get("left"):
+                if t is collector._plan["counts"]:
+                    mark["left"] = 3 if int(out[0]) else 1
+                mark["left"] -= 1
+                spent["plan"][-1] = (time.perf_counter() - mark["t0"]) * 1e3  # a later .cpu() of the call is not counted
+            return out
+
+        def restore():
+            L.mzs_replay_plan_steps = inner_plan
+            del torch.Tensor.cpu  # (the wrapper sat in Tensor's own dict, in front of the base class's method)
+        L.mzs_replay_plan_steps, torch.Tensor.cpu = plan_call, plan_cpu
+        undo.append(restore)
     total = []
     for _ in range(iters):
         for v in spent.values():
             v.append(0.0)
         t0 = time.perf_counter()
+        if plan:
+            mark.clear()
         fn()
         torch.cuda.synchronize()
         total.append((time.perf_counter() - t0) * 1e3)
     for u in undo:
         u()
     loop, add = float(np.median(spent["loop"])), float(np.median(spent["add_steps"]))
+    if plan:
+        return float(np.median(total)), loop, add, float(np.median(spent["plan"]))
     return float(np.median(total)), loop, add
 
 
@@ -99,13 +132,16 @@ def main():
     ap.add_argument("--simulations", type=int, default=50)
     ap.add_argument("--shape", action="append", default=[], metavar="ENVS,STEPS")
     ap.add_argument("--device-env", action="store_true", help="also time collection on DeviceCartPole and act() alone")
+    ap.add_argument("--device-plan", action="store_true",
+                    help="also time collection on DeviceCartPole with the episodes cut on the device (device_plan=True)")
     a = ap.parse_args()
     shapes = [tuple(int(x) for x in s.split(",")) for s in a.shape] or [(64, 64), (1024, 64)]
     warm_runtime()
     print(f"vector CartPole, {a.simulations} simulations, n_step {N_STEP}, episodes of at least {K} steps stored; "
           f"median of {a.iters} synchronised repetitions, ms")
     print(f"{'envs x steps':>12} | {'host collect':>12} {'host collect+add_many':>21} | {'device collect (incl. add)':>26} | "
-          f"{'host / device':>13}" + (f" | {'dev env collect (incl. add)':>27} {'steps x act()':>13}" if a.device_env else ""))
+          f"{'host / device':>13}" + (f" | {'dev env collect (incl. add)':>27} {'steps x act()':>13}" if a.device_env else "")
+          + (f" | {'dev plan collect (incl. add)':>28}" if a.device_plan else ""))
     for envs, steps in shapes:
         m = model()
         state = {"hk": mx.prng.PRNGKey(0), "dk": mx.prng.PRNGKey(0)}
@@ -146,11 +182,25 @@ def main():
                           num_simulations=a.simulations)
 
             line += f" | {median_ms(env_route, a.iters):27.3f} {median_ms(act_alone, a.iters):13.3f}"
+        if a.device_plan:
+            plan_buf = mx.DeviceReplayBuffer(cap, rows)
+            plan_dev = mx.DeviceVectorCollector(mx.DeviceCartPole(envs, seed=0), plan_buf, N_STEP, GAMMA, ALPHA,
+                                                min_length=K, device_plan=True)
+            state["pk"] = mx.prng.PRNGKey(0)
+
+            def plan_route():
+                _, state["pk"], _ = plan_dev.collect(m, state["pk"], steps, a.simulations)
+
+            line += f" | {median_ms(plan_route, a.iters):28.3f}"
         print(line, flush=True)
         if a.device_env:
             total, loop, add = split_ms(env_dev, env_route, a.iters)
             print(f"{'':>12}   dev env collect, split: {total:.3f} = step loop and download {loop:.3f} + add_steps "
                   f"{add:.3f} + host tail {total - loop - add:.3f}", flush=True)
+        if a.device_plan:
+            total, loop, add, plan = split_ms(plan_dev, plan_route, a.iters, plan=True)
+            print(f"{'':>12}   dev plan collect, split: {total:.3f} = step loop {loop:.3f} + plan and download {plan:.3f} "
+                  f"+ add_steps {add:.3f} + host tail {total - loop - plan - add:.3f}", flush=True)
 
 
 if __name__ == "__main__":
