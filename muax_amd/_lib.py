@@ -211,6 +211,15 @@ class MzsUnrollArgs(C.Structure):
                 + [(n, _vp) for n in ("obs", "actions", "returns", "values", "prio")])
 
 
+def args(cls, **fields):
+    """A `cls` argument struct with `struct_size` set and the given fields assigned (a tuple fills an array field)."""
+    a = cls()
+    a.struct_size = C.sizeof(cls)
+    for name, value in fields.items():
+        setattr(a, name, value)
+    return a
+
+
 EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_destroy",
                     "mzs_mlp_set_weights", "mzs_act_mlp", "mzs_root", "mzs_root_gumbel", "mzs_select",
                     "mzs_expand_backup", "mzs_expand_backup_select",

@@ -24,8 +24,12 @@
 // ring_steps x num_envs rows, so an episode's transitions lie num_envs rows apart and may wrap at the ring's end):
 //   replay_stage_kernel        one step's obs, a, v, pi of every environment into one ring row (rewards come later)
 //   replay_store_steps_kernel  the raw store reading that strided source: one wavefront per finished episode, the
-//                              same copies, nstep_transition, seq_scan and table row, so the same bits as the dense
-//                              store.  The strided reads have NOT been measured against the dense ones.
+//                              same transition pass (raw_store_pass, instantiated for pointers and for RingColumn)
+//                              and table row, so the same bits as the dense store.  The strided reads have NOT been
+//                              measured against the dense ones.
+// Every kernel that has one wavefront per episode or batch row opens with wave_item.  The four that write an episode's
+// weights (store, store_steps, reanalyse, prio_apply) run ONE loop, episode_weight_pass, each with its own
+// per-transition body, and take the table weight from table_weight.
 // Every prefix sum is the SEQUENTIAL fp64 sum (np.cumsum's order), one addition per element on a wave-uniform carry:
 // monotone, so the searches are well defined, and equal to the host's bit for bit.
 #pragma once
@@ -152,6 +156,11 @@ struct RingColumn {
   MZ_DEV T operator[](int t) const { return col[(size_t)ring_row(first, t, steps) * N]; }
 };
 
+// the wave prologue of the kernels that have one wavefront per episode / batch row: `const int e = wave_item(), lane =
+// wave_lane();` -- the item is wave-uniform; plain ints, so the kernels' lambdas may name them
+MZ_DEV int wave_item() { return __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6)); }
+MZ_DEV int wave_lane() { return threadIdx.x & 63; }
+
 MZ_DEV double lane_bcast(double x, int j) {  // j wave-uniform
   const int lo = __builtin_amdgcn_readlane(__double2loint(x), j);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(x), j);
@@ -185,12 +194,13 @@ MZ_DEV int upper_bound(const double* c, int n, double t) {
   return lo;
 }
 
-// Transition t of an episode of T steps with rewards r[0..T) and values v[0..T) (double, or float widened):
+// Transition t of an episode of T steps with rewards r[0..T) and values v[0..T) (double, or float widened; dense
+// pointers or columns of the collection ring: anything with operator[]):
 // vector.nstep_returns in its operation order -- i ascending (terms past the end are + gamma^i * 0), then the bootstrap --
 // and episode_trajectory's priority weight.  Returns w; Rn and boot (false: `done`) by reference.
 template <typename R, typename V>
-MZ_DEV double nstep_transition_of(R r, V v, int t, int T, int n_step, const double* gpow, int has_alpha, double alpha,
-                                  double& Rn, bool& boot) {
+MZ_DEV double nstep_transition(R r, V v, int t, int T, int n_step, const double* gpow, int has_alpha, double alpha,
+                               double& Rn, bool& boot) {
   Rn = 0.0;
   for (int i = 0; i < n_step; ++i) Rn = Rn + gpow[i] * (t + i < T ? (double)r[t + i] : 0.0);
   boot = t + n_step < T;
@@ -201,22 +211,55 @@ MZ_DEV double nstep_transition_of(R r, V v, int t, int T, int n_step, const doub
   return has_alpha ? (alpha == 1.0 ? d : pow(d, alpha)) : 1.0;
 }
 
-// r, v dense (pointers), or columns of the collection ring: the same statements either way
-template <typename TR, typename TV>
-MZ_DEV double nstep_transition(const TR* r, const TV* v, int t, int T, int n_step, const double* gpow, int has_alpha,
-                               double alpha, double& Rn, bool& boot) {
-  return nstep_transition_of(r, v, t, T, n_step, gpow, has_alpha, alpha, Rn, boot);
+// The weight pass of an episode of T transitions whose arena rows begin at dst, 64 transitions at a time: f(t) is
+// transition t's weight w (f also makes the kernel's own stores for t, w among them), cw its sequential prefix sum.
+// Returns the sum of the episode's weights (wave-uniform).
+template <typename F>
+MZ_DEV double episode_weight_pass(int T, int lane, size_t dst, const ReplayArena& ar, F f) {
+  double carry = 0.0;
+  for (int base = 0; base < T; base += 64) {
+    const int t = base + lane;
+    const bool in = t < T;
+    const double w = in ? f(t) : 0.0;
+    const int valid = T - base < 64 ? T - base : 64;
+    const double c = seq_scan(w, valid, lane, carry);
+    if (in) ar.cw[dst + t] = c;
+  }
+  return carry;
 }
 
-template <typename TR, typename TV>
-MZ_DEV double nstep_transition(RingColumn<TR> r, RingColumn<TV> v, int t, int T, int n_step, const double* gpow,
-                               int has_alpha, double alpha, double& Rn, bool& boot) {
-  return nstep_transition_of(r, v, t, T, n_step, gpow, has_alpha, alpha, Rn, boot);
+// an episode's weight in the table from the sum of its transition weights: the mean (mode 1) or the sum (mode 2)
+MZ_DEV double table_weight(int mode, double sum, int T) { return mode == 1 ? sum / (double)T : sum; }
+
+// The transition pass of a raw store (p: ReplayStoreArgs or ReplayStoreStepsArgs): a, r, v of the episode from the
+// dense stream (pointers at its first transition) or from the ring (RingColumn), Rn / done / w by nstep_transition.
+template <typename P, typename R, typename V, typename Ac>
+MZ_DEV double raw_store_pass(const P& p, R r, V v, Ac a, int T, int lane, size_t dst) {
+  const ReplayArena& ar = p.ar;
+  return episode_weight_pass(T, lane, dst, ar, [&](int t) {
+    ar.a[dst + t] = a[t];
+    double Rn;
+    bool boot;
+    const double w = nstep_transition(r, v, t, T, p.n_step, p.gpow, p.has_alpha, p.alpha, Rn, boot);
+    ar.r[dst + t] = (float)r[t];
+    ar.v[dst + t] = (float)v[t];  // (exact from the ring's float)
+    ar.Rn[dst + t] = (float)Rn;
+    ar.done[dst + t] = boot ? 0 : 1;
+    ar.w[dst + t] = w;
+    return w;
+  });
+}
+
+// lane 0: the episode's row of the table
+MZ_DEV void store_table_row(const ReplayArena& ar, int slot, size_t dst, int T, double w, long long serial) {
+  ar.t_start[slot] = (int32_t)dst;
+  ar.t_len[slot] = T;
+  ar.t_w[slot] = w;
+  ar.t_serial[slot] = serial;
 }
 
 __global__ void __launch_bounds__(64 * kReplayWaves) replay_store_kernel(ReplayStoreArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  const int e = wave_item(), lane = wave_lane();
   if (e >= p.episodes) return;
   const ReplayArena& ar = p.ar;
   const size_t src = (size_t)p.desc[4 * e], dst = (size_t)p.desc[4 * e + 1];
@@ -224,41 +267,23 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_store_kernel(ReplayS
   const size_t no = (size_t)T * ar.obs_dim, np_ = (size_t)T * ar.A;
   for (size_t i = lane; i < no; i += 64) ar.obs[dst * ar.obs_dim + i] = p.obs[src * ar.obs_dim + i];
   for (size_t i = lane; i < np_; i += 64) ar.pi[dst * ar.A + i] = p.pi[src * ar.A + i];
-  double carry = 0.0;
-  for (int base = 0; base < T; base += 64) {
-    const int t = base + lane;
-    const bool in = t < T;
-    double w = 0.0;
-    if (in) {
+  double sum;
+  if (p.raw) {
+    sum = raw_store_pass(p, p.r64 + src, p.v64 + src, p.a + src, T, lane, dst);
+  } else {
+    sum = episode_weight_pass(T, lane, dst, ar, [&](int t) {
       ar.a[dst + t] = p.a[src + t];
-      if (p.raw) {
-        const double* r = p.r64 + src;
-        double Rn;
-        bool boot;
-        w = nstep_transition(r, p.v64 + src, t, T, p.n_step, p.gpow, p.has_alpha, p.alpha, Rn, boot);
-        ar.r[dst + t] = (float)r[t];
-        ar.v[dst + t] = (float)p.v64[src + t];
-        ar.Rn[dst + t] = (float)Rn;
-        ar.done[dst + t] = boot ? 0 : 1;
-      } else {
-        w = p.w[src + t];
-        ar.r[dst + t] = p.r32[src + t];
-        ar.v[dst + t] = p.v32[src + t];
-        ar.Rn[dst + t] = p.Rn[src + t];
-        ar.done[dst + t] = p.done[src + t] ? 1 : 0;
-      }
+      const double w = p.w[src + t];
+      ar.r[dst + t] = p.r32[src + t];
+      ar.v[dst + t] = p.v32[src + t];
+      ar.Rn[dst + t] = p.Rn[src + t];
+      ar.done[dst + t] = p.done[src + t] ? 1 : 0;
       ar.w[dst + t] = w;
-    }
-    const int valid = T - base < 64 ? T - base : 64;
-    const double c = seq_scan(w, valid, lane, carry);
-    if (in) ar.cw[dst + t] = c;
+      return w;
+    });
   }
-  if (lane == 0) {
-    ar.t_start[slot] = (int32_t)dst;
-    ar.t_len[slot] = T;
-    ar.t_w[slot] = p.weight_mode == 0 ? p.ep_w[e] : p.weight_mode == 1 ? carry / (double)T : carry;
-    ar.t_serial[slot] = p.serial[e];
-  }
+  if (lane == 0)
+    store_table_row(ar, slot, dst, T, p.weight_mode == 0 ? p.ep_w[e] : table_weight(p.weight_mode, sum, T), p.serial[e]);
 }
 
 // One step of a vector environment into ring row p.row: four dense copies, consecutive lanes on consecutive elements.
@@ -282,8 +307,7 @@ __global__ void __launch_bounds__(kStageThreads) replay_stage_kernel(ReplayStage
 // steps * obs_dim and steps * A below 2^31, so the element index is an int).  How much these strided reads cost
 // against the dense store's has not been measured.
 __global__ void __launch_bounds__(64 * kReplayWaves) replay_store_steps_kernel(ReplayStoreStepsArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  const int e = wave_item(), lane = wave_lane();
   if (e >= p.episodes) return;
   const ReplayArena& ar = p.ar;
   const ReplayRing& g = p.ring;
@@ -298,34 +322,10 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_store_steps_kernel(R
     const int t = i / A, c = i - t * A;
     ar.pi[dst * A + i] = g.pi[((size_t)ring_row(first, t, g.steps) * N + env) * A + c];
   }
-  const RingColumn<double> r{g.r + env, first, g.steps, g.N};
-  const RingColumn<float> v{g.v + env, first, g.steps, g.N};
-  double carry = 0.0;
-  for (int base = 0; base < T; base += 64) {
-    const int t = base + lane;
-    const bool in = t < T;
-    double w = 0.0;
-    if (in) {
-      ar.a[dst + t] = g.a[(size_t)ring_row(first, t, g.steps) * N + env];
-      double Rn;
-      bool boot;
-      w = nstep_transition(r, v, t, T, p.n_step, p.gpow, p.has_alpha, p.alpha, Rn, boot);
-      ar.r[dst + t] = (float)r[t];
-      ar.v[dst + t] = v[t];  // (the dense store's (float)(double)v: the widening is exact)
-      ar.Rn[dst + t] = (float)Rn;
-      ar.done[dst + t] = boot ? 0 : 1;
-      ar.w[dst + t] = w;
-    }
-    const int valid = T - base < 64 ? T - base : 64;
-    const double c = seq_scan(w, valid, lane, carry);
-    if (in) ar.cw[dst + t] = c;
-  }
-  if (lane == 0) {
-    ar.t_start[slot] = (int32_t)dst;
-    ar.t_len[slot] = T;
-    ar.t_w[slot] = p.weight_mode == 1 ? carry / (double)T : carry;
-    ar.t_serial[slot] = p.serial[e];
-  }
+  const double sum = raw_store_pass(p, RingColumn<double>{g.r + env, first, g.steps, g.N},
+                                    RingColumn<float>{g.v + env, first, g.steps, g.N},
+                                    RingColumn<int32_t>{g.a + env, first, g.steps, g.N}, T, lane, dst);
+  if (lane == 0) store_table_row(ar, slot, dst, T, table_weight(p.weight_mode, sum, T), p.serial[e]);
 }
 
 // The episode plan of a collection call (vector.ring_plan and collect()'s returns, muax_amd/vector.py) on the device.
@@ -436,8 +436,7 @@ __global__ void __launch_bounds__(kPlanThreads) replay_plan_emit_kernel(ReplayPl
 }
 
 __global__ void __launch_bounds__(64 * kReplayWaves) replay_gather_obs_kernel(ReplayGatherArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  const int e = wave_item(), lane = wave_lane();
   const size_t od = (size_t)p.ar.obs_dim;
   if (e < p.episodes) {
     const size_t src = (size_t)p.desc[4 * e], dst = (size_t)p.desc[4 * e + 1];
@@ -452,8 +451,7 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_gather_obs_kernel(Re
 }
 
 __global__ void __launch_bounds__(64 * kReplayWaves) replay_reanalyse_kernel(ReplayReanalyseArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  const int e = wave_item(), lane = wave_lane();
   if (e >= p.episodes) return;
   const ReplayArena& ar = p.ar;
   const size_t src = (size_t)p.desc[4 * e], dst = (size_t)p.desc[4 * e + 1];
@@ -464,25 +462,17 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_reanalyse_kernel(Rep
   // another lane of the wave writes
   const float* r = ar.r + dst;
   const float* v = p.v + src;
-  double carry = 0.0;
-  for (int base = 0; base < T; base += 64) {
-    const int t = base + lane;
-    const bool in = t < T;
-    double w = 0.0;
-    if (in) {
-      double Rn;
-      bool boot;
-      w = nstep_transition(r, v, t, T, p.n_step, p.gpow, p.has_alpha, p.alpha, Rn, boot);
-      ar.v[dst + t] = v[t];
-      ar.Rn[dst + t] = (float)Rn;
-      ar.done[dst + t] = boot ? 0 : 1;
-      ar.w[dst + t] = w;
-    }
-    const int valid = T - base < 64 ? T - base : 64;
-    const double c = seq_scan(w, valid, lane, carry);
-    if (in) ar.cw[dst + t] = c;
-  }
-  if (lane == 0) ar.t_w[slot] = p.weight_mode == 1 ? carry / (double)T : carry;
+  const double sum = episode_weight_pass(T, lane, dst, ar, [&](int t) {
+    double Rn;
+    bool boot;
+    const double w = nstep_transition(r, v, t, T, p.n_step, p.gpow, p.has_alpha, p.alpha, Rn, boot);
+    ar.v[dst + t] = v[t];
+    ar.Rn[dst + t] = (float)Rn;
+    ar.done[dst + t] = boot ? 0 : 1;
+    ar.w[dst + t] = w;
+    return w;
+  });
+  if (lane == 0) ar.t_w[slot] = table_weight(p.weight_mode, sum, T);
 }
 
 __global__ void __launch_bounds__(64) replay_refresh_kernel(ReplayArena ar, int head, int count, int k) {
@@ -511,8 +501,7 @@ __global__ void __launch_bounds__(64) replay_refresh_kernel(ReplayArena ar, int 
 // without one, rounded to q.isw.  The draws, the searches and every copy are the same code with and without IS.
 template <bool IS>
 MZ_DEV void replay_sample_row(const ReplaySampleArgs& p, const ReplayIsArgs& q) {
-  const int lane = threadIdx.x & 63;
-  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  const int row = wave_item(), lane = wave_lane();
   if (row >= p.B) return;
   const ReplayArena& ar = p.ar;
   const int k = p.k, A = ar.A, od = ar.obs_dim;
@@ -613,8 +602,7 @@ MZ_DEV int ring_slot(const ReplayArena& ar, int head, int i) {
 // PRECONDITION of both priority kernels (mzs_replay_refresh's): the live episodes are the `count` table slots from
 // `head` on, wrapping at capacity, and their serials ascend along that ring (the store's running number).
 __global__ void __launch_bounds__(64 * kReplayWaves) replay_prio_mark_kernel(ReplayUpdateArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  const int row = wave_item(), lane = wave_lane();
   if (row >= p.B) return;
   const ReplayArena& ar = p.ar;
   // wave-uniform: the row's serial, the binary search for it along the ring, the episode's place
@@ -644,8 +632,7 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_prio_mark_kernel(Rep
 }
 
 __global__ void __launch_bounds__(64 * kReplayWaves) replay_prio_apply_kernel(ReplayUpdateArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * kReplayWaves + (threadIdx.x >> 6));
+  const int e = wave_item(), lane = wave_lane();
   if (e >= p.count) return;
   const ReplayArena& ar = p.ar;
   const int slot = ring_slot(ar, p.head, e);
@@ -654,30 +641,22 @@ __global__ void __launch_bounds__(64 * kReplayWaves) replay_prio_apply_kernel(Re
   const int T = ar.t_len[slot];
   if (first < 0 || T <= 0 || first + T > ar.max_steps) return;  // (the mark pass flags no such slot)
   const size_t dst = (size_t)first;
-  double carry = 0.0;
-  for (int base = 0; base < T; base += 64) {
-    const int t = base + lane;
-    const bool in = t < T;
-    double w = 0.0;
-    if (in) {
-      w = ar.w[dst + t];
-      const int o = p.owner[dst + t];
-      if (o >= 0) {
-        p.owner[dst + t] = -1;
-        const int i = o < p.B ? t - p.start[o] : -1;
-        if (i >= 0 && i < p.kp) {  // (always, with the scratch as the mark pass left it)
-          const double x = fabs((double)p.prio[(size_t)o * p.kp + i]) + p.eps;
-          w = p.alpha == 1.0 ? x : pow(x, p.alpha);
-          ar.w[dst + t] = w;
-        }
+  const double sum = episode_weight_pass(T, lane, dst, ar, [&](int t) {
+    double w = ar.w[dst + t];
+    const int o = p.owner[dst + t];
+    if (o >= 0) {
+      p.owner[dst + t] = -1;
+      const int i = o < p.B ? t - p.start[o] : -1;
+      if (i >= 0 && i < p.kp) {  // (always, with the scratch as the mark pass left it)
+        const double x = fabs((double)p.prio[(size_t)o * p.kp + i]) + p.eps;
+        w = p.alpha == 1.0 ? x : pow(x, p.alpha);
+        ar.w[dst + t] = w;
       }
     }
-    const int valid = T - base < 64 ? T - base : 64;
-    const double c = seq_scan(w, valid, lane, carry);
-    if (in) ar.cw[dst + t] = c;
-  }
+    return w;
+  });
   if (lane == 0) {
-    ar.t_w[slot] = p.weight_mode == 1 ? carry / (double)T : carry;
+    ar.t_w[slot] = table_weight(p.weight_mode, sum, T);
     p.touched[slot] = 0;
   }
 }

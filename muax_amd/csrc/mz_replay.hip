@@ -11,6 +11,14 @@
 
 namespace {
 
+// an argument struct is there and has the size this library was built for
+template <typename A>
+bool args_ok(const A* a, const char* who) {
+  if (a && a->struct_size == (int32_t)sizeof(A)) return true;
+  mzh::fail(nullptr, MZS_E_INVALID, "%s: null arguments or size mismatch (ABI)", who);
+  return false;
+}
+
 int check_arena(const mzs_replay_arena* ar, const char* who, mz::ReplayArena* out) {
   if (!ar || ar->struct_size != (int32_t)sizeof(mzs_replay_arena))
     return mzh::fail(nullptr, MZS_E_INVALID, "%s: null arena or size mismatch (ABI)", who);
@@ -37,15 +45,18 @@ bool finite_bits(double x) {
   return (u & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
 }
 
-int waves_grid(int n) { return (n + mz::kReplayWaves - 1) / mz::kReplayWaves; }
+// one launch of a kernel that has one wavefront per item, kReplayWaves of them per workgroup
+template <typename... KernelArgs, typename... Args>
+int launch_waves(void (*kernel)(KernelArgs...), int items, void* stream, const Args&... args) {
+  hipLaunchKernelGGL(kernel, dim3((items + mz::kReplayWaves - 1) / mz::kReplayWaves), dim3(64 * mz::kReplayWaves), 0,
+                     static_cast<hipStream_t>(stream), args...);
+  MZS_HIP(nullptr, hipGetLastError());
+  return MZS_OK;
+}
 
-// the episode descriptors of a reanalysis call (host copy): every range inside the stream, the arena and the table
-int check_stream_desc(const mzs_replay_arena* ar, const char* who, int32_t episodes, int64_t stream_rows,
-                      int64_t rows_padded, const int32_t* desc, const int32_t* desc_host) {
-  if (episodes <= 0 || episodes > ar->capacity || stream_rows <= 0 || rows_padded < stream_rows ||
-      rows_padded >= ((int64_t)1 << 31))
-    return mzh::fail(nullptr, MZS_E_INVALID, "%s: episodes must be 1..capacity, 1 <= stream_rows <= rows_padded < 2^31", who);
-  if (!desc || !desc_host) return mzh::fail(nullptr, MZS_E_INVALID, "%s: null descriptor pointer", who);
+// the [episodes][4] descriptors of a dense stream (host copy): every range inside the stream, the arena and the table
+int check_desc_ranges(const mzs_replay_arena* ar, const char* who, int32_t episodes, int64_t stream_rows,
+                      const int32_t* desc_host) {
   for (int e = 0; e < episodes; ++e) {
     const int32_t* d = desc_host + 4 * e;
     const int64_t src = d[0], dst = d[1], len = d[2];
@@ -56,11 +67,33 @@ int check_stream_desc(const mzs_replay_arena* ar, const char* who, int32_t episo
   return MZS_OK;
 }
 
+// the stream and the episode descriptors of a reanalysis call
+int check_stream_desc(const mzs_replay_arena* ar, const char* who, int32_t episodes, int64_t stream_rows,
+                      int64_t rows_padded, const int32_t* desc, const int32_t* desc_host) {
+  if (episodes <= 0 || episodes > ar->capacity || stream_rows <= 0 || rows_padded < stream_rows ||
+      rows_padded >= ((int64_t)1 << 31))
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: episodes must be 1..capacity, 1 <= stream_rows <= rows_padded < 2^31", who);
+  if (!desc || !desc_host) return mzh::fail(nullptr, MZS_E_INVALID, "%s: null descriptor pointer", who);
+  return check_desc_ranges(ar, who, episodes, stream_rows, desc_host);
+}
+
+// what nstep_transition needs (raw store, store from the ring, reanalysis) ...
+int check_nstep(int32_t n_step, const double* gpow, const char* who) {
+  if (n_step < 1 || !gpow) return mzh::fail(nullptr, MZS_E_INVALID, "%s: needs n_step >= 1 and gpow", who);
+  return MZS_OK;
+}
+
+// ... and the table weight of an episode whose transition weights the device computes
+int check_weight_mode(int32_t weight_mode, const char* who) {
+  if (weight_mode != 1 && weight_mode != 2)
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: weight_mode must be 1 (mean) or 2 (sum)", who);
+  return MZS_OK;
+}
+
 // the checks and the kernel arguments both sample entries share (the device is selected by the caller afterwards)
 int check_sample(const mzs_replay_arena* arena, const mzs_replay_sample_args* a, const char* who, mz::ReplaySampleArgs* p) {
   if (int rc = check_arena(arena, who, &p->ar)) return rc;
-  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_sample_args))
-    return mzh::fail(nullptr, MZS_E_INVALID, "%s: null arguments or size mismatch (ABI)", who);
+  if (!args_ok(a, who)) return MZS_E_INVALID;
   if (a->count <= 0 || a->count > arena->capacity || a->batch <= 0 || a->k_steps <= 0 || a->sample_per_trajectory <= 0)
     return mzh::fail(nullptr, MZS_E_INVALID, "%s: count in 1..capacity; batch, k_steps, sample_per_trajectory >= 1", who);
   if ((int64_t)a->k_steps * arena->num_actions >= ((int64_t)1 << 31) || a->k_steps >= arena->max_steps)
@@ -74,13 +107,15 @@ int check_sample(const mzs_replay_arena* arena, const mzs_replay_sample_args* a,
   return MZS_OK;
 }
 
+// the wider of a ring row's two vector fields, in floats
+int64_t ring_widest(const mzs_replay_ring* g) { return g->obs_dim > g->num_actions ? g->obs_dim : g->num_actions; }
+
 int check_ring(const mzs_replay_ring* g, const char* who, mz::ReplayRing* out) {
   if (!g || g->struct_size != (int32_t)sizeof(mzs_replay_ring))
     return mzh::fail(nullptr, MZS_E_INVALID, "%s: null ring or size mismatch (ABI)", who);
   if (g->ring_steps <= 0 || g->num_envs <= 0 || g->obs_dim <= 0 || g->num_actions <= 0)
     return mzh::fail(nullptr, MZS_E_INVALID, "%s: ring_steps, num_envs, obs_dim and num_actions must be positive", who);
-  const int64_t widest = g->obs_dim > g->num_actions ? g->obs_dim : g->num_actions;
-  if ((int64_t)g->ring_steps * widest >= ((int64_t)1 << 31))
+  if (g->ring_steps * ring_widest(g) >= ((int64_t)1 << 31))
     return mzh::fail(nullptr, MZS_E_INVALID, "%s: ring_steps * max(obs_dim, num_actions) must be below 2^31", who);
   if (!g->obs || !g->a || !g->r || !g->v || !g->pi) return mzh::fail(nullptr, MZS_E_INVALID, "%s: null ring pointer", who);
   if (int rc = mzh::check_device(g->device, who)) return rc;
@@ -96,8 +131,7 @@ extern "C" {
 int mzs_replay_store(const mzs_replay_arena* arena, const mzs_replay_store_args* a, void* stream_) {
   mz::ReplayStoreArgs p{};
   if (int rc = check_arena(arena, "mzs_replay_store", &p.ar)) return rc;
-  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_store_args))
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: null arguments or size mismatch (ABI)");
+  if (!args_ok(a, "mzs_replay_store")) return MZS_E_INVALID;
   if (a->episodes <= 0 || a->episodes > arena->capacity || a->stream_steps <= 0 || a->stream_steps >= ((int64_t)1 << 31))
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: episodes must be 1..capacity, stream_steps 1..2^31 - 1");
   if (!a->desc_host || !a->desc || !a->serial || !a->obs || !a->a || !a->pi || !a->r || !a->v)
@@ -105,17 +139,11 @@ int mzs_replay_store(const mzs_replay_arena* arena, const mzs_replay_store_args*
   if (a->weight_mode < 0 || a->weight_mode > 2 || (a->weight_mode == 0 && !a->ep_w))
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: weight_mode must be 0 (with ep_w), 1 or 2");
   if (a->raw) {
-    if (a->n_step <= 0 || !a->gpow) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: raw needs n_step >= 1 and gpow");
+    if (int rc = check_nstep(a->n_step, a->gpow, "mzs_replay_store")) return rc;
   } else if (!a->Rn || !a->done || !a->w || a->weight_mode != 0) {
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: without raw, Rn, done, w and ep_w must be given");
   }
-  for (int e = 0; e < a->episodes; ++e) {
-    const int32_t* d = a->desc_host + 4 * e;
-    const int64_t src = d[0], dst = d[1], len = d[2];
-    if (len <= 0 || src < 0 || src + len > a->stream_steps || dst < 0 || dst + len > arena->max_steps || d[3] < 0 ||
-        d[3] >= arena->capacity)
-      return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store: an episode's range leaves the stream, the arena or the table");
-  }
+  if (int rc = check_desc_ranges(arena, "mzs_replay_store", a->episodes, a->stream_steps, a->desc_host)) return rc;
   MZS_HIP(nullptr, hipSetDevice(arena->device));
   p.episodes = a->episodes; p.raw = a->raw ? 1 : 0; p.n_step = a->n_step; p.weight_mode = a->weight_mode;
   p.has_alpha = a->has_alpha ? 1 : 0; p.alpha = a->alpha;
@@ -124,10 +152,7 @@ int mzs_replay_store(const mzs_replay_arena* arena, const mzs_replay_store_args*
   if (a->raw) { p.r64 = static_cast<const double*>(a->r); p.v64 = static_cast<const double*>(a->v); }
   else { p.r32 = static_cast<const float*>(a->r); p.v32 = static_cast<const float*>(a->v); }
   p.Rn = a->Rn; p.done = a->done; p.w = a->w;
-  hipLaunchKernelGGL(mz::replay_store_kernel, dim3(waves_grid(a->episodes)), dim3(64 * mz::kReplayWaves), 0,
-                     static_cast<hipStream_t>(stream_), p);
-  MZS_HIP(nullptr, hipGetLastError());
-  return MZS_OK;
+  return launch_waves(mz::replay_store_kernel, a->episodes, stream_, p);
 }
 
 int mzs_replay_refresh(const mzs_replay_arena* arena, int32_t head, int32_t count, int32_t k_steps, void* stream_) {
@@ -146,18 +171,14 @@ int mzs_replay_sample(const mzs_replay_arena* arena, const mzs_replay_sample_arg
   mz::ReplaySampleArgs p{};
   if (int rc = check_sample(arena, a, "mzs_replay_sample", &p)) return rc;
   MZS_HIP(nullptr, hipSetDevice(arena->device));
-  hipLaunchKernelGGL(mz::replay_sample_kernel, dim3(waves_grid(a->batch)), dim3(64 * mz::kReplayWaves), 0,
-                     static_cast<hipStream_t>(stream_), p);
-  MZS_HIP(nullptr, hipGetLastError());
-  return MZS_OK;
+  return launch_waves(mz::replay_sample_kernel, a->batch, stream_, p);
 }
 
 int mzs_replay_sample_is(const mzs_replay_arena* arena, const mzs_replay_sample_args* a, const mzs_replay_is_args* w,
                          void* stream_) {
   mz::ReplaySampleArgs p{};
   if (int rc = check_sample(arena, a, "mzs_replay_sample_is", &p)) return rc;
-  if (!w || w->struct_size != (int32_t)sizeof(mzs_replay_is_args))
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample_is: null weight arguments or size mismatch (ABI)");
+  if (!args_ok(w, "mzs_replay_sample_is")) return MZS_E_INVALID;
   if (!finite_bits(w->beta) || w->beta < 0.0 || w->beta > 1.0)
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_sample_is: beta must be in 0..1");
   if (!finite_bits(w->num_windows) || w->num_windows < 1.0)
@@ -167,11 +188,10 @@ int mzs_replay_sample_is(const mzs_replay_arena* arena, const mzs_replay_sample_
   MZS_HIP(nullptr, hipSetDevice(arena->device));
   mz::ReplayIsArgs q{};
   q.beta = w->beta; q.N = w->num_windows; q.raw = w->normalize ? w->scratch : nullptr; q.isw = w->isw;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  hipLaunchKernelGGL(mz::replay_sample_is_kernel, dim3(waves_grid(a->batch)), dim3(64 * mz::kReplayWaves), 0, stream, p, q);
-  MZS_HIP(nullptr, hipGetLastError());
+  if (int rc = launch_waves(mz::replay_sample_is_kernel, a->batch, stream_, p, q)) return rc;
   if (w->normalize) {
-    hipLaunchKernelGGL(mz::replay_is_normalise_kernel, dim3(1), dim3(mz::kIsNormThreads), 0, stream, q, (int)a->batch);
+    hipLaunchKernelGGL(mz::replay_is_normalise_kernel, dim3(1), dim3(mz::kIsNormThreads), 0,
+                       static_cast<hipStream_t>(stream_), q, (int)a->batch);
     MZS_HIP(nullptr, hipGetLastError());
   }
   return MZS_OK;
@@ -180,8 +200,7 @@ int mzs_replay_sample_is(const mzs_replay_arena* arena, const mzs_replay_sample_
 int mzs_replay_gather_obs(const mzs_replay_arena* arena, const mzs_replay_gather_args* a, void* stream_) {
   mz::ReplayGatherArgs p{};
   if (int rc = check_arena(arena, "mzs_replay_gather_obs", &p.ar)) return rc;
-  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_gather_args))
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_gather_obs: null arguments or size mismatch (ABI)");
+  if (!args_ok(a, "mzs_replay_gather_obs")) return MZS_E_INVALID;
   if (int rc = check_stream_desc(arena, "mzs_replay_gather_obs", a->episodes, a->stream_rows, a->rows_padded, a->desc,
                                  a->desc_host))
     return rc;
@@ -192,39 +211,30 @@ int mzs_replay_gather_obs(const mzs_replay_arena* arena, const mzs_replay_gather
   // one tail wavefront per 1024 padding floats, 64 at the most (they stride)
   const int64_t pad = (a->rows_padded - a->stream_rows) * (int64_t)arena->obs_dim;
   p.pad_waves = (int)(pad <= 0 ? 0 : (pad + 1023) / 1024 < 64 ? (pad + 1023) / 1024 : 64);
-  hipLaunchKernelGGL(mz::replay_gather_obs_kernel, dim3(waves_grid(a->episodes + p.pad_waves)),
-                     dim3(64 * mz::kReplayWaves), 0, static_cast<hipStream_t>(stream_), p);
-  MZS_HIP(nullptr, hipGetLastError());
-  return MZS_OK;
+  return launch_waves(mz::replay_gather_obs_kernel, a->episodes + p.pad_waves, stream_, p);
 }
 
 int mzs_replay_reanalyse(const mzs_replay_arena* arena, const mzs_replay_reanalyse_args* a, void* stream_) {
   mz::ReplayReanalyseArgs p{};
   if (int rc = check_arena(arena, "mzs_replay_reanalyse", &p.ar)) return rc;
-  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_reanalyse_args))
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_reanalyse: null arguments or size mismatch (ABI)");
+  if (!args_ok(a, "mzs_replay_reanalyse")) return MZS_E_INVALID;
   if (int rc = check_stream_desc(arena, "mzs_replay_reanalyse", a->episodes, a->stream_rows, a->rows_padded, a->desc,
                                  a->desc_host))
     return rc;
-  if (a->n_step <= 0 || !a->gpow) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_reanalyse: needs n_step >= 1 and gpow");
-  if (a->weight_mode != 1 && a->weight_mode != 2)
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_reanalyse: weight_mode must be 1 (mean) or 2 (sum)");
+  if (int rc = check_nstep(a->n_step, a->gpow, "mzs_replay_reanalyse")) return rc;
+  if (int rc = check_weight_mode(a->weight_mode, "mzs_replay_reanalyse")) return rc;
   if (!a->pi || !a->v) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_reanalyse: null pi or v");
   MZS_HIP(nullptr, hipSetDevice(arena->device));
   p.episodes = a->episodes; p.n_step = a->n_step; p.weight_mode = a->weight_mode;
   p.has_alpha = a->has_alpha ? 1 : 0; p.alpha = a->alpha;
   p.desc = a->desc; p.gpow = a->gpow; p.pi = a->pi; p.v = a->v;
-  hipLaunchKernelGGL(mz::replay_reanalyse_kernel, dim3(waves_grid(a->episodes)), dim3(64 * mz::kReplayWaves), 0,
-                     static_cast<hipStream_t>(stream_), p);
-  MZS_HIP(nullptr, hipGetLastError());
-  return MZS_OK;
+  return launch_waves(mz::replay_reanalyse_kernel, a->episodes, stream_, p);
 }
 
 int mzs_replay_update_priorities(const mzs_replay_arena* arena, const mzs_replay_update_args* a, void* stream_) {
   mz::ReplayUpdateArgs p{};
   if (int rc = check_arena(arena, "mzs_replay_update_priorities", &p.ar)) return rc;
-  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_update_args))
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: null arguments or size mismatch (ABI)");
+  if (!args_ok(a, "mzs_replay_update_priorities")) return MZS_E_INVALID;
   if (a->head < 0 || a->head >= arena->capacity)
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: head must be in 0..capacity - 1");
   if (a->count < 0 || a->count > arena->capacity)
@@ -232,8 +242,7 @@ int mzs_replay_update_priorities(const mzs_replay_arena* arena, const mzs_replay
   if (a->batch < 0) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: batch must not be negative");
   if (a->k_prio < 1 || (int64_t)a->batch * a->k_prio >= ((int64_t)1 << 31))
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: k_prio must be >= 1, batch * k_prio < 2^31");
-  if (a->weight_mode != 1 && a->weight_mode != 2)
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: weight_mode must be 1 (mean) or 2 (sum)");
+  if (int rc = check_weight_mode(a->weight_mode, "mzs_replay_update_priorities")) return rc;
   if (!finite_bits(a->alpha) || a->alpha < 0.0 || a->alpha > 1.0)
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_update_priorities: alpha must be in 0..1");
   if (!finite_bits(a->eps) || a->eps < 0.0)
@@ -248,27 +257,21 @@ int mzs_replay_update_priorities(const mzs_replay_arena* arena, const mzs_replay
   p.alpha = a->alpha; p.eps = a->eps;
   p.serial = (const long long*)a->serial; p.start = a->start; p.prio = a->prio;
   p.owner = a->owner; p.touched = a->touched;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  hipLaunchKernelGGL(mz::replay_prio_mark_kernel, dim3(waves_grid(a->batch)), dim3(64 * mz::kReplayWaves), 0, stream, p);
-  MZS_HIP(nullptr, hipGetLastError());
-  hipLaunchKernelGGL(mz::replay_prio_apply_kernel, dim3(waves_grid(a->count)), dim3(64 * mz::kReplayWaves), 0, stream, p);
-  MZS_HIP(nullptr, hipGetLastError());
-  return MZS_OK;
+  if (int rc = launch_waves(mz::replay_prio_mark_kernel, a->batch, stream_, p)) return rc;
+  return launch_waves(mz::replay_prio_apply_kernel, a->count, stream_, p);
 }
 
 int mzs_replay_stage(const mzs_replay_ring* ring, const mzs_replay_stage_args* a, void* stream_) {
   mz::ReplayStageArgs p{};
   if (int rc = check_ring(ring, "mzs_replay_stage", &p.ring)) return rc;
-  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_stage_args))
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_stage: null arguments or size mismatch (ABI)");
+  if (!args_ok(a, "mzs_replay_stage")) return MZS_E_INVALID;
   if (a->row < 0 || a->row >= ring->ring_steps)
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_stage: row must be in 0..ring_steps - 1");
   if (!a->obs || !a->a || !a->v || !a->pi) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_stage: null pointer");
   MZS_HIP(nullptr, hipSetDevice(ring->device));
   p.row = a->row; p.obs_dim = ring->obs_dim; p.A = ring->num_actions;
   p.obs = a->obs; p.a = a->a; p.v = a->v; p.pi = a->pi;
-  const int64_t widest = (int64_t)ring->num_envs * (ring->obs_dim > ring->num_actions ? ring->obs_dim : ring->num_actions);
-  const int64_t blocks = (widest + mz::kStageThreads - 1) / mz::kStageThreads;
+  const int64_t blocks = (ring->num_envs * ring_widest(ring) + mz::kStageThreads - 1) / mz::kStageThreads;
   hipLaunchKernelGGL(mz::replay_stage_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(mz::kStageThreads), 0,
                      static_cast<hipStream_t>(stream_), p);
   MZS_HIP(nullptr, hipGetLastError());
@@ -280,17 +283,15 @@ int mzs_replay_store_steps(const mzs_replay_arena* arena, const mzs_replay_ring*
   mz::ReplayStoreStepsArgs p{};
   if (int rc = check_arena(arena, "mzs_replay_store_steps", &p.ar)) return rc;
   if (int rc = check_ring(ring, "mzs_replay_store_steps", &p.ring)) return rc;
-  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_store_steps_args))
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: null arguments or size mismatch (ABI)");
+  if (!args_ok(a, "mzs_replay_store_steps")) return MZS_E_INVALID;
   if (ring->obs_dim != arena->obs_dim || ring->num_actions != arena->num_actions || ring->device != arena->device)
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: ring and arena disagree in obs_dim, num_actions or device");
   if (a->episodes <= 0 || a->episodes > arena->capacity)
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: episodes must be 1..capacity");
-  if (!a->desc_host || !a->desc || !a->serial || !a->gpow)
+  if (!a->desc_host || !a->desc || !a->serial)
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: null pointer");
-  if (a->n_step < 1) return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: n_step must be >= 1");
-  if (a->weight_mode != 1 && a->weight_mode != 2)
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_store_steps: weight_mode must be 1 (mean) or 2 (sum)");
+  if (int rc = check_nstep(a->n_step, a->gpow, "mzs_replay_store_steps")) return rc;
+  if (int rc = check_weight_mode(a->weight_mode, "mzs_replay_store_steps")) return rc;
   for (int e = 0; e < a->episodes; ++e) {
     const int32_t* d = a->desc_host + 5 * e;
     const int64_t len = d[2], dst = d[3];
@@ -305,17 +306,13 @@ int mzs_replay_store_steps(const mzs_replay_arena* arena, const mzs_replay_ring*
   p.episodes = a->episodes; p.n_step = a->n_step; p.weight_mode = a->weight_mode;
   p.has_alpha = a->has_alpha ? 1 : 0; p.alpha = a->alpha;
   p.desc = a->desc; p.serial = (const long long*)a->serial; p.gpow = a->gpow;
-  hipLaunchKernelGGL(mz::replay_store_steps_kernel, dim3(waves_grid(a->episodes)), dim3(64 * mz::kReplayWaves), 0,
-                     static_cast<hipStream_t>(stream_), p);
-  MZS_HIP(nullptr, hipGetLastError());
-  return MZS_OK;
+  return launch_waves(mz::replay_store_steps_kernel, a->episodes, stream_, p);
 }
 
 int mzs_replay_plan_steps(const mzs_replay_ring* ring, const mzs_replay_plan_args* a, void* stream_) {
   mz::ReplayPlanArgs p{};
   if (int rc = check_ring(ring, "mzs_replay_plan_steps", &p.ring)) return rc;
-  if (!a || a->struct_size != (int32_t)sizeof(mzs_replay_plan_args))
-    return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_plan_steps: null arguments or size mismatch (ABI)");
+  if (!args_ok(a, "mzs_replay_plan_steps")) return MZS_E_INVALID;
   if (a->row0 < 0 || a->row0 >= ring->ring_steps)
     return mzh::fail(nullptr, MZS_E_INVALID, "mzs_replay_plan_steps: row0 must be in 0..ring_steps - 1");
   if (a->steps < 1 || a->steps > ring->ring_steps)

@@ -54,12 +54,9 @@ class DeviceCartPole:
         self._r = torch.zeros(self.n, dtype=torch.float64, device=dev)      # the host protocol's outputs
         self._done = torch.zeros(self.n, dtype=torch.uint8, device=dev)
         key = prng.PRNGKey(seed)
-        env = _lib.MzsEnvCartPole()
-        env.struct_size = C.sizeof(_lib.MzsEnvCartPole)
-        env.device, env.num_envs, env.max_episode_steps = dev.index, self.n, self.spec.max_episode_steps
-        env.key[0], env.key[1] = int(key[0]), int(key[1])
-        env.state, env.t, env.draws = self._state.data_ptr(), self._t.data_ptr(), self._draws.data_ptr()
-        self._env = env
+        self._env = _lib.args(_lib.MzsEnvCartPole, device=dev.index, num_envs=self.n,
+                              max_episode_steps=self.spec.max_episode_steps, key=(int(key[0]), int(key[1])),
+                              state=self._state.data_ptr(), t=self._t.data_ptr(), draws=self._draws.data_ptr())
 
     def _stream(self):
         import torch
@@ -82,8 +79,7 @@ class DeviceCartPole:
         import torch
 
         from . import _lib
-        s = _lib.MzsEnvStepArgs()
-        s.struct_size = C.sizeof(_lib.MzsEnvStepArgs)
+        s = _lib.args(_lib.MzsEnvStepArgs)  # (per step: fields by attribute, which is 1 us cheaper)
         s.a = self._view(a, torch.int32, "a")
         s.r_out, s.done_out = self._view(r_out, torch.float64, "r_out"), self._view(done_out, torch.uint8, "done_out")
         s.obs_out = self._obs.data_ptr()

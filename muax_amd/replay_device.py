@@ -70,6 +70,24 @@ def _columns(trajectory):
             np.ascontiguousarray(pi.reshape(T, -1), dtype=np.float32), col(w, np.float64))
 
 
+def _gpow(gamma, n):
+    """The discount powers gamma ** 0 .. gamma ** n the n-step kernels read."""
+    return np.array([float(gamma) ** i for i in range(int(n) + 1)], np.float64)
+
+
+def _check_nstep(who, n, weight):
+    if weight not in _WEIGHT_MODES:
+        raise ValueError("weight must be 'mean' or 'sum'")
+    if int(n) < 1:
+        raise ValueError(f"{who}: n must be at least 1")
+
+
+def _nstep_fields(n, weight_mode, alpha):
+    """The n-step fields the store, store_steps and reanalyse argument structs share."""
+    return dict(n_step=int(n), weight_mode=weight_mode, has_alpha=int(alpha is not None),
+                alpha=float(alpha if alpha is not None else 0.0))
+
+
 class DeviceReplayBuffer(BaseReplayBuffer):
     """Ring buffer of whole episodes on the GPU.
 
@@ -203,13 +221,9 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         shapes = {"obs": (S, self.obs_dim), "pi": (S, self.num_actions)}
         self._t = {n: torch.zeros(shapes.get(n, (S,)), dtype=dt, device=dev) for n, dt in _ARENA_FIELDS}
         self._t.update({n: torch.zeros(self._capacity, dtype=dt, device=dev) for n, dt in _TABLE_FIELDS})
-        ar = _lib.MzsReplayArena()
-        ar.struct_size = C.sizeof(_lib.MzsReplayArena)
-        ar.device = dev.index if dev.index is not None else torch.cuda.current_device()
-        ar.max_steps, ar.capacity, ar.obs_dim, ar.num_actions = S, self._capacity, self.obs_dim, self.num_actions
-        for n, x in self._t.items():
-            setattr(ar, n, x.data_ptr())
-        self._arena = ar
+        self._arena = _lib.args(_lib.MzsReplayArena, max_steps=S, capacity=self._capacity, obs_dim=self.obs_dim,
+                                num_actions=self.num_actions, **{n: x.data_ptr() for n, x in self._t.items()},
+                                device=dev.index if dev.index is not None else torch.cuda.current_device())
 
     def _stream(self):
         raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -223,17 +237,9 @@ class DeviceReplayBuffer(BaseReplayBuffer):
             raise ValueError(f"episode has obs_dim {obs_dim}, {num_actions} actions; the buffer holds "
                              f"obs_dim {self.obs_dim}, {self.num_actions} actions")
 
-    def _store(self, placed, host, device, raw=False, n=0, alpha=None, weight_mode=0, stream_steps=0):
-        """One upload (the arrays of `host`, by name, in one staging buffer) and one launch.  `placed`:
-        [(first transition in the stream, _Episode)] of the episodes that are still held; `device`: fields that
-        already are device tensors."""
-        live = {e.serial for e in self._eps}
-        placed = [(src, e) for src, e in placed if e.serial in live]
-        if not placed:
-            return
-        desc = np.array([[src, e.start, e.length, e.slot] for src, e in placed], np.int32)
-        host = dict(host, serial=np.array([e.serial for _, e in placed], np.int64), desc=desc)
-        # widest element type first, every block starting on a multiple of 16 bytes
+    def _upload(self, **host):
+        """Small host arrays in ONE staging tensor and one copy: the widest element type first, every block starting
+        on a multiple of 16 bytes.  Returns (the device tensor, {name: device pointer})."""
         names = sorted(host, key=lambda k: -host[k].dtype.itemsize)
         offs, total = {}, 0
         for k in names:
@@ -243,17 +249,21 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         for k in names:
             stage[offs[k]:offs[k] + host[k].nbytes] = host[k].reshape(-1).view(np.uint8)
         dstage = torch.from_numpy(stage).to(self._device)
-        base = dstage.data_ptr()
-        a = _lib.MzsReplayStoreArgs()
-        a.struct_size = C.sizeof(_lib.MzsReplayStoreArgs)
-        a.episodes, a.stream_steps = len(placed), stream_steps
-        a.raw, a.n_step, a.weight_mode = int(raw), int(n), weight_mode
-        a.has_alpha, a.alpha = int(alpha is not None), float(alpha if alpha is not None else 0.0)
-        a.desc_host = desc.ctypes.data
-        for k in names:
-            setattr(a, k, base + offs[k])
-        for k, x in device.items():
-            setattr(a, k, x.data_ptr())
+        return dstage, {k: dstage.data_ptr() + offs[k] for k in names}
+
+    def _store(self, placed, host, device, raw=False, n=0, alpha=None, weight_mode=0, stream_steps=0):
+        """One upload (the arrays of `host`, by name, in one staging buffer) and one launch.  `placed`:
+        [(first transition in the stream, _Episode)] of the episodes that are still held; `device`: fields that
+        already are device tensors."""
+        live = {e.serial for e in self._eps}
+        placed = [(src, e) for src, e in placed if e.serial in live]
+        if not placed:
+            return
+        desc = np.array([[src, e.start, e.length, e.slot] for src, e in placed], np.int32)
+        dstage, ptrs = self._upload(**host, serial=np.array([e.serial for _, e in placed], np.int64), desc=desc)
+        a = _lib.args(_lib.MzsReplayStoreArgs, episodes=len(placed), stream_steps=stream_steps, raw=int(raw),
+                      desc_host=desc.ctypes.data, **_nstep_fields(n, weight_mode, alpha), **ptrs,
+                      **{k: x.data_ptr() for k, x in device.items()})
         _lib.check(self._L.mzs_replay_store(C.byref(self._arena), C.byref(a), self._stream()))
         self._keep = (dstage, device)
 
@@ -289,14 +299,11 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         the n-step returns, `done` and the priority weights of `vector.nstep_returns` / `episode_trajectory`
         (w = |v - Rn| ** alpha, 1 when alpha is None) are computed on the device in fp64, in NumPy's operation
         order; the buffer weight of an episode is the `weight` ("mean" or "sum") of its transition weights."""
-        if weight not in _WEIGHT_MODES:
-            raise ValueError("weight must be 'mean' or 'sum'")
+        _check_nstep("add_raw", n, weight)
         lengths = [int(x) for x in np.asarray(lengths).reshape(-1)]
         M = sum(lengths)
         if not lengths or min(lengths) <= 0:
             raise ValueError("add_raw: episode lengths must be positive")
-        if int(n) < 1:
-            raise ValueError("add_raw: n must be at least 1")
         host, device = {}, {}
         for k, x, np_dt, t_dt in (("obs", obs, np.float32, torch.float32), ("a", a, np.int32, torch.int32),
                                   ("r", r, np.float64, torch.float64), ("v", v, np.float64, torch.float64),
@@ -314,7 +321,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
             raise ValueError("add_raw: a, r and v are one scalar per transition")
         self._check_dims(dims["obs"].shape[1], dims["pi"].shape[1])
         placed = self._place_all(lengths)
-        host["gpow"] = np.array([float(gamma) ** i for i in range(int(n) + 1)], np.float64)
+        host["gpow"] = _gpow(gamma, n)
         self._store(placed, host, device, raw=True, n=n, alpha=alpha, weight_mode=_WEIGHT_MODES[weight], stream_steps=M)
 
     def add_steps(self, ring, episodes, n, gamma, alpha=None, weight="mean"):
@@ -327,10 +334,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         have not been timed against `add_raw`'s dense ones.  An episode longer than `max_steps` is add_raw's
         ValueError, before anything is placed.  Returns the serial given to every episode, in order (an episode the
         collection itself evicts again has one, but is not stored)."""
-        if weight not in _WEIGHT_MODES:
-            raise ValueError("weight must be 'mean' or 'sum'")
-        if int(n) < 1:
-            raise ValueError("add_steps: n must be at least 1")
+        _check_nstep("add_steps", n, weight)
         episodes = [(int(env), int(first), int(T)) for env, first, T in episodes]
         if not episodes:
             return []
@@ -342,18 +346,10 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         live = {e.serial for e in self._eps}
         kept = [(env, first, e) for (env, first, _), (_, e) in zip(episodes, placed) if e.serial in live]
         desc = np.array([[env, first, e.length, e.start, e.slot] for env, first, e in kept], np.int32)
-        head = np.concatenate([np.array([e.serial for _, _, e in kept], np.int64).view(np.float64),
-                               np.array([float(gamma) ** i for i in range(int(n) + 1)], np.float64)])
-        stage = np.empty(head.nbytes + desc.nbytes, np.uint8)  # the 8-byte elements first
-        stage[:head.nbytes] = head.view(np.uint8)
-        stage[head.nbytes:] = desc.reshape(-1).view(np.uint8)
-        dstage = torch.from_numpy(stage).to(self._device)
-        a = _lib.MzsReplayStoreStepsArgs()
-        a.struct_size = C.sizeof(_lib.MzsReplayStoreStepsArgs)
-        a.episodes, a.n_step, a.weight_mode = len(kept), int(n), _WEIGHT_MODES[weight]
-        a.has_alpha, a.alpha = int(alpha is not None), float(alpha if alpha is not None else 0.0)
-        a.desc_host, a.desc = desc.ctypes.data, dstage.data_ptr() + head.nbytes
-        a.serial, a.gpow = dstage.data_ptr(), dstage.data_ptr() + 8 * len(kept)
+        dstage, ptrs = self._upload(serial=np.array([e.serial for _, _, e in kept], np.int64), gpow=_gpow(gamma, n),
+                                    desc=desc)
+        a = _lib.args(_lib.MzsReplayStoreStepsArgs, episodes=len(kept), desc_host=desc.ctypes.data,
+                      **_nstep_fields(n, _WEIGHT_MODES[weight], alpha), **ptrs)
         _lib.check(self._L.mzs_replay_store_steps(C.byref(self._arena), C.byref(ring), C.byref(a), self._stream()))
         self._keep = (dstage,)
         return serials
@@ -383,10 +379,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         One upload (descriptors and discount powers), two launches around the searches; no device-to-host copy and
         no synchronisation beyond what act() does on its route.  A serial that is not held is a KeyError, a
         repeated one a ValueError, both before anything is launched.  Returns the number of transitions refreshed."""
-        if weight not in _WEIGHT_MODES:
-            raise ValueError("weight must be 'mean' or 'sum'")
-        if int(n) < 1:
-            raise ValueError("reanalyse: n must be at least 1")
+        _check_nstep("reanalyse", n, weight)
         held = {e.serial: e for e in self._eps}
         serials = list(held) if serials is None else [int(s) for s in serials]
         if len(set(serials)) != len(serials):
@@ -400,19 +393,14 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         R = int(chunk_rows)
         plan = reanalyse_plan([e.length for e in eps], R)
         desc = np.array([[src, e.start, e.length, e.slot] for src, e in zip(plan.offsets, eps)], np.int32)
-        gpow = np.array([float(gamma) ** i for i in range(int(n) + 1)], np.float64)
-        stage = np.empty(gpow.nbytes + desc.nbytes, np.uint8)  # gpow (8-byte elements) first
-        stage[:gpow.nbytes] = gpow.view(np.uint8)
-        stage[gpow.nbytes:] = desc.reshape(-1).view(np.uint8)
-        dstage = torch.from_numpy(stage).to(self._device)
+        dstage, ptrs = self._upload(gpow=_gpow(gamma, n), desc=desc)
         dev, f32, stream = self._device, torch.float32, self._stream()
         obs = torch.empty((plan.rows_padded, self.obs_dim), dtype=f32, device=dev)
         pi = torch.empty((plan.rows_padded, self.num_actions), dtype=f32, device=dev)
         v = torch.empty(plan.rows_padded, dtype=f32, device=dev)
-        g = _lib.MzsReplayGatherArgs()
-        g.struct_size = C.sizeof(_lib.MzsReplayGatherArgs)
-        g.episodes, g.stream_rows, g.rows_padded = len(eps), plan.stream_rows, plan.rows_padded
-        g.desc, g.desc_host, g.obs = dstage.data_ptr() + gpow.nbytes, desc.ctypes.data, obs.data_ptr()
+        stream_args = dict(episodes=len(eps), stream_rows=plan.stream_rows, rows_padded=plan.rows_padded,
+                           desc=ptrs["desc"], desc_host=desc.ctypes.data)
+        g = _lib.args(_lib.MzsReplayGatherArgs, obs=obs.data_ptr(), **stream_args)
         _lib.check(self._L.mzs_replay_gather_obs(C.byref(self._arena), C.byref(g), stream))
         keys = prng.split(prng.as_key(key), plan.n_chunks)
         for c in range(plan.n_chunks):
@@ -421,13 +409,8 @@ class DeviceReplayBuffer(BaseReplayBuffer):
                                      device_outputs=True, **act_kwargs)
             pi[rows].copy_(pi_c)
             v[rows].copy_(v_c)
-        a = _lib.MzsReplayReanalyseArgs()
-        a.struct_size = C.sizeof(_lib.MzsReplayReanalyseArgs)
-        a.episodes, a.stream_rows, a.rows_padded = len(eps), plan.stream_rows, plan.rows_padded
-        a.desc, a.desc_host = g.desc, g.desc_host
-        a.n_step, a.weight_mode = int(n), _WEIGHT_MODES[weight]
-        a.has_alpha, a.alpha = int(alpha is not None), float(alpha if alpha is not None else 0.0)
-        a.gpow, a.pi, a.v = dstage.data_ptr(), pi.data_ptr(), v.data_ptr()
+        a = _lib.args(_lib.MzsReplayReanalyseArgs, gpow=ptrs["gpow"], pi=pi.data_ptr(), v=v.data_ptr(), **stream_args,
+                      **_nstep_fields(n, _WEIGHT_MODES[weight], alpha))
         _lib.check(self._L.mzs_replay_reanalyse(C.byref(self._arena), C.byref(a), self._stream()))
         self._keep = (dstage, obs, pi, v)
         self._clock += 1
@@ -479,8 +462,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         if self._prio_scratch is None:  # owner [max_steps] = -1, touched [capacity] = 0; the kernels leave them so
             self._prio_scratch = (torch.full((self._max_steps,), -1, dtype=torch.int32, device=dev),
                                   torch.zeros(self._capacity, dtype=torch.int32, device=dev))
-        u = _lib.MzsReplayUpdateArgs()
-        u.struct_size = C.sizeof(_lib.MzsReplayUpdateArgs)
+        u = _lib.args(_lib.MzsReplayUpdateArgs)  # (per training step: fields by attribute, which is 1 us cheaper)
         u.head, u.count, u.batch, u.k_prio = self._head, len(self._eps), B, prio.shape[1] if prio.ndim == 2 else 1
         u.weight_mode, u.alpha, u.eps = _WEIGHT_MODES[weight], alpha, eps
         u.serial, u.start, u.prio = serial.data_ptr(), start.data_ptr(), prio.data_ptr()
@@ -541,8 +523,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         pi = torch.empty((B, k, self.num_actions), dtype=f32, device=dev)
         serial = torch.empty(B, dtype=torch.int64, device=dev)
         start = torch.empty(B, dtype=torch.int32, device=dev)
-        s = _lib.MzsReplaySampleArgs()
-        s.struct_size = C.sizeof(_lib.MzsReplaySampleArgs)
+        s = _lib.args(_lib.MzsReplaySampleArgs)  # (per training step: fields by attribute, which is 1 us cheaper)
         s.count, s.batch, s.k_steps, s.sample_per_trajectory = len(self._eps), B, k, spt
         s.key[0], s.key[1] = int(key[0]), int(key[1])
         s.obs, s.a, s.r, s.Rn, s.v, s.done = (x.data_ptr() for x in (obs, a, r, Rn, v, done))
@@ -554,8 +535,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         isw = torch.empty(B, dtype=f32, device=dev)
         if is_normalize and (self._is_scratch is None or self._is_scratch.numel() < B):
             self._is_scratch = torch.empty(B, dtype=torch.float64, device=dev)  # raw weights; grows with the batch
-        q = _lib.MzsReplayIsArgs()
-        q.struct_size = C.sizeof(_lib.MzsReplayIsArgs)
+        q = _lib.args(_lib.MzsReplayIsArgs)
         q.normalize, q.beta, q.num_windows = int(bool(is_normalize)), is_beta, float(self._windows)
         q.isw, q.scratch = isw.data_ptr(), self._is_scratch.data_ptr() if is_normalize else None
         _lib.check(self._L.mzs_replay_sample_is(C.byref(self._arena), C.byref(s), C.byref(q), stream))

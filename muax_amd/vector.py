@@ -210,8 +210,6 @@ class DeviceVectorCollector:
         self._plan_held = 0      # device_plan: the longest open episode after the previous call (counts[2])
 
     def _alloc(self, N, obs_dim, A):
-        import ctypes as C
-
         import torch
 
         from . import _lib
@@ -221,13 +219,10 @@ class DeviceVectorCollector:
         shapes = {"obs": ((S, N, obs_dim), torch.float32), "a": ((S, N), torch.int32), "r": ((S, N), torch.float64),
                   "v": ((S, N), torch.float32), "pi": ((S, N, A), torch.float32)}
         self._fields = {k: torch.zeros(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
-        ring = _lib.MzsReplayRing()
-        ring.struct_size = C.sizeof(_lib.MzsReplayRing)
-        ring.device = buf._arena.device
-        ring.ring_steps, ring.num_envs, ring.obs_dim, ring.num_actions = S, N, obs_dim, A
-        for k, x in self._fields.items():
-            setattr(ring, k, x.data_ptr())
-        self._ring = ring
+        self._ring = _lib.args(_lib.MzsReplayRing, device=buf._arena.device, ring_steps=S, num_envs=N, obs_dim=obs_dim,
+                               num_actions=A, **{k: x.data_ptr() for k, x in self._fields.items()})
+        if hasattr(self.venv, "step_device"):  # the flags a device environment writes, beside the ring fields
+            self._done_rows = torch.zeros((S, N), dtype=torch.uint8, device=dev)
 
     def _stage(self, i, obs_d, a, pi, v):
         """One `mzs_replay_stage`: step i of the call into its ring row.  Returns the actions as int32 on the device."""
@@ -240,50 +235,70 @@ class DeviceVectorCollector:
         flat = obs_d.reshape(N, -1).contiguous()
         a32 = a.to(torch.int32).contiguous()
         pi32, v32 = pi.to(torch.float32).reshape(N, -1).contiguous(), v.to(torch.float32).reshape(N).contiguous()
-        s = _lib.MzsReplayStageArgs()
-        s.struct_size = C.sizeof(_lib.MzsReplayStageArgs)
+        s = _lib.args(_lib.MzsReplayStageArgs)  # (per step: fields by attribute, which is 1 us cheaper)
         s.row = (self._step0 + i) % self.ring_steps
         s.obs, s.a, s.v, s.pi = flat.data_ptr(), a32.data_ptr(), v32.data_ptr(), pi32.data_ptr()
         _lib.check(self.buffer._L.mzs_replay_stage(C.byref(self._ring), C.byref(s), self.buffer._stream()))
         return a32
 
-    def _steps_device_env(self, model, key, steps, num_simulations, temperature, act_kwargs, download=True):
-        """The step loop for a device environment (muax_amd/envs.py): the observations never leave the device, the
-        environment writes every step's rewards into the ring's `r` row and its flags into the same row of
-        `self._done_rows` (uint8 [ring_steps, N], beside the ring fields), and nothing in the loop copies to the host
-        or synchronises; all launches go on the one stream the staging launch uses, which orders the environment's
-        overwrite of its observation tensor after the staging launch that read it.  Afterwards the call's rows of `r`
-        and of the flags come down, in at most two copies each.  Returns (key, R [T, N] float64, D [T, N] bool);
-        with `download=False` (the device plan) nothing comes down and R, D are None."""
+    def _spans(self, steps):
+        """The ring rows of the call's `steps` steps as [(lo, hi)]: one span, two where they wrap past the ring's end."""
+        row0 = self._step0 % self.ring_steps
+        k = min(steps, self.ring_steps - row0)
+        return [(row0, row0 + k)] + ([(0, steps - k)] if k < steps else [])
+
+    def _steps(self, model, key, steps, num_simulations, temperature, act_kwargs):
+        """The step loop of every route: act() on device tensors, the staging launch, then the environment.  A host
+        environment gets the actions (the one device-to-host copy of the step) and returns NumPy; its rewards go up
+        into the ring's `r` rows after the loop.  A device environment (muax_amd/envs.py) keeps the observations on the
+        device and writes every step's rewards into the ring's `r` row and its flags into the same row of
+        `self._done_rows` (uint8 [ring_steps, N]); nothing in its loop copies to the host or synchronises, and all
+        launches go on the one stream the staging launch uses, which orders the environment's overwrite of its
+        observation tensor after the staging launch that read it.  Afterwards the call's rows of `r` and of the flags
+        come down, in at most two copies each.  Returns (key, R [T, N] float64, D [T, N] bool); under `device_plan`
+        nothing comes down and R, D are None."""
         import torch
         venv, S = self.venv, self.ring_steps
-        N = int(venv.n)
-        if self._obs is None:
-            dev = self.buffer._device
-            if dev is not None and dev.index is not None and torch.device(venv.device) != dev:
+        on_device = hasattr(venv, "step_device")
+        dev, first = self.buffer._device, self._obs is None
+        if first:
+            if on_device and dev is not None and dev.index is not None and torch.device(venv.device) != dev:
                 raise ValueError(f"collect: the environment is on {venv.device}, the buffer on {dev}")
-            self._obs = venv.reset_device()
-            if download:
-                self._open_start, self._open_r = np.zeros(N, np.int64), [[] for _ in range(N)]
-        obs_d = self._obs
+            self._obs = venv.reset_device() if on_device else np.asarray(venv.reset())
+        obs = self._obs
+        N = int(venv.n) if on_device else obs.shape[0]
+        if first and not self.device_plan:
+            self._open_start, self._open_r = np.zeros(N, np.int64), [[] for _ in range(N)]
+        if dev is None and not on_device:
+            dev = model.device
+        r_l, d_l = [], []
         for i in range(steps):
             key, subkey = prng.split(key)
+            obs_d = obs if on_device else torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).to(dev)
             a, pi, v = model.act(subkey, obs_d, with_pi=True, with_value=True, obs_from_batch=True, device_outputs=True,
                                  num_simulations=num_simulations, temperature=temperature, **act_kwargs)
             if self._ring is None:
                 self._alloc(N, int(obs_d.numel() // N), int(pi.shape[-1]))
-                self._done_rows = torch.zeros((S, N), dtype=torch.uint8, device=self._fields["r"].device)
             a32 = self._stage(i, obs_d, a, pi, v)
-            row = (self._step0 + i) % S
-            obs_d = venv.step_device(a32, self._fields["r"][row], self._done_rows[row])
-        self._obs = obs_d
-        if not download:
+            if on_device:
+                row = (self._step0 + i) % S
+                obs = venv.step_device(a32, self._fields["r"][row], self._done_rows[row])
+            else:
+                nxt, r, done = venv.step(a32.cpu().numpy())  # the one device-to-host copy of the step
+                r_l.append(np.asarray(r, np.float64)), d_l.append(np.asarray(done, bool))
+                obs = np.asarray(nxt)
+        self._obs = obs
+        if self.device_plan:
             return key, None, None
-        row0 = self._step0 % S
-        k = min(steps, S - row0)
-        parts = [(row0, row0 + k)] + ([(0, steps - k)] if k < steps else [])
-        R = np.concatenate([self._fields["r"][lo:hi].cpu().numpy() for lo, hi in parts])
-        D = np.concatenate([self._done_rows[lo:hi].cpu().numpy() for lo, hi in parts]).astype(bool)
+        spans = self._spans(steps)
+        if on_device:
+            R = np.concatenate([self._fields["r"][lo:hi].cpu().numpy() for lo, hi in spans])
+            D = np.concatenate([self._done_rows[lo:hi].cpu().numpy() for lo, hi in spans]).astype(bool)
+        else:
+            R, D, at = np.stack(r_l), np.stack(d_l), 0  # [T, N]
+            for lo, hi in spans:
+                self._fields["r"][lo:hi].copy_(torch.from_numpy(R[at:at + hi - lo]))
+                at += hi - lo
         return key, R, D
 
     def _collect_device_plan(self, model, key, steps, num_simulations, temperature, act_kwargs):
@@ -296,7 +311,7 @@ class DeviceVectorCollector:
         from . import _lib
         if int(self.venv.n) * steps >= 2 ** 31:
             raise ValueError("collect: device_plan needs num_envs * steps below 2^31")
-        key, _, _ = self._steps_device_env(model, key, steps, num_simulations, temperature, act_kwargs, download=False)
+        key, _, _ = self._steps(model, key, steps, num_simulations, temperature, act_kwargs)
         N, S = int(self._ring.num_envs), self.ring_steps
         dev = self._fields["r"].device
         if self._plan is None:
@@ -309,12 +324,8 @@ class DeviceVectorCollector:
             pl["ep"] = torch.zeros((N * steps, 4), dtype=torch.int32, device=dev)
             pl["ret"] = torch.zeros(N * steps, dtype=torch.float64, device=dev)
         max_out = int(pl["ep"].shape[0])
-        a = _lib.MzsReplayPlanArgs()
-        a.struct_size = C.sizeof(_lib.MzsReplayPlanArgs)
-        a.row0, a.steps, a.min_length, a.max_out = self._step0 % S, steps, self.min_length, max_out
-        a.done = self._done_rows.data_ptr()
-        for k, x in pl.items():
-            setattr(a, k, x.data_ptr())
+        a = _lib.args(_lib.MzsReplayPlanArgs, row0=self._step0 % S, steps=steps, min_length=self.min_length,
+                      max_out=max_out, done=self._done_rows.data_ptr(), **{k: x.data_ptr() for k, x in pl.items()})
         _lib.check(self.buffer._L.mzs_replay_plan_steps(C.byref(self._ring), C.byref(a), self.buffer._stream()))
         counts = pl["counts"].cpu().numpy()
         episodes = int(counts[0])
@@ -338,7 +349,6 @@ class DeviceVectorCollector:
         and the serial None for one dropped as shorter than `min_length`.
         ValueError before the first step when an open episode could outgrow the ring (its steps so far plus `steps`
         exceed `ring_steps`): nothing is overwritten and a call with fewer steps still works."""
-        import torch
         steps = int(steps)
         if steps < 1:
             raise ValueError("collect: steps must be at least 1")
@@ -354,37 +364,9 @@ class DeviceVectorCollector:
                              f"{S} steps (ring_steps)")
         if self.device_plan:
             return self._collect_device_plan(model, key, steps, num_simulations, temperature, act_kwargs)
-        step0, row0 = self._step0, self._step0 % S
-        k = min(steps, S - row0)  # the call's rows wrap past the ring's end when k < steps
-        if hasattr(self.venv, "step_device"):
-            key, R, D = self._steps_device_env(model, key, steps, num_simulations, temperature, act_kwargs)
-            N = R.shape[1]
-        else:
-            if self._obs is None:
-                self._obs = np.asarray(self.venv.reset())
-                N = self._obs.shape[0]
-                self._open_start, self._open_r = np.zeros(N, np.int64), [[] for _ in range(N)]
-            obs = self._obs
-            N = obs.shape[0]
-            dev = self.buffer._device if self.buffer._device is not None else model.device
-            r_l, d_l = [], []
-            for i in range(steps):
-                key, subkey = prng.split(key)
-                obs_d = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).to(dev)
-                a, pi, v = model.act(subkey, obs_d, with_pi=True, with_value=True, obs_from_batch=True,
-                                     device_outputs=True, num_simulations=num_simulations, temperature=temperature,
-                                     **act_kwargs)
-                if self._ring is None:
-                    self._alloc(N, int(obs_d.numel() // N), int(pi.shape[-1]))
-                a32 = self._stage(i, obs_d, a, pi, v)
-                nxt, r, done = self.venv.step(a32.cpu().numpy())  # the one device-to-host copy of the step
-                r_l.append(np.asarray(r, np.float64)), d_l.append(np.asarray(done, bool))
-                obs = np.asarray(nxt)
-            self._obs = obs
-            R, D = np.stack(r_l), np.stack(d_l)  # [T, N]
-            self._fields["r"][row0:row0 + k].copy_(torch.from_numpy(R[:k]))
-            if k < steps:
-                self._fields["r"][:steps - k].copy_(torch.from_numpy(R[k:]))
+        step0 = self._step0
+        key, R, D = self._steps(model, key, steps, num_simulations, temperature, act_kwargs)
+        N = R.shape[1]
         finished, dropped, new_open = ring_plan(D, self._open_start, step0, self.min_length)
         # the returns, from the host's rewards: the carried part of an episode, then the call's
         Rt = np.ascontiguousarray(R.T)
@@ -513,23 +495,26 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                              f"{type(buffer).__name__}.sample does not")
         if not callable(is_beta) and not 0.0 <= float(is_beta) <= 1.0:
             raise ValueError("fit_vector: is_beta must be None, a number in 0..1 or a callable")
-    if hasattr(venv, "step_device"):
-        if not device_collect:
-            raise ValueError(f"fit_vector: {type(venv).__name__} is a device environment (it has step_device) and needs "
-                             f"device_collect=True; device_collect is False")
-        if not hasattr(buffer, "add_steps"):
-            raise ValueError(f"fit_vector: {type(venv).__name__} is a device environment (it has step_device) and needs "
-                             f"a buffer with the device store, add_steps (DeviceReplayBuffer); "
-                             f"{type(buffer).__name__} has none")
+    on_device = hasattr(venv, "step_device")
+    if on_device and not device_collect:
+        raise ValueError(f"fit_vector: {type(venv).__name__} is a device environment (it has step_device) and needs "
+                         f"device_collect=True; device_collect is False")
     if device_collect:
         if not hasattr(buffer, "add_steps"):
-            raise ValueError(f"fit_vector: device_collect needs a buffer with the device store (DeviceReplayBuffer); "
-                             f"{type(buffer).__name__} has none")
+            if on_device:
+                needs = (f"{type(venv).__name__} is a device environment (it has step_device) and needs a buffer with "
+                         f"the device store, add_steps (DeviceReplayBuffer)")
+            else:
+                needs = "device_collect needs a buffer with the device store (DeviceReplayBuffer)"
+            raise ValueError(f"fit_vector: {needs}; {type(buffer).__name__} has none")
         collector = DeviceVectorCollector(venv, buffer, n_step, gamma, alpha, weight=trajectory_weight,
                                           min_length=k_steps, device_plan=device_plan)
     else:
         collector = VectorCollector(venv, n_step, gamma, alpha)
     prioritise = bool(priority_update) and hasattr(buffer, "update_priorities")
+    sample_kw = dict(num_trajectory=num_trajectory, k_steps=k_steps, sample_per_trajectory=sample_per_trajectory)
+    if prioritise:
+        sample_kw["with_indices"] = True
     key = prng.PRNGKey(random_seed)
     key, test_key, subkey = prng.split(key, 3)
     model.init(subkey, np.asarray(venv.reset())[:1].astype(float))
@@ -564,20 +549,11 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                 if is_beta is not None:
                     beta = is_beta(training_steps=training_step, max_training_steps=max_training_steps) \
                         if callable(is_beta) else is_beta
-                    got = buffer.sample(num_trajectory=num_trajectory, k_steps=k_steps,
-                                        sample_per_trajectory=sample_per_trajectory, with_indices=prioritise,
-                                        is_beta=float(beta))
-                    batch, isw = got[0], got[-1]
-                    indices = got[1] if prioritise else None
-                    loss += model.update(batch, sample_weight=isw)["loss"]
-                else:
-                    if prioritise:
-                        batch, indices = buffer.sample(num_trajectory=num_trajectory, k_steps=k_steps,
-                                                       sample_per_trajectory=sample_per_trajectory, with_indices=True)
-                    else:
-                        batch = buffer.sample(num_trajectory=num_trajectory,
-                                              sample_per_trajectory=sample_per_trajectory, k_steps=k_steps)
-                    loss += model.update(batch)["loss"]
+                    sample_kw["is_beta"] = float(beta)
+                got = buffer.sample(**sample_kw)  # batch[, indices][, isw]
+                got = got if prioritise or is_beta is not None else (got,)
+                batch, indices = got[0], got[1] if prioritise else None
+                loss += model.update(batch, **({} if is_beta is None else {"sample_weight": got[-1]}))["loss"]
                 if prioritise:
                     prio = value_priorities(model, batch) if priority_steps is None else \
                         unroll_value_priorities(model, batch, min(int(priority_steps), k_steps))

@@ -85,7 +85,7 @@ def split_ms(collector, fn, iters, plan=False):
         setattr(obj, name, outer)
         return lambda: setattr(obj, name, inner)
 
-    undo = [timed(collector, "_steps_device_env", "loop", False), timed(collector.buffer, "add_steps", "add_steps", True)]
+    undo = [timed(collector, "_steps", "loop", False), timed(collector.buffer, "add_steps", "add_steps", True)]
     if plan:  # from the plan call to the end of the collector's downloads: counts, then (if any episode ended) ep, ret
         L, cpu = collector.buffer._L, torch.Tensor.cpu
         inner_plan, mark = L.mzs_replay_plan_steps, {}
