@@ -846,6 +846,48 @@ typedef struct mzs_env_step_args {
 } mzs_env_step_args;
 int mzs_env_cartpole_step(const mzs_env_cartpole *env, const mzs_env_step_args *a, void *stream);
 
+/* ---- vector environments stepped on the device: Acrobot and MountainCar ----
+ * The two other discrete classic-control tasks behind one descriptor; `kind` selects the dynamics and with them the
+ * widths:            kind                  state [N, .] f64             obs_out [N, .] f32                     actions
+ *   MZS_ENV_ACROBOT      (1)   4: th1, th2, dth1, dth2     6: cos th1, sin th1, cos th2, sin th2, dth1, dth2    3
+ *   MZS_ENV_MOUNTAINCAR  (2)   2: x, v                     2: (float)x, (float)v                                3
+ * Conventions, arrays, auto-reset and the draw rule are the cart-pole's: with C drawn components, component c of
+ * environment e's d-th draw (d = draws[e], which then grows by one) is lo_c + width_c * u53(key, e, C d + c) --
+ *   Acrobot: all four components -0.1 + 0.2 u (C = 4);   MountainCar: x = -0.6 + 0.2 u, v = 0 (C = 1)
+ * -- no math-library call, so the same bits as the host's restatement.  C d + c is taken modulo 2^32.
+ * Acrobot (Sutton & Barto's "book" equations as in Gym's Acrobot-v1): action <= 0 is torque -1, 1 is 0, >= 2 is +1; one
+ *   classical Runge-Kutta step of dt = 0.2 of (state, torque) with m1 = m2 = 1, l1 = 1, lc1 = lc2 = 0.5, I1 = I2 = 1,
+ *   g = 9.8; then th1 and th2 are brought into [-pi, pi] by repeated -+2 pi (each way at most 64 times: far more than
+ *   any step from a wrapped state needs, and an infinite or absurdly large uploaded angle cannot keep the launch
+ *   running), dth1 is clamped to +-4 pi and dth2 to +-9 pi.  terminated = -cos th1 - cos(th1 + th2) > 1 on the NEW
+ *   state; r_out = -1.0, and 0.0 on a terminating step.
+ * MountainCar (Gym's MountainCar-v0 in fp64): the action is clamped to 0..2; v += (a - 1) 0.001 + cos(3 x) (-0.0025),
+ *   v clamped to +-0.07, x += v, x clamped to [-1.2, 0.6], v = 0 where x == -1.2 and v < 0; terminated = x >= 0.5 and
+ *   v >= 0; r_out = -1.0 on every step.
+ * Both: done_out = terminated or t + 1 >= max_episode_steps; a finished environment draws its next start state and sets
+ * t = 0 in the same launch, so obs_out already shows the next episode's first observation.  fp64, operation by
+ * operation, no fused multiply-add; sin and cos are the device library's, so a stepped state equals a host libm's to
+ * the last bits only (measured: profiles/env_device.txt).  mzs_env_step_args is the cart-pole's, obs_out [N, 6] or
+ * [N, 2].  One launch per call, one thread per environment, on the caller's stream; no allocation, no copy to the
+ * host, no synchronisation.  MZS_E_INVALID before any launch, nothing written, for a struct size, an unknown kind, a
+ * null pointer, num_envs < 1, max_episode_steps < 1, a state that is not 16-byte aligned or an obs_out that is not
+ * 8-BYTE aligned (obs is stored two floats at a time for both kinds).  errors: mzs_last_error(NULL) */
+#define MZS_ENV_ACROBOT 1
+#define MZS_ENV_MOUNTAINCAR 2
+typedef struct mzs_env_classic {
+  int32_t struct_size;       /* = sizeof(mzs_env_classic) */
+  int32_t device;
+  int32_t kind;              /* MZS_ENV_ACROBOT or MZS_ENV_MOUNTAINCAR */
+  int32_t num_envs;          /* N */
+  int32_t max_episode_steps;
+  uint32_t key[2];
+  double *state;             /* [N, 4] or [N, 2] */
+  int32_t *t;                /* [N] steps of the open episode */
+  int32_t *draws;            /* [N] start states drawn so far */
+} mzs_env_classic;
+int mzs_env_classic_reset(const mzs_env_classic *env, float *obs_out, void *stream);
+int mzs_env_classic_step(const mzs_env_classic *env, const mzs_env_step_args *a, void *stream);
+
 /* ---- forward value unroll of the default MLP trio: the priorities mzs_replay_update_priorities takes ----
  * For every window j < batch and step i < k_prio, with s_0 = Representation(obs[j]) and s_{i+1} = the next state of
  * Dynamic(s_i, actions[j][i]) (muax/nn.py:59-115):

@@ -10,7 +10,7 @@ from .episode_tracer import NStep, PNStep  # noqa: F401
 from .replay_buffer import Trajectory, TrajectoryReplayBuffer  # noqa: F401
 from .replay_device import DeviceReplayBuffer  # noqa: F401
 from . import envs  # noqa: F401
-from .envs import DeviceCartPole  # noqa: F401
+from .envs import DeviceAcrobot, DeviceCartPole, DeviceMountainCar  # noqa: F401
 from .loss import Transition, default_loss_fn  # noqa: F401
 from .model import MuZero  # noqa: F401
 from .nn import MZNetwork, MZNetworkParams, create_muzero_network  # noqa: F401
@@ -18,7 +18,7 @@ from .policy import GumbelMuZeroPolicy, MuZeroPolicy, Policy, StochasticMuZeroPo
 from .search import MuZeroSearch, PolicyOutput, SearchConfig, SearchTree, key_words  # noqa: F401
 from .sharding import allreduce_mean_flat, gather_roots, shard_roots  # noqa: F401
 from .vector import (DeviceVectorCollector, VectorCollector, episode_trajectory, fit_vector, nstep_returns,  # noqa: F401
-                     ring_plan, test_vector)
+                     ring_plan, test_vector, test_vector_device)
 from .train import _temperature_fn, collect_batched, fit, fit_batched, rollout, rollout_batched, test  # noqa: F401
 
 __version__ = "0.1.0"

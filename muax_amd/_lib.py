@@ -205,6 +205,15 @@ class MzsEnvStepArgs(C.Structure):
                 + [(n, _vp) for n in ("a", "obs_out", "r_out", "done_out")])
 
 
+MZS_ENV_ACROBOT, MZS_ENV_MOUNTAINCAR = 1, 2
+
+
+class MzsEnvClassic(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("device", C.c_int32), ("kind", C.c_int32), ("num_envs", C.c_int32),
+                 ("max_episode_steps", C.c_int32), ("key", C.c_uint32 * 2)]
+                + [(n, _vp) for n in ("state", "t", "draws")])
+
+
 class MzsUnrollArgs(C.Structure):
     _fields_ = ([("struct_size", C.c_int32), ("device", C.c_int32), ("batch", C.c_int32), ("row_steps", C.c_int32),
                  ("k_prio", C.c_int32), ("num_actions", C.c_int32), ("embed_dim", C.c_int32), ("reserved0", C.c_int32)]
@@ -236,7 +245,8 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_replay_gather_obs", "mzs_replay_reanalyse", "mzs_replay_update_priorities",
                     "mzs_mlp_unroll_values", "mzs_replay_sample_is", "mzs_mlp_loss_grad_weighted",
                     "mzs_replay_stage", "mzs_replay_store_steps", "mzs_replay_plan_steps",
-                    "mzs_env_cartpole_reset", "mzs_env_cartpole_step"]
+                    "mzs_env_cartpole_reset", "mzs_env_cartpole_step",
+                    "mzs_env_classic_reset", "mzs_env_classic_step"]
 
 _lib = None
 
@@ -317,6 +327,8 @@ def load(build_if_missing: bool = True):
     L.mzs_replay_plan_steps.argtypes = [C.POINTER(MzsReplayRing), C.POINTER(MzsReplayPlanArgs), _vp]
     L.mzs_env_cartpole_reset.argtypes = [C.POINTER(MzsEnvCartPole), _vp, _vp]
     L.mzs_env_cartpole_step.argtypes = [C.POINTER(MzsEnvCartPole), C.POINTER(MzsEnvStepArgs), _vp]
+    L.mzs_env_classic_reset.argtypes = [C.POINTER(MzsEnvClassic), _vp, _vp]
+    L.mzs_env_classic_step.argtypes = [C.POINTER(MzsEnvClassic), C.POINTER(MzsEnvStepArgs), _vp]
     L.mzs_mlp_unroll_values.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsUnrollArgs), _vp]
     L.mzs_tower_pair_scratch_bytes.restype = C.c_int64
     if L.mzs_abi_version() != 1:

@@ -8,7 +8,8 @@ when it has
                                              device views the step writes; obs: the next observations, device tensor
     n, spec.max_episode_steps, device
 
-with the conventions of the host protocol (muax_amd/vector.py): `done` marks the LAST step of an episode and the
+(`DeviceAcrobot` and `DeviceMountainCar` also expose `obs_dim` and `num_actions`) with the conventions of the host
+protocol (muax_amd/vector.py): `done` marks the LAST step of an episode and the
 returned observation of a finished environment is already the first one of its next episode.  Neither call may
 synchronise; both run on the current stream of `device`.  The returned tensor may be the environment's own and be
 overwritten by its next call: `DeviceVectorCollector` stages it in its ring before it steps again.
@@ -95,3 +96,84 @@ class DeviceCartPole:
         a = torch.from_numpy(np.ascontiguousarray(np.asarray(actions).reshape(-1), dtype=np.int32)).to(self.device)
         obs = self.step_device(a, self._r, self._done)
         return obs.cpu().numpy(), self._r.cpu().numpy(), self._done.cpu().numpy().astype(bool)
+
+
+class _DeviceClassic:
+    """What `DeviceAcrobot` and `DeviceMountainCar` share: the tensors of one `mzs_env_classic` descriptor and both
+    protocols on `mzs_env_classic_reset` / `mzs_env_classic_step`.  A subclass names its `_KIND` (the C ABI's constant, by name), `_ID`,
+    `_STATE_DIM`, `obs_dim` and `num_actions`."""
+    _KIND = _ID = _STATE_DIM = obs_dim = num_actions = None
+
+    def __init__(self, n, max_episode_steps, seed=0, device=None):
+        import torch
+
+        from . import _lib
+        name = type(self).__name__
+        self.n = int(n)
+        if self.n < 1 or int(max_episode_steps) < 1:
+            raise ValueError(f"{name}: n and max_episode_steps must be at least 1")
+        self.spec = SimpleNamespace(id=self._ID, max_episode_steps=int(max_episode_steps))
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"{name}: needs a GPU device")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._L = _lib.load()
+        dev = self.device
+        self._state = torch.zeros((self.n, self._STATE_DIM), dtype=torch.float64, device=dev)
+        self._t = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self._draws = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self._obs = torch.zeros((self.n, self.obs_dim), dtype=torch.float32, device=dev)
+        self._r = torch.zeros(self.n, dtype=torch.float64, device=dev)      # the host protocol's outputs
+        self._done = torch.zeros(self.n, dtype=torch.uint8, device=dev)
+        key = prng.PRNGKey(seed)
+        self._env = _lib.args(_lib.MzsEnvClassic, device=dev.index, kind=getattr(_lib, self._KIND), num_envs=self.n,
+                              max_episode_steps=self.spec.max_episode_steps, key=(int(key[0]), int(key[1])),
+                              state=self._state.data_ptr(), t=self._t.data_ptr(), draws=self._draws.data_ptr())
+
+    _stream = DeviceCartPole._stream
+    _view = DeviceCartPole._view
+
+    # ---- the device protocol
+    def reset_device(self):
+        from . import _lib
+        _lib.check(self._L.mzs_env_classic_reset(C.byref(self._env), self._obs.data_ptr(), self._stream()))
+        return self._obs
+
+    def step_device(self, a, r_out, done_out):
+        import torch
+
+        from . import _lib
+        s = _lib.args(_lib.MzsEnvStepArgs)  # (per step: fields by attribute, which is 1 us cheaper)
+        s.a = self._view(a, torch.int32, "a")
+        s.r_out, s.done_out = self._view(r_out, torch.float64, "r_out"), self._view(done_out, torch.uint8, "done_out")
+        s.obs_out = self._obs.data_ptr()
+        _lib.check(self._L.mzs_env_classic_step(C.byref(self._env), C.byref(s), self._stream()))
+        return self._obs
+
+    # ---- the host protocol
+    reset = DeviceCartPole.reset
+    step = DeviceCartPole.step
+
+
+class DeviceAcrobot(_DeviceClassic):
+    """N Acrobots (Gym's Acrobot-v1: Sutton & Barto's "book" equations, one Runge-Kutta step of 0.2 s per action) on the
+    device, one launch per step (`mzs_env_classic_step`), auto-reset inside that launch.  Three actions (torque -1, 0,
+    +1), observations (cos th1, sin th1, cos th2, sin th2, dth1, dth2), reward -1 per step and 0 on the step that
+    swings the tip above the bar.  Start states: environment e's d-th draw of component c is
+    `-0.1 + 0.2 * u53(PRNGKey(seed), e, 4 d + c)`.  Both protocols, as `DeviceCartPole`."""
+    _KIND, _ID, _STATE_DIM, obs_dim, num_actions = "MZS_ENV_ACROBOT", "Acrobot-v1", 4, 6, 3
+
+    def __init__(self, n, max_episode_steps=500, seed=0, device=None):
+        super().__init__(n, max_episode_steps, seed, device)
+
+
+class DeviceMountainCar(_DeviceClassic):
+    """N mountain cars (Gym's MountainCar-v0 in fp64) on the device, one launch per step (`mzs_env_classic_step`),
+    auto-reset inside that launch.  Three actions (push left, none, right), observations (x, v), reward -1 per step;
+    an episode ends at x >= 0.5 with v >= 0.  Start states: environment e's d-th draw is
+    x = `-0.6 + 0.2 * u53(PRNGKey(seed), e, d)`, v = 0.  Both protocols, as `DeviceCartPole`."""
+    _KIND, _ID, _STATE_DIM, obs_dim, num_actions = "MZS_ENV_MOUNTAINCAR", "MountainCar-v0", 2, 2, 3
+
+    def __init__(self, n, max_episode_steps=200, seed=0, device=None):
+        super().__init__(n, max_episode_steps, seed, device)

@@ -408,6 +408,38 @@ def test_vector(model, venv, key, num_simulations: int, max_steps=None):
     return float(G.mean())
 
 
+def test_vector_device(model, venv, key, num_simulations: int, max_steps=None):
+    """`test_vector` on a device environment (muax_amd/envs.py) without leaving the device: `reset_device` /
+    `step_device`, act() on the environment's observation tensor with device outputs, the returns `G` [N] and the mask
+    of the environments still in their first episode kept as device tensors.  Nothing inside the loop copies to the
+    host or synchronises except the "all finished" check, made after every 16th step only (the steps in between add
+    0.0 to every return: the value does not depend on when the loop stops).  At the end `G` comes down once and its mean
+    is taken on the host: the key stream, the fp64 additions and the mean are `test_vector`'s, so the value is
+    `test_vector(model, venv, key, ...)`'s exactly."""
+    import torch
+    if not hasattr(venv, "step_device"):
+        raise ValueError(f"test_vector_device needs a device environment (one with step_device); "
+                         f"{type(venv).__name__} has none: use test_vector")
+    obs = venv.reset_device()
+    N, dev = int(venv.n), obs.device
+    G = torch.zeros(N, dtype=torch.float64, device=dev)
+    live = torch.ones(N, dtype=torch.bool, device=dev)
+    r = torch.zeros(N, dtype=torch.float64, device=dev)
+    done = torch.zeros(N, dtype=torch.uint8, device=dev)
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    steps = max_steps if max_steps is not None else venv.spec.max_episode_steps
+    for i in range(steps):
+        key, subkey = prng.split(key)
+        a = model.act(subkey, obs, obs_from_batch=True, device_outputs=True, num_simulations=num_simulations,
+                      temperature=0.)
+        obs = venv.step_device(a.to(torch.int32).contiguous(), r, done)
+        G += torch.where(live, r, zero)
+        live &= done == 0
+        if i % 16 == 15 and not bool(live.any()):  # (the loop's one synchronisation, every 16th step)
+            break
+    return float(G.cpu().numpy().mean())
+
+
 def value_priorities(model, batch):
     """New priorities of a sampled batch from the CURRENT network: |value(repr(obs[:, 0])) - Rn[:, 0]| as [B] float32
     on the model's device -- the value error of every window's first transition, the one whose weight decided the
@@ -471,7 +503,8 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     result are unchanged.
     A `venv` with `step_device` (a device environment, muax_amd/envs.py) is stepped on the device by that collector;
     it needs `device_collect=True` and a buffer with the device store, and is a ValueError otherwise: stepping it
-    through host copies would hide the cost it exists to avoid.  `test_env` stays a host-protocol environment.
+    through host copies would hide the cost it exists to avoid.  A `test_env` with `step_device` is evaluated by
+    `test_vector_device` (no host hop per step), any other vector environment by `test_vector`; the value is the same.
     `device_plan=True` (needs `device_collect=True` and a device environment; a ValueError otherwise) hands the flag to
     that collector: the episodes are cut and their returns summed on the device (`DeviceVectorCollector`), `G` of the
     metrics row is then the mean of sequential fp64 sums -- equal to the host's for integer rewards.  False: the key
@@ -566,6 +599,8 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
             if hasattr(test_env, "observation_space"):  # a gym-style environment: the reference's test()
                 row["test_G"] = test(model, test_env, test_key, num_simulations=num_simulations,
                                      num_test_episodes=num_test_episodes)
+            elif hasattr(test_env, "step_device"):  # a device environment: evaluated where it lives, the same value
+                row["test_G"] = test_vector_device(model, test_env, test_key, num_simulations)
             else:  # a vector environment: all its episodes in lock step
                 row["test_G"] = test_vector(model, test_env, test_key, num_simulations)
         if metrics is not None:

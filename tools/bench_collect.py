@@ -18,7 +18,13 @@ trio and 50 simulations per step:
   dev plan the same collector with `device_plan=True`: the episodes are cut and their returns summed on the device
           (`mzs_replay_plan_steps`); per collect the counts and one row per finished episode come down.
 
+  with --env acrobot or --env mountaincar (default cartpole: everything above, unchanged) the device-environment
+  columns run on `muax_amd.DeviceAcrobot` / `DeviceMountainCar` (3 actions, 6 / 2 observations) and, there being no host
+  implementation of them, the host and device columns step a second instance of the same class through its HOST
+  protocol (three synchronising copies per step), which is what a user without the device route would do.
+
     python tools/bench_collect.py [--iters 20] [--shape ENVS,STEPS ...] [--simulations 50] [--device-env] [--device-plan]
+                                  [--env cartpole|acrobot|mountaincar]
 
 Every figure is the median of `--iters` repetitions of one whole collect (+ add), each ending in a device synchronise,
 after three untimed ones.  The two routes alternate shape by shape in one process; each keeps its own environment,
@@ -39,14 +45,18 @@ from cartpole_env import VectorCartPole  # noqa: E402
 from muax_amd.utils import warm_runtime  # noqa: E402
 
 A, E, OBS, SUPPORT, N_STEP, GAMMA, ALPHA, K = 2, 8, 4, 10, 10, 0.997, 0.5, 10
+# --env: (actions, observations, host-protocol environment, device environment)
+ENVS = {"cartpole": (A, OBS, lambda n: VectorCartPole(n, seed=0), lambda n: mx.DeviceCartPole(n, seed=0)),
+        "acrobot": (3, 6, lambda n: mx.DeviceAcrobot(n, seed=0), lambda n: mx.DeviceAcrobot(n, seed=0)),
+        "mountaincar": (3, 2, lambda n: mx.DeviceMountainCar(n, seed=0), lambda n: mx.DeviceMountainCar(n, seed=0))}
 
 
-def model():
+def model(actions=A, obs_dim=OBS):
     g = torch.Generator().manual_seed(0)
-    net = mx.nn.MZNetwork(mx.nn.Representation(E, generator=g), mx.nn.Prediction(A, 2 * SUPPORT + 1, generator=g),
-                          mx.nn.Dynamic(E, A, 2 * SUPPORT + 1, generator=g))
+    net = mx.nn.MZNetwork(mx.nn.Representation(E, generator=g), mx.nn.Prediction(actions, 2 * SUPPORT + 1, generator=g),
+                          mx.nn.Dynamic(E, actions, 2 * SUPPORT + 1, generator=g))
     m = mx.MuZero(net, support_size=SUPPORT)
-    m.init(0, np.zeros((1, OBS)))
+    m.init(0, np.zeros((1, obs_dim)))
     return m
 
 
@@ -134,22 +144,25 @@ def main():
     ap.add_argument("--device-env", action="store_true", help="also time collection on DeviceCartPole and act() alone")
     ap.add_argument("--device-plan", action="store_true",
                     help="also time collection on DeviceCartPole with the episodes cut on the device (device_plan=True)")
+    ap.add_argument("--env", default="cartpole", choices=list(ENVS),
+                    help="the environment; acrobot and mountaincar run the host columns on the device class's host protocol")
     a = ap.parse_args()
+    actions, obs_dim, host_env, device_env = ENVS[a.env]
     shapes = [tuple(int(x) for x in s.split(",")) for s in a.shape] or [(64, 64), (1024, 64)]
     warm_runtime()
-    print(f"vector CartPole, {a.simulations} simulations, n_step {N_STEP}, episodes of at least {K} steps stored; "
+    print(f"vector {'CartPole' if a.env == 'cartpole' else a.env}, {a.simulations} simulations, n_step {N_STEP}, episodes of at least {K} steps stored; "
           f"median of {a.iters} synchronised repetitions, ms")
     print(f"{'envs x steps':>12} | {'host collect':>12} {'host collect+add_many':>21} | {'device collect (incl. add)':>26} | "
           f"{'host / device':>13}" + (f" | {'dev env collect (incl. add)':>27} {'steps x act()':>13}" if a.device_env else "")
           + (f" | {'dev plan collect (incl. add)':>28}" if a.device_plan else ""))
     for envs, steps in shapes:
-        m = model()
+        m = model(actions, obs_dim)
         state = {"hk": mx.prng.PRNGKey(0), "dk": mx.prng.PRNGKey(0)}
         cap, rows = 8 * envs, 8 * envs * steps + 4096
         host_buf, dev_buf = mx.DeviceReplayBuffer(cap, rows), mx.DeviceReplayBuffer(cap, rows)
-        host = mx.VectorCollector(VectorCartPole(envs, seed=0), N_STEP, GAMMA, ALPHA)
-        host_only = mx.VectorCollector(VectorCartPole(envs, seed=0), N_STEP, GAMMA, ALPHA)
-        dev = mx.DeviceVectorCollector(VectorCartPole(envs, seed=0), dev_buf, N_STEP, GAMMA, ALPHA, min_length=K)
+        host = mx.VectorCollector(host_env(envs), N_STEP, GAMMA, ALPHA)
+        host_only = mx.VectorCollector(host_env(envs), N_STEP, GAMMA, ALPHA)
+        dev = mx.DeviceVectorCollector(host_env(envs), dev_buf, N_STEP, GAMMA, ALPHA, min_length=K)
 
         def host_collect():
             _, state["hk"], _ = host_only.collect(m, state["hk"], steps, a.simulations)
@@ -168,9 +181,9 @@ def main():
         line = f"{envs:>7} x {steps:<2} | {hc:12.3f} {hr:21.3f} | {dr:26.3f} | {hr / dr:12.2f}x"
         if a.device_env:
             env_buf = mx.DeviceReplayBuffer(cap, rows)
-            env_dev = mx.DeviceVectorCollector(mx.DeviceCartPole(envs, seed=0), env_buf, N_STEP, GAMMA, ALPHA, min_length=K)
+            env_dev = mx.DeviceVectorCollector(device_env(envs), env_buf, N_STEP, GAMMA, ALPHA, min_length=K)
             state["ek"] = state["ak"] = mx.prng.PRNGKey(0)
-            fixed = torch.from_numpy(VectorCartPole(envs, seed=0).reset()).to(m.device)
+            fixed = torch.from_numpy(host_env(envs).reset()).to(m.device)
 
             def env_route():
                 _, state["ek"], _ = env_dev.collect(m, state["ek"], steps, a.simulations)
@@ -184,7 +197,7 @@ def main():
             line += f" | {median_ms(env_route, a.iters):27.3f} {median_ms(act_alone, a.iters):13.3f}"
         if a.device_plan:
             plan_buf = mx.DeviceReplayBuffer(cap, rows)
-            plan_dev = mx.DeviceVectorCollector(mx.DeviceCartPole(envs, seed=0), plan_buf, N_STEP, GAMMA, ALPHA,
+            plan_dev = mx.DeviceVectorCollector(device_env(envs), plan_buf, N_STEP, GAMMA, ALPHA,
                                                 min_length=K, device_plan=True)
             state["pk"] = mx.prng.PRNGKey(0)
 
