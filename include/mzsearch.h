@@ -518,6 +518,9 @@ int mzs_mlp_wide_plan_policy(int32_t num_actions, int32_t embed_dim, int32_t sup
  * simulation's values afterwards) of mzs_tower_args; `x`, `y`, `action` are ignored.  `pair_scratch` != NULL: two
  * workgroups per root (batch <= 128), as for mzs_resnet_tower -- check the status words afterwards and repeat the
  * search without it if any is set.  `discount`: the constant muax's recurrent_fn returns (muax/model.py:274).
+ * Discount contract: every edge already expanded on the handle must carry the same `discount` as the argument.  The LDS
+ * tree build does not store per-edge discounts and applies the argument to existing edges; a tree continued from
+ * mzs_expand_backup[_select] calls with other discounts gives results that depend on MZS_SEARCH_LDS_TREE.
  * The handle's embed_dim must be 2304 (6 x 6 x 64) and its tree must use cached decisions (the default whenever
  * batch * (num_simulations + 1)^2 words fit 1 GiB).  Errors: mzs_last_error(h). */
 int mzs_resnet_search(mzs_handle *h, const mzs_tower_args *a, float discount, int32_t sim_begin, int32_t sim_end,

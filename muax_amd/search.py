@@ -488,7 +488,10 @@ class MuZeroSearch:
         `native_loop(handle, sim_begin, sim_end)`: nets whose recurrent_fn the library evaluates itself (the reference's
         ResNet nets: ResNetDynamic.hip_search -> mzs_resnet_search) run the WHOLE simulation loop as one launch -- every
         root advanced by its own workgroup(s), recurrent_fn and the tree update back to back, no per-simulation launch
-        and no row copies; `recurrent_fn` is then only the fall-back (a tree without cached decisions)."""
+        and no row copies; `recurrent_fn` is then only the fall-back (a tree without cached decisions).  Every edge already
+        expanded on the handle must carry the same discount as mzs_resnet_search's `discount` argument: the LDS tree
+        build does not store per-edge discounts and applies the argument to existing edges, so a tree continued from
+        expand_backup[_select] calls with other discounts gives results that depend on MZS_SEARCH_LDS_TREE."""
         prior_logits, value, embedding = root_fn_output
 
         def do_root():

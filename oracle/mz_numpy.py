@@ -153,7 +153,8 @@ def _select(tree, node, depth, pb_c_init, pb_c_base, noise, rows):
     inv = tree.root_invalid_actions[rows].astype(bool) & (depth[rows] == 0)[:, None]
     score = np.where(inv, -np.inf, score)
     srt = np.sort(score, axis=-1)
-    margin = srt[:, -1] - srt[:, -2] if score.shape[1] > 1 else np.full(len(rows), np.inf)
+    with np.errstate(invalid="ignore"):  # (-inf) - (-inf) = nan: a root with every action masked reports no margin
+        margin = srt[:, -1] - srt[:, -2] if score.shape[1] > 1 else np.full(len(rows), np.inf)
     return score.argmax(axis=-1).astype(np.int32), margin
 
 
@@ -309,8 +310,11 @@ def _score_considered(considered_visit, gumbel, logits, qv, vc):
     return np.maximum(-1e9, gumbel + logits + qv) + penalty
 
 
-def gumbel_search(tree, recurrent_fn, S, root_gumbel, max_considered=16, qtransform="mix", max_depth=None):
-    """mctx search with gumbel_muzero_{root,interior}_action_selection. Returns depth_sum."""
+def gumbel_search(tree, recurrent_fn, S, root_gumbel, max_considered=16, qtransform="mix", max_depth=None,
+                  min_margin=None):
+    """mctx search with gumbel_muzero_{root,interior}_action_selection. Returns depth_sum.
+    `min_margin` [B] (float64, start it at +inf): lowered in place to the smallest top1-top2 score margin of any
+    selection of the root's search, as `search` reports it (nan for a root with every action masked)."""
     B, A = tree.B, tree.A
     qt = qtransform_completed_by_mix_value if qtransform == "mix" else qtransform_by_parent_and_siblings
     max_depth = S if not max_depth or max_depth <= 0 else max_depth
@@ -340,6 +344,11 @@ def gumbel_search(tree, recurrent_fn, S, root_gumbel, max_considered=16, qtransf
                 probs = softmax(logits + qv)
                 score = probs - vc / (1 + vc.sum(-1, keepdims=True))
             a = score.argmax(-1).astype(np.int32)
+            if min_margin is not None and A > 1:
+                srt = np.sort(score, axis=-1)
+                with np.errstate(invalid="ignore"):  # (-inf) - (-inf) = nan: as in _select, such a root reports no margin
+                    m = srt[:, -1] - srt[:, -2]
+                min_margin[rows] = np.minimum(min_margin[rows], m)
             parent[rows] = n
             action[rows] = a
             nxt = tree.children_index[rows, n, a]

@@ -333,39 +333,16 @@ def test_error_behaviour():
 # ---------------------------------------------------------------- edge cases of the domain
 
 def _stepwise_vs_oracle(oracle, case, S, tiebreak, max_depth=None, key=(4, 5), fused_select=False):
-    """Drive the step-wise kernels and the oracle with the same (torch) net outputs; compare everything.
+    """Drive the step-wise kernels and the oracle with the same (torch) net outputs; compare everything (the loop is
+    scripted_search.drive_hip, shared with the scripted tests).
     fused_select: mzs_expand_backup_select (the next selection in the expand + backward launch) instead of two calls."""
-    from muax_amd import MuZeroSearch, SearchConfig
+    from scripted_search import drive_hip
     B, A, E = case["B"], case["A"], case["E"]
     root, rec = _torch_recurrent(case)
-    obs = torch.from_numpy(case["obs"]).cuda()
-    pl, v, emb = root(obs)
-    s = MuZeroSearch(B, SearchConfig(A, S, E, tiebreak=tiebreak, max_depth=max_depth))
-    inv = None if case["invalid"] is None else torch.from_numpy(case["invalid"])
-    s.root(pl, v, emb, list(key), inv, torch.from_numpy(case["noise"]), 0.25)
-    tree = oracle.Tree(B, S + 1, A, E)
-    cfg = oracle.SearchCfg(S, tiebreak=int(tiebreak), max_depth=max_depth or 0)
-    oracle.tree_init(tree, oracle.root_prior(pl.cpu().numpy(), case["noise"], 0.25, case["invalid"]),
-                     v.cpu().numpy(), emb.cpu().numpy(), case["invalid"])
-    k_sample, _, sims = oracle.sim_keys_from_act_key(list(key), S)
-    nxt = None
-    for sim in range(S):
-        action, pemb = nxt if fused_select and sim > 0 else s.select(sim)
-        p_ref, a_ref, _ = oracle.step_select(tree, cfg, sim, sims[sim])
-        assert np.array_equal(a_ref, action.cpu().numpy()), sim
-        outs = rec(action, pemb)
-        if fused_select:
-            nxt = s.expand_backup_select(sim, *outs)
-        else:
-            s.expand_backup(sim, *outs)
-        oracle.step_expand_backup(tree, sim, p_ref, a_ref, *[o.cpu().numpy() for o in outs])
-    out = s.finish(1.0, None, with_tree=True)
-    g = oracle.gumbel(k_sample, B * A).reshape(B, A)
-    a_ref, w_ref = oracle.summary_sample(tree, 1.0, g)
-    assert np.array_equal(a_ref, out.action.cpu().numpy())
-    assert np.array_equal(w_ref, out.action_weights.cpu().numpy())
-    assert_trees_equal(tree, out.search_tree, exact_floats=True)
-    return tree
+    res = drive_hip(oracle, B, A, E, S, root(torch.from_numpy(case["obs"]).cuda()), lambda sim, action, pemb: rec(action, pemb),
+                    tiebreak=tiebreak, max_depth=max_depth, key=key, invalid=case["invalid"], noise=case["noise"],
+                    fused_select=fused_select)
+    return res["tree"]
 
 
 def test_single_action_and_single_simulation(oracle):
