@@ -25,7 +25,7 @@ _HANDLE = ["mz_handle.h", "mz_host.h", "mz_keys.h", "mz_step.cuh", "mz_step_jump
 UNITS = {
     "mz_api.hip": _HANDLE + ["mz_fused_launch.h", "mz_fused.cuh"],
     "mz_act.hip": _HANDLE + ["mz_fused_launch.h", "mz_fused.cuh", "mz_wide_launch.h"],
-    "mz_stepwise.hip": _HANDLE + ["mz_mlp_generic.cuh"],
+    "mz_stepwise.hip": _HANDLE + ["mz_mlp_generic.cuh", "mz_step_kernels.cuh"],
     "mz_train.hip": ["mz_host.h", "mz_train_launch.h", "mz_train.cuh", "mz_spec.cuh", _ABI],
     "mz_selftest.hip": ["mz_host.h", "mz_dirichlet.cuh", "mz_spec.cuh", _ABI],
     "mz_fused_g0.hip": _FUSED,

@@ -5,7 +5,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#define MZ_NO_STEP_KERNELS  // (types of the step-wise path only: its kernels live in mz_stepwise.hip)
 #include "mz_handle.h"
 #include "mz_fused_launch.h"
 #include "mz_wide_launch.h"

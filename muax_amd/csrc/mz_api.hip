@@ -6,7 +6,6 @@
 #include <cstring>
 #include <mutex>
 
-#define MZ_NO_STEP_KERNELS  // (types of the step-wise path only: its kernels live in mz_stepwise.hip)
 #include "mz_handle.h"
 #include "mz_fused_launch.h"
 

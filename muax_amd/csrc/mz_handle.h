@@ -1,6 +1,6 @@
 // mz_handle.h -- the handle behind the C-ABI and the host helpers its routes share (not part of the ABI): mz_api.hip,
-// mz_act.hip, mz_stepwise.hip.  Every includer but mz_stepwise.hip defines MZ_NO_STEP_KERNELS first: the non-template
-// kernels of mz_step.cuh are emitted by that unit alone.
+// mz_act.hip, mz_stepwise.hip.  (Types and device functions of the step-wise path only: its kernels are in
+// mz_step_kernels.cuh, which mz_stepwise.hip alone includes.)
 #pragma once
 #include <string>
 #include <vector>

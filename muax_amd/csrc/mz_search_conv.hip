@@ -23,8 +23,7 @@
 
 #include <cstdlib>
 
-#define MZ_NO_STEP_KERNELS   // device functions and types of the step-wise path only: its kernels live in mz_stepwise.hip,
-#define MZ_NO_TOWER_KERNELS  // the recurrent kernel's in mz_conv.hip
+#define MZ_NO_TOWER_KERNELS  // (the recurrent kernel lives in mz_conv.hip)
 #include "mz_conv_host.h"
 #include "mz_step_jump.cuh"
 

@@ -4,6 +4,11 @@
 // recurrent_fn (mctx search.expand).  The tree lives in HBM in mctx's own
 // layout so that PolicyOutput.search_tree is a plain copy.  Same row mapping
 // and arithmetic spec as the fused kernel; A and E are run-time (A <= 64).
+//
+// This header: the types and the per-node device functions BOTH sets of tree
+// kernels share (every rule of the search is stated here once).  The cached-
+// decision bodies are in mz_step_jump.cuh, every __global__ of the path in
+// mz_step_kernels.cuh (included by mz_stepwise.hip alone).
 #pragma once
 #include "../../include/mzsearch.h"
 #include "mz_spec.cuh"
@@ -128,375 +133,6 @@ MZ_DEV void row_softmax_rt(const float (&x)[kMaxAS], int A, int j, float (&p)[kM
   for (int t = 0; t < kMaxAS; ++t) p[t] = e[t] / s;
 }
 
-#define MZ_ROW_SETUP                                              \
-  const int lane = threadIdx.x & 63;                              \
-  const int j = lane & 15;                                        \
-  const int r = blockIdx.x * (blockDim.x >> 4) + (threadIdx.x >> 4);  \
-  if (r >= s.B) return;                                           \
-  const int N = s.N, A = s.A, E = s.E;                            \
-  const size_t rb = (size_t)r * N;
-
-// mctx instantiate_tree_from_root + muzero_policy prelude (dirichlet, mask)
-#ifndef MZ_NO_STEP_KERNELS
-__global__ __launch_bounds__(256) void step_root_kernel(StepArgs s, const float* prior_logits,
-                                                         const float* value, const float* embedding,
-                                                         const uint8_t* invalid, const float* noise,
-                                                         float fraction, int gumbel_policy,
-                                                         const float* gumbel_in, uint32_t gk0, uint32_t gk1) {
-  MZ_ROW_SETUP
-  for (int n = j; n < N; n += 16) {
-    s.node_visits[rb + n] = 0;
-    s.raw_values[rb + n] = 0.0f;
-    s.node_values[rb + n] = 0.0f;
-    s.parents[rb + n] = -1;
-    s.action_from_parent[rb + n] = -1;
-  }
-  for (int i = j; i < N * A; i += 16) {
-    size_t o = rb * A + i;
-    s.children_index[o] = -1;
-    s.children_prior_logits[o] = 0.0f;
-    s.children_prior_probs[o] = 0.0f;
-    s.children_values[o] = 0.0f;
-    s.children_visits[o] = 0;
-    s.children_rewards[o] = 0.0f;
-    s.children_discounts[o] = 0.0f;
-  }
-  if (!s.wide)  // (wide: zeroed by a memset on the stream)
-    for (size_t i = j; i < (size_t)N * E; i += 16) s.embeddings[rb * E + i] = 0.0f;
-  float x[kMaxAS], pr[kMaxAS], lg[kMaxAS];
-  bool inv[kMaxAS];
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    int a = j + 16 * t;
-    x[t] = a < A ? prior_logits[(size_t)r * A + a] : 0.0f;
-    inv[t] = (invalid != nullptr && a < A) ? invalid[(size_t)r * A + a] != 0 : false;
-    if (a < A) s.root_invalid[(size_t)r * A + a] = inv[t] ? 1 : 0;
-  }
-  float mx = -INFINITY;
-  bool any_invalid = false;
-  if (!gumbel_policy) {
-    // mctx muzero_policy prelude: Dirichlet mix, log
-    row_softmax_rt(x, A, j, pr);
-    float keep = 1.0f - fraction;
-#pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) {
-      int a = j + 16 * t;
-      float nz = (noise != nullptr && a < A) ? noise[(size_t)r * A + a] : 0.0f;
-      float noisy = keep * pr[t] + fraction * nz;
-      lg[t] = log_pos(fmaxf(noisy, kFltTiny));
-      mx = a < A ? fmaxf(mx, lg[t]) : mx;
-    }
-    any_invalid = invalid != nullptr;
-  } else {
-    // mctx gumbel_muzero_policy: the logits only pass through _mask_invalid_actions; root Gumbel noise
-    const uint64_t rg = s.root_offset + (uint64_t)r;
-#pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) {
-      int a = j + 16 * t;
-      lg[t] = x[t];
-      mx = a < A ? fmaxf(mx, lg[t]) : mx;
-      any_invalid = any_invalid || inv[t];
-      if (a < A) {
-        float g;
-        if (gumbel_in != nullptr) {
-          g = gumbel_in[(size_t)r * A + a];
-        } else {
-          uint32_t x0, x1;
-          bool second;
-          bits_block(s.global_batch * (uint64_t)A, rg * (uint64_t)A + (uint64_t)a, x0, x1, second);
-          threefry2x32(gk0, gk1, x0, x1);
-          g = s.gumbel_scale * gumbel_from_bits(second ? x1 : x0);
-        }
-        s.root_gumbel[(size_t)r * A + a] = g;
-      }
-    }
-    any_invalid = ((__builtin_amdgcn_ballot_w64(any_invalid) >> (lane & 48)) & 0xffffull) != 0;  // any lane of the row
-  }
-  if (any_invalid) {
-    mx = row_max<4>(mx);
-#pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) lg[t] = inv[t] ? kFltLowest : lg[t] - mx;
-  }
-  float pq[kMaxAS];
-  row_softmax_rt(lg, A, j, pq);
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    int a = j + 16 * t;
-    if (a < A) {
-      s.children_prior_logits[rb * A + a] = lg[t];
-      s.children_prior_probs[rb * A + a] = pq[t];
-    }
-  }
-  if (s.wide) {
-    if (j == 0) s.xfer_node[r] = 0;
-  } else {
-    for (int i = j; i < E; i += 16) s.embeddings[rb * E + i] = embedding[(size_t)r * E + i];
-  }
-  if (j == 0) {
-    s.node_visits[rb] = 1;
-    s.raw_values[rb] = value[r];
-    s.node_values[rb] = value[r];
-    s.depth_sum[r] = 0;
-  }
-}
-#endif  // MZ_NO_STEP_KERNELS
-
-// mctx search.simulate (+ the parent-embedding gather of search.expand)
-#ifndef MZ_NO_STEP_KERNELS
-__global__ __launch_bounds__(256) void step_select_kernel(StepArgs s, int sim, int32_t* action_out,
-                                                           float* parent_embedding_out) {
-  MZ_ROW_SETUP
-  const uint64_t rg = s.root_offset + (uint64_t)r;
-  uint32_t k0 = 0, k1 = 0;
-  if (s.tiebreak) {
-    uint32_t x0, x1;
-    bool second;
-    bits_block(2 * s.global_batch, 2 * rg + (uint64_t)(j & 1), x0, x1, second);
-    threefry2x32(s.sim_keys[2 * sim], s.sim_keys[2 * sim + 1], x0, x1);
-    uint32_t word = second ? x1 : x0;
-    k0 = bcast_u<0>(word);
-    k1 = bcast_u<1>(word);
-  }
-  const int NB = (A + 1) / 2;
-  int node = 0, depth = 0, parent = 0, action = 0;
-  for (;;) {
-    const size_t nb = (rb + node) * A;
-    int nvis = s.node_visits[rb + node];
-    float nval = s.node_values[rb + node];
-    float tn = puct_scale(nvis, s.pb_c_init, s.pb_c_base);
-    uint32_t s0 = 0, s1 = 0;
-    if (s.tiebreak) {
-      // rng_key, action_selection_key = split(rng_key)
-      uint32_t x0 = (uint32_t)(j & 1), x1 = 2u + (uint32_t)(j & 1);
-      threefry2x32(k0, k1, x0, x1);
-      k0 = bcast_u<0>(x0); k1 = bcast_u<1>(x0);
-      s0 = bcast_u<0>(x1); s1 = bcast_u<1>(x1);
-    }
-    float q[kMaxAS];
-    int cidx[kMaxAS], cvis[kMaxAS];
-    float prob[kMaxAS];
-    float lo = nval, hi = nval;
-#pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) {
-      int a = j + 16 * t;
-      bool ok = a < A;
-      cidx[t] = -1; cvis[t] = 0; prob[t] = 0.0f; q[t] = 0.0f;
-      if (16 * t < A) {  // (wave-uniform: slots past the action count cost nothing)
-        size_t o = nb + (ok ? a : 0);
-        cidx[t] = s.children_index[o];
-        cvis[t] = s.children_visits[o];
-        prob[t] = s.children_prior_probs[o];
-        q[t] = s.children_rewards[o] + s.children_discounts[o] * s.children_values[o];
-        float safe = (ok && cvis[t] > 0) ? q[t] : nval;
-        lo = fminf(lo, safe);
-        hi = fmaxf(hi, safe);
-      }
-    }
-    lo = row_min<4>(lo);
-    hi = row_max<4>(hi);
-    float span = fmaxf(hi - lo, 1e-8f);
-    float sc[kMaxAS];
-#pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) {
-      int a = j + 16 * t;
-      bool ok = a < A;
-      sc[t] = -INFINITY;
-      if (16 * t < A) {
-        float value_score = ((cvis[t] > 0 ? q[t] : lo) - lo) / span;
-        float policy_score = (tn * prob[t]) / (float)(cvis[t] + 1);
-        sc[t] = value_score + policy_score;
-        if (depth == 0 && ok && s.root_invalid[(size_t)r * A + a]) sc[t] = -INFINITY;
-        if (!ok) sc[t] = -INFINITY;
-      }
-    }
-    // mctx adds 1e-7 * uniform[0,1) to every score.  If fl(score_a + 1e-7) < best for every other action
-    // the argmax cannot depend on the draw (rounding is monotone): only waves that hold a near tie pay for
-    // the threefry blocks.  (-inf scores stay -inf with or without noise.)
-    float bscore = -INFINITY;
-    int best = 1 << 20, bnext = -1;
-#pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) {
-      int a = j + 16 * t;
-      bool take = (t == 0) || (sc[t] > bscore);  // first max wins inside the lane
-      if (take) { bscore = sc[t]; best = (a < A) ? a : (1 << 20); bnext = cidx[t]; }
-    }
-    row_argmax<4>(bscore, best, bnext);
-    bool need_noise = false;
-    if (s.tiebreak) {
-      bool unsafe = false;
-#pragma unroll
-      for (int t = 0; t < kMaxAS; ++t) {
-        int a = j + 16 * t;
-        unsafe = unsafe || (a < A && a != best && !((sc[t] + 1e-7f) < bscore));
-      }
-      need_noise = __any(unsafe);
-    }
-    if (need_noise) {
-      bscore = -INFINITY; best = 1 << 20; bnext = -1;
-#pragma unroll
-      for (int t = 0; t < kMaxAS; ++t) {
-        int a = j + 16 * t;
-        float score = sc[t];
-        if (16 * t < A) {
-          int jb = a < NB ? a : a - NB;
-          uint32_t x0 = (uint32_t)jb, x1 = (NB + jb < A) ? (uint32_t)(NB + jb) : 0u;
-          threefry2x32(s0, s1, x0, x1);
-          score = score + 1e-7f * uniform_from_bits(a < NB ? x0 : x1);
-        }
-        bool take = (t == 0) || (score > bscore);
-        if (take) { bscore = score; best = (a < A) ? a : (1 << 20); bnext = cidx[t]; }
-      }
-      row_argmax<4>(bscore, best, bnext);
-    }
-    row_argmax<4>(bscore, best, bnext);
-    if (j == 0) s.path[rb + depth] = node | (best << 16);
-    parent = node;
-    action = best;
-    depth += 1;
-    if (bnext == -1 || depth >= s.max_depth) break;
-    node = bnext;
-  }
-  if (j == 0) {
-    s.sel_parent[r] = parent;
-    s.sel_action[r] = action;
-    s.sel_depth[r] = depth;
-    s.depth_sum[r] += depth;
-    action_out[r] = action;
-  }
-  if (s.wide) {
-    if (j == 0) s.xfer_node[r] = parent;
-  } else {
-    const float* src = s.embeddings + (rb + parent) * E;
-    for (int i = j; i < E; i += 16) parent_embedding_out[(size_t)r * E + i] = src[i];
-  }
-}
-#endif  // MZ_NO_STEP_KERNELS
-
-// mctx search.expand (update_tree_node + edge) and search.backward
-#ifndef MZ_NO_STEP_KERNELS
-__global__ __launch_bounds__(256) void step_expand_backup_kernel(StepArgs s, int sim, const float* reward,
-                                                                  const float* discount,
-                                                                  const float* prior_logits,
-                                                                  const float* value,
-                                                                  const float* next_embedding) {
-  MZ_ROW_SETUP
-  const int parent = s.sel_parent[r], action = s.sel_action[r], depth = s.sel_depth[r];
-  const size_t eo = (rb + parent) * A + action;
-  int next = s.children_index[eo];
-  const int newn = next == -1 ? sim + 1 : next;
-  const float v = value[r];
-  float x[kMaxAS], pr[kMaxAS];
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    int a = j + 16 * t;
-    x[t] = a < A ? prior_logits[(size_t)r * A + a] : 0.0f;
-  }
-  row_softmax_rt(x, A, j, pr);
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    int a = j + 16 * t;
-    if (a < A) {
-      s.children_prior_logits[(rb + newn) * A + a] = x[t];
-      s.children_prior_probs[(rb + newn) * A + a] = pr[t];
-    }
-  }
-  if (s.wide) {
-    if (j == 0) s.xfer_node[r] = newn;
-  } else {
-    for (int i = j; i < E; i += 16) s.embeddings[(rb + newn) * E + i] = next_embedding[(size_t)r * E + i];
-  }
-  const float rew_new = reward[r], dis_new = discount[r];
-  if (j == 0) {
-    s.raw_values[rb + newn] = v;
-    s.node_values[rb + newn] = v;
-    s.node_visits[rb + newn] = s.node_visits[rb + newn] + 1;
-    s.children_index[eo] = newn;
-    s.children_rewards[eo] = rew_new;
-    s.children_discounts[eo] = dis_new;
-    s.parents[rb + newn] = parent;
-    s.action_from_parent[rb + newn] = action;
-    // backward along the staged path (only this lane touches these words)
-    float leaf = v, childv = v;
-    for (int d = depth - 1; d >= 0; --d) {
-      int pk = s.path[rb + d];
-      int pn = pk & 0xffff, pa = pk >> 16;
-      size_t e2 = (rb + pn) * A + pa;
-      int cnt = s.node_visits[rb + pn];
-      float rw = (d == depth - 1) ? rew_new : s.children_rewards[e2];
-      float ds = (d == depth - 1) ? dis_new : s.children_discounts[e2];
-      leaf = rw + ds * leaf;
-      float newv = (s.node_values[rb + pn] * (float)cnt + leaf) / ((float)cnt + 1.0f);
-      s.node_values[rb + pn] = newv;
-      s.node_visits[rb + pn] = cnt + 1;
-      s.children_values[e2] = childv;
-      s.children_visits[e2] = s.children_visits[e2] + 1;
-      childv = newv;
-    }
-  }
-}
-#endif  // MZ_NO_STEP_KERNELS
-
-// mctx Tree.summary + _apply_temperature + jax.random.categorical
-#ifndef MZ_NO_STEP_KERNELS
-__global__ __launch_bounds__(256) void step_finish_kernel(StepArgs s, float temperature, const float* gumbel,
-                                                           uint32_t ks0, uint32_t ks1, int32_t* action_out,
-                                                           float* action_weights_out, float* search_value_out,
-                                                           int32_t* depth_sum_out) {
-  MZ_ROW_SETUP
-  const uint64_t rg = s.root_offset + (uint64_t)r;
-  int vc[kMaxAS];
-  int part = 0;
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    int a = j + 16 * t;
-    vc[t] = a < A ? s.children_visits[rb * A + a] : 0;
-    part += vc[t];
-  }
-  float total = (float)row_sum_i(part);
-  float denom = fmaxf(total, 1.0f);
-  float lg[kMaxAS], prob[kMaxAS];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    int a = j + 16 * t;
-    float p = (float)vc[t] / denom;
-    p = total > 0.0f ? p : 1.0f / (float)A;
-    prob[t] = p;
-    lg[t] = log_pos(fmaxf(p, kFltTiny));
-    mx = a < A ? fmaxf(mx, lg[t]) : mx;
-  }
-  mx = row_max<4>(mx);
-  float tden = fmaxf(temperature, kFltTiny);
-  float bscore = -INFINITY;
-  int best = 1 << 20, dummy = 0;
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    int a = j + 16 * t;
-    bool ok = a < A;
-    float g;
-    if (gumbel != nullptr) {
-      g = ok ? gumbel[(size_t)r * A + a] : 0.0f;
-    } else {
-      uint32_t x0, x1;
-      bool second;
-      bits_block(s.global_batch * (uint64_t)A, rg * (uint64_t)A + (uint64_t)(ok ? a : 0), x0, x1, second);
-      threefry2x32(ks0, ks1, x0, x1);
-      g = gumbel_from_bits(second ? x1 : x0);
-    }
-    float score = ok ? (lg[t] - mx) / tden + g : -INFINITY;
-    if (ok) action_weights_out[(size_t)r * A + a] = prob[t];
-    bool take = (t == 0) || (ok && score > bscore);
-    if (take) { bscore = score; best = ok ? a : (1 << 20); }
-  }
-  row_argmax<4>(bscore, best, dummy);
-  if (j == 0) {
-    action_out[r] = best;
-    if (search_value_out) search_value_out[r] = s.node_values[rb];
-    if (depth_sum_out) depth_sum_out[r] = s.depth_sum[r];
-  }
-}
-#endif  // MZ_NO_STEP_KERNELS
-
 // canonical 16-wide sum of a row-distributed vector with run-time length
 MZ_DEV float row_sum_rt(const float (&x)[kMaxAS], int A, int j) {
   float part = 0.0f;
@@ -599,133 +235,346 @@ MZ_DEV int row_gumbel_argmax(const StepArgs& s, int r, int A, int j, int conside
   return best;
 }
 
-// mctx search.simulate with gumbel_muzero_{root,interior}_action_selection
-#ifndef MZ_NO_STEP_KERNELS
-__global__ __launch_bounds__(256) void step_select_gumbel_kernel(StepArgs s, int sim, int32_t* action_out,
-                                                                  float* parent_embedding_out) {
-  MZ_ROW_SETUP
-  int node = 0, depth = 0, parent = 0, action = 0;
-  for (;;) {
-    const size_t nb = (rb + node) * A;
-    float qv[kMaxAS], logits[kMaxAS];
-    int vc[kMaxAS], cidx[kMaxAS], sum_visits;
-    row_qtransform(s, rb, node, A, j, qv, vc, logits, sum_visits);
+// the cached decisions of mz_step_jump.cuh (all null in a handle whose tree is walked level by level)
+struct JumpArgs {
+  int32_t* jump_pa;     // [B][N]  parent | action << 16 | near tie << 31
+  int32_t* jump_lv;     // [B][N]  level of `parent` (edges from the root)
+  int32_t* node_depth;  // [B][N]  length of the node's own root path
+  uint32_t* node_path;  // [B][N][N]  entry e = node at level e | action taken there << 16
+};
+
+// The statistics of ONE root's tree that the per-simulation step both reads and rewrites (the MuZero policy's decisions:
+// children_{index, visits, prior_probs, rewards, values}, node_{visits, values}, the JUMP records), as pointers to the
+// root's own rows.  The step-wise kernels point them at the HBM tree (tree_view_global).  The one-launch ResNet search
+// (mz_search_conv.hip) keeps them in the CU's LDS for the whole search when they fit (round 6): between two tree steps
+// of a root its XCD streams 5.7 MB of convolution weights through a 4 MB L2, so every tree step used to find its ~260
+// cache lines evicted -- 4.5 of the 7 us of a 44-level decision refresh were memory round trips, not arithmetic.
+struct TreeView {
+  int* cidx; int* cvis; float* prob; float* rew; float* val;  // [N][A], element (node, a) at [(node * A + a) * cs]
+  float* dis;    // [N][A] children_discounts, or nullptr: `disc` on every edge (an unexpanded child's value is +0, so
+  float disc;    // rew + disc * val is the same +0 as with the array's 0 there)
+  int* nvis; float* nval;  // [N], element `node` at [node * ns]
+  int* jpa; int* jlv;      // [N]
+  // word strides: 1 / 1 for the HBM tree's separate arrays; the LDS copy interleaves the five words of a child and the
+  // four of a node (cs = 5, ns = 4): one address per (node, action), its fields at immediate offsets (ds_read2_b32)
+  int cs, ns;
+  // root_invalid_actions of this lane's actions (bit t: action j + 16 t), read once by a caller that lives for a whole
+  // search; -1: level_load reads s.root_invalid whenever it meets the root (a global round trip in front of the scores)
+  int inv_bits;
+};
+// the HBM tree of a handle without JUMP arrays (the walking kernels): no records to point at
+MZ_DEV TreeView tree_view_global(const StepArgs& s, size_t rb) {
+  const size_t o = rb * (size_t)s.A;
+  TreeView T;
+  T.cidx = s.children_index + o; T.cvis = s.children_visits + o; T.prob = s.children_prior_probs + o;
+  T.rew = s.children_rewards + o; T.val = s.children_values + o; T.dis = s.children_discounts + o; T.disc = 0.0f;
+  T.nvis = s.node_visits + rb; T.nval = s.node_values + rb; T.jpa = nullptr; T.jlv = nullptr;
+  T.cs = 1; T.ns = 1; T.inv_bits = -1;
+  return T;
+}
+MZ_DEV TreeView tree_view_global(const StepArgs& s, const JumpArgs& g, size_t rb) {
+  TreeView T = tree_view_global(s, rb);
+  T.jpa = g.jump_pa + rb; T.jlv = g.jump_lv + rb;
+  return T;
+}
+
+// pUCT scores of all children of `node` (muzero_action_selection with qtransform_by_parent_and_siblings),
+// noise-free; first-max argmax; `near` = some other action is within the reach of the tie-break noise.
+// Split into the loads and the arithmetic so that a row can put the loads of several levels in flight before it
+// computes on the first (mzs_expand_backup refreshes up to kLevelsInFlight levels per row at once).
+struct LevelIn {
+  int cidx[kMaxAS], cvis[kMaxAS];
+  float prob[kMaxAS], rew[kMaxAS], dis[kMaxAS], val[kMaxAS];
+  int nvis, inv;  // inv: bit t = action j + 16 t is invalid at the root
+  float nval;
+};
+// AS: 0 = any action count up to 16 kMaxAS (every 16-lane slot behind a run-time test), else the number of slots the
+// caller's action count fills (16 (AS - 1) < A <= 16 AS): the same operations without the dead slots' branches
+template <int AS = 0>
+MZ_DEV void level_load(const StepArgs& s, const TreeView& T, int r, int node, int j, LevelIn& L) {
+  const int A = s.A;
+  const int nb = node * A;
+  L.nvis = T.nvis[node * T.ns];
+  L.nval = T.nval[node * T.ns];
+  L.inv = 0;
 #pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) cidx[t] = s.children_index[nb + (j + 16 * t < A ? j + 16 * t : 0)];
-    int best, next;
-    if (depth == 0) {
-      int ninv = 0;
-#pragma unroll
-      for (int t = 0; t < kMaxAS; ++t)
-        ninv += (j + 16 * t < A && s.root_invalid[(size_t)r * A + j + 16 * t]) ? 1 : 0;
-      const int num_valid = A - row_sum_i(ninv);
-      const int num_considered = min(s.max_considered, num_valid);
-      const int si = min(sum_visits, s.S - 1);
-      const int considered_visit = s.visit_table[(size_t)num_considered * s.S + si];
-      best = row_gumbel_argmax(s, r, A, j, considered_visit, logits, qv, vc, cidx, next);
-    } else {
-      float x[kMaxAS], p[kMaxAS];
-#pragma unroll
-      for (int t = 0; t < kMaxAS; ++t) x[t] = logits[t] + qv[t];
-      row_softmax_rt(x, A, j, p);
-      float bscore = -INFINITY;
-      int b2 = 1 << 20, bnext = -1;
-#pragma unroll
-      for (int t = 0; t < kMaxAS; ++t) {
-        int a = j + 16 * t;
-        bool ok = a < A;
-        float sc = ok ? p[t] - (float)vc[t] / (float)(1 + sum_visits) : -INFINITY;
-        bool take = (t == 0) || (sc > bscore);
-        if (take) { bscore = sc; b2 = ok ? a : (1 << 20); bnext = cidx[t]; }
-      }
-      row_argmax<4>(bscore, b2, bnext);
-      best = b2;
-      next = bnext;
+  for (int t = 0; t < (AS ? AS : kMaxAS); ++t) {
+    const int a = j + 16 * t;
+    const bool ok = a < A;
+    L.cidx[t] = -1; L.cvis[t] = 0; L.prob[t] = 0.0f; L.rew[t] = 0.0f; L.dis[t] = 0.0f; L.val[t] = 0.0f;
+    if (AS || 16 * t < A) {
+      const int o = nb + (ok ? a : 0);
+      L.cidx[t] = T.cidx[o * T.cs];
+      L.cvis[t] = T.cvis[o * T.cs];
+      L.prob[t] = T.prob[o * T.cs];
+      L.rew[t] = T.rew[o * T.cs];
+      L.dis[t] = T.dis ? T.dis[o * T.cs] : T.disc;
+      L.val[t] = T.val[o * T.cs];
+      if (T.inv_bits < 0 && node == 0 && ok && s.root_invalid[(size_t)r * A + a]) L.inv |= 1 << t;  // the root is level 0 only
     }
-    if (j == 0) s.path[rb + depth] = node | (best << 16);
-    parent = node;
-    action = best;
-    depth += 1;
-    if (next == -1 || depth >= s.max_depth) break;
-    node = next;
   }
-  if (j == 0) {
+  if (T.inv_bits >= 0 && node == 0) L.inv = T.inv_bits;
+}
+// `tbl` (optional, LDS): {sqrt(n) pb_c(n), RN(1 / n)} for n = 0 .. S + 1, built once per launch by a kernel that lives
+// for a whole search (mz_search_conv.hip) -- the same puct_scale() values, and x / n by Markstein's exact sequence for
+// n <= 1030 (div_small, mz_fused.cuh; tests/test_oracle_kat.py): the refresh of a path's decisions is arithmetic-bound,
+// a log, a sqrt and three of its four IEEE divisions per level go
+// TBL: `tbl` is there (the caller's launch built it): no code for the other case
+template <int AS = 0, bool TBL = false>
+MZ_DEV void level_compute(const StepArgs& s, int j, const LevelIn& L, float (&sc)[kMaxAS], int& best, int& child,
+                          bool& near, const float* tbl = nullptr) {
+  constexpr int NSLOT = AS ? AS : kMaxAS;
+  const int A = s.A;
+  const float nval = L.nval;
+  const float tn = (TBL || tbl) ? tbl[2 * L.nvis] : puct_scale(L.nvis, s.pb_c_init, s.pb_c_base);
+  float q[kMaxAS];
+  float lo = nval, hi = nval;
+#pragma unroll
+  for (int t = 0; t < NSLOT; ++t) {
+    const bool ok = j + 16 * t < A;
+    q[t] = 0.0f;
+    if (AS || 16 * t < A) {
+      q[t] = L.rew[t] + L.dis[t] * L.val[t];
+      const float safe = (ok && L.cvis[t] > 0) ? q[t] : nval;
+      lo = fminf(lo, safe);
+      hi = fmaxf(hi, safe);
+    }
+  }
+  lo = row_min<4>(lo);
+  hi = row_max<4>(hi);
+  const float span = fmaxf(hi - lo, 1e-8f);
+  float bscore = -INFINITY;
+  best = 1 << 20;
+  child = -1;
+  // two slots of actions: the lane's two value scores share their denominator -- ONE refined reciprocal and the
+  // hardware's own quotient correction on the packed pair (div_newton2, mz_spec.cuh: the IEEE quotient while every
+  // numerator is 0 or >= 2^-100 and the span is below 2^100; a wave-uniform test, the IEEE divisions otherwise) as in
+  // the fused kernel's puct_scores: 12 instructions instead of 26
+  [[maybe_unused]] f32x2 vs2 = splat2(0.0f);
+  [[maybe_unused]] bool have_vs2 = false;
+  if constexpr (AS == 2) {
+    const float n0 = (L.cvis[0] > 0 ? q[0] : lo) - lo, n1 = (L.cvis[1] > 0 ? q[1] : lo) - lo;
+    const uint32_t low = min(f2u(n0) - 1u, f2u(n1) - 1u);  // 0 wraps to the top: only (0, 2^-100) fails the test
+    const bool risky = (low < f2u(0x1p-100f) - 1u) | !(span < 0x1p100f);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(risky) == 0, 1)) {
+      const float y0 = __builtin_amdgcn_rcpf(span);
+      const float y = __builtin_fmaf(__builtin_fmaf(-span, y0, 1.0f), y0, y0);
+      vs2 = div_newton2((f32x2){n0, n1}, splat2(span), splat2(y));
+      have_vs2 = true;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NSLOT; ++t) {
+    const int a = j + 16 * t;
+    const bool ok = a < A;
+    sc[t] = -INFINITY;
+    if (AS || 16 * t < A) {
+      float value_score;
+      if (AS == 2 && have_vs2) value_score = t == 0 ? vs2.x : vs2.y;
+      else value_score = ((L.cvis[t] > 0 ? q[t] : lo) - lo) / span;
+      float policy_score;
+      if (TBL || tbl) {
+        const float x = tn * L.prob[t], d = (float)(L.cvis[t] + 1), y = tbl[2 * (L.cvis[t] + 1) + 1];
+        const float q0 = x * y;
+        policy_score = __builtin_fmaf(__builtin_fmaf(-q0, d, x), y, q0);
+      } else {
+        policy_score = (tn * L.prob[t]) / (float)(L.cvis[t] + 1);
+      }
+      sc[t] = value_score + policy_score;
+      if ((L.inv >> t) & 1) sc[t] = -INFINITY;
+      if (!ok) sc[t] = -INFINITY;
+    }
+    const bool take = (t == 0) || (sc[t] > bscore);  // first max wins inside the lane
+    if (take) { bscore = sc[t]; best = ok ? a : (1 << 20); child = L.cidx[t]; }
+  }
+  row_argmax<4>(bscore, best, child);
+  bool unsafe = false;
+  if (s.tiebreak) {
+#pragma unroll
+    for (int t = 0; t < NSLOT; ++t) {
+      const int a = j + 16 * t;
+      unsafe = unsafe | ((a < A) & (a != best) & !((sc[t] + 1e-7f) < bscore));
+    }
+  }
+  near = ((__builtin_amdgcn_ballot_w64(unsafe) >> (threadIdx.x & 48)) & 0xffffull) != 0;  // any lane of the row
+}
+MZ_DEV void level_decide(const StepArgs& s, const TreeView& T, int r, int node, int j, float (&sc)[kMaxAS],
+                         int (&cidx)[kMaxAS], int& best, int& child, bool& near) {
+  LevelIn L;
+  level_load(s, T, r, node, j, L);
+  level_compute(s, j, L, sc, best, child, near);
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) cidx[t] = L.cidx[t];
+}
+
+// mctx gumbel_muzero_{root,interior}_action_selection at `node` (the root is only ever selected at level 0):
+// deterministic in the node's statistics -- the root's sequential-halving table entry is indexed by its
+// own visit sum, i.e. by the number of the NEXT simulation once the backup has run.
+MZ_DEV void gumbel_decide(const StepArgs& s, size_t rb, int r, int node, int j, int& best, int& child) {
+  const int A = s.A;
+  const size_t nb = (rb + node) * A;
+  float qv[kMaxAS], logits[kMaxAS];
+  int vc[kMaxAS], cidx[kMaxAS], sum_visits;
+  row_qtransform(s, rb, node, A, j, qv, vc, logits, sum_visits);
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) cidx[t] = s.children_index[nb + (j + 16 * t < A ? j + 16 * t : 0)];
+  if (node == 0) {
+    int ninv = 0;
+#pragma unroll
+    for (int t = 0; t < kMaxAS; ++t) ninv += (j + 16 * t < A && s.root_invalid[(size_t)r * A + j + 16 * t]) ? 1 : 0;
+    const int num_valid = A - row_sum_i(ninv);
+    const int num_considered = min(s.max_considered, num_valid);
+    const int si = min(sum_visits, s.S - 1);
+    const int considered_visit = s.visit_table[(size_t)num_considered * s.S + si];
+    best = row_gumbel_argmax(s, r, A, j, considered_visit, logits, qv, vc, cidx, child);
+  } else {
+    float x[kMaxAS], p[kMaxAS];
+#pragma unroll
+    for (int t = 0; t < kMaxAS; ++t) x[t] = logits[t] + qv[t];
+    row_softmax_rt(x, A, j, p);
+    float bscore = -INFINITY;
+    best = 1 << 20;
+    child = -1;
+#pragma unroll
+    for (int t = 0; t < kMaxAS; ++t) {
+      const int a = j + 16 * t;
+      const bool ok = a < A;
+      const float sc = ok ? p[t] - (float)vc[t] / (float)(1 + sum_visits) : -INFINITY;
+      const bool take = (t == 0) || (sc > bscore);
+      if (take) { bscore = sc; best = ok ? a : (1 << 20); child = cidx[t]; }
+    }
+    row_argmax<4>(bscore, best, child);
+  }
+}
+template <bool GUMBEL>
+MZ_DEV void decide_any(const StepArgs& s, const TreeView& T, size_t rb, int r, int node, int j, int& best, int& child, bool& near) {
+  if constexpr (GUMBEL) {
+    gumbel_decide(s, rb, r, node, j, best, child);  // (the Gumbel policy's statistics stay in the HBM tree)
+    near = false;
+  } else {
+    float sc[kMaxAS];
+    int cidx[kMaxAS];
+    level_decide(s, T, r, node, j, sc, cidx, best, child, near);
+  }
+}
+
+
+// JAX's key chain of one simulation, walked lazily (only a near tie needs a key): the per-simulation root key, then
+// rng_key, action_selection_key = split(rng_key) once per level.  (k0, k1): rng_key after `level` splits (-1: not
+// started); (s0, s1): the action_selection_key of level `level - 1`.
+struct SimKeys {
+  uint32_t k0 = 0, k1 = 0, s0 = 0, s1 = 0;
+  int level = -1;
+};
+MZ_DEV void sim_keys_advance(const StepArgs& s, int sim, int r, int j, SimKeys& K, int level) {
+  if (K.level < 0) {
+    const uint64_t rg = s.root_offset + (uint64_t)r;
+    uint32_t x0, x1;
+    bool second;
+    bits_block(2 * s.global_batch, 2 * rg + (uint64_t)(j & 1), x0, x1, second);
+    threefry2x32(s.sim_keys[2 * sim], s.sim_keys[2 * sim + 1], x0, x1);
+    const uint32_t word = second ? x1 : x0;
+    K.k0 = bcast_u<0>(word);
+    K.k1 = bcast_u<1>(word);
+    K.level = 0;
+  }
+  while (K.level <= level) {
+    uint32_t x0 = (uint32_t)(j & 1), x1 = 2u + (uint32_t)(j & 1);
+    threefry2x32(K.k0, K.k1, x0, x1);
+    K.k0 = bcast_u<0>(x0); K.k1 = bcast_u<1>(x0);
+    K.s0 = bcast_u<0>(x1); K.s1 = bcast_u<1>(x1);
+    K.level += 1;
+  }
+}
+
+// mctx adds 1e-7 * uniform[0,1) to every score.  If fl(score_a + 1e-7) < best for every other action the argmax cannot
+// depend on the draw (rounding is monotone): only a row that holds a near tie (level_compute's `near`) pays for the
+// threefry blocks.  (-inf scores stay -inf with or without noise.)  This is that draw: the argmax of the row's noise-free
+// scores `sc` plus the noise of the level's action_selection_key (s0, s1), and the winner's child index.
+MZ_DEV void noisy_argmax(int A, int j, const float (&sc)[kMaxAS], const int (&cidx)[kMaxAS], uint32_t s0, uint32_t s1,
+                         int& best, int& child) {
+  const int NB = (A + 1) / 2;
+  float bscore = -INFINITY;
+  best = 1 << 20;
+  child = -1;
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    const int a = j + 16 * t;
+    float score = sc[t];
+    if (16 * t < A) {
+      const int jb = a < NB ? a : a - NB;
+      uint32_t x0 = (uint32_t)jb, x1 = (NB + jb < A) ? (uint32_t)(NB + jb) : 0u;
+      threefry2x32(s0, s1, x0, x1);
+      score = score + 1e-7f * uniform_from_bits(a < NB ? x0 : x1);
+    }
+    const bool take = (t == 0) || (score > bscore);
+    if (take) { bscore = score; best = (a < A) ? a : (1 << 20); child = cidx[t]; }
+  }
+  row_argmax<4>(bscore, best, child);
+}
+
+// What simulate() hands to expand(): the selection record, by the row's (WG: the workgroup's) first lane, and the
+// parent's embedding row into `parent_embedding_out` (nullptr: no gather -- a wide row moves by emb_xfer_kernel, or the
+// caller reads the tree's row in place).  `xfer`: note the parent in xfer_node; `sel_out`: the record to every thread;
+// `depth_acc`: the depth is added there (a register of the caller, who owns depth_sum[r] for the launch).
+template <bool WG>
+MZ_DEV void store_selection(const StepArgs& s, int r, int parent, int action, int depth, int32_t* action_out,
+                            float* parent_embedding_out, bool xfer, int* sel_out = nullptr, int* depth_acc = nullptr) {
+  const int j = threadIdx.x & 15;
+  const int E = s.E;
+  if (sel_out) { sel_out[0] = parent; sel_out[1] = action; sel_out[2] = depth; }
+  if (WG ? threadIdx.x == 0 : j == 0) {
     s.sel_parent[r] = parent;
     s.sel_action[r] = action;
     s.sel_depth[r] = depth;
-    s.depth_sum[r] += depth;
-    action_out[r] = action;
+    if (depth_acc) *depth_acc += depth;
+    else s.depth_sum[r] += depth;
+    if (action_out) action_out[r] = action;
+    if (xfer) s.xfer_node[r] = parent;
   }
-  if (s.wide) {
-    if (j == 0) s.xfer_node[r] = parent;
+  if (parent_embedding_out == nullptr) return;
+  const float* src = s.embeddings + ((size_t)r * s.N + parent) * E;
+  if (WG) {
+    for (int i = threadIdx.x; i < E; i += blockDim.x) parent_embedding_out[(size_t)r * E + i] = src[i];
   } else {
-    const float* src = s.embeddings + (rb + parent) * E;
     for (int i = j; i < E; i += 16) parent_embedding_out[(size_t)r * E + i] = src[i];
   }
 }
-#endif  // MZ_NO_STEP_KERNELS
 
-// tail of mctx gumbel_muzero_policy: best considered action + completed-Q policy target
-#ifndef MZ_NO_STEP_KERNELS
-__global__ __launch_bounds__(256) void step_finish_gumbel_kernel(StepArgs s, int32_t* action_out,
-                                                                  float* action_weights_out,
-                                                                  float* search_value_out, int32_t* depth_sum_out) {
-  MZ_ROW_SETUP
-  float qv[kMaxAS], logits[kMaxAS];
-  int vc[kMaxAS], cidx[kMaxAS] = {0, 0, 0, 0}, sum_visits, next;
-  row_qtransform(s, rb, 0, A, j, qv, vc, logits, sum_visits);
-  int mxv = 0;
-  bool any_inv = false;
+// mctx _mask_invalid_actions + softmax over a row: where any lane of the row says `masked`, x - max(x) with the invalid
+// actions at the lowest float; x holds what the softmax saw
+MZ_DEV void row_mask_invalid_softmax(float (&x)[kMaxAS], const bool (&inv)[kMaxAS], bool masked, int A, int j,
+                                     float (&p)[kMaxAS]) {
+  if (((__builtin_amdgcn_ballot_w64(masked) >> (threadIdx.x & 48)) & 0xffffull) != 0) {  // any lane of the row
+    float mx = -INFINITY;
 #pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    mxv = max(mxv, vc[t]);
-    any_inv = any_inv || (j + 16 * t < A && s.root_invalid[(size_t)r * A + j + 16 * t]);
-  }
-  const int considered_visit = row_max_i(mxv);
-  const int best = row_gumbel_argmax(s, r, A, j, considered_visit, logits, qv, vc, cidx, next);
-  any_inv = ((__builtin_amdgcn_ballot_w64(any_inv) >> (lane & 48)) & 0xffffull) != 0;
-  float x[kMaxAS], w[kMaxAS];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    x[t] = logits[t] + qv[t];
-    mx = (j + 16 * t < A) ? fmaxf(mx, x[t]) : mx;
-  }
-  if (any_inv) {
+    for (int t = 0; t < kMaxAS; ++t) mx = (j + 16 * t < A) ? fmaxf(mx, x[t]) : mx;
     mx = row_max<4>(mx);
 #pragma unroll
-    for (int t = 0; t < kMaxAS; ++t)
-      x[t] = (j + 16 * t < A && s.root_invalid[(size_t)r * A + j + 16 * t]) ? kFltLowest : x[t] - mx;
+    for (int t = 0; t < kMaxAS; ++t) x[t] = inv[t] ? kFltLowest : x[t] - mx;
   }
-  row_softmax_rt(x, A, j, w);
+  row_softmax_rt(x, A, j, p);
+}
+
+// expansion of node `newn`: its prior row is the softmax of the net's logits (logits to the HBM tree, probabilities
+// through the view)
+MZ_DEV void expand_prior_row(const StepArgs& s, const TreeView& T, size_t rb, int newn, const float* prior_logits_row, int j) {
+  const int A = s.A;
+  float x[kMaxAS], pr[kMaxAS];
 #pragma unroll
-  for (int t = 0; t < kMaxAS; ++t)
-    if (j + 16 * t < A) action_weights_out[(size_t)r * A + j + 16 * t] = w[t];
-  if (j == 0) {
-    action_out[r] = best;
-    if (search_value_out) search_value_out[r] = s.node_values[rb];
-    if (depth_sum_out) depth_sum_out[r] = s.depth_sum[r];
+  for (int t = 0; t < kMaxAS; ++t) {
+    const int a = j + 16 * t;
+    x[t] = a < A ? prior_logits_row[a] : 0.0f;
+  }
+  row_softmax_rt(x, A, j, pr);
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    const int a = j + 16 * t;
+    if (a < A) {
+      s.children_prior_logits[(rb + newn) * A + a] = x[t];
+      T.prob[(newn * A + a) * T.cs] = pr[t];
+    }
   }
 }
-#endif  // MZ_NO_STEP_KERNELS
-
-#undef MZ_ROW_SETUP
-
-// ---- wide embedding rows: one workgroup per (root, KiB of the row) ----
-// dir 0: rows[b] <- tree.embeddings[b][xfer_node[b]]   (parent embedding for recurrent_fn)
-// dir 1: tree.embeddings[b][xfer_node[b]] <- rows[b]   (root / next embedding)
-#ifndef MZ_NO_STEP_KERNELS
-__global__ __launch_bounds__(256) void emb_xfer_kernel(const StepArgs s, float* rows, int dir) {
-  const int b = blockIdx.x;
-  const size_t E = (size_t)s.E;
-  float* node = s.embeddings + ((size_t)b * s.N + s.xfer_node[b]) * E;
-  float* row = rows + (size_t)b * E;
-  const size_t i0 = (size_t)blockIdx.y * 1024, i1 = i0 + 1024 < E ? i0 + 1024 : E;
-  if (dir == 0)
-    for (size_t i = i0 + threadIdx.x; i < i1; i += 256) row[i] = node[i];
-  else
-    for (size_t i = i0 + threadIdx.x; i < i1; i += 256) node[i] = row[i];
-}
-#endif  // MZ_NO_STEP_KERNELS
 
 }  // namespace mz

@@ -15,7 +15,8 @@
 //
 // Every node stores its own root path (written once at expansion: parent's path + one entry), so the
 // backup finds its levels without a pointer chase.  Used (both policies) when N <= kJumpMaxNodes and B N^2
-// words fit the budget; otherwise mz_step.cuh's walking kernels run.
+// words fit the budget; otherwise the walking kernels run.  Device functions only: the bodies below are also the tree
+// step of the one-launch searches (mz_search_conv.hip, mz_mlp_generic.cuh); their kernels are in mz_step_kernels.cuh.
 #pragma once
 #include "mz_step.cuh"
 
@@ -41,245 +42,6 @@ __device__ unsigned long long g_jump_prof[1024 * 8];
 #endif
 constexpr int kLevelsInFlight = 3;  // levels of a backed-up path a 16-lane row refreshes at once (mzs_expand_backup)
 
-#define MZ_JROW_SETUP                                                 \
-  const int lane = threadIdx.x & 63;                                  \
-  const int j = lane & 15;                                            \
-  const int r = blockIdx.x * (blockDim.x >> 4) + (threadIdx.x >> 4);  \
-  if (r >= s.B) return;                                               \
-  const int N = s.N, A = s.A, E = s.E;                                \
-  const size_t rb = (size_t)r * N;                                    \
-  (void)lane; (void)N; (void)A; (void)E;
-
-struct JumpArgs {
-  int32_t* jump_pa;     // [B][N]  parent | action << 16 | near tie << 31
-  int32_t* jump_lv;     // [B][N]  level of `parent` (edges from the root)
-  int32_t* node_depth;  // [B][N]  length of the node's own root path
-  uint32_t* node_path;  // [B][N][N]  entry e = node at level e | action taken there << 16
-};
-
-// The statistics of ONE root's tree that the per-simulation step both reads and rewrites (the MuZero policy's decisions:
-// children_{index, visits, prior_probs, rewards, values}, node_{visits, values}, the JUMP records), as pointers to the
-// root's own rows.  The step-wise kernels point them at the HBM tree (tree_view_global).  The one-launch ResNet search
-// (mz_search_conv.hip) keeps them in the CU's LDS for the whole search when they fit (round 6): between two tree steps
-// of a root its XCD streams 5.7 MB of convolution weights through a 4 MB L2, so every tree step used to find its ~260
-// cache lines evicted -- 4.5 of the 7 us of a 44-level decision refresh were memory round trips, not arithmetic.
-struct TreeView {
-  int* cidx; int* cvis; float* prob; float* rew; float* val;  // [N][A], element (node, a) at [(node * A + a) * cs]
-  float* dis;    // [N][A] children_discounts, or nullptr: `disc` on every edge (an unexpanded child's value is +0, so
-  float disc;    // rew + disc * val is the same +0 as with the array's 0 there)
-  int* nvis; float* nval;  // [N], element `node` at [node * ns]
-  int* jpa; int* jlv;      // [N]
-  // word strides: 1 / 1 for the HBM tree's separate arrays; the LDS copy interleaves the five words of a child and the
-  // four of a node (cs = 5, ns = 4): one address per (node, action), its fields at immediate offsets (ds_read2_b32)
-  int cs, ns;
-  // root_invalid_actions of this lane's actions (bit t: action j + 16 t), read once by a caller that lives for a whole
-  // search; -1: level_load reads s.root_invalid whenever it meets the root (a global round trip in front of the scores)
-  int inv_bits;
-};
-MZ_DEV TreeView tree_view_global(const StepArgs& s, const JumpArgs& g, size_t rb) {
-  const size_t o = rb * (size_t)s.A;
-  TreeView T;
-  T.cidx = s.children_index + o; T.cvis = s.children_visits + o; T.prob = s.children_prior_probs + o;
-  T.rew = s.children_rewards + o; T.val = s.children_values + o; T.dis = s.children_discounts + o; T.disc = 0.0f;
-  T.nvis = s.node_visits + rb; T.nval = s.node_values + rb; T.jpa = g.jump_pa + rb; T.jlv = g.jump_lv + rb;
-  T.cs = 1; T.ns = 1; T.inv_bits = -1;
-  return T;
-}
-
-// pUCT scores of all children of `node` (muzero_action_selection with qtransform_by_parent_and_siblings),
-// noise-free; first-max argmax; `near` = some other action is within the reach of the tie-break noise.
-// Split into the loads and the arithmetic so that a row can put the loads of several levels in flight before it
-// computes on the first (mzs_expand_backup refreshes up to kLevelsInFlight levels per row at once).
-struct LevelIn {
-  int cidx[kMaxAS], cvis[kMaxAS];
-  float prob[kMaxAS], rew[kMaxAS], dis[kMaxAS], val[kMaxAS];
-  int nvis, inv;  // inv: bit t = action j + 16 t is invalid at the root
-  float nval;
-};
-// AS: 0 = any action count up to 16 kMaxAS (every 16-lane slot behind a run-time test), else the number of slots the
-// caller's action count fills (16 (AS - 1) < A <= 16 AS): the same operations without the dead slots' branches
-template <int AS = 0>
-MZ_DEV void level_load(const StepArgs& s, const TreeView& T, int r, int node, int j, LevelIn& L) {
-  const int A = s.A;
-  const int nb = node * A;
-  L.nvis = T.nvis[node * T.ns];
-  L.nval = T.nval[node * T.ns];
-  L.inv = 0;
-#pragma unroll
-  for (int t = 0; t < (AS ? AS : kMaxAS); ++t) {
-    const int a = j + 16 * t;
-    const bool ok = a < A;
-    L.cidx[t] = -1; L.cvis[t] = 0; L.prob[t] = 0.0f; L.rew[t] = 0.0f; L.dis[t] = 0.0f; L.val[t] = 0.0f;
-    if (AS || 16 * t < A) {
-      const int o = nb + (ok ? a : 0);
-      L.cidx[t] = T.cidx[o * T.cs];
-      L.cvis[t] = T.cvis[o * T.cs];
-      L.prob[t] = T.prob[o * T.cs];
-      L.rew[t] = T.rew[o * T.cs];
-      L.dis[t] = T.dis ? T.dis[o * T.cs] : T.disc;
-      L.val[t] = T.val[o * T.cs];
-      if (T.inv_bits < 0 && node == 0 && ok && s.root_invalid[(size_t)r * A + a]) L.inv |= 1 << t;  // the root is level 0 only
-    }
-  }
-  if (T.inv_bits >= 0 && node == 0) L.inv = T.inv_bits;
-}
-// `tbl` (optional, LDS): {sqrt(n) pb_c(n), RN(1 / n)} for n = 0 .. S + 1, built once per launch by a kernel that lives
-// for a whole search (mz_search_conv.hip) -- the same puct_scale() values, and x / n by Markstein's exact sequence for
-// n <= 1030 (div_small, mz_fused.cuh; tests/test_oracle_kat.py): the refresh of a path's decisions is arithmetic-bound,
-// a log, a sqrt and three of its four IEEE divisions per level go
-// TBL: `tbl` is there (the caller's launch built it): no code for the other case
-template <int AS = 0, bool TBL = false>
-MZ_DEV void level_compute(const StepArgs& s, int j, const LevelIn& L, float (&sc)[kMaxAS], int& best, int& child,
-                          bool& near, const float* tbl = nullptr) {
-  constexpr int NSLOT = AS ? AS : kMaxAS;
-  const int A = s.A;
-  const float nval = L.nval;
-  const float tn = (TBL || tbl) ? tbl[2 * L.nvis] : puct_scale(L.nvis, s.pb_c_init, s.pb_c_base);
-  float q[kMaxAS];
-  float lo = nval, hi = nval;
-#pragma unroll
-  for (int t = 0; t < NSLOT; ++t) {
-    const bool ok = j + 16 * t < A;
-    q[t] = 0.0f;
-    if (AS || 16 * t < A) {
-      q[t] = L.rew[t] + L.dis[t] * L.val[t];
-      const float safe = (ok && L.cvis[t] > 0) ? q[t] : nval;
-      lo = fminf(lo, safe);
-      hi = fmaxf(hi, safe);
-    }
-  }
-  lo = row_min<4>(lo);
-  hi = row_max<4>(hi);
-  const float span = fmaxf(hi - lo, 1e-8f);
-  float bscore = -INFINITY;
-  best = 1 << 20;
-  child = -1;
-  // two slots of actions: the lane's two value scores share their denominator -- ONE refined reciprocal and the
-  // hardware's own quotient correction on the packed pair (div_newton2, mz_spec.cuh: the IEEE quotient while every
-  // numerator is 0 or >= 2^-100 and the span is below 2^100; a wave-uniform test, the IEEE divisions otherwise) as in
-  // the fused kernel's puct_scores: 12 instructions instead of 26
-  [[maybe_unused]] f32x2 vs2 = splat2(0.0f);
-  [[maybe_unused]] bool have_vs2 = false;
-  if constexpr (AS == 2) {
-    const float n0 = (L.cvis[0] > 0 ? q[0] : lo) - lo, n1 = (L.cvis[1] > 0 ? q[1] : lo) - lo;
-    const uint32_t low = min(f2u(n0) - 1u, f2u(n1) - 1u);  // 0 wraps to the top: only (0, 2^-100) fails the test
-    const bool risky = (low < f2u(0x1p-100f) - 1u) | !(span < 0x1p100f);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(risky) == 0, 1)) {
-      const float y0 = __builtin_amdgcn_rcpf(span);
-      const float y = __builtin_fmaf(__builtin_fmaf(-span, y0, 1.0f), y0, y0);
-      vs2 = div_newton2((f32x2){n0, n1}, splat2(span), splat2(y));
-      have_vs2 = true;
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < NSLOT; ++t) {
-    const int a = j + 16 * t;
-    const bool ok = a < A;
-    sc[t] = -INFINITY;
-    if (AS || 16 * t < A) {
-      float value_score;
-      if (AS == 2 && have_vs2) value_score = t == 0 ? vs2.x : vs2.y;
-      else value_score = ((L.cvis[t] > 0 ? q[t] : lo) - lo) / span;
-      float policy_score;
-      if (TBL || tbl) {
-        const float x = tn * L.prob[t], d = (float)(L.cvis[t] + 1), y = tbl[2 * (L.cvis[t] + 1) + 1];
-        const float q0 = x * y;
-        policy_score = __builtin_fmaf(__builtin_fmaf(-q0, d, x), y, q0);
-      } else {
-        policy_score = (tn * L.prob[t]) / (float)(L.cvis[t] + 1);
-      }
-      sc[t] = value_score + policy_score;
-      if ((L.inv >> t) & 1) sc[t] = -INFINITY;
-      if (!ok) sc[t] = -INFINITY;
-    }
-    const bool take = (t == 0) || (sc[t] > bscore);  // first max wins inside the lane
-    if (take) { bscore = sc[t]; best = ok ? a : (1 << 20); child = L.cidx[t]; }
-  }
-  row_argmax<4>(bscore, best, child);
-  bool unsafe = false;
-  if (s.tiebreak) {
-#pragma unroll
-    for (int t = 0; t < NSLOT; ++t) {
-      const int a = j + 16 * t;
-      unsafe = unsafe | ((a < A) & (a != best) & !((sc[t] + 1e-7f) < bscore));
-    }
-  }
-  near = ((__builtin_amdgcn_ballot_w64(unsafe) >> (threadIdx.x & 48)) & 0xffffull) != 0;  // any lane of the row
-}
-MZ_DEV void level_decide(const StepArgs& s, const TreeView& T, int r, int node, int j, float (&sc)[kMaxAS],
-                         int (&cidx)[kMaxAS], int& best, int& child, bool& near) {
-  LevelIn L;
-  level_load(s, T, r, node, j, L);
-  level_compute(s, j, L, sc, best, child, near);
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) cidx[t] = L.cidx[t];
-}
-
-// mctx gumbel_muzero_{root,interior}_action_selection at `node` (the root is only ever selected at level 0):
-// deterministic in the node's statistics -- the root's sequential-halving table entry is indexed by its
-// own visit sum, i.e. by the number of the NEXT simulation once the backup has run.
-MZ_DEV void gumbel_decide(const StepArgs& s, size_t rb, int r, int node, int j, int& best, int& child) {
-  const int A = s.A;
-  const size_t nb = (rb + node) * A;
-  float qv[kMaxAS], logits[kMaxAS];
-  int vc[kMaxAS], cidx[kMaxAS], sum_visits;
-  row_qtransform(s, rb, node, A, j, qv, vc, logits, sum_visits);
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) cidx[t] = s.children_index[nb + (j + 16 * t < A ? j + 16 * t : 0)];
-  if (node == 0) {
-    int ninv = 0;
-#pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) ninv += (j + 16 * t < A && s.root_invalid[(size_t)r * A + j + 16 * t]) ? 1 : 0;
-    const int num_valid = A - row_sum_i(ninv);
-    const int num_considered = min(s.max_considered, num_valid);
-    const int si = min(sum_visits, s.S - 1);
-    const int considered_visit = s.visit_table[(size_t)num_considered * s.S + si];
-    best = row_gumbel_argmax(s, r, A, j, considered_visit, logits, qv, vc, cidx, child);
-  } else {
-    float x[kMaxAS], p[kMaxAS];
-#pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) x[t] = logits[t] + qv[t];
-    row_softmax_rt(x, A, j, p);
-    float bscore = -INFINITY;
-    best = 1 << 20;
-    child = -1;
-#pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) {
-      const int a = j + 16 * t;
-      const bool ok = a < A;
-      const float sc = ok ? p[t] - (float)vc[t] / (float)(1 + sum_visits) : -INFINITY;
-      const bool take = (t == 0) || (sc > bscore);
-      if (take) { bscore = sc; best = ok ? a : (1 << 20); child = cidx[t]; }
-    }
-    row_argmax<4>(bscore, best, child);
-  }
-}
-template <bool GUMBEL>
-MZ_DEV void decide_any(const StepArgs& s, const TreeView& T, size_t rb, int r, int node, int j, int& best, int& child, bool& near) {
-  if constexpr (GUMBEL) {
-    gumbel_decide(s, rb, r, node, j, best, child);  // (the Gumbel policy's statistics stay in the HBM tree)
-    near = false;
-  } else {
-    float sc[kMaxAS];
-    int cidx[kMaxAS];
-    level_decide(s, T, r, node, j, sc, cidx, best, child, near);
-  }
-}
-
-// root decision (after step_root_kernel): one row per root
-template <bool GUMBEL>
-__global__ __launch_bounds__(256) void jump_root_kernel(StepArgs s, JumpArgs g) {
-  MZ_JROW_SETUP
-  int best, child;
-  bool near;
-  decide_any<GUMBEL>(s, tree_view_global(s, g, rb), rb, r, 0, j, best, child, near);
-  if (j == 0) {
-    g.jump_pa[rb] = best << 16 | (near ? (int)0x80000000 : 0);
-    g.jump_lv[rb] = 0;
-    g.node_depth[rb] = 0;
-  }
-}
-
 // mctx search.simulate through the JUMP records, for root r.  WG: the calling workgroup belongs to this root alone
 // -- every row repeats the (O(1)) selection, so every thread knows the parent and the whole workgroup gathers its
 // embedding row (a separate transfer kernel costs its own 4.7 us minimum); otherwise one 16-lane row per root.
@@ -288,56 +50,21 @@ MZ_DEV void jump_select_core(const StepArgs& s, const JumpArgs& g, const TreeVie
                              int& depth) {
   const int lane = opaque_tid() & 63;
   const int j = lane & 15;
-  const int N = s.N, A = s.A;
+  const int N = s.N;
   const size_t rb = (size_t)r * N;
-  const uint64_t rg = s.root_offset + (uint64_t)r;
-  const int NB = (A + 1) / 2;
-  uint32_t k0 = 0, k1 = 0, s0 = 0, s1 = 0;
-  int klevel = -1;  // key walk not started
+  SimKeys K;
   int jw = T.jpa[0], level = T.jlv[0];
   for (;;) {
     parent = jw & 0xffff;
     action = (jw >> 16) & 0xff;
     if (jw < 0 && level + 1 <= s.max_depth) {
       // near tie at `parent`: score + 1e-7 * uniform(action_selection_key of this level), as mctx
-      if (klevel < 0) {
-        uint32_t x0, x1;
-        bool second;
-        bits_block(2 * s.global_batch, 2 * rg + (uint64_t)(j & 1), x0, x1, second);
-        threefry2x32(s.sim_keys[2 * sim], s.sim_keys[2 * sim + 1], x0, x1);
-        const uint32_t word = second ? x1 : x0;
-        k0 = bcast_u<0>(word);
-        k1 = bcast_u<1>(word);
-        klevel = 0;
-      }
-      while (klevel <= level) {  // rng_key, action_selection_key = split(rng_key), level by level
-        uint32_t x0 = (uint32_t)(j & 1), x1 = 2u + (uint32_t)(j & 1);
-        threefry2x32(k0, k1, x0, x1);
-        k0 = bcast_u<0>(x0); k1 = bcast_u<1>(x0);
-        s0 = bcast_u<0>(x1); s1 = bcast_u<1>(x1);
-        klevel += 1;
-      }
+      sim_keys_advance(s, sim, r, j, K, level);
       float sc[kMaxAS];
       int cidx[kMaxAS], best, child;
       bool near;
       level_decide(s, T, r, parent, j, sc, cidx, best, child, near);
-      float bscore = -INFINITY;
-      best = 1 << 20;
-      child = -1;
-#pragma unroll
-      for (int t = 0; t < kMaxAS; ++t) {
-        const int a = j + 16 * t;
-        float score = sc[t];
-        if (16 * t < A) {
-          const int jb = a < NB ? a : a - NB;
-          uint32_t x0 = (uint32_t)jb, x1 = (NB + jb < A) ? (uint32_t)(NB + jb) : 0u;
-          threefry2x32(s0, s1, x0, x1);
-          score = score + 1e-7f * uniform_from_bits(a < NB ? x0 : x1);
-        }
-        const bool take = (t == 0) || (score > bscore);
-        if (take) { bscore = score; best = (a < A) ? a : (1 << 20); child = cidx[t]; }
-      }
-      row_argmax<4>(bscore, best, child);
+      noisy_argmax(s.A, j, sc, cidx, K.s0, K.s1, best, child);
       action = best;
       if (child >= 0 && level + 1 < s.max_depth) {
         jw = T.jpa[child * T.ns];
@@ -360,44 +87,16 @@ MZ_DEV void jump_select_core(const StepArgs& s, const JumpArgs& g, const TreeVie
 template <bool WG>
 MZ_DEV void jump_select_body(const StepArgs& s, const JumpArgs& g, const TreeView& T, int sim, int r, int32_t* action_out,
                              float* parent_embedding_out, int* sel_out = nullptr, int* depth_acc = nullptr) {
-  const int j = threadIdx.x & 15;
-  const int N = s.N, E = s.E;
-  const size_t rb = (size_t)r * N;
   int parent, action, depth;
   jump_select_core(s, g, T, sim, r, parent, action, depth);
-  if (sel_out) { sel_out[0] = parent; sel_out[1] = action; sel_out[2] = depth; }
-  if (WG ? threadIdx.x == 0 : j == 0) {
-    s.sel_parent[r] = parent;
-    s.sel_action[r] = action;
-    s.sel_depth[r] = depth;
-    if (depth_acc) *depth_acc += depth;
-    else s.depth_sum[r] += depth;
-    if (action_out) action_out[r] = action;
-    if (WG) s.xfer_node[r] = parent;
-  }
-  if (parent_embedding_out == nullptr) return;
-  const float* src = s.embeddings + (rb + parent) * E;
-  if (WG) {
-    for (int i = threadIdx.x; i < E; i += blockDim.x) parent_embedding_out[(size_t)r * E + i] = src[i];
-  } else {
-    for (int i = j; i < E; i += 16) parent_embedding_out[(size_t)r * E + i] = src[i];
-  }
-}
-
-// WIDE: one 256-thread workgroup per root (wide embedding rows), else one row per root
-template <bool WIDE>
-__global__ __launch_bounds__(256) void jump_select_kernel(StepArgs s, JumpArgs g, int sim, int32_t* action_out,
-                                                           float* parent_embedding_out) {
-  const int r = WIDE ? (int)blockIdx.x : (int)(blockIdx.x * (blockDim.x >> 4) + (threadIdx.x >> 4));
-  if (r >= s.B) return;
-  jump_select_body<WIDE>(s, g, tree_view_global(s, g, (size_t)r * s.N), sim, r, action_out, parent_embedding_out);
+  store_selection<WG>(s, r, parent, action, depth, action_out, parent_embedding_out, WG, sel_out, depth_acc);
 }
 
 // mctx search.expand + search.backward + refresh of the decisions on the path: one workgroup per root.
 // `next_action_out` != null: the NEXT simulation's selection (simulate() of sim + 1: the root's fresh JUMP record is
 // in this workgroup's hands) and the gather of its parent's embedding row run as the tail of this launch -- one launch
 // and one kernel boundary fewer per simulation (mzs_expand_backup_select).
-// The body is a device function of the calling workgroup (any multiple of 64 threads): the step-wise kernel below runs
+// The body is a device function of the calling workgroup (any multiple of 64 threads): the step-wise kernel runs
 // it on a workgroup of its own, the fused ResNet search (mz_search_conv.hip) as the tail of the recurrent_fn pass of
 // the same root.  `prior_logits_row`: the root's A logits; `next_embedding_row` == nullptr: the caller has written the
 // new node's embedding row in place; `select_next`: also run simulate() of sim + 1 (sel_out[0..2] = its parent / action / depth
@@ -534,21 +233,7 @@ MZ_DEV void jump_expand_backup_body(const StepArgs& s, const JumpArgs& g, const 
   if (early_chain && (tid >> 6) == 1) return_chain(rw, ds, Gs, v, depth, tid & 63, true, rew_new, dis_new);
   // -- expand (row 0): prior of the new node, node and edge records --
   if (row == 0) {
-    float x[kMaxAS], pr[kMaxAS];
-#pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) {
-      const int a = j + 16 * t;
-      x[t] = a < A ? prior_logits_row[a] : 0.0f;
-    }
-    row_softmax_rt(x, A, j, pr);
-#pragma unroll
-    for (int t = 0; t < kMaxAS; ++t) {
-      const int a = j + 16 * t;
-      if (a < A) {
-        s.children_prior_logits[(rb + newn) * A + a] = x[t];
-        T.prob[(newn * A + a) * T.cs] = pr[t];
-      }
-    }
+    expand_prior_row(s, T, rb, newn, prior_logits_row, j);
     if (j == 0) {
       s.raw_values[rb + newn] = v;
       T.nval[newn * T.ns] = v;
@@ -696,19 +381,5 @@ MZ_DEV void jump_expand_backup_body(const StepArgs& s, const JumpArgs& g, const 
   }
   MZ_JT(6)
 }
-template <bool GUMBEL>
-__global__ __launch_bounds__(1024) void jump_expand_backup_kernel(StepArgs s, JumpArgs g, int sim, const float* reward,
-                                                                  const float* discount, const float* prior_logits,
-                                                                  const float* value, const float* next_embedding,
-                                                                  int32_t* next_action_out,
-                                                                  float* next_parent_embedding_out) {
-  extern __shared__ int lds_i[];
-  const int r = blockIdx.x;
-  jump_expand_backup_body<GUMBEL>(s, g, tree_view_global(s, g, (size_t)r * s.N), sim, r, lds_i, reward[r], discount[r], prior_logits + (size_t)r * s.A, value[r],
-                                  next_embedding + (size_t)r * s.E, next_action_out != nullptr, next_action_out,
-                                  next_parent_embedding_out);
-}
-
-#undef MZ_JROW_SETUP
 
 }  // namespace mz

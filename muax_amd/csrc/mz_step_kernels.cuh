@@ -1,0 +1,353 @@
+// mz_step_kernels.cuh -- every __global__ of the step-wise path, for mz_stepwise.hip alone (the unit that launches
+// them): the WALKING kernels (step_*: mctx's level-by-level simulate() and a one-lane backward, for a tree of more than
+// kJumpMaxNodes nodes, one over the slab budget, or MZS_STEP_WALK=1), the CACHED-DECISION kernels (jump_*: the bodies of
+// mz_step_jump.cuh) and what both share (root, finish, wide embedding rows).  Both sets give the same bits: every
+// per-node rule they apply is a device function of mz_step.cuh.
+#pragma once
+#include "mz_step_jump.cuh"
+
+#pragma clang fp contract(off)
+
+namespace mz {
+
+// one 16-lane row per root
+#define MZ_ROW_SETUP                                                  \
+  const int lane = threadIdx.x & 63;                                  \
+  const int j = lane & 15;                                            \
+  const int r = blockIdx.x * (blockDim.x >> 4) + (threadIdx.x >> 4);  \
+  if (r >= s.B) return;                                               \
+  const int N = s.N, A = s.A, E = s.E;                                \
+  const size_t rb = (size_t)r * N;                                    \
+  (void)lane; (void)N; (void)A; (void)E;
+
+// mctx instantiate_tree_from_root + muzero_policy prelude (dirichlet, mask)
+__global__ __launch_bounds__(256) void step_root_kernel(StepArgs s, const float* prior_logits,
+                                                         const float* value, const float* embedding,
+                                                         const uint8_t* invalid, const float* noise,
+                                                         float fraction, int gumbel_policy,
+                                                         const float* gumbel_in, uint32_t gk0, uint32_t gk1) {
+  MZ_ROW_SETUP
+  for (int n = j; n < N; n += 16) {
+    s.node_visits[rb + n] = 0;
+    s.raw_values[rb + n] = 0.0f;
+    s.node_values[rb + n] = 0.0f;
+    s.parents[rb + n] = -1;
+    s.action_from_parent[rb + n] = -1;
+  }
+  for (int i = j; i < N * A; i += 16) {
+    size_t o = rb * A + i;
+    s.children_index[o] = -1;
+    s.children_prior_logits[o] = 0.0f;
+    s.children_prior_probs[o] = 0.0f;
+    s.children_values[o] = 0.0f;
+    s.children_visits[o] = 0;
+    s.children_rewards[o] = 0.0f;
+    s.children_discounts[o] = 0.0f;
+  }
+  if (!s.wide)  // (wide: zeroed by a memset on the stream)
+    for (size_t i = j; i < (size_t)N * E; i += 16) s.embeddings[rb * E + i] = 0.0f;
+  float x[kMaxAS], pr[kMaxAS], lg[kMaxAS];
+  bool inv[kMaxAS];
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    int a = j + 16 * t;
+    x[t] = a < A ? prior_logits[(size_t)r * A + a] : 0.0f;
+    inv[t] = (invalid != nullptr && a < A) ? invalid[(size_t)r * A + a] != 0 : false;
+    if (a < A) s.root_invalid[(size_t)r * A + a] = inv[t] ? 1 : 0;
+  }
+  bool any_invalid = false;
+  if (!gumbel_policy) {
+    // mctx muzero_policy prelude: Dirichlet mix, log
+    row_softmax_rt(x, A, j, pr);
+    float keep = 1.0f - fraction;
+#pragma unroll
+    for (int t = 0; t < kMaxAS; ++t) {
+      int a = j + 16 * t;
+      float nz = (noise != nullptr && a < A) ? noise[(size_t)r * A + a] : 0.0f;
+      float noisy = keep * pr[t] + fraction * nz;
+      lg[t] = log_pos(fmaxf(noisy, kFltTiny));
+    }
+    any_invalid = invalid != nullptr;
+  } else {
+    // mctx gumbel_muzero_policy: the logits only pass through _mask_invalid_actions; root Gumbel noise
+    const uint64_t rg = s.root_offset + (uint64_t)r;
+#pragma unroll
+    for (int t = 0; t < kMaxAS; ++t) {
+      int a = j + 16 * t;
+      lg[t] = x[t];
+      any_invalid = any_invalid || inv[t];
+      if (a < A) {
+        float g;
+        if (gumbel_in != nullptr) {
+          g = gumbel_in[(size_t)r * A + a];
+        } else {
+          uint32_t x0, x1;
+          bool second;
+          bits_block(s.global_batch * (uint64_t)A, rg * (uint64_t)A + (uint64_t)a, x0, x1, second);
+          threefry2x32(gk0, gk1, x0, x1);
+          g = s.gumbel_scale * gumbel_from_bits(second ? x1 : x0);
+        }
+        s.root_gumbel[(size_t)r * A + a] = g;
+      }
+    }
+  }
+  float pq[kMaxAS];
+  row_mask_invalid_softmax(lg, inv, any_invalid, A, j, pq);
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    int a = j + 16 * t;
+    if (a < A) {
+      s.children_prior_logits[rb * A + a] = lg[t];
+      s.children_prior_probs[rb * A + a] = pq[t];
+    }
+  }
+  if (s.wide) {
+    if (j == 0) s.xfer_node[r] = 0;
+  } else {
+    for (int i = j; i < E; i += 16) s.embeddings[rb * E + i] = embedding[(size_t)r * E + i];
+  }
+  if (j == 0) {
+    s.node_visits[rb] = 1;
+    s.raw_values[rb] = value[r];
+    s.node_values[rb] = value[r];
+    s.depth_sum[r] = 0;
+  }
+}
+
+// mctx search.simulate, level by level from the root (+ the parent-embedding gather of search.expand): the decisions of
+// mz_step.cuh on the HBM tree, the visited (node, action) pairs staged in `path` for the backward pass
+template <bool GUMBEL>
+MZ_DEV void walk_select(const StepArgs& s, int sim, int r, int j, int32_t* action_out, float* parent_embedding_out) {
+  const size_t rb = (size_t)r * s.N;
+  const TreeView T = tree_view_global(s, rb);
+  SimKeys K;
+  int node = 0, depth = 0, parent = 0, action = 0;
+  for (;;) {
+    int best, child;
+    if constexpr (GUMBEL) {
+      gumbel_decide(s, rb, r, node, j, best, child);
+    } else {
+      float sc[kMaxAS];
+      int cidx[kMaxAS];
+      bool near;
+      level_decide(s, T, r, node, j, sc, cidx, best, child, near);
+      if (near) {  // (never without s.tiebreak)
+        sim_keys_advance(s, sim, r, j, K, depth);
+        noisy_argmax(s.A, j, sc, cidx, K.s0, K.s1, best, child);
+      }
+    }
+    if (j == 0) s.path[rb + depth] = node | (best << 16);
+    parent = node;
+    action = best;
+    depth += 1;
+    if (child == -1 || depth >= s.max_depth) break;
+    node = child;
+  }
+  store_selection<false>(s, r, parent, action, depth, action_out, s.wide ? nullptr : parent_embedding_out, s.wide != 0);
+}
+__global__ __launch_bounds__(256) void step_select_kernel(StepArgs s, int sim, int32_t* action_out,
+                                                           float* parent_embedding_out) {
+  MZ_ROW_SETUP
+  walk_select<false>(s, sim, r, j, action_out, parent_embedding_out);
+}
+// ... with gumbel_muzero_{root,interior}_action_selection
+__global__ __launch_bounds__(256) void step_select_gumbel_kernel(StepArgs s, int sim, int32_t* action_out,
+                                                                  float* parent_embedding_out) {
+  MZ_ROW_SETUP
+  walk_select<true>(s, sim, r, j, action_out, parent_embedding_out);
+}
+
+// mctx search.expand (update_tree_node + edge) and search.backward
+__global__ __launch_bounds__(256) void step_expand_backup_kernel(StepArgs s, int sim, const float* reward,
+                                                                  const float* discount,
+                                                                  const float* prior_logits,
+                                                                  const float* value,
+                                                                  const float* next_embedding) {
+  MZ_ROW_SETUP
+  const int parent = s.sel_parent[r], action = s.sel_action[r], depth = s.sel_depth[r];
+  const size_t eo = (rb + parent) * A + action;
+  int next = s.children_index[eo];
+  const int newn = next == -1 ? sim + 1 : next;
+  const float v = value[r];
+  expand_prior_row(s, tree_view_global(s, rb), rb, newn, prior_logits + (size_t)r * A, j);
+  if (s.wide) {
+    if (j == 0) s.xfer_node[r] = newn;
+  } else {
+    for (int i = j; i < E; i += 16) s.embeddings[(rb + newn) * E + i] = next_embedding[(size_t)r * E + i];
+  }
+  const float rew_new = reward[r], dis_new = discount[r];
+  if (j == 0) {
+    s.raw_values[rb + newn] = v;
+    s.node_values[rb + newn] = v;
+    s.node_visits[rb + newn] = s.node_visits[rb + newn] + 1;
+    s.children_index[eo] = newn;
+    s.children_rewards[eo] = rew_new;
+    s.children_discounts[eo] = dis_new;
+    s.parents[rb + newn] = parent;
+    s.action_from_parent[rb + newn] = action;
+    // backward along the staged path (only this lane touches these words)
+    float leaf = v, childv = v;
+    for (int d = depth - 1; d >= 0; --d) {
+      int pk = s.path[rb + d];
+      int pn = pk & 0xffff, pa = pk >> 16;
+      size_t e2 = (rb + pn) * A + pa;
+      int cnt = s.node_visits[rb + pn];
+      float rw = (d == depth - 1) ? rew_new : s.children_rewards[e2];
+      float ds = (d == depth - 1) ? dis_new : s.children_discounts[e2];
+      leaf = rw + ds * leaf;
+      float newv = (s.node_values[rb + pn] * (float)cnt + leaf) / ((float)cnt + 1.0f);
+      s.node_values[rb + pn] = newv;
+      s.node_visits[rb + pn] = cnt + 1;
+      s.children_values[e2] = childv;
+      s.children_visits[e2] = s.children_visits[e2] + 1;
+      childv = newv;
+    }
+  }
+}
+
+// mctx Tree.summary + _apply_temperature + jax.random.categorical
+__global__ __launch_bounds__(256) void step_finish_kernel(StepArgs s, float temperature, const float* gumbel,
+                                                           uint32_t ks0, uint32_t ks1, int32_t* action_out,
+                                                           float* action_weights_out, float* search_value_out,
+                                                           int32_t* depth_sum_out) {
+  MZ_ROW_SETUP
+  const uint64_t rg = s.root_offset + (uint64_t)r;
+  int vc[kMaxAS];
+  int part = 0;
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    int a = j + 16 * t;
+    vc[t] = a < A ? s.children_visits[rb * A + a] : 0;
+    part += vc[t];
+  }
+  float total = (float)row_sum_i(part);
+  float denom = fmaxf(total, 1.0f);
+  float lg[kMaxAS], prob[kMaxAS];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    int a = j + 16 * t;
+    float p = (float)vc[t] / denom;
+    p = total > 0.0f ? p : 1.0f / (float)A;
+    prob[t] = p;
+    lg[t] = log_pos(fmaxf(p, kFltTiny));
+    mx = a < A ? fmaxf(mx, lg[t]) : mx;
+  }
+  mx = row_max<4>(mx);
+  float tden = fmaxf(temperature, kFltTiny);
+  float bscore = -INFINITY;
+  int best = 1 << 20, dummy = 0;
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    int a = j + 16 * t;
+    bool ok = a < A;
+    float g;
+    if (gumbel != nullptr) {
+      g = ok ? gumbel[(size_t)r * A + a] : 0.0f;
+    } else {
+      uint32_t x0, x1;
+      bool second;
+      bits_block(s.global_batch * (uint64_t)A, rg * (uint64_t)A + (uint64_t)(ok ? a : 0), x0, x1, second);
+      threefry2x32(ks0, ks1, x0, x1);
+      g = gumbel_from_bits(second ? x1 : x0);
+    }
+    float score = ok ? (lg[t] - mx) / tden + g : -INFINITY;
+    if (ok) action_weights_out[(size_t)r * A + a] = prob[t];
+    bool take = (t == 0) || (ok && score > bscore);
+    if (take) { bscore = score; best = ok ? a : (1 << 20); }
+  }
+  row_argmax<4>(bscore, best, dummy);
+  if (j == 0) {
+    action_out[r] = best;
+    if (search_value_out) search_value_out[r] = s.node_values[rb];
+    if (depth_sum_out) depth_sum_out[r] = s.depth_sum[r];
+  }
+}
+
+// tail of mctx gumbel_muzero_policy: best considered action + completed-Q policy target
+__global__ __launch_bounds__(256) void step_finish_gumbel_kernel(StepArgs s, int32_t* action_out,
+                                                                  float* action_weights_out,
+                                                                  float* search_value_out, int32_t* depth_sum_out) {
+  MZ_ROW_SETUP
+  float qv[kMaxAS], logits[kMaxAS];
+  int vc[kMaxAS], cidx[kMaxAS] = {0, 0, 0, 0}, sum_visits, next;
+  row_qtransform(s, rb, 0, A, j, qv, vc, logits, sum_visits);
+  int mxv = 0;
+  bool inv[kMaxAS], any_inv = false;
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    mxv = max(mxv, vc[t]);
+    inv[t] = j + 16 * t < A && s.root_invalid[(size_t)r * A + j + 16 * t];
+    any_inv = any_inv || inv[t];
+  }
+  const int considered_visit = row_max_i(mxv);
+  const int best = row_gumbel_argmax(s, r, A, j, considered_visit, logits, qv, vc, cidx, next);
+  float x[kMaxAS], w[kMaxAS];
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) x[t] = logits[t] + qv[t];
+  row_mask_invalid_softmax(x, inv, any_inv, A, j, w);
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t)
+    if (j + 16 * t < A) action_weights_out[(size_t)r * A + j + 16 * t] = w[t];
+  if (j == 0) {
+    action_out[r] = best;
+    if (search_value_out) search_value_out[r] = s.node_values[rb];
+    if (depth_sum_out) depth_sum_out[r] = s.depth_sum[r];
+  }
+}
+
+// ---- wide embedding rows: one workgroup per (root, KiB of the row) ----
+// dir 0: rows[b] <- tree.embeddings[b][xfer_node[b]]   (parent embedding for recurrent_fn)
+// dir 1: tree.embeddings[b][xfer_node[b]] <- rows[b]   (root / next embedding)
+__global__ __launch_bounds__(256) void emb_xfer_kernel(const StepArgs s, float* rows, int dir) {
+  const int b = blockIdx.x;
+  const size_t E = (size_t)s.E;
+  float* node = s.embeddings + ((size_t)b * s.N + s.xfer_node[b]) * E;
+  float* row = rows + (size_t)b * E;
+  const size_t i0 = (size_t)blockIdx.y * 1024, i1 = i0 + 1024 < E ? i0 + 1024 : E;
+  if (dir == 0)
+    for (size_t i = i0 + threadIdx.x; i < i1; i += 256) row[i] = node[i];
+  else
+    for (size_t i = i0 + threadIdx.x; i < i1; i += 256) node[i] = row[i];
+}
+
+// root decision (after step_root_kernel): one row per root
+template <bool GUMBEL>
+__global__ __launch_bounds__(256) void jump_root_kernel(StepArgs s, JumpArgs g) {
+  MZ_ROW_SETUP
+  int best, child;
+  bool near;
+  decide_any<GUMBEL>(s, tree_view_global(s, g, rb), rb, r, 0, j, best, child, near);
+  if (j == 0) {
+    g.jump_pa[rb] = best << 16 | (near ? (int)0x80000000 : 0);
+    g.jump_lv[rb] = 0;
+    g.node_depth[rb] = 0;
+  }
+}
+
+// WIDE: one 256-thread workgroup per root (wide embedding rows), else one row per root
+template <bool WIDE>
+__global__ __launch_bounds__(256) void jump_select_kernel(StepArgs s, JumpArgs g, int sim, int32_t* action_out,
+                                                           float* parent_embedding_out) {
+  const int r = WIDE ? (int)blockIdx.x : (int)(blockIdx.x * (blockDim.x >> 4) + (threadIdx.x >> 4));
+  if (r >= s.B) return;
+  jump_select_body<WIDE>(s, g, tree_view_global(s, g, (size_t)r * s.N), sim, r, action_out, parent_embedding_out);
+}
+
+// mctx search.expand + search.backward + refresh of the decisions on the path, on a workgroup of its own per root
+template <bool GUMBEL>
+__global__ __launch_bounds__(1024) void jump_expand_backup_kernel(StepArgs s, JumpArgs g, int sim, const float* reward,
+                                                                  const float* discount, const float* prior_logits,
+                                                                  const float* value, const float* next_embedding,
+                                                                  int32_t* next_action_out,
+                                                                  float* next_parent_embedding_out) {
+  extern __shared__ int lds_i[];
+  const int r = blockIdx.x;
+  jump_expand_backup_body<GUMBEL>(s, g, tree_view_global(s, g, (size_t)r * s.N), sim, r, lds_i, reward[r], discount[r], prior_logits + (size_t)r * s.A, value[r],
+                                  next_embedding + (size_t)r * s.E, next_action_out != nullptr, next_action_out,
+                                  next_parent_embedding_out);
+}
+
+#undef MZ_ROW_SETUP
+
+}  // namespace mz

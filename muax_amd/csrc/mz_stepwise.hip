@@ -1,5 +1,6 @@
-// mz_stepwise.hip -- the routes on the HBM tree of mz_step.cuh, whose kernels THIS unit emits: the step-wise entry points
-// for plugin nets (mzs_root .. mzs_finish, mzs_tree_export) and the generic one-launch act() (mz_mlp_generic.cuh).
+// mz_stepwise.hip -- the routes on the HBM tree of mz_step.cuh, whose kernels (mz_step_kernels.cuh) THIS unit emits: the
+// step-wise entry points for plugin nets (mzs_root .. mzs_finish, mzs_tree_export) and the generic one-launch act()
+// (mz_mlp_generic.cuh).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -7,6 +8,7 @@
 
 #include "mz_handle.h"
 #include "mz_mlp_generic.cuh"
+#include "mz_step_kernels.cuh"
 
 using mzh::fail;
 

@@ -12,7 +12,6 @@
 #pragma once
 // mz_mlp_generic.cuh defines the root kernel of the generic act() route, which mz_stepwise.hip emits; this unit takes the
 // header's device functions only, so its copy of that kernel gets a name of its own (never launched)
-#define MZ_NO_STEP_KERNELS
 #define mz_mlp_root_kernel mz_unroll_unused_root_kernel
 #include "mz_mlp_generic.cuh"
 #undef mz_mlp_root_kernel

@@ -339,7 +339,7 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_act_wide_kernel(const F
       int best = at ? __builtin_ctzll(at) : 0;
       if constexpr (TIEBREAK) {
         // mctx adds 1e-7 * uniform[0, 1) to every score; if fl(score_a + 1e-7) < best for every other action the draw cannot
-        // change the argmax (rounding is monotone): only a near tie pays for the threefry blocks (mz_step.cuh)
+        // change the argmax (rounding is monotone): only a near tie pays for the threefry blocks (mz_step.cuh, noisy_argmax)
         const bool unsafe = ok && lane != best && !((sc + 1e-7f) < top);
         if (__builtin_amdgcn_ballot_w64(unsafe) != 0) {
           uint32_t s0 = 0, s1 = 0;

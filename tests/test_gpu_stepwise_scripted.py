@@ -1,4 +1,5 @@
-"""The step-wise kernels (mz_step.cuh, mz_step_jump.cuh, mz_stepwise.hip) against the C oracle, both fed the same
+"""The step-wise kernels (mz_step_kernels.cuh: the walking and the cached-decision set, both built from the per-node rules
+of mz_step.cuh, the second through the bodies of mz_step_jump.cuh; launched by mz_stepwise.hip) against the C oracle, both fed the same
 *script* instead of a net (tests/scripted_search.py): per-edge discounts with exact 0s and 1s, re-expansions that write
 other numbers than the first expansion, exact ties, logits of -1e9 and +-80, rewards in the thousands next to 1e-3, one
 line 130 levels deep.  The bar is the project's: the selected action and the parent embedding at every simulation, the
@@ -125,6 +126,30 @@ def test_wide_embedding_rows(oracle, walk, fused_select, monkeypatch):
     if walk:
         monkeypatch.setenv("MZS_STEP_WALK", "1")
     _run(oracle, "generic", 17, 7, 12, 70, e=260, tiebreak=True, fused_select=fused_select)
+
+
+@pytest.mark.parametrize("fused_select", [False, True])
+@pytest.mark.parametrize("S", [1023, 1024])
+def test_tree_size_where_the_walking_kernels_take_over(oracle, S, fused_select, monkeypatch):
+    """No MZS_STEP_WALK: S = 1023 (1024 nodes, kJumpMaxNodes) is the largest tree of the cached-decision kernels (their
+    LDS at 15 x 1025 words), S = 1024 the smallest one the walking kernels get by size alone.  Which set ran is read off
+    mzs_resnet_search, whose first question is whether the handle's tree has cached decisions: without them it answers
+    MZS_E_UNSUPPORTED, with them it goes on to reject its (null) arguments."""
+    from muax_amd import _lib
+    monkeypatch.delenv("MZS_STEP_WALK", raising=False)
+    monkeypatch.delenv("MZS_JUMP_BUDGET_MB", raising=False)
+    for family in ("generic", "deep_line"):
+        sc = ss.make_script(family, S, 3, 2, E, S)
+        res = ss.drive_hip_script(oracle, sc, tiebreak=True, fused_select=fused_select)
+        _check_against_script(sc, res, None)
+        h = res["handle"]
+        rc = _lib.load().mzs_resnet_search(h._h, None, 1.0, 0, 1, None)
+        msg = _lib.load().mzs_last_error(h._h).decode()
+        if S + 1 <= 1024:
+            assert rc == _lib.MZS_E_INVALID and "cached decisions" not in msg, (rc, msg)
+        else:
+            assert rc == _lib.MZS_E_UNSUPPORTED and "cached decisions" in msg, (rc, msg)
+        h.close()
 
 
 @pytest.mark.parametrize("policy", ["muzero", "gumbel"])
