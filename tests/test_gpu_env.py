@@ -19,87 +19,20 @@ import pytest
 import torch
 
 import cartpole_reference as cp
+import env_abi
 import muax_amd as mx
+from env_abi import _bits32
 from muax_amd import _lib, prng
-from replay_abi import Guarded
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-MIDDLE = np.array([False, True, False])
 MAX_DIFF = {"step": 0.0, "n": 0}  # the largest |device - reference| of a stepped state component, and how many states
+CARTPOLE = env_abi.EnvAbi(_lib.MzsEnvCartPole, "mzs_env_cartpole_reset", "mzs_env_cartpole_step", 4, 4)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class Env:
-    """Guarded buffers of one mzs_env_cartpole and the two calls."""
-
-    def __init__(self, N, max_steps, seed, state=None, t=None, draws=None):
-        self.N, self.max_steps, self.key = int(N), int(max_steps), prng.PRNGKey(seed)
-        z = np.zeros
-        self.g = dict(state=Guarded.of(z((N, 4)) if state is None else np.asarray(state, np.float64)),
-                      t=Guarded.of(np.asarray(z(N) if t is None else t, np.int32)),
-                      draws=Guarded.of(np.asarray(z(N) if draws is None else draws, np.int32)),
-                      obs=Guarded(N, 4, torch.float32, flat=False), a=Guarded(N, 1, torch.int32),
-                      r=Guarded(3, N, torch.float64, flat=False), done=Guarded(3, N, torch.uint8, flat=False))
-        self.L = _lib.load()
-        self.env = self.descriptor()
-
-    def descriptor(self, **over):
-        d = _lib.MzsEnvCartPole()
-        d.struct_size = C.sizeof(_lib.MzsEnvCartPole)
-        d.device, d.num_envs, d.max_episode_steps = torch.cuda.current_device(), self.N, self.max_steps
-        d.key[0], d.key[1] = int(self.key[0]), int(self.key[1])
-        d.state, d.t, d.draws = self.g["state"].ptr, self.g["t"].ptr, self.g["draws"].ptr
-        for k, v in over.items():
-            setattr(d, k, v)
-        return d
-
-    def step_args(self, **over):
-        s = _lib.MzsEnvStepArgs()
-        s.struct_size = C.sizeof(_lib.MzsEnvStepArgs)
-        s.a, s.obs_out = self.g["a"].ptr, self.g["obs"].ptr
-        s.r_out, s.done_out = self.g["r"].t[1].data_ptr(), self.g["done"].t[1].data_ptr()
-        for k, v in over.items():
-            setattr(s, k, v)
-        return s
-
-    def _call(self, fn, args, writes):
-        """`writes`: the buffers the call may write (r and done: their middle row only)."""
-        torch.cuda.synchronize()
-        before = {n: g.bits.clone() for n, g in self.g.items()}
-        rc = fn(*args, _stream())
-        torch.cuda.synchronize()
-        for n, g in self.g.items():
-            assert g.guards_intact(), f"{fn.__name__}: a guard of {n} was overwritten"
-            same = g.bits == before[n]
-            if rc == _lib.MZS_OK and n in writes:
-                same |= g.row_mask(MIDDLE if n in ("r", "done") else np.ones(g.rows, bool))
-            assert bool(same.all()), f"{fn.__name__}: {n} changed where it must not"
-        return rc
-
-    def reset(self, env=None, obs="own"):
-        obs = self.g["obs"].ptr if obs == "own" else obs
-        return self._call(self.L.mzs_env_cartpole_reset, (C.byref(env or self.env), C.c_void_p(obs)),
-                          ("state", "t", "draws", "obs"))
-
-    def step(self, a=None, env=None, args=None):
-        if a is not None:
-            self.g["a"].t.copy_(torch.as_tensor(np.asarray(a, np.int32)))
-        return self._call(self.L.mzs_env_cartpole_step, (C.byref(env or self.env), C.byref(args or self.step_args())),
-                          ("state", "t", "draws", "obs", "r", "done"))
-
-    def host(self):
-        """(state [N, 4] f64, t, draws, obs [N, 4] f32, r [N], done [N]) as the device holds them."""
-        g = self.g
-        return (g["state"].host(), g["t"].host(), g["draws"].host(), g["obs"].host(), g["r"].host()[1],
-                g["done"].host()[1])
-
-
-def _bits32(x):
-    return np.ascontiguousarray(x, F32).view(np.uint32)
+def Env(N, max_steps, seed, **buffers):
+    """Guarded buffers of one mzs_env_cartpole and the two calls (tests/env_abi.Env)."""
+    return env_abi.Env(CARTPOLE, N, max_steps, seed, **buffers)
 
 
 def _check_step(env, prev, a):
