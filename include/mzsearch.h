@@ -891,6 +891,57 @@ typedef struct mzs_env_classic {
 int mzs_env_classic_reset(const mzs_env_classic *env, float *obs_out, void *stream);
 int mzs_env_classic_step(const mzs_env_classic *env, const mzs_env_step_args *a, void *stream);
 
+/* ---- vector environments stepped on the device: 2048, with the legal-move mask of every returned observation ----
+ * Board: one uint64 per environment; nibble i (bits 4 i .. 4 i + 3) is the exponent of cell i, row-major, cell 0
+ *   top-left.  Exponent 0 is empty, exponent k is tile 2^k.
+ * Moves: actions 0 up, 1 right, 2 down, 3 left; any other value is treated as illegal.  A move slides every line toward
+ *   its edge and merges equal neighbours once per tile, starting from that edge: 2 2 2 2 -> 4 4 . . and
+ *   2 2 4 . -> 4 4 . .  Two tiles of exponent 15 do not merge.
+ * Reward: the sum of the tiles created by merging, as fp64, times 2^-reward_shift (reward_shift 0..11): a power of two
+ *   keeps every reward and every partial sum exact, so sequential and pairwise sums of an episode have the same bits.
+ * Illegal moves: a move that would leave the board unchanged is illegal.  Taking it is a no-op: reward 0, no spawn, no
+ *   draw consumed; t still advances.
+ * Spawns: after a legal move one tile spawns.  With d = draws[e] and (x0, x1) = threefry2x32(key, (e, d)) -- the block
+ *   and counter convention of the other environments' u53 -- and n the number of empty cells, enumerated in ascending
+ *   cell index, the cell chosen is number k = (uint64(x0) * n) >> 32 of them and the spawned exponent is 2 if
+ *   x1 < 0x1999999A, else 1; then draws[e] grows by one.  A reset spawns twice on an empty board.
+ * Termination: terminated = the board after the step has no legal move (no move changes it; evaluated after a no-op as
+ *   well, so an uploaded dead board -- an empty one included -- ends on its next step); done_out = terminated or
+ *   t + 1 >= max_episode_steps.  A finished environment resets in the same launch and sets t = 0: obs_out and the mask
+ *   are already the next episode's.
+ * Observation: obs_out float32 [N, 16], obs[i] = exponent_i / 16 (exact).
+ * Mask: invalid uint8 [N, 4], 1 where the move is illegal for the returned observation.  A board with no tile at all
+ *   reports every move as legal (zero-padded reanalysis rows: an all-invalid root must never reach a search).
+ * The descriptor and its four arrays are the caller's device memory; the mask lies in the descriptor, beside the state
+ * the launch already owns, and mzs_env_step_args is the other environments'.  Zeroed t and draws are a valid start; the
+ * board is whatever mzs_env_2048_reset or the caller put there.
+ * reset, step: one launch, one thread per environment, integer work in registers (no table in memory), on the caller's
+ * stream; no allocation, no copy to the host, no synchronisation.  MZS_E_INVALID before any launch, nothing written,
+ * for a struct size, a null pointer, num_envs < 1, max_episode_steps < 1, reward_shift outside 0..11, a board that is
+ * not 8-byte aligned, an invalid that is not 4-byte aligned (the mask is one 32-bit store) or an obs_out that is not
+ * 16-byte aligned (four float4 stores).  errors: mzs_last_error(NULL) */
+typedef struct mzs_env_2048 {
+  int32_t struct_size;       /* = sizeof(mzs_env_2048) */
+  int32_t device;
+  int32_t num_envs;          /* N */
+  int32_t max_episode_steps;
+  uint32_t key[2];
+  int32_t reward_shift;      /* 0..11: rewards are scaled by 2^-reward_shift */
+  int32_t reserved0;
+  uint64_t *board;           /* [N] */
+  int32_t *t;                /* [N] steps of the open episode */
+  int32_t *draws;            /* [N] spawns drawn so far */
+  uint8_t *invalid;          /* [N, 4] out: 1 where the move is illegal for the returned observation */
+} mzs_env_2048;
+int mzs_env_2048_reset(const mzs_env_2048 *env, float *obs_out, void *stream);
+int mzs_env_2048_step(const mzs_env_2048 *env, const mzs_env_step_args *a, void *stream);
+
+/* The same legality rule from observations: invalid_out [B, 4] = the mask of the boards obs [B, 16] encodes, decoded as
+ * exponent = lrintf(obs * 16) clamped to 0..15 (an all-zero row: mask 0).  One launch, one thread per row, on the
+ * caller's stream.  MZS_E_INVALID before any launch for a null pointer, B < 1, an obs that is not 16-byte aligned or an
+ * invalid_out that is not 4-byte aligned. */
+int mzs_env_2048_mask(int32_t device, const float *obs, uint8_t *invalid_out, int32_t B, void *stream);
+
 /* ---- forward value unroll of the default MLP trio: the priorities mzs_replay_update_priorities takes ----
  * For every window j < batch and step i < k_prio, with s_0 = Representation(obs[j]) and s_{i+1} = the next state of
  * Dynamic(s_i, actions[j][i]) (muax/nn.py:59-115):

@@ -10,7 +10,7 @@ from .episode_tracer import NStep, PNStep  # noqa: F401
 from .replay_buffer import Trajectory, TrajectoryReplayBuffer  # noqa: F401
 from .replay_device import DeviceReplayBuffer  # noqa: F401
 from . import envs  # noqa: F401
-from .envs import DeviceAcrobot, DeviceCartPole, DeviceMountainCar  # noqa: F401
+from .envs import Device2048, DeviceAcrobot, DeviceCartPole, DeviceMountainCar  # noqa: F401
 from .loss import Transition, default_loss_fn  # noqa: F401
 from .model import MuZero  # noqa: F401
 from .nn import MZNetwork, MZNetworkParams, create_muzero_network  # noqa: F401

@@ -6,7 +6,8 @@ act() dispatch (mz_act.hip), the step-wise path and the generic one-launch searc
 (mz_stepwise.hip), the training step (mz_train.hip), the self-test and Dirichlet kernels (mz_selftest.hip) --, the
 fused act() kernel instances in five groups (mz_fused_g*.hip, listed in mz_instances.def), the wide-action act()
 kernel (mz_wide.hip), the ResNet recurrent kernel (mz_conv.hip), the device-resident replay (mz_replay.hip), the
-forward value unroll behind its priorities (mz_unroll.hip) and the device vector environments (mz_env.hip).  Only the units whose sources changed are recompiled."""
+forward value unroll behind its priorities (mz_unroll.hip) and the device vector environments (mz_env.hip; 2048 with its
+legal-move masks in mz_env2048.hip).  Only the units whose sources changed are recompiled."""
 from __future__ import annotations
 
 import os
@@ -41,6 +42,7 @@ UNITS = {
     "mz_ez.hip": ["mz_host.h", "mz_ez.cuh", "mz_spec.cuh", _ABI],
     "mz_replay.hip": ["mz_host.h", "mz_replay.cuh", "mz_spec.cuh", _ABI],
     "mz_env.hip": ["mz_host.h", "mz_env.cuh", "mz_spec.cuh", _ABI],
+    "mz_env2048.hip": ["mz_host.h", "mz_env2048.cuh", "mz_2048.h", "mz_spec.cuh", _ABI],
     "mz_unroll.hip": ["mz_host.h", "mz_unroll.cuh", "mz_mlp_generic.cuh", "mz_step_jump.cuh", "mz_step.cuh", "mz_spec.cuh", _ABI],
 }
 SOURCES = list(UNITS)

@@ -214,6 +214,13 @@ class MzsEnvClassic(C.Structure):
                 + [(n, _vp) for n in ("state", "t", "draws")])
 
 
+class MzsEnv2048(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("device", C.c_int32), ("num_envs", C.c_int32),
+                 ("max_episode_steps", C.c_int32), ("key", C.c_uint32 * 2), ("reward_shift", C.c_int32),
+                 ("reserved0", C.c_int32)]
+                + [(n, _vp) for n in ("board", "t", "draws", "invalid")])
+
+
 class MzsUnrollArgs(C.Structure):
     _fields_ = ([("struct_size", C.c_int32), ("device", C.c_int32), ("batch", C.c_int32), ("row_steps", C.c_int32),
                  ("k_prio", C.c_int32), ("num_actions", C.c_int32), ("embed_dim", C.c_int32), ("reserved0", C.c_int32)]
@@ -246,7 +253,8 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_mlp_unroll_values", "mzs_replay_sample_is", "mzs_mlp_loss_grad_weighted",
                     "mzs_replay_stage", "mzs_replay_store_steps", "mzs_replay_plan_steps",
                     "mzs_env_cartpole_reset", "mzs_env_cartpole_step",
-                    "mzs_env_classic_reset", "mzs_env_classic_step"]
+                    "mzs_env_classic_reset", "mzs_env_classic_step",
+                    "mzs_env_2048_reset", "mzs_env_2048_step", "mzs_env_2048_mask"]
 
 _lib = None
 
@@ -329,6 +337,9 @@ def load(build_if_missing: bool = True):
     L.mzs_env_cartpole_step.argtypes = [C.POINTER(MzsEnvCartPole), C.POINTER(MzsEnvStepArgs), _vp]
     L.mzs_env_classic_reset.argtypes = [C.POINTER(MzsEnvClassic), _vp, _vp]
     L.mzs_env_classic_step.argtypes = [C.POINTER(MzsEnvClassic), C.POINTER(MzsEnvStepArgs), _vp]
+    L.mzs_env_2048_reset.argtypes = [C.POINTER(MzsEnv2048), _vp, _vp]
+    L.mzs_env_2048_step.argtypes = [C.POINTER(MzsEnv2048), C.POINTER(MzsEnvStepArgs), _vp]
+    L.mzs_env_2048_mask.argtypes = [C.c_int32, _vp, _vp, C.c_int32, _vp]
     L.mzs_mlp_unroll_values.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsUnrollArgs), _vp]
     L.mzs_tower_pair_scratch_bytes.restype = C.c_int64
     if L.mzs_abi_version() != 1:

@@ -360,7 +360,8 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         order = sorted((e.serial for e in self._eps), key=lambda s: (self._touched[s], s))
         return order[:max(int(count), 0)]
 
-    def reanalyse(self, model, key, n, gamma, alpha=None, weight="mean", serials=None, chunk_rows=4096, **act_kwargs):
+    def reanalyse(self, model, key, n, gamma, alpha=None, weight="mean", serials=None, chunk_rows=4096, mask_fn=None,
+                  **act_kwargs):
         """MuZero Reanalyse on the device: search the stored observations of the episodes `serials` (default: all
         held, oldest first; otherwise in the order given) again with `model` and overwrite, in place, their `pi`
         (search policy) and `v` (root value) and what follows from them -- `Rn`, `done`, `w = |v - Rn| ** alpha`
@@ -375,6 +376,11 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         `act_kwargs` reach act() untouched: its own defaults hold unless given here -- `num_simulations=5`,
         `temperature=1`, and the Dirichlet root noise `dirichlet_fraction=0.25` of acting; pass
         `dirichlet_fraction=0.0` for noise-free targets.  The actions act() returns are discarded.
+        `mask_fn` (e.g. `Device2048.invalid_actions_of`): every chunk is searched with
+        `invalid_actions=mask_fn(chunk)`, a uint8 [chunk_rows, A] device tensor with 1 where the action is illegal in
+        that row's stored observation -- without it the search would write policies with weight on illegal moves into
+        the buffer.  It is called on the padded rows as well (all-zero observations) and must leave such a row at least
+        one legal action.  None: nothing changes, padded rows included.
 
         One upload (descriptors and discount powers), two launches around the searches; no device-to-host copy and
         no synchronisation beyond what act() does on its route.  A serial that is not held is a KeyError, a
@@ -405,8 +411,9 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         keys = prng.split(prng.as_key(key), plan.n_chunks)
         for c in range(plan.n_chunks):
             rows = slice(c * R, (c + 1) * R)
+            mask = {} if mask_fn is None else {"invalid_actions": mask_fn(obs[rows])}
             _, pi_c, v_c = model.act(keys[c], obs[rows], with_pi=True, with_value=True, obs_from_batch=True,
-                                     device_outputs=True, **act_kwargs)
+                                     device_outputs=True, **mask, **act_kwargs)
             pi[rows].copy_(pi_c)
             v[rows].copy_(v_c)
         a = _lib.args(_lib.MzsReplayReanalyseArgs, gpow=ptrs["gpow"], pi=pi.data_ptr(), v=v.data_ptr(), **stream_args,

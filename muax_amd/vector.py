@@ -256,10 +256,17 @@ class DeviceVectorCollector:
         launches go on the one stream the staging launch uses, which orders the environment's overwrite of its
         observation tensor after the staging launch that read it.  Afterwards the call's rows of `r` and of the flags
         come down, in at most two copies each.  Returns (key, R [T, N] float64, D [T, N] bool); under `device_plan`
-        nothing comes down and R, D are None."""
+        nothing comes down and R, D are None.
+        A device environment with `invalid_actions_device` (the mask extension of muax_amd/envs.py, e.g. `Device2048`;
+        looked for once per call) has that tensor passed to every act() as `invalid_actions`: the environment's own
+        uint8 [N, A] mask of the observation act() is given, the same object every step.  The same stream order holds
+        for it: the environment's overwrite of the mask comes after the search that read it.  An environment without
+        the method gets exactly the act() calls it always got."""
         import torch
         venv, S = self.venv, self.ring_steps
         on_device = hasattr(venv, "step_device")
+        if on_device and hasattr(venv, "invalid_actions_device"):
+            act_kwargs = {"invalid_actions": venv.invalid_actions_device(), **act_kwargs}  # (a caller's own wins)
         dev, first = self.buffer._device, self._obs is None
         if first:
             if on_device and dev is not None and dev.index is not None and torch.device(venv.device) != dev:
@@ -391,14 +398,18 @@ class DeviceVectorCollector:
 
 def test_vector(model, venv, key, num_simulations: int, max_steps=None):
     """Greedy evaluation (muax/test.py:5-48: temperature 0, mean undiscounted return) on a vector
-    environment: the FIRST episode of each of its N environments, one batched act() per step."""
+    environment: the FIRST episode of each of its N environments, one batched act() per step.  An environment with
+    `invalid_actions()` (uint8 [N, A] as NumPy, 1 where the action is illegal for the observation last returned) has it
+    passed to every act() as `invalid_actions`; any other is evaluated as before."""
     obs = np.asarray(venv.reset())
     N = obs.shape[0]
     G, live = np.zeros(N), np.ones(N, bool)
     steps = max_steps if max_steps is not None else venv.spec.max_episode_steps
+    masked = hasattr(venv, "invalid_actions")
     for _ in range(steps):
         key, subkey = prng.split(key)
-        a = model.act(subkey, obs, obs_from_batch=True, num_simulations=num_simulations, temperature=0.)
+        mask = {"invalid_actions": venv.invalid_actions()} if masked else {}
+        a = model.act(subkey, obs, obs_from_batch=True, num_simulations=num_simulations, temperature=0., **mask)
         obs, r, done = venv.step(a)
         obs = np.asarray(obs)
         G += np.where(live, np.asarray(r, np.float64), 0.0)
@@ -415,11 +426,15 @@ def test_vector_device(model, venv, key, num_simulations: int, max_steps=None):
     host or synchronises except the "all finished" check, made after every 16th step only (the steps in between add
     0.0 to every return: the value does not depend on when the loop stops).  At the end `G` comes down once and its mean
     is taken on the host: the key stream, the fp64 additions and the mean are `test_vector`'s, so the value is
-    `test_vector(model, venv, key, ...)`'s exactly."""
+    `test_vector(model, venv, key, ...)`'s exactly.
+    An environment with `invalid_actions_device` (looked for once per call) has that tensor -- its own mask of the
+    observation act() is given, overwritten in place by its launches -- passed to every act() as `invalid_actions`;
+    the stream orders the environment's overwrite after the search that read it.  Any other is evaluated as before."""
     import torch
     if not hasattr(venv, "step_device"):
         raise ValueError(f"test_vector_device needs a device environment (one with step_device); "
                          f"{type(venv).__name__} has none: use test_vector")
+    mask = {"invalid_actions": venv.invalid_actions_device()} if hasattr(venv, "invalid_actions_device") else {}
     obs = venv.reset_device()
     N, dev = int(venv.n), obs.device
     G = torch.zeros(N, dtype=torch.float64, device=dev)
@@ -431,7 +446,7 @@ def test_vector_device(model, venv, key, num_simulations: int, max_steps=None):
     for i in range(steps):
         key, subkey = prng.split(key)
         a = model.act(subkey, obs, obs_from_batch=True, device_outputs=True, num_simulations=num_simulations,
-                      temperature=0.)
+                      temperature=0., **mask)
         obs = venv.step_device(a.to(torch.int32).contiguous(), r, done)
         G += torch.where(live, r, zero)
         live &= done == 0
@@ -482,6 +497,9 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     `reanalyse_every`-th iteration the `reanalyse_episodes` episodes (default: all) whose targets are the oldest are
     searched again with the current network (`DeviceReplayBuffer.reanalyse`, `num_simulations` simulations, act()'s
     other defaults), its key one extra split of the running key; 0: the key stream and every result are unchanged.
+    A `venv` with `invalid_actions_of` (the mask extension of muax_amd/envs.py, e.g. `Device2048`) hands it over as
+    `mask_fn`, so that no reanalysed search policy puts weight on a move that is illegal in its stored observation;
+    the collector passes such an environment's own mask to every act() of the collection (`DeviceVectorCollector`).
     `priority_update` (a buffer with `update_priorities`, i.e. the device buffer): every batch is sampled with its
     indices and, after its `update()`, `value_priorities` of the updated network are written back to the window starts
     with the loop's `alpha` (exponent 1 when `alpha` is None) and `weight=trajectory_weight`.  False, or a buffer
@@ -574,8 +592,10 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                    "G": float(np.mean([float(np.sum(t.rewards)) for t in trajs])) if trajs else float("nan")}
         if reanalyse_every > 0 and hasattr(buffer, "reanalyse") and len(buffer) and (it + 1) % reanalyse_every == 0:
             key, subkey = prng.split(key)
+            masks = {"mask_fn": venv.invalid_actions_of} if hasattr(venv, "invalid_actions_of") else {}
             buffer.reanalyse(model, subkey, n_step, gamma, alpha, weight=trajectory_weight,
-                             serials=buffer.stalest(reanalyse_episodes or len(buffer)), num_simulations=num_simulations)
+                             serials=buffer.stalest(reanalyse_episodes or len(buffer)), num_simulations=num_simulations,
+                             **masks)
         if len(buffer):
             loss = 0.0
             for _ in range(num_update_per_iteration):

@@ -22,9 +22,13 @@ trio and 50 simulations per step:
   columns run on `muax_amd.DeviceAcrobot` / `DeviceMountainCar` (3 actions, 6 / 2 observations) and, there being no host
   implementation of them, the host and device columns step a second instance of the same class through its HOST
   protocol (three synchronising copies per step), which is what a user without the device route would do.
+  --env 2048 does the same on `muax_amd.Device2048` (4 actions, 16 observations).  Its device-environment columns search
+  with the environment's legal-move mask (`invalid_actions_device()`, handed to every act() by the collector), and so
+  does the act()-alone column, on the mask of a freshly reset environment; the host columns go through
+  `VectorCollector`, which has no per-step mask, and search without one: the same launches, not the same episodes.
 
     python tools/bench_collect.py [--iters 20] [--shape ENVS,STEPS ...] [--simulations 50] [--device-env] [--device-plan]
-                                  [--env cartpole|acrobot|mountaincar]
+                                  [--env cartpole|acrobot|mountaincar|2048]
 
 Every figure is the median of `--iters` repetitions of one whole collect (+ add), each ending in a device synchronise,
 after three untimed ones.  The two routes alternate shape by shape in one process; each keeps its own environment,
@@ -48,7 +52,8 @@ A, E, OBS, SUPPORT, N_STEP, GAMMA, ALPHA, K = 2, 8, 4, 10, 10, 0.997, 0.5, 10
 # --env: (actions, observations, host-protocol environment, device environment)
 ENVS = {"cartpole": (A, OBS, lambda n: VectorCartPole(n, seed=0), lambda n: mx.DeviceCartPole(n, seed=0)),
         "acrobot": (3, 6, lambda n: mx.DeviceAcrobot(n, seed=0), lambda n: mx.DeviceAcrobot(n, seed=0)),
-        "mountaincar": (3, 2, lambda n: mx.DeviceMountainCar(n, seed=0), lambda n: mx.DeviceMountainCar(n, seed=0))}
+        "mountaincar": (3, 2, lambda n: mx.DeviceMountainCar(n, seed=0), lambda n: mx.DeviceMountainCar(n, seed=0)),
+        "2048": (4, 16, lambda n: mx.Device2048(n, seed=0, reward_shift=6), lambda n: mx.Device2048(n, seed=0, reward_shift=6))}
 
 
 def model(actions=A, obs_dim=OBS):
@@ -183,7 +188,10 @@ def main():
             env_buf = mx.DeviceReplayBuffer(cap, rows)
             env_dev = mx.DeviceVectorCollector(device_env(envs), env_buf, N_STEP, GAMMA, ALPHA, min_length=K)
             state["ek"] = state["ak"] = mx.prng.PRNGKey(0)
-            fixed = torch.from_numpy(host_env(envs).reset()).to(m.device)
+            fixed_env = host_env(envs)
+            fixed = torch.from_numpy(fixed_env.reset()).to(m.device)
+            mask = ({"invalid_actions": fixed_env.invalid_actions_device()}
+                    if hasattr(fixed_env, "invalid_actions_device") else {})
 
             def env_route():
                 _, state["ek"], _ = env_dev.collect(m, state["ek"], steps, a.simulations)
@@ -192,7 +200,7 @@ def main():
                 for _ in range(steps):
                     state["ak"], sub = mx.prng.split(state["ak"])
                     m.act(sub, fixed, with_pi=True, with_value=True, obs_from_batch=True, device_outputs=True,
-                          num_simulations=a.simulations)
+                          num_simulations=a.simulations, **mask)
 
             line += f" | {median_ms(env_route, a.iters):27.3f} {median_ms(act_alone, a.iters):13.3f}"
         if a.device_plan:
