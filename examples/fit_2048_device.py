@@ -3,8 +3,10 @@
 merges, spawns from a threefry stream), a `DeviceReplayBuffer` and `device_collect=True`.  The environment's own mask
 tensor goes into every act() of the collection and of the greedy test, and every reanalysis (`--reanalyse-every`)
 searches the stored observations under `venv.invalid_actions_of`, so no search policy in the buffer puts weight on a
-move that would leave the board unchanged.  The search is the deterministic MuZero one: the spawn is chance the model
-has to average over (`StochasticMuZeroPolicy` is not implemented).
+move that would leave the board unchanged.  The search of THIS example is the deterministic MuZero one: the spawn is
+chance the model has to average over.  (`StochasticMuZeroPolicy` -- the search over chance nodes, at 2048's 4 actions +
+32 chance codes among others -- is built, but it takes decision and chance functions, which the default network trio
+trained here does not have.)
 
 Scale.  The value head is a categorical over -support_size .. support_size of h(x) = sign(x)(sqrt(|x| + 1) - 1) + 0.001 x,
 so support_size 31 (the widest the fused kernels take) holds |x| up to 962.  Rewards are the merged tiles times

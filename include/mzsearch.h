@@ -50,13 +50,20 @@ typedef struct {
   int32_t max_depth;       /* <= 0: num_simulations (mctx default) */
   int32_t qtransform;      /* 0: qtransform_by_parent_and_siblings; 1: qtransform_completed_by_mix_value (gumbel policy only) */
   int32_t tiebreak;        /* 0: none; 1: JAX threefry stream (1e-7 * uniform); muzero policy only */
-  int32_t policy;          /* 0: mctx.muzero_policy (muax/policy.py:13-30); 1: mctx.gumbel_muzero_policy (muax/policy.py:33-47) */
+  int32_t policy;          /* 0: mctx.muzero_policy (muax/policy.py:13-30); 1: mctx.gumbel_muzero_policy (muax/policy.py:33-47);
+                              2: mctx.stochastic_muzero_policy (muax/policy.py:50-67), step-wise entries *_stochastic only */
   float pb_c_init;         /* 1.25  */
   float pb_c_base;         /* 19652 */
   int64_t global_batch;    /* B of the un-sharded batch (PRNG stream layout); 0 -> batch */
   int64_t root_offset;     /* global index of local root 0 */
   int32_t max_num_considered_actions; /* gumbel policy: 16 (muax/policy.py:45) */
   float gumbel_scale;                 /* gumbel policy: 1.0 (muax/policy.py:46) */
+  /* stochastic policy (0 for the others): C chance outcomes, num_actions + C <= 64 slots per node; the widths of the state
+   * and afterstate embeddings (0: embed_dim), embed_dim = max of the two, below 256 */
+  int32_t num_chance_outcomes;
+  int32_t state_embed_dim;
+  int32_t afterstate_embed_dim;
+  int32_t reserved0;
 } mzs_config;
 
 /* Weights of the default MLP trio (muax/nn.py:59-115), haiku layout w[in][out],
@@ -178,6 +185,51 @@ int mzs_finish(mzs_handle *h, float temperature, const float *gumbel,
                int32_t *action_out, float *action_weights_out,
                float *search_value_out, int32_t *depth_sum_out, void *stream);
 int mzs_tree_export(mzs_handle *h, const mzs_tree_view *out, void *stream);
+
+/* ---- step-wise path, stochastic policy (policy == 2): mctx.stochastic_muzero_policy with caller-run decision and chance
+ * functions.  A = num_actions, C = num_chance_outcomes; the search is the MuZero search above over A' = A + C slots per
+ * node (slots < A: actions, slots >= A: chance outcomes) -- same pUCT rule, qtransform_by_parent_and_siblings, key chain,
+ * backup, max_depth and re-expansion -- with these differences:
+ *   kind       the root and every even-depth node are decision nodes, odd-depth nodes chance nodes; max_depth and depth_sum
+ *              count both kinds of level
+ *   root       Dirichlet mix and invalid-action mask over the A actions as in mzs_root, the row then padded with C logits
+ *              of -inf, the invalid mask with C ones
+ *   selection  decision node: the MuZero rule over all A' slots (tie-break uniforms of length A'; chance slots have prior
+ *              probability 0 and are not special-cased); chance node: slot i scores p_i / (visits_i + 1), p the softmax of
+ *              the node's prior row, fp32, no noise, first maximum.  The key chain advances one split per level
+ *   expansion  child of a decision node: a chance node, prior row [-inf x A, chance_logits], value afterstate_value, edge
+ *              reward 0 and discount 1, the afterstate embedding; child of a chance node: a decision node, prior row
+ *              [action_logits, -inf x C], value / reward / discount of the chance function, the state embedding.  Both
+ *              embeddings live zero-padded in rows of embed_dim = max(state_embed_dim, afterstate_embed_dim) floats
+ *   finish     visit summary and the categorical sample over the first A slots; action_weights [B, A]; the Gumbel row is
+ *              drawn for shape [B, A]; search_value is the root's node value
+ * The trees are walked level by level (no cached decisions).  The entries above refuse a stochastic handle and these refuse
+ * any other; mzs_tree_export copies the A'-wide arrays ([B, N, A + C]). */
+typedef struct {
+  int32_t struct_size;                /* = sizeof(mzs_stochastic_outputs) */
+  int32_t reserved0;
+  /* decision function, evaluated at action clamp(slot, 0, A - 1) on the parent's first state_embed_dim floats */
+  const float *chance_logits;         /* [B, C] */
+  const float *afterstate_value;      /* [B] */
+  const float *afterstate_embedding;  /* [B, afterstate_embed_dim] */
+  /* chance function, evaluated at outcome clamp(slot - A, 0, C - 1) on the parent's first afterstate_embed_dim floats */
+  const float *action_logits;         /* [B, A] */
+  const float *value, *reward, *discount; /* [B] */
+  const float *state_embedding;       /* [B, state_embed_dim] */
+} mzs_stochastic_outputs;
+/* prior_logits, invalid_actions, dirichlet_noise: [B, A]; embedding: [B, state_embed_dim] */
+int mzs_root_stochastic(mzs_handle *h, const float *prior_logits, const float *value, const float *embedding,
+                        const uint8_t *invalid_actions, const float *dirichlet_noise, float dirichlet_fraction,
+                        const uint32_t key[2], void *stream);
+/* slot_out [B]: the selected slot in [0, A + C); parent_is_decision_out [B]: 1 where the selected edge leaves a decision
+ * node (the decision function's outputs will be used), 0 a chance node; parent_embedding_out [B, embed_dim] */
+int mzs_select_stochastic(mzs_handle *h, int32_t sim, int32_t *slot_out, int32_t *parent_is_decision_out,
+                          float *parent_embedding_out, void *stream);
+/* Both functions' outputs for every root; per root the kernel takes the set of the selected edge's parent kind */
+int mzs_expand_backup_stochastic(mzs_handle *h, int32_t sim, const mzs_stochastic_outputs *outputs, void *stream);
+/* gumbel: [B, A] or NULL (drawn from the key given to mzs_root_stochastic); action_weights_out: [B, A] */
+int mzs_finish_stochastic(mzs_handle *h, float temperature, const float *gumbel, int32_t *action_out,
+                          float *action_weights_out, float *search_value_out, int32_t *depth_sum_out, void *stream);
 
 /* ---- recurrent_fn of the EfficientZero-style nets ----
  * mzs_ez_recurrent evaluates, for a batch of 6x6xC hidden states (NHWC, C = 32 or 64) and actions, the whole

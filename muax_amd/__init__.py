@@ -15,7 +15,8 @@ from .loss import Transition, default_loss_fn  # noqa: F401
 from .model import MuZero  # noqa: F401
 from .nn import MZNetwork, MZNetworkParams, create_muzero_network  # noqa: F401
 from .policy import GumbelMuZeroPolicy, MuZeroPolicy, Policy, StochasticMuZeroPolicy  # noqa: F401
-from .search import MuZeroSearch, PolicyOutput, SearchConfig, SearchTree, key_words  # noqa: F401
+from .search import (ChanceRecurrentFnOutput, DecisionRecurrentFnOutput, MuZeroSearch, PolicyOutput, SearchConfig,  # noqa: F401
+                     SearchTree, key_words)
 from .sharding import allreduce_mean_flat, gather_roots, shard_roots  # noqa: F401
 from .vector import (DeviceVectorCollector, VectorCollector, episode_trajectory, fit_vector, nstep_returns,  # noqa: F401
                      ring_plan, test_vector, test_vector_device)

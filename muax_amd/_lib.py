@@ -21,7 +21,15 @@ class MzsConfig(C.Structure):
                 ("max_depth", C.c_int32), ("qtransform", C.c_int32), ("tiebreak", C.c_int32),
                 ("policy", C.c_int32), ("pb_c_init", C.c_float), ("pb_c_base", C.c_float),
                 ("global_batch", C.c_int64), ("root_offset", C.c_int64),
-                ("max_num_considered_actions", C.c_int32), ("gumbel_scale", C.c_float)]
+                ("max_num_considered_actions", C.c_int32), ("gumbel_scale", C.c_float),
+                ("num_chance_outcomes", C.c_int32), ("state_embed_dim", C.c_int32),
+                ("afterstate_embed_dim", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class MzsStochasticOutputs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved0", C.c_int32), ("chance_logits", _vp), ("afterstate_value", _vp),
+                ("afterstate_embedding", _vp), ("action_logits", _vp), ("value", _vp), ("reward", _vp),
+                ("discount", _vp), ("state_embedding", _vp)]
 
 
 MLP_WEIGHT_NAMES = ["repr_w", "repr_b", "pv_w1", "pv_b1", "pv_w2", "pv_b2", "pp_w1", "pp_b1", "pp_w2",
@@ -254,7 +262,9 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_replay_stage", "mzs_replay_store_steps", "mzs_replay_plan_steps",
                     "mzs_env_cartpole_reset", "mzs_env_cartpole_step",
                     "mzs_env_classic_reset", "mzs_env_classic_step",
-                    "mzs_env_2048_reset", "mzs_env_2048_step", "mzs_env_2048_mask"]
+                    "mzs_env_2048_reset", "mzs_env_2048_step", "mzs_env_2048_mask",
+                    "mzs_root_stochastic", "mzs_select_stochastic", "mzs_expand_backup_stochastic",
+                    "mzs_finish_stochastic"]
 
 _lib = None
 
@@ -287,6 +297,10 @@ def load(build_if_missing: bool = True):
     L.mzs_expand_backup_select.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.mzs_finish.argtypes = [_vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]
     L.mzs_tree_export.argtypes = [_vp, C.POINTER(MzsTreeView), _vp]
+    L.mzs_root_stochastic.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.POINTER(C.c_uint32 * 2), _vp]
+    L.mzs_select_stochastic.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp]
+    L.mzs_expand_backup_stochastic.argtypes = [_vp, C.c_int32, C.POINTER(MzsStochasticOutputs), _vp]
+    L.mzs_finish_stochastic.argtypes = [_vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]
     L.mzs_mlp_loss_grad.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsTrainArgs), _vp]
     L.mzs_resnet_tower.argtypes = [C.POINTER(MzsTowerArgs), _vp]
     L.mzs_register_fused_dispatch.argtypes = [_vp, C.c_int32]

@@ -68,7 +68,22 @@ int mzs_create(const mzs_config* cfg, mzs_handle** out) {
     return fail(nullptr, MZS_E_INVALID, "mzs_create: batch, num_actions, num_simulations, embed_dim must be positive");
   if (cfg->num_actions > 64) return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_create: num_actions > 64");
   if (cfg->num_simulations >= 65535) return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_create: num_simulations too large");
-  if (cfg->policy != 0 && cfg->policy != 1) return fail(nullptr, MZS_E_INVALID, "mzs_create: policy must be 0 (muzero) or 1 (gumbel)");
+  if (cfg->policy < 0 || cfg->policy > 2)
+    return fail(nullptr, MZS_E_INVALID, "mzs_create: policy must be 0 (muzero), 1 (gumbel) or 2 (stochastic)");
+  if (cfg->policy == 2) {
+    const int es = cfg->state_embed_dim > 0 ? cfg->state_embed_dim : cfg->embed_dim;
+    const int ea = cfg->afterstate_embed_dim > 0 ? cfg->afterstate_embed_dim : cfg->embed_dim;
+    if (cfg->num_chance_outcomes <= 0) return fail(nullptr, MZS_E_INVALID, "mzs_create: the stochastic policy needs num_chance_outcomes > 0");
+    if (cfg->num_actions + cfg->num_chance_outcomes > 64)
+      return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_create: num_actions + num_chance_outcomes > 64");
+    if (cfg->embed_dim != (es > ea ? es : ea))
+      return fail(nullptr, MZS_E_INVALID, "mzs_create: embed_dim must be max(state_embed_dim, afterstate_embed_dim)");
+    if (cfg->embed_dim >= mz::kWideEmb)
+      return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_create: the stochastic policy takes embeddings narrower than 256 floats");
+    static_assert(mz::kWideEmb == 256, "the message above names the bound");
+  } else if (cfg->num_chance_outcomes != 0) {
+    return fail(nullptr, MZS_E_INVALID, "mzs_create: num_chance_outcomes is for policy 2 (stochastic) only");
+  }
   if (cfg->qtransform != 0 && !(cfg->qtransform == 1 && cfg->policy == 1))
     return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_create: qtransform_completed_by_mix_value is built for the gumbel policy only");
   if (cfg->policy == 1 && cfg->max_num_considered_actions < 0)
@@ -83,6 +98,8 @@ int mzs_create(const mzs_config* cfg, mzs_handle** out) {
   h->cfg = *cfg;
   h->cu_count = prop.multiProcessorCount;
   if (h->cfg.global_batch <= 0) h->cfg.global_batch = cfg->batch;
+  if (h->cfg.state_embed_dim <= 0) h->cfg.state_embed_dim = cfg->embed_dim;
+  if (h->cfg.afterstate_embed_dim <= 0) h->cfg.afterstate_embed_dim = cfg->embed_dim;
   if (h->cfg.root_offset < 0 || h->cfg.root_offset + cfg->batch > h->cfg.global_batch) {
     delete h;
     return fail(nullptr, MZS_E_INVALID, "mzs_create: root_offset + batch exceeds global_batch");
@@ -129,6 +146,8 @@ int mzs_mlp_set_weights(mzs_handle* h, const mzs_mlp_weights* w) {
   if (!h) return MZS_E_INVALID;
   if (!w || w->struct_size != (int32_t)sizeof(mzs_mlp_weights))
     return fail(h, MZS_E_INVALID, "mzs_mlp_set_weights: null or size mismatch (ABI)");
+  if (h->cfg.policy == 2)
+    return fail(h, MZS_E_UNSUPPORTED, "mzs_mlp_set_weights: a stochastic handle runs the step-wise *_stochastic entries only");
   const float* const* ptrs = &w->repr_w;
   for (int i = 0; i < 18; ++i)
     if (!ptrs[i]) return fail(h, MZS_E_INVALID, "mzs_mlp_set_weights: null weight pointer");

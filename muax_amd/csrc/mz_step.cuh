@@ -41,6 +41,8 @@ struct StepArgs {
   float gumbel_scale;
   float* root_gumbel;           // [B, A]
   const int32_t* visit_table;   // [(max_considered + 1), S] seq_halving.get_table_of_considered_visits
+  // stochastic policy: A = AD + C slots per node (AD actions, then C chance outcomes); every other policy: AD = A
+  int32_t AD;
 };
 
 constexpr int kWideEmb = 256;
@@ -94,7 +96,8 @@ struct StepState {
   }
   StepArgs args(const mzs_config& c) const {
     StepArgs a;
-    a.B = c.batch; a.N = c.num_simulations + 1; a.A = c.num_actions; a.E = c.embed_dim;
+    a.B = c.batch; a.N = c.num_simulations + 1; a.AD = c.num_actions; a.E = c.embed_dim;
+    a.A = c.num_actions + (c.policy == 2 ? c.num_chance_outcomes : 0);
     a.S = c.num_simulations; a.max_depth = c.max_depth > 0 ? c.max_depth : c.num_simulations;
     a.tiebreak = c.tiebreak; a.pb_c_init = c.pb_c_init; a.pb_c_base = c.pb_c_base;
     a.global_batch = (uint64_t)c.global_batch; a.root_offset = (uint64_t)c.root_offset;
@@ -446,6 +449,27 @@ MZ_DEV void gumbel_decide(const StepArgs& s, size_t rb, int r, int node, int j, 
     row_argmax<4>(bscore, best, child);
   }
 }
+// mctx stochastic_muzero_policy at a CHANCE node (odd depth): slot i scores p_i / (children_visits_i + 1) with p the node's
+// stored prior probabilities (the softmax of [-inf x AD, chance_logits]: exact 0 on the AD action slots), an fp32
+// division, no noise, first maximum -- the visits of a chance node follow its outcome distribution (D'Hondt)
+MZ_DEV void chance_decide(const StepArgs& s, const TreeView& T, int node, int j, int& best, int& child) {
+  const int A = s.A;
+  const int nb = node * A;
+  float bscore = -INFINITY;
+  best = 1 << 20;
+  child = -1;
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    const int a = j + 16 * t;
+    const bool ok = a < A;
+    const int o = (nb + (ok ? a : 0)) * T.cs;
+    const int ci = T.cidx[o];
+    const float sc = ok ? T.prob[o] / (float)(T.cvis[o] + 1) : -INFINITY;
+    const bool take = (t == 0) || (sc > bscore);  // first max wins inside the lane
+    if (take) { bscore = sc; best = ok ? a : (1 << 20); child = ci; }
+  }
+  row_argmax<4>(bscore, best, child);
+}
 template <bool GUMBEL>
 MZ_DEV void decide_any(const StepArgs& s, const TreeView& T, size_t rb, int r, int node, int j, int& best, int& child, bool& near) {
   if constexpr (GUMBEL) {
@@ -543,8 +567,7 @@ MZ_DEV void store_selection(const StepArgs& s, int r, int parent, int action, in
 
 // mctx _mask_invalid_actions + softmax over a row: where any lane of the row says `masked`, x - max(x) with the invalid
 // actions at the lowest float; x holds what the softmax saw
-MZ_DEV void row_mask_invalid_softmax(float (&x)[kMaxAS], const bool (&inv)[kMaxAS], bool masked, int A, int j,
-                                     float (&p)[kMaxAS]) {
+MZ_DEV void row_mask_invalid(float (&x)[kMaxAS], const bool (&inv)[kMaxAS], bool masked, int A, int j) {
   if (((__builtin_amdgcn_ballot_w64(masked) >> (threadIdx.x & 48)) & 0xffffull) != 0) {  // any lane of the row
     float mx = -INFINITY;
 #pragma unroll
@@ -553,19 +576,18 @@ MZ_DEV void row_mask_invalid_softmax(float (&x)[kMaxAS], const bool (&inv)[kMaxA
 #pragma unroll
     for (int t = 0; t < kMaxAS; ++t) x[t] = inv[t] ? kFltLowest : x[t] - mx;
   }
+}
+MZ_DEV void row_mask_invalid_softmax(float (&x)[kMaxAS], const bool (&inv)[kMaxAS], bool masked, int A, int j,
+                                     float (&p)[kMaxAS]) {
+  row_mask_invalid(x, inv, masked, A, j);
   row_softmax_rt(x, A, j, p);
 }
 
 // expansion of node `newn`: its prior row is the softmax of the net's logits (logits to the HBM tree, probabilities
-// through the view)
-MZ_DEV void expand_prior_row(const StepArgs& s, const TreeView& T, size_t rb, int newn, const float* prior_logits_row, int j) {
+// through the view); x: the row-distributed logits (slots past A: any finite value)
+MZ_DEV void expand_prior_row(const StepArgs& s, const TreeView& T, size_t rb, int newn, const float (&x)[kMaxAS], int j) {
   const int A = s.A;
-  float x[kMaxAS], pr[kMaxAS];
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    const int a = j + 16 * t;
-    x[t] = a < A ? prior_logits_row[a] : 0.0f;
-  }
+  float pr[kMaxAS];
   row_softmax_rt(x, A, j, pr);
 #pragma unroll
   for (int t = 0; t < kMaxAS; ++t) {
@@ -575,6 +597,15 @@ MZ_DEV void expand_prior_row(const StepArgs& s, const TreeView& T, size_t rb, in
       T.prob[(newn * A + a) * T.cs] = pr[t];
     }
   }
+}
+MZ_DEV void expand_prior_row(const StepArgs& s, const TreeView& T, size_t rb, int newn, const float* prior_logits_row, int j) {
+  float x[kMaxAS];
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    const int a = j + 16 * t;
+    x[t] = a < s.A ? prior_logits_row[a] : 0.0f;
+  }
+  expand_prior_row(s, T, rb, newn, x, j);
 }
 
 }  // namespace mz

@@ -20,13 +20,9 @@ namespace mz {
   const size_t rb = (size_t)r * N;                                    \
   (void)lane; (void)N; (void)A; (void)E;
 
-// mctx instantiate_tree_from_root + muzero_policy prelude (dirichlet, mask)
-__global__ __launch_bounds__(256) void step_root_kernel(StepArgs s, const float* prior_logits,
-                                                         const float* value, const float* embedding,
-                                                         const uint8_t* invalid, const float* noise,
-                                                         float fraction, int gumbel_policy,
-                                                         const float* gumbel_in, uint32_t gk0, uint32_t gk1) {
-  MZ_ROW_SETUP
+// mctx instantiate_tree_from_root: the empty tree of root row rb, by the row's 16 lanes
+MZ_DEV void root_clear_tree(const StepArgs& s, size_t rb, int j) {
+  const int N = s.N, A = s.A, E = s.E;
   for (int n = j; n < N; n += 16) {
     s.node_visits[rb + n] = 0;
     s.raw_values[rb + n] = 0.0f;
@@ -46,6 +42,16 @@ __global__ __launch_bounds__(256) void step_root_kernel(StepArgs s, const float*
   }
   if (!s.wide)  // (wide: zeroed by a memset on the stream)
     for (size_t i = j; i < (size_t)N * E; i += 16) s.embeddings[rb * E + i] = 0.0f;
+}
+
+// mctx instantiate_tree_from_root + muzero_policy prelude (dirichlet, mask)
+__global__ __launch_bounds__(256) void step_root_kernel(StepArgs s, const float* prior_logits,
+                                                         const float* value, const float* embedding,
+                                                         const uint8_t* invalid, const float* noise,
+                                                         float fraction, int gumbel_policy,
+                                                         const float* gumbel_in, uint32_t gk0, uint32_t gk1) {
+  MZ_ROW_SETUP
+  root_clear_tree(s, rb, j);
   float x[kMaxAS], pr[kMaxAS], lg[kMaxAS];
   bool inv[kMaxAS];
 #pragma unroll
@@ -114,18 +120,72 @@ __global__ __launch_bounds__(256) void step_root_kernel(StepArgs s, const float*
   }
 }
 
+// mctx stochastic_muzero_policy's root: the muzero_policy prelude over the AD actions (prior_logits, invalid, noise:
+// [B, AD]), the row padded with -inf on the chance slots and the invalid mask with ones; embedding: [B, es], es <= E
+__global__ __launch_bounds__(256) void step_root_stochastic_kernel(StepArgs s, const float* prior_logits,
+                                                                    const float* value, const float* embedding,
+                                                                    int es, const uint8_t* invalid, const float* noise,
+                                                                    float fraction) {
+  MZ_ROW_SETUP
+  const int AD = s.AD;
+  root_clear_tree(s, rb, j);
+  float x[kMaxAS], pr[kMaxAS], lg[kMaxAS];
+  bool inv[kMaxAS];
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    const int a = j + 16 * t;
+    x[t] = a < AD ? prior_logits[(size_t)r * AD + a] : 0.0f;
+    inv[t] = (invalid != nullptr && a < AD) ? invalid[(size_t)r * AD + a] != 0 : false;
+    if (a < A) s.root_invalid[(size_t)r * A + a] = (a >= AD || inv[t]) ? 1 : 0;
+  }
+  row_softmax_rt(x, AD, j, pr);
+  const float keep = 1.0f - fraction;
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    const int a = j + 16 * t;
+    const float nz = (noise != nullptr && a < AD) ? noise[(size_t)r * AD + a] : 0.0f;
+    const float noisy = keep * pr[t] + fraction * nz;
+    lg[t] = log_pos(fmaxf(noisy, kFltTiny));
+  }
+  row_mask_invalid(lg, inv, invalid != nullptr, AD, j);
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) lg[t] = j + 16 * t < AD ? lg[t] : -INFINITY;
+  float pq[kMaxAS];
+  row_softmax_rt(lg, A, j, pq);
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    const int a = j + 16 * t;
+    if (a < A) {
+      s.children_prior_logits[rb * A + a] = lg[t];
+      s.children_prior_probs[rb * A + a] = pq[t];
+    }
+  }
+  for (int i = j; i < es; i += 16) s.embeddings[rb * E + i] = embedding[(size_t)r * es + i];
+  if (j == 0) {
+    s.node_visits[rb] = 1;
+    s.raw_values[rb] = value[r];
+    s.node_values[rb] = value[r];
+    s.depth_sum[r] = 0;
+  }
+}
+
 // mctx search.simulate, level by level from the root (+ the parent-embedding gather of search.expand): the decisions of
-// mz_step.cuh on the HBM tree, the visited (node, action) pairs staged in `path` for the backward pass
-template <bool GUMBEL>
-MZ_DEV void walk_select(const StepArgs& s, int sim, int r, int j, int32_t* action_out, float* parent_embedding_out) {
+// mz_step.cuh on the HBM tree, the visited (node, action) pairs staged in `path` for the backward pass.  KIND 0: the MuZero
+// rule at every node, 1: the Gumbel rules, 2 (stochastic): the MuZero rule at even depth, chance_decide at odd depth --
+// `kind_out`: 1 where the selected edge leaves a decision node
+template <int KIND>
+MZ_DEV void walk_select(const StepArgs& s, int sim, int r, int j, int32_t* action_out, float* parent_embedding_out,
+                        int32_t* kind_out = nullptr) {
   const size_t rb = (size_t)r * s.N;
   const TreeView T = tree_view_global(s, rb);
   SimKeys K;
   int node = 0, depth = 0, parent = 0, action = 0;
   for (;;) {
     int best, child;
-    if constexpr (GUMBEL) {
+    if constexpr (KIND == 1) {
       gumbel_decide(s, rb, r, node, j, best, child);
+    } else if (KIND == 2 && (depth & 1)) {
+      chance_decide(s, T, node, j, best, child);
     } else {
       float sc[kMaxAS];
       int cidx[kMaxAS];
@@ -144,17 +204,57 @@ MZ_DEV void walk_select(const StepArgs& s, int sim, int r, int j, int32_t* actio
     node = child;
   }
   store_selection<false>(s, r, parent, action, depth, action_out, s.wide ? nullptr : parent_embedding_out, s.wide != 0);
+  if (KIND == 2 && j == 0) kind_out[r] = (depth & 1) ? 1 : 0;  // the parent sits at depth - 1
 }
 __global__ __launch_bounds__(256) void step_select_kernel(StepArgs s, int sim, int32_t* action_out,
                                                            float* parent_embedding_out) {
   MZ_ROW_SETUP
-  walk_select<false>(s, sim, r, j, action_out, parent_embedding_out);
+  walk_select<0>(s, sim, r, j, action_out, parent_embedding_out);
+}
+// ... with chance nodes at odd depth (stochastic policy)
+__global__ __launch_bounds__(256) void step_select_stochastic_kernel(StepArgs s, int sim, int32_t* slot_out,
+                                                                      int32_t* parent_is_decision_out,
+                                                                      float* parent_embedding_out) {
+  MZ_ROW_SETUP
+  walk_select<2>(s, sim, r, j, slot_out, parent_embedding_out, parent_is_decision_out);
 }
 // ... with gumbel_muzero_{root,interior}_action_selection
 __global__ __launch_bounds__(256) void step_select_gumbel_kernel(StepArgs s, int sim, int32_t* action_out,
                                                                   float* parent_embedding_out) {
   MZ_ROW_SETUP
-  walk_select<true>(s, sim, r, j, action_out, parent_embedding_out);
+  walk_select<1>(s, sim, r, j, action_out, parent_embedding_out);
+}
+
+// The one-lane half of an expansion: node `newn` and its edge (parent, action), then mctx search.backward along the path
+// staged by walk_select (only this lane touches these words)
+MZ_DEV void expand_edge_backward(const StepArgs& s, size_t rb, int parent, int action, int depth, int newn, float v,
+                                 float rew_new, float dis_new) {
+  const int A = s.A;
+  const size_t eo = (rb + parent) * A + action;
+  s.raw_values[rb + newn] = v;
+  s.node_values[rb + newn] = v;
+  s.node_visits[rb + newn] = s.node_visits[rb + newn] + 1;
+  s.children_index[eo] = newn;
+  s.children_rewards[eo] = rew_new;
+  s.children_discounts[eo] = dis_new;
+  s.parents[rb + newn] = parent;
+  s.action_from_parent[rb + newn] = action;
+  float leaf = v, childv = v;
+  for (int d = depth - 1; d >= 0; --d) {
+    int pk = s.path[rb + d];
+    int pn = pk & 0xffff, pa = pk >> 16;
+    size_t e2 = (rb + pn) * A + pa;
+    int cnt = s.node_visits[rb + pn];
+    float rw = (d == depth - 1) ? rew_new : s.children_rewards[e2];
+    float ds = (d == depth - 1) ? dis_new : s.children_discounts[e2];
+    leaf = rw + ds * leaf;
+    float newv = (s.node_values[rb + pn] * (float)cnt + leaf) / ((float)cnt + 1.0f);
+    s.node_values[rb + pn] = newv;
+    s.node_visits[rb + pn] = cnt + 1;
+    s.children_values[e2] = childv;
+    s.children_visits[e2] = s.children_visits[e2] + 1;
+    childv = newv;
+  }
 }
 
 // mctx search.expand (update_tree_node + edge) and search.backward
@@ -176,48 +276,62 @@ __global__ __launch_bounds__(256) void step_expand_backup_kernel(StepArgs s, int
     for (int i = j; i < E; i += 16) s.embeddings[(rb + newn) * E + i] = next_embedding[(size_t)r * E + i];
   }
   const float rew_new = reward[r], dis_new = discount[r];
-  if (j == 0) {
-    s.raw_values[rb + newn] = v;
-    s.node_values[rb + newn] = v;
-    s.node_visits[rb + newn] = s.node_visits[rb + newn] + 1;
-    s.children_index[eo] = newn;
-    s.children_rewards[eo] = rew_new;
-    s.children_discounts[eo] = dis_new;
-    s.parents[rb + newn] = parent;
-    s.action_from_parent[rb + newn] = action;
-    // backward along the staged path (only this lane touches these words)
-    float leaf = v, childv = v;
-    for (int d = depth - 1; d >= 0; --d) {
-      int pk = s.path[rb + d];
-      int pn = pk & 0xffff, pa = pk >> 16;
-      size_t e2 = (rb + pn) * A + pa;
-      int cnt = s.node_visits[rb + pn];
-      float rw = (d == depth - 1) ? rew_new : s.children_rewards[e2];
-      float ds = (d == depth - 1) ? dis_new : s.children_discounts[e2];
-      leaf = rw + ds * leaf;
-      float newv = (s.node_values[rb + pn] * (float)cnt + leaf) / ((float)cnt + 1.0f);
-      s.node_values[rb + pn] = newv;
-      s.node_visits[rb + pn] = cnt + 1;
-      s.children_values[e2] = childv;
-      s.children_visits[e2] = s.children_visits[e2] + 1;
-      childv = newv;
+  if (j == 0) expand_edge_backward(s, rb, parent, action, depth, newn, v, rew_new, dis_new);
+}
+
+// mctx stochastic_muzero_policy's expansion: both functions' outputs arrive for every root and the row takes the set of
+// its parent's kind, merged here (no per-simulation torch op): a decision parent (the selection's depth - 1 even) gets a
+// chance child -- prior row [-inf x AD, chance_logits], afterstate value, edge reward 0 and discount 1, the afterstate
+// embedding --, a chance parent a decision child -- [action_logits, -inf x C] and the chance function's value, reward,
+// discount and state embedding.  Embedding rows are zero-padded to E.
+struct StochasticOutputs {
+  const float *chance_logits, *afterstate_value, *afterstate_embedding;      // [B, C] [B] [B, ea]
+  const float *action_logits, *value, *reward, *discount, *state_embedding;  // [B, AD] [B] [B] [B] [B, es]
+  int32_t ea, es;
+};
+__global__ __launch_bounds__(256) void step_expand_backup_stochastic_kernel(StepArgs s, int sim, StochasticOutputs o) {
+  MZ_ROW_SETUP
+  const int AD = s.AD, C = A - AD;
+  const int parent = s.sel_parent[r], action = s.sel_action[r], depth = s.sel_depth[r];
+  const bool chance_child = ((depth - 1) & 1) == 0;
+  const size_t eo = (rb + parent) * A + action;
+  const int next = s.children_index[eo];
+  const int newn = next == -1 ? sim + 1 : next;
+  float x[kMaxAS];
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) {
+    const int a = j + 16 * t;
+    x[t] = -INFINITY;
+    if (chance_child) {
+      if (a >= AD && a < A) x[t] = o.chance_logits[(size_t)r * C + (a - AD)];
+    } else {
+      if (a < AD) x[t] = o.action_logits[(size_t)r * AD + a];
     }
+  }
+  expand_prior_row(s, tree_view_global(s, rb), rb, newn, x, j);
+  const float* src = chance_child ? o.afterstate_embedding + (size_t)r * o.ea : o.state_embedding + (size_t)r * o.es;
+  const int w = chance_child ? o.ea : o.es;
+  for (int i = j; i < E; i += 16) s.embeddings[(rb + newn) * E + i] = i < w ? src[i] : 0.0f;
+  if (j == 0) {
+    const float v = chance_child ? o.afterstate_value[r] : o.value[r];
+    const float rew = chance_child ? 0.0f : o.reward[r], dis = chance_child ? 1.0f : o.discount[r];
+    expand_edge_backward(s, rb, parent, action, depth, newn, v, rew, dis);
   }
 }
 
-// mctx Tree.summary + _apply_temperature + jax.random.categorical
-__global__ __launch_bounds__(256) void step_finish_kernel(StepArgs s, float temperature, const float* gumbel,
-                                                           uint32_t ks0, uint32_t ks1, int32_t* action_out,
-                                                           float* action_weights_out, float* search_value_out,
-                                                           int32_t* depth_sum_out) {
-  MZ_ROW_SETUP
+// mctx Tree.summary + _apply_temperature + jax.random.categorical over the first A of the root's s.A slots (gumbel,
+// action_weights_out: [B, A]; the drawn Gumbel row is that of shape [global_batch, A])
+MZ_DEV void finish_row(const StepArgs& s, int r, int j, int A, float temperature, const float* gumbel, uint32_t ks0,
+                       uint32_t ks1, int32_t* action_out, float* action_weights_out, float* search_value_out,
+                       int32_t* depth_sum_out) {
+  const size_t rb = (size_t)r * s.N;
   const uint64_t rg = s.root_offset + (uint64_t)r;
   int vc[kMaxAS];
   int part = 0;
 #pragma unroll
   for (int t = 0; t < kMaxAS; ++t) {
     int a = j + 16 * t;
-    vc[t] = a < A ? s.children_visits[rb * A + a] : 0;
+    vc[t] = a < A ? s.children_visits[rb * s.A + a] : 0;
     part += vc[t];
   }
   float total = (float)row_sum_i(part);
@@ -262,6 +376,21 @@ __global__ __launch_bounds__(256) void step_finish_kernel(StepArgs s, float temp
     if (search_value_out) search_value_out[r] = s.node_values[rb];
     if (depth_sum_out) depth_sum_out[r] = s.depth_sum[r];
   }
+}
+__global__ __launch_bounds__(256) void step_finish_kernel(StepArgs s, float temperature, const float* gumbel,
+                                                           uint32_t ks0, uint32_t ks1, int32_t* action_out,
+                                                           float* action_weights_out, float* search_value_out,
+                                                           int32_t* depth_sum_out) {
+  MZ_ROW_SETUP
+  finish_row(s, r, j, A, temperature, gumbel, ks0, ks1, action_out, action_weights_out, search_value_out, depth_sum_out);
+}
+// ... over the decision slots of a stochastic tree (mctx _mask_tree(tree, num_actions, 'decision'))
+__global__ __launch_bounds__(256) void step_finish_stochastic_kernel(StepArgs s, float temperature, const float* gumbel,
+                                                                      uint32_t ks0, uint32_t ks1, int32_t* action_out,
+                                                                      float* action_weights_out, float* search_value_out,
+                                                                      int32_t* depth_sum_out) {
+  MZ_ROW_SETUP
+  finish_row(s, r, j, s.AD, temperature, gumbel, ks0, ks1, action_out, action_weights_out, search_value_out, depth_sum_out);
 }
 
 // tail of mctx gumbel_muzero_policy: best considered action + completed-Q policy target

@@ -57,7 +57,8 @@ static int ensure_step_state(mzs_handle* h) {
   if (h->step.allocated) return MZS_OK;
   const int rows = c.policy == 1 ? c.max_num_considered_actions + 1 : 0;
   const int table_words = rows * c.num_simulations;
-  hipError_t e = h->step.allocate(c.batch, c.num_simulations + 1, c.num_actions, c.embed_dim, table_words);
+  const int slots = c.num_actions + (c.policy == 2 ? c.num_chance_outcomes : 0);  // stochastic: actions, then chance outcomes
+  hipError_t e = h->step.allocate(c.batch, c.num_simulations + 1, slots, c.embed_dim, table_words);
   if (e != hipSuccess) return fail(h, MZS_E_RUNTIME, "tree allocation: %s", hipGetErrorString(e));
   // cached-decision kernels (mz_step_jump.cuh): bounded tree, B N^2 path words within the slab budget (8 GiB of the
   // 288 GB: 4096 roots x 300 simulations are 1.5 GB; MZS_JUMP_BUDGET_MB overrides); MZS_STEP_WALK=1 keeps the
@@ -69,7 +70,7 @@ static int ensure_step_state(mzs_handle* h) {
   const char* mb = getenv("MZS_JUMP_BUDGET_MB");
   const size_t budget = mb && atoll(mb) > 0 ? (size_t)atoll(mb) << 20 : (size_t)8 << 30;
   const size_t per_root = (3 * N + N * N) * 4;
-  if (N <= (size_t)mz::kJumpMaxNodes && !(walk && walk[0] == '1')) {
+  if (N <= (size_t)mz::kJumpMaxNodes && !(walk && walk[0] == '1') && c.policy != 2) {  // (chance nodes: walked only)
     const bool whole = B * per_root <= budget;
     size_t roots = whole ? B : budget / per_root;
     if (roots > B) roots = B;
@@ -110,6 +111,7 @@ int mzs_root(mzs_handle* h, const float* prior_logits, const float* value, const
   const mzs_config& c = h->cfg;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   MZS_HIP(h, hipSetDevice(c.device));
+  if (c.policy == 2) return fail(h, MZS_E_INVALID, "mzs_root: this handle runs the stochastic policy; use mzs_root_stochastic");
   if (c.policy != 0) return fail(h, MZS_E_INVALID, "mzs_root: this handle runs the gumbel policy; use mzs_root_gumbel");
   if (int rc = ensure_step_state(h)) return rc;
   uint32_t zero[2] = {0, 0};
@@ -134,7 +136,7 @@ int mzs_root_gumbel(mzs_handle* h, const float* prior_logits, const float* value
   if (!h) return MZS_E_INVALID;
   if (!prior_logits || !value || !embedding) return fail(h, MZS_E_INVALID, "mzs_root_gumbel: null input");
   const mzs_config& c = h->cfg;
-  if (c.policy != 1) return fail(h, MZS_E_INVALID, "mzs_root_gumbel: handle was created with policy 0 (muzero)");
+  if (c.policy != 1) return fail(h, MZS_E_INVALID, "mzs_root_gumbel: this handle does not run the gumbel policy (policy 1)");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   MZS_HIP(h, hipSetDevice(c.device));
   if (int rc = ensure_step_state(h)) return rc;
@@ -157,6 +159,7 @@ int mzs_select(mzs_handle* h, int32_t sim, int32_t* action_out, float* parent_em
   if (sim < 0 || sim >= h->cfg.num_simulations) return fail(h, MZS_E_INVALID, "mzs_select: sim out of range");
   if (!action_out || !parent_embedding_out) return fail(h, MZS_E_INVALID, "mzs_select: null output");
   const mzs_config& c = h->cfg;
+  if (c.policy == 2) return fail(h, MZS_E_INVALID, "mzs_select: this handle runs the stochastic policy; use mzs_select_stochastic");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   MZS_HIP(h, hipSetDevice(c.device));
   mz::StepArgs sa = h->step.args(c);
@@ -185,6 +188,7 @@ static int expand_backup_impl(mzs_handle* h, int32_t sim, const float* reward, c
   if (!reward || !discount || !prior_logits || !value || !next_embedding)
     return fail(h, MZS_E_INVALID, "%s: null input", who);
   const mzs_config& c = h->cfg;
+  if (c.policy == 2) return fail(h, MZS_E_INVALID, "%s: this handle runs the stochastic policy; use mzs_expand_backup_stochastic", who);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   MZS_HIP(h, hipSetDevice(c.device));
   mz::StepArgs sa = h->step.args(c);
@@ -231,9 +235,90 @@ int mzs_finish(mzs_handle* h, float temperature, const float* gumbel, int32_t* a
   if (!h->step.rooted) return fail(h, MZS_E_INVALID, "mzs_finish: call mzs_root first");
   if (!action_out || !action_weights_out) return fail(h, MZS_E_INVALID, "mzs_finish: null output");
   const mzs_config& c = h->cfg;
+  if (c.policy == 2) return fail(h, MZS_E_INVALID, "mzs_finish: this handle runs the stochastic policy; use mzs_finish_stochastic");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   MZS_HIP(h, hipSetDevice(c.device));
   launch_finish(h, h->step.args(c), temperature, gumbel, action_out, action_weights_out, search_value_out, depth_sum_out, stream);
+  MZS_HIP(h, hipGetLastError());
+  return MZS_OK;
+}
+
+// ---- stochastic policy (policy == 2): the walking kernels with chance nodes at odd depth ----
+static int stochastic_handle(mzs_handle* h, const char* who, bool rooted) {
+  if (!h) return MZS_E_INVALID;
+  if (h->cfg.policy != 2) return fail(h, MZS_E_INVALID, "%s: this handle does not run the stochastic policy (policy 2)", who);
+  if (rooted && !h->step.rooted) return fail(h, MZS_E_INVALID, "%s: call mzs_root_stochastic first", who);
+  return MZS_OK;
+}
+
+int mzs_root_stochastic(mzs_handle* h, const float* prior_logits, const float* value, const float* embedding,
+                        const uint8_t* invalid_actions, const float* dirichlet_noise, float dirichlet_fraction,
+                        const uint32_t key[2], void* stream_) {
+  if (int rc = stochastic_handle(h, "mzs_root_stochastic", false)) return rc;
+  if (!prior_logits || !value || !embedding) return fail(h, MZS_E_INVALID, "mzs_root_stochastic: null input");
+  if (!dirichlet_noise && dirichlet_fraction != 0.0f)
+    return fail(h, MZS_E_INVALID, "mzs_root_stochastic: dirichlet_fraction != 0 needs dirichlet_noise");
+  const mzs_config& c = h->cfg;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MZS_HIP(h, hipSetDevice(c.device));
+  if (int rc = ensure_step_state(h)) return rc;
+  uint32_t zero[2] = {0, 0};
+  mzh::derive_keys(key ? key : zero, c.num_simulations, h->k_sample, h->sim_keys.data());
+  if (c.tiebreak)
+    MZS_HIP(h, hipMemcpyAsync(h->step.sim_keys, h->sim_keys.data(), sizeof(uint32_t) * 2 * (size_t)c.num_simulations,
+                              hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(mz::step_root_stochastic_kernel, dim3(step_grid(c.batch)), dim3(step_block(c.batch)), 0, stream,
+                     h->step.args(c), prior_logits, value, embedding, c.state_embed_dim, invalid_actions, dirichlet_noise,
+                     dirichlet_fraction);
+  MZS_HIP(h, hipGetLastError());
+  h->step.rooted = true;
+  return MZS_OK;
+}
+
+int mzs_select_stochastic(mzs_handle* h, int32_t sim, int32_t* slot_out, int32_t* parent_is_decision_out,
+                          float* parent_embedding_out, void* stream_) {
+  if (int rc = stochastic_handle(h, "mzs_select_stochastic", true)) return rc;
+  const mzs_config& c = h->cfg;
+  if (sim < 0 || sim >= c.num_simulations) return fail(h, MZS_E_INVALID, "mzs_select_stochastic: sim out of range");
+  if (!slot_out || !parent_is_decision_out || !parent_embedding_out)
+    return fail(h, MZS_E_INVALID, "mzs_select_stochastic: null output");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MZS_HIP(h, hipSetDevice(c.device));
+  hipLaunchKernelGGL(mz::step_select_stochastic_kernel, dim3(step_grid(c.batch)), dim3(step_block(c.batch)), 0, stream,
+                     h->step.args(c), sim, slot_out, parent_is_decision_out, parent_embedding_out);
+  MZS_HIP(h, hipGetLastError());
+  return MZS_OK;
+}
+
+int mzs_expand_backup_stochastic(mzs_handle* h, int32_t sim, const mzs_stochastic_outputs* o, void* stream_) {
+  if (int rc = stochastic_handle(h, "mzs_expand_backup_stochastic", true)) return rc;
+  const mzs_config& c = h->cfg;
+  if (sim < 0 || sim >= c.num_simulations) return fail(h, MZS_E_INVALID, "mzs_expand_backup_stochastic: sim out of range");
+  if (!o || o->struct_size != (int32_t)sizeof(mzs_stochastic_outputs))
+    return fail(h, MZS_E_INVALID, "mzs_expand_backup_stochastic: null or size mismatch (ABI)");
+  if (!o->chance_logits || !o->afterstate_value || !o->afterstate_embedding || !o->action_logits || !o->value || !o->reward ||
+      !o->discount || !o->state_embedding)
+    return fail(h, MZS_E_INVALID, "mzs_expand_backup_stochastic: null input");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MZS_HIP(h, hipSetDevice(c.device));
+  const mz::StochasticOutputs k = {o->chance_logits, o->afterstate_value, o->afterstate_embedding, o->action_logits, o->value,
+                                   o->reward, o->discount, o->state_embedding, c.afterstate_embed_dim, c.state_embed_dim};
+  hipLaunchKernelGGL(mz::step_expand_backup_stochastic_kernel, dim3(step_grid(c.batch)), dim3(step_block(c.batch)), 0, stream,
+                     h->step.args(c), sim, k);
+  MZS_HIP(h, hipGetLastError());
+  return MZS_OK;
+}
+
+int mzs_finish_stochastic(mzs_handle* h, float temperature, const float* gumbel, int32_t* action_out, float* action_weights_out,
+                          float* search_value_out, int32_t* depth_sum_out, void* stream_) {
+  if (int rc = stochastic_handle(h, "mzs_finish_stochastic", true)) return rc;
+  if (!action_out || !action_weights_out) return fail(h, MZS_E_INVALID, "mzs_finish_stochastic: null output");
+  const mzs_config& c = h->cfg;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MZS_HIP(h, hipSetDevice(c.device));
+  hipLaunchKernelGGL(mz::step_finish_stochastic_kernel, dim3(step_grid(c.batch)), dim3(step_block(c.batch)), 0, stream,
+                     h->step.args(c), temperature, gumbel, h->k_sample[0], h->k_sample[1], action_out, action_weights_out,
+                     search_value_out, depth_sum_out);
   MZS_HIP(h, hipGetLastError());
   return MZS_OK;
 }
@@ -249,17 +334,18 @@ int mzs_tree_export(mzs_handle* h, const mzs_tree_view* out, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   MZS_HIP(h, hipSetDevice(c.device));
   const size_t BN = (size_t)c.batch * (c.num_simulations + 1);
+  const size_t A = (size_t)c.num_actions + (c.policy == 2 ? c.num_chance_outcomes : 0);  // stochastic: every slot of a node
   const mz::StepState& s = h->step;
 #define CP(dst, src, n) MZS_HIP(h, hipMemcpyAsync(dst, src, (n) * 4, hipMemcpyDeviceToDevice, stream))
   CP(out->node_visits, s.node_visits, BN); CP(out->raw_values, s.raw_values, BN);
   CP(out->node_values, s.node_values, BN); CP(out->parents, s.parents, BN);
   CP(out->action_from_parent, s.action_from_parent, BN);
-  CP(out->children_index, s.children_index, BN * c.num_actions);
-  CP(out->children_prior_logits, s.children_prior_logits, BN * c.num_actions);
-  CP(out->children_values, s.children_values, BN * c.num_actions);
-  CP(out->children_visits, s.children_visits, BN * c.num_actions);
-  CP(out->children_rewards, s.children_rewards, BN * c.num_actions);
-  CP(out->children_discounts, s.children_discounts, BN * c.num_actions);
+  CP(out->children_index, s.children_index, BN * A);
+  CP(out->children_prior_logits, s.children_prior_logits, BN * A);
+  CP(out->children_values, s.children_values, BN * A);
+  CP(out->children_visits, s.children_visits, BN * A);
+  CP(out->children_rewards, s.children_rewards, BN * A);
+  CP(out->children_discounts, s.children_discounts, BN * A);
   CP(out->embeddings, s.embeddings, BN * c.embed_dim);
 #undef CP
   return MZS_OK;

@@ -60,7 +60,9 @@ class MuZero:
     r"""MuZero algorithm (muax/model.py:16-50).
 
     Parameters mirror the reference: `network` (MZNetwork) or the three plugin callables, `policy_class`
-    / `policy`, `optimizer`, `loss_fn`, `discount`, `support_size`.  `recurrent_pred_on` selects which
+    / `policy` ("muzero" or "gumbel"; "stochastic" raises NotImplementedError: the network trio has no decision and
+    chance functions -- call StochasticMuZeroPolicy with your own), `optimizer`, `loss_fn`, `discount`,
+    `support_size`.  `recurrent_pred_on` selects which
     embedding the prediction net sees inside the search: "child" as muax/model.py:272, "parent" as the
     pip-release class muax/frameworks/coax/model.py:447-448.
     """
@@ -78,7 +80,10 @@ class MuZero:
             self.network = MZNetwork(rep, prediction_fn, dynamic_fn)
         if policy is not None:
             if policy not in ("muzero", "gumbel"):
-                raise NotImplementedError(f"policy={policy!r}: 'muzero' and 'gumbel' are built (SURVEY.md 8(f))")
+                # (the stochastic search itself is built -- StochasticMuZeroPolicy -- but this class's network trio has no
+                # decision / chance functions to hand it)
+                raise NotImplementedError(f"policy={policy!r}: MuZero runs 'muzero' and 'gumbel'; StochasticMuZeroPolicy is "
+                                          "called directly with decision_recurrent_fn and chance_recurrent_fn")
             policy_class = MuZeroPolicy if policy == "muzero" else GumbelMuZeroPolicy
         if not (isinstance(policy_class, type) and issubclass(policy_class, Policy)):
             raise TypeError("policy_class must be a subclass of muax_amd.policy.Policy")

@@ -109,9 +109,77 @@ class GumbelMuZeroPolicy(Policy):
 
 
 class StochasticMuZeroPolicy(Policy):
-    """muax/policy.py:50-67: out of scope (chance nodes; nothing in the core reference supplies the
-    decision/chance recurrent functions)."""
+    """muax/policy.py:50-67: mctx.stochastic_muzero_policy with the same keyword defaults, on the step-wise HIP
+    kernels (chance nodes at odd depth, MuZeroSearch.search_stochastic).
+
+    `root` is (prior_logits [B,A], value [B], state embedding [B,...]);
+    `decision_recurrent_fn(params, rng_key, action, state_embedding)` returns
+    (DecisionRecurrentFnOutput(chance_logits [B,C], afterstate_value [B]), afterstate_embedding) and
+    `chance_recurrent_fn(params, rng_key, chance_outcome, afterstate_embedding)` returns
+    (ChanceRecurrentFnOutput(action_logits [B,A], value, reward, discount [B]), state_embedding), as in mctx.
+    The number of chance outcomes and the afterstate embedding's shape come from the `num_chance_outcomes=` and
+    `afterstate_shape=` kwargs; without both, one dummy decision call at action 0 supplies them, as mctx does.
+    The returned search_tree is the decision slice [..., :A] of the children arrays (mctx's masked tree)."""
+
+    def __init__(self):
+        self._handles = {}
+        self._shapes = {}
 
     def __call__(self, params, rng_key, root, recurrent_fn=None, decision_recurrent_fn=None,
-                 chance_recurrent_fn=None, **kwargs):
-        raise NotImplementedError("stochastic MuZero is out of scope (SURVEY.md section 2, row 2)")
+                 chance_recurrent_fn=None, **kwargs) -> PolicyOutput:
+        if decision_recurrent_fn is None or chance_recurrent_fn is None:
+            raise ValueError("StochasticMuZeroPolicy needs decision_recurrent_fn and chance_recurrent_fn")
+        qt = kwargs.get("qtransform")
+        if getattr(qt, "__name__", qt) not in (None, "qtransform_by_parent_and_siblings"):
+            raise ValueError("only qtransform_by_parent_and_siblings is implemented")
+        prior_logits, value, embedding = root
+        B, A = prior_logits.shape
+        emb = embedding.reshape(B, -1)
+        shape = tuple(embedding.shape[1:])
+        C, after_shape = kwargs.get("num_chance_outcomes"), kwargs.get("afterstate_shape")
+        if C is None or after_shape is None:
+            skey = (fn_identity(decision_recurrent_fn), B, shape)
+            if skey not in self._shapes:
+                import torch
+                with torch.no_grad():
+                    out, after = decision_recurrent_fn(params, None, torch.zeros(B, dtype=torch.int32, device=emb.device),
+                                                       embedding)
+                self._shapes[skey] = (int(out[0].shape[-1]), tuple(after.shape[1:]))
+            C, after_shape = self._shapes[skey]
+        after_shape = tuple(after_shape)
+        Es, Ea = emb.shape[1], 1
+        for n in after_shape:
+            Ea *= int(n)
+        S = kwargs.get("num_simulations", 5)
+        key = (B, A, int(C), S, Es, Ea, kwargs.get("max_depth"), kwargs.get("tiebreak", True), kwargs.get("pb_c_init", 1.25),
+               kwargs.get("pb_c_base", 19652), str(prior_logits.device), kwargs.get("global_batch"),
+               kwargs.get("root_offset", 0))
+        if key not in self._handles:
+            cfg = SearchConfig(A, S, max(Es, Ea), max_depth=kwargs.get("max_depth"), tiebreak=kwargs.get("tiebreak", True),
+                               pb_c_init=kwargs.get("pb_c_init", 1.25), pb_c_base=float(kwargs.get("pb_c_base", 19652)),
+                               global_batch=kwargs.get("global_batch"), root_offset=kwargs.get("root_offset", 0),
+                               policy="stochastic", num_chance_outcomes=int(C), state_embed_dim=Es, afterstate_embed_dim=Ea)
+            self._handles[key] = MuZeroSearch(B, cfg, prior_logits.device)
+        h = self._handles[key]
+
+        def decision(action, flat_state):
+            out, after = decision_recurrent_fn(params, None, action, flat_state.reshape((B,) + shape))
+            return out, after.reshape(B, -1)
+
+        def chance(outcome, flat_after):
+            out, state = chance_recurrent_fn(params, None, outcome, flat_after.reshape((B,) + after_shape))
+            return out, state.reshape(B, -1)
+
+        out = h.search_stochastic((prior_logits, value, emb), decision, chance, key=rng_key,
+                                  invalid_actions=kwargs.get("invalid_actions"),
+                                  dirichlet_noise=kwargs.get("dirichlet_noise"),
+                                  dirichlet_fraction=kwargs.get("dirichlet_fraction", 0.25),
+                                  temperature=kwargs.get("temperature", 1.0), gumbel=kwargs.get("gumbel"),
+                                  with_tree=kwargs.get("with_tree", False), graph=kwargs.get("graph", False),
+                                  graph_key=(fn_identity(decision_recurrent_fn), fn_identity(chance_recurrent_fn),
+                                             id(params), shape),
+                                  graph_version=kwargs.get("graph_version", 0))
+        t = out.search_tree
+        if t is not None:  # mctx _mask_tree(tree, num_actions, 'decision')
+            t = t._replace(**{f: getattr(t, f)[..., :A] for f in t._fields if f.startswith("children_")})
+        return PolicyOutput(out.action, out.action_weights, t)

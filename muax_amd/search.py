@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import (MLP_WEIGHT_NAMES, TREE_FIELDS, TREE_INT_FIELDS, MzsActArgs, MzsActHostArgs, MzsConfig,
-                   MzsMlpWeights, MzsTreeView)
+                   MzsMlpWeights, MzsStochasticOutputs, MzsTreeView)
 
 
 class SearchTree(NamedTuple):
@@ -42,6 +42,20 @@ class PolicyOutput(NamedTuple):
     search_tree: Optional[SearchTree]
 
 
+class DecisionRecurrentFnOutput(NamedTuple):
+    """mctx.DecisionRecurrentFnOutput: what the decision function says of the afterstate of (state, action)."""
+    chance_logits: torch.Tensor      # [B, C]
+    afterstate_value: torch.Tensor   # [B]
+
+
+class ChanceRecurrentFnOutput(NamedTuple):
+    """mctx.ChanceRecurrentFnOutput: what the chance function says of the state after (afterstate, chance outcome)."""
+    action_logits: torch.Tensor      # [B, A]
+    value: torch.Tensor              # [B]
+    reward: torch.Tensor             # [B]
+    discount: torch.Tensor           # [B]
+
+
 @dataclass
 class SearchConfig:
     """Keyword arguments of MuZero.act that reach mctx.muzero_policy (muax/model.py:86-95)."""
@@ -54,10 +68,15 @@ class SearchConfig:
     pb_c_base: float = 19652.0
     global_batch: Optional[int] = None
     root_offset: int = 0
-    policy: str = "muzero"         # "muzero" (muax/policy.py:13-30) or "gumbel" (muax/policy.py:33-47)
+    policy: str = "muzero"         # "muzero" (muax/policy.py:13-30), "gumbel" (:33-47) or "stochastic" (:50-67)
     qtransform: str = "qtransform_by_parent_and_siblings"   # or "qtransform_completed_by_mix_value" (gumbel)
     max_num_considered_actions: int = 16
     gumbel_scale: float = 1.0
+    # policy "stochastic": C chance outcomes (num_actions + C <= 64) and the widths of the state and the afterstate
+    # embedding (None: embed_dim); embed_dim is the larger of the two
+    num_chance_outcomes: int = 0
+    state_embed_dim: Optional[int] = None
+    afterstate_embed_dim: Optional[int] = None
 
 
 _NO_ACT_CACHE = bool(__import__("os").environ.get("MUAX_AMD_NO_ACT_CACHE"))  # A/B switch of act_mlp's argument cache
@@ -124,7 +143,7 @@ class MuZeroSearch:
         c.num_simulations, c.embed_dim = cfg.num_simulations, cfg.embed_dim
         c.max_depth = cfg.max_depth or 0
         try:
-            c.policy = {"muzero": 0, "gumbel": 1}[cfg.policy]
+            c.policy = {"muzero": 0, "gumbel": 1, "stochastic": 2}[cfg.policy]
             c.qtransform = {"qtransform_by_parent_and_siblings": 0, "qtransform_completed_by_mix_value": 1}[
                 getattr(cfg.qtransform, "__name__", cfg.qtransform)]
         except KeyError as e:
@@ -134,6 +153,13 @@ class MuZeroSearch:
         c.pb_c_init, c.pb_c_base = cfg.pb_c_init, cfg.pb_c_base
         c.global_batch = cfg.global_batch or self.batch
         c.root_offset = cfg.root_offset
+        self._stochastic = cfg.policy == "stochastic"
+        self._es, self._ea = cfg.state_embed_dim or cfg.embed_dim, cfg.afterstate_embed_dim or cfg.embed_dim
+        if self._stochastic:
+            c.num_chance_outcomes, c.state_embed_dim, c.afterstate_embed_dim = cfg.num_chance_outcomes, self._es, self._ea
+        elif cfg.num_chance_outcomes:
+            raise ValueError("num_chance_outcomes is for policy='stochastic'")
+        self._slots = cfg.num_actions + (cfg.num_chance_outcomes if self._stochastic else 0)  # children per node
         h = C.c_void_p()
         _lib.check(self._L.mzs_create(C.byref(c), C.byref(h)))
         self._h = h
@@ -147,6 +173,8 @@ class MuZeroSearch:
             self.root_value = self._out[B + B * A:]
             self.search_value = torch.empty(B, dtype=torch.float32, device=self.device)
             self.depth_sum = torch.empty(B, dtype=torch.int32, device=self.device)
+            # select_stochastic: 1 where the selected edge leaves a decision node
+            self.parent_is_decision = torch.empty(B, dtype=torch.int32, device=self.device)
         self._out_host = None   # pinned mirror of _out (outputs_to_host)
         self._obs_stage = None  # (pinned host [B, obs_dim], its NumPy view, device twin, copy-done event)
         self._tree = None
@@ -192,7 +220,7 @@ class MuZeroSearch:
     def _alloc_tree(self) -> SearchTree:
         if self._tree is None:
             B, N = self.batch, self.cfg.num_simulations + 1
-            A, E = self.cfg.num_actions, self.cfg.embed_dim
+            A, E = self._slots, self.cfg.embed_dim
             shapes = {"embeddings": (B, N, E)}
             out = {}
             for f in TREE_FIELDS:
@@ -550,3 +578,111 @@ class MuZeroSearch:
                 entry = self._graphs[gkey] = (g, recurrent_fn, self._keep, graph_version)
             entry[0].replay()
         return self.finish(temperature, None if self.cfg.policy == "gumbel" else gumbel, with_tree)
+
+    # ------------------------------------------------------------------ step-wise path, stochastic policy
+    def root_stochastic(self, prior_logits, value, embedding, key=0, invalid_actions=None, dirichlet_noise=None,
+                        dirichlet_fraction: float = 0.25):
+        """RootFnOutput -> tree (mctx stochastic_muzero_policy prelude): the MuZero root over the A actions, the chance
+        slots padded with -inf / invalid.  embedding: the root's STATE embedding [B, state_embed_dim]."""
+        B, A, E = self.batch, self.cfg.num_actions, self.cfg.embed_dim
+        pl = self._f32(prior_logits, (B, A), "prior_logits")
+        v = self._f32(value, (B,), "value")
+        emb = self._f32(torch.as_tensor(embedding, device=self.device).reshape(B, -1), (B, self._es), "embedding")
+        inv = self._u8(invalid_actions, (B, A), "invalid_actions")
+        noise = self._f32(dirichlet_noise, (B, A), "dirichlet_noise")
+        kw = (C.c_uint32 * 2)(*key_words(key))
+        _lib.check(self._L.mzs_root_stochastic(self._h, _ptr(pl), _ptr(v), _ptr(emb), _ptr(inv), _ptr(noise),
+                                               C.c_float(dirichlet_fraction if noise is not None else 0.0),
+                                               C.byref(kw), self._stream()), self._h)
+        self._keep = (pl, v, emb, inv, noise)
+        if self._parent_emb is None:
+            self._parent_emb = torch.empty(B, E, dtype=torch.float32, device=self.device)
+
+    def select_stochastic(self, sim: int):
+        """One simulate() over decision and chance nodes: (slot [B] int32 in [0, A + C), parent_is_decision [B] int32,
+        parent embedding [B, embed_dim] -- the parent's own kind of embedding, zero-padded)."""
+        if self._parent_emb is None:
+            self._parent_emb = torch.empty(self.batch, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
+        _lib.check(self._L.mzs_select_stochastic(self._h, sim, _ptr(self.action), _ptr(self.parent_is_decision),
+                                                 _ptr(self._parent_emb), self._stream()), self._h)
+        return self.action, self.parent_is_decision, self._parent_emb
+
+    def expand_backup_stochastic(self, sim: int, decision_out, afterstate_embedding, chance_out, state_embedding):
+        """Both functions' outputs for every root (DecisionRecurrentFnOutput + afterstate embedding,
+        ChanceRecurrentFnOutput + state embedding): the kernel takes, per root, the set of its parent's kind."""
+        B, A, Cn = self.batch, self.cfg.num_actions, self.cfg.num_chance_outcomes
+        dev = self.device
+        keep = (self._f32(decision_out[0], (B, Cn), "chance_logits"), self._f32(decision_out[1], (B,), "afterstate_value"),
+                self._f32(torch.as_tensor(afterstate_embedding, device=dev).reshape(B, -1), (B, self._ea), "afterstate_embedding"),
+                self._f32(chance_out[0], (B, A), "action_logits"), self._f32(chance_out[1], (B,), "value"),
+                self._f32(chance_out[2], (B,), "reward"), self._f32(chance_out[3], (B,), "discount"),
+                self._f32(torch.as_tensor(state_embedding, device=dev).reshape(B, -1), (B, self._es), "state_embedding"))
+        o = MzsStochasticOutputs()
+        o.struct_size = C.sizeof(MzsStochasticOutputs)
+        (o.chance_logits, o.afterstate_value, o.afterstate_embedding, o.action_logits, o.value, o.reward, o.discount,
+         o.state_embedding) = (t.data_ptr() for t in keep)
+        _lib.check(self._L.mzs_expand_backup_stochastic(self._h, sim, C.byref(o), self._stream()), self._h)
+        self._keep = keep
+
+    def finish_stochastic(self, temperature: float = 1.0, gumbel=None, with_tree: bool = False) -> PolicyOutput:
+        """Summary and sample over the A actions; with_tree: the full tree, children arrays [B, N, A + C]."""
+        B, A = self.batch, self.cfg.num_actions
+        gum = self._f32(gumbel, (B, A), "gumbel")
+        _lib.check(self._L.mzs_finish_stochastic(self._h, C.c_float(temperature), _ptr(gum), _ptr(self.action),
+                                                 _ptr(self.action_weights), _ptr(self.search_value),
+                                                 _ptr(self.depth_sum), self._stream()), self._h)
+        self._keep = (gum,)
+        tree = None
+        if with_tree:
+            tree = self._alloc_tree()
+            view = self._tree_view(tree)
+            _lib.check(self._L.mzs_tree_export(self._h, C.byref(view), self._stream()), self._h)
+        return PolicyOutput(self.action, self.action_weights, tree)
+
+    def search_stochastic(self, root_fn_output, decision_fn, chance_fn, key=0, invalid_actions=None, dirichlet_noise=None,
+                          dirichlet_fraction=0.25, temperature=1.0, gumbel=None, with_tree=False, graph=False,
+                          graph_key=None, graph_version=0) -> PolicyOutput:
+        """mctx.stochastic_muzero_policy with caller-supplied functions of torch tensors:
+        decision_fn(action [B], state_embedding [B, state_embed_dim]) -> (DecisionRecurrentFnOutput, afterstate_embedding),
+        chance_fn(outcome [B], afterstate_embedding [B, afterstate_embed_dim]) -> (ChanceRecurrentFnOutput, state_embedding).
+
+        As in mctx BOTH functions are evaluated on all rows in every simulation -- the decision function at action
+        clamp(slot, 0, A - 1), the chance function at outcome clamp(slot - A, 0, C - 1), each on the parent row cut to its
+        own width -- and the expansion kernel keeps, per root, the half that matches the parent's kind.  key, noise,
+        invalid_actions, temperature, gumbel ([B, A]), with_tree and graph= / graph_key= / graph_version= as in search()."""
+        prior_logits, value, embedding = root_fn_output
+        A, Cn, S = self.cfg.num_actions, self.cfg.num_chance_outcomes, self.cfg.num_simulations
+
+        def do_root():
+            self.root_stochastic(prior_logits, value, embedding, key, invalid_actions, dirichlet_noise, dirichlet_fraction)
+
+        def loop():
+            for sim in range(S):
+                slot, _, pemb = self.select_stochastic(sim)
+                d_out, after = decision_fn(slot.clamp(0, A - 1), pemb[:, :self._es])
+                c_out, state = chance_fn((slot - A).clamp(0, Cn - 1), pemb[:, :self._ea])
+                self.expand_backup_stochastic(sim, d_out, after, c_out, state)
+
+        do_root()
+        if not graph:
+            loop()
+        else:
+            gkey = graph_key if graph_key is not None else (fn_identity(decision_fn), fn_identity(chance_fn))
+            entry = self._graphs.get(gkey)
+            if entry is not None and entry[3] != graph_version:
+                entry = None
+            if entry is None:
+                # warm-up run, then the tree is rebuilt from the same root and the loop is captured (as in search())
+                with torch.no_grad():
+                    side = torch.cuda.Stream(device=self.device)
+                    side.wait_stream(torch.cuda.current_stream(self.device))
+                    with torch.cuda.stream(side):
+                        loop()
+                    torch.cuda.current_stream(self.device).wait_stream(side)
+                    do_root()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        loop()
+                entry = self._graphs[gkey] = (g, (decision_fn, chance_fn), self._keep, graph_version)
+            entry[0].replay()
+        return self.finish_stochastic(temperature, gumbel, with_tree)

@@ -1,0 +1,92 @@
+"""What the chance rule and the merged expansion cost per simulation: one act of the stochastic step-wise search
+(4 actions + 32 chance outcomes, Stochastic MuZero's 2048 shape) beside the deterministic walking search (MZS_STEP_WALK=1)
+at 36 actions -- the same slots per node, simulations and roots, scripted net outputs (fixed tensors: no net time), two
+tree launches per simulation on either side.  Runs alternate between the two; medians and ranges over `--repeats`.
+
+    python tools/bench_stochastic.py [--sims 50] [--repeats 15] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+os.environ["MZS_STEP_WALK"] = "1"  # (read when a handle first allocates its tree)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from muax_amd import MuZeroSearch, SearchConfig  # noqa: E402
+
+A, C, E = 4, 32, 32
+
+
+def make(batch, sims):
+    g = torch.Generator().manual_seed(batch)
+    r = lambda *s: torch.randn(*s, generator=g).cuda()  # noqa: E731
+    st = MuZeroSearch(batch, SearchConfig(A, sims, E, policy="stochastic", num_chance_outcomes=C))
+    de = MuZeroSearch(batch, SearchConfig(A + C, sims, E, policy="muzero"))
+    disc = torch.full((batch,), 0.99).cuda()
+    s_root, d_root = (r(batch, A), r(batch), r(batch, E)), (r(batch, A + C), r(batch), r(batch, E))
+    s_out = ((r(batch, C), r(batch)), r(batch, E), (r(batch, A), r(batch), r(batch), disc), r(batch, E))
+    d_out = (r(batch), disc, r(batch, A + C), r(batch), r(batch, E))
+
+    def stochastic():
+        st.root_stochastic(*s_root, key=1)
+        for sim in range(sims):
+            st.select_stochastic(sim)
+            st.expand_backup_stochastic(sim, *s_out)
+        st.finish_stochastic()
+
+    def deterministic():
+        de.root(*d_root, key=1)
+        for sim in range(sims):
+            de.select(sim)
+            de.expand_backup(sim, *d_out)
+        de.finish()
+
+    return stochastic, deterministic, (st, de)
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3  # us
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sims", type=int, default=50)
+    ap.add_argument("--repeats", type=int, default=15)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    rows = []
+    for batch in (64, 1024):
+        sto, det, handles = make(batch, args.sims)
+        for _ in range(3):
+            sto(), det()
+        torch.cuda.synchronize()
+        t = {"stochastic": [], "deterministic": []}
+        for _ in range(args.repeats):  # alternating
+            t["stochastic"].append(timed(sto))
+            t["deterministic"].append(timed(det))
+        row = {"roots": batch, "sims": args.sims}
+        for k, v in t.items():
+            row[k] = {"median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1),
+                      "per_sim_us": round(statistics.median(v) / args.sims, 2)}
+        row["depth_mean"] = {k: round(float(h.depth_sum.float().mean()) / args.sims, 2)
+                             for k, h in zip(("stochastic", "deterministic"), handles)}
+        rows.append(row)
+        print(json.dumps(row))
+        for h in handles:
+            h.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
