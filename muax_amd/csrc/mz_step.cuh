@@ -47,6 +47,9 @@ struct StepArgs {
 
 constexpr int kWideEmb = 256;
 
+// children slots of a node: the actions and, under the stochastic policy, the chance outcomes after them
+inline int slots_per_node(const mzs_config& c) { return c.num_actions + (c.policy == 2 ? c.num_chance_outcomes : 0); }
+
 struct StepState {
   bool allocated = false, rooted = false;
   int32_t* node_visits = nullptr; float* raw_values = nullptr; float* node_values = nullptr;
@@ -97,7 +100,7 @@ struct StepState {
   StepArgs args(const mzs_config& c) const {
     StepArgs a;
     a.B = c.batch; a.N = c.num_simulations + 1; a.AD = c.num_actions; a.E = c.embed_dim;
-    a.A = c.num_actions + (c.policy == 2 ? c.num_chance_outcomes : 0);
+    a.A = slots_per_node(c);
     a.S = c.num_simulations; a.max_depth = c.max_depth > 0 ? c.max_depth : c.num_simulations;
     a.tiebreak = c.tiebreak; a.pb_c_init = c.pb_c_init; a.pb_c_base = c.pb_c_base;
     a.global_batch = (uint64_t)c.global_batch; a.root_offset = (uint64_t)c.root_offset;

@@ -44,32 +44,35 @@ MZ_DEV void root_clear_tree(const StepArgs& s, size_t rb, int j) {
     for (size_t i = j; i < (size_t)N * E; i += 16) s.embeddings[rb * E + i] = 0.0f;
 }
 
-// mctx instantiate_tree_from_root + muzero_policy prelude (dirichlet, mask)
-__global__ __launch_bounds__(256) void step_root_kernel(StepArgs s, const float* prior_logits,
-                                                         const float* value, const float* embedding,
-                                                         const uint8_t* invalid, const float* noise,
-                                                         float fraction, int gumbel_policy,
-                                                         const float* gumbel_in, uint32_t gk0, uint32_t gk1) {
-  MZ_ROW_SETUP
+// mctx instantiate_tree_from_root + the policy's prelude, for root row r.  The MuZero prelude (muzero_policy: Dirichlet
+// mix, log, mask) runs over the row's first AD slots (prior_logits, invalid, noise: [B, AD]) and pads the slots AD..A with
+// -inf logits and the invalid mark: AD < A is stochastic_muzero_policy's root (A - AD chance slots), AD == A pads nothing
+// and IS the deterministic root -- same operations, same order.  The Gumbel prelude (AD == A) is a branch of its own.
+// embedding: [B, es], es <= E, into a row that root_clear_tree zeroed.
+MZ_DEV void root_row(const StepArgs& s, int r, int j, int AD, int es, const float* prior_logits, const float* value,
+                     const float* embedding, const uint8_t* invalid, const float* noise, float fraction,
+                     int gumbel_policy, const float* gumbel_in, uint32_t gk0, uint32_t gk1) {
+  const int N = s.N, A = s.A, E = s.E;
+  const size_t rb = (size_t)r * N;
   root_clear_tree(s, rb, j);
   float x[kMaxAS], pr[kMaxAS], lg[kMaxAS];
   bool inv[kMaxAS];
 #pragma unroll
   for (int t = 0; t < kMaxAS; ++t) {
     int a = j + 16 * t;
-    x[t] = a < A ? prior_logits[(size_t)r * A + a] : 0.0f;
-    inv[t] = (invalid != nullptr && a < A) ? invalid[(size_t)r * A + a] != 0 : false;
-    if (a < A) s.root_invalid[(size_t)r * A + a] = inv[t] ? 1 : 0;
+    x[t] = a < AD ? prior_logits[(size_t)r * AD + a] : 0.0f;
+    inv[t] = (invalid != nullptr && a < AD) ? invalid[(size_t)r * AD + a] != 0 : false;
+    if (a < A) s.root_invalid[(size_t)r * A + a] = (a >= AD || inv[t]) ? 1 : 0;
   }
   bool any_invalid = false;
   if (!gumbel_policy) {
     // mctx muzero_policy prelude: Dirichlet mix, log
-    row_softmax_rt(x, A, j, pr);
+    row_softmax_rt(x, AD, j, pr);
     float keep = 1.0f - fraction;
 #pragma unroll
     for (int t = 0; t < kMaxAS; ++t) {
       int a = j + 16 * t;
-      float nz = (noise != nullptr && a < A) ? noise[(size_t)r * A + a] : 0.0f;
+      float nz = (noise != nullptr && a < AD) ? noise[(size_t)r * AD + a] : 0.0f;
       float noisy = keep * pr[t] + fraction * nz;
       lg[t] = log_pos(fmaxf(noisy, kFltTiny));
     }
@@ -97,8 +100,11 @@ __global__ __launch_bounds__(256) void step_root_kernel(StepArgs s, const float*
       }
     }
   }
+  row_mask_invalid(lg, inv, any_invalid, AD, j);
+#pragma unroll
+  for (int t = 0; t < kMaxAS; ++t) lg[t] = j + 16 * t < AD ? lg[t] : -INFINITY;
   float pq[kMaxAS];
-  row_mask_invalid_softmax(lg, inv, any_invalid, A, j, pq);
+  row_softmax_rt(lg, A, j, pq);
 #pragma unroll
   for (int t = 0; t < kMaxAS; ++t) {
     int a = j + 16 * t;
@@ -110,7 +116,7 @@ __global__ __launch_bounds__(256) void step_root_kernel(StepArgs s, const float*
   if (s.wide) {
     if (j == 0) s.xfer_node[r] = 0;
   } else {
-    for (int i = j; i < E; i += 16) s.embeddings[rb * E + i] = embedding[(size_t)r * E + i];
+    for (int i = j; i < es; i += 16) s.embeddings[rb * E + i] = embedding[(size_t)r * es + i];
   }
   if (j == 0) {
     s.node_visits[rb] = 1;
@@ -119,54 +125,21 @@ __global__ __launch_bounds__(256) void step_root_kernel(StepArgs s, const float*
     s.depth_sum[r] = 0;
   }
 }
-
-// mctx stochastic_muzero_policy's root: the muzero_policy prelude over the AD actions (prior_logits, invalid, noise:
-// [B, AD]), the row padded with -inf on the chance slots and the invalid mask with ones; embedding: [B, es], es <= E
+__global__ __launch_bounds__(256) void step_root_kernel(StepArgs s, const float* prior_logits,
+                                                         const float* value, const float* embedding,
+                                                         const uint8_t* invalid, const float* noise,
+                                                         float fraction, int gumbel_policy,
+                                                         const float* gumbel_in, uint32_t gk0, uint32_t gk1) {
+  MZ_ROW_SETUP
+  root_row(s, r, j, A, E, prior_logits, value, embedding, invalid, noise, fraction, gumbel_policy, gumbel_in, gk0, gk1);
+}
+// ... with chance slots (stochastic policy): AD = s.AD actions, a state embedding of es floats
 __global__ __launch_bounds__(256) void step_root_stochastic_kernel(StepArgs s, const float* prior_logits,
                                                                     const float* value, const float* embedding,
                                                                     int es, const uint8_t* invalid, const float* noise,
                                                                     float fraction) {
   MZ_ROW_SETUP
-  const int AD = s.AD;
-  root_clear_tree(s, rb, j);
-  float x[kMaxAS], pr[kMaxAS], lg[kMaxAS];
-  bool inv[kMaxAS];
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    const int a = j + 16 * t;
-    x[t] = a < AD ? prior_logits[(size_t)r * AD + a] : 0.0f;
-    inv[t] = (invalid != nullptr && a < AD) ? invalid[(size_t)r * AD + a] != 0 : false;
-    if (a < A) s.root_invalid[(size_t)r * A + a] = (a >= AD || inv[t]) ? 1 : 0;
-  }
-  row_softmax_rt(x, AD, j, pr);
-  const float keep = 1.0f - fraction;
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    const int a = j + 16 * t;
-    const float nz = (noise != nullptr && a < AD) ? noise[(size_t)r * AD + a] : 0.0f;
-    const float noisy = keep * pr[t] + fraction * nz;
-    lg[t] = log_pos(fmaxf(noisy, kFltTiny));
-  }
-  row_mask_invalid(lg, inv, invalid != nullptr, AD, j);
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) lg[t] = j + 16 * t < AD ? lg[t] : -INFINITY;
-  float pq[kMaxAS];
-  row_softmax_rt(lg, A, j, pq);
-#pragma unroll
-  for (int t = 0; t < kMaxAS; ++t) {
-    const int a = j + 16 * t;
-    if (a < A) {
-      s.children_prior_logits[rb * A + a] = lg[t];
-      s.children_prior_probs[rb * A + a] = pq[t];
-    }
-  }
-  for (int i = j; i < es; i += 16) s.embeddings[rb * E + i] = embedding[(size_t)r * es + i];
-  if (j == 0) {
-    s.node_visits[rb] = 1;
-    s.raw_values[rb] = value[r];
-    s.node_values[rb] = value[r];
-    s.depth_sum[r] = 0;
-  }
+  root_row(s, r, j, s.AD, es, prior_logits, value, embedding, invalid, noise, fraction, 0, nullptr, 0, 0);
 }
 
 // mctx search.simulate, level by level from the root (+ the parent-embedding gather of search.expand): the decisions of
@@ -257,6 +230,24 @@ MZ_DEV void expand_edge_backward(const StepArgs& s, size_t rb, int parent, int a
   }
 }
 
+// What an expansion of row r starts from: the record the selection left and the node it fills -- the edge's child where
+// one exists (re-expansion under max_depth), else node sim + 1
+struct Expansion { int parent, action, depth, newn; };
+MZ_DEV Expansion expansion_of(const StepArgs& s, size_t rb, int r, int sim) {
+  const int parent = s.sel_parent[r], action = s.sel_action[r], depth = s.sel_depth[r];
+  const int next = s.children_index[(rb + parent) * s.A + action];
+  return {parent, action, depth, next == -1 ? sim + 1 : next};
+}
+// ... and its embedding row: the w <= E floats of `row`, zero-padded to E (a wide row moves by emb_xfer_kernel)
+MZ_DEV void expand_embedding(const StepArgs& s, size_t rb, int r, int j, int newn, const float* row, int w) {
+  const int E = s.E;
+  if (s.wide) {
+    if (j == 0) s.xfer_node[r] = newn;
+  } else {
+    for (int i = j; i < E; i += 16) s.embeddings[(rb + newn) * E + i] = i < w ? row[i] : 0.0f;
+  }
+}
+
 // mctx search.expand (update_tree_node + edge) and search.backward
 __global__ __launch_bounds__(256) void step_expand_backup_kernel(StepArgs s, int sim, const float* reward,
                                                                   const float* discount,
@@ -264,19 +255,12 @@ __global__ __launch_bounds__(256) void step_expand_backup_kernel(StepArgs s, int
                                                                   const float* value,
                                                                   const float* next_embedding) {
   MZ_ROW_SETUP
-  const int parent = s.sel_parent[r], action = s.sel_action[r], depth = s.sel_depth[r];
-  const size_t eo = (rb + parent) * A + action;
-  int next = s.children_index[eo];
-  const int newn = next == -1 ? sim + 1 : next;
+  const Expansion x = expansion_of(s, rb, r, sim);
   const float v = value[r];
-  expand_prior_row(s, tree_view_global(s, rb), rb, newn, prior_logits + (size_t)r * A, j);
-  if (s.wide) {
-    if (j == 0) s.xfer_node[r] = newn;
-  } else {
-    for (int i = j; i < E; i += 16) s.embeddings[(rb + newn) * E + i] = next_embedding[(size_t)r * E + i];
-  }
+  expand_prior_row(s, tree_view_global(s, rb), rb, x.newn, prior_logits + (size_t)r * A, j);
+  expand_embedding(s, rb, r, j, x.newn, next_embedding + (size_t)r * E, E);
   const float rew_new = reward[r], dis_new = discount[r];
-  if (j == 0) expand_edge_backward(s, rb, parent, action, depth, newn, v, rew_new, dis_new);
+  if (j == 0) expand_edge_backward(s, rb, x.parent, x.action, x.depth, x.newn, v, rew_new, dis_new);
 }
 
 // mctx stochastic_muzero_policy's expansion: both functions' outputs arrive for every root and the row takes the set of
@@ -292,11 +276,8 @@ struct StochasticOutputs {
 __global__ __launch_bounds__(256) void step_expand_backup_stochastic_kernel(StepArgs s, int sim, StochasticOutputs o) {
   MZ_ROW_SETUP
   const int AD = s.AD, C = A - AD;
-  const int parent = s.sel_parent[r], action = s.sel_action[r], depth = s.sel_depth[r];
-  const bool chance_child = ((depth - 1) & 1) == 0;
-  const size_t eo = (rb + parent) * A + action;
-  const int next = s.children_index[eo];
-  const int newn = next == -1 ? sim + 1 : next;
+  const Expansion n = expansion_of(s, rb, r, sim);
+  const bool chance_child = ((n.depth - 1) & 1) == 0;
   float x[kMaxAS];
 #pragma unroll
   for (int t = 0; t < kMaxAS; ++t) {
@@ -308,15 +289,25 @@ __global__ __launch_bounds__(256) void step_expand_backup_stochastic_kernel(Step
       if (a < AD) x[t] = o.action_logits[(size_t)r * AD + a];
     }
   }
-  expand_prior_row(s, tree_view_global(s, rb), rb, newn, x, j);
-  const float* src = chance_child ? o.afterstate_embedding + (size_t)r * o.ea : o.state_embedding + (size_t)r * o.es;
-  const int w = chance_child ? o.ea : o.es;
-  for (int i = j; i < E; i += 16) s.embeddings[(rb + newn) * E + i] = i < w ? src[i] : 0.0f;
+  expand_prior_row(s, tree_view_global(s, rb), rb, n.newn, x, j);
+  expand_embedding(s, rb, r, j, n.newn,
+                   chance_child ? o.afterstate_embedding + (size_t)r * o.ea : o.state_embedding + (size_t)r * o.es,
+                   chance_child ? o.ea : o.es);
   if (j == 0) {
     const float v = chance_child ? o.afterstate_value[r] : o.value[r];
     const float rew = chance_child ? 0.0f : o.reward[r], dis = chance_child ? 1.0f : o.discount[r];
-    expand_edge_backward(s, rb, parent, action, depth, newn, v, rew, dis);
+    expand_edge_backward(s, rb, n.parent, n.action, n.depth, n.newn, v, rew, dis);
   }
+}
+
+// what every policy's finish returns beside the action weights, by the row's first lane: the action, the root's value
+// and the summed selection depths (both optional)
+MZ_DEV void finish_store(const StepArgs& s, int r, int j, int best, int32_t* action_out, float* search_value_out,
+                         int32_t* depth_sum_out) {
+  if (j != 0) return;
+  action_out[r] = best;
+  if (search_value_out) search_value_out[r] = s.node_values[(size_t)r * s.N];
+  if (depth_sum_out) depth_sum_out[r] = s.depth_sum[r];
 }
 
 // mctx Tree.summary + _apply_temperature + jax.random.categorical over the first A of the root's s.A slots (gumbel,
@@ -371,11 +362,7 @@ MZ_DEV void finish_row(const StepArgs& s, int r, int j, int A, float temperature
     if (take) { bscore = score; best = ok ? a : (1 << 20); }
   }
   row_argmax<4>(bscore, best, dummy);
-  if (j == 0) {
-    action_out[r] = best;
-    if (search_value_out) search_value_out[r] = s.node_values[rb];
-    if (depth_sum_out) depth_sum_out[r] = s.depth_sum[r];
-  }
+  finish_store(s, r, j, best, action_out, search_value_out, depth_sum_out);
 }
 __global__ __launch_bounds__(256) void step_finish_kernel(StepArgs s, float temperature, const float* gumbel,
                                                            uint32_t ks0, uint32_t ks1, int32_t* action_out,
@@ -418,11 +405,7 @@ __global__ __launch_bounds__(256) void step_finish_gumbel_kernel(StepArgs s, int
 #pragma unroll
   for (int t = 0; t < kMaxAS; ++t)
     if (j + 16 * t < A) action_weights_out[(size_t)r * A + j + 16 * t] = w[t];
-  if (j == 0) {
-    action_out[r] = best;
-    if (search_value_out) search_value_out[r] = s.node_values[rb];
-    if (depth_sum_out) depth_sum_out[r] = s.depth_sum[r];
-  }
+  finish_store(s, r, j, best, action_out, search_value_out, depth_sum_out);
 }
 
 // ---- wide embedding rows: one workgroup per (root, KiB of the row) ----

@@ -21,8 +21,8 @@ static void emb_xfer(const mz::StepArgs& sa, float* rows, int dir, hipStream_t s
   hipLaunchKernelGGL(mz::emb_xfer_kernel, dim3(sa.B, (sa.E + 1023) / 1024), dim3(256), 0, stream, sa, rows, dir);
 }
 
-// What roots a tree: the root inference's outputs and, by policy, the Dirichlet noise (MuZero) or the Gumbel noise -- null:
-// drawn from the key gk -- (Gumbel); the other policy's members are null / 0
+// What roots a tree: the root inference's outputs and, by policy, the Dirichlet noise (MuZero, stochastic) or the Gumbel
+// noise -- null: drawn from the key gk -- (Gumbel); the other policies' members are null / 0
 struct RootInputs {
   const float *prior_logits, *value, *embedding;
   const uint8_t* invalid_actions;
@@ -35,18 +35,26 @@ struct RootInputs {
 static void launch_root(mzs_handle* h, const mz::StepArgs& sa, const RootInputs& in, bool jump, hipStream_t stream) {
   const dim3 grid(step_grid(sa.B)), blk(step_block(sa.B));
   const int gumbel = h->cfg.policy == 1;
-  hipLaunchKernelGGL(mz::step_root_kernel, grid, blk, 0, stream, sa, in.prior_logits, in.value, in.embedding, in.invalid_actions,
-                     in.dirichlet_noise, in.dirichlet_fraction, gumbel, in.gumbel, in.gk[0], in.gk[1]);
+  if (h->cfg.policy == 2)
+    hipLaunchKernelGGL(mz::step_root_stochastic_kernel, grid, blk, 0, stream, sa, in.prior_logits, in.value, in.embedding,
+                       h->cfg.state_embed_dim, in.invalid_actions, in.dirichlet_noise, in.dirichlet_fraction);
+  else
+    hipLaunchKernelGGL(mz::step_root_kernel, grid, blk, 0, stream, sa, in.prior_logits, in.value, in.embedding, in.invalid_actions,
+                       in.dirichlet_noise, in.dirichlet_fraction, gumbel, in.gumbel, in.gk[0], in.gk[1]);
   if (jump && gumbel) hipLaunchKernelGGL(mz::jump_root_kernel<true>, grid, blk, 0, stream, sa, h->jump);
   else if (jump) hipLaunchKernelGGL(mz::jump_root_kernel<false>, grid, blk, 0, stream, sa, h->jump);
 }
-// the policy's action choice over sa's rows (gumbel: the MuZero policy's optional sampling noise; k_sample from the key walk)
+// the policy's action choice over sa's rows (gumbel: the MuZero and the stochastic policy's optional sampling noise;
+// k_sample from the key walk)
 static void launch_finish(mzs_handle* h, const mz::StepArgs& sa, float temperature, const float* gumbel, int32_t* action_out,
                           float* action_weights_out, float* search_value_out, int32_t* depth_sum_out, hipStream_t stream) {
   const dim3 grid(step_grid(sa.B)), blk(step_block(sa.B));
   if (h->cfg.policy == 1)
     hipLaunchKernelGGL(mz::step_finish_gumbel_kernel, grid, blk, 0, stream, sa, action_out, action_weights_out,
                        search_value_out, depth_sum_out);
+  else if (h->cfg.policy == 2)
+    hipLaunchKernelGGL(mz::step_finish_stochastic_kernel, grid, blk, 0, stream, sa, temperature, gumbel, h->k_sample[0],
+                       h->k_sample[1], action_out, action_weights_out, search_value_out, depth_sum_out);
   else
     hipLaunchKernelGGL(mz::step_finish_kernel, grid, blk, 0, stream, sa, temperature, gumbel, h->k_sample[0], h->k_sample[1],
                        action_out, action_weights_out, search_value_out, depth_sum_out);
@@ -57,8 +65,7 @@ static int ensure_step_state(mzs_handle* h) {
   if (h->step.allocated) return MZS_OK;
   const int rows = c.policy == 1 ? c.max_num_considered_actions + 1 : 0;
   const int table_words = rows * c.num_simulations;
-  const int slots = c.num_actions + (c.policy == 2 ? c.num_chance_outcomes : 0);  // stochastic: actions, then chance outcomes
-  hipError_t e = h->step.allocate(c.batch, c.num_simulations + 1, slots, c.embed_dim, table_words);
+  hipError_t e = h->step.allocate(c.batch, c.num_simulations + 1, mz::slots_per_node(c), c.embed_dim, table_words);
   if (e != hipSuccess) return fail(h, MZS_E_RUNTIME, "tree allocation: %s", hipGetErrorString(e));
   // cached-decision kernels (mz_step_jump.cuh): bounded tree, B N^2 path words within the slab budget (8 GiB of the
   // 288 GB: 4096 roots x 300 simulations are 1.5 GB; MZS_JUMP_BUDGET_MB overrides); MZS_STEP_WALK=1 keeps the
@@ -100,98 +107,139 @@ int mzh::step_view(mzs_handle* h, mz::StepArgs* sa, mz::JumpArgs* ja, int* polic
   return MZS_OK;
 }
 
-extern "C" {
-
-int mzs_root(mzs_handle* h, const float* prior_logits, const float* value, const float* embedding, const uint8_t* invalid_actions,
-             const float* dirichlet_noise, float dirichlet_fraction, const uint32_t key[2], void* stream_) {
+// What a step-wise entry works with once its call passed: the stream, the tree and the one-row-per-root geometry
+struct StepCall { hipStream_t stream; mz::StepArgs sa; dim3 grid, blk; };
+constexpr int kMuZero = 1, kGumbel = 2, kDeterministic = kMuZero | kGumbel, kStochastic = 4;  // policies an entry serves (bits)
+constexpr int32_t kNoSim = 0;  // (what an entry without a simulation index passes)
+// How every step-wise entry opens: the refusals in the order its family reports them -- the stochastic entries: policy,
+// root, sim, arguments; every other: root, sim, arguments, policy -- in the entry's own words (bad_args: null when the
+// arguments are in order), then the device, the tree (`rooted`: the entry needs one; a root entry allocates it) and the call.
+static int step_begin(mzs_handle* h, const char* who, int serves, const char* other_policy, bool rooted, int32_t sim,
+                      const char* bad_args, void* stream_, StepCall* call) {
   if (!h) return MZS_E_INVALID;
-  if (!prior_logits || !value || !embedding) return fail(h, MZS_E_INVALID, "mzs_root: null input");
-  if (!dirichlet_noise && dirichlet_fraction != 0.0f)
-    return fail(h, MZS_E_INVALID, "mzs_root: dirichlet_fraction != 0 needs dirichlet_noise");
   const mzs_config& c = h->cfg;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const bool stochastic = serves == kStochastic, served = (serves >> c.policy) & 1;
+  auto refuse = [&](const char* what) { return fail(h, MZS_E_INVALID, "%s", (std::string(who) + ": " + what).c_str()); };
+  if (stochastic && !served) return refuse(other_policy);
+  if (rooted && !h->step.rooted) return refuse(stochastic ? "call mzs_root_stochastic first" : "call mzs_root first");
+  if (sim < 0 || sim >= c.num_simulations) return refuse("sim out of range");
+  if (bad_args) return refuse(bad_args);
+  if (!served) return refuse(other_policy);
   MZS_HIP(h, hipSetDevice(c.device));
-  if (c.policy == 2) return fail(h, MZS_E_INVALID, "mzs_root: this handle runs the stochastic policy; use mzs_root_stochastic");
-  if (c.policy != 0) return fail(h, MZS_E_INVALID, "mzs_root: this handle runs the gumbel policy; use mzs_root_gumbel");
-  if (int rc = ensure_step_state(h)) return rc;
-  uint32_t zero[2] = {0, 0};
-  mzh::derive_keys(key ? key : zero, h->cfg.num_simulations, h->k_sample, h->sim_keys.data());
+  if (int rc = rooted ? MZS_OK : ensure_step_state(h)) return rc;
+  *call = {static_cast<hipStream_t>(stream_), h->step.args(c), dim3(step_grid(c.batch)), dim3(step_block(c.batch))};
+  return MZS_OK;
+}
+static int launched(mzs_handle* h) {
+  MZS_HIP(h, hipGetLastError());
+  return MZS_OK;
+}
+static const char* root_bad_args(const RootInputs& in) {
+  if (!in.prior_logits || !in.value || !in.embedding) return "null input";
+  if (!in.dirichlet_noise && in.dirichlet_fraction != 0.0f) return "dirichlet_fraction != 0 needs dirichlet_noise";
+  return nullptr;
+}
+
+// the keys of a MuZero or stochastic tree from the act's key (null: zero): k_sample, and with tie-break noise every
+// simulation's key on the device
+static int seed_tree_keys(mzs_handle* h, const uint32_t key[2], hipStream_t stream) {
+  const mzs_config& c = h->cfg;
+  const uint32_t zero[2] = {0, 0};
+  mzh::derive_keys(key ? key : zero, c.num_simulations, h->k_sample, h->sim_keys.data());
   if (c.tiebreak) {
     // pageable source: the runtime stages it before the call returns, so the next act() may rewrite sim_keys
     MZS_HIP(h, hipMemcpyAsync(h->step.sim_keys, h->sim_keys.data(), sizeof(uint32_t) * 2 * (size_t)c.num_simulations,
                               hipMemcpyHostToDevice, stream));
   }
-  mz::StepArgs sa = h->step.args(c);
-  if (sa.wide) MZS_HIP(h, hipMemsetAsync(sa.embeddings, 0, sizeof(float) * (size_t)sa.B * sa.N * sa.E, stream));
-  launch_root(h, sa, {prior_logits, value, embedding, invalid_actions, dirichlet_noise, dirichlet_fraction, nullptr, {0, 0}},
-              h->use_jump, stream);
-  if (sa.wide) emb_xfer(sa, const_cast<float*>(embedding), 1, stream);
-  MZS_HIP(h, hipGetLastError());
-  h->step.rooted = true;
   return MZS_OK;
+}
+// the whole batch rooted: the root launch and, for wide embeddings, the rows zeroed before and the root's row scattered after
+static int root_batch(mzs_handle* h, const StepCall& call, const RootInputs& in) {
+  const mz::StepArgs& sa = call.sa;
+  hipStream_t stream = call.stream;
+  if (sa.wide) MZS_HIP(h, hipMemsetAsync(sa.embeddings, 0, sizeof(float) * (size_t)sa.B * sa.N * sa.E, stream));
+  launch_root(h, sa, in, h->use_jump, stream);
+  if (sa.wide) emb_xfer(sa, const_cast<float*>(in.embedding), 1, stream);
+  h->step.rooted = true;
+  return launched(h);
+}
+// mzs_root and mzs_root_stochastic: the roots of the MuZero prelude (Dirichlet noise, the tree's keys)
+static int root_dirichlet(mzs_handle* h, const char* who, int serves, const char* other_policy, const RootInputs& in,
+                          const uint32_t key[2], void* stream_) {
+  StepCall c;
+  if (int rc = step_begin(h, who, serves, other_policy, false, kNoSim, root_bad_args(in), stream_, &c)) return rc;
+  if (int rc = seed_tree_keys(h, key, c.stream)) return rc;
+  return root_batch(h, c, in);
+}
+static int finish_impl(mzs_handle* h, const char* who, int serves, const char* other_policy, float temperature, const float* gumbel,
+                       int32_t* action_out, float* action_weights_out, float* search_value_out, int32_t* depth_sum_out,
+                       void* stream_) {
+  StepCall c;
+  if (int rc = step_begin(h, who, serves, other_policy, true, kNoSim, !action_out || !action_weights_out ? "null output" : nullptr,
+                          stream_, &c))
+    return rc;
+  launch_finish(h, c.sa, temperature, gumbel, action_out, action_weights_out, search_value_out, depth_sum_out, c.stream);
+  return launched(h);
+}
+
+extern "C" {
+
+int mzs_root(mzs_handle* h, const float* prior_logits, const float* value, const float* embedding, const uint8_t* invalid_actions,
+             const float* dirichlet_noise, float dirichlet_fraction, const uint32_t key[2], void* stream_) {
+  return root_dirichlet(h, "mzs_root", kMuZero,
+                        h && h->cfg.policy == 2 ? "this handle runs the stochastic policy; use mzs_root_stochastic"
+                                                : "this handle runs the gumbel policy; use mzs_root_gumbel",
+                        {prior_logits, value, embedding, invalid_actions, dirichlet_noise, dirichlet_fraction, nullptr, {0, 0}}, key,
+                        stream_);
 }
 
 int mzs_root_gumbel(mzs_handle* h, const float* prior_logits, const float* value, const float* embedding,
                     const uint8_t* invalid_actions, const float* gumbel, const uint32_t key[2], void* stream_) {
-  if (!h) return MZS_E_INVALID;
-  if (!prior_logits || !value || !embedding) return fail(h, MZS_E_INVALID, "mzs_root_gumbel: null input");
-  const mzs_config& c = h->cfg;
-  if (c.policy != 1) return fail(h, MZS_E_INVALID, "mzs_root_gumbel: this handle does not run the gumbel policy (policy 1)");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MZS_HIP(h, hipSetDevice(c.device));
-  if (int rc = ensure_step_state(h)) return rc;
+  RootInputs in = {prior_logits, value, embedding, invalid_actions, nullptr, 0.0f, gumbel, {0, 0}};
+  StepCall c;
+  if (int rc = step_begin(h, "mzs_root_gumbel", kGumbel, "this handle does not run the gumbel policy (policy 1)", false, kNoSim,
+                          root_bad_args(in), stream_, &c))
+    return rc;
   // mctx gumbel_muzero_policy: rng_key, gumbel_rng = jax.random.split(rng_key)
-  uint32_t zero[2] = {0, 0}, gk[2];
-  mzh::h_split(key ? key : zero, 2, 1, gk);
-  mz::StepArgs sa = h->step.args(c);
-  if (sa.wide) MZS_HIP(h, hipMemsetAsync(sa.embeddings, 0, sizeof(float) * (size_t)sa.B * sa.N * sa.E, stream));
-  launch_root(h, sa, {prior_logits, value, embedding, invalid_actions, nullptr, 0.0f, gumbel, {gk[0], gk[1]}}, h->use_jump,
-              stream);
-  if (sa.wide) emb_xfer(sa, const_cast<float*>(embedding), 1, stream);
-  MZS_HIP(h, hipGetLastError());
-  h->step.rooted = true;
-  return MZS_OK;
+  const uint32_t zero[2] = {0, 0};
+  mzh::h_split(key ? key : zero, 2, 1, in.gk);
+  return root_batch(h, c, in);
 }
 
 int mzs_select(mzs_handle* h, int32_t sim, int32_t* action_out, float* parent_embedding_out, void* stream_) {
-  if (!h) return MZS_E_INVALID;
-  if (!h->step.rooted) return fail(h, MZS_E_INVALID, "mzs_select: call mzs_root first");
-  if (sim < 0 || sim >= h->cfg.num_simulations) return fail(h, MZS_E_INVALID, "mzs_select: sim out of range");
-  if (!action_out || !parent_embedding_out) return fail(h, MZS_E_INVALID, "mzs_select: null output");
+  StepCall call;
+  if (int rc = step_begin(h, "mzs_select", kDeterministic, "this handle runs the stochastic policy; use mzs_select_stochastic", true,
+                          sim, !action_out || !parent_embedding_out ? "null output" : nullptr, stream_, &call))
+    return rc;
   const mzs_config& c = h->cfg;
-  if (c.policy == 2) return fail(h, MZS_E_INVALID, "mzs_select: this handle runs the stochastic policy; use mzs_select_stochastic");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MZS_HIP(h, hipSetDevice(c.device));
-  mz::StepArgs sa = h->step.args(c);
-  const dim3 grid(step_grid(c.batch)), blk(step_block(c.batch));
+  const mz::StepArgs& sa = call.sa;
+  hipStream_t stream = call.stream;
   const bool gathers = h->use_jump && sa.wide;  // one workgroup per root: selection + the gather of the wide embedding row
   if (gathers)
     hipLaunchKernelGGL(mz::jump_select_kernel<true>, dim3(c.batch), dim3(256), 0, stream, sa, h->jump, sim, action_out,
                        parent_embedding_out);
   else if (h->use_jump)
-    hipLaunchKernelGGL(mz::jump_select_kernel<false>, grid, blk, 0, stream, sa, h->jump, sim, action_out, parent_embedding_out);
+    hipLaunchKernelGGL(mz::jump_select_kernel<false>, call.grid, call.blk, 0, stream, sa, h->jump, sim, action_out,
+                       parent_embedding_out);
   else if (c.policy == 1)
-    hipLaunchKernelGGL(mz::step_select_gumbel_kernel, grid, blk, 0, stream, sa, sim, action_out, parent_embedding_out);
+    hipLaunchKernelGGL(mz::step_select_gumbel_kernel, call.grid, call.blk, 0, stream, sa, sim, action_out, parent_embedding_out);
   else
-    hipLaunchKernelGGL(mz::step_select_kernel, grid, blk, 0, stream, sa, sim, action_out, parent_embedding_out);
+    hipLaunchKernelGGL(mz::step_select_kernel, call.grid, call.blk, 0, stream, sa, sim, action_out, parent_embedding_out);
   if (sa.wide && !gathers) emb_xfer(sa, parent_embedding_out, 0, stream);
-  MZS_HIP(h, hipGetLastError());
-  return MZS_OK;
+  return launched(h);
 }
 
 static int expand_backup_impl(mzs_handle* h, int32_t sim, const float* reward, const float* discount, const float* prior_logits,
                               const float* value, const float* next_embedding, int32_t* next_action_out,
                               float* next_parent_embedding_out, void* stream_, const char* who) {
-  if (!h) return MZS_E_INVALID;
-  if (!h->step.rooted) return fail(h, MZS_E_INVALID, "%s: call mzs_root first", who);
-  if (sim < 0 || sim >= h->cfg.num_simulations) return fail(h, MZS_E_INVALID, "%s: sim out of range", who);
-  if (!reward || !discount || !prior_logits || !value || !next_embedding)
-    return fail(h, MZS_E_INVALID, "%s: null input", who);
+  StepCall call;
+  if (int rc = step_begin(h, who, kDeterministic, "this handle runs the stochastic policy; use mzs_expand_backup_stochastic", true,
+                          sim, !reward || !discount || !prior_logits || !value || !next_embedding ? "null input" : nullptr,
+                          stream_, &call))
+    return rc;
   const mzs_config& c = h->cfg;
-  if (c.policy == 2) return fail(h, MZS_E_INVALID, "%s: this handle runs the stochastic policy; use mzs_expand_backup_stochastic", who);
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MZS_HIP(h, hipSetDevice(c.device));
-  mz::StepArgs sa = h->step.args(c);
+  const mz::StepArgs& sa = call.sa;
+  hipStream_t stream = call.stream;
   const bool want_next = next_action_out != nullptr && sim + 1 < c.num_simulations;
   if (h->use_jump) {
     // small batches: 16 levels in flight per root; large ones: one wavefront per root keeps the launch small;
@@ -205,8 +253,8 @@ static int expand_backup_impl(mzs_handle* h, int32_t sim, const float* reward, c
       hipLaunchKernelGGL(mz::jump_expand_backup_kernel<false>, dim3(c.batch), blk, lds, stream, sa, h->jump, sim, reward,
                          discount, prior_logits, value, next_embedding, next_action_out, next_parent_embedding_out);
   } else
-    hipLaunchKernelGGL(mz::step_expand_backup_kernel, dim3(step_grid(c.batch)), dim3(step_block(c.batch)), 0, stream, sa, sim,
-                       reward, discount, prior_logits, value, next_embedding);
+    hipLaunchKernelGGL(mz::step_expand_backup_kernel, call.grid, call.blk, 0, stream, sa, sim, reward, discount, prior_logits,
+                       value, next_embedding);
   if (sa.wide && !h->use_jump) emb_xfer(sa, const_cast<float*>(next_embedding), 1, stream);
   MZS_HIP(h, hipGetLastError());
   // the walking kernels (trees beyond the cached-decision budget, MZS_STEP_WALK=1) select in a launch of their own
@@ -231,96 +279,48 @@ int mzs_expand_backup_select(mzs_handle* h, int32_t sim, const float* reward, co
 
 int mzs_finish(mzs_handle* h, float temperature, const float* gumbel, int32_t* action_out,
                float* action_weights_out, float* search_value_out, int32_t* depth_sum_out, void* stream_) {
-  if (!h) return MZS_E_INVALID;
-  if (!h->step.rooted) return fail(h, MZS_E_INVALID, "mzs_finish: call mzs_root first");
-  if (!action_out || !action_weights_out) return fail(h, MZS_E_INVALID, "mzs_finish: null output");
-  const mzs_config& c = h->cfg;
-  if (c.policy == 2) return fail(h, MZS_E_INVALID, "mzs_finish: this handle runs the stochastic policy; use mzs_finish_stochastic");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MZS_HIP(h, hipSetDevice(c.device));
-  launch_finish(h, h->step.args(c), temperature, gumbel, action_out, action_weights_out, search_value_out, depth_sum_out, stream);
-  MZS_HIP(h, hipGetLastError());
-  return MZS_OK;
+  return finish_impl(h, "mzs_finish", kDeterministic, "this handle runs the stochastic policy; use mzs_finish_stochastic",
+                     temperature, gumbel, action_out, action_weights_out, search_value_out, depth_sum_out, stream_);
 }
 
 // ---- stochastic policy (policy == 2): the walking kernels with chance nodes at odd depth ----
-static int stochastic_handle(mzs_handle* h, const char* who, bool rooted) {
-  if (!h) return MZS_E_INVALID;
-  if (h->cfg.policy != 2) return fail(h, MZS_E_INVALID, "%s: this handle does not run the stochastic policy (policy 2)", who);
-  if (rooted && !h->step.rooted) return fail(h, MZS_E_INVALID, "%s: call mzs_root_stochastic first", who);
-  return MZS_OK;
-}
+static const char* const kNotStochastic = "this handle does not run the stochastic policy (policy 2)";
 
 int mzs_root_stochastic(mzs_handle* h, const float* prior_logits, const float* value, const float* embedding,
                         const uint8_t* invalid_actions, const float* dirichlet_noise, float dirichlet_fraction,
                         const uint32_t key[2], void* stream_) {
-  if (int rc = stochastic_handle(h, "mzs_root_stochastic", false)) return rc;
-  if (!prior_logits || !value || !embedding) return fail(h, MZS_E_INVALID, "mzs_root_stochastic: null input");
-  if (!dirichlet_noise && dirichlet_fraction != 0.0f)
-    return fail(h, MZS_E_INVALID, "mzs_root_stochastic: dirichlet_fraction != 0 needs dirichlet_noise");
-  const mzs_config& c = h->cfg;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MZS_HIP(h, hipSetDevice(c.device));
-  if (int rc = ensure_step_state(h)) return rc;
-  uint32_t zero[2] = {0, 0};
-  mzh::derive_keys(key ? key : zero, c.num_simulations, h->k_sample, h->sim_keys.data());
-  if (c.tiebreak)
-    MZS_HIP(h, hipMemcpyAsync(h->step.sim_keys, h->sim_keys.data(), sizeof(uint32_t) * 2 * (size_t)c.num_simulations,
-                              hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(mz::step_root_stochastic_kernel, dim3(step_grid(c.batch)), dim3(step_block(c.batch)), 0, stream,
-                     h->step.args(c), prior_logits, value, embedding, c.state_embed_dim, invalid_actions, dirichlet_noise,
-                     dirichlet_fraction);
-  MZS_HIP(h, hipGetLastError());
-  h->step.rooted = true;
-  return MZS_OK;
+  return root_dirichlet(h, "mzs_root_stochastic", kStochastic, kNotStochastic,
+                        {prior_logits, value, embedding, invalid_actions, dirichlet_noise, dirichlet_fraction, nullptr, {0, 0}}, key,
+                        stream_);
 }
 
 int mzs_select_stochastic(mzs_handle* h, int32_t sim, int32_t* slot_out, int32_t* parent_is_decision_out,
                           float* parent_embedding_out, void* stream_) {
-  if (int rc = stochastic_handle(h, "mzs_select_stochastic", true)) return rc;
-  const mzs_config& c = h->cfg;
-  if (sim < 0 || sim >= c.num_simulations) return fail(h, MZS_E_INVALID, "mzs_select_stochastic: sim out of range");
-  if (!slot_out || !parent_is_decision_out || !parent_embedding_out)
-    return fail(h, MZS_E_INVALID, "mzs_select_stochastic: null output");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MZS_HIP(h, hipSetDevice(c.device));
-  hipLaunchKernelGGL(mz::step_select_stochastic_kernel, dim3(step_grid(c.batch)), dim3(step_block(c.batch)), 0, stream,
-                     h->step.args(c), sim, slot_out, parent_is_decision_out, parent_embedding_out);
-  MZS_HIP(h, hipGetLastError());
-  return MZS_OK;
+  StepCall c;
+  if (int rc = step_begin(h, "mzs_select_stochastic", kStochastic, kNotStochastic, true, sim,
+                          !slot_out || !parent_is_decision_out || !parent_embedding_out ? "null output" : nullptr, stream_, &c))
+    return rc;
+  hipLaunchKernelGGL(mz::step_select_stochastic_kernel, c.grid, c.blk, 0, c.stream, c.sa, sim, slot_out, parent_is_decision_out,
+                     parent_embedding_out);
+  return launched(h);
 }
 
 int mzs_expand_backup_stochastic(mzs_handle* h, int32_t sim, const mzs_stochastic_outputs* o, void* stream_) {
-  if (int rc = stochastic_handle(h, "mzs_expand_backup_stochastic", true)) return rc;
-  const mzs_config& c = h->cfg;
-  if (sim < 0 || sim >= c.num_simulations) return fail(h, MZS_E_INVALID, "mzs_expand_backup_stochastic: sim out of range");
-  if (!o || o->struct_size != (int32_t)sizeof(mzs_stochastic_outputs))
-    return fail(h, MZS_E_INVALID, "mzs_expand_backup_stochastic: null or size mismatch (ABI)");
-  if (!o->chance_logits || !o->afterstate_value || !o->afterstate_embedding || !o->action_logits || !o->value || !o->reward ||
-      !o->discount || !o->state_embedding)
-    return fail(h, MZS_E_INVALID, "mzs_expand_backup_stochastic: null input");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MZS_HIP(h, hipSetDevice(c.device));
+  const char* bad = !o || o->struct_size != (int32_t)sizeof(mzs_stochastic_outputs) ? "null or size mismatch (ABI)"
+                    : !o->chance_logits || !o->afterstate_value || !o->afterstate_embedding || !o->action_logits || !o->value ||
+                          !o->reward || !o->discount || !o->state_embedding ? "null input" : nullptr;
+  StepCall c;
+  if (int rc = step_begin(h, "mzs_expand_backup_stochastic", kStochastic, kNotStochastic, true, sim, bad, stream_, &c)) return rc;
   const mz::StochasticOutputs k = {o->chance_logits, o->afterstate_value, o->afterstate_embedding, o->action_logits, o->value,
-                                   o->reward, o->discount, o->state_embedding, c.afterstate_embed_dim, c.state_embed_dim};
-  hipLaunchKernelGGL(mz::step_expand_backup_stochastic_kernel, dim3(step_grid(c.batch)), dim3(step_block(c.batch)), 0, stream,
-                     h->step.args(c), sim, k);
-  MZS_HIP(h, hipGetLastError());
-  return MZS_OK;
+                                   o->reward, o->discount, o->state_embedding, h->cfg.afterstate_embed_dim, h->cfg.state_embed_dim};
+  hipLaunchKernelGGL(mz::step_expand_backup_stochastic_kernel, c.grid, c.blk, 0, c.stream, c.sa, sim, k);
+  return launched(h);
 }
 
 int mzs_finish_stochastic(mzs_handle* h, float temperature, const float* gumbel, int32_t* action_out, float* action_weights_out,
                           float* search_value_out, int32_t* depth_sum_out, void* stream_) {
-  if (int rc = stochastic_handle(h, "mzs_finish_stochastic", true)) return rc;
-  if (!action_out || !action_weights_out) return fail(h, MZS_E_INVALID, "mzs_finish_stochastic: null output");
-  const mzs_config& c = h->cfg;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MZS_HIP(h, hipSetDevice(c.device));
-  hipLaunchKernelGGL(mz::step_finish_stochastic_kernel, dim3(step_grid(c.batch)), dim3(step_block(c.batch)), 0, stream,
-                     h->step.args(c), temperature, gumbel, h->k_sample[0], h->k_sample[1], action_out, action_weights_out,
-                     search_value_out, depth_sum_out);
-  MZS_HIP(h, hipGetLastError());
-  return MZS_OK;
+  return finish_impl(h, "mzs_finish_stochastic", kStochastic, kNotStochastic, temperature, gumbel, action_out, action_weights_out,
+                     search_value_out, depth_sum_out, stream_);
 }
 
 int mzs_tree_export(mzs_handle* h, const mzs_tree_view* out, void* stream_) {
@@ -334,7 +334,7 @@ int mzs_tree_export(mzs_handle* h, const mzs_tree_view* out, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   MZS_HIP(h, hipSetDevice(c.device));
   const size_t BN = (size_t)c.batch * (c.num_simulations + 1);
-  const size_t A = (size_t)c.num_actions + (c.policy == 2 ? c.num_chance_outcomes : 0);  // stochastic: every slot of a node
+  const size_t A = (size_t)mz::slots_per_node(c);
   const mz::StepState& s = h->step;
 #define CP(dst, src, n) MZS_HIP(h, hipMemcpyAsync(dst, src, (n) * 4, hipMemcpyDeviceToDevice, stream))
   CP(out->node_visits, s.node_visits, BN); CP(out->raw_values, s.raw_values, BN);
@@ -402,10 +402,7 @@ static int act_mlp_generic_chunks(mzs_handle* h, const mzs_act_args* a, const mz
   if (c.policy == 1) {
     mzh::h_split(a->key, 2, 1, gk);  // mctx gumbel_muzero_policy: rng_key, gumbel_rng = split(rng_key)
   } else {
-    mzh::derive_keys(a->key, h->cfg.num_simulations, h->k_sample, h->sim_keys.data());
-    if (c.tiebreak)
-      MZS_HIP(h, hipMemcpyAsync(h->step.sim_keys, h->sim_keys.data(), sizeof(uint32_t) * 2 * (size_t)c.num_simulations,
-                                hipMemcpyHostToDevice, stream));
+    if (int rc = seed_tree_keys(h, a->key, stream)) return rc;
   }
   const mz::StepArgs whole = h->step.args(c);
   const bool gum = c.policy == 1;

@@ -7,8 +7,37 @@ from abc import ABC, abstractmethod
 from .search import MuZeroSearch, PolicyOutput, SearchConfig, fn_identity
 
 
+def _search_config(kwargs, num_actions, embed_dim, puct=True, **fields):
+    """The keyword arguments every policy takes (and, `puct`, those of the pUCT rule) with the reference's defaults, plus the
+    policy's own SearchConfig `fields` -> (cache key, SearchConfig)."""
+    get = kwargs.get
+    common = dict(max_depth=get("max_depth"), global_batch=get("global_batch"), root_offset=get("root_offset", 0))
+    if puct:
+        common.update(tiebreak=get("tiebreak", True), pb_c_init=get("pb_c_init", 1.25),
+                      pb_c_base=float(get("pb_c_base", 19652)))
+    cfg = SearchConfig(num_actions, get("num_simulations", 5), embed_dim, **common, **fields)
+    return (num_actions, cfg.num_simulations, embed_dim) + tuple(common.values()) + tuple(fields.values()), cfg
+
+
+def _flat_recurrent(recurrent_fn, params, batch, shape):
+    """recurrent_fn in the search's calling convention: flat embedding rows in and out."""
+    def rec(action, flat_emb):
+        (reward, discount, logits, v), nxt = recurrent_fn(params, None, action, flat_emb.reshape((batch,) + shape))
+        return reward, discount, logits, v, nxt.reshape(batch, -1)
+    return rec
+
+
 class Policy(ABC):
-    """muax/policy.py:7-10."""
+    """muax/policy.py:7-10.  One search handle per (batch, device, configuration), kept for the policy's lifetime."""
+
+    def __init__(self):
+        self._handles = {}
+
+    def _handle(self, batch, device, cfg_key, cfg):
+        key = (batch, cfg_key, str(device))
+        if key not in self._handles:
+            self._handles[key] = MuZeroSearch(batch, cfg, device)
+        return self._handles[key]
 
     @abstractmethod
     def __call__(self, params, rng_key, root, recurrent_fn=None, decision_recurrent_fn=None,
@@ -23,37 +52,15 @@ class MuZeroPolicy(Policy):
     `recurrent_fn(params, rng_key, action, embedding)` returns ((reward, discount, prior_logits, value),
     next_embedding) as in muax/model.py:265-282.  Runs the step-wise HIP search (any plugin nets)."""
 
-    def __init__(self):
-        self._handles = {}
-
-    def _handle(self, batch, cfg_key, cfg, device):
-        key = (batch, cfg_key, str(device))
-        if key not in self._handles:
-            self._handles[key] = MuZeroSearch(batch, cfg, device)
-        return self._handles[key]
-
     def __call__(self, params, rng_key, root, recurrent_fn, **kwargs) -> PolicyOutput:
         prior_logits, value, embedding = root
         if kwargs.get("qtransform") not in (None, "qtransform_by_parent_and_siblings"):
             raise ValueError("only qtransform_by_parent_and_siblings is implemented")
         B, A = prior_logits.shape
         emb = embedding.reshape(B, -1)
-        S = kwargs.get("num_simulations", 5)
-        cfg_key = (A, S, emb.shape[1], kwargs.get("max_depth"), kwargs.get("tiebreak", True),
-                   kwargs.get("pb_c_init", 1.25), kwargs.get("pb_c_base", 19652), kwargs.get("global_batch"),
-                   kwargs.get("root_offset", 0))
-        cfg = SearchConfig(A, S, emb.shape[1], max_depth=kwargs.get("max_depth"),
-                           tiebreak=kwargs.get("tiebreak", True), pb_c_init=kwargs.get("pb_c_init", 1.25),
-                           pb_c_base=float(kwargs.get("pb_c_base", 19652)), global_batch=kwargs.get("global_batch"),
-                           root_offset=kwargs.get("root_offset", 0))
-        h = self._handle(B, cfg_key, cfg, prior_logits.device)
+        h = self._handle(B, prior_logits.device, *_search_config(kwargs, A, emb.shape[1]))
         shape = tuple(embedding.shape[1:])
-
-        def rec(action, flat_emb):
-            (reward, discount, logits, v), nxt = recurrent_fn(params, None, action, flat_emb.reshape((B,) + shape))
-            return reward, discount, logits, v, nxt.reshape(B, -1)
-
-        return h.search((prior_logits, value, emb), rec, key=rng_key,
+        return h.search((prior_logits, value, emb), _flat_recurrent(recurrent_fn, params, B, shape), key=rng_key,
                         invalid_actions=kwargs.get("invalid_actions"),
                         dirichlet_noise=kwargs.get("dirichlet_noise"),
                         dirichlet_fraction=kwargs.get("dirichlet_fraction", 0.25),
@@ -73,35 +80,18 @@ class GumbelMuZeroPolicy(Policy):
     through MuZero.act the Gumbel search runs with THAT transform unless one is passed explicitly --
     muax_amd.MuZero reproduces this."""
 
-    def __init__(self):
-        self._handles = {}
-
     def __call__(self, params, rng_key, root, recurrent_fn=None, decision_recurrent_fn=None,
                  chance_recurrent_fn=None, **kwargs) -> PolicyOutput:
         prior_logits, value, embedding = root
         B, A = prior_logits.shape
         emb = embedding.reshape(B, -1)
-        S = kwargs.get("num_simulations", 5)
         qt = kwargs.get("qtransform") or "qtransform_completed_by_mix_value"
-        qt = getattr(qt, "__name__", qt)
-        key = (B, A, S, emb.shape[1], kwargs.get("max_depth"), qt, kwargs.get("max_num_considered_actions", 16),
-               kwargs.get("gumbel_scale", 1), str(prior_logits.device), kwargs.get("global_batch"),
-               kwargs.get("root_offset", 0))
-        if key not in self._handles:
-            cfg = SearchConfig(A, S, emb.shape[1], max_depth=kwargs.get("max_depth"), tiebreak=False,
-                               policy="gumbel", qtransform=qt,
-                               max_num_considered_actions=kwargs.get("max_num_considered_actions", 16),
-                               gumbel_scale=float(kwargs.get("gumbel_scale", 1)), global_batch=kwargs.get("global_batch"),
-                               root_offset=kwargs.get("root_offset", 0))
-            self._handles[key] = MuZeroSearch(B, cfg, prior_logits.device)
-        h = self._handles[key]
+        h = self._handle(B, prior_logits.device, *_search_config(
+            kwargs, A, emb.shape[1], puct=False, tiebreak=False, policy="gumbel", qtransform=getattr(qt, "__name__", qt),
+            max_num_considered_actions=kwargs.get("max_num_considered_actions", 16),
+            gumbel_scale=float(kwargs.get("gumbel_scale", 1))))
         shape = tuple(embedding.shape[1:])
-
-        def rec(action, flat_emb):
-            (reward, discount, logits, v), nxt = recurrent_fn(params, None, action, flat_emb.reshape((B,) + shape))
-            return reward, discount, logits, v, nxt.reshape(B, -1)
-
-        return h.search((prior_logits, value, emb), rec, key=rng_key,
+        return h.search((prior_logits, value, emb), _flat_recurrent(recurrent_fn, params, B, shape), key=rng_key,
                         invalid_actions=kwargs.get("invalid_actions"), gumbel=kwargs.get("gumbel"),
                         with_tree=kwargs.get("with_tree", False), graph=kwargs.get("graph", False),
                         graph_key=(fn_identity(recurrent_fn), id(params), shape),
@@ -122,7 +112,7 @@ class StochasticMuZeroPolicy(Policy):
     The returned search_tree is the decision slice [..., :A] of the children arrays (mctx's masked tree)."""
 
     def __init__(self):
-        self._handles = {}
+        super().__init__()
         self._shapes = {}
 
     def __call__(self, params, rng_key, root, recurrent_fn=None, decision_recurrent_fn=None,
@@ -150,17 +140,8 @@ class StochasticMuZeroPolicy(Policy):
         Es, Ea = emb.shape[1], 1
         for n in after_shape:
             Ea *= int(n)
-        S = kwargs.get("num_simulations", 5)
-        key = (B, A, int(C), S, Es, Ea, kwargs.get("max_depth"), kwargs.get("tiebreak", True), kwargs.get("pb_c_init", 1.25),
-               kwargs.get("pb_c_base", 19652), str(prior_logits.device), kwargs.get("global_batch"),
-               kwargs.get("root_offset", 0))
-        if key not in self._handles:
-            cfg = SearchConfig(A, S, max(Es, Ea), max_depth=kwargs.get("max_depth"), tiebreak=kwargs.get("tiebreak", True),
-                               pb_c_init=kwargs.get("pb_c_init", 1.25), pb_c_base=float(kwargs.get("pb_c_base", 19652)),
-                               global_batch=kwargs.get("global_batch"), root_offset=kwargs.get("root_offset", 0),
-                               policy="stochastic", num_chance_outcomes=int(C), state_embed_dim=Es, afterstate_embed_dim=Ea)
-            self._handles[key] = MuZeroSearch(B, cfg, prior_logits.device)
-        h = self._handles[key]
+        h = self._handle(B, prior_logits.device, *_search_config(
+            kwargs, A, max(Es, Ea), policy="stochastic", num_chance_outcomes=int(C), state_embed_dim=Es, afterstate_embed_dim=Ea))
 
         def decision(action, flat_state):
             out, after = decision_recurrent_fn(params, None, action, flat_state.reshape((B,) + shape))

@@ -405,39 +405,38 @@ class MuZeroSearch:
         return action, weights, value
 
     # ------------------------------------------------------------------ step-wise path
+    def _parent_embedding(self):
+        """The persistent [B, embed_dim] buffer the selections hand out, allocated on first use."""
+        if self._parent_emb is None:
+            self._parent_emb = torch.empty(self.batch, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
+        return self._parent_emb
+
+    def _root(self, entry, prior_logits, value, embedding, width, key, invalid_actions, noise, noise_name, fraction=None):
+        """RootFnOutput (embedding: [B, width]) + the policy's [B, A] noise -> `entry`; fraction: the Dirichlet roots'."""
+        B, A = self.batch, self.cfg.num_actions
+        pl = self._f32(prior_logits, (B, A), "prior_logits")
+        v = self._f32(value, (B,), "value")
+        emb = self._f32(torch.as_tensor(embedding, device=self.device).reshape(B, -1), (B, width), "embedding")
+        inv = self._u8(invalid_actions, (B, A), "invalid_actions")
+        nz = self._f32(noise, (B, A), noise_name)
+        tail = () if fraction is None else (C.c_float(fraction if nz is not None else 0.0),)
+        kw = (C.c_uint32 * 2)(*key_words(key))
+        _lib.check(entry(self._h, _ptr(pl), _ptr(v), _ptr(emb), _ptr(inv), _ptr(nz), *tail, C.byref(kw), self._stream()),
+                   self._h)
+        self._keep = (pl, v, emb, inv, nz)
+        self._parent_embedding()
+
     def root(self, prior_logits, value, embedding, key=0, invalid_actions=None,
              dirichlet_noise=None, dirichlet_fraction: float = 0.25):
         """RootFnOutput -> tree (mctx muzero_policy prelude + instantiate_tree_from_root)."""
-        B, A, E = self.batch, self.cfg.num_actions, self.cfg.embed_dim
-        pl = self._f32(prior_logits, (B, A), "prior_logits")
-        v = self._f32(value, (B,), "value")
-        emb = self._f32(torch.as_tensor(embedding, device=self.device).reshape(B, -1), (B, E),
-                        "embedding")
-        inv = self._u8(invalid_actions, (B, A), "invalid_actions")
-        noise = self._f32(dirichlet_noise, (B, A), "dirichlet_noise")
-        kw = (C.c_uint32 * 2)(*key_words(key))
-        _lib.check(self._L.mzs_root(self._h, _ptr(pl), _ptr(v), _ptr(emb), _ptr(inv), _ptr(noise),
-                                    C.c_float(dirichlet_fraction if noise is not None else 0.0),
-                                    C.byref(kw), self._stream()), self._h)
-        self._keep = (pl, v, emb, inv, noise)
-        if self._parent_emb is None:
-            self._parent_emb = torch.empty(B, E, dtype=torch.float32, device=self.device)
+        self._root(self._L.mzs_root, prior_logits, value, embedding, self.cfg.embed_dim, key, invalid_actions,
+                   dirichlet_noise, "dirichlet_noise", dirichlet_fraction)
 
     def root_gumbel(self, prior_logits, value, embedding, key=0, invalid_actions=None, gumbel=None):
         """Gumbel MuZero root (mctx gumbel_muzero_policy prelude): invalid-action mask only, root Gumbel
         noise drawn from the key (or injected)."""
-        B, A, E = self.batch, self.cfg.num_actions, self.cfg.embed_dim
-        pl = self._f32(prior_logits, (B, A), "prior_logits")
-        v = self._f32(value, (B,), "value")
-        emb = self._f32(torch.as_tensor(embedding, device=self.device).reshape(B, -1), (B, E), "embedding")
-        inv = self._u8(invalid_actions, (B, A), "invalid_actions")
-        g = self._f32(gumbel, (B, A), "gumbel")
-        kw = (C.c_uint32 * 2)(*key_words(key))
-        _lib.check(self._L.mzs_root_gumbel(self._h, _ptr(pl), _ptr(v), _ptr(emb), _ptr(inv), _ptr(g),
-                                           C.byref(kw), self._stream()), self._h)
-        self._keep = (pl, v, emb, inv, g)
-        if self._parent_emb is None:
-            self._parent_emb = torch.empty(B, E, dtype=torch.float32, device=self.device)
+        self._root(self._L.mzs_root_gumbel, prior_logits, value, embedding, self.cfg.embed_dim, key, invalid_actions,
+                   gumbel, "gumbel")
 
     def select(self, sim: int):
         """One mctx simulate(): returns (action [B] int32, parent embedding [B,E])."""
@@ -447,18 +446,18 @@ class MuZeroSearch:
                                       self._stream()), self._h)
         return self.action, self._parent_emb
 
+    def _recurrent_outputs(self, reward, discount, prior_logits, value, next_embedding):
+        """RecurrentFnOutput + next embedding as the checked float32 tensors the expansion entries read."""
+        B, A, E = self.batch, self.cfg.num_actions, self.cfg.embed_dim
+        return (self._f32(reward, (B,), "reward"), self._f32(discount, (B,), "discount"),
+                self._f32(prior_logits, (B, A), "prior_logits"), self._f32(value, (B,), "value"),
+                self._f32(torch.as_tensor(next_embedding, device=self.device).reshape(B, -1), (B, E), "next_embedding"))
+
     def expand_backup(self, sim: int, reward, discount, prior_logits, value, next_embedding):
         """RecurrentFnOutput + next embedding -> expand + backward."""
-        B, A, E = self.batch, self.cfg.num_actions, self.cfg.embed_dim
-        r = self._f32(reward, (B,), "reward")
-        d = self._f32(discount, (B,), "discount")
-        pl = self._f32(prior_logits, (B, A), "prior_logits")
-        v = self._f32(value, (B,), "value")
-        ne = self._f32(torch.as_tensor(next_embedding, device=self.device).reshape(B, -1), (B, E),
-                       "next_embedding")
-        _lib.check(self._L.mzs_expand_backup(self._h, sim, _ptr(r), _ptr(d), _ptr(pl), _ptr(v),
-                                             _ptr(ne), self._stream()), self._h)
-        self._keep = (r, d, pl, v, ne)
+        keep = self._recurrent_outputs(reward, discount, prior_logits, value, next_embedding)
+        _lib.check(self._L.mzs_expand_backup(self._h, sim, *map(_ptr, keep), self._stream()), self._h)
+        self._keep = keep
 
     def expand_backup_select(self, sim: int, reward, discount, prior_logits, value, next_embedding):
         """expand_backup(sim) and select(sim + 1) in ONE launch (mzs_expand_backup_select): returns the next
@@ -466,13 +465,7 @@ class MuZeroSearch:
         the last simulation."""
         if self._parent_emb is None:
             raise ValueError("root() first")
-        B, A, E = self.batch, self.cfg.num_actions, self.cfg.embed_dim
-        r = self._f32(reward, (B,), "reward")
-        d = self._f32(discount, (B,), "discount")
-        pl = self._f32(prior_logits, (B, A), "prior_logits")
-        v = self._f32(value, (B,), "value")
-        ne = self._f32(torch.as_tensor(next_embedding, device=self.device).reshape(B, -1), (B, E),
-                       "next_embedding")
+        r, d, pl, v, ne = self._recurrent_outputs(reward, discount, prior_logits, value, next_embedding)
         pe = self._parent_emb
         if ne.untyped_storage().data_ptr() == pe.untyped_storage().data_ptr():
             # an identity (or slicing / offset-view) recurrent_fn: the launch's tail overwrites the buffer select()
@@ -484,12 +477,11 @@ class MuZeroSearch:
         self._keep = (r, d, pl, v, ne)
         return (self.action, self._parent_emb) if sim + 1 < self.cfg.num_simulations else None
 
-    def finish(self, temperature: float = 1.0, gumbel=None, with_tree: bool = False) -> PolicyOutput:
+    def _finish(self, entry, temperature, gumbel, with_tree) -> PolicyOutput:
         B, A = self.batch, self.cfg.num_actions
         gum = self._f32(gumbel, (B, A), "gumbel")
-        _lib.check(self._L.mzs_finish(self._h, C.c_float(temperature), _ptr(gum), _ptr(self.action),
-                                      _ptr(self.action_weights), _ptr(self.search_value),
-                                      _ptr(self.depth_sum), self._stream()), self._h)
+        _lib.check(entry(self._h, C.c_float(temperature), _ptr(gum), _ptr(self.action), _ptr(self.action_weights),
+                         _ptr(self.search_value), _ptr(self.depth_sum), self._stream()), self._h)
         self._keep = (gum,)
         tree = None
         if with_tree:
@@ -497,6 +489,33 @@ class MuZeroSearch:
             view = self._tree_view(tree)
             _lib.check(self._L.mzs_tree_export(self._h, C.byref(view), self._stream()), self._h)
         return PolicyOutput(self.action, self.action_weights, tree)
+
+    def finish(self, temperature: float = 1.0, gumbel=None, with_tree: bool = False) -> PolicyOutput:
+        return self._finish(self._L.mzs_finish, temperature, gumbel, with_tree)
+
+    def _run_loop(self, do_root, loop, graph, gkey, fns, graph_version):
+        """The simulation loop of a rooted tree: eager, or (graph) captured once per (gkey, graph_version) and replayed;
+        `fns`: the callables the capture froze, kept alive with it."""
+        if not graph:
+            return loop()
+        entry = self._graphs.get(gkey)
+        if entry is not None and entry[3] != graph_version:
+            entry = None
+        if entry is None:
+            # warm-up run (lazy library initialisation must not happen under capture), then the tree
+            # is rebuilt from the same root and the loop is captured (capture records, it does not run)
+            with torch.no_grad():
+                side = torch.cuda.Stream(device=self.device)
+                side.wait_stream(torch.cuda.current_stream(self.device))
+                with torch.cuda.stream(side):
+                    loop()
+                torch.cuda.current_stream(self.device).wait_stream(side)
+                do_root()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    loop()
+            entry = self._graphs[gkey] = (g, fns, self._keep, graph_version)
+        entry[0].replay()
 
     def search(self, root_fn_output, recurrent_fn, key=0, invalid_actions=None,
                dirichlet_noise=None, dirichlet_fraction=0.25, temperature=1.0, gumbel=None,
@@ -553,30 +572,9 @@ class MuZeroSearch:
                 native_loop = None  # (trees beyond the cached-decision budget keep the per-simulation launches)
                 self._native_loop_unusable = True
                 do_root()  # select(0) above has already counted simulation 0's depth; the fall-back loop starts from the root again
-        if native_loop is not None:
-            pass
-        elif not graph:
-            loop()
-        else:
+        if native_loop is None:
             gkey = graph_key if graph_key is not None else fn_identity(recurrent_fn)
-            entry = self._graphs.get(gkey)
-            if entry is not None and entry[3] != graph_version:
-                entry = None
-            if entry is None:
-                # warm-up run (lazy library initialisation must not happen under capture), then the tree
-                # is rebuilt from the same root and the loop is captured (capture records, it does not run)
-                with torch.no_grad():
-                    side = torch.cuda.Stream(device=self.device)
-                    side.wait_stream(torch.cuda.current_stream(self.device))
-                    with torch.cuda.stream(side):
-                        loop()
-                    torch.cuda.current_stream(self.device).wait_stream(side)
-                    do_root()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        loop()
-                entry = self._graphs[gkey] = (g, recurrent_fn, self._keep, graph_version)
-            entry[0].replay()
+            self._run_loop(do_root, loop, graph, gkey, recurrent_fn, graph_version)
         return self.finish(temperature, None if self.cfg.policy == "gumbel" else gumbel, with_tree)
 
     # ------------------------------------------------------------------ step-wise path, stochastic policy
@@ -584,28 +582,16 @@ class MuZeroSearch:
                         dirichlet_fraction: float = 0.25):
         """RootFnOutput -> tree (mctx stochastic_muzero_policy prelude): the MuZero root over the A actions, the chance
         slots padded with -inf / invalid.  embedding: the root's STATE embedding [B, state_embed_dim]."""
-        B, A, E = self.batch, self.cfg.num_actions, self.cfg.embed_dim
-        pl = self._f32(prior_logits, (B, A), "prior_logits")
-        v = self._f32(value, (B,), "value")
-        emb = self._f32(torch.as_tensor(embedding, device=self.device).reshape(B, -1), (B, self._es), "embedding")
-        inv = self._u8(invalid_actions, (B, A), "invalid_actions")
-        noise = self._f32(dirichlet_noise, (B, A), "dirichlet_noise")
-        kw = (C.c_uint32 * 2)(*key_words(key))
-        _lib.check(self._L.mzs_root_stochastic(self._h, _ptr(pl), _ptr(v), _ptr(emb), _ptr(inv), _ptr(noise),
-                                               C.c_float(dirichlet_fraction if noise is not None else 0.0),
-                                               C.byref(kw), self._stream()), self._h)
-        self._keep = (pl, v, emb, inv, noise)
-        if self._parent_emb is None:
-            self._parent_emb = torch.empty(B, E, dtype=torch.float32, device=self.device)
+        self._root(self._L.mzs_root_stochastic, prior_logits, value, embedding, self._es, key, invalid_actions,
+                   dirichlet_noise, "dirichlet_noise", dirichlet_fraction)
 
     def select_stochastic(self, sim: int):
         """One simulate() over decision and chance nodes: (slot [B] int32 in [0, A + C), parent_is_decision [B] int32,
         parent embedding [B, embed_dim] -- the parent's own kind of embedding, zero-padded)."""
-        if self._parent_emb is None:
-            self._parent_emb = torch.empty(self.batch, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
-        _lib.check(self._L.mzs_select_stochastic(self._h, sim, _ptr(self.action), _ptr(self.parent_is_decision),
-                                                 _ptr(self._parent_emb), self._stream()), self._h)
-        return self.action, self.parent_is_decision, self._parent_emb
+        pe = self._parent_embedding()
+        _lib.check(self._L.mzs_select_stochastic(self._h, sim, _ptr(self.action), _ptr(self.parent_is_decision), _ptr(pe),
+                                                 self._stream()), self._h)
+        return self.action, self.parent_is_decision, pe
 
     def expand_backup_stochastic(self, sim: int, decision_out, afterstate_embedding, chance_out, state_embedding):
         """Both functions' outputs for every root (DecisionRecurrentFnOutput + afterstate embedding,
@@ -626,18 +612,7 @@ class MuZeroSearch:
 
     def finish_stochastic(self, temperature: float = 1.0, gumbel=None, with_tree: bool = False) -> PolicyOutput:
         """Summary and sample over the A actions; with_tree: the full tree, children arrays [B, N, A + C]."""
-        B, A = self.batch, self.cfg.num_actions
-        gum = self._f32(gumbel, (B, A), "gumbel")
-        _lib.check(self._L.mzs_finish_stochastic(self._h, C.c_float(temperature), _ptr(gum), _ptr(self.action),
-                                                 _ptr(self.action_weights), _ptr(self.search_value),
-                                                 _ptr(self.depth_sum), self._stream()), self._h)
-        self._keep = (gum,)
-        tree = None
-        if with_tree:
-            tree = self._alloc_tree()
-            view = self._tree_view(tree)
-            _lib.check(self._L.mzs_tree_export(self._h, C.byref(view), self._stream()), self._h)
-        return PolicyOutput(self.action, self.action_weights, tree)
+        return self._finish(self._L.mzs_finish_stochastic, temperature, gumbel, with_tree)
 
     def search_stochastic(self, root_fn_output, decision_fn, chance_fn, key=0, invalid_actions=None, dirichlet_noise=None,
                           dirichlet_fraction=0.25, temperature=1.0, gumbel=None, with_tree=False, graph=False,
@@ -664,25 +639,6 @@ class MuZeroSearch:
                 self.expand_backup_stochastic(sim, d_out, after, c_out, state)
 
         do_root()
-        if not graph:
-            loop()
-        else:
-            gkey = graph_key if graph_key is not None else (fn_identity(decision_fn), fn_identity(chance_fn))
-            entry = self._graphs.get(gkey)
-            if entry is not None and entry[3] != graph_version:
-                entry = None
-            if entry is None:
-                # warm-up run, then the tree is rebuilt from the same root and the loop is captured (as in search())
-                with torch.no_grad():
-                    side = torch.cuda.Stream(device=self.device)
-                    side.wait_stream(torch.cuda.current_stream(self.device))
-                    with torch.cuda.stream(side):
-                        loop()
-                    torch.cuda.current_stream(self.device).wait_stream(side)
-                    do_root()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        loop()
-                entry = self._graphs[gkey] = (g, (decision_fn, chance_fn), self._keep, graph_version)
-            entry[0].replay()
+        gkey = graph_key if graph_key is not None else (fn_identity(decision_fn), fn_identity(chance_fn))
+        self._run_loop(do_root, loop, graph, gkey, (decision_fn, chance_fn), graph_version)
         return self.finish_stochastic(temperature, gumbel, with_tree)
