@@ -231,6 +231,39 @@ int mzs_expand_backup_stochastic(mzs_handle *h, int32_t sim, const mzs_stochasti
 int mzs_finish_stochastic(mzs_handle *h, float temperature, const float *gumbel, int32_t *action_out,
                           float *action_weights_out, float *search_value_out, int32_t *depth_sum_out, void *stream);
 
+/* ---- the default stochastic MLP family evaluated by the library: the decision and the chance function between
+ * mzs_select_stochastic and mzs_expand_backup_stochastic in ONE launch (muax_amd/csrc/mz_stoch_mlp.cuh) ----
+ * Every head is Linear(16)-elu-Linear, haiku layout w[in][out], float32 device pointers; E = embed_dim =
+ * state_embed_dim = afterstate_embed_dim, A = num_actions, C = num_chance_outcomes, F = 2 * support_size + 1.
+ *   decision function  as = min_max_normalize(ad([s, onehot(a, A)])); afterstate value = decode(av(as)); chance logits = ac(as)
+ *   chance function    reward = decode(cr([as, onehot(c, C)])); s' = min_max_normalize(cn([as, onehot(c, C)]));
+ *                      value = decode(pv(s')); action logits = pp(s'); discount = the constant below
+ * decode = support_to_scalar(softmax(.)); the arithmetic is the "MZ-F32" spec of the default trio. */
+typedef struct mzs_stochastic_mlp_weights {
+  int32_t struct_size;        /* = sizeof(mzs_stochastic_mlp_weights) */
+  int32_t support_size;       /* 8 .. 31 */
+  float discount;
+  float reserved0;
+  const float *ad_w1, *ad_b1, *ad_w2, *ad_b2; /* afterstate dynamics [E+A,16] [16] [16,E] [E] */
+  const float *av_w1, *av_b1, *av_w2, *av_b2; /* afterstate value    [E,16]   [16] [16,F] [F] */
+  const float *ac_w1, *ac_b1, *ac_w2, *ac_b2; /* chance logits       [E,16]   [16] [16,C] [C] */
+  const float *cr_w1, *cr_b1, *cr_w2, *cr_b2; /* chance reward       [E+C,16] [16] [16,F] [F] */
+  const float *cn_w1, *cn_b1, *cn_w2, *cn_b2; /* chance next state   [E+C,16] [16] [16,E] [E] */
+  const float *pv_w1, *pv_b1, *pv_w2, *pv_b2; /* prediction value    [E,16]   [16] [16,F] [F] */
+  const float *pp_w1, *pp_b1, *pp_w2, *pp_b2; /* prediction policy   [E,16]   [16] [16,A] [A] */
+} mzs_stochastic_mlp_weights;
+/* Binds the weights to a stochastic handle (policy 2) whose two embeddings are both embed_dim wide.  Refused, with the
+ * limit named: any other handle, num_actions + num_chance_outcomes > 64, support_size outside 8 .. 31, an LDS need
+ * beyond a workgroup's.  The arrays stay the caller's and are read at every mzs_mlp_stochastic_recurrent. */
+int mzs_mlp_set_stochastic_weights(mzs_handle *h, const mzs_stochastic_mlp_weights *w);
+/* slot, parent_is_decision [B], parent_embedding [B, embed_dim]: what mzs_select_stochastic wrote.  Per root ONLY the
+ * function of the parent's kind is evaluated -- decision parent: at action clamp(slot, 0, A - 1), chance parent: at
+ * outcome clamp(slot - A, 0, C - 1) -- and only that function's rows of `outputs` (the arrays of mzs_stochastic_outputs,
+ * WRITTEN here) are stored; the rows of the other kind are left untouched, mzs_expand_backup_stochastic does not read
+ * them.  One launch on `stream`, nothing else: the loop stays capturable.  Needs no rooted tree. */
+int mzs_mlp_stochastic_recurrent(mzs_handle *h, const int32_t *slot, const int32_t *parent_is_decision,
+                                 const float *parent_embedding, const mzs_stochastic_outputs *outputs, void *stream);
+
 /* ---- recurrent_fn of the EfficientZero-style nets ----
  * mzs_ez_recurrent evaluates, for a batch of 6x6xC hidden states (NHWC, C = 32 or 64) and actions, the whole
  * MuZero._recurrent_inference (muax/model.py:265-282) of EZDynamic + EZPrediction with use_v2 = True

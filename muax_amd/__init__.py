@@ -11,9 +11,10 @@ from .replay_buffer import Trajectory, TrajectoryReplayBuffer  # noqa: F401
 from .replay_device import DeviceReplayBuffer  # noqa: F401
 from . import envs  # noqa: F401
 from .envs import Device2048, DeviceAcrobot, DeviceCartPole, DeviceMountainCar  # noqa: F401
-from .loss import Transition, default_loss_fn  # noqa: F401
+from .loss import Transition, default_loss_fn, stochastic_loss_fn  # noqa: F401
 from .model import MuZero  # noqa: F401
-from .nn import MZNetwork, MZNetworkParams, create_muzero_network  # noqa: F401
+from .nn import (MZNetwork, MZNetworkParams, SMZNetwork, SMZNetworkParams, create_muzero_network,  # noqa: F401
+                 create_stochastic_muzero_network)
 from .policy import GumbelMuZeroPolicy, MuZeroPolicy, Policy, StochasticMuZeroPolicy  # noqa: F401
 from .search import (ChanceRecurrentFnOutput, DecisionRecurrentFnOutput, MuZeroSearch, PolicyOutput, SearchConfig,  # noqa: F401
                      SearchTree, key_words)

@@ -2,8 +2,8 @@
 
 The library is several translation units compiled in parallel (each `hipcc -c`, objects under muax_amd/lib/obj/)
 and linked into one shared object: the C-ABI's handle and registries (mz_api.hip) and one unit per route -- the fused
-act() dispatch (mz_act.hip), the step-wise path and the generic one-launch search with the step kernels
-(mz_stepwise.hip), the training step (mz_train.hip), the self-test and Dirichlet kernels (mz_selftest.hip) --, the
+act() dispatch (mz_act.hip), the step-wise path, the generic one-launch search and the stochastic MLP family's recurrent step with the
+step kernels (mz_stepwise.hip), the training step (mz_train.hip), the self-test and Dirichlet kernels (mz_selftest.hip) --, the
 fused act() kernel instances in five groups (mz_fused_g*.hip, listed in mz_instances.def), the wide-action act()
 kernel (mz_wide.hip), the ResNet recurrent kernel (mz_conv.hip), the device-resident replay (mz_replay.hip), the
 forward value unroll behind its priorities (mz_unroll.hip) and the device vector environments (mz_env.hip; 2048 with its
@@ -26,7 +26,7 @@ _HANDLE = ["mz_handle.h", "mz_host.h", "mz_keys.h", "mz_step.cuh", "mz_step_jump
 UNITS = {
     "mz_api.hip": _HANDLE + ["mz_fused_launch.h", "mz_fused.cuh"],
     "mz_act.hip": _HANDLE + ["mz_fused_launch.h", "mz_fused.cuh", "mz_wide_launch.h"],
-    "mz_stepwise.hip": _HANDLE + ["mz_mlp_generic.cuh", "mz_step_kernels.cuh"],
+    "mz_stepwise.hip": _HANDLE + ["mz_mlp_generic.cuh", "mz_step_kernels.cuh", "mz_stoch_mlp.cuh"],
     "mz_train.hip": ["mz_host.h", "mz_train_launch.h", "mz_train.cuh", "mz_spec.cuh", _ABI],
     "mz_selftest.hip": ["mz_host.h", "mz_dirichlet.cuh", "mz_spec.cuh", _ABI],
     "mz_fused_g0.hip": _FUSED,

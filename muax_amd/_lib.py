@@ -32,6 +32,16 @@ class MzsStochasticOutputs(C.Structure):
                 ("discount", _vp), ("state_embedding", _vp)]
 
 
+# the seven Linear(16)-elu-Linear stacks of mzs_stochastic_mlp_weights, in the struct's order
+STOCHASTIC_MLP_HEADS = ["ad", "av", "ac", "cr", "cn", "pv", "pp"]
+STOCHASTIC_MLP_WEIGHT_NAMES = [f"{h}_{a}" for h in STOCHASTIC_MLP_HEADS for a in ("w1", "b1", "w2", "b2")]
+
+
+class MzsStochasticMlpWeights(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("support_size", C.c_int32), ("discount", C.c_float), ("reserved0", C.c_float)]
+                + [(n, _vp) for n in STOCHASTIC_MLP_WEIGHT_NAMES])
+
+
 MLP_WEIGHT_NAMES = ["repr_w", "repr_b", "pv_w1", "pv_b1", "pv_w2", "pv_b2", "pp_w1", "pp_b1", "pp_w2",
                     "pp_b2", "dr_w1", "dr_b1", "dr_w2", "dr_b2", "dn_w1", "dn_b1", "dn_w2", "dn_b2"]
 
@@ -264,7 +274,7 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_env_classic_reset", "mzs_env_classic_step",
                     "mzs_env_2048_reset", "mzs_env_2048_step", "mzs_env_2048_mask",
                     "mzs_root_stochastic", "mzs_select_stochastic", "mzs_expand_backup_stochastic",
-                    "mzs_finish_stochastic"]
+                    "mzs_finish_stochastic", "mzs_mlp_set_stochastic_weights", "mzs_mlp_stochastic_recurrent"]
 
 _lib = None
 
@@ -301,6 +311,8 @@ def load(build_if_missing: bool = True):
     L.mzs_select_stochastic.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp]
     L.mzs_expand_backup_stochastic.argtypes = [_vp, C.c_int32, C.POINTER(MzsStochasticOutputs), _vp]
     L.mzs_finish_stochastic.argtypes = [_vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.mzs_mlp_set_stochastic_weights.argtypes = [_vp, C.POINTER(MzsStochasticMlpWeights)]
+    L.mzs_mlp_stochastic_recurrent.argtypes = [_vp, _vp, _vp, _vp, C.POINTER(MzsStochasticOutputs), _vp]
     L.mzs_mlp_loss_grad.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsTrainArgs), _vp]
     L.mzs_resnet_tower.argtypes = [C.POINTER(MzsTowerArgs), _vp]
     L.mzs_register_fused_dispatch.argtypes = [_vp, C.c_int32]

@@ -35,6 +35,8 @@ struct mzs_handle {
   float* gen_scratch = nullptr;    // generic route: prior logits [B, A] | embeddings [B, E] | actions [B]
   bool allow_wide = false;         // mzs_mlp_allow_wide: 17..64 actions under the MuZero policy take the wide one-launch kernel
   bool allow_wide_gumbel = false;  // mzs_mlp_allow_wide_gumbel: ... and under the Gumbel policy (a handle opts in separately)
+  bool have_stochastic_weights = false;  // mzs_mlp_set_stochastic_weights: the default stochastic MLP family (policy 2)
+  mzs_stochastic_mlp_weights sw = {};
 };
 
 namespace mzh {

@@ -1,6 +1,6 @@
 // mz_stepwise.hip -- the routes on the HBM tree of mz_step.cuh, whose kernels (mz_step_kernels.cuh) THIS unit emits: the
-// step-wise entry points for plugin nets (mzs_root .. mzs_finish, mzs_tree_export) and the generic one-launch act()
-// (mz_mlp_generic.cuh).
+// step-wise entry points for plugin nets (mzs_root .. mzs_finish, mzs_tree_export), the generic one-launch act()
+// (mz_mlp_generic.cuh) and the default stochastic MLP family's one-launch recurrent step (mz_stoch_mlp.cuh).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +9,7 @@
 #include "mz_handle.h"
 #include "mz_mlp_generic.cuh"
 #include "mz_step_kernels.cuh"
+#include "mz_stoch_mlp.cuh"
 
 using mzh::fail;
 
@@ -321,6 +322,67 @@ int mzs_finish_stochastic(mzs_handle* h, float temperature, const float* gumbel,
                           float* search_value_out, int32_t* depth_sum_out, void* stream_) {
   return finish_impl(h, "mzs_finish_stochastic", kStochastic, kNotStochastic, temperature, gumbel, action_out, action_weights_out,
                      search_value_out, depth_sum_out, stream_);
+}
+
+// ---- the default stochastic MLP family between the select and the expansion (mz_stoch_mlp.cuh) ----
+// what keeps a handle (and, `w`, a weight set) off the one-launch recurrent step: null when it is served
+static int stoch_mlp_refusal(mzs_handle* h, const char* who, int support_size) {
+  const mzs_config& c = h->cfg;
+  auto refuse = [&](int code, const char* what) { return fail(h, code, "%s", (std::string(who) + ": " + what).c_str()); };
+  if (c.policy != 2) return refuse(MZS_E_INVALID, kNotStochastic);
+  if (c.state_embed_dim != c.embed_dim || c.afterstate_embed_dim != c.embed_dim)
+    return refuse(MZS_E_UNSUPPORTED, "state_embed_dim and afterstate_embed_dim must both equal embed_dim");
+  if (c.num_actions + c.num_chance_outcomes > 64) return refuse(MZS_E_UNSUPPORTED, "num_actions + num_chance_outcomes > 64");
+  if (support_size < 8 || support_size > 31) return refuse(MZS_E_UNSUPPORTED, "support_size must be 8..31");
+  if (sizeof(float) * (size_t)mz::stoch_scratch_words(c.embed_dim, c.num_actions, c.num_chance_outcomes) > 64 * 1024)
+    return refuse(MZS_E_UNSUPPORTED, "embedding too large for the LDS of a workgroup (64 KiB)");
+  return MZS_OK;
+}
+
+int mzs_mlp_set_stochastic_weights(mzs_handle* h, const mzs_stochastic_mlp_weights* w) {
+  if (!h) return MZS_E_INVALID;
+  const char* who = "mzs_mlp_set_stochastic_weights";
+  if (!w || w->struct_size != (int32_t)sizeof(mzs_stochastic_mlp_weights))
+    return fail(h, MZS_E_INVALID, "%s: null or size mismatch (ABI)", who);
+  if (int rc = stoch_mlp_refusal(h, who, w->support_size)) return rc;
+  const float* const* wp = &w->ad_w1;
+  for (int i = 0; i < 28; ++i)
+    if (!wp[i]) return fail(h, MZS_E_INVALID, "%s: null weight array", who);
+  h->sw = *w;
+  h->have_stochastic_weights = true;
+  return MZS_OK;
+}
+
+int mzs_mlp_stochastic_recurrent(mzs_handle* h, const int32_t* slot, const int32_t* parent_is_decision,
+                                 const float* parent_embedding, const mzs_stochastic_outputs* o, void* stream_) {
+  if (!h) return MZS_E_INVALID;
+  const char* who = "mzs_mlp_stochastic_recurrent";
+  const mzs_config& c = h->cfg;
+  // (the weights' own limits are looked at once there are weights: a handle of another policy is told so first)
+  if (c.policy == 2 && !h->have_stochastic_weights) return fail(h, MZS_E_INVALID, "%s: call mzs_mlp_set_stochastic_weights first", who);
+  if (int rc = stoch_mlp_refusal(h, who, h->sw.support_size)) return rc;
+  if (!o || o->struct_size != (int32_t)sizeof(mzs_stochastic_outputs)) return fail(h, MZS_E_INVALID, "%s: null or size mismatch (ABI)", who);
+  if (!slot || !parent_is_decision || !parent_embedding) return fail(h, MZS_E_INVALID, "%s: null input", who);
+  if (!o->chance_logits || !o->afterstate_value || !o->afterstate_embedding || !o->action_logits || !o->value || !o->reward ||
+      !o->discount || !o->state_embedding)
+    return fail(h, MZS_E_INVALID, "%s: null output", who);
+  MZS_HIP(h, hipSetDevice(c.device));
+  const mzs_stochastic_mlp_weights& s = h->sw;
+  mz::StochMlp w;
+  w.ad = {s.ad_w1, s.ad_b1, s.ad_w2, s.ad_b2}; w.av = {s.av_w1, s.av_b1, s.av_w2, s.av_b2};
+  w.ac = {s.ac_w1, s.ac_b1, s.ac_w2, s.ac_b2}; w.cr = {s.cr_w1, s.cr_b1, s.cr_w2, s.cr_b2};
+  w.cn = {s.cn_w1, s.cn_b1, s.cn_w2, s.cn_b2}; w.pv = {s.pv_w1, s.pv_b1, s.pv_w2, s.pv_b2};
+  w.pp = {s.pp_w1, s.pp_b1, s.pp_w2, s.pp_b2};
+  w.E = c.embed_dim; w.A = c.num_actions; w.C = c.num_chance_outcomes; w.F = 2 * s.support_size + 1;
+  w.support = s.support_size; w.discount = s.discount;
+  // (the struct's arrays are const for the expansion, which reads them; this entry is their writer)
+  auto out = [](const float* p) { return const_cast<float*>(p); };
+  const mz::StochRecurrentArgs a = {c.batch, slot, parent_is_decision, parent_embedding, out(o->chance_logits),
+                                    out(o->afterstate_value), out(o->afterstate_embedding), out(o->action_logits), out(o->value),
+                                    out(o->reward), out(o->discount), out(o->state_embedding)};
+  const size_t lds = sizeof(float) * (size_t)mz::stoch_scratch_words(w.E, w.A, w.C);
+  hipLaunchKernelGGL(mz::mz_stoch_mlp_recurrent_kernel, dim3(c.batch), dim3(64), lds, static_cast<hipStream_t>(stream_), w, a);
+  return launched(h);
 }
 
 int mzs_tree_export(mzs_handle* h, const mzs_tree_view* out, void* stream_) {

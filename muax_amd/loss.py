@@ -19,6 +19,18 @@ muax/loss.py:60-61).  Reference quirks handled explicitly:
 Beyond the reference: `sample_weight` [B], the importance-sampling weights of prioritised replay
 (`DeviceReplayBuffer.sample(is_beta=)`), turns every mean_B CE(...) into mean_B (sample_weight * CE(...)) on both
 routes; the L2 term is not weighted.
+
+`stochastic_loss_fn` is the Stochastic MuZero loss of the reference's acme agent
+(muax/frameworks/acme/jax/stochastic_muzero/learning.py:200-277) in the conventions above -- a sum over steps, support
+targets by scalar_to_support, the same L2 term over all six modules, the halved hidden-state gradient before each
+afterstate step -- on torch autograd only.  Its reference quirks:
+  * learning.py:262 measures the VQ commitment against the straight-through code, whose value is the one-hot but whose
+    gradient is the encoder output's own: the term's gradient is identically zero.  Here the encoder output commits to
+    the DETACHED one-hot, which is what a commitment term is for;
+  * learning.py:230-231 hands the chance network argmax(code), an integer: the straight-through estimator it has just
+    built never carries a gradient.  Here the chance dynamics take the straight-through code itself as their one-hot
+    input, so the encoder learns from the losses downstream of the outcome;
+  * learning.py:273 divides by the unroll length; here that is `divide_by_length=True`, as in default_loss_fn.
 """
 from __future__ import annotations
 
@@ -76,6 +88,61 @@ def default_loss_fn(muzero_instance, batch: Transition, divide_by_length: bool =
     l2 = 0.5 * sum((p ** 2).sum() for m in muzero_instance.network if isinstance(m, torch.nn.Module)
                    for p in m.parameters())
     return loss + 1e-4 * l2
+
+
+def stochastic_loss_fn(muzero_instance, batch: Transition, vqvae_beta: float = 0.25, divide_by_length: bool = False,
+                       sample_weight=None):
+    """The Stochastic MuZero loss for a model built on an `SMZNetwork` (module docstring).  `batch` fields are [B, L, ...]
+    with an observation for EVERY step (obs [B, L, obs_dim]): the chance code of transition i is encoded from obs_i.
+    Step 0 contributes CE(v_0, Rn_0) + CE(pi_0, pi_0); transition i = 1..L-1, with action a_{i-1} and the code of obs_i:
+    CE(r, r_{i-1}) + CE(v_i, Rn_i) + CE(pi_i, pi_i) + CE(chance_logits, sg(code)) + CE(afterstate value, Rn_{i-1})
+    + vqvae_beta * mean ||encoded - sg(onehot)||^2, each a mean over the batch (`sample_weight` [B]: of weight * term)."""
+    m = muzero_instance
+    dev = m.device
+    rep, pred, after_dy, after_pred, chance_dy, enc = m.network
+    fdt = next((p.dtype for n in m.network if isinstance(n, torch.nn.Module) for p in n.parameters()), torch.float32)
+    t = lambda x, dt=fdt: torch.as_tensor(x, dtype=dt, device=dev)  # noqa: E731
+    a = t(batch.a, torch.long)
+    B, L = a.shape[:2]
+    a = a.reshape(B, L)
+    obs = t(batch.obs)
+    if obs.dim() < 3 or obs.shape[0] != B or obs.shape[1] < L:
+        raise ValueError(f"the stochastic loss needs every step's observation: batch.obs must be [B, L, ...] with L = {L} "
+                         f"rows per window, got {tuple(obs.shape)} (DeviceReplayBuffer.sample keeps the first row only)")
+    S = m._support_size
+    r_t = mx_utils.scalar_to_support(t(batch.r).reshape(B, L), S).detach()
+    Rn_t = mx_utils.scalar_to_support(t(batch.Rn).reshape(B, L), S).detach()
+    pi = t(batch.pi).reshape(B, L, -1).detach()
+    sw = None
+    if sample_weight is not None:
+        sw = torch.as_tensor(sample_weight, device=dev).detach().to(fdt)
+        if tuple(sw.shape) != (B,):
+            raise ValueError(f"sample_weight must be [B] with B = {B}, got {tuple(sw.shape)}")
+    mean = (lambda x: x.mean()) if sw is None else (lambda x: (x * sw).mean())
+    s = rep(obs[:, 0])
+    v, logits = pred(s)
+    loss = mean(softmax_cross_entropy(v, Rn_t[:, 0])) + mean(softmax_cross_entropy(logits, pi[:, 0]))
+    for i in range(1, L):
+        encoded, onehot, code = enc.code(obs[:, i]) if hasattr(enc, "code") else _straight_through(enc(obs[:, i]))
+        s = mx_utils.scale_gradient(s, 0.5)  # Appendix G
+        after = after_dy(s, a[:, i - 1])
+        av, chance_logits = after_pred(after)
+        r, s = chance_dy(after, code)
+        v, logits = pred(s)
+        loss = (loss + mean(softmax_cross_entropy(r, r_t[:, i - 1])) + mean(softmax_cross_entropy(v, Rn_t[:, i]))
+                + mean(softmax_cross_entropy(logits, pi[:, i])) + mean(softmax_cross_entropy(chance_logits, code.detach()))
+                + mean(softmax_cross_entropy(av, Rn_t[:, i - 1]))
+                + vqvae_beta * mean(((encoded - onehot.detach()) ** 2).mean(dim=-1)))
+    if divide_by_length:
+        loss = loss / L
+    l2 = 0.5 * sum((p ** 2).sum() for n in m.network if isinstance(n, torch.nn.Module) for p in n.parameters())
+    return loss + 1e-4 * l2
+
+
+def _straight_through(encoded):
+    """(encoded, argmax one-hot, straight-through code) for a plugin encoder that returns the code logits only."""
+    onehot = torch.nn.functional.one_hot(encoded.argmax(dim=-1), encoded.shape[-1]).to(encoded.dtype)
+    return encoded, onehot, encoded + (onehot - encoded).detach()
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -21,10 +21,11 @@ import torch
 from . import nn as mz_nn
 from . import prng
 from . import utils as mx_utils
-from .nn import MZNetwork, MZNetworkParams
+from .nn import MZNetwork, MZNetworkParams, SMZNetwork, SMZNetworkParams
 from .optimizers import optimizer  # noqa: F401  (the README's `muax.model.optimizer(...)`)
-from .policy import GumbelMuZeroPolicy, MuZeroPolicy, Policy
-from .search import MuZeroSearch, PolicyOutput, SearchConfig  # noqa: F401  (PolicyOutput: re-exported type)
+from .policy import GumbelMuZeroPolicy, MuZeroPolicy, Policy, StochasticMuZeroPolicy
+from .search import (ChanceRecurrentFnOutput, DecisionRecurrentFnOutput, MuZeroSearch, PolicyOutput,  # noqa: F401
+                     SearchConfig)  # (PolicyOutput: re-exported type)
 
 
 def _dirichlet(key_words, alpha: float, shape, device, global_batch=None, root_offset=0) -> torch.Tensor:
@@ -60,9 +61,10 @@ class MuZero:
     r"""MuZero algorithm (muax/model.py:16-50).
 
     Parameters mirror the reference: `network` (MZNetwork) or the three plugin callables, `policy_class`
-    / `policy` ("muzero" or "gumbel"; "stochastic" raises NotImplementedError: the network trio has no decision and
-    chance functions -- call StochasticMuZeroPolicy with your own), `optimizer`, `loss_fn`, `discount`,
-    `support_size`.  `recurrent_pred_on` selects which
+    / `policy` ("muzero" or "gumbel"; "stochastic" with an `SMZNetwork` -- nn.create_stochastic_muzero_network or six
+    plugin modules: Stochastic MuZero, chance nodes in the search and loss.stochastic_loss_fn in update(); with a plain
+    MZNetwork it raises NotImplementedError, the trio has no decision and chance functions), `optimizer`, `loss_fn`,
+    `discount`, `support_size`.  `recurrent_pred_on` selects which
     embedding the prediction net sees inside the search: "child" as muax/model.py:272, "parent" as the
     pip-release class muax/frameworks/coax/model.py:447-448.
     """
@@ -71,7 +73,12 @@ class MuZero:
                  policy: Optional[str] = None, optimizer=None, loss_fn=None, discount: float = 0.99,
                  support_size: int = 10, recurrent_pred_on: str = "child", device=None,
                  representation_fn=None, capture_graph: bool = False, root_graph_cache: int = 2):
-        if isinstance(network, MZNetwork):
+        self._stochastic = isinstance(network, SMZNetwork)
+        if self._stochastic:
+            if policy not in (None, "stochastic"):
+                raise ValueError(f"policy={policy!r}: an SMZNetwork runs policy='stochastic'")
+            self.network, policy, policy_class = network, None, StochasticMuZeroPolicy
+        elif isinstance(network, MZNetwork):
             self.network = network
         else:
             rep = representation_fn if representation_fn is not None else network
@@ -80,14 +87,20 @@ class MuZero:
             self.network = MZNetwork(rep, prediction_fn, dynamic_fn)
         if policy is not None:
             if policy not in ("muzero", "gumbel"):
-                # (the stochastic search itself is built -- StochasticMuZeroPolicy -- but this class's network trio has no
-                # decision / chance functions to hand it)
-                raise NotImplementedError(f"policy={policy!r}: MuZero runs 'muzero' and 'gumbel'; StochasticMuZeroPolicy is "
-                                          "called directly with decision_recurrent_fn and chance_recurrent_fn")
+                # (an MZNetwork trio has no decision / chance functions to hand the stochastic search)
+                raise NotImplementedError(f"policy={policy!r}: an MZNetwork runs 'muzero' and 'gumbel'; policy='stochastic' "
+                                          "needs an SMZNetwork (nn.create_stochastic_muzero_network), or call "
+                                          "StochasticMuZeroPolicy directly with decision_recurrent_fn and chance_recurrent_fn")
             policy_class = MuZeroPolicy if policy == "muzero" else GumbelMuZeroPolicy
         if not (isinstance(policy_class, type) and issubclass(policy_class, Policy)):
             raise TypeError("policy_class must be a subclass of muax_amd.policy.Policy")
-        self.repr_func, self.pred_func, self.dy_func = self.network
+        if self._stochastic:
+            (self.repr_func, self.pred_func, self.after_dy_func, self.after_pred_func, self.chance_dy_func,
+             self.enc_func) = self.network
+            self.dy_func = None
+        else:
+            self.repr_func, self.pred_func, self.dy_func = self.network
+        self._last_route = None  # stochastic act(): "hip_stochastic_mlp" or "callables"
         self._policy = policy_class()
         self._optimizer = optimizer
         self.loss_fn = loss_fn
@@ -127,11 +140,18 @@ class MuZero:
         with torch.no_grad():
             s = self.repr_func(x)
             self.pred_func(s)
-            self.dy_func(s, torch.zeros(s.shape[0], dtype=torch.long))
+            zeros = torch.zeros(s.shape[0], dtype=torch.long)
+            if self._stochastic:  # all six modules
+                after = self.after_dy_func(s, zeros)
+                self.after_pred_func(after)
+                self.chance_dy_func(after, zeros)
+                self.enc_func(x)
+            else:
+                self.dy_func(s, zeros)
         for m in self.network:
             if isinstance(m, torch.nn.Module):
                 m.to(self.device)
-        self._params = MZNetworkParams(*[dict(m.named_parameters()) if isinstance(m, torch.nn.Module) else None
+        self._params = (SMZNetworkParams if self._stochastic else MZNetworkParams)(*[dict(m.named_parameters()) if isinstance(m, torch.nn.Module) else None
                                          for m in self.network])
         self._weights_version += 1
         self._fused_train = None
@@ -326,6 +346,10 @@ class MuZero:
         PolicyOutput holds NumPy arrays."""
         if self._params is None:
             raise ValueError("call init() first")
+        if self._stochastic:
+            return self._plan_stochastic(rng_key, obs, num_simulations, temperature, invalid_actions, max_depth, qtransform,
+                                         dirichlet_fraction, dirichlet_alpha, pb_c_init, pb_c_base, dirichlet_noise, gumbel,
+                                         tiebreak, with_tree, global_batch, root_offset)
         gumbel_policy = isinstance(self._policy, GumbelMuZeroPolicy)
         if qtransform is None:
             qtransform = "qtransform_by_parent_and_siblings"  # muax/model.py:230-231, for EVERY policy
@@ -414,6 +438,84 @@ class MuZero:
                                 global_batch=global_batch, root_offset=root_offset, native_loop=self._native_loop(root))
 
         return self._checked_search(run), root[1]
+
+    # ------------------------------------------------------------------ Stochastic MuZero (SMZNetwork)
+    def _decision_inference(self, params, rng_key, action, embedding):
+        """mctx decision_recurrent_fn -> (DecisionRecurrentFnOutput(chance_logits, afterstate_value), afterstate)."""
+        with torch.no_grad():
+            after = self.after_dy_func(embedding, action)
+            av, chance_logits = self.after_pred_func(after)
+            av = mx_utils.support_to_scalar(torch.softmax(av, dim=-1), self._support_size).flatten()
+        return DecisionRecurrentFnOutput(chance_logits, av), after
+
+    def _chance_inference(self, params, rng_key, outcome, afterstate):
+        """mctx chance_recurrent_fn -> (ChanceRecurrentFnOutput(action_logits, value, reward, discount), next state)."""
+        with torch.no_grad():
+            r, s = self.chance_dy_func(afterstate, outcome)
+            v, logits = self.pred_func(s)
+            r = mx_utils.support_to_scalar(torch.softmax(r, dim=-1), self._support_size).flatten()
+            v = mx_utils.support_to_scalar(torch.softmax(v, dim=-1), self._support_size).flatten()
+        return ChanceRecurrentFnOutput(logits, v, r, torch.full_like(r, self._discount)), s
+
+    def _stochastic_handle(self, B, A, Cn, E, S, max_depth, pb_c_init, pb_c_base, tiebreak, global_batch, root_offset):
+        """The search handle of this stochastic act() configuration with the default family's weights bound: created once,
+        the weights re-bound when their version changed (update(), weights_changed())."""
+        key = ("stochastic", B, A, Cn, E, S, max_depth, pb_c_init, pb_c_base, tiebreak, global_batch, root_offset)
+        h = self._fused.get(key)
+        if h is None:
+            s = MuZeroSearch(B, SearchConfig(A, S, E, max_depth=max_depth, tiebreak=tiebreak, pb_c_init=pb_c_init,
+                                             pb_c_base=float(pb_c_base), policy="stochastic", num_chance_outcomes=Cn,
+                                             global_batch=global_batch, root_offset=root_offset), self.device)
+            h = self._fused[key] = [s, None]
+        if h[1] != self._weights_version:
+            w = {k: v.detach() for k, v in mz_nn.stochastic_mlp_weights(self.network).items()}
+            h[0].set_stochastic_mlp_weights(w, self._support_size, self._discount)
+            h[1] = self._weights_version
+        return h[0]
+
+    def _plan_stochastic(self, rng_key, obs, num_simulations, temperature, invalid_actions, max_depth, qtransform,
+                         dirichlet_fraction, dirichlet_alpha, pb_c_init, pb_c_base, dirichlet_noise, gumbel, tiebreak,
+                         with_tree, global_batch, root_offset):
+        """_plan for an SMZNetwork -> (PolicyOutput, root value): root inference on the torch modules, once; then the
+        search with the decision and the chance function evaluated by the library (the default stochastic MLP family on a
+        GPU, support_size 8..31: MuZeroSearch.search_stochastic_mlp; MUAX_AMD_STOCHASTIC_MLP=0 switches it off) or, for
+        plugin modules, by StochasticMuZeroPolicy on callables built from them.  `_last_route` names the route taken."""
+        qt = getattr(qtransform, "__name__", qtransform)
+        if qt not in (None, "qtransform_by_parent_and_siblings"):
+            raise ValueError(f"qtransform {qt!r} is not implemented for this policy")
+        key = prng.as_key(rng_key)
+        self._last_fused = None
+        obs_t = obs if isinstance(obs, torch.Tensor) and obs.device == self.device \
+            else torch.as_tensor(obs, dtype=torch.float32).to(self.device)
+        root = self._root_inference_eager(obs_t)
+        B, A = root[0].shape
+        Cn = getattr(self.after_pred_func, "num_actions", None)
+        if dirichlet_noise is None and dirichlet_fraction:
+            k_dir = prng.split(key, 3)[1]  # mctx: rng_key, dirichlet_rng_key, search_rng_key = split(key, 3)
+            dirichlet_noise = _dirichlet(k_dir, dirichlet_alpha, (B, A), self.device, global_batch, root_offset)
+        hip = (mz_nn.is_default_stochastic_mlp(self.network) and self.device.type == "cuda"
+               and 8 <= self._support_size <= 31 and os.environ.get("MUAX_AMD_STOCHASTIC_MLP", "1") != "0")
+        if hip:
+            h = self._stochastic_handle(B, A, Cn, root[2].shape[1], num_simulations, max_depth, pb_c_init, pb_c_base,
+                                        tiebreak, global_batch, root_offset)
+            out = h.search_stochastic_mlp(root, key=key, invalid_actions=invalid_actions, dirichlet_noise=dirichlet_noise,
+                                          dirichlet_fraction=dirichlet_fraction, temperature=temperature, gumbel=gumbel,
+                                          with_tree=with_tree, graph=self.capture_graph, graph_version=self._weights_version)
+            t = out.search_tree
+            if t is not None:  # the decision slice, as StochasticMuZeroPolicy returns it (mctx _mask_tree)
+                t = t._replace(**{f: getattr(t, f)[..., :A] for f in t._fields if f.startswith("children_")})
+            self._last_route = "hip_stochastic_mlp"
+            return PolicyOutput(out.action, out.action_weights, t), root[1]
+        shapes = {} if Cn is None else dict(num_chance_outcomes=Cn, afterstate_shape=tuple(root[2].shape[1:]))
+        out = self._policy(self._params, key, root, decision_recurrent_fn=self._decision_inference,
+                           chance_recurrent_fn=self._chance_inference, num_simulations=num_simulations,
+                           temperature=temperature, invalid_actions=invalid_actions, max_depth=max_depth,
+                           dirichlet_fraction=dirichlet_fraction, dirichlet_noise=dirichlet_noise, pb_c_init=pb_c_init,
+                           pb_c_base=pb_c_base, gumbel=gumbel, tiebreak=tiebreak, with_tree=with_tree,
+                           graph=self.capture_graph, graph_version=self._weights_version, global_batch=global_batch,
+                           root_offset=root_offset, **shapes)
+        self._last_route = "callables"
+        return out, root[1]
 
     _warned_stepwise = set()
 
@@ -564,7 +666,8 @@ class MuZero:
             and mz_nn.is_default_mlp_trio(self.network) and (self.repr_func.obs_dim or 999) <= 128 \
             and not kwargs.get("pi_all_pairs", False)
         if backend == "hip" and not fused:
-            raise ValueError("backend='hip' needs the default MLP trio on a GPU and the default loss")
+            raise ValueError("backend='hip' needs the default MLP trio on a GPU and the default loss"
+                             + (" (the stochastic loss of an SMZNetwork runs on torch autograd only)" if self._stochastic else ""))
         if fused:
             try:
                 if self._fused_train is None:
@@ -595,7 +698,7 @@ class MuZero:
                     raise
                 fused = False
         if not fused:
-            loss_fn = self.loss_fn or mz_loss.default_loss_fn
+            loss_fn = self.loss_fn or (mz_loss.stochastic_loss_fn if self._stochastic else mz_loss.default_loss_fn)
             loss = loss_fn(self, batch, *args, **kwargs)
             loss.backward()
             if dp_mean:
@@ -618,6 +721,8 @@ class MuZero:
             raise ValueError(f"backend must be 'auto', 'hip' or 'torch', got {backend!r}")
         if self._params is None:
             raise ValueError("call init() first")
+        if self._stochastic:
+            raise NotImplementedError("unroll_values is not built for an SMZNetwork (its unroll needs every step's chance code)")
         _, _, kp = mz_unroll.batch_window(batch, k_prio)
         trio = self.device.type == "cuda" and mz_nn.is_default_mlp_trio(self.network)
         if backend == "hip" and not trio:
@@ -630,6 +735,9 @@ class MuZero:
 
     def save_load(self, file, save=True):
         """muax/model.py:203-212, on torch state dicts (the reference pickles haiku params)."""
+        if self._stochastic:
+            raise NotImplementedError("checkpoints of an SMZNetwork are not built: save its six modules' state_dict()s "
+                                      "(model.network) and the optimiser state yourself")
         mods = {n: m for n, m in zip(("representation", "prediction", "dynamic"), self.network)
                 if isinstance(m, torch.nn.Module)}
         if save:

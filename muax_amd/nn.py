@@ -117,7 +117,9 @@ class Dynamic(nn.Module):
         self.r_func = _mlp2(embedding_dim + num_actions, full_support_size, generator)
 
     def forward(self, s, a):
-        sa = torch.cat([s, torch.nn.functional.one_hot(a.long(), self.num_actions).to(s.dtype)], dim=1)
+        # a: indices [B], or -- the stochastic loss's straight-through chance code -- the one-hot rows [B, A] themselves
+        onehot = a if a.dim() == 2 and a.is_floating_point() else torch.nn.functional.one_hot(a.long(), self.num_actions)
+        sa = torch.cat([s, onehot.to(s.dtype)], dim=1)
         return _apply_mlp2(self.r_func, sa), min_max_normalize(_apply_mlp2(self.ns_func, sa))
 
 
@@ -175,6 +177,8 @@ def create_muzero_network(representation_module, prediction_module, dynamic_modu
 
 
 def is_default_mlp_trio(network: MZNetwork) -> bool:
+    if len(network) != 3:  # (an SMZNetwork)
+        return False
     r, p, d = network
     return type(r) is Representation and type(p) is Prediction and type(d) is Dynamic
 
@@ -187,6 +191,104 @@ def mlp_trio_weights(network: MZNetwork) -> dict:
             "pp_w1": p.pi_func[0].w, "pp_b1": p.pi_func[0].b, "pp_w2": p.pi_func[1].w, "pp_b2": p.pi_func[1].b,
             "dr_w1": d.r_func[0].w, "dr_b1": d.r_func[0].b, "dr_w2": d.r_func[1].w, "dr_b2": d.r_func[1].b,
             "dn_w1": d.ns_func[0].w, "dn_b1": d.ns_func[0].b, "dn_w2": d.ns_func[1].w, "dn_b2": d.ns_func[1].b}
+
+
+# ---------------------------------------------------------------------------------------------------
+# Default stochastic MLP family (Stochastic MuZero): the model of muax/frameworks/acme/jax/stochastic_muzero/networks.py
+# at the scale and in the blocks of the default trio above, so that the library evaluates the decision and the chance
+# function itself (muax_amd/csrc/mz_stoch_mlp.cuh) to the arithmetic of the trio.
+# ---------------------------------------------------------------------------------------------------
+class SMZNetworkParams(NamedTuple):
+    representation: Optional[dict] = None
+    prediction: Optional[dict] = None
+    afterstate_dynamic: Optional[dict] = None
+    afterstate_prediction: Optional[dict] = None
+    chance_dynamic: Optional[dict] = None
+    encoder: Optional[dict] = None
+
+
+class SMZNetwork(NamedTuple):
+    """The six functions of a Stochastic MuZero model.  representation_fn(obs) -> s; prediction_fn(s) -> (v_logits,
+    pi_logits); afterstate_dynamic_fn(s, a) -> afterstate; afterstate_prediction_fn(afterstate) -> (afterstate value
+    logits, chance logits); chance_dynamic_fn(afterstate, c) -> (r_logits, next s); encoder_fn(obs) -> chance-code
+    logits [C] (training only)."""
+    representation_fn: Callable
+    prediction_fn: Callable
+    afterstate_dynamic_fn: Callable
+    afterstate_prediction_fn: Callable
+    chance_dynamic_fn: Callable
+    encoder_fn: Callable
+
+
+class AfterstateDynamic(nn.Module):
+    """as = min_max_normalize(mlp2([s, onehot(a, A)])), width E: `Dynamic`'s next-state branch without a reward head.
+
+    The reference's acme net (stochastic_muzero/networks.py) does NOT normalise the afterstate.  This one does, so that
+    every embedding the search tree stores lies in [0, 1] like the others, and so that the function is exactly the
+    dynamics half of the default trio's recurrent inference, which the library and its CPU oracle already state."""
+
+    def __init__(self, embedding_dim: int, num_actions: int, generator=None, name="afterstate_dynamic"):
+        super().__init__()
+        self.embedding_dim, self.num_actions = embedding_dim, num_actions
+        self.as_func = _mlp2(embedding_dim + num_actions, embedding_dim, generator)
+
+    def forward(self, s, a):
+        sa = torch.cat([s, torch.nn.functional.one_hot(a.long(), self.num_actions).to(s.dtype)], dim=1)
+        return min_max_normalize(_apply_mlp2(self.as_func, sa))
+
+
+class ChanceEncoder(nn.Module):
+    """mlp2(obs_dim, C) on an observation: the chance-code logits.  `code()`: the argmax one-hot with a straight-through
+    gradient (select_closest_code of the reference's networks.py on a one-hot codebook)."""
+
+    def __init__(self, num_chance_outcomes: int, obs_dim: Optional[int] = None, generator=None, name="encoder"):
+        super().__init__()
+        self.num_chance_outcomes, self.obs_dim, self._gen = num_chance_outcomes, obs_dim, generator
+        self.enc_func = _mlp2(obs_dim, num_chance_outcomes, generator) if obs_dim else None
+
+    def materialize(self, obs_dim: int):
+        if self.enc_func is None:
+            self.obs_dim = obs_dim
+            self.enc_func = _mlp2(obs_dim, self.num_chance_outcomes, self._gen)
+
+    def forward(self, obs):
+        self.materialize(obs.shape[-1])
+        return _apply_mlp2(self.enc_func, obs)
+
+    def code(self, obs):
+        """(encoded [B, C], one-hot of its argmax (no gradient), the straight-through code encoded + sg(onehot - encoded))"""
+        e = self.forward(obs)
+        onehot = torch.nn.functional.one_hot(e.argmax(dim=-1), self.num_chance_outcomes).to(e.dtype)
+        return e, onehot, e + (onehot - e).detach()
+
+
+def create_stochastic_muzero_network(embedding_dim: int, num_actions: int, num_chance_outcomes: int,
+                                     full_support_size: int, generator=None) -> SMZNetwork:
+    """The default stochastic MLP family: every head Linear(16)-elu-Linear in haiku layout and init, made of the default
+    trio's blocks wherever the mathematics is the same -- `Representation`, `Prediction(A, F)`, `AfterstateDynamic`, the
+    afterstate prediction a `Prediction(C, F)` (afterstate value logits, chance logits), the chance dynamics a
+    `Dynamic(E, C, F)` (reward logits, next state), `ChanceEncoder`."""
+    E, A, Cn, F = embedding_dim, num_actions, num_chance_outcomes, full_support_size
+    return SMZNetwork(Representation(E, generator=generator), Prediction(A, F, generator=generator),
+                      AfterstateDynamic(E, A, generator), Prediction(Cn, F, generator=generator, name="afterstate_prediction"),
+                      Dynamic(E, Cn, F, generator, name="chance_dynamic"), ChanceEncoder(Cn, generator=generator))
+
+
+def is_default_stochastic_mlp(network) -> bool:
+    if not isinstance(network, SMZNetwork):
+        return False
+    r, p, ad, ap, cd, en = network
+    return (type(r) is Representation and type(p) is Prediction and type(ad) is AfterstateDynamic
+            and type(ap) is Prediction and type(cd) is Dynamic and type(en) is ChanceEncoder)
+
+
+def stochastic_mlp_weights(network: SMZNetwork) -> dict:
+    """The 28 arrays of the decision and the chance function in the order of mzs_stochastic_mlp_weights
+    (include/mzsearch.h): ad, av, ac, cr, cn, pv, pp, each w1, b1, w2, b2."""
+    _, p, ad, ap, cd, _ = network
+    heads = {"ad": ad.as_func, "av": ap.v_func, "ac": ap.pi_func, "cr": cd.r_func, "cn": cd.ns_func,
+             "pv": p.v_func, "pp": p.pi_func}
+    return {f"{h}_{n}{i + 1}": getattr(m[i], n) for h, m in heads.items() for i in (0, 1) for n in ("w", "b")}
 
 
 # ---------------------------------------------------------------------------------------------------

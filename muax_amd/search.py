@@ -16,7 +16,8 @@ import torch
 
 from . import _lib
 from ._lib import (MLP_WEIGHT_NAMES, TREE_FIELDS, TREE_INT_FIELDS, MzsActArgs, MzsActHostArgs, MzsConfig,
-                   MzsMlpWeights, MzsStochasticOutputs, MzsTreeView)
+                   MzsMlpWeights, MzsStochasticMlpWeights, MzsStochasticOutputs, MzsTreeView,
+                   STOCHASTIC_MLP_WEIGHT_NAMES)
 
 
 class SearchTree(NamedTuple):
@@ -164,6 +165,7 @@ class MuZeroSearch:
         _lib.check(self._L.mzs_create(C.byref(c), C.byref(h)))
         self._h = h
         self._weights = None
+        self._stochastic_weights = self._stochastic_out = None  # set_stochastic_mlp_weights; its recurrent step's outputs
         B, A = self.batch, cfg.num_actions
         with torch.cuda.device(self.device):
             # action | action_weights | root_value in ONE allocation: a NumPy caller gets them with one copy
@@ -614,6 +616,79 @@ class MuZeroSearch:
         """Summary and sample over the A actions; with_tree: the full tree, children arrays [B, N, A + C]."""
         return self._finish(self._L.mzs_finish_stochastic, temperature, gumbel, with_tree)
 
+    def set_stochastic_mlp_weights(self, weights: dict, support_size: int = 10, discount: float = 0.99):
+        """Weights of the default stochastic MLP family (nn.stochastic_mlp_weights: 28 arrays, haiku layout w[in][out]) for
+        search_stochastic_mlp.  The handle must run the stochastic policy with both embeddings embed_dim wide."""
+        A, Cn, E = self.cfg.num_actions, self.cfg.num_chance_outcomes, self.cfg.embed_dim
+        F, H = 2 * support_size + 1, 16
+        heads = {"ad": (E + A, E), "av": (E, F), "ac": (E, Cn), "cr": (E + Cn, F), "cn": (E + Cn, E), "pv": (E, F),
+                 "pp": (E, A)}
+        shapes = {}
+        for h, (i, o) in heads.items():
+            shapes.update({f"{h}_w1": (i, H), f"{h}_b1": (H,), f"{h}_w2": (H, o), f"{h}_b2": (o,)})
+        keep = {n: self._f32(weights[n], shapes[n], n) for n in STOCHASTIC_MLP_WEIGHT_NAMES}
+        w = _lib.args(MzsStochasticMlpWeights, support_size=support_size, discount=discount,
+                      **{n: keep[n].data_ptr() for n in STOCHASTIC_MLP_WEIGHT_NAMES})
+        _lib.check(self._L.mzs_mlp_set_stochastic_weights(self._h, C.byref(w)), self._h)
+        self._stochastic_weights = keep  # keep the device buffers alive
+
+    def stochastic_mlp_recurrent(self, slot, parent_is_decision, parent_embedding):
+        """The decision or the chance function of the bound default family for every root, by its parent's kind, in ONE
+        launch (mzs_mlp_stochastic_recurrent) -> the MzsStochasticOutputs block of the handle's persistent output arrays,
+        which expand_backup_stochastic_outputs takes.  Rows of the other kind keep what they held."""
+        if self._stochastic_weights is None:
+            raise ValueError("set_stochastic_mlp_weights() first")
+        if self._stochastic_out is None:
+            B, A, Cn, E = self.batch, self.cfg.num_actions, self.cfg.num_chance_outcomes, self.cfg.embed_dim
+            with torch.cuda.device(self.device):
+                bufs = [torch.zeros(B * n, dtype=torch.float32, device=self.device) for n in (Cn, 1, E, A, 1, 1, 1, E)]
+            o = _lib.args(MzsStochasticOutputs)
+            (o.chance_logits, o.afterstate_value, o.afterstate_embedding, o.action_logits, o.value, o.reward, o.discount,
+             o.state_embedding) = (t.data_ptr() for t in bufs)
+            self._stochastic_out = (o, bufs)
+        o = self._stochastic_out[0]
+        _lib.check(self._L.mzs_mlp_stochastic_recurrent(self._h, _ptr(slot), _ptr(parent_is_decision), _ptr(parent_embedding),
+                                                        C.byref(o), self._stream()), self._h)
+        return o
+
+    def expand_backup_stochastic_outputs(self, sim: int, outputs):
+        """expand_backup_stochastic on a filled MzsStochasticOutputs block (stochastic_mlp_recurrent's)."""
+        _lib.check(self._L.mzs_expand_backup_stochastic(self._h, sim, C.byref(outputs), self._stream()), self._h)
+
+    def _search_stochastic(self, root_fn_output, recurrent_expand, gkey, fns, key, invalid_actions, dirichlet_noise,
+                           dirichlet_fraction, temperature, gumbel, with_tree, graph, graph_version) -> PolicyOutput:
+        """The stochastic search around `recurrent_expand(sim, slot, parent_is_decision, parent_embedding)`, which evaluates
+        the functions and expands: root, S x (select -> recurrent_expand), eager or as one captured graph, finish."""
+        prior_logits, value, embedding = root_fn_output
+
+        def do_root():
+            self.root_stochastic(prior_logits, value, embedding, key, invalid_actions, dirichlet_noise, dirichlet_fraction)
+
+        def loop():
+            for sim in range(self.cfg.num_simulations):
+                recurrent_expand(sim, *self.select_stochastic(sim))
+
+        do_root()
+        self._run_loop(do_root, loop, graph, gkey, fns, graph_version)
+        return self.finish_stochastic(temperature, gumbel, with_tree)
+
+    def search_stochastic_mlp(self, root_fn_output, key=0, invalid_actions=None, dirichlet_noise=None, dirichlet_fraction=0.25,
+                              temperature=1.0, gumbel=None, with_tree=False, graph=False, graph_key=None,
+                              graph_version=0) -> PolicyOutput:
+        """search_stochastic with the two callables replaced by the library's own evaluation of the default stochastic MLP
+        family (set_stochastic_mlp_weights): three launches per simulation -- select, the function of each root's parent
+        kind, expand + backward -- and no torch op.  Arguments as search_stochastic; the kernel reads the bound weight
+        arrays at every launch, so a captured loop sees in-place weight updates (a re-bound array: new graph_version)."""
+        if self._stochastic_weights is None:
+            raise ValueError("set_stochastic_mlp_weights() first")
+
+        def recurrent_expand(sim, slot, kind, pemb):
+            self.expand_backup_stochastic_outputs(sim, self.stochastic_mlp_recurrent(slot, kind, pemb))
+
+        gkey = graph_key if graph_key is not None else "stochastic_mlp"
+        return self._search_stochastic(root_fn_output, recurrent_expand, gkey, self._stochastic_weights, key, invalid_actions,
+                                       dirichlet_noise, dirichlet_fraction, temperature, gumbel, with_tree, graph, graph_version)
+
     def search_stochastic(self, root_fn_output, decision_fn, chance_fn, key=0, invalid_actions=None, dirichlet_noise=None,
                           dirichlet_fraction=0.25, temperature=1.0, gumbel=None, with_tree=False, graph=False,
                           graph_key=None, graph_version=0) -> PolicyOutput:
@@ -625,20 +700,13 @@ class MuZeroSearch:
         clamp(slot, 0, A - 1), the chance function at outcome clamp(slot - A, 0, C - 1), each on the parent row cut to its
         own width -- and the expansion kernel keeps, per root, the half that matches the parent's kind.  key, noise,
         invalid_actions, temperature, gumbel ([B, A]), with_tree and graph= / graph_key= / graph_version= as in search()."""
-        prior_logits, value, embedding = root_fn_output
-        A, Cn, S = self.cfg.num_actions, self.cfg.num_chance_outcomes, self.cfg.num_simulations
+        A, Cn = self.cfg.num_actions, self.cfg.num_chance_outcomes
 
-        def do_root():
-            self.root_stochastic(prior_logits, value, embedding, key, invalid_actions, dirichlet_noise, dirichlet_fraction)
+        def recurrent_expand(sim, slot, _, pemb):
+            d_out, after = decision_fn(slot.clamp(0, A - 1), pemb[:, :self._es])
+            c_out, state = chance_fn((slot - A).clamp(0, Cn - 1), pemb[:, :self._ea])
+            self.expand_backup_stochastic(sim, d_out, after, c_out, state)
 
-        def loop():
-            for sim in range(S):
-                slot, _, pemb = self.select_stochastic(sim)
-                d_out, after = decision_fn(slot.clamp(0, A - 1), pemb[:, :self._es])
-                c_out, state = chance_fn((slot - A).clamp(0, Cn - 1), pemb[:, :self._ea])
-                self.expand_backup_stochastic(sim, d_out, after, c_out, state)
-
-        do_root()
         gkey = graph_key if graph_key is not None else (fn_identity(decision_fn), fn_identity(chance_fn))
-        self._run_loop(do_root, loop, graph, gkey, (decision_fn, chance_fn), graph_version)
-        return self.finish_stochastic(temperature, gumbel, with_tree)
+        return self._search_stochastic(root_fn_output, recurrent_expand, gkey, (decision_fn, chance_fn), key, invalid_actions,
+                                       dirichlet_noise, dirichlet_fraction, temperature, gumbel, with_tree, graph, graph_version)

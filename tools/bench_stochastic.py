@@ -4,6 +4,10 @@ at 36 actions -- the same slots per node, simulations and roots, scripted net ou
 tree launches per simulation on either side.  Runs alternate between the two; medians and ranges over `--repeats`.
 
     python tools/bench_stochastic.py [--sims 50] [--repeats 15] [--out FILE]
+
+--mlp: the default stochastic MLP family (E = 16) searched two ways from the same root outputs -- the callable route
+(search_stochastic with the torch modules: both functions on every root, a few dozen small torch launches per simulation)
+and the library route (search_stochastic_mlp: one launch for the functions) -- eager and graph=True, alternating.
 """
 import argparse
 import json
@@ -57,12 +61,61 @@ def timed(fn):
     return a.elapsed_time(b) * 1e3  # us
 
 
+def make_mlp(batch, sims, graph):
+    """(callable route, library route, handles) for one act of the default family at 2048's shape."""
+    import numpy as np
+
+    import muax_amd as mx
+    e = 16
+    net = mx.create_stochastic_muzero_network(e, A, C, 21, generator=torch.Generator().manual_seed(1))
+    m = mx.MuZero(net, policy="stochastic")
+    m.init(0, np.zeros((1, 16), np.float32))
+    g = torch.Generator().manual_seed(batch)
+    root = m._root_inference_eager(torch.rand(batch, 16, generator=g).cuda())
+    cfg = SearchConfig(A, sims, e, policy="stochastic", num_chance_outcomes=C)
+    hc, hl = MuZeroSearch(batch, cfg), MuZeroSearch(batch, cfg)
+    hl.set_stochastic_mlp_weights({k: v.detach() for k, v in mx.nn.stochastic_mlp_weights(net).items()}, 10, 0.99)
+    dec = lambda a, s: m._decision_inference(None, None, a, s)  # noqa: E731
+    cha = lambda c, s: m._chance_inference(None, None, c, s)  # noqa: E731
+    return (lambda: hc.search_stochastic(root, dec, cha, key=1, dirichlet_fraction=0.0, graph=graph),
+            lambda: hl.search_stochastic_mlp(root, key=1, dirichlet_fraction=0.0, graph=graph), (hc, hl))
+
+
+def main_mlp(args):
+    rows = []
+    for batch in (64, 1024):
+        for graph in (False, True):
+            call, lib, handles = make_mlp(batch, args.sims, graph)
+            for _ in range(3):
+                call(), lib()
+            torch.cuda.synchronize()
+            t = {"callables": [], "library": []}
+            for _ in range(args.repeats):  # alternating
+                t["callables"].append(timed(call))
+                t["library"].append(timed(lib))
+            row = {"roots": batch, "sims": args.sims, "graph": graph}
+            for k, v in t.items():
+                row[k] = {"median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1),
+                          "per_sim_us": round(statistics.median(v) / args.sims, 2)}
+            row["speedup_median"] = round(row["callables"]["median_us"] / row["library"]["median_us"], 2)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            for h in handles:
+                h.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sims", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=15)
     ap.add_argument("--out")
+    ap.add_argument("--mlp", action="store_true")
     args = ap.parse_args()
+    if args.mlp:
+        return main_mlp(args)
     rows = []
     for batch in (64, 1024):
         sto, det, handles = make(batch, args.sims)
