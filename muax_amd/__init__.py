@@ -12,6 +12,7 @@ from .replay_device import DeviceReplayBuffer  # noqa: F401
 from . import envs  # noqa: F401
 from .envs import Device2048, DeviceAcrobot, DeviceCartPole, DeviceMountainCar  # noqa: F401
 from .loss import Transition, default_loss_fn, stochastic_loss_fn  # noqa: F401
+from ._lib import NoCachedDecisions, NoKernelInstance, TooLargeForLds, Unsupported  # noqa: F401
 from .model import MuZero  # noqa: F401
 from .nn import (MZNetwork, MZNetworkParams, SMZNetwork, SMZNetworkParams, create_muzero_network,  # noqa: F401
                  create_stochastic_muzero_network)

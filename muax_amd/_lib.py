@@ -374,13 +374,38 @@ def load(build_if_missing: bool = True):
     return L
 
 
+class Unsupported(ValueError):
+    """MZS_E_UNSUPPORTED: the arguments are well formed, the library has no kernel for this configuration."""
+
+
+class NoKernelInstance(Unsupported):
+    """No instance of the fused act() / training kernel for this shape: one may be built on demand (muax_amd/_jit.py)."""
+
+
+class TooLargeForLds(Unsupported):
+    """The shape is beyond what the kernel keeps in the LDS of a workgroup / a CU."""
+
+
+class NoCachedDecisions(Unsupported):
+    """The handle's tree is walked level by level; the entry needs the cached decisions of mz_step_jump.cuh."""
+
+
+# MZS_E_UNSUPPORTED is one status code: the library's message tells WHICH refusal it is.  The only place where a message
+# of the library is inspected -- callers catch the classes.
+_REFUSALS = (("no fused kernel instance", NoKernelInstance), ("no kernel instance", NoKernelInstance),
+             ("too large for the LDS", TooLargeForLds), ("cached decisions", NoCachedDecisions))
+
+
 def check(code: int, handle=None):
     """Map C-ABI status codes onto Python exceptions (ValueError for bad arguments, as the
-    reference raises for bad shapes/arguments; RuntimeError for device failures)."""
+    reference raises for bad shapes/arguments -- its subclass Unsupported, or the more specific class of _REFUSALS, for
+    a configuration without a kernel; RuntimeError for device failures).  The library's message is the exception's text."""
     if code == MZS_OK:
         return
     msg = load().mzs_last_error(handle)
     msg = msg.decode() if msg else f"mzsearch error {code}"
-    if code in (MZS_E_INVALID, MZS_E_UNSUPPORTED):
+    if code == MZS_E_UNSUPPORTED:
+        raise next((cls for words, cls in _REFUSALS if words in msg), Unsupported)(msg)
+    if code == MZS_E_INVALID:
         raise ValueError(msg)
     raise RuntimeError(msg)

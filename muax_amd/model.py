@@ -18,6 +18,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import _lib
 from . import nn as mz_nn
 from . import prng
 from . import utils as mx_utils
@@ -35,8 +36,6 @@ def _dirichlet(key_words, alpha: float, shape, device, global_batch=None, root_o
     (mzs_dirichlet, muax_amd/csrc/mz_dirichlet.cuh).  The key walk is exact; the float bits are spec-to-confirm
     against a real jax (oracle/mz_oracle.c), so `dirichlet_noise=` stays the way to inject an exact array."""
     import ctypes as C
-
-    from . import _lib
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("muax_amd draws the root noise on the GPU (there is no CPU search path)")
@@ -100,7 +99,7 @@ class MuZero:
             self.dy_func = None
         else:
             self.repr_func, self.pred_func, self.dy_func = self.network
-        self._last_route = None  # stochastic act(): "hip_stochastic_mlp" or "callables"
+        self._last_route = None  # of the last act(): "fused_host", "fused", "stepwise"; "hip_stochastic_mlp", "callables"
         self._policy = policy_class()
         self._optimizer = optimizer
         self.loss_fn = loss_fn
@@ -268,41 +267,6 @@ class MuZero:
             discount = torch.ones_like(r) * self._discount
         return (r, discount, logits, v), next_embedding
 
-    def _with_jit(self, A, E, S, call, handle=None, gumbel=False):
-        """call() -- a fused act(); when the library has no instance of the kernel for this shape, build one on demand
-        (muax_amd/_jit.py: one translation unit, cached on disk, planned for the policy class `gumbel` names) and call
-        again; a shape outside the kernel's limits (more than 16 actions, more than 255 simulations, embeddings wider than
-        64) switches `handle` to the library's wide-action kernel (17..64 actions: mzs_mlp_allow_wide for the MuZero
-        policy, mzs_mlp_allow_wide_gumbel for the Gumbel policy; MUAX_AMD_WIDE=0 skips both) or its generic one-launch
-        search (mzs_mlp_allow_generic).  Re-raises the
-        ValueError when neither applies: the caller then runs the step-wise path with the torch modules."""
-        try:
-            return call()
-        except ValueError as e:
-            if "no fused kernel instance" not in str(e):
-                raise
-            from . import _jit
-            if _jit.ensure_instance(A, E, 2 * self._support_size + 1, S, gumbel=gumbel):
-                return call()
-            tail = _jit.build_log_tail()
-            if tail and _jit.last_build_log not in MuZero._warned_stepwise:  # a compiler was there and the build FAILED: say so
-                MuZero._warned_stepwise.add(_jit.last_build_log)
-                import warnings
-                warnings.warn(f"muax_amd: the on-demand build of a fused act() instance for num_actions={A}, embedding_dim="
-                              f"{E}, num_simulations={S} failed; compiler log {_jit.last_build_log}:\n{tail}",
-                              RuntimeWarning, stacklevel=3)
-            # outside the fused kernel's limits (or no compiler): the wide-action kernel of the library (17..64 actions,
-            # either policy; tried first) and its generic one-launch search, which takes what the wide kernel declines
-            wide = os.environ.get("MUAX_AMD_WIDE", "1") != "0"
-            generic = os.environ.get("MUAX_AMD_GENERIC", "1") != "0"
-            if handle is None or not (wide or generic):
-                raise
-            if wide:
-                handle.allow_wide(gumbel=gumbel)
-            if generic:
-                handle.allow_generic()
-            return call()  # (a ValueError of this call -- both routes declined -- sends the caller to the step-wise path)
-
     def _native_loop(self, root):
         """The one-launch simulation loop, when the nets are ones the library evaluates itself (the reference's ResNet
         nets with the prediction net on the child's embedding): a callable for MuZeroSearch.search, else None."""
@@ -314,40 +278,102 @@ class MuZero:
         return lambda handle, b, e: dy.hip_search(self.pred_func, handle, self._support_size, self._discount, b, e)
 
     # ------------------------------------------------------------------ act
-    def _fused_handle(self, B, A, E, obs_dim, S, max_depth, pb_c_init, pb_c_base, tiebreak, policy="muzero",
-                      qtransform="qtransform_by_parent_and_siblings", max_considered=16, gumbel_scale=1.0,
-                      global_batch=None, root_offset=0):
-        """The MuZeroSearch handle of this act() configuration: created once (mzs_create + its device buffers);
-        a new weights version only re-binds the weight pointers (mzs_mlp_set_weights), it does not re-create the
-        handle -- no allocation on the update()-then-act() cycle of fit()."""
-        key = (B, A, E, obs_dim, S, max_depth, pb_c_init, pb_c_base, tiebreak, policy, qtransform, max_considered,
-               gumbel_scale, global_batch, root_offset)
+    def _device_obs(self, obs):
+        """Observations as a float32 tensor on the model's device: what the torch modules take."""
+        return obs if isinstance(obs, torch.Tensor) and obs.device == self.device \
+            else torch.as_tensor(obs, dtype=torch.float32).to(self.device)
+
+    def _root_noise(self, key, noise, fraction, alpha, obs, A, global_batch, root_offset):
+        """mctx.muzero_policy's root noise [B, A] for the roots `obs`: `noise` when the caller gave one (or switched the
+        noise off), else rows [root_offset, root_offset + B) of the global batch's Dirichlet draw -- a shard draws exactly
+        its rows, results do not depend on the split.  A = None: one row through the plugin nets tells the width."""
+        if noise is not None or not fraction:
+            return noise
+        B = obs.shape[0]
+        if A is None:
+            with torch.no_grad():
+                A = self.pred_func(self.repr_func(self._device_obs(obs[:1])))[1].shape[-1]
+        k_dir = prng.split(key, 3)[1]  # mctx: rng_key, dirichlet_rng_key, search_rng_key = split(key, 3)
+        return _dirichlet(k_dir, alpha, (B, A), self.device, global_batch, root_offset)
+
+    def _handle(self, batch, cfg, bind, *more):
+        """The MuZeroSearch handle of an act() configuration, cached under (batch, cfg, *more); `cfg`: SearchConfig's
+        arguments in the order of its fields.  Created once (mzs_create + its device buffers); a new weights version
+        only re-binds the weight pointers (`bind(handle, *more)`), it does not re-create the handle -- no allocation on the
+        update()-then-act() cycle of fit()."""
+        key = (batch, cfg) + more
         h = self._fused.get(key)
         if h is None:
-            s = MuZeroSearch(B, SearchConfig(A, S, E, max_depth=max_depth, tiebreak=tiebreak,
-                                             pb_c_init=pb_c_init, pb_c_base=float(pb_c_base), policy=policy,
-                                             qtransform=qtransform, max_num_considered_actions=max_considered,
-                                             gumbel_scale=float(gumbel_scale), global_batch=global_batch,
-                                             root_offset=root_offset), self.device)
-            h = self._fused[key] = [s, None]
+            h = self._fused[key] = [MuZeroSearch(batch, SearchConfig(*cfg), self.device), None]
         if h[1] != self._weights_version:
-            w = {k: v.detach() for k, v in mz_nn.mlp_trio_weights(self.network).items()}
-            h[0].set_mlp_weights(w, obs_dim, self._support_size, self._discount, self._recurrent_pred_on)
+            bind(h[0], *more)
             h[1] = self._weights_version
         return h[0]
 
-    def _plan(self, params, rng_key, obs, num_simulations=5, temperature=1., invalid_actions=None,
-              max_depth=None, loop_fn=None, qtransform=None, dirichlet_fraction=0.25, dirichlet_alpha=0.3,
-              pb_c_init=1.25, pb_c_base=19652, dirichlet_noise=None, gumbel=None, tiebreak=True,
-              with_tree=False, max_num_considered_actions=16, gumbel_scale=1.0, global_batch=None, root_offset=0,
-              host_io=False):
-        """muax/model.py:222-243 -> (PolicyOutput, root value).  `host_io`: the caller gave host observations and
-        wants host results; the fused path then makes the whole round trip in one C call (mzs_act_mlp_host) and the
+    def _bind_trio(self, handle, obs_dim):
+        w = {k: v.detach() for k, v in mz_nn.mlp_trio_weights(self.network).items()}
+        handle.set_mlp_weights(w, obs_dim, self._support_size, self._discount, self._recurrent_pred_on)
+
+    def _act_fused(self, key, obs, host_io, gumbel, cfg, kw):
+        """One act() of the default MLP trio inside the library -> _route's record, or None.  `host_io`: the whole round
+        trip in one C call (mzs_act_mlp_host: staging, root-noise draw from the key, search, one download, sync; NumPy
+        results), else mzs_act_mlp on device tensors, results in the handle's buffers.  `cfg`: the handle's SearchConfig
+        arguments, (A, S, E, ...); `kw`: the call's keyword arguments; `gumbel`: the policy class.  When the library has no instance
+        of the fused kernel for the shape, build one on demand (muax_amd/_jit.py: one translation unit, cached on disk,
+        planned for the policy class) and call again; a shape outside that kernel's limits (more than 16 actions, more
+        than 255 simulations, embeddings wider than 64) switches the handle to the library's wide-action kernel (17..64
+        actions: mzs_mlp_allow_wide for the MuZero policy, mzs_mlp_allow_wide_gumbel for the Gumbel policy;
+        MUAX_AMD_WIDE=0 skips both) and its generic one-launch search (mzs_mlp_allow_generic; MUAX_AMD_GENERIC=0), which
+        takes what the wide kernel declines.  None when none of them takes the shape: the caller then runs the step-wise
+        path with the torch modules."""
+        A, S, E = cfg[:3]
+        B, obs_dim = obs.shape
+        h = self._handle(B, cfg, self._bind_trio, obs_dim)
+        call = h.act_mlp_host if host_io else h.act_mlp
+        try:
+            try:
+                out = call(obs, key, **kw)
+            except _lib.NoKernelInstance:
+                from . import _jit
+                if not _jit.ensure_instance(A, E, 2 * self._support_size + 1, S, gumbel=gumbel):
+                    tail = _jit.build_log_tail()
+                    if tail and _jit.last_build_log not in MuZero._warned_stepwise:  # a compiler was there and the build FAILED: say so
+                        MuZero._warned_stepwise.add(_jit.last_build_log)
+                        import warnings
+                        warnings.warn(f"muax_amd: the on-demand build of a fused act() instance for num_actions={A}, embedding_dim="
+                                      f"{E}, num_simulations={S} failed; compiler log {_jit.last_build_log}:\n{tail}",
+                                      RuntimeWarning, stacklevel=3)
+                    wide = os.environ.get("MUAX_AMD_WIDE", "1") != "0"
+                    generic = os.environ.get("MUAX_AMD_GENERIC", "1") != "0"
+                    if not (wide or generic):
+                        raise
+                    if wide:
+                        h.allow_wide(gumbel=gumbel)
+                    if generic:
+                        h.allow_generic()
+                out = call(obs, key, **kw)
+        except _lib.NoKernelInstance as e:
+            self._warn_stepwise(A, E, S, e)
+            return None
+        if host_io:
+            return PolicyOutput(out[0], out[1], None), out[2], None, "fused_host"
+        return out, h.root_value, h, "fused"
+
+    def _route(self, rng_key, obs, *, num_simulations=5, temperature=1., invalid_actions=None, max_depth=None,
+               loop_fn=None, qtransform=None, dirichlet_fraction=0.25, dirichlet_alpha=0.3, pb_c_init=1.25,
+               pb_c_base=19652, dirichlet_noise=None, gumbel=None, tiebreak=True, with_tree=False,
+               max_num_considered_actions=16, gumbel_scale=1.0, global_batch=None, root_offset=0,
+               host_io=False):
+        """One search of `obs` [B, ...] by the first route that takes it (the keywords and defaults of
+        muax/model.py:222-243) -> the record (PolicyOutput, the root's network value, the fused handle whose buffers
+        hold both -- they then come back in one copy -- or None, the route's name).  `host_io`: the caller gave host
+        observations and wants host results; the fused path then makes the whole round trip in one C call and the
         PolicyOutput holds NumPy arrays."""
         if self._params is None:
             raise ValueError("call init() first")
+        key = prng.as_key(rng_key)
         if self._stochastic:
-            return self._plan_stochastic(rng_key, obs, num_simulations, temperature, invalid_actions, max_depth, qtransform,
+            return self._plan_stochastic(key, obs, num_simulations, temperature, invalid_actions, max_depth, qtransform,
                                          dirichlet_fraction, dirichlet_alpha, pb_c_init, pb_c_base, dirichlet_noise, gumbel,
                                          tiebreak, with_tree, global_batch, root_offset)
         gumbel_policy = isinstance(self._policy, GumbelMuZeroPolicy)
@@ -357,87 +383,53 @@ class MuZero:
         if qtransform != "qtransform_by_parent_and_siblings" and not (
                 gumbel_policy and qtransform == "qtransform_completed_by_mix_value"):
             raise ValueError(f"qtransform {qtransform!r} is not implemented for this policy")
-        key = prng.as_key(rng_key)
-        B = obs.shape[0]
-        A = self.pred_func.num_actions if hasattr(self.pred_func, "num_actions") else None
-        fused_ok = mz_nn.is_default_mlp_trio(self.network) and obs.ndim == 2
-        self._last_fused = None  # the fused handle of this act(), if any (its outputs come back in one copy)
-        host_io = (host_io and fused_ok and not with_tree and gumbel is None and not isinstance(obs, torch.Tensor)
+        S, A = num_simulations, getattr(self.pred_func, "num_actions", None)
+        # the fused kernels: the default MLP trio under a policy of the library's own -- a user subclass never
+        fused = mz_nn.is_default_mlp_trio(self.network) and obs.ndim == 2 \
+            and type(self._policy) is (GumbelMuZeroPolicy if gumbel_policy else MuZeroPolicy)
+        host_io = (host_io and fused and not with_tree and gumbel is None and not isinstance(obs, torch.Tensor)
                    and not isinstance(dirichlet_noise, torch.Tensor) and not isinstance(invalid_actions, torch.Tensor))
-        if gumbel_policy and fused_ok and type(self._policy) is GumbelMuZeroPolicy:
-            try:
-                h = self._fused_handle(B, A, self.repr_func.embedding_dim, obs.shape[1], num_simulations, max_depth,
-                                       1.25, 19652, False, "gumbel", qtransform, max_num_considered_actions,
-                                       gumbel_scale, global_batch, root_offset)
-                E_ = self.repr_func.embedding_dim
-                if host_io:
-                    a_, w_, v_ = self._with_jit(A, E_, num_simulations, lambda: h.act_mlp_host(
-                        obs, key, dirichlet_fraction=0.0, invalid_actions=invalid_actions), h, gumbel=True)
-                    return PolicyOutput(a_, w_, None), v_
-                out = self._with_jit(A, E_, num_simulations, lambda: h.act_mlp(
-                    obs, key, invalid_actions=invalid_actions, gumbel=gumbel, with_tree=with_tree), h, gumbel=True)
-                self._last_fused = h
-                return out, h.root_value
-            except ValueError as e:
-                if "no fused kernel instance" not in str(e):
-                    raise
-                self._warn_stepwise(A, self.repr_func.embedding_dim, num_simulations, e)
-        def device_obs():  # plugin nets (and the step-wise fall-back) run on device tensors
-            return obs if isinstance(obs, torch.Tensor) and obs.device == self.device \
-                else torch.as_tensor(obs, dtype=torch.float32).to(self.device)
-
-        if gumbel_policy:
-            root = self._root_inference(params, key, device_obs())
-            out = self._checked_search(lambda: self._policy(
-                params, key, root, self._recurrent_inference, num_simulations=num_simulations,
-                invalid_actions=invalid_actions, max_depth=max_depth, qtransform=qtransform,
-                max_num_considered_actions=max_num_considered_actions, gumbel_scale=gumbel_scale,
-                gumbel=gumbel, with_tree=with_tree, graph=self.capture_graph, graph_version=self._weights_version,
-                global_batch=global_batch, root_offset=root_offset, native_loop=self._native_loop(root)))
-            return out, root[1]
-        if host_io and type(self._policy) is MuZeroPolicy:
-            try:  # NumPy in, NumPy out: one C call (staging, root-noise draw from the key, search, one download, sync)
-                h = self._fused_handle(B, A, self.repr_func.embedding_dim, obs.shape[1], num_simulations, max_depth,
-                                       pb_c_init, pb_c_base, tiebreak, global_batch=global_batch, root_offset=root_offset)
-                a_, w_, v_ = self._with_jit(A, self.repr_func.embedding_dim, num_simulations, lambda: h.act_mlp_host(
-                    obs, key, dirichlet_noise=dirichlet_noise, dirichlet_fraction=dirichlet_fraction,
-                    dirichlet_alpha=dirichlet_alpha, invalid_actions=invalid_actions, temperature=temperature), h)
-                return PolicyOutput(a_, w_, None), v_
-            except ValueError as e:
-                if "no fused kernel instance" not in str(e):
-                    raise
-        if dirichlet_noise is None and dirichlet_fraction:
-            k_dir = prng.split(key, 3)[1]  # mctx: rng_key, dirichlet_rng_key, search_rng_key = split(key, 3)
-            if A is None:
-                with torch.no_grad():
-                    A = self.pred_func(self.repr_func(torch.as_tensor(obs[:1], dtype=torch.float32).to(self.device)))[1].shape[-1]
-            # a shard draws exactly its rows of the whole batch's noise: results do not depend on the split
-            dirichlet_noise = _dirichlet(k_dir, dirichlet_alpha, (B, A), self.device, global_batch, root_offset)
-        if fused_ok and type(self._policy) is MuZeroPolicy:
+        if not (gumbel_policy or host_io):  # (the host round trip draws its noise inside the C call)
+            dirichlet_noise = self._root_noise(key, dirichlet_noise, dirichlet_fraction, dirichlet_alpha, obs, A,
+                                               global_batch, root_offset)
+        if fused:
             E = self.repr_func.embedding_dim
-            try:
-                h = self._fused_handle(B, A, E, obs.shape[1], num_simulations, max_depth, pb_c_init, pb_c_base,
-                                       tiebreak, global_batch=global_batch, root_offset=root_offset)
-                out = self._with_jit(A, E, num_simulations, lambda: h.act_mlp(
-                    obs, key, dirichlet_noise=dirichlet_noise, dirichlet_fraction=dirichlet_fraction,
-                    invalid_actions=invalid_actions, temperature=temperature, gumbel=gumbel, with_tree=with_tree), h)
-                self._last_fused = h
-                return out, h.root_value
-            except ValueError as e:
-                if "no fused kernel instance" not in str(e):
-                    raise
-                self._warn_stepwise(A, E, num_simulations, e)
-        root = self._root_inference(params, key, device_obs())
+            if gumbel_policy:  # (no pUCT constants, no tie-break noise, no root noise, no temperature in this policy)
+                cfg = (A, S, E, max_depth, False, 1.25, 19652.0, global_batch, root_offset, "gumbel", qtransform,
+                       max_num_considered_actions, float(gumbel_scale))
+                kw = dict(dirichlet_fraction=0.0, invalid_actions=invalid_actions) if host_io else \
+                    dict(invalid_actions=invalid_actions, gumbel=gumbel, with_tree=with_tree)
+            else:
+                cfg = (A, S, E, max_depth, tiebreak, pb_c_init, float(pb_c_base), global_batch, root_offset)
+                kw = dict(dirichlet_noise=dirichlet_noise, dirichlet_fraction=dirichlet_fraction,
+                          dirichlet_alpha=dirichlet_alpha, invalid_actions=invalid_actions,
+                          temperature=temperature) if host_io else \
+                    dict(dirichlet_noise=dirichlet_noise, dirichlet_fraction=dirichlet_fraction,
+                         invalid_actions=invalid_actions, temperature=temperature, gumbel=gumbel, with_tree=with_tree)
+            served = self._act_fused(key, obs, host_io, gumbel_policy, cfg, kw)
+            if served is not None:
+                return served
+        # the step-wise kernels, the torch modules between them: plugin nets, user policies, shapes the library declined
+        if gumbel_policy:
+            policy_kw = dict(qtransform=qtransform, max_num_considered_actions=max_num_considered_actions,
+                             gumbel_scale=gumbel_scale)
+        else:
+            policy_kw = dict(temperature=temperature, dirichlet_fraction=dirichlet_fraction, pb_c_init=pb_c_init,
+                             pb_c_base=pb_c_base, tiebreak=tiebreak,
+                             dirichlet_noise=self._root_noise(key, dirichlet_noise, dirichlet_fraction, dirichlet_alpha,
+                                                              obs, A, global_batch, root_offset))
+        root = self._root_inference(self._params, key, self._device_obs(obs))
+        out = self._checked_search(lambda: self._policy(
+            self._params, key, root, self._recurrent_inference, num_simulations=S, invalid_actions=invalid_actions,
+            max_depth=max_depth, gumbel=gumbel, with_tree=with_tree, graph=self.capture_graph,
+            graph_version=self._weights_version, global_batch=global_batch, root_offset=root_offset,
+            native_loop=self._native_loop(root), **policy_kw))
+        return out, root[1], None, "stepwise"
 
-        def run():
-            return self._policy(params, key, root, self._recurrent_inference, num_simulations=num_simulations,
-                                temperature=temperature, invalid_actions=invalid_actions, max_depth=max_depth,
-                                dirichlet_fraction=dirichlet_fraction, dirichlet_noise=dirichlet_noise,
-                                pb_c_init=pb_c_init, pb_c_base=pb_c_base, gumbel=gumbel, tiebreak=tiebreak,
-                                with_tree=with_tree, graph=self.capture_graph, graph_version=self._weights_version,
-                                global_batch=global_batch, root_offset=root_offset, native_loop=self._native_loop(root))
-
-        return self._checked_search(run), root[1]
+    def _plan(self, params, rng_key, obs, **settings):
+        """muax/model.py:222-243 -> (PolicyOutput, root value); `settings`: _route's keywords."""
+        out, root_value, _, self._last_route = self._route(rng_key, obs, **settings)
+        return out, root_value
 
     # ------------------------------------------------------------------ Stochastic MuZero (SMZNetwork)
     def _decision_inference(self, params, rng_key, action, embedding):
@@ -457,55 +449,38 @@ class MuZero:
             v = mx_utils.support_to_scalar(torch.softmax(v, dim=-1), self._support_size).flatten()
         return ChanceRecurrentFnOutput(logits, v, r, torch.full_like(r, self._discount)), s
 
-    def _stochastic_handle(self, B, A, Cn, E, S, max_depth, pb_c_init, pb_c_base, tiebreak, global_batch, root_offset):
-        """The search handle of this stochastic act() configuration with the default family's weights bound: created once,
-        the weights re-bound when their version changed (update(), weights_changed())."""
-        key = ("stochastic", B, A, Cn, E, S, max_depth, pb_c_init, pb_c_base, tiebreak, global_batch, root_offset)
-        h = self._fused.get(key)
-        if h is None:
-            s = MuZeroSearch(B, SearchConfig(A, S, E, max_depth=max_depth, tiebreak=tiebreak, pb_c_init=pb_c_init,
-                                             pb_c_base=float(pb_c_base), policy="stochastic", num_chance_outcomes=Cn,
-                                             global_batch=global_batch, root_offset=root_offset), self.device)
-            h = self._fused[key] = [s, None]
-        if h[1] != self._weights_version:
-            w = {k: v.detach() for k, v in mz_nn.stochastic_mlp_weights(self.network).items()}
-            h[0].set_stochastic_mlp_weights(w, self._support_size, self._discount)
-            h[1] = self._weights_version
-        return h[0]
+    def _bind_stochastic(self, handle):
+        w = {k: v.detach() for k, v in mz_nn.stochastic_mlp_weights(self.network).items()}
+        handle.set_stochastic_mlp_weights(w, self._support_size, self._discount)
 
-    def _plan_stochastic(self, rng_key, obs, num_simulations, temperature, invalid_actions, max_depth, qtransform,
+    def _plan_stochastic(self, key, obs, num_simulations, temperature, invalid_actions, max_depth, qtransform,
                          dirichlet_fraction, dirichlet_alpha, pb_c_init, pb_c_base, dirichlet_noise, gumbel, tiebreak,
                          with_tree, global_batch, root_offset):
-        """_plan for an SMZNetwork -> (PolicyOutput, root value): root inference on the torch modules, once; then the
-        search with the decision and the chance function evaluated by the library (the default stochastic MLP family on a
-        GPU, support_size 8..31: MuZeroSearch.search_stochastic_mlp; MUAX_AMD_STOCHASTIC_MLP=0 switches it off) or, for
-        plugin modules, by StochasticMuZeroPolicy on callables built from them.  `_last_route` names the route taken."""
+        """_route for an SMZNetwork: root inference on the torch modules, once; then the search with the decision and the
+        chance function evaluated by the library (the default stochastic MLP family on a GPU, support_size 8..31:
+        MuZeroSearch.search_stochastic_mlp; MUAX_AMD_STOCHASTIC_MLP=0 switches it off) or, for plugin modules, by
+        StochasticMuZeroPolicy on callables built from them."""
         qt = getattr(qtransform, "__name__", qtransform)
         if qt not in (None, "qtransform_by_parent_and_siblings"):
             raise ValueError(f"qtransform {qt!r} is not implemented for this policy")
-        key = prng.as_key(rng_key)
-        self._last_fused = None
-        obs_t = obs if isinstance(obs, torch.Tensor) and obs.device == self.device \
-            else torch.as_tensor(obs, dtype=torch.float32).to(self.device)
-        root = self._root_inference_eager(obs_t)
+        root = self._root_inference_eager(self._device_obs(obs))
         B, A = root[0].shape
         Cn = getattr(self.after_pred_func, "num_actions", None)
-        if dirichlet_noise is None and dirichlet_fraction:
-            k_dir = prng.split(key, 3)[1]  # mctx: rng_key, dirichlet_rng_key, search_rng_key = split(key, 3)
-            dirichlet_noise = _dirichlet(k_dir, dirichlet_alpha, (B, A), self.device, global_batch, root_offset)
+        dirichlet_noise = self._root_noise(key, dirichlet_noise, dirichlet_fraction, dirichlet_alpha, obs, A, global_batch,
+                                           root_offset)
         hip = (mz_nn.is_default_stochastic_mlp(self.network) and self.device.type == "cuda"
                and 8 <= self._support_size <= 31 and os.environ.get("MUAX_AMD_STOCHASTIC_MLP", "1") != "0")
         if hip:
-            h = self._stochastic_handle(B, A, Cn, root[2].shape[1], num_simulations, max_depth, pb_c_init, pb_c_base,
-                                        tiebreak, global_batch, root_offset)
+            h = self._handle(B, (A, num_simulations, root[2].shape[1], max_depth, tiebreak, pb_c_init, float(pb_c_base),
+                                 global_batch, root_offset, "stochastic", "qtransform_by_parent_and_siblings", 16, 1.0, Cn),
+                             self._bind_stochastic)
             out = h.search_stochastic_mlp(root, key=key, invalid_actions=invalid_actions, dirichlet_noise=dirichlet_noise,
                                           dirichlet_fraction=dirichlet_fraction, temperature=temperature, gumbel=gumbel,
                                           with_tree=with_tree, graph=self.capture_graph, graph_version=self._weights_version)
             t = out.search_tree
             if t is not None:  # the decision slice, as StochasticMuZeroPolicy returns it (mctx _mask_tree)
                 t = t._replace(**{f: getattr(t, f)[..., :A] for f in t._fields if f.startswith("children_")})
-            self._last_route = "hip_stochastic_mlp"
-            return PolicyOutput(out.action, out.action_weights, t), root[1]
+            return PolicyOutput(out.action, out.action_weights, t), root[1], None, "hip_stochastic_mlp"
         shapes = {} if Cn is None else dict(num_chance_outcomes=Cn, afterstate_shape=tuple(root[2].shape[1:]))
         out = self._policy(self._params, key, root, decision_recurrent_fn=self._decision_inference,
                            chance_recurrent_fn=self._chance_inference, num_simulations=num_simulations,
@@ -514,8 +489,7 @@ class MuZero:
                            pb_c_base=pb_c_base, gumbel=gumbel, tiebreak=tiebreak, with_tree=with_tree,
                            graph=self.capture_graph, graph_version=self._weights_version, global_batch=global_batch,
                            root_offset=root_offset, **shapes)
-        self._last_route = "callables"
-        return out, root[1]
+        return out, root[1], None, "callables"
 
     _warned_stepwise = set()
 
@@ -534,7 +508,7 @@ class MuZero:
                           f"simulations; the generic one-launch route is about 16x, the wide-action kernel for 17..64 actions, "
                           f"MuZero or Gumbel policy, less)"
                           + (f"; last failed on-demand build: {_jit_tail()}" if _jit_tail() else ""),
-                          RuntimeWarning, stacklevel=4)
+                          RuntimeWarning, stacklevel=5)  # (act <- _route <- _act_fused <- here)
 
     def _checked_search(self, run):
         """Run a step-wise search; if the ResNet recurrent kernel went through pair mode (two workgroups per
@@ -556,6 +530,26 @@ class MuZero:
             if getattr(dy, "_pair_scratch", None):  # the repeat must not have gone through pair mode again
                 raise RuntimeError("muax_amd: pair mode is still active after it was disabled")
         return out
+
+    @staticmethod
+    def _deliver(out, root_value, h, on_device):
+        """(action, action_weights, root_value) of _route's record as the caller wants them: device tensors of its own
+        (`on_device`: no sync) or NumPy arrays (one host sync, like the reference's np.asarray)."""
+        if isinstance(out.action, np.ndarray):  # the fused path's host round trip: results are already NumPy
+            return out.action, out.action_weights, root_value
+        if on_device:
+            # the search handle's output buffers are reused by the next act(): hand out copies (stream-ordered, no sync)
+            if h is not None:
+                return h.outputs_clone()  # one copy kernel instead of three
+            return out.action.clone(), out.action_weights.clone(), root_value.clone()
+        if h is not None:
+            # fused path, device inputs: the three outputs share one allocation -> one device-to-host copy, one sync
+            return h.outputs_to_host()
+        # one device-to-host copy instead of three (each costs a synchronisation): action, weights, value
+        B, A = out.action_weights.shape
+        host = torch.cat([out.action.to(torch.float32), out.action_weights.reshape(-1),
+                          root_value.reshape(-1).to(torch.float32)]).cpu().numpy()
+        return host[:B].astype(np.int32), host[B:B + B * A].reshape(B, A).copy(), host[B + B * A:].copy()
 
     def act(self, rng_key, obs, with_pi: bool = False, with_value: bool = False, obs_from_batch: bool = False,
             num_simulations: int = 5, temperature: float = 1., invalid_actions=None, max_depth: int = None,
@@ -584,38 +578,16 @@ class MuZero:
             obs = np.asarray(obs, dtype=np.float32)
             if not obs_from_batch:
                 obs = obs[None]
-        plan_output, root_value = self._plan(
-            self.params, rng_key, obs, num_simulations=num_simulations, temperature=temperature,
+        out, root_value, handle, self._last_route = self._route(
+            rng_key, obs, num_simulations=num_simulations, temperature=temperature,
             invalid_actions=invalid_actions, max_depth=max_depth, loop_fn=loop_fn, qtransform=qtransform,
             dirichlet_fraction=dirichlet_fraction, dirichlet_alpha=dirichlet_alpha, pb_c_init=pb_c_init,
             pb_c_base=pb_c_base, dirichlet_noise=dirichlet_noise, gumbel=gumbel, tiebreak=tiebreak,
             max_num_considered_actions=max_num_considered_actions, gumbel_scale=gumbel_scale,
             global_batch=global_batch, root_offset=root_offset, host_io=not (device_outputs and obs_from_batch))
-        if isinstance(plan_output.action, np.ndarray):  # the fused path's host round trip: results are already NumPy
-            action, weights = plan_output.action, plan_output.action_weights
-            if not obs_from_batch:
-                action, root_value = int(action[0]), float(root_value[0])
-        elif device_outputs and obs_from_batch:
-            # the search handle's output buffers are reused by the next act(): hand out copies (stream-ordered, no sync)
-            if self._last_fused is not None and getattr(self._last_fused, "_out", None) is not None:
-                action, weights, root_value = self._last_fused.outputs_clone()  # one copy kernel instead of three
-            else:
-                action, weights, root_value = plan_output.action.clone(), plan_output.action_weights.clone(), root_value.clone()
-        else:
-            if self._last_fused is not None:
-                # fused path, device inputs: the three outputs share one allocation -> one device-to-host copy, one sync
-                action, weights, root_value = self._last_fused.outputs_to_host()
-            else:
-                # one device-to-host copy instead of three (each costs a synchronisation): action, weights, value
-                A = plan_output.action_weights.shape[1]
-                B = plan_output.action.shape[0]
-                host = torch.cat([plan_output.action.to(torch.float32), plan_output.action_weights.reshape(-1),
-                                  root_value.reshape(-1).to(torch.float32)]).cpu().numpy()
-                action = host[:B].astype(np.int32)
-                weights = host[B:B + B * A].reshape(B, A).copy()
-                root_value = host[B + B * A:].copy()
-            if not obs_from_batch:
-                action, root_value = int(action[0]), float(root_value[0])  # weights keep their leading 1 (muax/model.py:176)
+        action, weights, root_value = self._deliver(out, root_value, handle, device_outputs and obs_from_batch)
+        if not obs_from_batch:
+            action, root_value = int(action[0]), float(root_value[0])  # weights keep their leading 1 (muax/model.py:176)
         if with_pi and with_value:
             return action, weights, root_value
         elif not with_pi and with_value:
@@ -675,15 +647,14 @@ class MuZero:
                 try:
                     loss, flat = self._fused_train(batch, divide_by_length=kwargs.get("divide_by_length", False),
                                                    sample_weight=sample_weight)
-                except ValueError as e:
+                except _lib.NoKernelInstance:
                     # a shape of the default trio the library lists no training instance for: build one on demand
                     # (muax_amd/_jit.py::ensure_train_instance, or ensure_wide_train_instance for 17 to 64 actions; once
                     # per shape, cached on disk) and call again
                     from . import _jit
                     ft = self._fused_train
                     shape = (ft.A, ft.E, 2 * ft.S + 1)
-                    if "no kernel instance" not in str(e) or not (_jit.ensure_train_instance(*shape)
-                                                                  or _jit.ensure_wide_train_instance(*shape)):
+                    if not (_jit.ensure_train_instance(*shape) or _jit.ensure_wide_train_instance(*shape)):
                         raise
                     loss, flat = ft(batch, divide_by_length=kwargs.get("divide_by_length", False),
                                     sample_weight=sample_weight)
@@ -691,10 +662,10 @@ class MuZero:
                     allreduce_mean_flat([flat])
                 for p, g in zip(self._fused_train.params, self._fused_train.views):
                     p.grad = g
-            except ValueError as e:
+            except (_lib.NoKernelInstance, _lib.TooLargeForLds):
                 # shapes the kernel cannot serve (no instance, or an unroll longer than its LDS keeps) take the
                 # torch route under backend="auto"; the kernel refuses them on the host, before any launch
-                if backend == "hip" or not any(m in str(e) for m in ("no kernel instance", "too large for the LDS")):
+                if backend == "hip":
                     raise
                 fused = False
         if not fused:

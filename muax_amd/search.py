@@ -568,9 +568,7 @@ class MuZeroSearch:
                 native_loop(self, 0, self.cfg.num_simulations)
                 if ev:
                     ev[1].record()
-            except ValueError as e:
-                if "cached decisions" not in str(e):
-                    raise
+            except _lib.NoCachedDecisions:
                 native_loop = None  # (trees beyond the cached-decision budget keep the per-simulation launches)
                 self._native_loop_unusable = True
                 do_root()  # select(0) above has already counted simulation 0's depth; the fall-back loop starts from the root again

@@ -223,6 +223,7 @@ def test_plugin_nets_go_through_stepwise_path_and_agree_with_fused():
               tiebreak=False, temperature=0.)
     a1, pi1, v1 = m.act(7, batch, **kw)
     a2, pi2, v2 = m2.act(7, batch, **kw)
+    assert m._last_route == "fused_host" and m2._last_route == "stepwise"
     assert np.allclose(v1, v2, rtol=2e-3, atol=2e-3)
     same = (pi1 == pi2).all(1)
     assert same.mean() > 0.9 and (a1[same] == a2[same]).all()

@@ -616,6 +616,7 @@ def test_model_act_above_the_fused_kernels_limits_takes_the_generic_route(oracle
         a, pi, v = m.act(2, obs, with_pi=True, with_value=True, obs_from_batch=True, num_simulations=S)
         assert a.shape == (10,) and np.allclose(pi.sum(1), 1, atol=1e-6) and np.allclose(pi * S, np.round(pi * S), atol=1e-4)
         assert len(m._policy._handles) == 0  # NOT through the step-wise policy adapter
+        assert m._last_route == "fused_host"
         w = {k: p.detach().cpu().numpy() for k, p in mx.nn.mlp_trio_weights(m.network).items()}
         mlp = oracle.Mlp(w, 4, 8, A, 21)
         noise = oracle.dirichlet(oracle.split([0, 2], 3)[1], 0.3, 10, A)
