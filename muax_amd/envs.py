@@ -34,8 +34,10 @@ import ctypes as C
 from types import SimpleNamespace
 
 import numpy as np
+import torch
 
-from . import prng
+from . import _lib, prng
+from ._call import device_index, raw_stream
 
 
 class _DeviceEnv:
@@ -47,9 +49,6 @@ class _DeviceEnv:
     _HOST_HINT = ""
 
     def __init__(self, n, max_episode_steps, seed=0, device=None):
-        import torch
-
-        from . import _lib
         dev = self._open(n, max_episode_steps, device)
         self._state = torch.zeros((self.n, self._STATE_DIM), dtype=torch.float64, device=dev)
         key = prng.PRNGKey(seed)
@@ -61,19 +60,15 @@ class _DeviceEnv:
     def _open(self, n, max_episode_steps, device):
         """The checks and tensors of every descriptor: n, spec, device, the library, t, draws, obs and the host
         protocol's outputs.  Returns the device."""
-        import torch
-
-        from . import _lib
         name = type(self).__name__
         self.n = int(n)
         if self.n < 1 or int(max_episode_steps) < 1:
             raise ValueError(f"{name}: n and max_episode_steps must be at least 1")
         self.spec = SimpleNamespace(id=self._ID, max_episode_steps=int(max_episode_steps))
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.device = torch.device("cuda" if device is None else device)
         if self.device.type != "cuda":
             raise ValueError(f"{name}: needs a GPU device{self._HOST_HINT}")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device("cuda", device_index(self.device))
         self._L = _lib.load()
         dev = self.device
         self._t = torch.zeros(self.n, dtype=torch.int32, device=dev)
@@ -84,10 +79,7 @@ class _DeviceEnv:
         return dev
 
     def _stream(self):
-        import torch
-        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        return C.c_void_p(raw(self.device.index) if raw is not None
-                          else torch.cuda.current_stream(self.device).cuda_stream)
+        return raw_stream(self.device.index)
 
     def _view(self, x, dtype, name):
         if x.dtype != dtype or x.device != self.device or tuple(x.shape) != (self.n,) or not x.is_contiguous():
@@ -96,14 +88,10 @@ class _DeviceEnv:
 
     # ---- the device protocol
     def reset_device(self):
-        from . import _lib
         _lib.check(getattr(self._L, self._RESET)(C.byref(self._env), self._obs.data_ptr(), self._stream()))
         return self._obs
 
     def step_device(self, a, r_out, done_out):
-        import torch
-
-        from . import _lib
         s = _lib.args(_lib.MzsEnvStepArgs)  # (per step: fields by attribute, which is 1 us cheaper)
         s.a = self._view(a, torch.int32, "a")
         s.r_out, s.done_out = self._view(r_out, torch.float64, "r_out"), self._view(done_out, torch.uint8, "done_out")
@@ -116,7 +104,6 @@ class _DeviceEnv:
         return self.reset_device().cpu().numpy()
 
     def step(self, actions):
-        import torch
         a = torch.from_numpy(np.ascontiguousarray(np.asarray(actions).reshape(-1), dtype=np.int32)).to(self.device)
         obs = self.step_device(a, self._r, self._done)
         return obs.cpu().numpy(), self._r.cpu().numpy(), self._done.cpu().numpy().astype(bool)
@@ -177,9 +164,6 @@ class Device2048(_DeviceEnv):
     _ID, obs_dim, num_actions = "2048", 16, 4
 
     def __init__(self, n, max_episode_steps=2000, seed=0, reward_shift=0, device=None):
-        import torch
-
-        from . import _lib
         self.reward_shift = int(reward_shift)
         if not 0 <= self.reward_shift <= 11:
             raise ValueError("Device2048: reward_shift must be in 0..11")
@@ -202,9 +186,6 @@ class Device2048(_DeviceEnv):
         """The mask of observations [B, 16] (a float32 device tensor, e.g. stored ones) as a new uint8 [B, 4] device
         tensor: one launch of `mzs_env_2048_mask` on the current stream, no synchronisation.  An all-zero row (the
         padding of a reanalysis chunk) reports every move as legal."""
-        import torch
-
-        from . import _lib
         if not isinstance(obs, torch.Tensor) or obs.device != self.device or obs.dtype != torch.float32 \
                 or obs.ndim != 2 or obs.shape[1] != self.obs_dim or obs.shape[0] < 1:
             raise ValueError(f"invalid_actions_of: obs must be a float32 [B >= 1, {self.obs_dim}] tensor on {self.device}")

@@ -22,6 +22,7 @@ from . import _lib
 from . import nn as mz_nn
 from . import prng
 from . import utils as mx_utils
+from ._call import capture, device_index, raw_stream
 from .nn import MZNetwork, MZNetworkParams, SMZNetwork, SMZNetworkParams
 from .optimizers import optimizer  # noqa: F401  (the README's `muax.model.optimizer(...)`)
 from .policy import GumbelMuZeroPolicy, MuZeroPolicy, Policy, StochasticMuZeroPolicy
@@ -41,13 +42,12 @@ def _dirichlet(key_words, alpha: float, shape, device, global_batch=None, root_o
         raise RuntimeError("muax_amd draws the root noise on the GPU (there is no CPU search path)")
     B, A = shape
     kw = (C.c_uint32 * 2)(int(key_words[0]) & 0xFFFFFFFF, int(key_words[1]) & 0xFFFFFFFF)
-    idx = device.index if device.index is not None else torch.cuda.current_device()
+    idx = device_index(device)
     device = torch.device("cuda", idx)  # ONE ordinal for the buffer, the stream and the launch
     out = torch.empty(B, A, dtype=torch.float32, device=device)
     with torch.cuda.device(device):
         _lib.check(_lib.load().mzs_dirichlet(idx, C.byref(kw), float(alpha), B, A, global_batch or B,
-                                             root_offset, out.data_ptr(),
-                                             C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+                                             root_offset, out.data_ptr(), raw_stream(idx)))
     return out
 
 
@@ -226,7 +226,7 @@ class MuZero:
                         self._root_inference_eager(static_in)
                 cur.wait_stream(side)
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with capture(g):
                     out = self._root_inference_eager(static_in)
                 ent = self._root_graphs[key] = (g, static_in, out)
                 self._root_graph_lru.append(key)

@@ -9,12 +9,16 @@ through the step-wise search path.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import os
 from typing import Callable, NamedTuple, Optional
 
 import torch
 from torch import nn
+
+from . import _lib
+from ._call import device_index, launch, raw_stream
 
 HIDDEN = 16  # hk.Linear(16) in every default head (muax/nn.py:77,81,97,101)
 
@@ -316,6 +320,27 @@ def _same_pad(size: int, k: int, stride: int):
     return total // 2, total - total // 2
 
 
+def pack_conv3x3(w, cin_pad=None):
+    """An HWIO 3x3 kernel [3, 3, Cin, Cout] in the HIP kernels' order Wp[tap][c][g][co][i] = w[tap][16 c + 4 g + i][co]
+    (mz_conv.cuh), the input channels zero-padded to `cin_pad` (a multiple of 16; None: Cin is one already)."""
+    cin, cout = w.shape[2], w.shape[3]
+    w = w.detach().reshape(9, cin, cout)
+    if cin_pad and cin_pad != cin:
+        w = torch.cat([w, w.new_zeros(9, cin_pad - cin, cout)], dim=1)
+    return w.reshape(9, w.shape[1] // 16, 4, 4, cout).permute(0, 1, 2, 4, 3).contiguous()
+
+
+def _memo(owner, slot, params, build):
+    """`build()` as kept in owner.<slot>; built again (under no_grad) when one of `params` has moved or been written."""
+    sig = tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in params)
+    hit = getattr(owner, slot, None)
+    if hit is None or hit[0] != sig:
+        with torch.no_grad():
+            hit = (sig, build())
+        setattr(owner, slot, hit)
+    return hit[1]
+
+
 class HkConv2D(nn.Module):
     """hk.Conv2D(channels, kernel_shape, stride, padding='SAME', with_bias=False) on NHWC tensors;
     weight stored HWIO like haiku (w[kh][kw][in][out]), TruncatedNormal(1/sqrt(fan_in)) init."""
@@ -365,47 +390,22 @@ class HkConv2D(nn.Module):
     def _packed(self):
         """The HWIO kernel in the HIP kernels' order Wp[tap][c][g][co][i] = w[tap][16 c + 4 g + i][co] (fewer than 16 input
         channels: zero rows up to 16); rebuilt when the parameter changes."""
-        sig = (self.w.data_ptr(), self.w._version, self.w.device)
-        if getattr(self, "_pack_sig", None) != sig:
-            co, cin = self.out_channels, self.w.shape[2]
-            with torch.no_grad():
-                w = self.w.detach().reshape(9, cin, co)
-                if cin % 16:
-                    w = torch.cat([w, w.new_zeros(9, 16 - cin % 16, co)], dim=1)
-                self._pack = w.reshape(9, w.shape[1] // 16, 4, 4, co).permute(0, 1, 2, 4, 3).contiguous()
-            self._pack_sig = sig
-        return self._pack
+        return _memo(self, "_pack", [self.w], lambda: pack_conv3x3(self.w, -(-self.w.shape[2] // 16) * 16))
 
     def _conv_hip(self, x, in_div=None, relu=False):
-        import ctypes as C
-
-        from . import _lib
-        L = _lib.load()
-        xc = x.contiguous()
-        wp = self._packed()
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        xc, wp = x.contiguous(), self._packed()
+        B, H, W, cin = xc.shape
         if self.stride == 1:
             if in_div is not None:
                 xc = xc / in_div
             y = torch.empty_like(xc)
-            a = _lib.MzsConv3x3Args()
-            a.struct_size = C.sizeof(_lib.MzsConv3x3Args)
-            a.device = dev
-            a.batch, a.height, a.width, a.channels, a.relu = xc.shape[0], xc.shape[1], xc.shape[2], xc.shape[3], int(relu)
-            a.x, a.w_packed, a.y = xc.data_ptr(), wp.data_ptr(), y.data_ptr()
-            with torch.cuda.device(x.device):
-                _lib.check(L.mzs_conv3x3_nhwc(C.byref(a), stream))
+            launch("mzs_conv3x3_nhwc", _lib.MzsConv3x3Args, x.device, batch=B, height=H, width=W, channels=cin,
+                   relu=int(relu), x=xc.data_ptr(), w_packed=wp.data_ptr(), y=y.data_ptr())
             return y
-        y = torch.empty(xc.shape[0], -(-xc.shape[1] // 2), -(-xc.shape[2] // 2), self.out_channels, dtype=torch.float32, device=x.device)
-        a = _lib.MzsConv3x3sArgs()
-        a.struct_size = C.sizeof(_lib.MzsConv3x3sArgs)
-        a.device = dev
-        a.batch, a.height, a.width, a.in_channels, a.out_channels = xc.shape[0], xc.shape[1], xc.shape[2], xc.shape[3], self.out_channels
-        a.relu, a.in_div = int(relu), float(in_div) if in_div is not None else 0.0
-        a.x, a.w_packed, a.y = xc.data_ptr(), wp.data_ptr(), y.data_ptr()
-        with torch.cuda.device(x.device):
-            _lib.check(L.mzs_conv3x3_stride2_nhwc(C.byref(a), stream))
+        y = torch.empty(B, -(-H // 2), -(-W // 2), self.out_channels, dtype=torch.float32, device=x.device)
+        launch("mzs_conv3x3_stride2_nhwc", _lib.MzsConv3x3sArgs, x.device, batch=B, height=H, width=W, in_channels=cin,
+               out_channels=self.out_channels, relu=int(relu), in_div=float(in_div) if in_div is not None else 0.0,
+               x=xc.data_ptr(), w_packed=wp.data_ptr(), y=y.data_ptr())
         return y
 
     def scaled(self, x, in_div=None, relu=False):
@@ -447,11 +447,8 @@ class HkConv2D(nn.Module):
         kernel); rebuilt when the parameter changes, differentiable view while training."""
         if torch.is_grad_enabled() and self.w.requires_grad:
             return self.w.permute(3, 2, 0, 1)
-        sig = (self.w.data_ptr(), self.w._version, self.w.dtype, self.w.device)
-        if getattr(self, "_oihw_sig", None) != sig:
-            self._oihw_cache = self.w.detach().permute(3, 2, 0, 1).contiguous(memory_format=torch.channels_last)
-            self._oihw_sig = sig
-        return self._oihw_cache
+        return _memo(self, "_oihw_cache", [self.w],
+                     lambda: self.w.detach().permute(3, 2, 0, 1).contiguous(memory_format=torch.channels_last))
 
 
 class HkLayerNorm(nn.Module):
@@ -516,28 +513,20 @@ def ln_act(x, ln: "HkLayerNorm", relu: bool = False, add_ln=None, residual=None)
         if residual is not None:
             y = residual + y
         return torch.relu(y) if relu else y
-    import ctypes as C
-
-    from . import _lib
-    L = _lib.load()
     B, n = x.shape[0], x[0].numel()
     xs = [x.contiguous()]
-    a = _lib.MzsLayerNormArgs()
-    a.struct_size = C.sizeof(_lib.MzsLayerNormArgs)
-    a.device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    a.batch, a.n, a.channels, a.relu, a.eps = B, n, x.shape[-1], int(relu), 1e-5
-    a.x, a.scale, a.offset = xs[0].data_ptr(), ln.scale.data_ptr(), ln.offset.data_ptr()
+    more = {}
     if add_ln is not None:
         xs.append(add_ln[0].contiguous())
-        a.x2, a.scale2, a.offset2 = xs[1].data_ptr(), add_ln[1].scale.data_ptr(), add_ln[1].offset.data_ptr()
+        more.update(x2=xs[1].data_ptr(), scale2=add_ln[1].scale.data_ptr(), offset2=add_ln[1].offset.data_ptr())
     if residual is not None:
         xs.append(residual.contiguous())
-        a.residual = xs[-1].data_ptr()
+        more["residual"] = xs[-1].data_ptr()
     y = torch.empty_like(xs[0])
-    ws = torch.empty(L.mzs_layernorm_workspace_bytes(B, n) // 8, dtype=torch.float64, device=x.device)
-    a.y, a.workspace, a.workspace_bytes = y.data_ptr(), ws.data_ptr(), ws.numel() * 8
-    with torch.cuda.device(x.device):
-        _lib.check(L.mzs_layernorm_act(C.byref(a), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+    ws = torch.empty(_lib.load().mzs_layernorm_workspace_bytes(B, n) // 8, dtype=torch.float64, device=x.device)
+    launch("mzs_layernorm_act", _lib.MzsLayerNormArgs, x.device, batch=B, n=n, channels=x.shape[-1], relu=int(relu),
+           eps=1e-5, x=xs[0].data_ptr(), scale=ln.scale.data_ptr(), offset=ln.offset.data_ptr(), y=y.data_ptr(),
+           workspace=ws.data_ptr(), workspace_bytes=ws.numel() * 8, **more)
     return y
 
 
@@ -587,6 +576,24 @@ def avg_pool_same(x: torch.Tensor, window: int = 3, stride: int = 2) -> torch.Te
 _POOL_COUNTS = {}
 
 
+def _resblock_hip(entry, workspace_bytes, blk, x, proj=None):
+    """A residual block (conv_0, ln_0, conv_1, ln_1 of `blk`; `proj` = (conv, LayerNorm) of a projected shortcut) on a
+    dense NHWC `x` as one C call of `entry`, its fp64-typed workspace sized by the library's `workspace_bytes`."""
+    B, H, W, c = x.shape
+    keep, more = [blk.conv_0._packed(), blk.conv_1._packed()], {}
+    if proj:
+        keep.append(proj[0]._packed())
+        more = dict(w_proj=keep[2].data_ptr(), proj_scale=proj[1].scale.data_ptr(), proj_offset=proj[1].offset.data_ptr())
+    y = torch.empty_like(x)
+    ws = torch.empty(getattr(_lib.load(), workspace_bytes)(B, H, W, c) // 8, dtype=torch.float64, device=x.device)
+    launch(entry, _lib.MzsResblockArgs, x.device, batch=B, height=H, width=W, channels=c, eps=1e-5, x=x.data_ptr(),
+           w0=keep[0].data_ptr(), w1=keep[1].data_ptr(), ln0_scale=blk.ln_0.scale.data_ptr(),
+           ln0_offset=blk.ln_0.offset.data_ptr(), ln1_scale=blk.ln_1.scale.data_ptr(),
+           ln1_offset=blk.ln_1.offset.data_ptr(), y=y.data_ptr(), workspace=ws.data_ptr(),
+           workspace_bytes=ws.numel() * 8, **more)
+    return y
+
+
 class ResidualConvBlockV1(nn.Module):
     """muax/nn.py:118-148: conv-LN-relu-conv-LN, (projected) shortcut, relu."""
 
@@ -612,28 +619,8 @@ class ResidualConvBlockV1(nn.Module):
         return all(ln.scale is not None and ln.fused_ok(x) for ln in lns)
 
     def _forward_hip(self, x):
-        import ctypes as C
-
-        from . import _lib
-        L = _lib.load()
-        B, H, W, Cc = x.shape
-        a = _lib.MzsResblockArgs()
-        a.struct_size = C.sizeof(_lib.MzsResblockArgs)
-        a.device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        a.batch, a.height, a.width, a.channels, a.eps = B, H, W, Cc, 1e-5
-        keep = [self.conv_0._packed(), self.conv_1._packed()]
-        a.x, a.w0, a.w1 = x.data_ptr(), keep[0].data_ptr(), keep[1].data_ptr()
-        if self.use_projection:
-            keep.append(self.proj_conv._packed())
-            a.w_proj, a.proj_scale, a.proj_offset = keep[2].data_ptr(), self.proj_ln.scale.data_ptr(), self.proj_ln.offset.data_ptr()
-        a.ln0_scale, a.ln0_offset = self.ln_0.scale.data_ptr(), self.ln_0.offset.data_ptr()
-        a.ln1_scale, a.ln1_offset = self.ln_1.scale.data_ptr(), self.ln_1.offset.data_ptr()
-        y = torch.empty_like(x)
-        ws = torch.empty(L.mzs_resblock_workspace_bytes(B, H, W, Cc) // 8, dtype=torch.float64, device=x.device)
-        a.y, a.workspace, a.workspace_bytes = y.data_ptr(), ws.data_ptr(), ws.numel() * 8
-        with torch.cuda.device(x.device):
-            _lib.check(L.mzs_resblock_v1(C.byref(a), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
-        return y
+        return _resblock_hip("mzs_resblock_v1", "mzs_resblock_workspace_bytes", self, x,
+                             (self.proj_conv, self.proj_ln) if self.use_projection else None)
 
     def forward(self, x):
         # ln_act = the torch expressions in training / on the CPU, one fused HIP call per chain in GPU inference
@@ -671,25 +658,7 @@ class ResidualConvBlockV2(nn.Module):
         return all(ln.scale is not None and ln.fused_ok(x) for ln in (self.ln_0, self.ln_1))
 
     def _forward_hip(self, x):
-        import ctypes as C
-
-        from . import _lib
-        L = _lib.load()
-        B, H, W, Cc = x.shape
-        a = _lib.MzsResblockArgs()
-        a.struct_size = C.sizeof(_lib.MzsResblockArgs)
-        a.device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        a.batch, a.height, a.width, a.channels, a.eps = B, H, W, Cc, 1e-5
-        keep = [self.conv_0._packed(), self.conv_1._packed()]
-        a.x, a.w0, a.w1 = x.data_ptr(), keep[0].data_ptr(), keep[1].data_ptr()
-        a.ln0_scale, a.ln0_offset = self.ln_0.scale.data_ptr(), self.ln_0.offset.data_ptr()
-        a.ln1_scale, a.ln1_offset = self.ln_1.scale.data_ptr(), self.ln_1.offset.data_ptr()
-        y = torch.empty_like(x)
-        ws = torch.empty(L.mzs_resblock_v2_workspace_bytes(B, H, W, Cc) // 8, dtype=torch.float64, device=x.device)
-        a.y, a.workspace, a.workspace_bytes = y.data_ptr(), ws.data_ptr(), ws.numel() * 8
-        with torch.cuda.device(x.device):
-            _lib.check(L.mzs_resblock_v2(C.byref(a), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
-        return y
+        return _resblock_hip("mzs_resblock_v2", "mzs_resblock_v2_workspace_bytes", self, x)
 
     def forward(self, x):
         if self._hip_ok(x):
@@ -710,6 +679,29 @@ def _head(conv_channels, n_convs, hidden, out, gen):
     for _ in range(n_convs):
         layers += [HkConv2D(conv_channels, 1, 1, generator=gen), nn.ReLU()]
     return _Seq(*layers, nn.Flatten(1), LazyHkLinear(hidden, generator=gen), nn.ReLU(), LazyHkLinear(out, generator=gen))
+
+
+def _head_arrays(seq, convs, hidden, out):
+    """The arrays of a built `_head` in the C structs' order -- the 1x1 conv weights, then l1.w, l1.b, l2.w, l2.b -- or
+    None when `seq` is not that head: `convs` the (in, out) channels of its convolutions, `hidden` and `out` the widths
+    of its two biased linear layers, the first on the flattened 6 x 6 map of the last convolution.  (The kernels' map is
+    6 x 6 and the conv channels are checked, so the first layer's input width was determined before it was checked.)"""
+    ws = [m for m in seq if isinstance(m, HkConv2D)]
+    ls = [m for m in seq if isinstance(m, LazyHkLinear)]
+    if not (len(ws) == len(convs) and len(ls) == 2 and all(m.w is not None for m in ws + ls)
+            and all(m.with_bias for m in ls)
+            and [tuple(m.w.shape) for m in ws] == [(1, 1) + tuple(c) for c in convs]
+            and [tuple(m.w.shape) for m in ls] == [(36 * convs[-1][1], hidden), (hidden, out)]):
+        return None
+    return [m.w for m in ws] + [ls[0].w, ls[0].b, ls[1].w, ls[1].b]
+
+
+def _prediction_head_arrays(pred, support_size: int):
+    """The 11 head arrays of a ResNetPrediction at the widths the kernels are built for (64 -> 16 channels, hidden 16),
+    the value head first (MzsRootTailArgs.HEAD_FIELDS; the tail of MzsTowerArgs.HEAD_FIELDS), or None."""
+    v = _head_arrays(pred.v_func, [(64, 16), (16, 16)], 16, 2 * support_size + 1)
+    p = _head_arrays(pred.pi_func, [(64, 16)], 16, pred.num_actions)
+    return None if v is None or p is None else v + p
 
 
 class _LNReluHead(nn.Module):
@@ -790,6 +782,21 @@ class EZPrediction(nn.Module):
         return self.v_func(o), self.pi_func(o)
 
 
+def _ez_block_ok(b, c) -> bool:
+    """A built identity-shortcut V2 block of c -> c channels: what mzs_ez_recurrent evaluates."""
+    return (isinstance(b, ResidualConvBlockV2) and not b.use_projection and b.conv_0.w is not None
+            and b.conv_1.w is not None and tuple(b.conv_0.w.shape) == (3, 3, c, c)
+            and tuple(b.conv_1.w.shape) == (3, 3, c, c) and b.ln_0.scale is not None and b.ln_1.scale is not None)
+
+
+def _ez_head_ok(h, c, n) -> bool:
+    """A built _LNReluHead on a 6 x 6 x c map with n outputs."""
+    return (isinstance(h, _LNReluHead) and h.conv.w is not None and tuple(h.conv.w.shape) == (1, 1, c, 16)
+            and h.fc.w is not None and tuple(h.fc.w.shape) == (576, 32) and h.out.w is not None
+            and tuple(h.out.w.shape) == (32, n) and h.out.b is not None and h.ln_in.scale is not None
+            and h.ln_mid.scale is not None and h.ln_vec.scale is not None)
+
+
 class EZDynamic(nn.Module):
     """muax/nn.py:267-309: the RAW action index enters as one extra plane (no / num_actions here, unlike
     ResNetDynamic), one 3x3 convolution with a residual connection, one residual block, the reward head."""
@@ -822,51 +829,29 @@ class EZDynamic(nn.Module):
     # ---- HIP path of the whole recurrent_fn (mzs_ez_recurrent, muax_amd/csrc/mz_ez.cuh) ----
     use_hip_recurrent = True
 
-    @staticmethod
-    def _pack_conv(w, cin_pad=None):
-        """HWIO [3, 3, Cin, Cout] -> the kernels' Wp[tap][Cin / 16][g][Cout][i] = W[tap][16 c + 4 g + i][co]."""
-        cin, cout = w.shape[2], w.shape[3]
-        if cin_pad and cin_pad != cin:
-            w = torch.cat([w, w.new_zeros(3, 3, cin_pad - cin, cout)], dim=2)
-            cin = cin_pad
-        return w.reshape(9, cin // 16, 4, 4, cout).permute(0, 1, 2, 4, 3).contiguous()
-
     def _ez_packed(self, pred):
         blocks, heads = (self.block, pred.block), (self.r_func, pred.v_func, pred.pi_func)
-        ps = [self.ln_in.scale, self.ln_in.offset, self.conv.w] + [p for b in blocks for p in b.parameters()] \
-            + [p for h in heads for p in h.parameters()]
-        sig = tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in ps)
-        if getattr(self, "_ez_sig", None) != sig:
-            C_ = self.conv.out_channels
-            with torch.no_grad():
-                ln = lambda m: torch.stack([m.scale, m.offset]).contiguous()  # noqa: E731
-                pk = {"d_ln_in": ln(self.ln_in), "d_conv": self._pack_conv(self.conv.w, C_ + 16),
-                      "d_ln0": ln(self.block.ln_0), "d_conv0": self._pack_conv(self.block.conv_0.w),
-                      "d_ln1": ln(self.block.ln_1), "d_conv1": self._pack_conv(self.block.conv_1.w),
-                      "p_ln0": ln(pred.block.ln_0), "p_conv0": self._pack_conv(pred.block.conv_0.w),
-                      "p_ln1": ln(pred.block.ln_1), "p_conv1": self._pack_conv(pred.block.conv_1.w)}
-                for name, h in zip("rvp", heads):
-                    pk[name] = {"ln_in": ln(h.ln_in), "c1": h.conv.w.reshape(C_, 16).contiguous(), "ln_mid": ln(h.ln_mid),
-                                "fc": h.fc.w.detach().contiguous(), "ln_vec": ln(h.ln_vec),
-                                "out_w": h.out.w.detach().contiguous(), "out_b": h.out.b.detach().contiguous()}
-            self._ez_pack, self._ez_sig = pk, sig
-        return self._ez_pack
+
+        def build():
+            c = self.conv.out_channels
+            ln = lambda m: torch.stack([m.scale, m.offset]).contiguous()  # noqa: E731
+            pk = {"d_ln_in": ln(self.ln_in), "d_conv": pack_conv3x3(self.conv.w, c + 16),
+                  "d_ln0": ln(self.block.ln_0), "d_conv0": pack_conv3x3(self.block.conv_0.w),
+                  "d_ln1": ln(self.block.ln_1), "d_conv1": pack_conv3x3(self.block.conv_1.w),
+                  "p_ln0": ln(pred.block.ln_0), "p_conv0": pack_conv3x3(pred.block.conv_0.w),
+                  "p_ln1": ln(pred.block.ln_1), "p_conv1": pack_conv3x3(pred.block.conv_1.w)}
+            for name, h in zip("rvp", heads):
+                pk[name] = {"ln_in": ln(h.ln_in), "c1": h.conv.w.reshape(c, 16).contiguous(), "ln_mid": ln(h.ln_mid),
+                            "fc": h.fc.w.detach().contiguous(), "ln_vec": ln(h.ln_vec),
+                            "out_w": h.out.w.detach().contiguous(), "out_b": h.out.b.detach().contiguous()}
+            return pk
+        return _memo(self, "_ez_pack", [self.ln_in.scale, self.ln_in.offset, self.conv.w]
+                     + [p for m in blocks + heads for p in m.parameters()], build)
 
     def hip_recurrent(self, pred, s, a, support_size: int):
         """The whole recurrent_fn of muax/model.py:265-282 for the EZ nets in ONE HIP launch (mzs_ez_recurrent):
         returns (reward [B], value [B], prior_logits [B, A], next_state [B, 6, 6, C]), or None when the nets are not
         the shapes the kernel is built for (the caller then runs the torch modules)."""
-        def blk_ok(b, c):
-            return (isinstance(b, ResidualConvBlockV2) and not b.use_projection and b.conv_0.w is not None
-                    and b.conv_1.w is not None and tuple(b.conv_0.w.shape) == (3, 3, c, c)
-                    and tuple(b.conv_1.w.shape) == (3, 3, c, c) and b.ln_0.scale is not None and b.ln_1.scale is not None)
-
-        def head_ok(h, c, n):
-            return (isinstance(h, _LNReluHead) and h.conv.w is not None and tuple(h.conv.w.shape) == (1, 1, c, 16)
-                    and h.fc.w is not None and tuple(h.fc.w.shape) == (576, 32) and h.out.w is not None
-                    and tuple(h.out.w.shape) == (32, n) and h.out.b is not None and h.ln_in.scale is not None
-                    and h.ln_mid.scale is not None and h.ln_vec.scale is not None)
-
         F = 2 * support_size + 1
         if not (self.use_hip_recurrent and self.use_v2 and isinstance(pred, EZPrediction) and s.is_cuda
                 and s.dtype == torch.float32 and s.dim() == 4 and tuple(s.shape[1:3]) == (6, 6) and s.shape[3] in (32, 64)
@@ -875,13 +860,9 @@ class EZDynamic(nn.Module):
                 and pred.num_actions <= 64 and pred.num_actions == self.num_actions and pred.block is not None):
             return None  # (an inference-only entry point, like ResNetDynamic.hip_recurrent: no autograd through it)
         c = s.shape[3]
-        if not (blk_ok(self.block, c) and blk_ok(pred.block, c) and head_ok(self.r_func, c, F)
-                and head_ok(pred.v_func, c, F) and head_ok(pred.pi_func, c, pred.num_actions)):
+        if not (_ez_block_ok(self.block, c) and _ez_block_ok(pred.block, c) and _ez_head_ok(self.r_func, c, F)
+                and _ez_head_ok(pred.v_func, c, F) and _ez_head_ok(pred.pi_func, c, pred.num_actions)):
             return None
-        import ctypes as C
-
-        from . import _lib
-        L = _lib.load()
         pk = self._ez_packed(pred)
         B = s.shape[0]
         x = s.contiguous()
@@ -889,20 +870,11 @@ class EZDynamic(nn.Module):
         y = torch.empty_like(x)
         outs = (torch.empty(B, device=x.device), torch.empty(B, device=x.device),
                 torch.empty(B, pred.num_actions, device=x.device))
-        args = _lib.MzsEzArgs()
-        args.struct_size = C.sizeof(_lib.MzsEzArgs)
-        args.device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        args.batch, args.channels, args.num_actions, args.support_size = B, c, pred.num_actions, support_size
-        args.x, args.action, args.y = x.data_ptr(), act.data_ptr(), y.data_ptr()
-        args.reward, args.value, args.prior_logits = (o.data_ptr() for o in outs)
-        for name in _lib.MzsEzArgs.WEIGHTS:
-            setattr(args, name, pk[name].data_ptr())
-        for name in "rvp":
-            hd = getattr(args, name)
-            for f in _lib.MzsEzHead.FIELDS:
-                setattr(hd, f, pk[name][f].data_ptr())
-        with torch.cuda.device(x.device):
-            _lib.check(L.mzs_ez_recurrent(C.byref(args), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        heads = {h: _lib.MzsEzHead(*(pk[h][f].data_ptr() for f in _lib.MzsEzHead.FIELDS)) for h in "rvp"}
+        launch("mzs_ez_recurrent", _lib.MzsEzArgs, x.device, batch=B, channels=c, num_actions=pred.num_actions,
+               support_size=support_size, x=x.data_ptr(), action=act.data_ptr(), y=y.data_ptr(),
+               reward=outs[0].data_ptr(), value=outs[1].data_ptr(), prior_logits=outs[2].data_ptr(),
+               **{name: pk[name].data_ptr() for name in _lib.MzsEzArgs.WEIGHTS}, **heads)
         self._ez_keep = (x, act)  # alive until the stream has consumed them
         return outs[0], outs[1], outs[2], y
 
@@ -939,17 +911,11 @@ class ResNetRepresentation(nn.Module):
         """Root inference of muax/model.py:251-263 with the tail in ONE HIP launch: returns (embedding [B, 6, 6, 64],
         value [B], prior_logits [B, A]) or None when the nets / the input are not what mzs_resnet_root_tail is built for
         (the caller then runs the modules).  Inference only."""
-        def head_ok(seq, convs, hidden):
-            ws = [m for m in seq if isinstance(m, HkConv2D)]
-            ls = [m for m in seq if isinstance(m, LazyHkLinear)]
-            return (len(ws) == len(convs) and len(ls) == 2 and all(m.w is not None and m.w.is_cuda for m in ws + ls)
-                    and [tuple(m.w.shape[2:]) for m in ws] == convs and tuple(ls[0].w.shape) == (576, hidden)
-                    and all(m.with_bias for m in ls))
         if not (self.use_hip_root and isinstance(pred, ResNetPrediction) and obs.is_cuda and obs.dim() == 4
                 and not torch.is_grad_enabled() and 2 * support_size + 1 <= 64 and pred.num_actions <= 64):
             return None
-        if not (head_ok(pred.v_func, [(64, 16), (16, 16)], 16) and head_ok(pred.pi_func, [(64, 16)], 16)
-                and pred.v_func[7].w.shape[1] == 2 * support_size + 1 and pred.pi_func[5].w.shape[1] == pred.num_actions):
+        heads = _prediction_head_arrays(pred, support_size)
+        if heads is None:
             return None
         # the map before the last pool, from the input's size alone (two stride-2 stems and one pool, SAME: ceil
         # division each) -- decided BEFORE any compute, so an unsupported size does not run the net twice
@@ -958,34 +924,20 @@ class ResNetRepresentation(nn.Module):
         hw = [half(half(half(n))) for n in obs.shape[1:3]]
         if not all(half(n) == 6 for n in hw):
             return None
-        heads_t = [m.w for seq in (pred.v_func, pred.pi_func) for m in seq if isinstance(m, (HkConv2D, LazyHkLinear))]
-        if not all(t.dtype == torch.float32 and t.device == obs.device for t in heads_t):
+        if not all(t.dtype == torch.float32 and t.device == obs.device for t in heads):
             return None
         x = self.forward(obs, before_last_pool=True)
         if not (x.dtype == torch.float32 and x.shape[3] == 64 and list(x.shape[1:3]) == hw):
             return None
-        import ctypes as C
-
-        from . import _lib
-        L = _lib.load()
         x = x.contiguous()
         B = x.shape[0]
-        vf, pf = pred.v_func, pred.pi_func
-        heads = [vf[0].w, vf[2].w, vf[5].w, vf[5].b, vf[7].w, vf[7].b, pf[0].w, pf[3].w, pf[3].b, pf[5].w, pf[5].b]
         keep = [h.detach().contiguous() for h in heads]
-        a = _lib.MzsRootTailArgs()
-        a.struct_size = C.sizeof(_lib.MzsRootTailArgs)
-        a.device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        a.batch, a.height, a.width = B, x.shape[1], x.shape[2]
-        a.num_actions, a.support_size, a.normalize = pred.num_actions, support_size, 1
-        a.x = x.data_ptr()
-        for name, t in zip(_lib.MzsRootTailArgs.HEAD_FIELDS, keep):
-            setattr(a, name, t.data_ptr())
         emb = torch.empty(B, 6, 6, 64, device=x.device)
         value, logits = torch.empty(B, device=x.device), torch.empty(B, pred.num_actions, device=x.device)
-        a.embedding, a.value, a.prior_logits = emb.data_ptr(), value.data_ptr(), logits.data_ptr()
-        with torch.cuda.device(x.device):
-            _lib.check(L.mzs_resnet_root_tail(C.byref(a), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+        launch("mzs_resnet_root_tail", _lib.MzsRootTailArgs, x.device, batch=B, height=x.shape[1], width=x.shape[2],
+               num_actions=pred.num_actions, support_size=support_size, normalize=1, x=x.data_ptr(),
+               embedding=emb.data_ptr(), value=value.data_ptr(), prior_logits=logits.data_ptr(),
+               **{name: t.data_ptr() for name, t in zip(_lib.MzsRootTailArgs.HEAD_FIELDS, keep)})
         self._root_keep = keep  # alive until the stream has consumed them
         return emb, value, logits
 
@@ -1042,45 +994,39 @@ class ResNetDynamic(nn.Module):
                 and (inference or not (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))))
 
     def _packed(self):
-        ps = [self.ns_stem.w] + [p for b in self.ns_blocks for p in b.parameters()]
-        sig = tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in ps)
-        if getattr(self, "_pack_sig", None) != sig:
-            with torch.no_grad():
-                # kernel layout of a 3x3 conv: Wp[tap][c][g][co][i] = W[tap][16 c + 4 g + i][co]  (mz_conv.cuh)
-                pack = lambda w: w.reshape(9, 4, 4, 4, 64).permute(0, 1, 2, 4, 3)  # noqa: E731
-                conv = torch.stack([torch.stack([pack(b.proj_conv.w), pack(b.conv_0.w), pack(b.conv_1.w)])
-                                    for b in self.ns_blocks])
-                ln = torch.stack([torch.stack([torch.stack([m.scale, m.offset]) for m in (b.proj_ln, b.ln_0, b.ln_1)])
-                                  for b in self.ns_blocks])
-                self._pack = (self.ns_stem.w.reshape(65, 64).contiguous(), conv.contiguous(), ln.contiguous())
-            self._pack_sig = sig
-        return self._pack
+        def build():
+            conv = torch.stack([torch.stack([pack_conv3x3(m.w) for m in (b.proj_conv, b.conv_0, b.conv_1)])
+                                for b in self.ns_blocks])
+            ln = torch.stack([torch.stack([torch.stack([m.scale, m.offset]) for m in (b.proj_ln, b.ln_0, b.ln_1)])
+                              for b in self.ns_blocks])
+            return self.ns_stem.w.reshape(65, 64).contiguous(), conv.contiguous(), ln.contiguous()
+        return _memo(self, "_pack", [self.ns_stem.w] + [p for b in self.ns_blocks for p in b.parameters()], build)
 
-    def _tower_args(self, B, device, pred=None, support_size=None):
-        """mzs_tower_args with the weights (and, with `pred`, the 17 head arrays + the three per-root outputs) filled in;
-        returns (args, tensors to keep alive, (reward, value, prior_logits) or None, device ordinal)."""
-        import ctypes as C
+    def _tower_heads(self, pred, support_size: int):
+        """The 17 head arrays of MzsTowerArgs.HEAD_FIELDS -- the reward head's, then the prediction net's -- or None when
+        the nets are not the shapes the one-launch recurrent kernel is built for (muax/nn.py:313-378 at 64 channels)."""
+        if not (isinstance(pred, ResNetPrediction) and 2 * support_size + 1 <= 64 and pred.num_actions <= 64
+                and pred.num_actions == self.num_actions):
+            return None
+        r = _head_arrays(self.r_func, [(65, 64), (64, 64)], 64, 2 * support_size + 1)
+        vp = _prediction_head_arrays(pred, support_size)
+        return None if r is None or vp is None else r + vp
 
-        from . import _lib
+    def _tower_args(self, B, device, heads=None, support_size=None):
+        """mzs_tower_args with the weights (and, with `heads` = _tower_heads(), the 17 head arrays + the three per-root
+        outputs) filled in; returns (args, tensors to keep alive, (reward, value, prior_logits) or None, device ordinal)."""
         stem, conv, ln = self._packed()
-        args = _lib.MzsTowerArgs()
-        args.struct_size = C.sizeof(_lib.MzsTowerArgs)
-        dev_index = device.index if device.index is not None else torch.cuda.current_device()
-        args.device = dev_index
-        args.batch, args.blocks, args.normalize, args.num_actions = B, len(self.ns_blocks), 1, self.num_actions
-        args.stem_w, args.conv_w, args.ln = stem.data_ptr(), conv.data_ptr(), ln.data_ptr()
+        dev_index = device_index(device)
+        args = _lib.args(_lib.MzsTowerArgs, device=dev_index, batch=B, blocks=len(self.ns_blocks), normalize=1,
+                         num_actions=self.num_actions, stem_w=stem.data_ptr(), conv_w=conv.data_ptr(), ln=ln.data_ptr())
         keep, outs = [stem, conv, ln], None
-        if pred is not None:
-            rf, vf, pf = self.r_func, pred.v_func, pred.pi_func
-            heads = [rf[0].w, rf[2].w, rf[5].w, rf[5].b, rf[7].w, rf[7].b,
-                     vf[0].w, vf[2].w, vf[5].w, vf[5].b, vf[7].w, vf[7].b,
-                     pf[0].w, pf[3].w, pf[3].b, pf[5].w, pf[5].b]
+        if heads is not None:
             hk = [h.detach().contiguous() for h in heads]
             keep += hk
             for name, t in zip(_lib.MzsTowerArgs.HEAD_FIELDS, hk):
                 setattr(args, name, t.data_ptr())
             outs = (torch.empty(B, device=device), torch.empty(B, device=device),
-                    torch.empty(B, pred.num_actions, device=device))
+                    torch.empty(B, self.num_actions, device=device))
             args.reward, args.value, args.prior_logits = (o.data_ptr() for o in outs)
             args.support_size = support_size
         return args, keep, outs, dev_index
@@ -1099,20 +1045,18 @@ class ResNetDynamic(nn.Module):
                 return key, first
         return None, False
 
-    def _tower_hip(self, s, a, pred=None, support_size=None):
-        import ctypes as C
-
-        from . import _lib
+    def _tower_hip(self, s, a, heads=None, support_size=None):
         L = _lib.load()
         x = s.contiguous()
         act = a.to(torch.int32).contiguous()
         y = torch.empty_like(x)
-        args, keep, outs, dev_index = self._tower_args(x.shape[0], x.device, pred, support_size)
+        args, keep, outs, dev_index = self._tower_args(x.shape[0], x.device, heads, support_size)
         args.x, args.action, args.y = x.data_ptr(), act.data_ptr(), y.data_ptr()
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        key, first = self._pair_scratch_for(L, args, x.shape[0], x.device, dev_index, stream)
+        stream = raw_stream(dev_index)
+        # (the scratch is keyed by the stream as an integer; c_void_p.value of the null stream is None: 0)
+        key, first = self._pair_scratch_for(L, args, x.shape[0], x.device, dev_index, stream.value or 0)
         with torch.cuda.device(x.device):
-            _lib.check(L.mzs_resnet_tower(C.byref(args), C.c_void_p(stream)))
+            _lib.check(L.mzs_resnet_tower(C.byref(args), stream))
             if args.pair_scratch and first and not torch.cuda.is_current_stream_capturing():
                 # first launch on this scratch: make sure the two halves of every root found each other (they
                 # meet in one XCD's L2; a part or driver that places workgroups differently reports it here)
@@ -1120,7 +1064,7 @@ class ResNetDynamic(nn.Module):
                     type(self).use_pair_tower = False
                     del self._pair_scratch[key]
                     args.pair_scratch, args.pair_scratch_bytes = None, 0
-                    _lib.check(L.mzs_resnet_tower(C.byref(args), C.c_void_p(stream)))
+                    _lib.check(L.mzs_resnet_tower(C.byref(args), stream))
         return y if outs is None else (outs[0], outs[1], outs[2], y)
 
     use_hip_search = True  # the whole simulation loop as one launch (mzs_resnet_search); MZS_RESNET_SEARCH=0 turns it off
@@ -1139,17 +1083,17 @@ class ResNetDynamic(nn.Module):
         `sim_begin` has run) in ONE launch: recurrent_fn of muax/model.py:265-282 + mctx's expand / backward / next
         simulate per root, back to back on the workgroup(s) that own the root (muax_amd/csrc/mz_search_conv.hip).
         Pair mode (<= 128 roots): check pair_lost() afterwards, as for hip_recurrent."""
-        import ctypes as C
-
-        from . import _lib
         L = _lib.load()
         B, dev = handle.batch, handle.device
-        args, keep, outs, dev_index = self._tower_args(B, dev, pred, support_size)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        self._pair_scratch_for(L, args, B, dev, dev_index, stream)
+        heads = self._tower_heads(pred, support_size)
+        if heads is None:
+            raise ValueError("hip_search: the nets are not the shapes mzs_resnet_search is built for (hip_search_ok)")
+        args, keep, outs, dev_index = self._tower_args(B, dev, heads, support_size)
+        stream = raw_stream(dev_index)
+        self._pair_scratch_for(L, args, B, dev, dev_index, stream.value or 0)
         with torch.cuda.device(dev):
-            _lib.check(L.mzs_resnet_search(handle._h, C.byref(args), C.c_float(discount), sim_begin, sim_end,
-                                           C.c_void_p(stream)), handle._h)
+            _lib.check(L.mzs_resnet_search(handle._h, C.byref(args), C.c_float(discount), sim_begin, sim_end, stream),
+                       handle._h)
         self._search_keep = (keep, outs)  # alive until the stream has consumed them
 
     def pair_status(self):
@@ -1170,26 +1114,13 @@ class ResNetDynamic(nn.Module):
         self._pair_scratch.clear()
 
     def _heads_ok(self, pred, s, support_size: int) -> bool:
-        """The nets are the shapes the one-launch recurrent kernel is built for (muax/nn.py:313-378 at 64 channels)."""
-        def head_ok(seq, convs, hidden, in_ch):
-            ws = [m for m in seq if isinstance(m, HkConv2D)]
-            ls = [m for m in seq if isinstance(m, LazyHkLinear)]
-            return (len(ws) == len(convs) and len(ls) == 2 and all(m.w is not None for m in ws + ls)
-                    and [tuple(m.w.shape[2:]) for m in ws] == convs and ls[0].w.shape[1] == hidden
-                    and all(m.with_bias for m in ls))
-        return (isinstance(pred, ResNetPrediction) and self._hip_tower_ok(s, inference=True) and 2 * support_size + 1 <= 64
-                and pred.num_actions <= 64 and pred.num_actions == self.num_actions
-                and head_ok(self.r_func, [(65, 64), (64, 64)], 64, 65)
-                and head_ok(pred.v_func, [(64, 16), (16, 16)], 16, 64)
-                and head_ok(pred.pi_func, [(64, 16)], 16, 64)
-                and self.r_func[7].w.shape[1] == 2 * support_size + 1
-                and pred.v_func[7].w.shape[1] == 2 * support_size + 1)
+        """The one-launch recurrent kernel applies to `s` and these nets."""
+        return self._hip_tower_ok(s, inference=True) and self._tower_heads(pred, support_size) is not None
 
     def hip_recurrent(self, pred, s, a, support_size: int):
         """The whole recurrent_fn of muax/model.py:265-282 for the ResNet nets in ONE HIP launch: reward head,
         next-state tower, prediction heads on the next state, both support decodes.  Returns
         (reward [B], value [B], prior_logits [B, A], next_state [B, 6, 6, 64]) or None when the nets are not
         the shapes the kernel is built for (the caller then runs the torch modules)."""
-        if not self._heads_ok(pred, s, support_size):
-            return None
-        return self._tower_hip(s, a, pred, support_size)
+        heads = self._tower_heads(pred, support_size) if self._hip_tower_ok(s, inference=True) else None
+        return None if heads is None else self._tower_hip(s, a, heads, support_size)

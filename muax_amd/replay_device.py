@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, prng
+from ._call import device_index, raw_stream
 from .episode_tracer import Transition
 from .replay_buffer import BaseReplayBuffer
 
@@ -223,12 +224,10 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         self._t.update({n: torch.zeros(self._capacity, dtype=dt, device=dev) for n, dt in _TABLE_FIELDS})
         self._arena = _lib.args(_lib.MzsReplayArena, max_steps=S, capacity=self._capacity, obs_dim=self.obs_dim,
                                 num_actions=self.num_actions, **{n: x.data_ptr() for n, x in self._t.items()},
-                                device=dev.index if dev.index is not None else torch.cuda.current_device())
+                                device=device_index(dev))
 
     def _stream(self):
-        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        idx = self._arena.device
-        return C.c_void_p(raw(idx) if raw is not None else torch.cuda.current_stream(self._device).cuda_stream)
+        return raw_stream(self._arena.device)
 
     def _check_dims(self, obs_dim, num_actions):
         if self._arena is None:

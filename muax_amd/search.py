@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._call import capture, device_index, raw_stream
 from ._lib import (MLP_WEIGHT_NAMES, TREE_FIELDS, TREE_INT_FIELDS, MzsActArgs, MzsActHostArgs, MzsConfig,
                    MzsMlpWeights, MzsStochasticMlpWeights, MzsStochasticOutputs, MzsTreeView,
                    STOCHASTIC_MLP_WEIGHT_NAMES)
@@ -134,7 +135,7 @@ class MuZeroSearch:
             raise RuntimeError("muax_amd needs a ROCm GPU (gfx950); there is no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None \
             else torch.device(device)
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self._dev_index = device_index(self.device)
         self.batch, self.cfg = int(batch), cfg
         self._L = _lib.load()
         c = MzsConfig()
@@ -197,11 +198,7 @@ class MuZeroSearch:
 
     # ------------------------------------------------------------------ helpers
     def _stream(self):
-        # torch's current stream of this device, raw (torch.cuda.current_stream() builds a Stream object: ~6 us per call)
-        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        if raw is not None:
-            return C.c_void_p(raw(self._dev_index))
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return raw_stream(self._dev_index)  # torch's current stream of this device, raw
 
     def _f32(self, t, shape, name):
         if t is None:
@@ -292,13 +289,9 @@ class MuZeroSearch:
                   "dr_w1": (E + A, H), "dr_b1": (H,), "dr_w2": (H, F), "dr_b2": (F,),
                   "dn_w1": (E + A, H), "dn_b1": (H,), "dn_w2": (H, E), "dn_b2": (E,)}
         keep = {n: self._f32(weights[n], shapes[n], n) for n in MLP_WEIGHT_NAMES}
-        w = MzsMlpWeights()
-        w.struct_size = C.sizeof(MzsMlpWeights)
-        w.obs_dim, w.support_size = obs_dim, support_size
-        w.recurrent_pred_on = {"child": 0, "parent": 1}[recurrent_pred_on]
-        w.discount = discount
-        for n in MLP_WEIGHT_NAMES:
-            setattr(w, n, keep[n].data_ptr())
+        w = _lib.args(MzsMlpWeights, obs_dim=obs_dim, support_size=support_size, discount=discount,
+                      recurrent_pred_on={"child": 0, "parent": 1}[recurrent_pred_on],
+                      **{n: keep[n].data_ptr() for n in MLP_WEIGHT_NAMES})
         _lib.check(self._L.mzs_mlp_set_weights(self._h, C.byref(w)), self._h)
         self._weights = (keep, obs_dim)  # keep the device buffers alive
 
@@ -514,7 +507,7 @@ class MuZeroSearch:
                 torch.cuda.current_stream(self.device).wait_stream(side)
                 do_root()
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with capture(g):
                     loop()
             entry = self._graphs[gkey] = (g, fns, self._keep, graph_version)
         entry[0].replay()

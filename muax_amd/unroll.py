@@ -5,7 +5,11 @@ the priorities |v_i - Rn_i| that `DeviceReplayBuffer.update_priorities` takes as
 MLP trio); `torch_unroll_values` the same unroll on the model's torch modules, for the CPU and for any nets."""
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
+
+from . import _call, _lib
 
 # what mzs_mlp_unroll_values states (include/mzsearch.h): outside them backend="auto" takes the torch route
 LIMITS = {"obs_dim": (1, 128), "embed_dim": (1, 64), "num_actions": (1, 64), "support_size": (8, 31)}
@@ -54,16 +58,13 @@ def torch_unroll_values(model, batch, kp):
 
 class FusedUnrollValues:
     """The kernel route for one model: the weight struct is kept and rebuilt only when a parameter tensor moved
-    (optimisers update in place), as FusedLossGrad keeps its own."""
+    (optimisers update in place): _call.MlpWeights, as in FusedLossGrad."""
 
     def __init__(self, muzero_instance):
-        import ctypes as C
-
-        from . import _lib
         from . import nn as mz_nn
         if not mz_nn.is_default_mlp_trio(muzero_instance.network):
             raise ValueError("the value-unroll kernel is built for the default MLP trio")
-        self.m, self._C, self._lib = muzero_instance, C, _lib
+        self.m = muzero_instance
         params = mz_nn.mlp_trio_weights(muzero_instance.network)
         self.params = [params[n] for n in _lib.MLP_WEIGHT_NAMES]
         self.dev = self.params[0].device
@@ -72,10 +73,10 @@ class FusedUnrollValues:
         self._L = _lib.load()
         r, p, _ = muzero_instance.network
         self.obs_dim, self.E, self.A = r.obs_dim, r.embedding_dim, p.num_actions
-        self._w = self._w_keep = self._w_ptrs = None
+        self._weights, self._w = _call.MlpWeights(self.params), None
 
     def __call__(self, batch, kp):
-        C, _lib, dev = self._C, self._lib, self.dev
+        dev = self.dev
 
         def t(x, dt):  # (tensors that already are what the kernel reads pass through untouched)
             if isinstance(x, torch.Tensor) and x.dtype == dt and x.device == dev and x.is_contiguous():
@@ -88,28 +89,16 @@ class FusedUnrollValues:
         Rn = t(batch.Rn, torch.float32).reshape(B, L)
         if obs.shape[1] != self.obs_dim:
             raise ValueError(f"batch.obs has {obs.shape[1]} features, the network takes {self.obs_dim}")
-        ptrs = tuple(x.data_ptr() for x in self.params)
-        if self._w is None or ptrs != self._w_ptrs or not all(x.is_contiguous() for x in self.params):
-            w = _lib.MzsMlpWeights()
-            w.struct_size = C.sizeof(_lib.MzsMlpWeights)
-            w.obs_dim = self.obs_dim
-            keep = [x.detach().contiguous() for x in self.params]
-            for n, x in zip(_lib.MLP_WEIGHT_NAMES, keep):
-                setattr(w, n, x.data_ptr())
-            self._w, self._w_keep = w, keep
-            self._w_ptrs = ptrs if all(k.data_ptr() == q for k, q in zip(keep, ptrs)) else None
-        w = self._w
-        w.support_size, w.discount = self.m._support_size, self.m._discount
+        w, keep = self._weights.get()
+        self._w = w  # (read by nobody here: tests/test_gpu_unroll_values.py checks through it that the struct is kept)
+        w.obs_dim, w.support_size, w.discount = self.obs_dim, self.m._support_size, self.m._discount
         out = torch.empty((2, B, kp), dtype=torch.float32, device=dev)
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        args = _lib.MzsUnrollArgs()
-        args.struct_size = C.sizeof(_lib.MzsUnrollArgs)
+        idx = _call.device_index(dev)
+        args = _lib.args(_lib.MzsUnrollArgs)
         args.device, args.batch, args.row_steps, args.k_prio = idx, B, L, kp
         args.num_actions, args.embed_dim = self.A, self.E
         args.obs, args.actions, args.returns = obs.data_ptr(), a.data_ptr(), Rn.data_ptr()
         args.values, args.prio = out[0].data_ptr(), out[1].data_ptr()
-        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        stream = C.c_void_p(raw(idx) if raw is not None else torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(self._L.mzs_mlp_unroll_values(C.byref(w), C.byref(args), stream))
-        self._keep = (obs, a, Rn, self._w_keep)  # (alive until the next call: the launch is asynchronous)
+        _lib.check(self._L.mzs_mlp_unroll_values(C.byref(w), C.byref(args), _call.raw_stream(idx)))
+        self._keep = (obs, a, Rn, keep)  # (alive until the next call: the launch is asynchronous)
         return out[0], out[1]
