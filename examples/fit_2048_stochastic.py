@@ -67,13 +67,15 @@ def main():
     ap.add_argument("--max-episode-steps", type=int, default=200)
     ap.add_argument("--reward-shift", type=int, default=6)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--one-launch", action="store_true",
+                    help="act() with the whole search in one launch (MuZero(stochastic_one_launch=True)): the same bits")
     args = ap.parse_args()
 
     support_size, E, Cn, discount, k_steps = 31, 32, 32, 0.997, 5
     venv = muax.Device2048(args.envs, max_episode_steps=args.max_episode_steps, seed=args.seed, reward_shift=args.reward_shift)
     net = muax.create_stochastic_muzero_network(E, venv.num_actions, Cn, 2 * support_size + 1)
     model = muax.MuZero(net, policy="stochastic", discount=discount, support_size=support_size,
-                        optimizer=muax.optimizers.create_optimizer("adam", 2e-3))
+                        optimizer=muax.optimizers.create_optimizer("adam", 2e-3), stochastic_one_launch=args.one_launch)
     obs = venv.reset_device()
     model.init(args.seed, np.zeros((1, obs.shape[1]), np.float32))
     buffer = muax.TrajectoryReplayBuffer(2000, random_seed=args.seed)

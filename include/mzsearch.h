@@ -264,6 +264,48 @@ int mzs_mlp_set_stochastic_weights(mzs_handle *h, const mzs_stochastic_mlp_weigh
 int mzs_mlp_stochastic_recurrent(mzs_handle *h, const int32_t *slot, const int32_t *parent_is_decision,
                                  const float *parent_embedding, const mzs_stochastic_outputs *outputs, void *stream);
 
+/* ---- the WHOLE stochastic search of the bound family in ONE launch, the tree in LDS (muax_amd/csrc/mz_stoch_wide.cuh):
+ * what mzs_root_stochastic, num_simulations x (mzs_select_stochastic, mzs_mlp_stochastic_recurrent,
+ * mzs_expand_backup_stochastic) and mzs_finish_stochastic compute, bit for bit, one root per wavefront.
+ * Limits (mzs_mlp_stochastic_plan): num_actions + num_chance_outcomes <= 64, embed_dim <= 64 = both embedding widths,
+ * support_size 8..31, num_simulations <= 255, one root's tree within the 160 KiB of a CU's LDS. */
+/* The kernel's LDS plan for a shape (host arithmetic, no device needed): out = {roots (wavefronts) per workgroup, LDS
+ * bytes per workgroup, resident roots per CU, 1 when the embeddings are kept in LDS}; MZS_E_UNSUPPORTED when the kernel
+ * declines the shape, MZS_E_INVALID for a null `out`. */
+int mzs_mlp_stochastic_plan(int32_t num_actions, int32_t num_chance_outcomes, int32_t embed_dim, int32_t support_size,
+                            int32_t num_simulations, int32_t out[4]);
+typedef struct mzs_stochastic_search_args {
+  int32_t struct_size;             /* = sizeof(mzs_stochastic_search_args) */
+  int32_t export_tree;             /* 1: the finished tree into the handle's HBM tree arrays, for mzs_tree_export; 0: they
+                                      are not touched */
+  const float *prior_logits;       /* [B, A]  RootFnOutput, as mzs_root_stochastic takes it */
+  const float *value;              /* [B] */
+  const float *embedding;          /* [B, embed_dim] */
+  const uint8_t *invalid_actions;  /* [B, A] or NULL */
+  const float *dirichlet_noise;    /* [B, A] or NULL (then dirichlet_fraction must be 0) */
+  const float *gumbel;             /* [B, A] or NULL: the categorical's Gumbel row drawn from `key` */
+  uint32_t key[2];                 /* the act rng_key (HOST values) */
+  float dirichlet_fraction;
+  float temperature;
+  /* NULL, or a DEVICE array of 4 + 2 num_simulations words that REPLACES key, temperature and dirichlet_fraction: a
+   * captured launch freezes this struct's values, not the array's contents (mzs_stochastic_search_block fills a host copy) */
+  const uint32_t *device_block;
+  int32_t *action;                 /* out [B] */
+  float *action_weights;           /* out [B, A] */
+  float *search_value;             /* out [B] or NULL: the root's node value after the search */
+  int32_t *depth_sum;              /* out [B] or NULL: sum over simulations of the selection depth, both kinds of level */
+} mzs_stochastic_search_args;
+/* One launch on `stream`, nothing else: capturable, no synchronisation, no copy to the host (the first call of a handle
+ * that exports a tree, or whose plan keeps the embeddings in HBM, allocates).  Needs mzs_mlp_set_stochastic_weights.
+ * Refused before any launch, the message (mzs_last_error) naming the limit: MZS_E_INVALID for a handle of another policy,
+ * unbound weights, a null or mis-sized struct, a null required pointer (prior_logits, value, embedding, action,
+ * action_weights); MZS_E_UNSUPPORTED for a shape the plan declines or embedding widths that differ. */
+int mzs_mlp_stochastic_search(mzs_handle *h, const mzs_stochastic_search_args *args, void *stream);
+/* HOST arithmetic: the 4 + 2 num_simulations words of `device_block` for (key, temperature, dirichlet_fraction) into
+ * out_words -- k_sample[2], the two floats' bits, every simulation's key.  key NULL: zero. */
+int mzs_stochastic_search_block(const uint32_t key[2], int32_t num_simulations, float temperature, float dirichlet_fraction,
+                                uint32_t *out_words);
+
 /* ---- recurrent_fn of the EfficientZero-style nets ----
  * mzs_ez_recurrent evaluates, for a batch of 6x6xC hidden states (NHWC, C = 32 or 64) and actions, the whole
  * MuZero._recurrent_inference (muax/model.py:265-282) of EZDynamic + EZPrediction with use_v2 = True

@@ -5,7 +5,7 @@ and linked into one shared object: the C-ABI's handle and registries (mz_api.hip
 act() dispatch (mz_act.hip), the step-wise path, the generic one-launch search and the stochastic MLP family's recurrent step with the
 step kernels (mz_stepwise.hip), the training step (mz_train.hip), the self-test and Dirichlet kernels (mz_selftest.hip) --, the
 fused act() kernel instances in five groups (mz_fused_g*.hip, listed in mz_instances.def), the wide-action act()
-kernel (mz_wide.hip), the ResNet recurrent kernel (mz_conv.hip), the device-resident replay (mz_replay.hip), the
+kernel (mz_wide.hip), the one-launch stochastic search (mz_stoch_wide.hip), the ResNet recurrent kernel (mz_conv.hip), the device-resident replay (mz_replay.hip), the
 forward value unroll behind its priorities (mz_unroll.hip) and the device vector environments (mz_env.hip; 2048 with its
 legal-move masks in mz_env2048.hip).  Only the units whose sources changed are recompiled."""
 from __future__ import annotations
@@ -26,7 +26,8 @@ _HANDLE = ["mz_handle.h", "mz_host.h", "mz_keys.h", "mz_step.cuh", "mz_step_jump
 UNITS = {
     "mz_api.hip": _HANDLE + ["mz_fused_launch.h", "mz_fused.cuh"],
     "mz_act.hip": _HANDLE + ["mz_fused_launch.h", "mz_fused.cuh", "mz_wide_launch.h"],
-    "mz_stepwise.hip": _HANDLE + ["mz_mlp_generic.cuh", "mz_step_kernels.cuh", "mz_stoch_mlp.cuh"],
+    "mz_stepwise.hip": _HANDLE + ["mz_mlp_generic.cuh", "mz_step_kernels.cuh", "mz_stoch_mlp.cuh", "mz_stoch_wide_launch.h",
+                        "mz_wide_launch.h", "mz_fused_launch.h", "mz_fused.cuh"],
     "mz_train.hip": ["mz_host.h", "mz_train_launch.h", "mz_train.cuh", "mz_spec.cuh", _ABI],
     "mz_selftest.hip": ["mz_host.h", "mz_dirichlet.cuh", "mz_spec.cuh", _ABI],
     "mz_fused_g0.hip": _FUSED,
@@ -35,6 +36,8 @@ UNITS = {
     "mz_fused_g3.hip": _FUSED,
     "mz_fused_g4.hip": _FUSED,
     "mz_wide.hip": ["mz_wide.cuh", "mz_wide_launch.h", "mz_fused_launch.h", "mz_fused.cuh", "mz_spec.cuh", "mz_host.h", _ABI],
+    "mz_stoch_wide.hip": ["mz_stoch_wide.cuh", "mz_stoch_wide_launch.h", "mz_wide.cuh", "mz_wide_launch.h", "mz_fused_launch.h",
+                          "mz_fused.cuh", "mz_spec.cuh", "mz_host.h", "mz_keys.h", _ABI],
     "mz_conv.hip": ["mz_host.h", "mz_conv_host.h", "mz_conv.cuh", "mz_spec.cuh", _ABI],
     "mz_search_conv.hip": ["mz_host.h", "mz_conv_host.h", "mz_conv.cuh", "mz_step.cuh", "mz_step_jump.cuh", "mz_spec.cuh", _ABI],
     "mz_norm.hip": ["mz_host.h", "mz_norm.cuh", "mz_repr.cuh", "mz_repr_host.h", "mz_spec.cuh", _ABI],

@@ -42,6 +42,14 @@ class MzsStochasticMlpWeights(C.Structure):
                 + [(n, _vp) for n in STOCHASTIC_MLP_WEIGHT_NAMES])
 
 
+class MzsStochasticSearchArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("export_tree", C.c_int32), ("prior_logits", _vp), ("value", _vp),
+                ("embedding", _vp), ("invalid_actions", _vp), ("dirichlet_noise", _vp), ("gumbel", _vp),
+                ("key", C.c_uint32 * 2), ("dirichlet_fraction", C.c_float), ("temperature", C.c_float),
+                ("device_block", _vp), ("action", _vp), ("action_weights", _vp), ("search_value", _vp),
+                ("depth_sum", _vp)]
+
+
 MLP_WEIGHT_NAMES = ["repr_w", "repr_b", "pv_w1", "pv_b1", "pv_w2", "pv_b2", "pp_w1", "pp_b1", "pp_w2",
                     "pp_b2", "dr_w1", "dr_b1", "dr_w2", "dr_b2", "dn_w1", "dn_b1", "dn_w2", "dn_b2"]
 
@@ -274,7 +282,8 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_env_classic_reset", "mzs_env_classic_step",
                     "mzs_env_2048_reset", "mzs_env_2048_step", "mzs_env_2048_mask",
                     "mzs_root_stochastic", "mzs_select_stochastic", "mzs_expand_backup_stochastic",
-                    "mzs_finish_stochastic", "mzs_mlp_set_stochastic_weights", "mzs_mlp_stochastic_recurrent"]
+                    "mzs_finish_stochastic", "mzs_mlp_set_stochastic_weights", "mzs_mlp_stochastic_recurrent",
+                    "mzs_mlp_stochastic_plan", "mzs_mlp_stochastic_search", "mzs_stochastic_search_block"]
 
 _lib = None
 
@@ -313,6 +322,9 @@ def load(build_if_missing: bool = True):
     L.mzs_finish_stochastic.argtypes = [_vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]
     L.mzs_mlp_set_stochastic_weights.argtypes = [_vp, C.POINTER(MzsStochasticMlpWeights)]
     L.mzs_mlp_stochastic_recurrent.argtypes = [_vp, _vp, _vp, _vp, C.POINTER(MzsStochasticOutputs), _vp]
+    L.mzs_mlp_stochastic_plan.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_int32 * 4)]
+    L.mzs_mlp_stochastic_search.argtypes = [_vp, C.POINTER(MzsStochasticSearchArgs), _vp]
+    L.mzs_stochastic_search_block.argtypes = [C.POINTER(C.c_uint32 * 2), C.c_int32, C.c_float, C.c_float, _vp]
     L.mzs_mlp_loss_grad.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsTrainArgs), _vp]
     L.mzs_resnet_tower.argtypes = [C.POINTER(MzsTowerArgs), _vp]
     L.mzs_register_fused_dispatch.argtypes = [_vp, C.c_int32]

@@ -19,7 +19,7 @@ struct mzs_handle {
   std::vector<uint32_t> sim_keys;  // [num_simulations][2], sized at create: simulate_key of every simulation
   uint64_t* prof = nullptr;        // MZ_PROFILE builds only
   int32_t* fused_table = nullptr;  // gumbel policy, fused path: seq_halving table on the device
-  float* fused_emb = nullptr;      // fused path, embed_dim > 16: [B][S+1][E] embeddings in HBM
+  float* fused_emb = nullptr;      // fused path, embed_dim > 16, and the one-launch stochastic search: [B][S+1][E] embeddings in HBM
   int32_t* fused_path = nullptr;   // fused path, instances with the root paths in HBM: [B][S+1][fused_path_words]
   int fused_path_words = 0;
   int cu_count = 0;

@@ -5,11 +5,13 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 #include "mz_handle.h"
 #include "mz_mlp_generic.cuh"
 #include "mz_step_kernels.cuh"
 #include "mz_stoch_mlp.cuh"
+#include "mz_stoch_wide_launch.h"
 
 using mzh::fail;
 
@@ -383,6 +385,60 @@ int mzs_mlp_stochastic_recurrent(mzs_handle* h, const int32_t* slot, const int32
   const size_t lds = sizeof(float) * (size_t)mz::stoch_scratch_words(w.E, w.A, w.C);
   hipLaunchKernelGGL(mz::mz_stoch_mlp_recurrent_kernel, dim3(c.batch), dim3(64), lds, static_cast<hipStream_t>(stream_), w, a);
   return launched(h);
+}
+
+// ---- the whole stochastic search of the bound family in ONE launch, the tree in LDS (mz_stoch_wide.cuh) ----
+int mzs_mlp_stochastic_search(mzs_handle* h, const mzs_stochastic_search_args* a, void* stream_) {
+  if (!h) return MZS_E_INVALID;
+  const char* who = "mzs_mlp_stochastic_search";
+  const mzs_config& c = h->cfg;
+  if (c.policy == 2 && !h->have_stochastic_weights) return fail(h, MZS_E_INVALID, "%s: call mzs_mlp_set_stochastic_weights first", who);
+  if (int rc = stoch_mlp_refusal(h, who, h->sw.support_size)) return rc;
+  if (!a || a->struct_size != (int32_t)sizeof(mzs_stochastic_search_args)) return fail(h, MZS_E_INVALID, "%s: null or size mismatch (ABI)", who);
+  if (!a->prior_logits || !a->value || !a->embedding) return fail(h, MZS_E_INVALID, "%s: null input", who);
+  if (!a->action || !a->action_weights) return fail(h, MZS_E_INVALID, "%s: null output", who);
+  if (!a->dirichlet_noise && a->dirichlet_fraction != 0.0f && !a->device_block)
+    return fail(h, MZS_E_INVALID, "%s: dirichlet_fraction != 0 needs dirichlet_noise", who);
+  const mzs_stochastic_mlp_weights& s = h->sw;
+  mz::WidePlan pl;
+  if (const char* limit = mz::stoch_wide_plan(c.num_actions, c.num_chance_outcomes, c.embed_dim, 2 * s.support_size + 1,
+                                              c.num_simulations, &pl))
+    return fail(h, MZS_E_UNSUPPORTED, "%s", (std::string(who) + ": " + limit).c_str());
+  MZS_HIP(h, hipSetDevice(c.device));
+  const bool ex = a->export_tree != 0;
+  if (ex)
+    if (int rc = ensure_step_state(h)) return rc;
+  const size_t BN = (size_t)c.batch * (c.num_simulations + 1);
+  if (!pl.emb_lds && !ex && !h->fused_emb)
+    MZS_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->fused_emb), BN * c.embed_dim * sizeof(float)));
+  mz::StochWideParams p = {};
+  p.prior_logits = a->prior_logits; p.value = a->value; p.embedding = a->embedding;
+  p.invalid = a->invalid_actions; p.dirichlet_noise = a->dirichlet_noise; p.gumbel = a->gumbel;
+  memcpy(p.w, &s.ad_w1, sizeof p.w);
+  p.action = a->action; p.action_weights = a->action_weights; p.search_value = a->search_value; p.depth_sum = a->depth_sum;
+  if (ex) {
+    const mz::StepState& t = h->step;
+    p.t_node_visits = t.node_visits; p.t_raw_values = t.raw_values; p.t_node_values = t.node_values;
+    p.t_parents = t.parents; p.t_action_from_parent = t.action_from_parent;
+    p.t_children_index = t.children_index; p.t_children_prior_logits = t.children_prior_logits;
+    p.t_children_prior_probs = t.children_prior_probs; p.t_children_values = t.children_values;
+    p.t_children_visits = t.children_visits; p.t_children_rewards = t.children_rewards;
+    p.t_children_discounts = t.children_discounts; p.t_embeddings = t.embeddings;
+    p.t_root_invalid = t.root_invalid; p.t_depth_sum = t.depth_sum;
+  }
+  p.emb_scratch = h->fused_emb;
+  p.dyn = a->device_block;
+  p.B = c.batch; p.A = c.num_actions; p.C = c.num_chance_outcomes; p.E = c.embed_dim; p.F = 2 * s.support_size + 1;
+  p.support = s.support_size; p.S = c.num_simulations; p.max_depth = c.max_depth; p.export_tree = ex;
+  p.pb_c_init = c.pb_c_init; p.pb_c_base = c.pb_c_base; p.dirichlet_fraction = a->dirichlet_fraction;
+  p.discount = s.discount; p.temperature = a->temperature;
+  p.global_batch = (uint64_t)c.global_batch; p.root_offset = (uint64_t)c.root_offset;
+  mzh::derive_keys(a->key, c.num_simulations, p.k_sample, &p.sim_keys[0][0]);  // num_simulations <= 255 (the plan)
+  std::string err;
+  if (int rc = mz::stoch_wide_launch(c.tiebreak != 0, c.device, p, pl, static_cast<hipStream_t>(stream_), &err))
+    return fail(h, rc, "%s", (std::string(who) + ": " + err).c_str());
+  if (ex) h->step.rooted = true;  // the HBM tree is that of a finished step-wise search: mzs_tree_export serves it
+  return MZS_OK;
 }
 
 int mzs_tree_export(mzs_handle* h, const mzs_tree_view* out, void* stream_) {

@@ -22,13 +22,12 @@ inline int wide_weight_words(int A, int E, int F) {
   const int H = kHidden, X = E + A;
   return (E * H + H + H * F + F) + (E * H + H + H * A + A) + (X * H + H + H * F + F) + (X * H + H + H * E + E);
 }
-// false: the wide kernel declines the shape (also when one root does not fit a CU's LDS)
-// gumbel: the plan of the Gumbel MuZero modes (the larger record: fewer resident roots, a smaller largest S)
-inline bool wide_plan(int A, int E, int F, int S, bool gumbel, WidePlan* out) {
-  if (A < 17 || A > 64 || E < 1 || E > 64 || F < 17 || F > 63 || S < 1 || S > 255) return false;
+// The split of a CU's LDS that keeps most roots resident, for a kernel of this mapping (mz_wide.cuh, mz_stoch_wide.cuh):
+// `wgt` weight words (rounded) and the pUCT table per workgroup, per root S + 1 records of `rec` words, the path and --
+// when it costs no resident root -- the embeddings.  false: one root does not fit
+inline bool wide_fit(int wgt, int rec, int E, int S, WidePlan* out) {
   WidePlan best{};
-  const int N = S + 1, rec = 4 + (gumbel ? 5 : 4) * A;
-  const int wgt = wide_round4(wide_weight_words(A, E, F)), wg = wgt + wide_round4(S + 2);
+  const int N = S + 1, wg = wgt + wide_round4(S + 2);
   for (int emb = 1; emb >= 0; --emb)
     for (int w = 1; w <= kWideMaxWaves; ++w) {
       const int root = wide_round4(N * rec + N + (emb ? N * E : 0));
@@ -41,6 +40,12 @@ inline bool wide_plan(int A, int E, int F, int S, bool gumbel, WidePlan* out) {
   if (best.roots_per_cu == 0) return false;
   *out = best;
   return true;
+}
+// false: the wide kernel declines the shape (also when one root does not fit a CU's LDS)
+// gumbel: the plan of the Gumbel MuZero modes (the larger record: fewer resident roots, a smaller largest S)
+inline bool wide_plan(int A, int E, int F, int S, bool gumbel, WidePlan* out) {
+  if (A < 17 || A > 64 || E < 1 || E > 64 || F < 17 || F > 63 || S < 1 || S > 255) return false;
+  return wide_fit(wide_round4(wide_weight_words(A, E, F)), 4 + (gumbel ? 5 : 4) * A, E, S, out);
 }
 
 // mode: that of the fused dispatchers (0 / 1 MuZero policy, 2 / 3 Gumbel policy); the Gumbel modes are served only with

@@ -27,7 +27,7 @@ from .nn import MZNetwork, MZNetworkParams, SMZNetwork, SMZNetworkParams
 from .optimizers import optimizer  # noqa: F401  (the README's `muax.model.optimizer(...)`)
 from .policy import GumbelMuZeroPolicy, MuZeroPolicy, Policy, StochasticMuZeroPolicy
 from .search import (ChanceRecurrentFnOutput, DecisionRecurrentFnOutput, MuZeroSearch, PolicyOutput,  # noqa: F401
-                     SearchConfig)  # (PolicyOutput: re-exported type)
+                     SearchConfig, stochastic_plan)  # (PolicyOutput: re-exported type)
 
 
 def _dirichlet(key_words, alpha: float, shape, device, global_batch=None, root_offset=0) -> torch.Tensor:
@@ -71,7 +71,8 @@ class MuZero:
     def __init__(self, network=None, prediction_fn=None, dynamic_fn=None, policy_class=MuZeroPolicy,
                  policy: Optional[str] = None, optimizer=None, loss_fn=None, discount: float = 0.99,
                  support_size: int = 10, recurrent_pred_on: str = "child", device=None,
-                 representation_fn=None, capture_graph: bool = False, root_graph_cache: int = 2):
+                 representation_fn=None, capture_graph: bool = False, root_graph_cache: int = 2,
+                 stochastic_one_launch: bool = False):
         self._stochastic = isinstance(network, SMZNetwork)
         if self._stochastic:
             if policy not in (None, "stochastic"):
@@ -99,7 +100,8 @@ class MuZero:
             self.dy_func = None
         else:
             self.repr_func, self.pred_func, self.dy_func = self.network
-        self._last_route = None  # of the last act(): "fused_host", "fused", "stepwise"; "hip_stochastic_mlp", "callables"
+        # of the last act(): "fused_host", "fused", "stepwise"; "hip_stochastic_mlp", "hip_stochastic_one_launch", "callables"
+        self._last_route = None
         self._policy = policy_class()
         self._optimizer = optimizer
         self.loss_fn = loss_fn
@@ -112,6 +114,9 @@ class MuZero:
             torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu"))
         # plugin (non-default) nets: run the S x (select, recurrent_fn, expand_backup) loop as one hipGraph
         self.capture_graph = bool(capture_graph)
+        # default stochastic MLP family: the whole search in one launch wherever search.stochastic_plan admits the shape
+        # (off by default: the two routes give the same bits, the speed is measured on one shape only -- README)
+        self.stochastic_one_launch = bool(stochastic_one_launch)
         # captured root-inference graphs kept per weights version (one per observation shape; each pins its static
         # input and a private memory pool: hundreds of MB for Atari-shaped batches -- INTEGRATION.md)
         self.root_graph_cache = max(1, int(root_graph_cache))
@@ -458,7 +463,8 @@ class MuZero:
                          with_tree, global_batch, root_offset):
         """_route for an SMZNetwork: root inference on the torch modules, once; then the search with the decision and the
         chance function evaluated by the library (the default stochastic MLP family on a GPU, support_size 8..31:
-        MuZeroSearch.search_stochastic_mlp; MUAX_AMD_STOCHASTIC_MLP=0 switches it off) or, for plugin modules, by
+        MuZeroSearch.search_stochastic_mlp, as one launch with `stochastic_one_launch` where search.stochastic_plan admits
+        the shape; MUAX_AMD_STOCHASTIC_MLP=0 switches the library route off) or, for plugin modules, by
         StochasticMuZeroPolicy on callables built from them."""
         qt = getattr(qtransform, "__name__", qtransform)
         if qt not in (None, "qtransform_by_parent_and_siblings"):
@@ -474,13 +480,17 @@ class MuZero:
             h = self._handle(B, (A, num_simulations, root[2].shape[1], max_depth, tiebreak, pb_c_init, float(pb_c_base),
                                  global_batch, root_offset, "stochastic", "qtransform_by_parent_and_siblings", 16, 1.0, Cn),
                              self._bind_stochastic)
+            one_launch = self.stochastic_one_launch and stochastic_plan(A, Cn, root[2].shape[1], self._support_size,
+                                                                        num_simulations) is not None
             out = h.search_stochastic_mlp(root, key=key, invalid_actions=invalid_actions, dirichlet_noise=dirichlet_noise,
                                           dirichlet_fraction=dirichlet_fraction, temperature=temperature, gumbel=gumbel,
-                                          with_tree=with_tree, graph=self.capture_graph, graph_version=self._weights_version)
+                                          with_tree=with_tree, graph=self.capture_graph, graph_version=self._weights_version,
+                                          one_launch=one_launch)
             t = out.search_tree
             if t is not None:  # the decision slice, as StochasticMuZeroPolicy returns it (mctx _mask_tree)
                 t = t._replace(**{f: getattr(t, f)[..., :A] for f in t._fields if f.startswith("children_")})
-            return PolicyOutput(out.action, out.action_weights, t), root[1], None, "hip_stochastic_mlp"
+            return (PolicyOutput(out.action, out.action_weights, t), root[1], None,
+                    "hip_stochastic_one_launch" if one_launch else "hip_stochastic_mlp")
         shapes = {} if Cn is None else dict(num_chance_outcomes=Cn, afterstate_shape=tuple(root[2].shape[1:]))
         out = self._policy(self._params, key, root, decision_recurrent_fn=self._decision_inference,
                            chance_recurrent_fn=self._chance_inference, num_simulations=num_simulations,

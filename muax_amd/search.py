@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from ._call import capture, device_index, raw_stream
 from ._lib import (MLP_WEIGHT_NAMES, TREE_FIELDS, TREE_INT_FIELDS, MzsActArgs, MzsActHostArgs, MzsConfig,
-                   MzsMlpWeights, MzsStochasticMlpWeights, MzsStochasticOutputs, MzsTreeView,
+                   MzsMlpWeights, MzsStochasticMlpWeights, MzsStochasticOutputs, MzsStochasticSearchArgs, MzsTreeView,
                    STOCHASTIC_MLP_WEIGHT_NAMES)
 
 
@@ -118,6 +118,17 @@ def wide_plan(num_actions: int, embed_dim: int, support_size: int, num_simulatio
         raise ValueError(f"unknown policy: {policy!r}") from None
     out = (C.c_int32 * 4)()
     if _lib.load().mzs_mlp_wide_plan_policy(num_actions, embed_dim, support_size, num_simulations, pol, C.byref(out)) != 0:
+        return None
+    return dict(waves=out[0], lds_bytes=out[1], roots_per_cu=out[2], emb_lds=bool(out[3]))
+
+
+def stochastic_plan(num_actions: int, num_chance_outcomes: int, embed_dim: int, support_size: int, num_simulations: int):
+    """The one-launch stochastic search's LDS plan for a shape (mzs_mlp_stochastic_plan; host arithmetic, no device
+    needed): the dict of `wide_plan`, or None when the kernel declines the shape (num_actions + num_chance_outcomes > 64,
+    embed_dim > 64, support_size outside 8..31, more than 255 simulations, or one root's tree beyond a CU's 160 KiB)."""
+    out = (C.c_int32 * 4)()
+    if _lib.load().mzs_mlp_stochastic_plan(num_actions, num_chance_outcomes, embed_dim, support_size, num_simulations,
+                                           C.byref(out)) != 0:
         return None
     return dict(waves=out[0], lds_bytes=out[1], roots_per_cu=out[2], emb_lds=bool(out[3]))
 
@@ -663,15 +674,91 @@ class MuZeroSearch:
         self._run_loop(do_root, loop, graph, gkey, fns, graph_version)
         return self.finish_stochastic(temperature, gumbel, with_tree)
 
+    def _search_stochastic_one_launch(self, root_fn_output, gkey, key, invalid_actions, dirichlet_noise, dirichlet_fraction,
+                                      temperature, gumbel, with_tree, graph, graph_version) -> PolicyOutput:
+        """The whole search as ONE launch (mzs_mlp_stochastic_search).  graph: that launch captured as a one-node graph
+        per (gkey, which optional inputs are there, with_tree, graph_version) -- the inputs then travel through persistent
+        buffers and key, temperature and dirichlet_fraction through the entry's device block, so a replay sees this
+        call's values."""
+        B, A, S = self.batch, self.cfg.num_actions, self.cfg.num_simulations
+        prior_logits, value, embedding = root_fn_output
+        ins = dict(prior_logits=self._f32(prior_logits, (B, A), "prior_logits"), value=self._f32(value, (B,), "value"),
+                   embedding=self._f32(torch.as_tensor(embedding, device=self.device).reshape(B, -1), (B, self._es), "embedding"),
+                   invalid_actions=self._u8(invalid_actions, (B, A), "invalid_actions"),
+                   dirichlet_noise=self._f32(dirichlet_noise, (B, A), "dirichlet_noise"),
+                   gumbel=self._f32(gumbel, (B, A), "gumbel"))
+        fraction = dirichlet_fraction if ins["dirichlet_noise"] is not None else 0.0
+        kw = (C.c_uint32 * 2)(*key_words(key))
+
+        def launch(tensors, block):
+            a = _lib.args(MzsStochasticSearchArgs, export_tree=int(bool(with_tree)), key=tuple(kw), dirichlet_fraction=fraction,
+                          temperature=temperature, device_block=None if block is None else block.data_ptr(),
+                          action=self.action.data_ptr(), action_weights=self.action_weights.data_ptr(),
+                          search_value=self.search_value.data_ptr(), depth_sum=self.depth_sum.data_ptr(),
+                          **{n: None if t is None else t.data_ptr() for n, t in tensors.items()})
+            _lib.check(self._L.mzs_mlp_stochastic_search(self._h, C.byref(a), self._stream()), self._h)
+
+        if not graph:
+            launch(ins, None)
+            self._keep = tuple(ins.values())
+        else:
+            gk = (gkey, "one_launch", tuple(t is not None for t in ins.values()), bool(with_tree))
+            entry = self._graphs.get(gk)
+            if entry is not None and entry[3] != graph_version:
+                entry = None
+            if entry is None:
+                with torch.cuda.device(self.device):
+                    bufs = {n: None if t is None else torch.empty_like(t) for n, t in ins.items()}
+                    host = torch.empty(4 + 2 * S, dtype=torch.int32).pin_memory()
+                    block = torch.empty(4 + 2 * S, dtype=torch.int32, device=self.device)
+                stage = (bufs, host, block, torch.cuda.Event())
+            else:
+                stage = entry[1]
+            bufs, host, block, ev = stage
+            for n, t in ins.items():
+                if t is not None:
+                    bufs[n].copy_(t)
+            ev.synchronize()  # the previous upload has left the pinned block (no-op when it has, or never ran)
+            _lib.check(self._L.mzs_stochastic_search_block(C.byref(kw), S, temperature, fraction, host.data_ptr()))
+            with torch.cuda.device(self.device):
+                block.copy_(host, non_blocking=True)
+                ev.record(torch.cuda.current_stream(self.device))
+            if entry is None:
+                # warm-up run (the handle's first call may allocate; not under capture), then the capture (it records only)
+                side = torch.cuda.Stream(device=self.device)
+                side.wait_stream(torch.cuda.current_stream(self.device))
+                with torch.cuda.stream(side):
+                    launch(bufs, block)
+                torch.cuda.current_stream(self.device).wait_stream(side)
+                g = torch.cuda.CUDAGraph()
+                with capture(g):
+                    launch(bufs, block)
+                entry = self._graphs[gk] = (g, stage, self._stochastic_weights, graph_version)
+            entry[0].replay()
+        tree = None
+        if with_tree:
+            tree = self._alloc_tree()
+            view = self._tree_view(tree)
+            _lib.check(self._L.mzs_tree_export(self._h, C.byref(view), self._stream()), self._h)
+        return PolicyOutput(self.action, self.action_weights, tree)
+
     def search_stochastic_mlp(self, root_fn_output, key=0, invalid_actions=None, dirichlet_noise=None, dirichlet_fraction=0.25,
                               temperature=1.0, gumbel=None, with_tree=False, graph=False, graph_key=None,
-                              graph_version=0) -> PolicyOutput:
+                              graph_version=0, one_launch=False) -> PolicyOutput:
         """search_stochastic with the two callables replaced by the library's own evaluation of the default stochastic MLP
         family (set_stochastic_mlp_weights): three launches per simulation -- select, the function of each root's parent
         kind, expand + backward -- and no torch op.  Arguments as search_stochastic; the kernel reads the bound weight
-        arrays at every launch, so a captured loop sees in-place weight updates (a re-bound array: new graph_version)."""
+        arrays at every launch, so a captured loop sees in-place weight updates (a re-bound array: new graph_version).
+
+        one_launch=True: root set-up, every simulation and the finish in ONE launch with the tree in LDS
+        (mzs_mlp_stochastic_search) -- the same arguments, the same return value, the same bits; a captured graph is one
+        kernel node.  A shape `stochastic_plan` declines is then a ValueError naming the limit."""
         if self._stochastic_weights is None:
             raise ValueError("set_stochastic_mlp_weights() first")
+        if one_launch:
+            return self._search_stochastic_one_launch(root_fn_output, graph_key if graph_key is not None else "stochastic_mlp",
+                                                      key, invalid_actions, dirichlet_noise, dirichlet_fraction, temperature,
+                                                      gumbel, with_tree, graph, graph_version)
 
         def recurrent_expand(sim, slot, kind, pemb):
             self.expand_backup_stochastic_outputs(sim, self.stochastic_mlp_recurrent(slot, kind, pemb))

@@ -5,9 +5,11 @@ tree launches per simulation on either side.  Runs alternate between the two; me
 
     python tools/bench_stochastic.py [--sims 50] [--repeats 15] [--out FILE]
 
---mlp: the default stochastic MLP family (E = 16) searched two ways from the same root outputs -- the callable route
-(search_stochastic with the torch modules: both functions on every root, a few dozen small torch launches per simulation)
-and the library route (search_stochastic_mlp: one launch for the functions) -- eager and graph=True, alternating.
+--mlp: the default stochastic MLP family (E = 16) searched three ways from the same root outputs -- the callable route
+(search_stochastic with the torch modules: both functions on every root, a few dozen small torch launches per simulation),
+the step-wise library route (search_stochastic_mlp: one launch for the functions, three launches per simulation) and the
+one-launch route (search_stochastic_mlp(one_launch=True): the whole search in one launch, tree in LDS) -- at 64, 1024 and
+4096 roots, eager and graph=True, alternating.
 """
 import argparse
 import json
@@ -62,7 +64,7 @@ def timed(fn):
 
 
 def make_mlp(batch, sims, graph):
-    """(callable route, library route, handles) for one act of the default family at 2048's shape."""
+    """(callable route, library route, one-launch route, handles) for one act of the default family at 2048's shape."""
     import numpy as np
 
     import muax_amd as mx
@@ -73,31 +75,37 @@ def make_mlp(batch, sims, graph):
     g = torch.Generator().manual_seed(batch)
     root = m._root_inference_eager(torch.rand(batch, 16, generator=g).cuda())
     cfg = SearchConfig(A, sims, e, policy="stochastic", num_chance_outcomes=C)
-    hc, hl = MuZeroSearch(batch, cfg), MuZeroSearch(batch, cfg)
-    hl.set_stochastic_mlp_weights({k: v.detach() for k, v in mx.nn.stochastic_mlp_weights(net).items()}, 10, 0.99)
+    hc, hl, ho = MuZeroSearch(batch, cfg), MuZeroSearch(batch, cfg), MuZeroSearch(batch, cfg)
+    for h in (hl, ho):
+        h.set_stochastic_mlp_weights({k: v.detach() for k, v in mx.nn.stochastic_mlp_weights(net).items()}, 10, 0.99)
     dec = lambda a, s: m._decision_inference(None, None, a, s)  # noqa: E731
     cha = lambda c, s: m._chance_inference(None, None, c, s)  # noqa: E731
     return (lambda: hc.search_stochastic(root, dec, cha, key=1, dirichlet_fraction=0.0, graph=graph),
-            lambda: hl.search_stochastic_mlp(root, key=1, dirichlet_fraction=0.0, graph=graph), (hc, hl))
+            lambda: hl.search_stochastic_mlp(root, key=1, dirichlet_fraction=0.0, graph=graph),
+            lambda: ho.search_stochastic_mlp(root, key=1, dirichlet_fraction=0.0, graph=graph, one_launch=True), (hc, hl, ho))
 
 
 def main_mlp(args):
     rows = []
-    for batch in (64, 1024):
+    for batch in (64, 1024, 4096):
         for graph in (False, True):
-            call, lib, handles = make_mlp(batch, args.sims, graph)
+            call, lib, one, handles = make_mlp(batch, args.sims, graph)
             for _ in range(3):
-                call(), lib()
+                call(), lib(), one()
             torch.cuda.synchronize()
-            t = {"callables": [], "library": []}
+            same = torch.equal(handles[1].action_weights, handles[2].action_weights) and torch.equal(handles[1].action, handles[2].action)
+            t = {"callables": [], "library": [], "one_launch": []}
             for _ in range(args.repeats):  # alternating
                 t["callables"].append(timed(call))
                 t["library"].append(timed(lib))
+                t["one_launch"].append(timed(one))
             row = {"roots": batch, "sims": args.sims, "graph": graph}
             for k, v in t.items():
                 row[k] = {"median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1),
                           "per_sim_us": round(statistics.median(v) / args.sims, 2)}
             row["speedup_median"] = round(row["callables"]["median_us"] / row["library"]["median_us"], 2)
+            row["one_launch_speedup_median"] = round(row["library"]["median_us"] / row["one_launch"]["median_us"], 2)
+            row["one_launch_same_bits"] = same
             rows.append(row)
             print(json.dumps(row), flush=True)
             for h in handles:
