@@ -1,7 +1,7 @@
 """2048 with Stochastic MuZero: `muax.Device2048` stepped on the device, every act() the stochastic search over chance
 nodes (4 actions + 32 chance codes) on the default stochastic MLP family -- the decision and the chance function
 evaluated by the library, one launch per simulation --, training with `loss.stochastic_loss_fn` from a host
-`TrajectoryReplayBuffer`.
+`TrajectoryReplayBuffer` (on torch autograd, or with --fused-update on the fused training kernel of this shape).
 
 The loss encodes a chance code from EVERY step's observation, which `DeviceReplayBuffer.sample` does not hand out (it
 keeps the first row of a window), and `fit_vector(device_collect=True)` stores into that buffer only.  So this example
@@ -11,7 +11,8 @@ episodes (`episode_trajectory`) and goes into the host buffer.
 
 Nothing here has been run to a result: whether this recipe learns 2048 is not known.
 
-    python examples/fit_2048_stochastic.py [--envs 256] [--steps 64] [--iterations 3] [--updates 20]
+    python examples/fit_2048_stochastic.py [--envs 256] [--steps 64] [--iterations 3] [--updates 20] [--one-launch]
+                                           [--fused-update]
 """
 import argparse
 import json
@@ -69,13 +70,16 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--one-launch", action="store_true",
                     help="act() with the whole search in one launch (MuZero(stochastic_one_launch=True)): the same bits")
+    ap.add_argument("--fused-update", action="store_true",
+                    help="update() on the fused training kernel (MuZero(stochastic_fused_update=True)) instead of autograd")
     args = ap.parse_args()
 
     support_size, E, Cn, discount, k_steps = 31, 32, 32, 0.997, 5
     venv = muax.Device2048(args.envs, max_episode_steps=args.max_episode_steps, seed=args.seed, reward_shift=args.reward_shift)
     net = muax.create_stochastic_muzero_network(E, venv.num_actions, Cn, 2 * support_size + 1)
     model = muax.MuZero(net, policy="stochastic", discount=discount, support_size=support_size,
-                        optimizer=muax.optimizers.create_optimizer("adam", 2e-3), stochastic_one_launch=args.one_launch)
+                        optimizer=muax.optimizers.create_optimizer("adam", 2e-3), stochastic_one_launch=args.one_launch,
+                        stochastic_fused_update=args.fused_update)
     obs = venv.reset_device()
     model.init(args.seed, np.zeros((1, obs.shape[1]), np.float32))
     buffer = muax.TrajectoryReplayBuffer(2000, random_seed=args.seed)
@@ -92,7 +96,7 @@ def main():
             for _ in range(args.updates):
                 loss = model.update(buffer.sample(num_trajectory=32, k_steps=k_steps))["loss"]
         scores = [float(np.sum(tr.batched_transitions.r)) * 2 ** args.reward_shift for tr in episodes]
-        print(json.dumps({"iteration": it, "route": model._last_route, "episodes": len(episodes), "buffer": len(buffer),
+        print(json.dumps({"iteration": it, "route": model._last_route, "update_route": model._last_update_route, "episodes": len(episodes), "buffer": len(buffer),
                           "mean_score": round(float(np.mean(scores)), 1) if scores else None, "loss": round(loss, 4),
                           "collect_s": round(t1 - t0, 2), "update_s": round(time.perf_counter() - t1, 2)}), flush=True)
 

@@ -431,6 +431,67 @@ int mzs_mlp_loss_grad(const mzs_mlp_weights *w, const mzs_train_args *a, void *s
 int mzs_mlp_loss_grad_weighted(const mzs_mlp_weights *w, const mzs_train_args *a, const float *sample_weight,
                                void *stream);
 
+/* ---- training step of the default stochastic MLP family (muax_amd/csrc/mz_stoch_train.cuh) ----
+ * Loss and gradients of muax_amd/loss.py::stochastic_loss_fn for the six modules of
+ * nn.create_stochastic_muzero_network: step 0 contributes CE(v_0, Rn_0) + CE(pi_0, pi_0); transition i = 1 .. L-1, with
+ * action a_{i-1} and the chance code c_i = argmax encoder(obs_i) (the lowest index among equal maxima),
+ *   CE(r, r_{i-1}) + CE(v_i, Rn_i) + CE(pi_i, pi_i) + CE(chance logits, onehot(c_i)) + CE(afterstate value, Rn_{i-1})
+ *   + vqvae_beta * mean_C (encoder(obs_i) - onehot(c_i))^2,
+ * every term times loss_scale (times sample_weight[row] when given), plus l2_coeff * 0.5 * sum ||w||^2 over all 34
+ * arrays.  The gradient is one flat vector in the member order of mzs_stochastic_train_weights.  Two launches on
+ * `stream` that only enqueue (capturable), a fixed-order reduction: bit-reproducible run to run.
+ * The chance dynamics read the exact one-hot of c_i where the torch formula computes e + (onehot - e) in floating
+ * point (an ulp of the input apart).
+ * Refusals, all before any launch: a null pointer or a struct size mismatch, a workspace below
+ * mzs_stochastic_mlp_train_workspace_bytes (MZS_E_INVALID); obs_dim beyond 32, support_size outside 8 .. 31, an
+ * (A, C, E, F) without a listed kernel instance ("no kernel instance"), unroll_steps beyond what the instance keeps in
+ * LDS ("too large for the LDS", the limit named) (MZS_E_UNSUPPORTED). */
+typedef struct mzs_stochastic_train_weights {
+  int32_t struct_size;        /* = sizeof(mzs_stochastic_train_weights) */
+  int32_t obs_dim;            /* 1 .. 32 */
+  int32_t support_size;       /* 8 .. 31 */
+  int32_t reserved0;
+  const float *repr_w, *repr_b;               /* representation      [obs_dim,E] [E] */
+  const float *ad_w1, *ad_b1, *ad_w2, *ad_b2; /* the 28 arrays of mzs_stochastic_mlp_weights, in its order */
+  const float *av_w1, *av_b1, *av_w2, *av_b2;
+  const float *ac_w1, *ac_b1, *ac_w2, *ac_b2;
+  const float *cr_w1, *cr_b1, *cr_w2, *cr_b2;
+  const float *cn_w1, *cn_b1, *cn_w2, *cn_b2;
+  const float *pv_w1, *pv_b1, *pv_w2, *pv_b2;
+  const float *pp_w1, *pp_b1, *pp_w2, *pp_b2;
+  const float *en_w1, *en_b1, *en_w2, *en_b2; /* chance encoder      [obs_dim,16] [16] [16,C] [C] */
+} mzs_stochastic_train_weights;
+typedef struct mzs_stochastic_train_args {
+  int32_t struct_size;          /* = sizeof(mzs_stochastic_train_args) */
+  int32_t device;
+  int32_t batch;                /* B */
+  int32_t unroll_steps;         /* L */
+  int32_t num_actions;          /* A */
+  int32_t num_chance_outcomes;  /* C */
+  int32_t embed_dim;            /* E */
+  int32_t reserved0;
+  const float *obs;             /* [B, L, obs_dim]: an observation for every step */
+  const int32_t *actions;       /* [B, L] */
+  const float *rewards;         /* [B, L] */
+  const float *returns;         /* [B, L] */
+  const float *policy;          /* [B, L, A] */
+  const float *sample_weight;   /* [B] or NULL (all 1) */
+  float loss_scale;             /* 1/B or 1/(B L) */
+  float l2_coeff;               /* 1e-4 */
+  float vqvae_beta;             /* 0.25 */
+  float reserved1;
+  float *loss;                  /* [1] out */
+  float *grads;                 /* [mzs_stochastic_mlp_num_params] out */
+  void *workspace;              /* >= mzs_stochastic_mlp_train_workspace_bytes(...) */
+  int64_t workspace_bytes;
+} mzs_stochastic_train_args;
+int64_t mzs_stochastic_mlp_num_params(int32_t obs_dim, int32_t embed_dim, int32_t num_actions,
+                                      int32_t num_chance_outcomes, int32_t support_size);
+int64_t mzs_stochastic_mlp_train_workspace_bytes(int32_t batch, int32_t obs_dim, int32_t embed_dim, int32_t num_actions,
+                                                 int32_t num_chance_outcomes, int32_t support_size);
+/* errors: mzs_last_error(NULL) */
+int mzs_stochastic_mlp_loss_grad(const mzs_stochastic_train_weights *w, const mzs_stochastic_train_args *a, void *stream);
+
 /* ---- next-state tower of the ResNet dynamics net ----
  * mzs_resnet_tower evaluates, for a batch of 6x6x64 hidden states (NHWC, the reference's embedding
  * layout), what muax/nn.py:344-378 calls ns_func followed by min_max_normalize2d: conv1x1 on

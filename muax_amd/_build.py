@@ -3,7 +3,7 @@
 The library is several translation units compiled in parallel (each `hipcc -c`, objects under muax_amd/lib/obj/)
 and linked into one shared object: the C-ABI's handle and registries (mz_api.hip) and one unit per route -- the fused
 act() dispatch (mz_act.hip), the step-wise path, the generic one-launch search and the stochastic MLP family's recurrent step with the
-step kernels (mz_stepwise.hip), the training step (mz_train.hip), the self-test and Dirichlet kernels (mz_selftest.hip) --, the
+step kernels (mz_stepwise.hip), the training step (mz_train.hip; the stochastic family's in mz_stoch_train.hip), the self-test and Dirichlet kernels (mz_selftest.hip) --, the
 fused act() kernel instances in five groups (mz_fused_g*.hip, listed in mz_instances.def), the wide-action act()
 kernel (mz_wide.hip), the one-launch stochastic search (mz_stoch_wide.hip), the ResNet recurrent kernel (mz_conv.hip), the device-resident replay (mz_replay.hip), the
 forward value unroll behind its priorities (mz_unroll.hip) and the device vector environments (mz_env.hip; 2048 with its
@@ -29,6 +29,7 @@ UNITS = {
     "mz_stepwise.hip": _HANDLE + ["mz_mlp_generic.cuh", "mz_step_kernels.cuh", "mz_stoch_mlp.cuh", "mz_stoch_wide_launch.h",
                         "mz_wide_launch.h", "mz_fused_launch.h", "mz_fused.cuh"],
     "mz_train.hip": ["mz_host.h", "mz_train_launch.h", "mz_train.cuh", "mz_spec.cuh", _ABI],
+    "mz_stoch_train.hip": ["mz_host.h", "mz_stoch_train.cuh", "mz_train.cuh", "mz_spec.cuh", _ABI],
     "mz_selftest.hip": ["mz_host.h", "mz_dirichlet.cuh", "mz_spec.cuh", _ABI],
     "mz_fused_g0.hip": _FUSED,
     "mz_fused_g1.hip": _FUSED,

@@ -65,10 +65,11 @@ def capture(graph):
 class MlpWeights:
     """The MzsMlpWeights struct of the default trio's 18 parameter tensors (`params`, in MLP_WEIGHT_NAMES order), kept
     and rebuilt only when a tensor moved (optimisers update in place) or is not contiguous.  The callers set the scalar
-    fields (obs_dim, support_size, discount) themselves."""
+    fields (obs_dim, support_size, discount) themselves.  `cls`, `names`: another weight struct of the same kind and its
+    pointer members in the order of `params` (the stochastic family's 34: MzsStochasticTrainWeights)."""
 
-    def __init__(self, params):
-        self.params = params
+    def __init__(self, params, cls=_lib.MzsMlpWeights, names=_lib.MLP_WEIGHT_NAMES):
+        self.params, self._cls, self._names = params, cls, names
         self._w = self._keep = self._ptrs = None
 
     def get(self):
@@ -76,7 +77,7 @@ class MlpWeights:
         ptrs = tuple(x.data_ptr() for x in self.params)
         if ptrs != self._ptrs or not all(x.is_contiguous() for x in self.params):
             keep = [x.detach().contiguous() for x in self.params]
-            self._w = _lib.args(_lib.MzsMlpWeights, **{n: x.data_ptr() for n, x in zip(_lib.MLP_WEIGHT_NAMES, keep)})
+            self._w = _lib.args(self._cls, **{n: x.data_ptr() for n, x in zip(self._names, keep)})
             self._keep = keep
             # a contiguous copy is not cached: it would go stale under an in-place update of its original
             self._ptrs = ptrs if all(k.data_ptr() == q for k, q in zip(keep, ptrs)) else None

@@ -50,6 +50,24 @@ class MzsStochasticSearchArgs(C.Structure):
                 ("depth_sum", _vp)]
 
 
+# the 34 arrays of mzs_stochastic_train_weights (the fused stochastic training step), in the struct's order
+STOCHASTIC_TRAIN_WEIGHT_NAMES = ["repr_w", "repr_b"] + STOCHASTIC_MLP_WEIGHT_NAMES + ["en_w1", "en_b1", "en_w2", "en_b2"]
+
+
+class MzsStochasticTrainWeights(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("obs_dim", C.c_int32), ("support_size", C.c_int32), ("reserved0", C.c_int32)]
+                + [(n, _vp) for n in STOCHASTIC_TRAIN_WEIGHT_NAMES])
+
+
+class MzsStochasticTrainArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("device", C.c_int32), ("batch", C.c_int32), ("unroll_steps", C.c_int32),
+                ("num_actions", C.c_int32), ("num_chance_outcomes", C.c_int32), ("embed_dim", C.c_int32),
+                ("reserved0", C.c_int32), ("obs", _vp), ("actions", _vp), ("rewards", _vp), ("returns", _vp),
+                ("policy", _vp), ("sample_weight", _vp), ("loss_scale", C.c_float), ("l2_coeff", C.c_float),
+                ("vqvae_beta", C.c_float), ("reserved1", C.c_float), ("loss", _vp), ("grads", _vp), ("workspace", _vp),
+                ("workspace_bytes", C.c_int64)]
+
+
 MLP_WEIGHT_NAMES = ["repr_w", "repr_b", "pv_w1", "pv_b1", "pv_w2", "pv_b2", "pp_w1", "pp_b1", "pp_w2",
                     "pp_b2", "dr_w1", "dr_b1", "dr_w2", "dr_b2", "dn_w1", "dn_b1", "dn_w2", "dn_b2"]
 
@@ -283,7 +301,9 @@ EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_dest
                     "mzs_env_2048_reset", "mzs_env_2048_step", "mzs_env_2048_mask",
                     "mzs_root_stochastic", "mzs_select_stochastic", "mzs_expand_backup_stochastic",
                     "mzs_finish_stochastic", "mzs_mlp_set_stochastic_weights", "mzs_mlp_stochastic_recurrent",
-                    "mzs_mlp_stochastic_plan", "mzs_mlp_stochastic_search", "mzs_stochastic_search_block"]
+                    "mzs_mlp_stochastic_plan", "mzs_mlp_stochastic_search", "mzs_stochastic_search_block",
+                    "mzs_stochastic_mlp_loss_grad", "mzs_stochastic_mlp_num_params",
+                    "mzs_stochastic_mlp_train_workspace_bytes"]
 
 _lib = None
 
@@ -348,6 +368,11 @@ def load(build_if_missing: bool = True):
     for n in EXPORTED_SYMBOLS[2:]:
         getattr(L, n).restype = C.c_int
     L.mzs_mlp_num_params.restype = C.c_int64
+    L.mzs_stochastic_mlp_num_params.argtypes = [C.c_int32] * 5
+    L.mzs_stochastic_mlp_num_params.restype = C.c_int64
+    L.mzs_stochastic_mlp_train_workspace_bytes.argtypes = [C.c_int32] * 6
+    L.mzs_stochastic_mlp_train_workspace_bytes.restype = C.c_int64
+    L.mzs_stochastic_mlp_loss_grad.argtypes = [C.POINTER(MzsStochasticTrainWeights), C.POINTER(MzsStochasticTrainArgs), _vp]
     L.mzs_mlp_train_workspace_bytes.restype = C.c_int64
     L.mzs_dirichlet.argtypes = [C.c_int32, C.POINTER(C.c_uint32 * 2), C.c_float, C.c_int32, C.c_int32, C.c_int64,
                                 C.c_int64, _vp, _vp]

@@ -23,7 +23,8 @@ routes; the L2 term is not weighted.
 `stochastic_loss_fn` is the Stochastic MuZero loss of the reference's acme agent
 (muax/frameworks/acme/jax/stochastic_muzero/learning.py:200-277) in the conventions above -- a sum over steps, support
 targets by scalar_to_support, the same L2 term over all six modules, the halved hidden-state gradient before each
-afterstate step -- on torch autograd only.  Its reference quirks:
+afterstate step -- on torch autograd; `StochasticFusedLossGrad` (below) is the same loss and its gradients from one HIP
+kernel for the default stochastic MLP family.  Its reference quirks:
   * learning.py:262 measures the VQ commitment against the straight-through code, whose value is the one-hot but whose
     gradient is the encoder output's own: the term's gradient is identically zero.  Here the encoder output commits to
     the DETACHED one-hot, which is what a commitment term is for;
@@ -225,4 +226,81 @@ class FusedLossGrad:
         else:
             _lib.check(self._L.mzs_mlp_loss_grad_weighted(C.byref(w), C.byref(args), sw.data_ptr(), stream))
         self._keep, self._keep_w = (obs, a, r, Rn, pi, keep), sw
+        return self.loss, self.grads
+
+
+class StochasticFusedLossGrad:
+    """value_and_grad of `stochastic_loss_fn` for the default stochastic MLP family, `FusedLossGrad`'s sibling: loss and
+    every gradient from one forward+backward HIP kernel and its fixed-order reduction (muax_amd/csrc/mz_stoch_train.cuh
+    through mzs_stochastic_mlp_loss_grad).  The gradient is ONE flat fp32 vector in the C-ABI's order of the 34 arrays
+    (`_lib.STOCHASTIC_TRAIN_WEIGHT_NAMES`); `views` maps it onto the parameters.  The kernel hands the chance dynamics the
+    exact one-hot of the code where `stochastic_loss_fn` computes e + (onehot - e) in floating point."""
+
+    def __init__(self, muzero_instance):
+        from . import nn as mz_nn
+        if not mz_nn.is_default_stochastic_mlp(muzero_instance.network):
+            raise ValueError("the fused stochastic training step is built for the default stochastic MLP family")
+        self.m = muzero_instance
+        self._L = _lib.load()
+        params = mz_nn.stochastic_train_weights(muzero_instance.network)
+        self.params = [params[n] for n in _lib.STOCHASTIC_TRAIN_WEIGHT_NAMES]
+        dev = self.params[0].device
+        if dev.type != "cuda":
+            raise RuntimeError("muax_amd needs a ROCm GPU (gfx950); there is no CPU fallback")
+        r, p, _, ap, _, _ = muzero_instance.network
+        self.obs_dim, self.E, self.A, self.C = r.obs_dim, r.embedding_dim, p.num_actions, ap.num_actions
+        self.S = muzero_instance._support_size
+        n = int(self._L.mzs_stochastic_mlp_num_params(self.obs_dim, self.E, self.A, self.C, self.S))
+        assert n == sum(x.numel() for x in self.params)
+        self.grads = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.views, off = [], 0
+        for x in self.params:
+            self.views.append(self.grads[off:off + x.numel()].view_as(x))
+            off += x.numel()
+        self._ws = None
+        self._weights = _call.MlpWeights(self.params, _lib.MzsStochasticTrainWeights, _lib.STOCHASTIC_TRAIN_WEIGHT_NAMES)
+
+    def __call__(self, batch: Transition, vqvae_beta: float = 0.25, divide_by_length: bool = False, sample_weight=None):
+        """(loss [1], flat gradient) of the batch; `batch.obs` is [B, L, obs_dim], an observation for every step."""
+        dev = self.grads.device
+
+        def t(x, dt):
+            if isinstance(x, torch.Tensor) and x.dtype == dt and x.device == dev and x.is_contiguous():
+                return x
+            return torch.as_tensor(x, device=dev).to(dt).contiguous()
+        a = t(batch.a, torch.int32)
+        B, L = a.shape[:2]
+        a = a.reshape(B, L)
+        obs = t(batch.obs, torch.float32)
+        if obs.dim() < 3 or obs.shape[0] != B or obs.shape[1] < L:
+            raise ValueError(f"the stochastic loss needs every step's observation: batch.obs must be [B, L, ...] with L = {L} "
+                             f"rows per window, got {tuple(obs.shape)} (DeviceReplayBuffer.sample keeps the first row only)")
+        obs = obs[:, :L].reshape(B, L, -1).contiguous()
+        if obs.shape[2] != self.obs_dim:
+            raise ValueError(f"batch.obs has {obs.shape[2]} features, the network takes {self.obs_dim}")
+        r, Rn = t(batch.r, torch.float32).reshape(B, L), t(batch.Rn, torch.float32).reshape(B, L)
+        pi = t(batch.pi, torch.float32).reshape(B, L, self.A)
+        sw = None
+        if sample_weight is not None:  # (the shape alone: looking at the values would synchronise)
+            if tuple(getattr(sample_weight, "shape", ())) != (B,):
+                raise ValueError(f"sample_weight must be [B] with B = {B}, got "
+                                 f"{tuple(getattr(sample_weight, 'shape', ()))}")
+            sw = t(sample_weight.detach() if isinstance(sample_weight, torch.Tensor) else sample_weight, torch.float32)
+        need = int(self._L.mzs_stochastic_mlp_train_workspace_bytes(B, self.obs_dim, self.E, self.A, self.C, self.S))
+        if self._ws is None or self._ws.numel() * 4 < need:
+            self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+        w, keep = self._weights.get()
+        w.obs_dim, w.support_size = self.obs_dim, self.S
+        idx = _call.device_index(dev)
+        args = _lib.args(_lib.MzsStochasticTrainArgs, device=idx, batch=B, unroll_steps=L, num_actions=self.A,
+                         num_chance_outcomes=self.C, embed_dim=self.E, obs=obs.data_ptr(), actions=a.data_ptr(),
+                         rewards=r.data_ptr(), returns=Rn.data_ptr(), policy=pi.data_ptr(),
+                         sample_weight=None if sw is None else sw.data_ptr(),
+                         loss_scale=1.0 / (B * L) if divide_by_length else 1.0 / B, l2_coeff=1e-4,
+                         vqvae_beta=float(vqvae_beta), loss=self.loss.data_ptr(), grads=self.grads.data_ptr(),
+                         workspace=self._ws.data_ptr(), workspace_bytes=self._ws.numel() * 4)
+        with torch.cuda.device(idx):
+            _lib.check(self._L.mzs_stochastic_mlp_loss_grad(C.byref(w), C.byref(args), _call.raw_stream(idx)))
+        self._keep = (obs, a, r, Rn, pi, sw, keep)
         return self.loss, self.grads

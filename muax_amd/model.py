@@ -72,7 +72,7 @@ class MuZero:
                  policy: Optional[str] = None, optimizer=None, loss_fn=None, discount: float = 0.99,
                  support_size: int = 10, recurrent_pred_on: str = "child", device=None,
                  representation_fn=None, capture_graph: bool = False, root_graph_cache: int = 2,
-                 stochastic_one_launch: bool = False):
+                 stochastic_one_launch: bool = False, stochastic_fused_update: bool = False):
         self._stochastic = isinstance(network, SMZNetwork)
         if self._stochastic:
             if policy not in (None, "stochastic"):
@@ -117,6 +117,10 @@ class MuZero:
         # default stochastic MLP family: the whole search in one launch wherever search.stochastic_plan admits the shape
         # (off by default: the two routes give the same bits, the speed is measured on one shape only -- README)
         self.stochastic_one_launch = bool(stochastic_one_launch)
+        # default stochastic MLP family: update() takes loss and gradients from the fused training kernel
+        # (loss.StochasticFusedLossGrad) instead of torch autograd (off by default: timed on two shapes only -- README)
+        self.stochastic_fused_update = bool(stochastic_fused_update)
+        self._last_update_route = None  # of the last update(): "hip_stochastic_fused", "hip_fused", "torch"
         # captured root-inference graphs kept per weights version (one per observation shape; each pins its static
         # input and a private memory pool: hundreds of MB for Atari-shaped batches -- INTEGRATION.md)
         self.root_graph_cache = max(1, int(root_graph_cache))
@@ -125,6 +129,7 @@ class MuZero:
         self._loaded_opt_state = None
         self._param_list = None
         self._fused_train = None
+        self._fused_stoch_train = None
         self._fused_unroll = None
         self._disc_const = None
         self._fused = {}
@@ -159,6 +164,7 @@ class MuZero:
                                          for m in self.network])
         self._weights_version += 1
         self._fused_train = None
+        self._fused_stoch_train = None
         self._fused_unroll = None
         return self._params
 
@@ -614,6 +620,11 @@ class MuZero:
         vector; the data-parallel gradient mean is then one all-reduce of that vector (RCCL on GPUs) and the
         optimiser (muax/optimizers.py mirror on torch.optim) consumes views of it.  Plugin nets or a custom
         loss_fn take the torch autograd route (backend="torch" forces it; "hip" refuses to fall back).
+        An SMZNetwork runs loss.stochastic_loss_fn on autograd; a model made with `stochastic_fused_update=True` takes the
+        default stochastic MLP family's step (obs_dim up to 32, no custom loss_fn) from its own fused kernel instead
+        (mzs_stochastic_mlp_loss_grad, muax_amd/csrc/mz_stoch_train.cuh; `vqvae_beta`, `divide_by_length` and
+        `sample_weight` reach it), "auto" falling to autograd for a shape without a listed instance or an unroll beyond
+        the kernel's LDS.  `_last_update_route` names the route taken: "hip_stochastic_fused", "hip_fused" or "torch".
         `dp_mean=False` skips the gradient mean over the ranks of an initialised process group (a rank-local step:
         bench.py times update() with and without its collective).
         `sample_weight` [B]: importance-sampling weights (`DeviceReplayBuffer.sample(is_beta=)`); row b's cross
@@ -647,9 +658,31 @@ class MuZero:
         fused = backend != "torch" and self.loss_fn is None and self.device.type == "cuda" \
             and mz_nn.is_default_mlp_trio(self.network) and (self.repr_func.obs_dim or 999) <= 128 \
             and not kwargs.get("pi_all_pairs", False)
-        if backend == "hip" and not fused:
+        # ... and, with `stochastic_fused_update`, the default stochastic family under its own loss and that loss's keywords
+        stoch_fused = self.stochastic_fused_update and backend != "torch" and self.loss_fn is None \
+            and self.device.type == "cuda" and mz_nn.is_default_stochastic_mlp(self.network) \
+            and (self.repr_func.obs_dim or 999) <= 32 and not args \
+            and set(kwargs) <= {"vqvae_beta", "divide_by_length", "sample_weight"}
+        if stoch_fused:
+            try:
+                if self._fused_stoch_train is None:
+                    self._fused_stoch_train = mz_loss.StochasticFusedLossGrad(self)
+                loss, flat = self._fused_stoch_train(batch, vqvae_beta=kwargs.get("vqvae_beta", 0.25),
+                                                     divide_by_length=kwargs.get("divide_by_length", False),
+                                                     sample_weight=sample_weight)
+                if dp_mean:
+                    allreduce_mean_flat([flat])
+                for p, g in zip(self._fused_stoch_train.params, self._fused_stoch_train.views):
+                    p.grad = g
+            except (_lib.NoKernelInstance, _lib.TooLargeForLds):  # (refused on the host, before any launch)
+                if backend == "hip":
+                    raise
+                stoch_fused = False
+        if backend == "hip" and not (fused or stoch_fused):
             raise ValueError("backend='hip' needs the default MLP trio on a GPU and the default loss"
-                             + (" (the stochastic loss of an SMZNetwork runs on torch autograd only)" if self._stochastic else ""))
+                             + (" (the stochastic loss of an SMZNetwork runs on torch autograd only, unless the model was made with "
+                                "stochastic_fused_update=True: the default stochastic MLP family on a GPU, obs_dim up to 32)"
+                                if self._stochastic else ""))
         if fused:
             try:
                 if self._fused_train is None:
@@ -678,12 +711,13 @@ class MuZero:
                 if backend == "hip":
                     raise
                 fused = False
-        if not fused:
+        if not (fused or stoch_fused):
             loss_fn = self.loss_fn or (mz_loss.stochastic_loss_fn if self._stochastic else mz_loss.default_loss_fn)
             loss = loss_fn(self, batch, *args, **kwargs)
             loss.backward()
             if dp_mean:
                 allreduce_mean_flat([p.grad for p in all_params()])
+        self._last_update_route = "hip_stochastic_fused" if stoch_fused else "hip_fused" if fused else "torch"
         self._optimizer.step()
         self._weights_version += 1
         return {"loss": float(loss.item())}

@@ -295,6 +295,14 @@ def stochastic_mlp_weights(network: SMZNetwork) -> dict:
     return {f"{h}_{n}{i + 1}": getattr(m[i], n) for h, m in heads.items() for i in (0, 1) for n in ("w", "b")}
 
 
+def stochastic_train_weights(network: SMZNetwork) -> dict:
+    """All 34 arrays of the family in the order of mzs_stochastic_train_weights: the representation's two, the 28 above,
+    the encoder's four."""
+    r, en = network[0], network[5]
+    return {"repr_w": r.repr_func.w, "repr_b": r.repr_func.b, **stochastic_mlp_weights(network),
+            "en_w1": en.enc_func[0].w, "en_b1": en.enc_func[0].b, "en_w2": en.enc_func[1].w, "en_b2": en.enc_func[1].b}
+
+
 # ---------------------------------------------------------------------------------------------------
 # Convolutional plugin nets (SURVEY.md 8(f) n3; muax/nn.py:47-56,118-395) as torch modules (MIOpen / hipBLASLt
 # kernels underneath) that the step-wise search drives -- optionally as one hipGraph (MuZero(capture_graph=True)).

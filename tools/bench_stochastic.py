@@ -10,6 +10,13 @@ tree launches per simulation on either side.  Runs alternate between the two; me
 the step-wise library route (search_stochastic_mlp: one launch for the functions, three launches per simulation) and the
 one-launch route (search_stochastic_mlp(one_launch=True): the whole search in one launch, tree in LDS) -- at 64, 1024 and
 4096 roots, eager and graph=True, alternating.
+
+--train: the training step of the default family at (A, C, E, F) = (4, 32, 16, 21) and (4, 32, 32, 63), obs_dim 16,
+L = 5, B = 32 and 1024: loss plus gradients (loss.StochasticFusedLossGrad against stochastic_loss_fn + backward) and the
+whole update() (MuZero(stochastic_fused_update=True) under backend="hip" against backend="torch", Adam), the two routes
+alternating in one process after warm_runtime().  Host wall time around a synchronised call, in microseconds: the
+torch route is launch-bound, so its figure is mostly host time and moves with the load of the machine; median, min
+and max over `--repeats` (at least 15).
 """
 import argparse
 import json
@@ -115,13 +122,76 @@ def main_mlp(args):
             json.dump(rows, f, indent=1)
 
 
+def wall(fn):
+    import time
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e6  # us
+
+
+def main_train(args):
+    import numpy as np
+
+    import muax_amd as mx
+    from muax_amd.utils import warm_runtime
+    warm_runtime()
+    repeats = max(15, args.repeats)
+    rows = []
+    od, L = 16, 5
+    for e, support in ((16, 10), (32, 31)):
+        for batch in (32, 1024):
+            rng = np.random.default_rng(batch)
+            b = mx.Transition(obs=torch.from_numpy(rng.uniform(0, 1, (batch, L, od)).astype(np.float32)).cuda(),
+                              a=torch.from_numpy(rng.integers(0, A, (batch, L)).astype(np.int32)).cuda(),
+                              r=torch.from_numpy(rng.uniform(-1, 2, (batch, L)).astype(np.float32)).cuda(),
+                              Rn=torch.from_numpy(rng.uniform(-5, 9, (batch, L)).astype(np.float32)).cuda(),
+                              pi=torch.from_numpy(rng.dirichlet(np.ones(A), (batch, L)).astype(np.float32)).cuda())
+            models = {}
+            for route in ("fused", "torch"):
+                net = mx.create_stochastic_muzero_network(e, A, C, 2 * support + 1, generator=torch.Generator().manual_seed(1))
+                m = models[route] = mx.MuZero(net, policy="stochastic", support_size=support, stochastic_fused_update=True,
+                                              optimizer=mx.optimizers.create_optimizer("adam", 1e-3))
+                m.init(0, np.zeros((1, od), np.float32))
+            fused = mx.loss.StochasticFusedLossGrad(models["fused"])
+
+            def grad_torch(m=models["torch"]):
+                for mod in m.network:
+                    mod.zero_grad(set_to_none=True)
+                mx.loss.stochastic_loss_fn(m, b).backward()
+            calls = {"loss_grad": {"fused": lambda: fused(b), "torch": grad_torch},
+                     "update": {"fused": lambda: models["fused"].update(b, backend="hip"),
+                                "torch": lambda: models["torch"].update(b, backend="torch")}}
+            row = {"A": A, "C": C, "E": e, "F": 2 * support + 1, "obs_dim": od, "L": L, "B": batch, "repeats": repeats}
+            for what, pair in calls.items():
+                for _ in range(5):  # warm-up: workspace, optimiser state, torch's autograd caches
+                    pair["fused"](), pair["torch"]()
+                t = {"fused": [], "torch": []}
+                for _ in range(repeats):  # alternating
+                    for k in ("fused", "torch"):
+                        t[k].append(wall(pair[k]))
+                row[what] = {k: {"median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1),
+                                 "max_us": round(max(v), 1)} for k, v in t.items()}
+                row[what]["torch_over_fused_median"] = round(row[what]["torch"]["median_us"] / row[what]["fused"]["median_us"], 2)
+            assert models["fused"]._last_update_route == "hip_stochastic_fused" and models["torch"]._last_update_route == "torch"
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sims", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=15)
     ap.add_argument("--out")
     ap.add_argument("--mlp", action="store_true")
+    ap.add_argument("--train", action="store_true")
     args = ap.parse_args()
+    if args.train:
+        return main_train(args)
     if args.mlp:
         return main_mlp(args)
     rows = []
