@@ -28,8 +28,8 @@ UNITS = {
     "mz_act.hip": _HANDLE + ["mz_fused_launch.h", "mz_fused.cuh", "mz_wide_launch.h"],
     "mz_stepwise.hip": _HANDLE + ["mz_mlp_generic.cuh", "mz_step_kernels.cuh", "mz_stoch_mlp.cuh", "mz_stoch_wide_launch.h",
                         "mz_wide_launch.h", "mz_fused_launch.h", "mz_fused.cuh"],
-    "mz_train.hip": ["mz_host.h", "mz_train_launch.h", "mz_train.cuh", "mz_spec.cuh", _ABI],
-    "mz_stoch_train.hip": ["mz_host.h", "mz_stoch_train.cuh", "mz_train.cuh", "mz_spec.cuh", _ABI],
+    "mz_train.hip": ["mz_host.h", "mz_train_launch.h", "mz_train.cuh", "mz_train_blocks.cuh", "mz_spec.cuh", _ABI],
+    "mz_stoch_train.hip": ["mz_host.h", "mz_train_launch.h", "mz_stoch_train.cuh", "mz_train_blocks.cuh", "mz_spec.cuh", _ABI],
     "mz_selftest.hip": ["mz_host.h", "mz_dirichlet.cuh", "mz_spec.cuh", _ABI],
     "mz_fused_g0.hip": _FUSED,
     "mz_fused_g1.hip": _FUSED,

@@ -22,7 +22,7 @@ JIT_DIR = os.path.join(_build.LIB_DIR, "jit")
 _SOURCES = ["mz_fused_jit.hip", "mz_fused_group.inc", "mz_fused_launch.h", "mz_fused.cuh", "mz_spec.cuh", "mz_host.h"]
 _loaded = {}   # shape -> CDLL (kept alive: the library calls into it)
 _failed = set()
-_TRAIN_SOURCES = ["mz_train_jit.hip", "mz_train_launch.h", "mz_train.cuh", "mz_spec.cuh", "mz_host.h"]
+_TRAIN_SOURCES = ["mz_train_jit.hip", "mz_train_launch.h", "mz_train.cuh", "mz_train_blocks.cuh", "mz_spec.cuh", "mz_host.h"]
 # Bump when plan() changes its answer for any shape: the number is part of every cached file's name (and this file is
 # hashed into it as well), so a cache directory that survives a planner change cannot serve an instance whose record
 # kind / roots per workgroup differ from what the planner now says.

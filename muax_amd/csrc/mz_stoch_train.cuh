@@ -2,12 +2,9 @@
 // the default stochastic MLP family (nn.create_stochastic_muzero_network): six modules, seven Linear(16)-elu-Linear
 // stacks, the representation and the chance encoder.
 //
-// The mapping and every arithmetic block are mz_train.cuh's: one sample per DPP row of 16 lanes (feature k in lane
-// k & 15, slot k >> 4), four samples per wavefront, 16 per 256-thread workgroup; the weights in LDS as [K][ld(N)] blocks
-// with odd strides; the weight-gradient tiles (fp32 MFMA 16x16x4, the sample index as k) stay in accumulators across the
-// unroll steps; each wavefront writes one partial row to the workspace and a second launch sums the rows in a fixed
-// order and adds the L2 term.  No float atomics.  What differs is the graph and its 34 arrays, so TrainParams and the
-// reduction have siblings here; mz_train.cuh is untouched.
+// The mapping, the argument block, every arithmetic block and the reduction are mz_train_blocks.cuh's, shared with
+// mz_train.cuh; this file is the graph of the family: StochTrainCfg (the LDS plan of an (A, C, E, F) instance), the
+// encoder's forward and mz_stoch_train_kernel, whose partial rows go to mz_train_reduce_kernel<34>.
 //
 // Sweep 1 walks s_0 -> (after_1, c_1, s_1) -> ... through the encoder's argmax (the LOWEST index among equal maxima,
 // torch.argmax on the CPU), the afterstate dynamics and the chance dynamics' next-state branch, and keeps s_i, after_i and
@@ -17,15 +14,10 @@
 // dynamics' two stacks leave on their code inputs (straight through) plus the commitment term's; the chance-logit cross
 // entropy gives it nothing (detached target).
 //
-// One liberty: the chance dynamics and the chance-logit target read the EXACT one-hot of c_i where torch computes
-// e + (onehot - e) in floating point; the two differ by an ulp of the input.
+// One liberty: the chance dynamics and the chance-logit target read the EXACT one-hot of c_i (concat_onehot) where torch
+// computes e + (onehot - e) in floating point; the two differ by an ulp of the input.
 #pragma once
-// mz_train.cuh also DEFINES its reduction kernel, which is no template: a second translation unit that includes it
-// beside mz_train.hip would define the same symbol again.  This unit only wants the device functions, so it takes that
-// kernel under another name (never launched here); mz_train.cuh itself stays as it is.
-#define mz_train_reduce_kernel mz_train_reduce_kernel_unused_by_stoch_train
-#include "mz_train.cuh"
-#undef mz_train_reduce_kernel
+#include "mz_train_blocks.cuh"
 
 #pragma clang fp contract(off)
 
@@ -33,30 +25,16 @@ namespace mz {
 
 constexpr int STOCH_TRAIN_ARRAYS = 34;
 constexpr int STOCH_TRAIN_MAX_OBS = 32;  // two slots of encoder-layer tiles; mzs_stochastic_mlp_loss_grad names it
-
-struct StochTrainParams {
-  const float* obs;     // [B][L][obs_dim]
-  const int32_t* act;   // [B][L]
-  const float* rew;     // [B][L]
-  const float* ret;     // [B][L]
-  const float* pi;      // [B][L][A]
-  // repr_w, repr_b; ad, av, ac, cr, cn, pv, pp each w1, b1, w2, b2 (mzs_stochastic_mlp_weights' order); en_w1 .. en_b2
-  const float* w[STOCH_TRAIN_ARRAYS];
-  int off[STOCH_TRAIN_ARRAYS + 1];  // flat offsets in the gradient vector; off[34] = total
-  int B, L, obs_dim, support;
-  float loss_scale, l2, beta;
-  float* ws;            // [waves][off[34] + 1]
-  float* grads;         // [off[34]]
-  float* loss;          // [1]
-  int waves;
-  const float* row_w;   // [B] or null
-};
+// repr_w, repr_b; ad, av, ac, cr, cn, pv, pp each w1, b1, w2, b2 (mzs_stochastic_mlp_weights' order); en_w1 .. en_b2
+using StochTrainParams = TrainParamsT<STOCH_TRAIN_ARRAYS>;
 
 template <int A_, int C_, int E_, int F_>
 struct StochTrainCfg {
   static constexpr int A = A_, C = C_, E = E_, F = F_, H = 16, XA = E_ + A_, XC = E_ + C_;
   static constexpr int ES = (E + 15) / 16, FS = (F + 15) / 16, CS = (C + 15) / 16, AS = 1;
   static constexpr int XAS = (XA + 15) / 16, XCS = (XC + 15) / 16, OS = STOCH_TRAIN_MAX_OBS / 16;
+  static constexpr int NA = STOCH_TRAIN_ARRAYS;
+  static constexpr const char* DIMS = "(A, C, E, F)";
   static_assert(A <= 16, "policy head in one slot");
   static_assert(C <= 64 && E <= 64 && F <= 63, "at most four slots per vector");
   static constexpr int ld(int n) { return 16 * ((n + 15) / 16) + 1; }
@@ -84,87 +62,6 @@ struct StochTrainCfg {
   static constexpr int CK_WORDS_PER_STEP = CK_CODE + 16;
   static constexpr int MAX_UNROLL = (TRAIN_LDS_BYTES / 4 - WEIGHT_WORDS) / CK_WORDS_PER_STEP;
 };
-
-// index of the largest of the C logits of a row, the lowest index among equal maxima
-template <int C>
-MZ_DEV int argmax_first(const float (&e)[(C + 15) / 16], int j) {
-  float best = -INFINITY, bi = 1024.0f;
-#pragma unroll
-  for (int t = 0; t < (C + 15) / 16; ++t) {
-    const bool up = (j + 16 * t < C) && e[t] > best;
-    best = up ? e[t] : best;
-    bi = up ? (float)(j + 16 * t) : bi;
-  }
-  const float m = row_max<4>(best);
-  const int c = (int)row_min<4>(best == m ? bi : 1024.0f);
-  return c < C ? c : 0;
-}
-
-// x = [v, onehot(a)] as a row-distributed vector of E + N elements
-template <int E, int N>
-MZ_DEV void concat_onehot(const float (&v)[(E + 15) / 16], int a, int j, float (&x)[(E + N + 15) / 16]) {
-#pragma unroll
-  for (int t = 0; t < (E + N + 15) / 16; ++t) {
-    const int k = j + 16 * t;
-    float s = 0.0f;
-    if (t < (E + 15) / 16) s = (k < E) ? v[t] : 0.0f;
-    x[t] = (k >= E && k < E + N) ? ((k - E == a) ? 1.0f : 0.0f) : s;
-  }
-}
-
-// One Linear(16)-elu-Linear stack under a cross entropy: forward from x, CE(logits, t) into the return value, both
-// layers' gradient tiles and bias sums, and dh, the gradient at the hidden layer's pre-activation (the caller takes it
-// back through W1 to whichever inputs it needs).
-template <int K, int N>
-MZ_DEV float head_ce(const float (&x)[(K + 15) / 16], const float* W1, const float* W2, const float (&t)[(N + 15) / 16],
-                     int j, float scale, f32x4 (&g1)[(K + 15) / 16][1], float (&b1)[1], f32x4 (&g2)[1][(N + 15) / 16],
-                     float (&b2)[(N + 15) / 16], float (&dh)[1]) {
-  constexpr int NS = (N + 15) / 16;
-  float h[1], l[NS], dl[NS];
-  lin_fwd<K, 16>(x, W1, j, h);
-  elu_vec(h);
-  lin_fwd<16, N>(h, W2, j, l);
-  const float ce = ce_and_grad<N>(l, t, j, scale, dl);
-  grad_tiles(h, dl, g2);
-#pragma unroll
-  for (int s = 0; s < NS; ++s) b2[s] = b2[s] + dl[s];
-  lin_bwd<16, N>(dl, W2, j, dh);
-  dh[0] = dh[0] * elu_grad(h[0]);
-  grad_tiles(x, dh, g1);
-  b1[0] = b1[0] + dh[0];
-  return ce;
-}
-
-// One stack under min_max_normalize: forward from x (the normalised output is re-evaluated, not read back), the gradient
-// g of the output taken through the normaliser and both layers; dh as in head_ce.
-template <int K, int E>
-MZ_DEV void state_bwd(const float (&x)[(K + 15) / 16], const float* W1, const float* W2, const float (&g)[(E + 15) / 16],
-                      int j, f32x4 (&g1)[(K + 15) / 16][1], float (&b1)[1], f32x4 (&g2)[1][(E + 15) / 16],
-                      float (&b2)[(E + 15) / 16], float (&dh)[1]) {
-  constexpr int ES = (E + 15) / 16;
-  float h[1], u[ES], s[ES], du[ES], mn, mx, c;
-  lin_fwd<K, 16>(x, W1, j, h);
-  elu_vec(h);
-  lin_fwd<16, E>(h, W2, j, u);
-  minmax_fwd<E>(u, j, s, mn, mx, c);
-  minmax_bwd<E>(g, u, s, mn, mx, c, j, du);
-  grad_tiles(h, du, g2);
-#pragma unroll
-  for (int t = 0; t < ES; ++t) b2[t] = b2[t] + du[t];
-  lin_bwd<16, E>(du, W2, j, dh);
-  dh[0] = dh[0] * elu_grad(h[0]);
-  grad_tiles(x, dh, g1);
-  b1[0] = b1[0] + dh[0];
-}
-
-template <int K, int E>
-MZ_DEV void state_fwd(const float (&x)[(K + 15) / 16], const float* W1, const float* W2, int j, float (&s)[(E + 15) / 16]) {
-  float h[1], u[(E + 15) / 16], mn, mx, c;
-  lin_fwd<K, 16>(x, W1, j, h);
-  elu_vec(h);
-  lin_fwd<16, E>(h, W2, j, u);
-  minmax_fwd<E>(u, j, s, mn, mx, c);
-}
 
 // the encoder: h = elu(obs W1 + b1) over the run-time obs_dim (obs read per row, a broadcast), e = h W2 + b2
 template <int C>
@@ -409,55 +306,6 @@ __global__ __launch_bounds__(256) void mz_stoch_train_kernel(const StochTrainPar
   store_tiles(g_en2, dst + off[32], H, C, lane);   store_bias(b_en2, dst + off[33], C, lane);
   const float wl = rows_sum(loss * scale);
   if (lane == 0) dst[off[STOCH_TRAIN_ARRAYS]] = wl;
-}
-
-// mz_train_reduce_kernel for 34 arrays: the fixed-order sum of the per-wavefront partials, plus the L2 term.
-__global__ __launch_bounds__(256) void mz_stoch_train_reduce_kernel(const StochTrainParams p) {
-  constexpr int NA = STOCH_TRAIN_ARRAYS;
-  const int NP = p.off[NA];
-  __shared__ float red[256];
-  const int pl = threadIdx.x & 31, q = threadIdx.x >> 5;
-  const int idx = blockIdx.x * 32 + pl;
-  const int per = (p.waves + 7) / 8;
-  const int w0 = q * per, w1 = min(p.waves, w0 + per);
-  float acc = 0.0f;
-  if (idx < NP) {
-    const float* src = p.ws + idx;
-    int w = w0;
-    for (; w + 8 <= w1; w += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = src[(size_t)(w + u) * (NP + 1)];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc = acc + v[u];
-    }
-    for (; w < w1; ++w) acc = acc + src[(size_t)w * (NP + 1)];
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  if (q == 0 && idx < NP) {
-    float t = red[pl];
-#pragma unroll
-    for (int g = 1; g < 8; ++g) t = t + red[32 * g + pl];
-    int a = 0;
-    while (idx >= p.off[a + 1]) ++a;
-    p.grads[idx] = t + p.l2 * p.w[a][idx - p.off[a]];
-  }
-  if (blockIdx.x == gridDim.x - 1) {
-    __syncthreads();
-    float la = 0.0f;
-    for (int w = threadIdx.x; w < p.waves; w += 256) la = la + p.ws[(size_t)w * (NP + 1) + NP];
-    float sq = 0.0f;
-    for (int a = 0; a < NA; ++a)
-      for (int i = threadIdx.x; i < p.off[a + 1] - p.off[a]; i += 256) sq = __builtin_fmaf(p.w[a][i], p.w[a][i], sq);
-    red[threadIdx.x] = la + 0.5f * p.l2 * sq;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if (threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) p.loss[0] = red[0];
-  }
 }
 
 }  // namespace mz

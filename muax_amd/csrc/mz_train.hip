@@ -2,17 +2,18 @@
 // per batch row): the instances of mz_train.cuh built into the library, and the hand-over to the ones built on demand (mz_train_jit.hip through mzs_register_train_dispatch).
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-
+#include "mz_train.cuh"
 #include "mz_train_launch.h"
 
 using mzh::fail;
+namespace th = mz::train_host;
 
-static void mlp_offsets(int obs_dim, int E, int A, int F, int off[19]) {
+static const char kWho[] = "mzs_mlp_loss_grad";
+
+static void mlp_offsets(int obs_dim, int E, int A, int F, int (&off)[19]) {
   const int H = mz::TrainCfg<2, 8, 21>::H, X = E + A;  // (the hidden width is the same constant in every TrainCfg)
   const int sizes[18] = {obs_dim * E, E, E * H, H, H * F, F, E * H, H, H * A, A, X * H, H, H * F, F, X * H, H, H * E, E};
-  off[0] = 0;
-  for (int i = 0; i < 18; ++i) off[i + 1] = off[i] + sizes[i];
+  th::offsets(sizes, off);
 }
 
 extern "C" {
@@ -27,8 +28,7 @@ int64_t mzs_mlp_num_params(int32_t obs_dim, int32_t embed_dim, int32_t num_actio
 
 int64_t mzs_mlp_train_workspace_bytes(int32_t batch, int32_t obs_dim, int32_t embed_dim, int32_t num_actions,
                                       int32_t support_size) {
-  const int64_t waves = 4 * (int64_t)((batch + 15) / 16);
-  return waves * (mzs_mlp_num_params(obs_dim, embed_dim, num_actions, support_size) + 1) * (int64_t)sizeof(float);
+  return th::workspace_bytes(batch, mzs_mlp_num_params(obs_dim, embed_dim, num_actions, support_size));
 }
 
 }  // extern "C"
@@ -36,37 +36,21 @@ int64_t mzs_mlp_train_workspace_bytes(int32_t batch, int32_t obs_dim, int32_t em
 // THE training step behind mzs_mlp_loss_grad (row_w null) and mzs_mlp_loss_grad_weighted: checks, argument block, the
 // instance's two launches.  Both entries report under the first one's name.
 static int loss_grad(const mzs_mlp_weights* w, const mzs_train_args* a, const float* row_w, void* stream_) {
-  if (!w || w->struct_size != (int32_t)sizeof(mzs_mlp_weights))
-    return fail(nullptr, MZS_E_INVALID, "mzs_mlp_loss_grad: null weights or size mismatch (ABI)");
-  if (!a || a->struct_size != (int32_t)sizeof(mzs_train_args))
-    return fail(nullptr, MZS_E_INVALID, "mzs_mlp_loss_grad: null arguments or size mismatch (ABI)");
-  const float* const* ptrs = &w->repr_w;
-  for (int i = 0; i < 18; ++i)
-    if (!ptrs[i]) return fail(nullptr, MZS_E_INVALID, "mzs_mlp_loss_grad: null weight pointer");
-  if (a->batch <= 0 || a->unroll_steps <= 0) return fail(nullptr, MZS_E_INVALID, "mzs_mlp_loss_grad: batch and unroll_steps must be positive");
-  if (!a->obs || !a->actions || !a->rewards || !a->returns || !a->policy || !a->loss || !a->grads || !a->workspace)
-    return fail(nullptr, MZS_E_INVALID, "mzs_mlp_loss_grad: null batch / output / workspace pointer");
-  if (w->obs_dim <= 0 || w->obs_dim > 128) return fail(nullptr, MZS_E_UNSUPPORTED, "mzs_mlp_loss_grad: obs_dim must be 1..128");
+  if (int rc = th::check<18>(w, a, kWho)) return rc;
+  if (w->obs_dim <= 0 || w->obs_dim > 128) return fail(nullptr, MZS_E_UNSUPPORTED, "%s: obs_dim must be 1..128", kWho);
   const int A = a->num_actions, E = a->embed_dim, F = 2 * w->support_size + 1;
   if (a->workspace_bytes < mzs_mlp_train_workspace_bytes(a->batch, w->obs_dim, E, A, w->support_size))
-    return fail(nullptr, MZS_E_INVALID, "mzs_mlp_loss_grad: workspace too small");
-  if (int rc = mzh::select_device(a->device, "mzs_mlp_loss_grad")) return rc;
-  mz::TrainParams p;
-  memset(&p, 0, sizeof p);
-  p.obs = a->obs; p.act = a->actions; p.rew = a->rewards; p.ret = a->returns; p.pi = a->policy;
-  for (int i = 0; i < 18; ++i) p.w[i] = ptrs[i];
+    return fail(nullptr, MZS_E_INVALID, "%s: workspace too small", kWho);
+  if (int rc = mzh::select_device(a->device, kWho)) return rc;
+  mz::TrainParams p = th::params<18>(*w, *a, row_w);
   mlp_offsets(w->obs_dim, E, A, F, p.off);
-  p.B = a->batch; p.L = a->unroll_steps; p.obs_dim = w->obs_dim; p.support = w->support_size;
-  p.loss_scale = a->loss_scale; p.l2 = a->l2_coeff;
-  p.ws = static_cast<float*>(a->workspace); p.grads = a->grads; p.loss = a->loss;
-  p.waves = 4 * ((a->batch + 15) / 16);
-  p.row_w = row_w;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   char msg[256] = "";
   auto filed = [&](int rc, const char* fmt) { return rc == MZS_OK ? MZS_OK : fail(nullptr, rc, fmt, msg); };
-#define MZ_TRAIN_INST(a_, e_, f_)       \
-  if (A == a_ && E == e_ && F == f_)    \
-    return filed(mz::launch_train<mz::TrainCfg<a_, e_, f_>>(p, stream, msg, (int)sizeof msg), "mzs_mlp_loss_grad: %s");
+#define MZ_TRAIN_INST(a_, e_, f_)    \
+  if (A == a_ && E == e_ && F == f_) \
+    return filed(mz::launch_train<mz::TrainCfg<a_, e_, f_>>(mz::mz_train_kernel<mz::TrainCfg<a_, e_, f_>>, p, stream, msg, (int)sizeof msg), \
+                 "mzs_mlp_loss_grad: %s");
   MZ_TRAIN_INST(2, 8, 21) MZ_TRAIN_INST(4, 32, 21) MZ_TRAIN_INST(3, 8, 21) MZ_TRAIN_INST(4, 8, 21)
   MZ_TRAIN_INST(2, 16, 21) MZ_TRAIN_INST(4, 16, 21)
   MZ_TRAIN_INST(2, 10, 21) MZ_TRAIN_INST(4, 10, 21)  // the reference notebooks

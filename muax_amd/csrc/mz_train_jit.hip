@@ -11,12 +11,14 @@
 #if !defined(MZ_TRAIN_A) || !defined(MZ_TRAIN_E) || !defined(MZ_TRAIN_F)
 #error "build through muax_amd/_jit.py"
 #endif
+#include "mz_train.cuh"
 #include "mz_train_launch.h"
 
 // (argument block of mzs_mlp_loss_grad's own launcher; the caller has validated it and selected the device)
 extern "C" int mzs_jit_train_launch(const void* params, void* stream_, char* err, int errlen) {
-  return mz::launch_train<mz::TrainCfg<MZ_TRAIN_A, MZ_TRAIN_E, MZ_TRAIN_F>>(*static_cast<const mz::TrainParams*>(params),
-                                                                           static_cast<hipStream_t>(stream_), err, errlen);
+  using Cfg = mz::TrainCfg<MZ_TRAIN_A, MZ_TRAIN_E, MZ_TRAIN_F>;
+  return mz::launch_train<Cfg>(mz::mz_train_kernel<Cfg>, *static_cast<const mz::TrainParams*>(params),
+                               static_cast<hipStream_t>(stream_), err, errlen);
 }
 extern "C" void mzs_jit_train_shape(int32_t* A, int32_t* E, int32_t* F) {
   *A = MZ_TRAIN_A; *E = MZ_TRAIN_E; *F = MZ_TRAIN_F;

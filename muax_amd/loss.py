@@ -3,7 +3,8 @@
 Two routes to the same number.  `default_loss_fn` is the formula in plain PyTorch ops (autograd does the backward
 pass): it serves plugin nets and custom losses, and it is the reference the fused kernel is tested against.
 `FusedLossGrad` (below) is the product path for the default MLP trio: loss and every gradient from ONE hand-written
-forward+backward HIP kernel (muax_amd/csrc/mz_train.cuh through mzs_mlp_loss_grad).  The reference's formula:
+forward+backward HIP kernel (muax_amd/csrc/mz_train.cuh through mzs_mlp_loss_grad; its blocks, shared with the
+stochastic family's kernel, in mz_train_blocks.cuh).  The reference's formula:
 
     loss = sum_{i<L} [ mean_B CE(r_logits_i, support(r_i)) + mean_B CE(v_logits_i, support(Rn_i))
                        + mean_B CE(pi_logits_i, pi_i) ]  +  1e-4 * 0.5 * sum ||param||^2
@@ -150,29 +151,26 @@ def _straight_through(encoded):
 
 
 # ---------------------------------------------------------------------------------------------------
-# HIP path: loss and gradients of the default MLP trio in one fused forward+backward kernel
-# (muax_amd/csrc/mz_train.cuh through the C-ABI entry mzs_mlp_loss_grad).
+# HIP path: loss and gradients in one fused forward+backward kernel and its fixed-order reduction, for the default MLP
+# trio (muax_amd/csrc/mz_train.cuh through mzs_mlp_loss_grad) and the default stochastic MLP family
+# (mz_stoch_train.cuh through mzs_stochastic_mlp_loss_grad).  The two kernels are built from the same blocks
+# (mz_train_blocks.cuh) and the two wrappers from `_FusedStep`.
 # ---------------------------------------------------------------------------------------------------
-class FusedLossGrad:
-    """value_and_grad of the default loss (muax/loss.py:10-88 via muax/model.py:245-249) for the default
-    MLP trio.  The gradient comes back as ONE flat fp32 vector in the C-ABI's array order (that is also the
-    buffer a data-parallel all-reduce works on); `views` maps it onto the 18 parameters."""
+class _FusedStep:
+    """What the two fused training steps share: the parameter list in the C ABI's order, the flat gradient with its
+    `views`, the workspace, the weight struct, the batch plumbing and the keep-alive of what the launch reads.  A
+    subclass sets obs_dim / E / A (/ C), names its weights and states `_num_params`, `_workspace_bytes`, `_obs` and
+    `_launch`."""
 
-    def __init__(self, muzero_instance):
-        from . import nn as mz_nn
-        if not mz_nn.is_default_mlp_trio(muzero_instance.network):
-            raise ValueError("the fused training step is built for the default MLP trio")
+    def __init__(self, muzero_instance, params, names, weight_struct):
         self.m = muzero_instance
         self._L = _lib.load()
-        params = mz_nn.mlp_trio_weights(muzero_instance.network)
-        self.params = [params[n] for n in _lib.MLP_WEIGHT_NAMES]
+        self.params = [params[n] for n in names]
         dev = self.params[0].device
         if dev.type != "cuda":
             raise RuntimeError("muax_amd needs a ROCm GPU (gfx950); there is no CPU fallback")
-        r, p, _ = muzero_instance.network
-        self.obs_dim, self.E, self.A = r.obs_dim, r.embedding_dim, p.num_actions
         self.S = muzero_instance._support_size
-        n = int(self._L.mzs_mlp_num_params(self.obs_dim, self.E, self.A, self.S))
+        n = int(self._num_params())
         assert n == sum(x.numel() for x in self.params)
         self.grads = torch.zeros(n, dtype=torch.float32, device=dev)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -181,11 +179,9 @@ class FusedLossGrad:
             self.views.append(self.grads[off:off + x.numel()].view_as(x))
             off += x.numel()
         self._ws = None
-        self._weights = _call.MlpWeights(self.params)
+        self._weights = _call.MlpWeights(self.params, weight_struct, names)
 
-    def __call__(self, batch: Transition, divide_by_length: bool = False, sample_weight=None):
-        """(loss [1], flat gradient) of the batch.  `sample_weight` [B] (float32 on the device is read in place): the
-        weighted entry mzs_mlp_loss_grad_weighted, each row's cross entropies and gradient scaled by its weight."""
+    def _step(self, batch, divide_by_length, sample_weight, **extra):
         dev = self.grads.device
 
         def t(x, dt):  # (tensors that already are what the kernel reads pass through untouched)
@@ -195,28 +191,62 @@ class FusedLossGrad:
         a = t(batch.a, torch.int32)
         B, L = a.shape[:2]
         a = a.reshape(B, L)
-        obs = t(batch.obs, torch.float32)[:, 0].reshape(B, -1).contiguous()
+        obs = self._obs(t(batch.obs, torch.float32), B, L)
+        if obs.shape[-1] != self.obs_dim:
+            raise ValueError(f"batch.obs has {obs.shape[-1]} features, the network takes {self.obs_dim}")
         r, Rn = t(batch.r, torch.float32).reshape(B, L), t(batch.Rn, torch.float32).reshape(B, L)
         pi = t(batch.pi, torch.float32).reshape(B, L, self.A)
-        if obs.shape[1] != self.obs_dim:
-            raise ValueError(f"batch.obs has {obs.shape[1]} features, the network takes {self.obs_dim}")
         sw = None
         if sample_weight is not None:  # (the shape alone: looking at the values would synchronise)
             if tuple(getattr(sample_weight, "shape", ())) != (B,):
                 raise ValueError(f"sample_weight must be [B] with B = {B}, got "
                                  f"{tuple(getattr(sample_weight, 'shape', ()))}")
             sw = t(sample_weight.detach() if isinstance(sample_weight, torch.Tensor) else sample_weight, torch.float32)
-        need = int(self._L.mzs_mlp_train_workspace_bytes(B, self.obs_dim, self.E, self.A, self.S))
+        need = int(self._workspace_bytes(B))
         if self._ws is None or self._ws.numel() * 4 < need:
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
         w, keep = self._weights.get()
+        self._launch(w, _call.device_index(dev), B, L, obs, a, r, Rn, pi, sw,
+                     1.0 / (B * L) if divide_by_length else 1.0 / B, **extra)
+        self._keep, self._keep_w = (obs, a, r, Rn, pi, keep), sw  # (alive until the next call: the launch is asynchronous)
+        return self.loss, self.grads
+
+
+class FusedLossGrad(_FusedStep):
+    """value_and_grad of the default loss (muax/loss.py:10-88 via muax/model.py:245-249) for the default
+    MLP trio.  The gradient comes back as ONE flat fp32 vector in the C-ABI's array order (that is also the
+    buffer a data-parallel all-reduce works on); `views` maps it onto the 18 parameters."""
+
+    def __init__(self, muzero_instance):
+        from . import nn as mz_nn
+        if not mz_nn.is_default_mlp_trio(muzero_instance.network):
+            raise ValueError("the fused training step is built for the default MLP trio")
+        r, p, _ = muzero_instance.network
+        self.obs_dim, self.E, self.A = r.obs_dim, r.embedding_dim, p.num_actions
+        super().__init__(muzero_instance, mz_nn.mlp_trio_weights(muzero_instance.network), _lib.MLP_WEIGHT_NAMES,
+                         _lib.MzsMlpWeights)
+
+    def _num_params(self):
+        return self._L.mzs_mlp_num_params(self.obs_dim, self.E, self.A, self.S)
+
+    def _workspace_bytes(self, B):
+        return self._L.mzs_mlp_train_workspace_bytes(B, self.obs_dim, self.E, self.A, self.S)
+
+    def _obs(self, obs, B, L):  # the first row of every window
+        return obs[:, 0].reshape(B, -1).contiguous()
+
+    def __call__(self, batch: Transition, divide_by_length: bool = False, sample_weight=None):
+        """(loss [1], flat gradient) of the batch.  `sample_weight` [B] (float32 on the device is read in place): the
+        weighted entry mzs_mlp_loss_grad_weighted, each row's cross entropies and gradient scaled by its weight."""
+        return self._step(batch, divide_by_length, sample_weight)
+
+    def _launch(self, w, idx, B, L, obs, a, r, Rn, pi, sw, loss_scale):
         w.obs_dim, w.support_size, w.discount = self.obs_dim, self.S, self.m._discount
-        idx = _call.device_index(dev)
         args = _lib.args(_lib.MzsTrainArgs)  # (per update: fields by attribute, which is 1 us cheaper than keywords)
         args.device, args.batch, args.unroll_steps, args.num_actions, args.embed_dim = idx, B, L, self.A, self.E
         args.obs, args.actions, args.rewards = obs.data_ptr(), a.data_ptr(), r.data_ptr()
         args.returns, args.policy = Rn.data_ptr(), pi.data_ptr()
-        args.loss_scale = 1.0 / (B * L) if divide_by_length else 1.0 / B
+        args.loss_scale = loss_scale
         args.l2_coeff = 1e-4
         args.loss, args.grads = self.loss.data_ptr(), self.grads.data_ptr()
         args.workspace, args.workspace_bytes = self._ws.data_ptr(), self._ws.numel() * 4
@@ -225,11 +255,9 @@ class FusedLossGrad:
             _lib.check(self._L.mzs_mlp_loss_grad(C.byref(w), C.byref(args), stream))
         else:
             _lib.check(self._L.mzs_mlp_loss_grad_weighted(C.byref(w), C.byref(args), sw.data_ptr(), stream))
-        self._keep, self._keep_w = (obs, a, r, Rn, pi, keep), sw
-        return self.loss, self.grads
 
 
-class StochasticFusedLossGrad:
+class StochasticFusedLossGrad(_FusedStep):
     """value_and_grad of `stochastic_loss_fn` for the default stochastic MLP family, `FusedLossGrad`'s sibling: loss and
     every gradient from one forward+backward HIP kernel and its fixed-order reduction (muax_amd/csrc/mz_stoch_train.cuh
     through mzs_stochastic_mlp_loss_grad).  The gradient is ONE flat fp32 vector in the C-ABI's order of the 34 arrays
@@ -240,67 +268,34 @@ class StochasticFusedLossGrad:
         from . import nn as mz_nn
         if not mz_nn.is_default_stochastic_mlp(muzero_instance.network):
             raise ValueError("the fused stochastic training step is built for the default stochastic MLP family")
-        self.m = muzero_instance
-        self._L = _lib.load()
-        params = mz_nn.stochastic_train_weights(muzero_instance.network)
-        self.params = [params[n] for n in _lib.STOCHASTIC_TRAIN_WEIGHT_NAMES]
-        dev = self.params[0].device
-        if dev.type != "cuda":
-            raise RuntimeError("muax_amd needs a ROCm GPU (gfx950); there is no CPU fallback")
         r, p, _, ap, _, _ = muzero_instance.network
         self.obs_dim, self.E, self.A, self.C = r.obs_dim, r.embedding_dim, p.num_actions, ap.num_actions
-        self.S = muzero_instance._support_size
-        n = int(self._L.mzs_stochastic_mlp_num_params(self.obs_dim, self.E, self.A, self.C, self.S))
-        assert n == sum(x.numel() for x in self.params)
-        self.grads = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.views, off = [], 0
-        for x in self.params:
-            self.views.append(self.grads[off:off + x.numel()].view_as(x))
-            off += x.numel()
-        self._ws = None
-        self._weights = _call.MlpWeights(self.params, _lib.MzsStochasticTrainWeights, _lib.STOCHASTIC_TRAIN_WEIGHT_NAMES)
+        super().__init__(muzero_instance, mz_nn.stochastic_train_weights(muzero_instance.network),
+                         _lib.STOCHASTIC_TRAIN_WEIGHT_NAMES, _lib.MzsStochasticTrainWeights)
 
-    def __call__(self, batch: Transition, vqvae_beta: float = 0.25, divide_by_length: bool = False, sample_weight=None):
-        """(loss [1], flat gradient) of the batch; `batch.obs` is [B, L, obs_dim], an observation for every step."""
-        dev = self.grads.device
+    def _num_params(self):
+        return self._L.mzs_stochastic_mlp_num_params(self.obs_dim, self.E, self.A, self.C, self.S)
 
-        def t(x, dt):
-            if isinstance(x, torch.Tensor) and x.dtype == dt and x.device == dev and x.is_contiguous():
-                return x
-            return torch.as_tensor(x, device=dev).to(dt).contiguous()
-        a = t(batch.a, torch.int32)
-        B, L = a.shape[:2]
-        a = a.reshape(B, L)
-        obs = t(batch.obs, torch.float32)
+    def _workspace_bytes(self, B):
+        return self._L.mzs_stochastic_mlp_train_workspace_bytes(B, self.obs_dim, self.E, self.A, self.C, self.S)
+
+    def _obs(self, obs, B, L):  # a row for every step
         if obs.dim() < 3 or obs.shape[0] != B or obs.shape[1] < L:
             raise ValueError(f"the stochastic loss needs every step's observation: batch.obs must be [B, L, ...] with L = {L} "
                              f"rows per window, got {tuple(obs.shape)} (DeviceReplayBuffer.sample keeps the first row only)")
-        obs = obs[:, :L].reshape(B, L, -1).contiguous()
-        if obs.shape[2] != self.obs_dim:
-            raise ValueError(f"batch.obs has {obs.shape[2]} features, the network takes {self.obs_dim}")
-        r, Rn = t(batch.r, torch.float32).reshape(B, L), t(batch.Rn, torch.float32).reshape(B, L)
-        pi = t(batch.pi, torch.float32).reshape(B, L, self.A)
-        sw = None
-        if sample_weight is not None:  # (the shape alone: looking at the values would synchronise)
-            if tuple(getattr(sample_weight, "shape", ())) != (B,):
-                raise ValueError(f"sample_weight must be [B] with B = {B}, got "
-                                 f"{tuple(getattr(sample_weight, 'shape', ()))}")
-            sw = t(sample_weight.detach() if isinstance(sample_weight, torch.Tensor) else sample_weight, torch.float32)
-        need = int(self._L.mzs_stochastic_mlp_train_workspace_bytes(B, self.obs_dim, self.E, self.A, self.C, self.S))
-        if self._ws is None or self._ws.numel() * 4 < need:
-            self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
-        w, keep = self._weights.get()
+        return obs[:, :L].reshape(B, L, -1).contiguous()
+
+    def __call__(self, batch: Transition, vqvae_beta: float = 0.25, divide_by_length: bool = False, sample_weight=None):
+        """(loss [1], flat gradient) of the batch; `batch.obs` is [B, L, obs_dim], an observation for every step."""
+        return self._step(batch, divide_by_length, sample_weight, vqvae_beta=vqvae_beta)
+
+    def _launch(self, w, idx, B, L, obs, a, r, Rn, pi, sw, loss_scale, vqvae_beta):
         w.obs_dim, w.support_size = self.obs_dim, self.S
-        idx = _call.device_index(dev)
         args = _lib.args(_lib.MzsStochasticTrainArgs, device=idx, batch=B, unroll_steps=L, num_actions=self.A,
                          num_chance_outcomes=self.C, embed_dim=self.E, obs=obs.data_ptr(), actions=a.data_ptr(),
                          rewards=r.data_ptr(), returns=Rn.data_ptr(), policy=pi.data_ptr(),
-                         sample_weight=None if sw is None else sw.data_ptr(),
-                         loss_scale=1.0 / (B * L) if divide_by_length else 1.0 / B, l2_coeff=1e-4,
+                         sample_weight=None if sw is None else sw.data_ptr(), loss_scale=loss_scale, l2_coeff=1e-4,
                          vqvae_beta=float(vqvae_beta), loss=self.loss.data_ptr(), grads=self.grads.data_ptr(),
                          workspace=self._ws.data_ptr(), workspace_bytes=self._ws.numel() * 4)
         with torch.cuda.device(idx):
             _lib.check(self._L.mzs_stochastic_mlp_loss_grad(C.byref(w), C.byref(args), _call.raw_stream(idx)))
-        self._keep = (obs, a, r, Rn, pi, sw, keep)
-        return self.loss, self.grads
