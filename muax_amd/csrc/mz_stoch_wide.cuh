@@ -1,8 +1,9 @@
 // mz_stoch_wide.cuh -- the WHOLE stochastic search of the default stochastic MLP family (mctx stochastic_muzero_policy,
 // DESIGN.md 4.7) in ONE launch, the root's tree in LDS: the root set-up of mzs_root_stochastic, every simulation (select
 // -> decision or chance function -> expand -> backward), the summary and the sampling of mzs_finish_stochastic.  Root
-// inference stays with the caller: the kernel takes the RootFnOutput arrays.  The mapping is mz_wide.cuh's, and so are
-// the wavefront primitives (included, not restated):
+// inference stays with the caller: the kernel takes the RootFnOutput arrays.  The mapping, the tree record and the rules
+// both one-launch kernels follow (pUCT score, tie-break noise, expansion, backup, summary and sampling, tree export) are
+// mz_wave_tree.cuh's:
 //
 //   * one root per WAVEFRONT, lane i owns slot i of a node (A actions, then C chance outcomes, A + C <= 64); records lie
 //     [field][slot] in LDS, the path too, the node embeddings when that costs no resident root (else HBM scratch);
@@ -42,13 +43,6 @@ struct StochWideShape {
 struct StochHead {
   const float *w1, *b1, *w2, *b2;
 };
-// muax/nn.py:37-44 over the E elements in lanes [0, E)
-MZ_DEV float wave_min_max_normalize(float s, int E, int lane) {
-  const float mn = wave_min(lane < E ? s : INFINITY), mx = wave_max(lane < E ? s : -INFINITY);
-  float scale = mx - mn;
-  scale = scale < 1e-5f ? scale + 1e-5f : scale;
-  return (s - mn) / scale;
-}
 
 // MODE 0 / 1: without / with mctx's tie-break noise at the decision nodes (the handle's `tiebreak`)
 template <int MODE>
@@ -79,8 +73,8 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
   };
   const StochHead ad = head(0, E + A, E), av = head(1, E, F), ac = head(2, E, C), cr = head(3, E + C, F),
                   cn = head(4, E + C, E), pv = head(5, E, F), pp = head(6, E, A);
-  float* tbl = wl + sh.weight_words;  // sqrt(n) pb_c(n), n = 0 .. S + 1 (a node's visit count)
-  for (int n = tid; n < S + 2; n += blockDim.x) tbl[n] = puct_scale(n, p.pb_c_init, p.pb_c_base);
+  float* tbl = wl + sh.weight_words;
+  wave_stage_puct_table(tbl, S, p.pb_c_init, p.pb_c_base);
   __syncthreads();
 
   const int r = blockIdx.x * sh.waves + wave;
@@ -97,15 +91,9 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
   const float temperature = p.dyn ? __uint_as_float(p.dyn[2]) : p.temperature;
   const float fraction = p.dyn ? __uint_as_float(p.dyn[3]) : p.dirichlet_fraction;
 
-  // ---- this root's block: records [N][REC] | path [N] | embeddings [N][E] (or in HBM) ----
-  // record: visits, value, raw value, (parent + 1) | (slot + 1) << 16 | chance node << 30, then per slot: (child + 1) |
-  // visits << 16, prior probability, child value, reward -- all zero is mctx's empty tree
+  // ---- this root's block (mz_wave_tree.cuh; a chance node's record says so in its parent word) ----
   int* tree = stoch_lds + sh.wg_words + wave * sh.root_words;
-  int* path = tree + N * REC;
-  {
-    int4* q4 = reinterpret_cast<int4*>(tree);
-    for (int q = lane; q < sh.root_words / 4; q += 64) q4[q] = make_int4(0, 0, 0, 0);
-  }
+  int* path = wave_tree_setup(tree, sh.root_words, N, REC, lane);
   float* emb = sh.emb_lds ? reinterpret_cast<float*>(path + N) : (ex ? p.t_embeddings : p.emb_scratch) + (size_t)r * N * E;
   const size_t tn0 = (size_t)r * N;  // this root's first node in the export arrays
   const bool inv = (p.invalid != nullptr && act) ? p.invalid[(size_t)r * A + al] != 0 : false;
@@ -128,14 +116,14 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
     const float prob = wave_softmax(lg, AC, lane);
     if (lane < E) emb[lane] = p.embedding[(size_t)r * E + ec];
     if (ok) {
-      tree[4 + AC + sl] = __float_as_int(prob);
+      tree[rec_child(kChildProb, AC, sl)] = __float_as_int(prob);
       if (ex) p.t_children_prior_logits[tn0 * AC + sl] = lg;
     }
     if (lane == 0) {
       const float v = p.value[r];
-      tree[0] = 1;
-      tree[1] = __float_as_int(v);
-      tree[2] = __float_as_int(v);
+      tree[kRecVisits] = 1;
+      tree[kRecValue] = __float_as_int(v);
+      tree[kRecRaw] = __float_as_int(v);
     }
     wave_sync();
   }
@@ -143,69 +131,30 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
   // ---- simulations ----
   int depth_sum = 0;
   for (int sim = 0; sim < S; ++sim) {
-    // the tie-break key walk, advanced only as far as a near tie asks for: kk = the key after `klevel` splits
-    [[maybe_unused]] uint32_t kk0 = 0, kk1 = 0;
+    [[maybe_unused]] uint32_t kk0 = 0, kk1 = 0;  // the tie-break key walk (wave_noisy_argmax)
     [[maybe_unused]] int klevel = -1;
     int node = 0, depth = 0, parent = 0, action = 0, next = -1;
     for (;;) {
       const int* rec = tree + node * REC;
-      const int iv = rec[4 + sl];
-      const float prob = __int_as_float(rec[4 + AC + sl]);
-      const int cvis = iv >> 16, cidx = (iv & 0xffff) - 1;
+      const int link = rec[rec_child(kChildLink, AC, sl)];
+      const float prob = __int_as_float(rec[rec_child(kChildProb, AC, sl)]);
+      const int cvis = link_visits(link), cidx = link_child(link);
       int best;
       if (depth & 1) {
         // chance node (mz_step.cuh chance_decide): no noise, first maximum
         best = wave_first_max(ok ? prob / (float)(cvis + 1) : -INFINITY);
       } else {
         // decision node (level_decide): every edge has reward 0 and discount 1
-        const int nvis = rec[0];
-        const float nval = __int_as_float(rec[1]);
-        const float q = __int_as_float(rec[4 + 3 * AC + sl]) + 1.0f * __int_as_float(rec[4 + 2 * AC + sl]);
-        const bool seen = ok && cvis > 0;
-        const float safe = seen ? q : nval;
-        const float lo = fminf(nval, wave_min(safe)), hi = fmaxf(nval, wave_max(safe));
-        const float span = fmaxf(hi - lo, 1e-8f);
-        const float value_score = ((seen ? q : lo) - lo) / span;
-        const float policy_score = (tbl[nvis] * prob) / (float)(cvis + 1);
-        float sc = value_score + policy_score;
+        const int nvis = rec[kRecVisits];
+        const float nval = __int_as_float(rec[kRecValue]);
+        const float q = __int_as_float(rec[rec_child(kChildReward, AC, sl)]) + 1.0f * __int_as_float(rec[rec_child(kChildValue, AC, sl)]);
+        float sc = wave_puct_score(ok && cvis > 0, q, nval, tbl[nvis], prob, cvis);
         if (!ok || (depth == 0 && root_masked)) sc = -INFINITY;
-        float top = wave_max(sc);
-        unsigned long long at = __builtin_amdgcn_ballot_w64(sc == top);
-        best = at ? __builtin_ctzll(at) : 0;
-        if constexpr (TIEBREAK) {
-          // only a near tie pays for the threefry blocks (mz_step.cuh noisy_argmax; mz_wide.cuh)
-          const bool unsafe = ok && lane != best && !((sc + 1e-7f) < top);
-          if (__builtin_amdgcn_ballot_w64(unsafe) != 0) {
-            uint32_t s0 = 0, s1 = 0;
-            if (klevel < 0) {  // this root's key of the simulation: split(simulate_key, global_batch)[root]
-              uint32_t x0, x1;
-              bool second;
-              bits_block(2 * p.global_batch, 2 * rg + (uint64_t)(lane & 1), x0, x1, second);
-              threefry2x32(p.dyn ? p.dyn[kStochBlockHead + 2 * sim] : p.sim_keys[sim][0],
-                           p.dyn ? p.dyn[kStochBlockHead + 2 * sim + 1] : p.sim_keys[sim][1], x0, x1);
-              const uint32_t word = second ? x1 : x0;
-              kk0 = (uint32_t)w_rdl_i((int)word, 0);
-              kk1 = (uint32_t)w_rdl_i((int)word, 1);
-              klevel = 0;
-            }
-            while (klevel <= depth) {  // rng_key, action_selection_key = split(rng_key), once per level of either kind
-              uint32_t x0 = (uint32_t)(lane & 1), x1 = 2u + (uint32_t)(lane & 1);
-              threefry2x32(kk0, kk1, x0, x1);
-              kk0 = (uint32_t)w_rdl_i((int)x0, 0);
-              kk1 = (uint32_t)w_rdl_i((int)x0, 1);
-              s0 = (uint32_t)w_rdl_i((int)x1, 0);
-              s1 = (uint32_t)w_rdl_i((int)x1, 1);
-              ++klevel;
-            }
-            const int NB = (AC + 1) / 2, jb = sl < NB ? sl : sl - NB;
-            uint32_t x0 = (uint32_t)jb, x1 = (NB + jb < AC) ? (uint32_t)(NB + jb) : 0u;
-            threefry2x32(s0, s1, x0, x1);
-            const float noised = sc + 1e-7f * uniform_from_bits(sl < NB ? x0 : x1);
-            best = wave_first_max(ok ? noised : -INFINITY);
-          }
-        }
+        best = wave_noisy_argmax<TIEBREAK>(sc, ok, sl, AC, depth, lane, p.global_batch, rg, [&](int i) {
+          return p.dyn ? p.dyn[kStochBlockHead + 2 * sim + i] : p.sim_keys[sim][i];
+        }, kk0, kk1, klevel);
       }
-      if (lane == 0) path[depth] = node | (best << 16);
+      if (lane == 0) path[depth] = path_word(node, best);
       parent = node;
       action = best;
       next = w_rdl_i(cidx, best);
@@ -245,125 +194,27 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
     }
     const float prob = wave_softmax(logit, AC, lane);
 
-    // expand (step_expand_backup_stochastic_kernel); a node met again at max_depth keeps its children
-    {
-      int* nrec = tree + newn * REC;
-      if (ok) {
-        nrec[4 + AC + sl] = __float_as_int(prob);
-        if (ex) p.t_children_prior_logits[(tn0 + newn) * AC + sl] = logit;
-      }
-      if (lane == 0) {
-        nrec[0] = nrec[0] + 1;
-        nrec[1] = __float_as_int(value);
-        nrec[2] = __float_as_int(value);
-        nrec[3] = (parent + 1) | ((action + 1) << 16) | (decision ? 1 << 30 : 0);
-        int* prec = tree + parent * REC;
-        prec[4 + action] = (prec[4 + action] & ~0xffff) | (newn + 1);
-        prec[4 + 3 * AC + action] = __float_as_int(reward);  // (0 from a decision parent)
-      }
-      wave_sync();
-    }
-
-    // backward: lane l owns path entry base + l of a chunk of up to 64 levels, deepest chunk first; the edge of level d
-    // leaves a decision node (reward 0, discount 1) where d is even
-    {
-      float leaf = value, childv = value;
-      for (int top = depth; top > 0; top -= 64) {
-        const int base = top > 64 ? top - 64 : 0, n = top - base;
-        const bool mine = lane < n;
-        const int pk = path[base + (mine ? lane : 0)];
-        int* prec = tree + (pk & 0xffff) * REC;
-        const int pa = pk >> 16;
-        const int cnt = prec[0];
-        const float nv = __int_as_float(prec[1]);
-        const float rw = __int_as_float(prec[4 + 3 * AC + pa]);
-        const float ds = ((base + lane) & 1) ? disc : 1.0f;
-        const int iv = prec[4 + pa];
-        float myleaf = 0.0f;
-        for (int l = n - 1; l >= 0; --l) {  // leaf_value = reward + discount * leaf_value, level by level
-          leaf = w_rdl(rw, l) + w_rdl(ds, l) * leaf;
-          myleaf = lane == l ? leaf : myleaf;
-        }
-        const float newv = (nv * (float)cnt + myleaf) / ((float)cnt + 1.0f);
-        const float below = __shfl_down(newv, 1);
-        const float cv = lane == n - 1 ? childv : below;  // children_values = the child's node value after ITS update
-        if (mine) {
-          prec[0] = cnt + 1;
-          prec[1] = __float_as_int(newv);
-          prec[4 + 2 * AC + pa] = __float_as_int(cv);
-          prec[4 + pa] = iv + (1 << 16);
-        }
-        childv = w_rdl(newv, 0);
-      }
-      wave_sync();
-    }
+    // expand (step_expand_backup_stochastic_kernel; the reward is 0 from a decision parent) and backward
+    if (ex && ok) p.t_children_prior_logits[(tn0 + newn) * AC + sl] = logit;
+    wave_tree_expand<false>(tree, REC, AC, newn, parent, action, decision, ok, sl, lane, prob, logit, value, reward);
+    wave_tree_backward<true>(tree, path, REC, AC, depth, value, disc, lane);
   }
 
-  // ---- finish_row over the A actions: mctx Tree.summary + _apply_temperature + jax.random.categorical ----
+  // ---- finish_row over the A actions ----
   {
-    const int vc = act ? (tree[4 + al] >> 16) : 0;
-    const float total = (float)wave_sum_i(vc);
-    const float denom = fmaxf(total, 1.0f);
-    float pw = (float)vc / denom;
-    pw = total > 0.0f ? pw : 1.0f / (float)A;
-    const float lg = log_pos(fmaxf(pw, kFltTiny));
-    const float mx = wave_max(act ? lg : -INFINITY);
-    const float tden = fmaxf(temperature, kFltTiny);
-    float g;
-    if (p.gumbel != nullptr) {
-      g = act ? p.gumbel[(size_t)r * A + al] : 0.0f;
-    } else {
-      uint32_t x0, x1;
-      bool second;
-      bits_block(p.global_batch * (uint64_t)A, rg * (uint64_t)A + (uint64_t)al, x0, x1, second);
-      threefry2x32(p.dyn ? p.dyn[0] : p.k_sample[0], p.dyn ? p.dyn[1] : p.k_sample[1], x0, x1);
-      g = gumbel_from_bits(second ? x1 : x0);
-    }
-    const int best = wave_first_max(act ? (lg - mx) / tden + g : -INFINITY);
+    float pw;
+    const int best = wave_summary_sample(tree, AC, A, act, al, lane, temperature, p.gumbel ? p.gumbel + (size_t)r * A : nullptr,
+                                         p.global_batch, rg, [&](int i) { return p.dyn ? p.dyn[i] : p.k_sample[i]; }, pw);
     if (act) p.action_weights[(size_t)r * A + al] = pw;
     if (lane == 0) {
       p.action[r] = best;
-      if (p.search_value) p.search_value[r] = __int_as_float(tree[1]);
+      if (p.search_value) p.search_value[r] = __int_as_float(tree[kRecValue]);
       if (p.depth_sum) p.depth_sum[r] = depth_sum;
     }
   }
 
-  // ---- the finished tree into the handle's HBM arrays, as the step-wise kernels leave them (the prior logits of
-  // expanded nodes are there already) ----
-  if (ex) {
-    for (int n = lane; n < N; n += 64) {
-      const int* rec = tree + n * REC;
-      p.t_node_visits[tn0 + n] = rec[0];
-      p.t_node_values[tn0 + n] = __int_as_float(rec[1]);
-      p.t_raw_values[tn0 + n] = __int_as_float(rec[2]);
-      p.t_parents[tn0 + n] = (rec[3] & 0xffff) - 1;
-      p.t_action_from_parent[tn0 + n] = ((rec[3] >> 16) & 0xff) - 1;
-    }
-    if (ok) p.t_root_invalid[(size_t)r * AC + sl] = root_masked ? 1 : 0;
-    if (lane == 0) p.t_depth_sum[r] = depth_sum;
-    for (int n = 0; n < N; ++n) {
-      const int* rec = tree + n * REC;
-      const bool empty = rec[0] == 0;  // a node no simulation created (re-expansions at max_depth)
-      const float edge_disc = (rec[3] >> 30) & 1 ? disc : 1.0f;  // the edges of a chance node carry the bound discount
-      if (ok) {
-        const size_t o = (tn0 + n) * AC + sl;
-        const int iv = rec[4 + sl];
-        const int cidx = (iv & 0xffff) - 1;
-        p.t_children_index[o] = cidx;
-        p.t_children_visits[o] = iv >> 16;
-        p.t_children_prior_probs[o] = __int_as_float(rec[4 + AC + sl]);
-        p.t_children_values[o] = __int_as_float(rec[4 + 2 * AC + sl]);
-        p.t_children_rewards[o] = __int_as_float(rec[4 + 3 * AC + sl]);
-        p.t_children_discounts[o] = cidx >= 0 ? edge_disc : 0.0f;
-        if (empty) p.t_children_prior_logits[o] = 0.0f;
-      }
-      if (sh.emb_lds) {
-        if (lane < E) p.t_embeddings[(tn0 + n) * E + ec] = emb[n * E + ec];
-      } else if (empty && lane < E) {
-        p.t_embeddings[(tn0 + n) * E + ec] = 0.0f;
-      }
-    }
-  }
+  // ---- the finished tree into the handle's HBM arrays, as the step-wise kernels leave them ----
+  if (ex) wave_tree_export<true>(p, tree, emb, sh.emb_lds, r, N, REC, AC, E, ok, sl, lane, disc, root_masked, depth_sum);
 }
 
 }  // namespace mz

@@ -5,31 +5,6 @@
 #include "mz_host.h"
 
 namespace mz {
-namespace {
-
-template <int MODE>
-int launch_wide(int device, const FusedParams& p, const WideShape& sh, size_t lds, hipStream_t stream, std::string* err) {
-  static mzh::LdsGrant granted;  // the kernel's dynamic-LDS limit, raised once per device
-  if (!granted.covers(device, lds)) {
-    const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&mz_act_wide_kernel<MODE>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr_err != hipSuccess) {
-      *err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(attr_err);
-      return MZS_E_RUNTIME;
-    }
-    granted.note(device, lds);
-  }
-  const int grid = (p.B + sh.waves - 1) / sh.waves;
-  hipLaunchKernelGGL(mz_act_wide_kernel<MODE>, dim3(grid), dim3(64 * sh.waves), lds, stream, p, sh);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    *err = std::string("wide kernel launch: ") + hipGetErrorString(e);
-    return MZS_E_RUNTIME;
-  }
-  return MZS_OK;
-}
-
-}  // namespace
 
 int wide_dispatch(int mode, bool gumbel_ok, int device, const FusedParams& p, hipStream_t stream, int A, int E, int F,
                   std::string* err) {
@@ -40,10 +15,10 @@ int wide_dispatch(int mode, bool gumbel_ok, int device, const FusedParams& p, hi
   const WideShape sh = {A, E, F, pl.rec_words, pl.root_words, pl.wg_words, pl.weight_words, pl.emb_lds, pl.waves};
   const size_t lds = (size_t)pl.lds_bytes;
   switch (mode) {
-    case 0: return launch_wide<0>(device, p, sh, lds, stream, err);
-    case 1: return launch_wide<1>(device, p, sh, lds, stream, err);
-    case 2: return launch_wide<2>(device, p, sh, lds, stream, err);
-    default: return launch_wide<3>(device, p, sh, lds, stream, err);
+    case 0: return launch_wave_per_root<mz_act_wide_kernel<0>>("wide kernel launch: ", device, p, sh, lds, stream, err);
+    case 1: return launch_wave_per_root<mz_act_wide_kernel<1>>("wide kernel launch: ", device, p, sh, lds, stream, err);
+    case 2: return launch_wave_per_root<mz_act_wide_kernel<2>>("wide kernel launch: ", device, p, sh, lds, stream, err);
+    default: return launch_wave_per_root<mz_act_wide_kernel<3>>("wide kernel launch: ", device, p, sh, lds, stream, err);
   }
 }
 
@@ -54,10 +29,7 @@ extern "C" int mzs_mlp_wide_plan_policy(int32_t num_actions, int32_t embed_dim, 
   mz::WidePlan pl;
   if (!out || policy < 0 || policy > 1) return MZS_E_INVALID;
   if (!mz::wide_plan(num_actions, embed_dim, 2 * support_size + 1, num_simulations, policy == 1, &pl)) return MZS_E_UNSUPPORTED;
-  out[0] = pl.waves;
-  out[1] = pl.lds_bytes;
-  out[2] = pl.roots_per_cu;
-  out[3] = pl.emb_lds;
+  mz::wide_plan_out(pl, out);
   return MZS_OK;
 }
 extern "C" int mzs_mlp_wide_plan(int32_t num_actions, int32_t embed_dim, int32_t support_size, int32_t num_simulations,

@@ -3,6 +3,7 @@
 #include <string>
 
 #include "mz_fused_launch.h"
+#include "mz_host.h"
 
 namespace mz {
 
@@ -46,6 +47,35 @@ inline bool wide_fit(int wgt, int rec, int E, int S, WidePlan* out) {
 inline bool wide_plan(int A, int E, int F, int S, bool gumbel, WidePlan* out) {
   if (A < 17 || A > 64 || E < 1 || E > 64 || F < 17 || F > 63 || S < 1 || S > 255) return false;
   return wide_fit(wide_round4(wide_weight_words(A, E, F)), 4 + (gumbel ? 5 : 4) * A, E, S, out);
+}
+// what the plan entries of the C-ABI report
+inline void wide_plan_out(const WidePlan& pl, int32_t out[4]) {
+  out[0] = pl.waves, out[1] = pl.lds_bytes, out[2] = pl.roots_per_cu, out[3] = pl.emb_lds;
+}
+
+// Launch of a kernel of this mapping (one root per wavefront, sh.waves roots per workgroup, `lds` bytes of dynamic LDS):
+// MZS_OK, or MZS_E_RUNTIME with *err = the HIP error (`what` in front of a launch error)
+template <auto Kernel, class Params, class Shape>
+int launch_wave_per_root(const char* what, int device, const Params& p, const Shape& sh, size_t lds, hipStream_t stream,
+                         std::string* err) {
+  static mzh::LdsGrant granted;  // the kernel's dynamic-LDS limit, raised once per device
+  if (!granted.covers(device, lds)) {
+    const hipError_t attr_err =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (attr_err != hipSuccess) {
+      *err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(attr_err);
+      return MZS_E_RUNTIME;
+    }
+    granted.note(device, lds);
+  }
+  const int grid = (p.B + sh.waves - 1) / sh.waves;
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(64 * sh.waves), lds, stream, p, sh);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    *err = std::string(what) + hipGetErrorString(e);
+    return MZS_E_RUNTIME;
+  }
+  return MZS_OK;
 }
 
 // mode: that of the fused dispatchers (0 / 1 MuZero policy, 2 / 3 Gumbel policy); the Gumbel modes are served only with

@@ -42,6 +42,7 @@ SEARCH_CASES = [
     (1, 1, 1, 8, 1, 3, False, False, None),      # every width 1
     (4, 3, 5, 8, 4, 1, False, False, None),      # one simulation
     (4, 3, 5, 8, 4, 12, False, False, 3),        # max_depth reached: re-expansion, both node kinds
+    (1, 1, 2, 8, 2, 70, False, False, None),     # one chain: simulations 65..70 back up over two chunks of 64 levels
     "emb_hbm",                                   # (3, 5, E*, 10, 2, S*): the plan keeps the embeddings in HBM
 ]
 
