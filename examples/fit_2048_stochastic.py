@@ -1,20 +1,25 @@
 """2048 with Stochastic MuZero: `muax.Device2048` stepped on the device, every act() the stochastic search over chance
 nodes (4 actions + 32 chance codes) on the default stochastic MLP family -- the decision and the chance function
-evaluated by the library, one launch per simulation --, training with `loss.stochastic_loss_fn` from a host
-`TrajectoryReplayBuffer` (on torch autograd, or with --fused-update on the fused training kernel of this shape).
+evaluated by the library, one launch per simulation --, training with `loss.stochastic_loss_fn` (on torch autograd, or
+with --fused-update on the fused training kernel of this shape).
 
-The loss encodes a chance code from EVERY step's observation, which `DeviceReplayBuffer.sample` does not hand out (it
-keeps the first row of a window), and `fit_vector(device_collect=True)` stores into that buffer only.  So this example
-has its own short loop: the step loop runs on the device with no per-step host copy (observation, mask, action, search
-policy, value, reward and flag stay device tensors), the iteration's stream comes down once, is cut into finished
-episodes (`episode_trajectory`) and goes into the host buffer.
+The default route is the project's own loop: `fit_vector(device_collect=True, device_plan=True)` on a
+`DeviceReplayBuffer`.  The episodes are cut and stored on the device, every batch is one `sample(all_obs=True)` launch
+-- the loss encodes a chance code from EVERY step's observation -- and only the rows of the finished-episode plan come
+to the host.  `update_s` is the time from an iteration's first sample() to the end of its last update().
+
+--host-buffer is the comparison route, a short loop of this file's own: the step loop runs on the device with no
+per-step host copy (observation, mask, action, search policy, value, reward and flag stay device tensors), the
+iteration's stream comes down once, is cut into finished episodes (`episode_trajectory`) and goes into a host
+`TrajectoryReplayBuffer`, whose batches are uploaded again.
 
 Nothing here has been run to a result: whether this recipe learns 2048 is not known.
 
     python examples/fit_2048_stochastic.py [--envs 256] [--steps 64] [--iterations 3] [--updates 20] [--one-launch]
-                                           [--fused-update]
+                                           [--fused-update] [--host-buffer]
 """
 import argparse
+import functools
 import json
 import os
 import sys
@@ -58,6 +63,51 @@ def collect(model, venv, obs, key, steps, num_simulations, pending, n_step, gamm
     return out, obs, key
 
 
+class _Report(list):
+    """fit_vector's metrics rows, printed as they arrive in the form of the host route's lines."""
+
+    def __init__(self, model, buffer, scale):
+        super().__init__()
+        self.model, self.buffer, self.scale, self.first, self.last = model, buffer, scale, None, None
+        sample, update = buffer.sample, model.update
+
+        @functools.wraps(sample)  # (fit_vector reads sample's signature)
+        def timed_sample(*a, **kw):
+            self.first = time.perf_counter() if self.first is None else self.first
+            return sample(*a, **kw)
+
+        @functools.wraps(update)
+        def timed_update(*a, **kw):
+            out = update(*a, **kw)  # (returns the loss as a float: the step has run)
+            self.last = time.perf_counter()
+            return out
+        buffer.sample, model.update = timed_sample, timed_update
+
+    def append(self, row):
+        super().append(row)
+        score = row["G"] * self.scale
+        line = {"iteration": row["iteration"], "route": self.model._last_route,
+                "update_route": self.model._last_update_route, "episodes": row["episodes"], "buffer": len(self.buffer),
+                "mean_score": round(score, 1) if np.isfinite(score) else None, "loss": round(row.get("loss", float("nan")), 4),
+                "collect_s": round(row["collect_s"], 3),
+                "update_s": round(self.last - self.first, 3) if self.first is not None else 0.0}
+        if "test_G" in row:
+            line["test_score"] = round(row["test_G"] * self.scale, 1)
+        self.first = self.last = None
+        print(json.dumps(line), flush=True)
+
+
+def fit_on_device(model, venv, args, discount, k_steps):
+    buffer = muax.DeviceReplayBuffer(2000, 2000 * args.max_episode_steps, random_seed=args.seed)
+    test_env = muax.Device2048(args.test_envs, max_episode_steps=args.max_episode_steps, seed=args.seed + 1,
+                               reward_shift=args.reward_shift)
+    muax.fit_vector(model, venv, test_env, n_step=10, gamma=discount, alpha=0.5, buffer=buffer, iterations=args.iterations,
+                    steps_per_iteration=args.steps, num_simulations=args.sims, k_steps=k_steps, num_trajectory=32,
+                    num_update_per_iteration=args.updates, test_interval=max(args.iterations, 1), random_seed=args.seed,
+                    trajectory_weight="sum", metrics=_Report(model, buffer, 2 ** args.reward_shift), device_collect=True,
+                    device_plan=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=256)
@@ -72,6 +122,9 @@ def main():
                     help="act() with the whole search in one launch (MuZero(stochastic_one_launch=True)): the same bits")
     ap.add_argument("--fused-update", action="store_true",
                     help="update() on the fused training kernel (MuZero(stochastic_fused_update=True)) instead of autograd")
+    ap.add_argument("--host-buffer", action="store_true",
+                    help="this file's own loop on a host TrajectoryReplayBuffer instead of fit_vector on the device buffer")
+    ap.add_argument("--test-envs", type=int, default=16, help="greedy test episodes after the first iteration (fit_vector)")
     args = ap.parse_args()
 
     support_size, E, Cn, discount, k_steps = 31, 32, 32, 0.997, 5
@@ -80,6 +133,9 @@ def main():
     model = muax.MuZero(net, policy="stochastic", discount=discount, support_size=support_size,
                         optimizer=muax.optimizers.create_optimizer("adam", 2e-3), stochastic_one_launch=args.one_launch,
                         stochastic_fused_update=args.fused_update)
+    if not args.host_buffer:
+        fit_on_device(model, venv, args, discount, k_steps)
+        return
     obs = venv.reset_device()
     model.init(args.seed, np.zeros((1, obs.shape[1]), np.float32))
     buffer = muax.TrajectoryReplayBuffer(2000, random_seed=args.seed)
@@ -98,7 +154,7 @@ def main():
         scores = [float(np.sum(tr.batched_transitions.r)) * 2 ** args.reward_shift for tr in episodes]
         print(json.dumps({"iteration": it, "route": model._last_route, "update_route": model._last_update_route, "episodes": len(episodes), "buffer": len(buffer),
                           "mean_score": round(float(np.mean(scores)), 1) if scores else None, "loss": round(loss, 4),
-                          "collect_s": round(t1 - t0, 2), "update_s": round(time.perf_counter() - t1, 2)}), flush=True)
+                          "collect_s": round(t1 - t0, 3), "update_s": round(time.perf_counter() - t1, 3)}), flush=True)
 
 
 if __name__ == "__main__":

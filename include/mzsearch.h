@@ -779,15 +779,23 @@ int mzs_replay_refresh(const mzs_replay_arena *arena, int32_t head, int32_t coun
  *   episode e = the first with CW[e] > u0 * CW[count - 1];   m = length(e) - k_steps;
  *   start i = the first i < m with cw[i] > u1 * cw[m - 1], or floor(u1 * m) when cw[m - 1] == 0;
  *   the outputs are transitions i .. i + k_steps - 1 of that episode (obs: transition i alone).
+ *   obs_steps == k_steps: obs is [batch, k_steps, obs_dim] and row j holds the observations of transitions
+ *   i .. i + k_steps - 1, one contiguous run of the arena copied in the same launch from the same draw and searches
+ *   (the layout mzs_stochastic_mlp_loss_grad reads); every other output, and obs[j][0], has the bits of obs_steps == 0.
+ *   obs_steps == 0: obs is [batch, obs_dim] as above.  Any other value is MZS_E_INVALID before any launch, as is
+ *   k_steps * obs_dim >= 2^31 with obs_steps set.
  * With every weight zero (CW[count - 1] == 0: the caller's error) the draw lands on the newest episode; a row whose
- * episode is no longer than k_steps is zero-filled, serial and start -1. */
+ * episode is no longer than k_steps is zero-filled (all k_steps * obs_dim floats of obs with obs_steps), serial and
+ * start -1.
+ * obs_steps takes the place of a reserved field that was never read and that callers zero-fill: the struct's size and
+ * layout, and MZS_ABI_VERSION, are unchanged. */
 typedef struct mzs_replay_sample_args {
   int32_t struct_size;     /* = sizeof(mzs_replay_sample_args) */
   int32_t count;           /* rows of the compact table */
   int32_t batch, k_steps, sample_per_trajectory;
   uint32_t key[2];         /* HOST values */
-  int32_t reserved0;
-  float *obs;              /* out [batch, obs_dim] */
+  int32_t obs_steps;       /* 0, or k_steps (was reserved0, which every caller zero-filled) */
+  float *obs;              /* out [batch, obs_dim], or [batch, k_steps, obs_dim] with obs_steps == k_steps */
   int32_t *a;              /* out [batch, k_steps] */
   float *r, *Rn, *v;       /* out [batch, k_steps] */
   uint8_t *done;           /* out [batch, k_steps], 0 / 1 */

@@ -185,7 +185,7 @@ class MzsReplayStoreArgs(C.Structure):
 
 class MzsReplaySampleArgs(C.Structure):
     _fields_ = ([("struct_size", C.c_int32), ("count", C.c_int32), ("batch", C.c_int32), ("k_steps", C.c_int32),
-                 ("sample_per_trajectory", C.c_int32), ("key", C.c_uint32 * 2), ("reserved0", C.c_int32)]
+                 ("sample_per_trajectory", C.c_int32), ("key", C.c_uint32 * 2), ("obs_steps", C.c_int32)]
                 + [(n, _vp) for n in ("obs", "a", "r", "Rn", "v", "done", "pi", "w", "serial", "start")])
 
 

@@ -8,7 +8,8 @@
 //   replay_refresh_kernel  the live episodes, oldest first, as a compact table with the inclusive prefix sum CW of the
 //                          weights of those longer than k_steps (one wavefront; after adds or a change of k_steps)
 //   replay_sample_kernel   per batch row: two threefry draws, the episode and the start by binary search in CW / cw,
-//                          then 64 lanes copy the window; replay_sample_is_kernel, the same rows, adds the row's
+//                          then 64 lanes copy the window (obs: its first row, or with obs_steps the contiguous run
+//                          of all k); replay_sample_is_kernel, the same rows, adds the row's
 //                          importance-sampling weight, which replay_is_normalise_kernel scales by the batch maximum
 // and the two of reanalysis (fresh search results for episodes already held), again one wavefront per episode:
 //   replay_gather_obs_kernel  the observations of the selected episodes as one dense stream, zero-padded to whole chunks
@@ -86,6 +87,7 @@ struct ReplayReanalyseArgs {
 struct ReplaySampleArgs {
   ReplayArena ar;
   int count, B, k, spt;
+  int obs_steps;              // 0: obs is [B, obs_dim], the window's first observation; k: [B, k, obs_dim], every step's
   uint32_t key0, key1;
   float* obs; int32_t* a; float* r; float* Rn; float* v; uint8_t* done; float* pi; float* w;
   long long* serial; int32_t* start;
@@ -505,6 +507,8 @@ MZ_DEV void replay_sample_row(const ReplaySampleArgs& p, const ReplayIsArgs& q) 
   if (row >= p.B) return;
   const ReplayArena& ar = p.ar;
   const int k = p.k, A = ar.A, od = ar.obs_dim;
+  // floats of obs per row: the window's observations are ONE contiguous run of the arena, its first obs_dim the default
+  const int no = (p.obs_steps ? k : 1) * od;
   // the draws and the two searches are wave-uniform: scalar loads, done once per row
   const double u0 = uniform53(p.key0, p.key1, (uint32_t)(row / p.spt), 0u);
   const double u1 = uniform53(p.key0, p.key1, (uint32_t)row, 1u);
@@ -516,7 +520,7 @@ MZ_DEV void replay_sample_row(const ReplaySampleArgs& p, const ReplayIsArgs& q) 
   const size_t ok = (size_t)row * k;
   if (m <= 0) {  // nothing to draw from (the host refuses such a buffer; all-zero weights can still lead here): zeros
     for (int i = lane; i < k * A; i += 64) p.pi[ok * A + i] = 0.f;
-    for (int i = lane; i < od; i += 64) p.obs[(size_t)row * od + i] = 0.f;
+    for (int i = lane; i < no; i += 64) p.obs[(size_t)row * no + i] = 0.f;
     for (int i = lane; i < k; i += 64) {
       p.a[ok + i] = 0; p.r[ok + i] = 0.f; p.Rn[ok + i] = 0.f; p.v[ok + i] = 0.f; p.done[ok + i] = 0; p.w[ok + i] = 0.f;
     }
@@ -547,7 +551,7 @@ MZ_DEV void replay_sample_row(const ReplaySampleArgs& p, const ReplayIsArgs& q) 
     p.done[ok + i] = ar.done[at + i];
     p.w[ok + i] = (float)ar.w[at + i];
   }
-  for (int i = lane; i < od; i += 64) p.obs[(size_t)row * od + i] = ar.obs[at * od + i];
+  for (int i = lane; i < no; i += 64) p.obs[(size_t)row * no + i] = ar.obs[at * od + i];
   if (lane == 0) { p.serial[row] = ar.c_serial[e]; p.start[row] = s; }
   if constexpr (IS) {
     // wave-uniform: the marginal probability of window (e, s), the same for every row whatever shares its episode

@@ -98,10 +98,14 @@ int check_sample(const mzs_replay_arena* arena, const mzs_replay_sample_args* a,
     return mzh::fail(nullptr, MZS_E_INVALID, "%s: count in 1..capacity; batch, k_steps, sample_per_trajectory >= 1", who);
   if ((int64_t)a->k_steps * arena->num_actions >= ((int64_t)1 << 31) || a->k_steps >= arena->max_steps)
     return mzh::fail(nullptr, MZS_E_INVALID, "%s: k_steps too large", who);
+  if (a->obs_steps != 0 && a->obs_steps != a->k_steps)
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: obs_steps must be 0 (the first observation) or k_steps (every step's)", who);
+  if (a->obs_steps != 0 && (int64_t)a->k_steps * arena->obs_dim >= ((int64_t)1 << 31))
+    return mzh::fail(nullptr, MZS_E_INVALID, "%s: with obs_steps, k_steps * obs_dim must be below 2^31", who);
   if (!a->obs || !a->a || !a->r || !a->Rn || !a->v || !a->done || !a->pi || !a->w || !a->serial || !a->start)
     return mzh::fail(nullptr, MZS_E_INVALID, "%s: null output pointer", who);
   p->count = a->count; p->B = a->batch; p->k = a->k_steps; p->spt = a->sample_per_trajectory;
-  p->key0 = a->key[0]; p->key1 = a->key[1];
+  p->obs_steps = a->obs_steps; p->key0 = a->key[0]; p->key1 = a->key[1];
   p->obs = a->obs; p->a = a->a; p->r = a->r; p->Rn = a->Rn; p->v = a->v; p->done = a->done; p->pi = a->pi; p->w = a->w;
   p->serial = (long long*)a->serial; p->start = a->start;
   return MZS_OK;

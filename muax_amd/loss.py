@@ -113,7 +113,7 @@ def stochastic_loss_fn(muzero_instance, batch: Transition, vqvae_beta: float = 0
     obs = t(batch.obs)
     if obs.dim() < 3 or obs.shape[0] != B or obs.shape[1] < L:
         raise ValueError(f"the stochastic loss needs every step's observation: batch.obs must be [B, L, ...] with L = {L} "
-                         f"rows per window, got {tuple(obs.shape)} (DeviceReplayBuffer.sample keeps the first row only)")
+                         f"rows per window, got {tuple(obs.shape)} (DeviceReplayBuffer.sample hands them out with all_obs=True)")
     S = m._support_size
     r_t = mx_utils.scalar_to_support(t(batch.r).reshape(B, L), S).detach()
     Rn_t = mx_utils.scalar_to_support(t(batch.Rn).reshape(B, L), S).detach()
@@ -282,7 +282,7 @@ class StochasticFusedLossGrad(_FusedStep):
     def _obs(self, obs, B, L):  # a row for every step
         if obs.dim() < 3 or obs.shape[0] != B or obs.shape[1] < L:
             raise ValueError(f"the stochastic loss needs every step's observation: batch.obs must be [B, L, ...] with L = {L} "
-                             f"rows per window, got {tuple(obs.shape)} (DeviceReplayBuffer.sample keeps the first row only)")
+                             f"rows per window, got {tuple(obs.shape)} (DeviceReplayBuffer.sample hands them out with all_obs=True)")
         return obs[:, :L].reshape(B, L, -1).contiguous()
 
     def __call__(self, batch: Transition, vqvae_beta: float = 0.25, divide_by_length: bool = False, sample_weight=None):

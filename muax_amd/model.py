@@ -712,7 +712,7 @@ class MuZero:
                     raise
                 fused = False
         if not (fused or stoch_fused):
-            loss_fn = self.loss_fn or (mz_loss.stochastic_loss_fn if self._stochastic else mz_loss.default_loss_fn)
+            loss_fn = self.loss_fn or (mz_loss.stochastic_loss_fn if self.trains_stochastic else mz_loss.default_loss_fn)
             loss = loss_fn(self, batch, *args, **kwargs)
             loss.backward()
             if dp_mean:
@@ -721,6 +721,12 @@ class MuZero:
         self._optimizer.step()
         self._weights_version += 1
         return {"loss": float(loss.item())}
+
+    @property
+    def trains_stochastic(self):
+        """Whether update() trains with loss.stochastic_loss_fn (an SMZNetwork): its batches then need an observation
+        for every step of a window, `DeviceReplayBuffer.sample(all_obs=True)`."""
+        return self._stochastic
 
     def unroll_values(self, batch, k_prio=None, backend: str = "auto"):
         """The forward unroll of a sampled batch with the CURRENT network: `(values, priorities)`, both [B, kp] float32

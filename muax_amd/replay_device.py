@@ -100,7 +100,8 @@ class DeviceReplayBuffer(BaseReplayBuffer):
     `sample()` differs from the host buffer in two documented ways: the batch size is FIXED (episodes no longer than
     `k_steps` carry no probability instead of shortening the batch), and the random stream is a threefry key
     (`random_seed`, split on every call, or `key=`) instead of Python's `random`.  `obs` comes out as [B, 1, obs_dim],
-    the window's first observation -- all the losses read."""
+    the window's first observation -- all the deterministic losses read -- or, with `sample(all_obs=True)`, as
+    [B, k_steps, obs_dim], every step's, which the stochastic loss needs."""
 
     def __init__(self, capacity, max_steps, obs_dim=None, num_actions=None, random_seed=None, device=None,
                  transition_class=Transition):
@@ -478,7 +479,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         self._dirty = True
 
     def sample(self, batch_size=32, num_trajectory: int = None, k_steps: int = 5, sample_per_trajectory: int = 1,
-               key=None, with_indices: bool = False, is_beta=None, is_normalize: bool = True):
+               key=None, with_indices: bool = False, is_beta=None, is_normalize: bool = True, all_obs: bool = False):
         """A batch of `num_trajectory * sample_per_trajectory` windows of `k_steps` transitions (the arguments of
         muax/replay_buffer.py:192-240; `batch_size` alone means that many trajectories, one window each) as a
         Transition of device tensors: obs [B, 1, obs_dim], a [B, k] int32, r / Rn / v / w [B, k] float32, done
@@ -496,7 +497,14 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         weight of the batch, so that the weights only ever scale a step down.  A zero-filled row gets 0.  The draws
         and every field are those of the call without `is_beta`, bit for bit, and nothing is copied to the host or
         synchronised: one more small launch for the normalisation.  Outside 0..1 or not finite: ValueError before
-        any launch.  None: no weights, today's return value."""
+        any launch.  None: no weights, today's return value.
+
+        `all_obs=True`: obs is [B, k_steps, obs_dim], the observation of EVERY transition of the window -- what
+        `loss.stochastic_loss_fn` and the fused stochastic training step read (the chance code of transition i is
+        encoded from obs_i).  The same launch copies them: a window's observations are one contiguous run of the
+        arena.  Every other field, the indices and `isw` are those of the call without it for the same key, bit for
+        bit, and obs[:, 0] is that call's obs[:, 0].  `value_priorities`, `unroll_values` and `default_loss_fn` read
+        obs[:, 0] alone and are therefore indifferent to the flag.  False: obs [B, 1, obs_dim], today's return value."""
         if is_beta is not None:
             is_beta = float(is_beta)
             if not 0.0 <= is_beta <= 1.0:  # (False for NaN)
@@ -522,7 +530,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         else:
             key = prng.as_key(key)
         dev, f32 = self._device, torch.float32
-        obs = torch.empty((B, 1, self.obs_dim), dtype=f32, device=dev)
+        obs = torch.empty((B, k if all_obs else 1, self.obs_dim), dtype=f32, device=dev)
         a = torch.empty((B, k), dtype=torch.int32, device=dev)
         r, Rn, v, w = (torch.empty((B, k), dtype=f32, device=dev) for _ in range(4))
         done = torch.empty((B, k), dtype=torch.bool, device=dev)
@@ -531,6 +539,7 @@ class DeviceReplayBuffer(BaseReplayBuffer):
         start = torch.empty(B, dtype=torch.int32, device=dev)
         s = _lib.args(_lib.MzsReplaySampleArgs)  # (per training step: fields by attribute, which is 1 us cheaper)
         s.count, s.batch, s.k_steps, s.sample_per_trajectory = len(self._eps), B, k, spt
+        s.obs_steps = k if all_obs else 0
         s.key[0], s.key[1] = int(key[0]), int(key[1])
         s.obs, s.a, s.r, s.Rn, s.v, s.done = (x.data_ptr() for x in (obs, a, r, Rn, v, done))
         s.pi, s.w, s.serial, s.start = pi.data_ptr(), w.data_ptr(), serial.data_ptr(), start.data_ptr()

@@ -486,7 +486,8 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                max_training_steps: int = 10000, test_interval: int = 10, num_test_episodes: int = 10,
                random_seed: int = 42, temperature_fn=None, metrics=None, trajectory_weight: str = "mean",
                reanalyse_every: int = 0, reanalyse_episodes=None, priority_update: bool = False,
-               priority_steps=None, is_beta=None, device_collect: bool = False, device_plan: bool = False):
+               priority_steps=None, is_beta=None, device_collect: bool = False, device_plan: bool = False,
+               all_obs=None):
     """The reference's fit() loop (muax/train.py:175-241: temperature schedule, buffer sampling, update,
     greedy test) with the acting half on a vector environment: per iteration `steps_per_iteration`
     batched act() calls -> finished episodes -> buffer, then `num_update_per_iteration` updates.
@@ -526,7 +527,15 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     `device_plan=True` (needs `device_collect=True` and a device environment; a ValueError otherwise) hands the flag to
     that collector: the episodes are cut and their returns summed on the device (`DeviceVectorCollector`), `G` of the
     metrics row is then the mean of sequential fp64 sums -- equal to the host's for integer rewards.  False: the key
-    stream and every result are unchanged."""
+    stream and every result are unchanged.
+    `all_obs`: whether every batch is sampled with `sample(all_obs=True)`, an observation for every step of a window
+    (`DeviceReplayBuffer.sample`).  None asks for them exactly when `update()` trains with `loss.stochastic_loss_fn` (a
+    model on an `SMZNetwork`, `MuZero.trains_stochastic`) and the buffer's `sample` takes `all_obs`; the host
+    `TrajectoryReplayBuffer` returns every row anyway and is left alone.  True / False force it; True with a buffer
+    whose `sample` takes no `all_obs` is a ValueError.  So a stochastic model trains through this loop on a
+    `DeviceReplayBuffer` and a device environment, with `reanalyse_every`, `priority_update` and `is_beta` as for the
+    deterministic model; `priority_steps` with such a model is a ValueError (`MuZero.unroll_values` unrolls the
+    deterministic dynamics and is not built for an `SMZNetwork`).  For any other model None changes nothing."""
     if priority_steps is not None and int(priority_steps) < 1:
         raise ValueError("priority_steps must be None or >= 1")
     if trajectory_weight not in ("mean", "sum"):
@@ -539,13 +548,23 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     from .train import _temperature_fn, test
     temperature_fn = temperature_fn or _temperature_fn
     buffer = buffer if buffer is not None else TrajectoryReplayBuffer(500)
+    import inspect
+    sample_takes = inspect.signature(buffer.sample).parameters
     if is_beta is not None:
-        import inspect
-        if "is_beta" not in inspect.signature(buffer.sample).parameters:
+        if "is_beta" not in sample_takes:
             raise ValueError(f"fit_vector: is_beta needs a buffer whose sample() takes is_beta (DeviceReplayBuffer); "
                              f"{type(buffer).__name__}.sample does not")
         if not callable(is_beta) and not 0.0 <= float(is_beta) <= 1.0:
             raise ValueError("fit_vector: is_beta must be None, a number in 0..1 or a callable")
+    stochastic = bool(getattr(model, "trains_stochastic", False))  # (update()'s own predicate for stochastic_loss_fn)
+    if all_obs and "all_obs" not in sample_takes:
+        raise ValueError(f"fit_vector: all_obs needs a buffer whose sample() takes all_obs (DeviceReplayBuffer); "
+                         f"{type(buffer).__name__}.sample does not")
+    all_obs = (stochastic and "all_obs" in sample_takes) if all_obs is None else bool(all_obs)
+    prioritise = bool(priority_update) and hasattr(buffer, "update_priorities")
+    if prioritise and priority_steps is not None and stochastic:
+        raise ValueError("fit_vector: priority_update with priority_steps needs MuZero.unroll_values, which is not built "
+                         "for an SMZNetwork (a stochastic model); use priority_steps=None (value_priorities)")
     on_device = hasattr(venv, "step_device")
     if on_device and not device_collect:
         raise ValueError(f"fit_vector: {type(venv).__name__} is a device environment (it has step_device) and needs "
@@ -562,10 +581,11 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                                           min_length=k_steps, device_plan=device_plan)
     else:
         collector = VectorCollector(venv, n_step, gamma, alpha)
-    prioritise = bool(priority_update) and hasattr(buffer, "update_priorities")
     sample_kw = dict(num_trajectory=num_trajectory, k_steps=k_steps, sample_per_trajectory=sample_per_trajectory)
     if prioritise:
         sample_kw["with_indices"] = True
+    if all_obs:
+        sample_kw["all_obs"] = True
     key = prng.PRNGKey(random_seed)
     key, test_key, subkey = prng.split(key, 3)
     model.init(subkey, np.asarray(venv.reset())[:1].astype(float))

@@ -2,10 +2,14 @@
 slices, five uploads per batch) against `DeviceReplayBuffer.sample` + `update()` (one launch, the batch read in place),
 and each `sample` on its own.  Default MLP trio on CartPole shapes, 500 stored episodes of about 200 steps.
 
-    python tools/bench_replay.py [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
+    python tools/bench_replay.py [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...] [--all-obs] [--obs-dim 4]
     python tools/bench_replay.py --reanalyse [--iters 200] [--episodes 500]
     python tools/bench_replay.py --priorities [--prio-steps KP] [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
     python tools/bench_replay.py --is-weights [--is-beta 0.4] [--iters 200] [--episodes 500] [--shape NUM_TRAJECTORY,K ...]
+
+`--all-obs` (the default mode): the device columns sample with `all_obs=True`, every step's observation
+([B, k, obs_dim]) in the same launch; `--obs-dim` sets the observation width of the stored episodes and the model (16 is
+2048's).  The host buffer returns every row anyway.
 
 `--reanalyse` times, on the same device buffer and with 50 simulations, (a) `DeviceReplayBuffer.reanalyse()` of the
 whole buffer, (b) the same work through the host -- `episode().obs` downloaded, `act` NumPy in / out in the same
@@ -187,6 +191,7 @@ def is_weight_figures(dev, shapes, iters, beta):
 
 
 def main():
+    global OBS
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reanalyse", action="store_true", help="time reanalysis instead of sampling")
     ap.add_argument("--priorities", action="store_true", help="time the training step with the priority write-back")
@@ -195,10 +200,15 @@ def main():
     ap.add_argument("--is-weights", action="store_true",
                     help="time sample(is_beta=) beside sample() and update(sample_weight=) beside update()")
     ap.add_argument("--is-beta", type=float, default=0.4, help="with --is-weights: the exponent (default 0.4)")
+    ap.add_argument("--all-obs", action="store_true",
+                    help="default mode: the device columns sample every step's observation (all_obs=True)")
+    ap.add_argument("--obs-dim", type=int, default=OBS, help="observation width (default 4, CartPole's)")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--episodes", type=int, default=500)
     ap.add_argument("--shape", action="append", default=[], metavar="NUM_TRAJECTORY,K")
     a = ap.parse_args()
+    OBS = a.obs_dim
+    obs_kw = {"all_obs": True} if a.all_obs else {}
     shapes = [tuple(int(x) for x in s.split(",")) for s in a.shape] or [(32, 10), (4096, 10)]
     warm_runtime()
     eps = episodes(a.episodes, np.random.default_rng(0))
@@ -220,16 +230,18 @@ def main():
     if a.is_weights:
         is_weight_figures(dev, shapes, a.iters, a.is_beta)
         return
+    if a.all_obs:
+        print(f"device columns with all_obs=True: obs [B, k, {OBS}]")
     print(f"{'num_trajectory x k':>18} | {'host sample':>11} {'host s+upd':>10} | {'dev sample':>10} {'dev s+upd':>9} | "
           f"{'update':>7} | {'s+upd host/dev':>14} {'sample host/dev':>15}")
     for n, k in shapes:
         m_host, m_dev = model(), model()
-        fixed = dev.sample(num_trajectory=n, k_steps=k)
+        fixed = dev.sample(num_trajectory=n, k_steps=k, **obs_kw)
         res = {
             "hs": median_ms(lambda: host.sample(num_trajectory=n, k_steps=k), a.iters),
             "hu": median_ms(lambda: m_host.update(host.sample(num_trajectory=n, k_steps=k), backend="hip"), a.iters),
-            "ds": median_ms(lambda: dev.sample(num_trajectory=n, k_steps=k), a.iters),
-            "du": median_ms(lambda: m_dev.update(dev.sample(num_trajectory=n, k_steps=k), backend="hip"), a.iters),
+            "ds": median_ms(lambda: dev.sample(num_trajectory=n, k_steps=k, **obs_kw), a.iters),
+            "du": median_ms(lambda: m_dev.update(dev.sample(num_trajectory=n, k_steps=k, **obs_kw), backend="hip"), a.iters),
             "u": median_ms(lambda: m_dev.update(fixed, backend="hip"), a.iters),
         }
         print(f"{n:>13} x {k:<2} | {res['hs']:11.3f} {res['hu']:10.3f} | {res['ds']:10.3f} {res['du']:9.3f} | "
