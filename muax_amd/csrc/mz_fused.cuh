@@ -71,7 +71,6 @@ namespace mz {
 #endif
 
 constexpr int kMaxSims = 256;
-constexpr int kHidden = 16;  // hk.Linear(16) everywhere in muax/nn.py:73-115
 
 struct FusedParams {
   // inputs

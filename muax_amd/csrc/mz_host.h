@@ -59,4 +59,14 @@ inline int select_device(int device, const char* who) {
   MZS_HIP(nullptr, hipSetDevice(device));
   return MZS_OK;
 }
+
+// the 18 weight pointers of the default MLP trio into a kernel argument block with the same member names
+template <class D>
+void copy_weights(const mzs_mlp_weights& w, D& d) {
+  d.repr_w = w.repr_w; d.repr_b = w.repr_b;
+  d.pv_w1 = w.pv_w1; d.pv_b1 = w.pv_b1; d.pv_w2 = w.pv_w2; d.pv_b2 = w.pv_b2;
+  d.pp_w1 = w.pp_w1; d.pp_b1 = w.pp_b1; d.pp_w2 = w.pp_w2; d.pp_b2 = w.pp_b2;
+  d.dr_w1 = w.dr_w1; d.dr_b1 = w.dr_b1; d.dr_w2 = w.dr_w2; d.dr_b2 = w.dr_b2;
+  d.dn_w1 = w.dn_w1; d.dn_b1 = w.dn_b1; d.dn_w2 = w.dn_w2; d.dn_b2 = w.dn_b2;
+}
 }  // namespace mzh

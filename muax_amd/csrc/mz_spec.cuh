@@ -23,6 +23,12 @@ namespace mz {
 constexpr float kFltTiny = 1.17549435e-38f;
 constexpr float kFltLowest = -3.40282347e+38f;
 
+constexpr int kHidden = 16;  // hk.Linear(16) everywhere in muax/nn.py:73-115
+// one Linear(16)-elu-Linear head, haiku layout w1 [in, 16], b1 [16], w2 [16, out], b2 [out] (global memory or LDS)
+struct Mlp2 {
+  const float *w1, *b1, *w2, *b2;
+};
+
 template <int I, int N>
 struct StaticFor {
   template <class Fn>

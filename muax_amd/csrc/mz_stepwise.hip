@@ -566,8 +566,7 @@ int mzh::act_mlp_generic(mzs_handle* h, const mzs_act_args* a, void* stream_) {
   mzh::copy_weights(w, g);
   g.obs_dim = w.obs_dim; g.E = E; g.A = A; g.F = F; g.support = w.support_size; g.pred_on_parent = w.recurrent_pred_on;
   g.discount = w.discount;
-  const int ew = E > w.obs_dim ? E : w.obs_dim;
-  const size_t lds_root = sizeof(float) * (size_t)mz::gen_scratch_words(ew, A);
+  const size_t lds_root = sizeof(float) * (size_t)mz::gen_scratch_words(mz::gen_obs_width(E, w.obs_dim), A);
   const size_t lds_search = sizeof(int32_t) * 15 * ((size_t)S + 2) + sizeof(float) * (size_t)mz::gen_scratch_words(E, A);
   if (lds_root > 64 * 1024 || lds_search > 64 * 1024)
     return fail(h, MZS_E_UNSUPPORTED, "mzs_act_mlp (generic route): num_simulations / embedding too large for the LDS of a workgroup");

@@ -39,10 +39,6 @@ namespace mz {
 struct StochWideShape {
   int rec_words, root_words, wg_words, weight_words, emb_lds, waves;
 };
-// one Linear(16)-elu-Linear head in LDS, haiku layout
-struct StochHead {
-  const float *w1, *b1, *w2, *b2;
-};
 
 // MODE 0 / 1: without / with mctx's tie-break noise at the decision nodes (the handle's `tiebreak`)
 template <int MODE>
@@ -64,14 +60,14 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
     return static_cast<const float*>(d);
   };
   auto head = [&](int i, int n_in, int n_out) {
-    StochHead h;
+    Mlp2 h;
     h.w1 = stage(p.w[4 * i], n_in * H);
     h.b1 = stage(p.w[4 * i + 1], H);
     h.w2 = stage(p.w[4 * i + 2], H * n_out);
     h.b2 = stage(p.w[4 * i + 3], n_out);
     return h;
   };
-  const StochHead ad = head(0, E + A, E), av = head(1, E, F), ac = head(2, E, C), cr = head(3, E + C, F),
+  const Mlp2 ad = head(0, E + A, E), av = head(1, E, F), ac = head(2, E, C), cr = head(3, E + C, F),
                   cn = head(4, E + C, E), pv = head(5, E, F), pp = head(6, E, A);
   float* tbl = wl + sh.weight_words;
   wave_stage_puct_table(tbl, S, p.pb_c_init, p.pb_c_base);
@@ -175,7 +171,7 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
     const float s_par = lane < E ? emb[parent * E + ec] : 0.0f;
     float reward = 0.0f, value, logit;
     {
-      const StochHead d1 = decision ? ad : cn;  // the next embedding's head; the rows of lanes without a head repeat it
+      const Mlp2 d1 = decision ? ad : cn;  // the next embedding's head; the rows of lanes without a head repeat it
       const float* w1 = ((grp || decision) ? d1.w1 : cr.w1) + u;
       float a1 = wide_chain(s_par, E, w1);
       a1 = __builtin_fmaf(1.0f, w1[(E + hot) * H], a1);  // (the one-hot's other links add nothing: see the header)
@@ -183,7 +179,7 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
       const float ns = wave_min_max_normalize(wide_out<16>(h, d1.w2, d1.b2, E, ec), E, lane);
       if (lane < E) emb[newn * E + ec] = ns;
       if (!decision) reward = wave_decode(wide_out<0>(h, cr.w2, cr.b2, F, fc), F, p.support, lane);
-      const StochHead hv = decision ? av : pv, hp = decision ? ac : pp;
+      const Mlp2 hv = decision ? av : pv, hp = decision ? ac : pp;
       const int n_pol = decision ? C : A, pj = decision ? lane - A : lane;
       const int pjc = pj < 0 ? 0 : (pj > n_pol - 1 ? n_pol - 1 : pj);
       const float h2 = elu(wide_chain(ns, E, (grp ? hp.w1 : hv.w1) + u) + (grp ? hp.b1 : hv.b1)[u]);

@@ -6,15 +6,11 @@
 //
 // in ONE launch, one wavefront per window.  Only what a value needs is evaluated: the value head of the prediction net
 // (not the policy head) and the next-state branch of the dynamics net (not the reward head).  Everything is built from the
-// run-time-shape blocks of mz_mlp_generic.cuh, so the arithmetic is the project's one spec ("MZ-F32") for any widths:
+// run-time-shape blocks and stages of mz_mlp_blocks.cuh, so the arithmetic is the project's one spec ("MZ-F32") for any widths:
 // v_i has the bits of the oracle's root_inference / recurrent_inference chain, and of act()'s root value for i = 0.
 // No atomics, nothing that depends on the launch geometry: the same bits on every run.
 #pragma once
-// mz_mlp_generic.cuh defines the root kernel of the generic act() route, which mz_stepwise.hip emits; this unit takes the
-// header's device functions only, so its copy of that kernel gets a name of its own (never launched)
-#define mz_mlp_root_kernel mz_unroll_unused_root_kernel
-#include "mz_mlp_generic.cuh"
-#undef mz_mlp_root_kernel
+#include "mz_mlp_blocks.cuh"
 
 #pragma clang fp contract(off)
 
@@ -30,34 +26,17 @@ struct UnrollArgs {
   float* prio;       // [B, kp] or null
 };
 
-// gen_prediction without the policy head: value logits of the embedding `s` (LDS) -> G.vl, the decoded value returned in
-// lanes 0..15 (G.hid[0..16) and G.vl are free again after the last barrier)
-MZ_DEV float gen_value(const MlpGen& w, const GenLds& G, const float* s, int tid) {
-  if (tid < 16) G.hid[tid] = elu(gen_linear(s, w.E, w.pv_w1, w.pv_b1, kGenHidden, tid));
-  __syncthreads();
-  for (int j = tid; j < w.F; j += 64) G.vl[j] = gen_linear(G.hid, kGenHidden, w.pv_w2, w.pv_b2, w.F, j);
-  __syncthreads();
-  float v = 0.0f;
-  if (tid < 16) v = gen_decode(G.vl, w.F, w.support, tid);
-  __syncthreads();
-  return v;
-}
-
 __global__ __launch_bounds__(64) void mz_mlp_unroll_kernel(const UnrollArgs p) {
   extern __shared__ float unroll_f[];
   const MlpGen& w = p.w;
   const int r = blockIdx.x, tid = threadIdx.x;
   if (r >= p.B) return;
   const int E = w.E, A = w.A;
-  const GenLds G = gen_lds(unroll_f, E > w.obs_dim ? E : w.obs_dim, A);  // sa holds the observation first
-  for (int i = tid; i < w.obs_dim; i += 64) G.sa[i] = p.obs[(size_t)r * w.obs_dim + i];
-  __syncthreads();
-  for (int e = tid; e < E; e += 64) G.ns[e] = gen_linear(G.sa, w.obs_dim, w.repr_w, w.repr_b, E, e);
-  __syncthreads();
-  gen_min_max_normalize(G.ns, E, tid);
-  __syncthreads();
+  const GenLds G = gen_lds(unroll_f, gen_obs_width(E, w.obs_dim), A);
+  gen_embed(w.repr_w, w.repr_b, p.obs + (size_t)r * w.obs_dim, w.obs_dim, E, G, tid);
+  const Mlp2 pv = w.pv(), pp = w.pp(), dr = w.dr(), dn = w.dn();  // (pp, dr: passed with their flags false, never read)
   for (int i = 0; i < p.kp; ++i) {
-    const float v = gen_value(w, G, G.ns, tid);
+    const float v = gen_prediction(pv, pp, false, 0, E, w.F, w.support, G, G.ns, tid);
     if (tid == 0) {
       const size_t o = (size_t)r * p.kp + i;
       if (p.values) p.values[o] = v;
@@ -66,16 +45,8 @@ __global__ __launch_bounds__(64) void mz_mlp_unroll_kernel(const UnrollArgs p) {
     }
     if (i + 1 == p.kp) break;
     // Dynamic's next-state branch on [s, onehot(a)]; the one-hot by comparison: an action outside 0..A-1 is all zeros
-    const int action = p.act[(size_t)r * p.L + i];
-    for (int k = tid; k < E; k += 64) G.sa[k] = G.ns[k];
-    for (int k = tid; k < A; k += 64) G.sa[E + k] = (k == action) ? 1.0f : 0.0f;
-    __syncthreads();
-    if (tid < 16) G.hid[16 + tid] = elu(gen_linear(G.sa, E + A, w.dn_w1, w.dn_b1, kGenHidden, tid));
-    __syncthreads();
-    for (int e = tid; e < E; e += 64) G.ns[e] = gen_linear(G.hid + 16, kGenHidden, w.dn_w2, w.dn_b2, E, e);
-    __syncthreads();
-    gen_min_max_normalize(G.ns, E, tid);
-    __syncthreads();
+    gen_stage_input(G, G.ns, E, A, p.act[(size_t)r * p.L + i], tid);
+    gen_next_state(dn, dr, false, E + A, E, w.F, G, tid);
   }
 }
 

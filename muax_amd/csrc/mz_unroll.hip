@@ -34,18 +34,13 @@ int mzs_mlp_unroll_values(const mzs_mlp_weights* w, const mzs_unroll_args* a, vo
   if (int rc = mzh::select_device(a->device, "mzs_mlp_unroll_values")) return rc;
   mz::UnrollArgs p{};
   mz::MlpGen& g = p.w;
-  g.repr_w = w->repr_w; g.repr_b = w->repr_b;
-  g.pv_w1 = w->pv_w1; g.pv_b1 = w->pv_b1; g.pv_w2 = w->pv_w2; g.pv_b2 = w->pv_b2;
-  g.pp_w1 = w->pp_w1; g.pp_b1 = w->pp_b1; g.pp_w2 = w->pp_w2; g.pp_b2 = w->pp_b2;
-  g.dr_w1 = w->dr_w1; g.dr_b1 = w->dr_b1; g.dr_w2 = w->dr_w2; g.dr_b2 = w->dr_b2;
-  g.dn_w1 = w->dn_w1; g.dn_b1 = w->dn_b1; g.dn_w2 = w->dn_w2; g.dn_b2 = w->dn_b2;
+  mzh::copy_weights(*w, g);
   g.obs_dim = w->obs_dim; g.E = a->embed_dim; g.A = a->num_actions; g.F = 2 * w->support_size + 1;
   g.support = w->support_size; g.pred_on_parent = 0; g.discount = w->discount;
   p.B = a->batch; p.L = a->row_steps; p.kp = a->k_prio;
   p.obs = a->obs; p.act = a->actions; p.Rn = a->returns; p.values = a->values; p.prio = a->prio;
   // the trio's scratch with the observation in the place of [s, onehot]: 2.2 KiB at the widest shape
-  const int ew = g.E > g.obs_dim ? g.E : g.obs_dim;
-  const size_t lds = sizeof(float) * (size_t)mz::gen_scratch_words(ew, g.A);
+  const size_t lds = sizeof(float) * (size_t)mz::gen_scratch_words(mz::gen_obs_width(g.E, g.obs_dim), g.A);
   hipLaunchKernelGGL(mz::mz_mlp_unroll_kernel, dim3(a->batch), dim3(64), lds, static_cast<hipStream_t>(stream_), p);
   MZS_HIP(nullptr, hipGetLastError());
   return MZS_OK;

@@ -1,5 +1,5 @@
 """Tree-step phase timers (s_memtime, -DMZ_PROFILE build: python tools/profile_search.py build) of the generic one-launch
-search of the default trio (mz_mlp_generic.cuh), per simulation.   python tools/profile_generic.py"""
+search of the default trio (mz_mlp_generic.cuh; its net stages: mz_mlp_blocks.cuh), per simulation.   python tools/profile_generic.py"""
 import os, sys, ctypes as C
 import numpy as np, torch
 sys.path.insert(0, '/root/repo')

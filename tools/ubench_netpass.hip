@@ -29,7 +29,7 @@
 
 using namespace mz;
 using Cfg = FusedCfg<2, 8, 2, 51, 1, 4>;  // CartPole shapes (BASELINE configs[1])
-constexpr int A = Cfg::A, E = Cfg::E, F = 21, H = kHidden, SUPPORT = 10;
+constexpr int A = Cfg::A, E = Cfg::E, F = 21, H = kHidden, SUPPORT = 10;  // (kHidden: mz_spec.cuh)
 
 struct Out {
   float reward, value, pil[A], pprob[A], ns[E];

@@ -24,7 +24,7 @@ using namespace mz;
 #define NP_WAVES_PER_SIMD 2
 #endif
 using Cfg = FusedCfg<4, 32, 2, 51, 1, 4, true>;
-constexpr int A = Cfg::A, E = Cfg::E, F = 21, H = kHidden, SUPPORT = 10;
+constexpr int A = Cfg::A, E = Cfg::E, F = 21, H = kHidden, SUPPORT = 10;  // (kHidden: mz_spec.cuh)
 
 struct BenchParams {
   FusedParams fp;
