@@ -33,7 +33,13 @@
 //   * backup is lane-parallel: the discounted-return chain advances all path
 //     entries at once (G[e] = r[e] + g G[e+1] through a row_shl:1 DPP operand),
 //     running means and prior / (visits + 1) divide by small integers with a
-//     correctly rounded reciprocal from an LDS table (Markstein, 3 ops);
+//     correctly rounded reciprocal from an LDS table (Markstein, 3 ops).  A path of up to 15 edges is one pass of its
+//     row.  A deeper one overflows the row: plain-record instances then lay the wave's four paths end to end over the
+//     64 lanes (lane off[q] + e owns entry e of row q, off = the prefix sums of depth + 1; the rows' values are read
+//     with v_readlane and selected per lane, neighbours come through wave_shl:1, a leaf ends its root's segment of the
+//     chain and of the JUMP scan) and back them up in ONE pass when the four entry counts sum to at most 64 -- on the
+//     4096 x 50 CartPole workload 68 % of the wave-simulations with a deep row; the others, and the compact / packed /
+//     LONG instances, take 16-entry chunks, deepest first, with carries between them.  Both mappings run one body;
 //   * the node record has an odd word stride (16 records of a row in 16 banks),
 //     embeddings move to HBM when E > 16 so that 16 roots still fit a CU;
 //   * the MLPs run as row-distributed fma chains: input element i lives in lane
@@ -1316,20 +1322,35 @@ __global__ __launch_bounds__(C::THREADS, (C::PH && !C::LONG) ? 2 : 1) void mz_ac
     {
       // wave-uniform trip counts: the deepest of the wave's four rows
       int wmax;
+      const int dep0 = __builtin_amdgcn_readlane(depth, 0), dep1 = __builtin_amdgcn_readlane(depth, 16);
+      const int dep2 = __builtin_amdgcn_readlane(depth, 32), dep3 = __builtin_amdgcn_readlane(depth, 48);
       {
-        const int d0 = __builtin_amdgcn_readlane(depth, 0), d1 = __builtin_amdgcn_readlane(depth, 16);
-        const int d2 = __builtin_amdgcn_readlane(depth, 32), d3 = __builtin_amdgcn_readlane(depth, 48);
         int m01, m23;  // (scalar max: the compiler otherwise moves two of the four back into VGPRs for a v_max3)
-        asm("s_max_i32 %0, %1, %2" : "=s"(m01) : "s"(d0), "s"(d1) : "scc");
-        asm("s_max_i32 %0, %1, %2" : "=s"(m23) : "s"(d2), "s"(d3) : "scc");
+        asm("s_max_i32 %0, %1, %2" : "=s"(m01) : "s"(dep0), "s"(dep1) : "scc");
+        asm("s_max_i32 %0, %1, %2" : "=s"(m23) : "s"(dep2), "s"(dep3) : "scc");
         asm("s_max_i32 %0, %1, %2" : "=s"(wmax) : "s"(m01), "s"(m23) : "scc");
       }
+      // the wide pass (below): plain-record instances whose rows hold one path word per lane
+      constexpr bool kWideBackup = !C::PH && C::PATHS == 1 && A <= 16;
+      // first lane of rows 1..3 when the wave's four paths lie end to end: the exclusive prefix sums of (depth + 1)
+      const int woff1 = dep0 + 1, woff2 = woff1 + dep1 + 1, woff3 = woff2 + dep2 + 1;
       float G = value;        // leaf_value walking up (row uniform)
       float carry_v = value;  // node value of the entry just below this chunk
       int carry_n = -1;       // node index of the entry just below this chunk
       int carry_j = 0;        // resolved JUMP word of the entry just below this chunk
-      for (int c = wmax >> 4; c >= 0; --c) {
-        const int e = 16 * c + j;
+      // ONE pass of the backup over the entries the lanes own, in two lane mappings:
+      //   ROW  (wide_c false): lane j of a row owns entry e = 16 c + j of that row's path; chunk c of every row at once,
+      //        neighbours through row_shl:1, what crosses a chunk through the carries above;
+      //   WIDE (wide_c true):  the wave's four paths lie end to end over its 64 lanes, lane off[q] + e owns entry e of row
+      //        q; neighbours through wave_shl:1, nothing is carried.
+      // The arguments are the values of the row the lane works for (ROW: the lane's own row, i.e. the variables of the same
+      // names; WIDE: picked per lane); `psrc` / `srcrow` name the register and the first lane of the row that hold the
+      // parent's path words.
+      auto backup_pass = [&](auto wide_c, const int c, float* const tree, const int e, const int depth, const int parent,
+                             const int action, const int newn, const float value, const uint32_t inv_bits,
+                             const int cv_next, const int psrc, const int srcrow) {
+        constexpr bool WIDE = decltype(wide_c)::value;
+        int* const itree = reinterpret_cast<int*>(tree);
         const bool valid = e <= depth;
         const bool isleaf = e == depth;
         const bool edge = e < depth;
@@ -1339,16 +1360,7 @@ __global__ __launch_bounds__(C::THREADS, (C::PH && !C::LONG) ? 2 : 1) void mz_ac
           // word (ec * ENTRY_BITS) / 32 of the parent's path sits in that lane (and slot) of this row's ppw, loaded
           // before the network pass: a cross-lane fetch, not a second LDS read behind the expansion's stores
           const int widx = (ec * C::ENTRY_BITS) >> 5;
-          // the entries of chunk c lie in ONE of the row's path registers (16 entries are 4 or 8 words; a register slot is
-          // 16 words): picked with a wave-uniform select, then ONE cross-lane fetch -- round 5: a fetch per slot and a
-          // per-lane select cost a 255-simulation instance (eight slots) 1700 cycles per simulation in this phase.  (The
-          // lanes at and past the leaf, whose clamped entry 0 sits in slot 0, fetch a word they never use: their (pn, pa)
-          // are overridden below.)
-          const int slot_c = ((16 * c * C::ENTRY_BITS) >> 5) >> 4;
-          int psrc = ppw[0];
-#pragma unroll
-          for (int t = 1; t < C::PATHS; ++t) psrc = (slot_c == t) ? ppw[t] : psrc;
-          const int pword = __builtin_amdgcn_ds_bpermute(4 * ((lane & ~15) + (widx & 15)), psrc);
+          const int pword = __builtin_amdgcn_ds_bpermute(4 * (srcrow + (widx & 15)), psrc);
           const int ent = (pword >> ((ec * C::ENTRY_BITS) & 31)) & ((1 << C::ENTRY_BITS) - 1);
           pn = ent & ((1 << C::ENTRY_ACT_SHIFT) - 1);
           pa = ent >> C::ENTRY_ACT_SHIFT;
@@ -1395,20 +1407,34 @@ __global__ __launch_bounds__(C::THREADS, (C::PH && !C::LONG) ? 2 : 1) void mz_ac
 #pragma unroll
         for (int a = 1; a < A; ++a) re = (pa == a) ? rew[a] : re;
         re = edge ? re : 0.0f;  // identity step for the leaf entry and for idle lanes
-        const float ge = edge ? p.discount : 1.0f;
+        float ge = edge ? p.discount : 1.0f;
+        if constexpr (WIDE) {
+          // the lane behind a leaf belongs to the next root: a leaf is a segment end that restates its own value
+          // (0 * G[next root's entry 0] + value), so nothing crosses from one root into the next
+          re = isleaf ? value : re;
+          ge = isleaf ? 0.0f : ge;
+        }
         // leaf_value = reward + discount * leaf_value, deepest entry first.  Every lane keeps its OWN
         // entry's value: one step is G[e] = re[e] + ge[e] * G[e + 1] on all lanes at once (row_shl:1;
         // lane 15 keeps the product with the value carried in from the chunk below), so entry e is final
         // after (deepest entry - e + 1) steps and stays put afterwards; identity lanes hold the carry.
         // Steps above the wave's deepest entry are identities for every row and are jumped over.
-        const int kstart = min(15, wmax - 16 * c);
+        // WIDE: the same step over the whole wave (wave_shl:1; lane 63, a leaf or idle, keeps its product), every lane
+        // starting from its row's leaf value; a row's entries are final after (its depth + 1) <= wmax + 1 steps, and
+        // further steps restate them
+        if constexpr (WIDE) G = value;
         float Gt = ge * G;
-#define MZ_GSTEP_TXT "s_nop 1\n\tv_mul_f32_dpp %0, %1, %2 row_shl:1 row_mask:0xf bank_mask:0xf\n\tv_add_f32 %1, %0, %3\n\t"
-#define MZ_GSTEP4 \
-  asm volatile(MZ_GSTEP_TXT MZ_GSTEP_TXT MZ_GSTEP_TXT MZ_GSTEP_TXT : "+v"(Gt), "+v"(G) : "v"(ge), "v"(re));
-        if (kstart >= 12) { MZ_GSTEP4 }
-        if (kstart >= 8) { MZ_GSTEP4 }
-        if (kstart >= 4) { MZ_GSTEP4 }
+#define MZ_GSTEP_TXT(SHL) "s_nop 1\n\tv_mul_f32_dpp %0, %1, %2 " SHL " row_mask:0xf bank_mask:0xf\n\tv_add_f32 %1, %0, %3\n\t"
+#define MZ_GSTEP4(SHL) \
+  asm volatile(MZ_GSTEP_TXT(SHL) MZ_GSTEP_TXT(SHL) MZ_GSTEP_TXT(SHL) MZ_GSTEP_TXT(SHL) : "+v"(Gt), "+v"(G) : "v"(ge), "v"(re));
+        if constexpr (WIDE) {
+          for (int k = wmax >> 2; k > 0; --k) { MZ_GSTEP4("wave_shl:1") }
+        } else {
+          const int kstart = min(15, wmax - 16 * c);
+          if (kstart >= 12) { MZ_GSTEP4("row_shl:1") }
+          if (kstart >= 8) { MZ_GSTEP4("row_shl:1") }
+          if (kstart >= 4) { MZ_GSTEP4("row_shl:1") }
+        }
         float sc[A];
         // the last four steps always run.  Two actions, MuZero policy: the policy scores div_small(tn prob[a], vis[a] + 1,
         // rcp1[a]) -- twelve instructions that need nothing from the chain -- take the place of the steps' wait states
@@ -1417,34 +1443,40 @@ __global__ __launch_bounds__(C::THREADS, (C::PH && !C::LONG) ? 2 : 1) void mz_ac
         constexpr bool kFill = !C::GUMBEL && A == 2;
         if constexpr (kFill) {
           float d0, d1, x0, x1, q0, q1, r0, r1;
-#define MZ_GSTEP_BODY "v_mul_f32_dpp %[Gt], %[G], %[ge] row_shl:1 row_mask:0xf bank_mask:0xf\n\tv_add_f32 %[G], %[Gt], %[re]\n\t"
-          asm volatile(
-              "v_add_u32 %[d0], 1, %[v0]\n\tv_add_u32 %[d1], 1, %[v1]\n\tv_mul_f32 %[x0], %[tn], %[p0]\n\t" MZ_GSTEP_BODY
-              "v_cvt_f32_i32 %[d0], %[d0]\n\tv_cvt_f32_i32 %[d1], %[d1]\n\tv_mul_f32 %[x1], %[tn], %[p1]\n\t" MZ_GSTEP_BODY
-              "v_mul_f32 %[q0], %[x0], %[y0]\n\tv_mul_f32 %[q1], %[x1], %[y1]\n\tv_fma_f32 %[r0], -%[q0], %[d0], %[x0]\n\t" MZ_GSTEP_BODY
-              "v_fma_f32 %[r1], -%[q1], %[d1], %[x1]\n\tv_fma_f32 %[s0], %[r0], %[y0], %[q0]\n\tv_fma_f32 %[s1], %[r1], %[y1], %[q1]\n\t"
-              MZ_GSTEP_BODY
-              : [Gt] "+v"(Gt), [G] "+v"(G), [d0] "=&v"(d0), [d1] "=&v"(d1), [x0] "=&v"(x0), [x1] "=&v"(x1), [q0] "=&v"(q0),
-                [q1] "=&v"(q1), [r0] "=&v"(r0), [r1] "=&v"(r1), [s0] "=&v"(sc[0]), [s1] "=&v"(sc[A - 1])
-              : [ge] "v"(ge), [re] "v"(re), [tn] "v"(tn_rc.x), [p0] "v"(prob[0]), [p1] "v"(prob[A - 1]), [v0] "v"(vis[0]),
-                [v1] "v"(vis[A - 1]), [y0] "v"(rcp1[0]), [y1] "v"(rcp1[A - 1]));
+#define MZ_GSTEP_BODY(SHL) "v_mul_f32_dpp %[Gt], %[G], %[ge] " SHL " row_mask:0xf bank_mask:0xf\n\tv_add_f32 %[G], %[Gt], %[re]\n\t"
+#define MZ_GFILL4(SHL)                                                                                                            \
+  asm volatile(                                                                                                                   \
+      "v_add_u32 %[d0], 1, %[v0]\n\tv_add_u32 %[d1], 1, %[v1]\n\tv_mul_f32 %[x0], %[tn], %[p0]\n\t" MZ_GSTEP_BODY(SHL)              \
+      "v_cvt_f32_i32 %[d0], %[d0]\n\tv_cvt_f32_i32 %[d1], %[d1]\n\tv_mul_f32 %[x1], %[tn], %[p1]\n\t" MZ_GSTEP_BODY(SHL)            \
+      "v_mul_f32 %[q0], %[x0], %[y0]\n\tv_mul_f32 %[q1], %[x1], %[y1]\n\tv_fma_f32 %[r0], -%[q0], %[d0], %[x0]\n\t" MZ_GSTEP_BODY(SHL) \
+      "v_fma_f32 %[r1], -%[q1], %[d1], %[x1]\n\tv_fma_f32 %[s0], %[r0], %[y0], %[q0]\n\tv_fma_f32 %[s1], %[r1], %[y1], %[q1]\n\t"   \
+      MZ_GSTEP_BODY(SHL)                                                                                                          \
+      : [Gt] "+v"(Gt), [G] "+v"(G), [d0] "=&v"(d0), [d1] "=&v"(d1), [x0] "=&v"(x0), [x1] "=&v"(x1), [q0] "=&v"(q0),               \
+        [q1] "=&v"(q1), [r0] "=&v"(r0), [r1] "=&v"(r1), [s0] "=&v"(sc[0]), [s1] "=&v"(sc[A - 1])                                  \
+      : [ge] "v"(ge), [re] "v"(re), [tn] "v"(tn_rc.x), [p0] "v"(prob[0]), [p1] "v"(prob[A - 1]), [v0] "v"(vis[0]),                \
+        [v1] "v"(vis[A - 1]), [y0] "v"(rcp1[0]), [y1] "v"(rcp1[A - 1]));
+          if constexpr (WIDE) { MZ_GFILL4("wave_shl:1") } else { MZ_GFILL4("row_shl:1") }
+#undef MZ_GFILL4
 #undef MZ_GSTEP_BODY
         } else {
-          MZ_GSTEP4
+          if constexpr (WIDE) { MZ_GSTEP4("wave_shl:1") } else { MZ_GSTEP4("row_shl:1") }
         }
 #undef MZ_GSTEP4
 #undef MZ_GSTEP_TXT
         const float Gown = G;
-        G = bcast<0>(G);  // carried into the chunk above
+        if constexpr (!WIDE) G = bcast<0>(G);  // carried into the chunk above
         MZ_TICKW(8);  // G chain
         const float newv = div_small(pv * (float)cnt + Gown, (float)cnt + 1.0f, tn_rc.y);
         // children_values[parent, action] = node_values[child]: the child is the next entry
+        // (WIDE: the next entry is the next lane of the wave; the lane below a row's last edge is its leaf, covered by
+        // the selects on e == depth - 1 and isleaf, and nothing is carried)
+        constexpr int kShl1 = WIDE ? 0x130 /* wave_shl:1 */ : 0x101 /* row_shl:1 */;
         float childv = __int_as_float(__builtin_amdgcn_update_dpp(
-            __float_as_int(carry_v), __float_as_int(newv), 0x101 /* row_shl:1 */, 0xf, 0xf, false));
+            __float_as_int(carry_v), __float_as_int(newv), kShl1, 0xf, 0xf, false));
         childv = (e == depth - 1) ? value : childv;
-        carry_v = bcast<0>(newv);
-        const int next_pn = __builtin_amdgcn_update_dpp(carry_n, pn, 0x101, 0xf, 0xf, false);
-        carry_n = bcast_i<0>(pn);
+        if constexpr (!WIDE) carry_v = bcast<0>(newv);
+        const int next_pn = __builtin_amdgcn_update_dpp(carry_n, pn, kShl1, 0xf, 0xf, false);
+        if constexpr (!WIDE) carry_n = bcast_i<0>(pn);
 #pragma unroll
         for (int a = 0; a < A; ++a) val[a] = (edge && pa == a) ? childv : val[a];
         const float nval = edge ? newv : pv;
@@ -1489,8 +1521,24 @@ __global__ __launch_bounds__(C::THREADS, (C::PH && !C::LONG) ? 2 : 1) void mz_ac
   }
         MZ_JSCAN(1) MZ_JSCAN(2) MZ_JSCAN(4) MZ_JSCAN(8)
 #undef MZ_JSCAN
-        jwd = (jwd & done) | (carry_j & ~done);
-        carry_j = bcast_i<0>(jwd);
+        if constexpr (!WIDE) {
+          jwd = (jwd & done) | (carry_j & ~done);
+          carry_j = bcast_i<0>(jwd);
+        } else {
+          // the scan ran inside each DPP row of 16 lanes.  A lane still open inherits through the end of its DPP row: the
+          // resolved word of lane 0 of the next one, last DPP row first (lane 63, a leaf or idle, is never open, and a
+          // leaf closes every chain of its root, so no chain crosses into the next root)
+          const int drow = lane >> 4;
+#pragma unroll
+          for (int q = 2; q >= 0; --q) {
+            const int cj = __builtin_amdgcn_readlane(jwd, 16 * (q + 1));
+            jwd = (drow == q && done == 0) ? cj : jwd;
+          }
+          // the root's refreshed word: entry 0 of each row, handed to the lanes of that row
+          const int w0 = __builtin_amdgcn_readlane(jwd, 0), w1 = __builtin_amdgcn_readlane(jwd, woff1);
+          const int w2 = __builtin_amdgcn_readlane(jwd, woff2), w3 = __builtin_amdgcn_readlane(jwd, woff3);
+          carry_j = drow == 0 ? w0 : drow == 1 ? w1 : drow == 2 ? w2 : w3;
+        }
         MZ_TICKW(11);  // decide + JUMP scan
         if (valid) {
           // one masked region; for the leaf entry the header / edge stores rewrite what was loaded
@@ -1508,6 +1556,50 @@ __global__ __launch_bounds__(C::THREADS, (C::PH && !C::LONG) ? 2 : 1) void mz_ac
           }
           nd[C::off_val(pa)] = cvn;
           C::store_vis(ndi, pa, cin);
+        }
+      };
+      // A path of more than 15 edges overflows its row.  When the wave's four paths still fit its 64 lanes (on the
+      // 4096 x 50 CartPole workload 68 % of the wave-simulations with such a row), ONE wide pass does the work of the
+      // two chunk passes; a wave with no such row, or with more than 64 entries, takes the chunk loop.
+      bool wide = false;
+      if constexpr (kWideBackup) wide = wmax >= 16 && woff3 + dep3 + 1 <= 64;
+      if (wide) {
+        if constexpr (kWideBackup) {
+          // the lane's (row q, entry e): q counts the segment starts at or below the lane (idle lanes land behind row
+          // 3's leaf); the rows' values are read once with v_readlane and selected by q
+          const bool q1 = lane >= woff1, q2 = lane >= woff2, q3 = lane >= woff3;
+          auto sel = [&](int x0, int x1, int x2, int x3) {
+            int x = q1 ? x1 : x0;
+            x = q2 ? x2 : x;
+            return q3 ? x3 : x;
+          };
+          auto pick = [&](int x) {
+            return sel(__builtin_amdgcn_readlane(x, 0), __builtin_amdgcn_readlane(x, 16), __builtin_amdgcn_readlane(x, 32),
+                       __builtin_amdgcn_readlane(x, 48));
+          };
+          // (parent, action, depth, newn) travel as one word: 12 + 4 + 8 + 8 bits, the fields of a JUMP word and a node
+          const unsigned pk = (unsigned)pick((int)((unsigned)parent | ((unsigned)action << 12) | ((unsigned)depth << 16) | ((unsigned)newn << 24)));
+          const int q16 = sel(0, 16, 32, 48);
+          float* const wtree = tree - (lane >> 4) * C::ROOT_WORDS + sel(0, C::ROOT_WORDS, 2 * C::ROOT_WORDS, 3 * C::ROOT_WORDS);
+          int cvn = 0;
+          if constexpr (C::GUMBEL) cvn = pick(cv_next);
+          backup_pass(std::true_type{}, 0, wtree, lane - sel(0, woff1, woff2, woff3), (int)((pk >> 16) & 0xffu),
+                      (int)(pk & 0xfffu), (int)((pk >> 12) & 0xfu), (int)(pk >> 24), __int_as_float(pick(__float_as_int(value))),
+                      (uint32_t)pick((int)inv_bits), cvn, ppw[0], q16);
+        }
+      } else {
+        for (int c = wmax >> 4; c >= 0; --c) {
+          // the entries of chunk c lie in ONE of the row's path registers (16 entries are 4 or 8 words; a register slot is
+          // 16 words): picked with a wave-uniform select, then ONE cross-lane fetch -- round 5: a fetch per slot and a
+          // per-lane select cost a 255-simulation instance (eight slots) 1700 cycles per simulation in this phase.  (The
+          // lanes at and past the leaf, whose clamped entry 0 sits in slot 0, fetch a word they never use: their (pn, pa)
+          // are overridden in the pass.)
+          const int slot_c = ((16 * c * C::ENTRY_BITS) >> 5) >> 4;
+          int psrc = ppw[0];
+#pragma unroll
+          for (int t = 1; t < C::PATHS; ++t) psrc = (slot_c == t) ? ppw[t] : psrc;
+          backup_pass(std::false_type{}, c, tree, 16 * c + j, depth, parent, action, newn, value, inv_bits, cv_next, psrc,
+                      lane & ~15);
         }
       }
       root_jw = carry_j;  // entry 0 is the root: its refreshed JUMP word

@@ -45,3 +45,14 @@ wm = (dep-1).reshape(S-1,B//4,4).max(2)
 print("P(second pass: deepest row of the wave >= 16 levels) = %.3f ; mean passes %.3f" % ((wm>=16).mean(), 1+(wm>=16).mean()))
 rowdeep=(dep-1>=16)
 print("P(a single row >= 16 levels) = %.3f ; all four rows of a wave: %.4f" % (rowdeep.mean(), rowdeep.reshape(S-1,B//4,4).all(2).mean()))
+# packing the wave's four paths end to end over its 64 lanes (profiles/deep_backup_packed.txt): a wave-simulation whose
+# deepest row has >= 16 edges needs no second pass when its four entry counts (depth + 1) sum to at most 64
+tot = dep.reshape(S-1,B//4,4).sum(2)
+deep = wm >= 16
+print("deep wave-simulations (deepest row >= 16 edges): %d of %d; of them sum(depth + 1) <= 64: %d = %.1f%%" % (deep.sum(), deep.size, (deep & (tot<=64)).sum(), 100.0*(deep & (tot<=64)).sum()/max(1,deep.sum())))
+print("deepest row >= 32 edges (three passes today): %d" % (wm>=32).sum())
+edges = [0,17,25,33,41,49,57,65,73,81,97,1000]
+h_all = np.histogram(tot, edges)[0]; h_deep = np.histogram(tot[deep], edges)[0]
+print("histogram of sum(depth + 1) per wave-simulation: bin, all, deep")
+for i in range(len(edges)-1):
+    print("  %4d..%-4d %8d %8d" % (edges[i], edges[i+1]-1, h_all[i], h_deep[i]))
