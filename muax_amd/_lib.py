@@ -26,10 +26,13 @@ class MzsConfig(C.Structure):
                 ("afterstate_embed_dim", C.c_int32), ("reserved0", C.c_int32)]
 
 
+# the eight arrays of mzs_stochastic_outputs, in the struct's order: the decision function's three, the chance function's five
+STOCHASTIC_OUTPUT_FIELDS = ("chance_logits", "afterstate_value", "afterstate_embedding", "action_logits", "value", "reward",
+                            "discount", "state_embedding")
+
+
 class MzsStochasticOutputs(C.Structure):
-    _fields_ = [("struct_size", C.c_int32), ("reserved0", C.c_int32), ("chance_logits", _vp), ("afterstate_value", _vp),
-                ("afterstate_embedding", _vp), ("action_logits", _vp), ("value", _vp), ("reward", _vp),
-                ("discount", _vp), ("state_embedding", _vp)]
+    _fields_ = [("struct_size", C.c_int32), ("reserved0", C.c_int32)] + [(n, _vp) for n in STOCHASTIC_OUTPUT_FIELDS]
 
 
 # the seven Linear(16)-elu-Linear stacks of mzs_stochastic_mlp_weights, in the struct's order
@@ -280,30 +283,147 @@ def args(cls, **fields):
     return a
 
 
-EXPORTED_SYMBOLS = ["mzs_abi_version", "mzs_last_error", "mzs_create", "mzs_destroy",
-                    "mzs_mlp_set_weights", "mzs_act_mlp", "mzs_root", "mzs_root_gumbel", "mzs_select",
-                    "mzs_expand_backup", "mzs_expand_backup_select",
-                    "mzs_finish", "mzs_tree_export", "mzs_mlp_loss_grad", "mzs_mlp_num_params",
-                    "mzs_mlp_train_workspace_bytes", "mzs_resnet_tower", "mzs_tower_pair_scratch_bytes",
-                    "mzs_dirichlet", "mzs_act_mlp_host", "mzs_selftest", "mzs_layernorm_act",
-                    "mzs_layernorm_workspace_bytes", "mzs_ez_recurrent", "mzs_resnet_search",
-                    "mzs_register_fused_dispatch", "mzs_register_fused_dispatch_muzero", "mzs_fused_jit_abi", "mzs_mlp_allow_generic", "mzs_conv3x3_nhwc",
-                    "mzs_resblock_v1", "mzs_resblock_workspace_bytes", "mzs_conv3x3_stride2_nhwc", "mzs_resnet_root_tail",
-                    "mzs_resblock_v2", "mzs_resblock_v2_workspace_bytes", "mzs_register_train_dispatch", "mzs_train_jit_abi",
-                    "mzs_mlp_allow_wide", "mzs_mlp_wide_plan",
-                    "mzs_mlp_allow_wide_gumbel", "mzs_mlp_wide_plan_policy",
-                    "mzs_replay_store", "mzs_replay_refresh", "mzs_replay_sample",
-                    "mzs_replay_gather_obs", "mzs_replay_reanalyse", "mzs_replay_update_priorities",
-                    "mzs_mlp_unroll_values", "mzs_replay_sample_is", "mzs_mlp_loss_grad_weighted",
-                    "mzs_replay_stage", "mzs_replay_store_steps", "mzs_replay_plan_steps",
-                    "mzs_env_cartpole_reset", "mzs_env_cartpole_step",
-                    "mzs_env_classic_reset", "mzs_env_classic_step",
-                    "mzs_env_2048_reset", "mzs_env_2048_step", "mzs_env_2048_mask",
-                    "mzs_root_stochastic", "mzs_select_stochastic", "mzs_expand_backup_stochastic",
-                    "mzs_finish_stochastic", "mzs_mlp_set_stochastic_weights", "mzs_mlp_stochastic_recurrent",
-                    "mzs_mlp_stochastic_plan", "mzs_mlp_stochastic_search", "mzs_stochastic_search_block",
-                    "mzs_stochastic_mlp_loss_grad", "mzs_stochastic_mlp_num_params",
-                    "mzs_stochastic_mlp_train_workspace_bytes"]
+# The two tables below ARE the binding: every `typedef struct` and every function of include/mzsearch.h, in the header's
+# order.  tests/test_abi_cpu.py compares both with the header, and every struct's layout with the host compiler's.
+STRUCTS = {
+    "mzs_config": MzsConfig,
+    "mzs_mlp_weights": MzsMlpWeights,
+    "mzs_tree_view": MzsTreeView,
+    "mzs_act_args": MzsActArgs,
+    "mzs_act_host_args": MzsActHostArgs,
+    "mzs_stochastic_outputs": MzsStochasticOutputs,
+    "mzs_stochastic_mlp_weights": MzsStochasticMlpWeights,
+    "mzs_stochastic_search_args": MzsStochasticSearchArgs,
+    "mzs_ez_head": MzsEzHead,
+    "mzs_ez_args": MzsEzArgs,
+    "mzs_layernorm_args": MzsLayerNormArgs,
+    "mzs_train_args": MzsTrainArgs,
+    "mzs_stochastic_train_weights": MzsStochasticTrainWeights,
+    "mzs_stochastic_train_args": MzsStochasticTrainArgs,
+    "mzs_tower_args": MzsTowerArgs,
+    "mzs_root_tail_args": MzsRootTailArgs,
+    "mzs_conv3x3_args": MzsConv3x3Args,
+    "mzs_conv3x3s_args": MzsConv3x3sArgs,
+    "mzs_resblock_args": MzsResblockArgs,
+    "mzs_replay_arena": MzsReplayArena,
+    "mzs_replay_store_args": MzsReplayStoreArgs,
+    "mzs_replay_sample_args": MzsReplaySampleArgs,
+    "mzs_replay_is_args": MzsReplayIsArgs,
+    "mzs_replay_gather_args": MzsReplayGatherArgs,
+    "mzs_replay_reanalyse_args": MzsReplayReanalyseArgs,
+    "mzs_replay_update_args": MzsReplayUpdateArgs,
+    "mzs_replay_ring": MzsReplayRing,
+    "mzs_replay_stage_args": MzsReplayStageArgs,
+    "mzs_replay_store_steps_args": MzsReplayStoreStepsArgs,
+    "mzs_replay_plan_args": MzsReplayPlanArgs,
+    "mzs_env_cartpole": MzsEnvCartPole,
+    "mzs_env_step_args": MzsEnvStepArgs,
+    "mzs_env_classic": MzsEnvClassic,
+    "mzs_env_2048": MzsEnv2048,
+    "mzs_unroll_args": MzsUnrollArgs,
+}
+
+_P, _i32, _i64, _f32 = C.POINTER, C.c_int32, C.c_int64, C.c_float
+_key, _plan = _P(C.c_uint32 * 2), _P(C.c_int32 * 4)  # `const uint32_t key[2]` (host values), `int32_t out[4]`
+_arena, _ring, _step = _P(MzsReplayArena), _P(MzsReplayRing), _P(MzsEnvStepArgs)
+
+# name -> (restype, argtypes)
+ENTRIES = {
+    "mzs_abi_version": (C.c_int, []),
+    "mzs_last_error": (C.c_char_p, [_vp]),
+    "mzs_create": (C.c_int, [_P(MzsConfig), _P(_vp)]),
+    "mzs_destroy": (C.c_int, [_vp]),
+    # fused path: whole act() for the default MLP trio in one launch
+    "mzs_mlp_set_weights": (C.c_int, [_vp, _P(MzsMlpWeights)]),
+    "mzs_act_mlp": (C.c_int, [_vp, _P(MzsActArgs), _vp]),
+    # the same from HOST memory
+    "mzs_act_mlp_host": (C.c_int, [_vp, _P(MzsActHostArgs), _vp]),
+    # step-wise path: any repr/pred/dyn plugin nets run by the caller
+    "mzs_root": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _key, _vp]),
+    "mzs_root_gumbel": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _key, _vp]),
+    "mzs_select": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    "mzs_expand_backup": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mzs_expand_backup_select": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mzs_finish": (C.c_int, [_vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mzs_tree_export": (C.c_int, [_vp, _P(MzsTreeView), _vp]),
+    # step-wise path, stochastic policy
+    "mzs_root_stochastic": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _key, _vp]),
+    "mzs_select_stochastic": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "mzs_expand_backup_stochastic": (C.c_int, [_vp, _i32, _P(MzsStochasticOutputs), _vp]),
+    "mzs_finish_stochastic": (C.c_int, [_vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the default stochastic MLP family evaluated by the library
+    "mzs_mlp_set_stochastic_weights": (C.c_int, [_vp, _P(MzsStochasticMlpWeights)]),
+    "mzs_mlp_stochastic_recurrent": (C.c_int, [_vp, _vp, _vp, _vp, _P(MzsStochasticOutputs), _vp]),
+    # the WHOLE stochastic search of the bound family in ONE launch
+    "mzs_mlp_stochastic_plan": (C.c_int, [_i32] * 5 + [_plan]),
+    "mzs_mlp_stochastic_search": (C.c_int, [_vp, _P(MzsStochasticSearchArgs), _vp]),
+    "mzs_stochastic_search_block": (C.c_int, [_key, _i32, _f32, _f32, _vp]),
+    # recurrent_fn of the EfficientZero-style nets
+    "mzs_ez_recurrent": (C.c_int, [_P(MzsEzArgs), _vp]),
+    # fused LayerNorm of the convolutional plugin nets
+    "mzs_layernorm_act": (C.c_int, [_P(MzsLayerNormArgs), _vp]),
+    "mzs_layernorm_workspace_bytes": (_i64, [_i32, _i32]),
+    # device self-test
+    "mzs_selftest": (C.c_int, [_i32, _P(_i64 * 4)]),
+    # root exploration noise
+    "mzs_dirichlet": (C.c_int, [_i32, _key, _f32, _i32, _i32, _i64, _i64, _vp, _vp]),
+    # training step of the default MLP trio
+    "mzs_mlp_num_params": (_i64, [_i32] * 4),
+    "mzs_mlp_train_workspace_bytes": (_i64, [_i32] * 5),
+    "mzs_mlp_loss_grad": (C.c_int, [_P(MzsMlpWeights), _P(MzsTrainArgs), _vp]),
+    "mzs_mlp_loss_grad_weighted": (C.c_int, [_P(MzsMlpWeights), _P(MzsTrainArgs), _vp, _vp]),
+    # training step of the default stochastic MLP family
+    "mzs_stochastic_mlp_num_params": (_i64, [_i32] * 5),
+    "mzs_stochastic_mlp_train_workspace_bytes": (_i64, [_i32] * 6),
+    "mzs_stochastic_mlp_loss_grad": (C.c_int, [_P(MzsStochasticTrainWeights), _P(MzsStochasticTrainArgs), _vp]),
+    # next-state tower of the ResNet dynamics net, and the tail of root inference with those nets
+    "mzs_resnet_tower": (C.c_int, [_P(MzsTowerArgs), _vp]),
+    "mzs_tower_pair_scratch_bytes": (_i64, [_i32]),
+    "mzs_resnet_root_tail": (C.c_int, [_P(MzsRootTailArgs), _vp]),
+    # 3x3 convolutions, stems and whole residual blocks of the representation nets
+    "mzs_conv3x3_nhwc": (C.c_int, [_P(MzsConv3x3Args), _vp]),
+    "mzs_conv3x3_stride2_nhwc": (C.c_int, [_P(MzsConv3x3sArgs), _vp]),
+    "mzs_resblock_v1": (C.c_int, [_P(MzsResblockArgs), _vp]),
+    "mzs_resblock_workspace_bytes": (_i64, [_i32] * 4),
+    "mzs_resblock_v2": (C.c_int, [_P(MzsResblockArgs), _vp]),
+    "mzs_resblock_v2_workspace_bytes": (_i64, [_i32] * 4),
+    # fused-kernel instances built on demand, and the routes for shapes without one
+    "mzs_register_fused_dispatch": (C.c_int, [_vp, _i32]),
+    "mzs_register_fused_dispatch_muzero": (C.c_int, [_vp, _i32]),
+    "mzs_fused_jit_abi": (C.c_int, []),
+    "mzs_register_train_dispatch": (C.c_int, [_vp, _i32, _i32, _i32, _i32]),
+    "mzs_train_jit_abi": (C.c_int, []),
+    "mzs_mlp_allow_generic": (C.c_int, [_vp, _i32]),
+    "mzs_mlp_allow_wide": (C.c_int, [_vp, _i32]),
+    "mzs_mlp_allow_wide_gumbel": (C.c_int, [_vp, _i32]),
+    "mzs_mlp_wide_plan": (C.c_int, [_i32] * 4 + [_plan]),
+    "mzs_mlp_wide_plan_policy": (C.c_int, [_i32] * 5 + [_plan]),
+    # the simulation loop of a search with the ResNet nets in ONE launch
+    "mzs_resnet_search": (C.c_int, [_vp, _P(MzsTowerArgs), _f32, _i32, _i32, _vp]),
+    # device-resident trajectory replay
+    "mzs_replay_store": (C.c_int, [_arena, _P(MzsReplayStoreArgs), _vp]),
+    "mzs_replay_refresh": (C.c_int, [_arena, _i32, _i32, _i32, _vp]),
+    "mzs_replay_sample": (C.c_int, [_arena, _P(MzsReplaySampleArgs), _vp]),
+    "mzs_replay_sample_is": (C.c_int, [_arena, _P(MzsReplaySampleArgs), _P(MzsReplayIsArgs), _vp]),
+    "mzs_replay_gather_obs": (C.c_int, [_arena, _P(MzsReplayGatherArgs), _vp]),
+    "mzs_replay_reanalyse": (C.c_int, [_arena, _P(MzsReplayReanalyseArgs), _vp]),
+    "mzs_replay_update_priorities": (C.c_int, [_arena, _P(MzsReplayUpdateArgs), _vp]),
+    # collection on the device: steps staged in a ring, episodes cut in the store launch
+    "mzs_replay_stage": (C.c_int, [_ring, _P(MzsReplayStageArgs), _vp]),
+    "mzs_replay_store_steps": (C.c_int, [_arena, _ring, _P(MzsReplayStoreStepsArgs), _vp]),
+    "mzs_replay_plan_steps": (C.c_int, [_ring, _P(MzsReplayPlanArgs), _vp]),
+    # vector environments stepped on the device: the cart-pole; Acrobot and MountainCar; 2048
+    "mzs_env_cartpole_reset": (C.c_int, [_P(MzsEnvCartPole), _vp, _vp]),
+    "mzs_env_cartpole_step": (C.c_int, [_P(MzsEnvCartPole), _step, _vp]),
+    "mzs_env_classic_reset": (C.c_int, [_P(MzsEnvClassic), _vp, _vp]),
+    "mzs_env_classic_step": (C.c_int, [_P(MzsEnvClassic), _step, _vp]),
+    "mzs_env_2048_reset": (C.c_int, [_P(MzsEnv2048), _vp, _vp]),
+    "mzs_env_2048_step": (C.c_int, [_P(MzsEnv2048), _step, _vp]),
+    "mzs_env_2048_mask": (C.c_int, [_i32, _vp, _vp, _i32, _vp]),
+    # forward value unroll of the default MLP trio
+    "mzs_mlp_unroll_values": (C.c_int, [_P(MzsMlpWeights), _P(MzsUnrollArgs), _vp]),
+}
+EXPORTED_SYMBOLS = list(ENTRIES)
 
 _lib = None
 
@@ -320,91 +440,9 @@ def load(build_if_missing: bool = True):
             raise RuntimeError(f"{path} is missing: build it with `python -m muax_amd._build`")
         _build.build()
     L = C.CDLL(path)
-    L.mzs_abi_version.restype = C.c_int
-    L.mzs_last_error.restype = C.c_char_p
-    L.mzs_last_error.argtypes = [_vp]
-    L.mzs_create.argtypes = [C.POINTER(MzsConfig), C.POINTER(_vp)]
-    L.mzs_destroy.argtypes = [_vp]
-    L.mzs_mlp_set_weights.argtypes = [_vp, C.POINTER(MzsMlpWeights)]
-    L.mzs_act_mlp.argtypes = [_vp, C.POINTER(MzsActArgs), _vp]
-    L.mzs_act_mlp_host.argtypes = [_vp, C.POINTER(MzsActHostArgs), _vp]
-    L.mzs_selftest.argtypes = [C.c_int32, C.POINTER(C.c_int64 * 4)]
-    L.mzs_root.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.POINTER(C.c_uint32 * 2), _vp]
-    L.mzs_root_gumbel.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint32 * 2), _vp]
-    L.mzs_select.argtypes = [_vp, C.c_int32, _vp, _vp, _vp]
-    L.mzs_expand_backup.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.mzs_expand_backup_select.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.mzs_finish.argtypes = [_vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.mzs_tree_export.argtypes = [_vp, C.POINTER(MzsTreeView), _vp]
-    L.mzs_root_stochastic.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.POINTER(C.c_uint32 * 2), _vp]
-    L.mzs_select_stochastic.argtypes = [_vp, C.c_int32, _vp, _vp, _vp, _vp]
-    L.mzs_expand_backup_stochastic.argtypes = [_vp, C.c_int32, C.POINTER(MzsStochasticOutputs), _vp]
-    L.mzs_finish_stochastic.argtypes = [_vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]
-    L.mzs_mlp_set_stochastic_weights.argtypes = [_vp, C.POINTER(MzsStochasticMlpWeights)]
-    L.mzs_mlp_stochastic_recurrent.argtypes = [_vp, _vp, _vp, _vp, C.POINTER(MzsStochasticOutputs), _vp]
-    L.mzs_mlp_stochastic_plan.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_int32 * 4)]
-    L.mzs_mlp_stochastic_search.argtypes = [_vp, C.POINTER(MzsStochasticSearchArgs), _vp]
-    L.mzs_stochastic_search_block.argtypes = [C.POINTER(C.c_uint32 * 2), C.c_int32, C.c_float, C.c_float, _vp]
-    L.mzs_mlp_loss_grad.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsTrainArgs), _vp]
-    L.mzs_resnet_tower.argtypes = [C.POINTER(MzsTowerArgs), _vp]
-    L.mzs_register_fused_dispatch.argtypes = [_vp, C.c_int32]
-    L.mzs_register_fused_dispatch_muzero.argtypes = [_vp, C.c_int32]
-    L.mzs_register_train_dispatch.argtypes = [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    L.mzs_mlp_allow_generic.argtypes = [_vp, C.c_int32]
-    L.mzs_mlp_allow_wide.argtypes = [_vp, C.c_int32]
-    L.mzs_mlp_wide_plan.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_int32 * 4)]
-    L.mzs_mlp_allow_wide_gumbel.argtypes = [_vp, C.c_int32]
-    L.mzs_mlp_wide_plan_policy.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_int32 * 4)]
-    L.mzs_conv3x3_nhwc.argtypes = [C.POINTER(MzsConv3x3Args), _vp]
-    L.mzs_resblock_v1.argtypes = [C.POINTER(MzsResblockArgs), _vp]
-    L.mzs_conv3x3_stride2_nhwc.argtypes = [C.POINTER(MzsConv3x3sArgs), _vp]
-    L.mzs_resnet_root_tail.argtypes = [C.POINTER(MzsRootTailArgs), _vp]
-    L.mzs_resblock_workspace_bytes.argtypes = [C.c_int32] * 4
-    L.mzs_resblock_v2.argtypes = [C.POINTER(MzsResblockArgs), _vp]
-    L.mzs_resblock_v2_workspace_bytes.argtypes = [C.c_int32] * 4
-    L.mzs_resnet_search.argtypes = [_vp, C.POINTER(MzsTowerArgs), C.c_float, C.c_int32, C.c_int32, _vp]
-    L.mzs_mlp_num_params.argtypes = [C.c_int32] * 4
-    L.mzs_mlp_train_workspace_bytes.argtypes = [C.c_int32] * 5
-    for n in EXPORTED_SYMBOLS[2:]:
-        getattr(L, n).restype = C.c_int
-    L.mzs_mlp_num_params.restype = C.c_int64
-    L.mzs_stochastic_mlp_num_params.argtypes = [C.c_int32] * 5
-    L.mzs_stochastic_mlp_num_params.restype = C.c_int64
-    L.mzs_stochastic_mlp_train_workspace_bytes.argtypes = [C.c_int32] * 6
-    L.mzs_stochastic_mlp_train_workspace_bytes.restype = C.c_int64
-    L.mzs_stochastic_mlp_loss_grad.argtypes = [C.POINTER(MzsStochasticTrainWeights), C.POINTER(MzsStochasticTrainArgs), _vp]
-    L.mzs_mlp_train_workspace_bytes.restype = C.c_int64
-    L.mzs_dirichlet.argtypes = [C.c_int32, C.POINTER(C.c_uint32 * 2), C.c_float, C.c_int32, C.c_int32, C.c_int64,
-                                C.c_int64, _vp, _vp]
-    L.mzs_ez_recurrent.argtypes = [C.POINTER(MzsEzArgs), _vp]
-    L.mzs_layernorm_act.argtypes = [C.POINTER(MzsLayerNormArgs), _vp]
-    L.mzs_layernorm_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
-    L.mzs_layernorm_workspace_bytes.restype = C.c_int64
-    L.mzs_resblock_workspace_bytes.restype = C.c_int64
-    L.mzs_resblock_v2_workspace_bytes.restype = C.c_int64
-    L.mzs_tower_pair_scratch_bytes.argtypes = [C.c_int32]
-    L.mzs_replay_store.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayStoreArgs), _vp]
-    L.mzs_replay_refresh.argtypes = [C.POINTER(MzsReplayArena), C.c_int32, C.c_int32, C.c_int32, _vp]
-    L.mzs_replay_sample.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplaySampleArgs), _vp]
-    L.mzs_replay_sample_is.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplaySampleArgs),
-                                       C.POINTER(MzsReplayIsArgs), _vp]
-    L.mzs_mlp_loss_grad_weighted.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsTrainArgs), _vp, _vp]
-    L.mzs_replay_gather_obs.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayGatherArgs), _vp]
-    L.mzs_replay_reanalyse.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayReanalyseArgs), _vp]
-    L.mzs_replay_update_priorities.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayUpdateArgs), _vp]
-    L.mzs_replay_stage.argtypes = [C.POINTER(MzsReplayRing), C.POINTER(MzsReplayStageArgs), _vp]
-    L.mzs_replay_store_steps.argtypes = [C.POINTER(MzsReplayArena), C.POINTER(MzsReplayRing),
-                                         C.POINTER(MzsReplayStoreStepsArgs), _vp]
-    L.mzs_replay_plan_steps.argtypes = [C.POINTER(MzsReplayRing), C.POINTER(MzsReplayPlanArgs), _vp]
-    L.mzs_env_cartpole_reset.argtypes = [C.POINTER(MzsEnvCartPole), _vp, _vp]
-    L.mzs_env_cartpole_step.argtypes = [C.POINTER(MzsEnvCartPole), C.POINTER(MzsEnvStepArgs), _vp]
-    L.mzs_env_classic_reset.argtypes = [C.POINTER(MzsEnvClassic), _vp, _vp]
-    L.mzs_env_classic_step.argtypes = [C.POINTER(MzsEnvClassic), C.POINTER(MzsEnvStepArgs), _vp]
-    L.mzs_env_2048_reset.argtypes = [C.POINTER(MzsEnv2048), _vp, _vp]
-    L.mzs_env_2048_step.argtypes = [C.POINTER(MzsEnv2048), C.POINTER(MzsEnvStepArgs), _vp]
-    L.mzs_env_2048_mask.argtypes = [C.c_int32, _vp, _vp, C.c_int32, _vp]
-    L.mzs_mlp_unroll_values.argtypes = [C.POINTER(MzsMlpWeights), C.POINTER(MzsUnrollArgs), _vp]
-    L.mzs_tower_pair_scratch_bytes.restype = C.c_int64
+    for name, (restype, argtypes) in ENTRIES.items():
+        f = getattr(L, name)  # (AttributeError: the shared object lacks a declared entry)
+        f.restype, f.argtypes = restype, argtypes
     if L.mzs_abi_version() != 1:
         raise RuntimeError("libmzsearch.so ABI version mismatch")
     _lib = L

@@ -18,7 +18,7 @@ from . import _lib
 from ._call import capture, device_index, raw_stream
 from ._lib import (MLP_WEIGHT_NAMES, TREE_FIELDS, TREE_INT_FIELDS, MzsActArgs, MzsActHostArgs, MzsConfig,
                    MzsMlpWeights, MzsStochasticMlpWeights, MzsStochasticOutputs, MzsStochasticSearchArgs, MzsTreeView,
-                   STOCHASTIC_MLP_WEIGHT_NAMES)
+                   STOCHASTIC_MLP_WEIGHT_NAMES, STOCHASTIC_OUTPUT_FIELDS)
 
 
 class SearchTree(NamedTuple):
@@ -149,29 +149,25 @@ class MuZeroSearch:
         self._dev_index = device_index(self.device)
         self.batch, self.cfg = int(batch), cfg
         self._L = _lib.load()
-        c = MzsConfig()
-        c.struct_size = C.sizeof(MzsConfig)
-        c.device = self._dev_index
-        c.batch, c.num_actions = self.batch, cfg.num_actions
-        c.num_simulations, c.embed_dim = cfg.num_simulations, cfg.embed_dim
-        c.max_depth = cfg.max_depth or 0
         try:
-            c.policy = {"muzero": 0, "gumbel": 1, "stochastic": 2}[cfg.policy]
-            c.qtransform = {"qtransform_by_parent_and_siblings": 0, "qtransform_completed_by_mix_value": 1}[
+            policy = {"muzero": 0, "gumbel": 1, "stochastic": 2}[cfg.policy]
+            qtransform = {"qtransform_by_parent_and_siblings": 0, "qtransform_completed_by_mix_value": 1}[
                 getattr(cfg.qtransform, "__name__", cfg.qtransform)]
         except KeyError as e:
             raise ValueError(f"unknown policy / qtransform: {e}") from None
-        c.tiebreak = int(bool(cfg.tiebreak))
-        c.max_num_considered_actions, c.gumbel_scale = cfg.max_num_considered_actions, cfg.gumbel_scale
-        c.pb_c_init, c.pb_c_base = cfg.pb_c_init, cfg.pb_c_base
-        c.global_batch = cfg.global_batch or self.batch
-        c.root_offset = cfg.root_offset
         self._stochastic = cfg.policy == "stochastic"
         self._es, self._ea = cfg.state_embed_dim or cfg.embed_dim, cfg.afterstate_embed_dim or cfg.embed_dim
+        chance = {}
         if self._stochastic:
-            c.num_chance_outcomes, c.state_embed_dim, c.afterstate_embed_dim = cfg.num_chance_outcomes, self._es, self._ea
+            chance = dict(num_chance_outcomes=cfg.num_chance_outcomes, state_embed_dim=self._es, afterstate_embed_dim=self._ea)
         elif cfg.num_chance_outcomes:
             raise ValueError("num_chance_outcomes is for policy='stochastic'")
+        c = _lib.args(MzsConfig, device=self._dev_index, batch=self.batch, num_actions=cfg.num_actions,
+                      num_simulations=cfg.num_simulations, embed_dim=cfg.embed_dim, max_depth=cfg.max_depth or 0,
+                      policy=policy, qtransform=qtransform, tiebreak=int(bool(cfg.tiebreak)),
+                      max_num_considered_actions=cfg.max_num_considered_actions, gumbel_scale=cfg.gumbel_scale,
+                      pb_c_init=cfg.pb_c_init, pb_c_base=cfg.pb_c_base, global_batch=cfg.global_batch or self.batch,
+                      root_offset=cfg.root_offset, **chance)
         self._slots = cfg.num_actions + (cfg.num_chance_outcomes if self._stochastic else 0)  # children per node
         h = C.c_void_p()
         _lib.check(self._L.mzs_create(C.byref(c), C.byref(h)))
@@ -241,10 +237,14 @@ class MuZeroSearch:
         return self._tree
 
     def _tree_view(self, tree: SearchTree) -> MzsTreeView:
-        v = MzsTreeView()
-        for f in TREE_FIELDS:
-            setattr(v, f, getattr(tree, f).data_ptr())
-        return v
+        return MzsTreeView(**{f: getattr(tree, f).data_ptr() for f in TREE_FIELDS})
+
+    def _export_tree(self) -> SearchTree:
+        """The finished tree of the handle copied into its persistent tree tensors (mzs_tree_export)."""
+        tree = self._alloc_tree()
+        view = self._tree_view(tree)
+        _lib.check(self._L.mzs_tree_export(self._h, C.byref(view), self._stream()), self._h)
+        return tree
 
     def outputs_to_host(self):
         """(action int32 [B], action_weights f32 [B, A], root_value f32 [B]) as fresh NumPy arrays: ONE
@@ -344,14 +344,10 @@ class MuZeroSearch:
             noise = self._f32(dirichlet_noise, (B, A), "dirichlet_noise")
             inv = self._u8(invalid_actions, (B, A), "invalid_actions")
             gum = self._f32(gumbel, (B, A), "gumbel")
-            a = MzsActArgs()
-            a.struct_size = C.sizeof(MzsActArgs)
-            a.obs, a.dirichlet_noise = obs_t.data_ptr(), (noise.data_ptr() if noise is not None else None)
-            a.invalid_actions = inv.data_ptr() if inv is not None else None
-            a.gumbel = gum.data_ptr() if gum is not None else None
-            a.action, a.action_weights = self.action.data_ptr(), self.action_weights.data_ptr()
-            a.root_value, a.search_value = self.root_value.data_ptr(), self.search_value.data_ptr()
-            a.depth_sum = self.depth_sum.data_ptr()
+            a = _lib.args(MzsActArgs, obs=obs_t.data_ptr(), dirichlet_noise=_ptr(noise), invalid_actions=_ptr(inv),
+                          gumbel=_ptr(gum), action=self.action.data_ptr(), action_weights=self.action_weights.data_ptr(),
+                          root_value=self.root_value.data_ptr(), search_value=self.search_value.data_ptr(),
+                          depth_sum=self.depth_sum.data_ptr())
             tree = None
             if with_tree:
                 tree = self._alloc_tree()
@@ -383,30 +379,23 @@ class MuZeroSearch:
         obs = np.ascontiguousarray(obs, np.float32)
         if obs.shape != (B, od):
             raise ValueError(f"obs: expected shape {(B, od)}, got {obs.shape}")
-        a = MzsActHostArgs()
-        a.struct_size = C.sizeof(MzsActHostArgs)
-        a.obs = obs.ctypes.data
-        keep = [obs]
+        nz = iv = None  # (the converted arrays stay alive until the call has returned)
         if dirichlet_noise is not None:
             nz = np.ascontiguousarray(dirichlet_noise, np.float32)
             if nz.shape != (B, A):
                 raise ValueError(f"dirichlet_noise: expected shape {(B, A)}, got {nz.shape}")
-            a.dirichlet_noise = nz.ctypes.data
-            keep.append(nz)
         if invalid_actions is not None:
             iv = np.ascontiguousarray(np.asarray(invalid_actions) != 0, np.uint8)
             if iv.shape != (B, A):
                 raise ValueError(f"invalid_actions: expected shape {(B, A)}, got {iv.shape}")
-            a.invalid_actions = iv.ctypes.data
-            keep.append(iv)
-        a.draw_dirichlet = 1
-        k = key_words(key)
-        a.key[0], a.key[1] = k
-        a.dirichlet_fraction, a.dirichlet_alpha, a.temperature = dirichlet_fraction, dirichlet_alpha, temperature
         action = np.empty(B, np.int32)
         weights = np.empty((B, A), np.float32)
         value = np.empty(B, np.float32)
-        a.action, a.action_weights, a.root_value = action.ctypes.data, weights.ctypes.data, value.ctypes.data
+        a = _lib.args(MzsActHostArgs, draw_dirichlet=1, obs=obs.ctypes.data,
+                      dirichlet_noise=None if nz is None else nz.ctypes.data,
+                      invalid_actions=None if iv is None else iv.ctypes.data, key=key_words(key),
+                      dirichlet_fraction=dirichlet_fraction, dirichlet_alpha=dirichlet_alpha, temperature=temperature,
+                      action=action.ctypes.data, action_weights=weights.ctypes.data, root_value=value.ctypes.data)
         _lib.check(self._L.mzs_act_mlp_host(self._h, C.byref(a), self._stream()), self._h)
         return action, weights, value
 
@@ -489,12 +478,7 @@ class MuZeroSearch:
         _lib.check(entry(self._h, C.c_float(temperature), _ptr(gum), _ptr(self.action), _ptr(self.action_weights),
                          _ptr(self.search_value), _ptr(self.depth_sum), self._stream()), self._h)
         self._keep = (gum,)
-        tree = None
-        if with_tree:
-            tree = self._alloc_tree()
-            view = self._tree_view(tree)
-            _lib.check(self._L.mzs_tree_export(self._h, C.byref(view), self._stream()), self._h)
-        return PolicyOutput(self.action, self.action_weights, tree)
+        return PolicyOutput(self.action, self.action_weights, self._export_tree() if with_tree else None)
 
     def finish(self, temperature: float = 1.0, gumbel=None, with_tree: bool = False) -> PolicyOutput:
         return self._finish(self._L.mzs_finish, temperature, gumbel, with_tree)
@@ -607,10 +591,7 @@ class MuZeroSearch:
                 self._f32(chance_out[0], (B, A), "action_logits"), self._f32(chance_out[1], (B,), "value"),
                 self._f32(chance_out[2], (B,), "reward"), self._f32(chance_out[3], (B,), "discount"),
                 self._f32(torch.as_tensor(state_embedding, device=dev).reshape(B, -1), (B, self._es), "state_embedding"))
-        o = MzsStochasticOutputs()
-        o.struct_size = C.sizeof(MzsStochasticOutputs)
-        (o.chance_logits, o.afterstate_value, o.afterstate_embedding, o.action_logits, o.value, o.reward, o.discount,
-         o.state_embedding) = (t.data_ptr() for t in keep)
+        o = _lib.args(MzsStochasticOutputs, **{n: t.data_ptr() for n, t in zip(STOCHASTIC_OUTPUT_FIELDS, keep)})
         _lib.check(self._L.mzs_expand_backup_stochastic(self._h, sim, C.byref(o), self._stream()), self._h)
         self._keep = keep
 
@@ -644,9 +625,7 @@ class MuZeroSearch:
             B, A, Cn, E = self.batch, self.cfg.num_actions, self.cfg.num_chance_outcomes, self.cfg.embed_dim
             with torch.cuda.device(self.device):
                 bufs = [torch.zeros(B * n, dtype=torch.float32, device=self.device) for n in (Cn, 1, E, A, 1, 1, 1, E)]
-            o = _lib.args(MzsStochasticOutputs)
-            (o.chance_logits, o.afterstate_value, o.afterstate_embedding, o.action_logits, o.value, o.reward, o.discount,
-             o.state_embedding) = (t.data_ptr() for t in bufs)
+            o = _lib.args(MzsStochasticOutputs, **{n: t.data_ptr() for n, t in zip(STOCHASTIC_OUTPUT_FIELDS, bufs)})
             self._stochastic_out = (o, bufs)
         o = self._stochastic_out[0]
         _lib.check(self._L.mzs_mlp_stochastic_recurrent(self._h, _ptr(slot), _ptr(parent_is_decision), _ptr(parent_embedding),
@@ -735,12 +714,7 @@ class MuZeroSearch:
                     launch(bufs, block)
                 entry = self._graphs[gk] = (g, stage, self._stochastic_weights, graph_version)
             entry[0].replay()
-        tree = None
-        if with_tree:
-            tree = self._alloc_tree()
-            view = self._tree_view(tree)
-            _lib.check(self._L.mzs_tree_export(self._h, C.byref(view), self._stream()), self._h)
-        return PolicyOutput(self.action, self.action_weights, tree)
+        return PolicyOutput(self.action, self.action_weights, self._export_tree() if with_tree else None)
 
     def search_stochastic_mlp(self, root_fn_output, key=0, invalid_actions=None, dirichlet_noise=None, dirichlet_fraction=0.25,
                               temperature=1.0, gumbel=None, with_tree=False, graph=False, graph_key=None,

@@ -1,8 +1,6 @@
 """The device plan's arithmetic on the host (no GPU): the plain-loop reference tests/plan_reference.py, which the GPU
 tests hold the kernels against, must itself be `vector.ring_plan` and collect()'s `np.sum` returns, and the public
 switches must refuse what they cannot serve."""
-import os
-import re
 
 import numpy as np
 import pytest
@@ -109,9 +107,6 @@ def test_fit_vector_device_plan_needs_device_collect():
 
 
 def test_abi_declares_the_plan_entry():
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mzsearch.h")).read()
-    assert "mzs_replay_plan_steps" in _lib.EXPORTED_SYMBOLS
-    body = re.search(r"typedef struct mzs_replay_plan_args \{(.*?)\} mzs_replay_plan_args;", header, re.S).group(1)
-    names = re.findall(r"(\w+);", body)
-    assert names == [n for n, _ in _lib.MzsReplayPlanArgs._fields_]
+    """(The entry and its block against the header: tests/test_abi_cpu.py, for the whole ABI.)"""
+    assert "mzs_replay_plan_steps" in _lib.EXPORTED_SYMBOLS and _lib.STRUCTS["mzs_replay_plan_args"] is _lib.MzsReplayPlanArgs
     assert _lib.replay_plan_scratch(1) == 2 and _lib.replay_plan_scratch(256) == 257 and _lib.replay_plan_scratch(257) == 259

@@ -2,11 +2,6 @@
 (tests/priority_reference.py) on hand-computed cases, the ABI declarations, the checks `update_priorities` makes before
 it touches the device, `value_priorities`, and `fit_vector(priority_update=)` on a buffer without the method.  No GPU,
 no kernel."""
-import ctypes
-import os
-import re
-import shutil
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
@@ -16,9 +11,8 @@ import torch
 import muax_amd as mx
 import priority_reference as pref
 from helpers import train_model
-from muax_amd import _build, _lib, vector
+from muax_amd import _lib, vector
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN, INF = float("nan"), float("inf")
 # two live episodes: slot 2 holds serial 7 (rows 4..8), slot 0 serial 9 (rows 0..2); slot 1 is not live
 LIVE = [(2, 4, 5, 7), (0, 0, 3, 9)]
@@ -85,32 +79,9 @@ def test_reference_skips_write_nothing():
     assert slots == {2} and w2.tolist() == [1, 2, 3, -9, 1, 1, 1, 2, 3, -9]  # row 9 (past the end) untouched
 
 
-def _header_size(tmp_path, struct):
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    src = tmp_path / "size.cpp"
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "mzsearch.h"\nint main() {\n'
-                   f'  std::printf("%zu %zu %zu\\n", sizeof({struct}), offsetof({struct}, alpha), '
-                   f'offsetof({struct}, touched));\n  return 0;\n}}\n')
-    exe = str(tmp_path / "size")
-    subprocess.check_call([cxx, "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    return [int(x) for x in subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout.split()]
-
-
-def test_header_and_bindings_agree_on_the_priority_entry(tmp_path):
-    header = open(os.path.join(ROOT, "include", "mzsearch.h")).read()
-    declared = set(re.findall(r"\b(mzs_[a-z0-9_]+)\s*\(", header))
-    name = "mzs_replay_update_priorities"
-    assert name in declared and name in _lib.EXPORTED_SYMBOLS and re.search(r"#define MZS_ABI_VERSION 1\b", header)
-    body = re.search(r"typedef struct mzs_replay_update_args \{(.*?)\} mzs_replay_update_args;", header, re.S).group(1)
-    fields = [f for decl in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";")
-              for f in re.findall(r"\*?\s*([A-Za-z_0-9]+)\s*(?:,|$)", decl.strip())]
-    assert fields == [n for n, _ in _lib.MzsReplayUpdateArgs._fields_]
-    U = _lib.MzsReplayUpdateArgs
-    assert [ctypes.sizeof(U), U.alpha.offset, U.touched.offset] == _header_size(tmp_path, "mzs_replay_update_args")
-    _build.build()
-    f = getattr(ctypes.CDLL(_build.LIB_PATH), name)
-    f.restype = ctypes.c_int
+def test_header_and_bindings_agree_on_the_priority_entry():
+    """(Its declaration, member list, size and offsets: tests/test_abi_cpu.py, for the whole ABI.)"""
+    f = _lib.load(build_if_missing=True).mzs_replay_update_priorities
     assert f(None, None, None) == _lib.MZS_E_INVALID  # a null block is refused before any device call
 
 

@@ -1,11 +1,5 @@
 """CPU tests of the reanalysis path's host parts: the stream plan, the NumPy restatement the GPU tests compare the
 write-back kernel with (tests/reanalyse_reference.py), the staleness order and the ABI declarations.  No GPU, no kernel."""
-import ctypes
-import os
-import re
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -13,10 +7,7 @@ import muax_amd as mx
 import reanalyse_reference as rref
 from muax_amd import _build, _lib, replay_device, vector
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mzs_replay_gather_obs", "mzs_replay_reanalyse")
-STRUCTS = {"mzs_replay_gather_args": "MzsReplayGatherArgs", "mzs_replay_reanalyse_args": "MzsReplayReanalyseArgs",
-           "mzs_replay_arena": "MzsReplayArena"}
 
 
 def test_plan_of_episodes_that_straddle_chunks():
@@ -63,34 +54,13 @@ def test_reference_agrees_with_episode_trajectory(alpha):
         assert (w == 1.0).all()
 
 
-def _header_sizes(tmp_path):
-    """sizeof of the structs of STRUCTS as the C compiler sees include/mzsearch.h."""
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    src = tmp_path / "sizes.cpp"
-    src.write_text('#include <cstdio>\n#include "mzsearch.h"\nint main() {\n'
-                   + "".join(f'  std::printf("{s} %zu\\n", sizeof({s}));\n' for s in STRUCTS) + "  return 0;\n}\n")
-    exe = str(tmp_path / "sizes")
-    subprocess.check_call([cxx, "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout
-    return {name: int(size) for name, size in (line.split() for line in out.splitlines())}
-
-
-def test_header_and_bindings_agree_on_the_reanalysis_entries(tmp_path):
-    header = open(os.path.join(ROOT, "include", "mzsearch.h")).read()
-    declared = set(re.findall(r"\b(mzs_[a-z0-9_]+)\s*\(", header))
-    assert set(NEW) <= declared and set(NEW) <= set(_lib.EXPORTED_SYMBOLS)
+def test_header_and_bindings_agree_on_the_reanalysis_entries():
+    """(Declarations, sizes and layouts: tests/test_abi_cpu.py, for the whole ABI.)"""
     assert "mz_replay.hip" in _build.UNITS and "mz_replay.cuh" in _build.UNITS["mz_replay.hip"]
-    sizes = _header_sizes(tmp_path)
-    for c_name, py_name in STRUCTS.items():
-        assert ctypes.sizeof(getattr(_lib, py_name)) == sizes[c_name], c_name
-    _build.build()
-    lib = ctypes.CDLL(_build.LIB_PATH)
+    lib = _lib.load(build_if_missing=True)
     for s in NEW:
-        f = getattr(lib, s)
-        f.restype = ctypes.c_int
         # a null block is refused before any device call
-        assert f(None, None, None) == _lib.MZS_E_INVALID
+        assert getattr(lib, s)(None, None, None) == _lib.MZS_E_INVALID
 
 
 def test_stalest_and_argument_checks_need_no_device():

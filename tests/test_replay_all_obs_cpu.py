@@ -3,10 +3,6 @@
 refuses before anything runs -- on stub buffers, and the ABI: `obs_steps` took the place of `reserved0` in
 `mzs_replay_sample_args` without moving anything."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
@@ -17,8 +13,6 @@ import muax_amd as mx
 import replay_obs_reference as obsref
 import replay_reference as ref
 from muax_amd import _lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- the reference ----
@@ -164,26 +158,10 @@ def test_sample_takes_all_obs_and_checks_before_any_device_use():
 
 
 # ---- the ABI ----
-def test_obs_steps_sits_where_reserved0_was(tmp_path):
-    header = open(os.path.join(ROOT, "include", "mzsearch.h")).read()
-    body = re.search(r"typedef struct mzs_replay_sample_args \{(.*?)\} mzs_replay_sample_args;", header, re.S).group(1)
-    fields = [f for decl in re.sub(r"/\*.*?\*/", "", body, flags=re.S).split(";")
-              for f in re.findall(r"\*?\s*([A-Za-z_0-9]+)\s*(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
+def test_obs_steps_sits_where_reserved0_was():
+    """(That these are the header's members and the compiler's offsets: tests/test_abi_cpu.py, for every struct.)"""
     S = _lib.MzsReplaySampleArgs
-    assert fields == [n for n, _ in S._fields_] and "reserved0" not in fields
-    assert re.search(r"#define MZS_ABI_VERSION 1\b", header)
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    src = tmp_path / "layout.cpp"
-    src.write_text('#include <cstdio>\n#include <cstddef>\n#include "mzsearch.h"\nint main() {\n'
-                   '  std::printf("%zu %zu %zu %zu\\n", sizeof(mzs_replay_sample_args), '
-                   'offsetof(mzs_replay_sample_args, obs_steps), offsetof(mzs_replay_sample_args, key), '
-                   'offsetof(mzs_replay_sample_args, obs));\n  return 0;\n}\n')
-    exe = str(tmp_path / "layout")
-    subprocess.check_call([cxx, "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout
-    size, at, key_at, obs_at = (int(x) for x in out.split())
+    assert "obs_steps" in dict(S._fields_) and "reserved0" not in dict(S._fields_)
     # 112 bytes as before the field had a name; the int32 behind key[2] at byte 28, the first pointer behind it
-    assert (size, at, key_at, obs_at) == (112, 28, 20, 32)
-    assert (ctypes.sizeof(S), S.obs_steps.offset, S.key.offset, S.obs.offset) == (size, at, key_at, obs_at)
+    assert (ctypes.sizeof(S), S.obs_steps.offset, S.key.offset, S.obs.offset) == (112, 28, 20, 32)
     assert S.obs_steps.size == 4 and _lib.args(S).obs_steps == 0  # zero-filled: today's behaviour

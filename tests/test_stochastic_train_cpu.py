@@ -9,17 +9,12 @@ import torch
 
 import muax_amd as mx
 import stochastic_train_reference as ref
-from muax_amd import _build, _lib
+from muax_amd import _lib
 from test_stochastic_loss_cpu import A, B, CN, E, L, OD, SUP, numpy_loss
 
 
 def test_num_params_is_the_summed_numel():
-    _build.build()
-    lib = ctypes.CDLL(_build.LIB_PATH)  # (loads without a device, as in test_host_cpu.py)
-    lib.mzs_stochastic_mlp_num_params.restype = ctypes.c_int64
-    lib.mzs_stochastic_mlp_num_params.argtypes = [ctypes.c_int32] * 5
-    lib.mzs_stochastic_mlp_train_workspace_bytes.restype = ctypes.c_int64
-    lib.mzs_stochastic_mlp_train_workspace_bytes.argtypes = [ctypes.c_int32] * 6
+    lib = _lib.load(build_if_missing=True)  # (loads without a device, as in test_host_cpu.py)
     for a, c, e, s, od in ref.SHAPES + [(4, 32, 32, 31, 16)]:
         m = ref.smz_model(a, c, e, s, od, seed=1, device="cpu")
         w = mx.nn.stochastic_train_weights(m.network)

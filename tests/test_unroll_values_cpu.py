@@ -9,7 +9,6 @@ a softmax and the decode, whose inverse-h amplifies an error of the expectation 
 measured at 2.5e-6 of the largest priority on these cases (|v| up to 5.0, v within 1.5e-4 absolute; 2.7e-6 and 1.6e-4
 with |v| up to 6.1 on other seeds); the bar is about eight times that."""
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
@@ -127,14 +126,11 @@ def test_arguments_are_checked_before_anything_runs(oracle, monkeypatch):
 
 
 def test_abi_declarations():
-    header = open(_build.CSRC + "/../../include/mzsearch.h").read()
-    assert re.search(r"\bint mzs_mlp_unroll_values\(const mzs_mlp_weights \*w, const mzs_unroll_args \*a, void \*stream\);", header)
-    assert "mzs_mlp_unroll_values" in _lib.EXPORTED_SYMBOLS and re.search(r"#define MZS_ABI_VERSION 1\b", header)
+    """(The prototype, the member list and the layout against the header: tests/test_abi_cpu.py, for the whole ABI.)"""
+    P = C.POINTER
+    assert _lib.ENTRIES["mzs_mlp_unroll_values"] == (C.c_int, [P(_lib.MzsMlpWeights), P(_lib.MzsUnrollArgs), C.c_void_p])
     assert "mz_unroll.hip" in _build.UNITS and {"mz_unroll.cuh", "mz_mlp_generic.cuh"} <= set(_build.UNITS["mz_unroll.hip"])
     assert "mz_unroll.hip" not in _build.UNIT_FLAGS and "-ffp-contract=off" in _build.FLAGS  # built as mz_stepwise.hip is
-    body = re.search(r"typedef struct mzs_unroll_args \{(.*?)\} mzs_unroll_args;", header, re.S).group(1)
-    declared = re.findall(r"\b(\w+);", body)
-    assert declared == [n for n, _ in _lib.MzsUnrollArgs._fields_]
     assert C.sizeof(_lib.MzsUnrollArgs) == 8 * 4 + 5 * 8
     assert _lib.MzsUnrollArgs.obs.offset == 32 and _lib.MzsUnrollArgs.prio.offset == 64
 

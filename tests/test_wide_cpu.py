@@ -1,21 +1,14 @@
 """The wide-action act() route (mzs_mlp_allow_wide, muax_amd/csrc/mz_wide.cuh) as far as a machine without a GPU sees it:
 the ABI declares and exports it, the Python handle offers it, the on-demand planner still has nothing for such shapes, and
 the LDS plan (host arithmetic) gives what its formula says."""
-import ctypes
-import os
-import re
 
 from muax_amd import MuZeroSearch, _build, _jit, _lib
 from muax_amd.search import wide_plan
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 def test_header_declares_and_bindings_list_allow_wide():
-    header = open(os.path.join(ROOT, "include", "mzsearch.h")).read()
-    declared = set(re.findall(r"\b(mzs_[a-z0-9_]+)\s*\(", header))
-    assert {"mzs_mlp_allow_wide", "mzs_mlp_wide_plan", "mzs_mlp_allow_generic"} <= declared
-    assert "mzs_mlp_allow_wide" in _lib.EXPORTED_SYMBOLS and "mzs_mlp_wide_plan" in _lib.EXPORTED_SYMBOLS
+    # (EXPORTED_SYMBOLS is the header's set: tests/test_abi_cpu.py)
+    assert {"mzs_mlp_allow_wide", "mzs_mlp_wide_plan", "mzs_mlp_allow_generic"} <= set(_lib.EXPORTED_SYMBOLS)
     assert callable(getattr(MuZeroSearch, "allow_wide"))
     assert "mz_wide.hip" in _build.UNITS
 
@@ -27,13 +20,9 @@ def test_no_on_demand_instance_for_wide_action_sets():
 
 
 def test_built_library_exports_the_wide_entry_points():
-    _build.build()
-    lib = ctypes.CDLL(_build.LIB_PATH)
+    lib = _lib.load(build_if_missing=True)
     assert lib.mzs_mlp_allow_wide and lib.mzs_mlp_wide_plan
-    lib.mzs_abi_version.restype = ctypes.c_int
     assert lib.mzs_abi_version() == 1
-    lib.mzs_mlp_allow_wide.argtypes = [ctypes.c_void_p, ctypes.c_int32]
-    lib.mzs_mlp_allow_wide.restype = ctypes.c_int
     assert lib.mzs_mlp_allow_wide(None, 1) == _lib.MZS_E_INVALID  # no handle: refused, nothing touched
 
 
