@@ -16,7 +16,7 @@ iteration's stream comes down once, is cut into finished episodes (`episode_traj
 Nothing here has been run to a result: whether this recipe learns 2048 is not known.
 
     python examples/fit_2048_stochastic.py [--envs 256] [--steps 64] [--iterations 3] [--updates 20] [--one-launch]
-                                           [--fused-update] [--host-buffer]
+                                           [--root-in-kernel] [--fused-update] [--host-buffer]
 """
 import argparse
 import functools
@@ -120,6 +120,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--one-launch", action="store_true",
                     help="act() with the whole search in one launch (MuZero(stochastic_one_launch=True)): the same bits")
+    ap.add_argument("--root-in-kernel", action="store_true",
+                    help="act() with root inference by the library too (MuZero(stochastic_root_in_kernel=True)): no torch "
+                         "module in an act(); with --one-launch an act() is one launch")
     ap.add_argument("--fused-update", action="store_true",
                     help="update() on the fused training kernel (MuZero(stochastic_fused_update=True)) instead of autograd")
     ap.add_argument("--host-buffer", action="store_true",
@@ -132,7 +135,7 @@ def main():
     net = muax.create_stochastic_muzero_network(E, venv.num_actions, Cn, 2 * support_size + 1)
     model = muax.MuZero(net, policy="stochastic", discount=discount, support_size=support_size,
                         optimizer=muax.optimizers.create_optimizer("adam", 2e-3), stochastic_one_launch=args.one_launch,
-                        stochastic_fused_update=args.fused_update)
+                        stochastic_fused_update=args.fused_update, stochastic_root_in_kernel=args.root_in_kernel)
     if not args.host_buffer:
         fit_on_device(model, venv, args, discount, k_steps)
         return

@@ -306,6 +306,31 @@ int mzs_mlp_stochastic_search(mzs_handle *h, const mzs_stochastic_search_args *a
 int mzs_stochastic_search_block(const uint32_t key[2], int32_t num_simulations, float temperature, float dirichlet_fraction,
                                 uint32_t *out_words);
 
+/* ---- root inference of the bound family evaluated by the library (muax_amd/csrc/mz_stoch_wide.cuh): the default
+ * Representation, s = min_max_normalize(obs @ repr_w + repr_b), then value = decode(pv(s)), prior logits = pp(s) with the
+ * heads bound by mzs_mlp_set_stochastic_weights -- RootFnOutput without a torch module.  Arithmetic "MZ-F32": the fma chain
+ * over the observation in index order from 0, the bias last; one root per wavefront, embed_dim <= 64. ----
+ * Binds the representation's weights, float32 device pointers repr_w [obs_dim, embed_dim] and repr_b [embed_dim], haiku
+ * layout; any obs_dim >= 1.  They take no LDS (read from global memory once per root): mzs_mlp_stochastic_plan does not
+ * change.  The arrays stay the caller's and are read at every launch.  MZS_E_INVALID for a handle of another policy,
+ * obs_dim < 1, a null array. */
+int mzs_mlp_set_stochastic_representation(mzs_handle *h, int32_t obs_dim, const float *repr_w, const float *repr_b);
+/* obs [B, obs_dim] -> prior_logits_out [B, A], value_out [B], embedding_out [B, embed_dim], what mzs_root_stochastic takes.
+ * One launch on `stream`, no LDS tree, capturable.  Refused before the launch, the message naming the cause: MZS_E_INVALID
+ * for a handle of another policy, weights or representation not bound, a null obs or output; MZS_E_UNSUPPORTED for
+ * embed_dim > 64 (and what mzs_mlp_set_stochastic_weights refuses). */
+int mzs_mlp_stochastic_root(mzs_handle *h, const float *obs, float *prior_logits_out, float *value_out,
+                            float *embedding_out, void *stream);
+/* mzs_mlp_stochastic_search with the root inference inside the launch: obs [B, obs_dim] replaces the RootFnOutput arrays
+ * of `args`, whose prior_logits, value and embedding must be NULL; root_value_out [B] receives the root's network value,
+ * node 0's embedding is exported with export_tree.  Bit for bit mzs_mlp_stochastic_root followed by
+ * mzs_mlp_stochastic_search.  Everything else as there: one launch, capturable, device_block honoured, the same plan.
+ * Refused before any launch: MZS_E_INVALID for a handle of another policy, weights or representation not bound, a null or
+ * mis-sized struct, a null obs, root_value_out, action or action_weights, a non-null root array in `args`;
+ * MZS_E_UNSUPPORTED for a shape the plan declines. */
+int mzs_mlp_stochastic_search_obs(mzs_handle *h, const mzs_stochastic_search_args *args, const float *obs,
+                                  float *root_value_out, void *stream);
+
 /* ---- recurrent_fn of the EfficientZero-style nets ----
  * mzs_ez_recurrent evaluates, for a batch of 6x6xC hidden states (NHWC, C = 32 or 64) and actions, the whole
  * MuZero._recurrent_inference (muax/model.py:265-282) of EZDynamic + EZPrediction with use_v2 = True

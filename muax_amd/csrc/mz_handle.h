@@ -37,6 +37,8 @@ struct mzs_handle {
   bool allow_wide_gumbel = false;  // mzs_mlp_allow_wide_gumbel: ... and under the Gumbel policy (a handle opts in separately)
   bool have_stochastic_weights = false;  // mzs_mlp_set_stochastic_weights: the default stochastic MLP family (policy 2)
   mzs_stochastic_mlp_weights sw = {};
+  int32_t stoch_obs_dim = 0;  // mzs_mlp_set_stochastic_representation (0: not bound): the family's root inference in the library
+  const float *stoch_repr_w = nullptr, *stoch_repr_b = nullptr;
 };
 
 namespace mzh {

@@ -387,15 +387,71 @@ int mzs_mlp_stochastic_recurrent(mzs_handle* h, const int32_t* slot, const int32
   return launched(h);
 }
 
-// ---- the whole stochastic search of the bound family in ONE launch, the tree in LDS (mz_stoch_wide.cuh) ----
-int mzs_mlp_stochastic_search(mzs_handle* h, const mzs_stochastic_search_args* a, void* stream_) {
+// ---- root inference of the bound family in the library (mz_stoch_wide.cuh: wave_root_state + the prediction heads) ----
+int mzs_mlp_set_stochastic_representation(mzs_handle* h, int32_t obs_dim, const float* repr_w, const float* repr_b) {
   if (!h) return MZS_E_INVALID;
-  const char* who = "mzs_mlp_stochastic_search";
+  const char* who = "mzs_mlp_set_stochastic_representation";
+  if (h->cfg.policy != 2) return fail(h, MZS_E_INVALID, "%s", (std::string(who) + ": " + kNotStochastic).c_str());
+  if (obs_dim < 1) return fail(h, MZS_E_INVALID, "%s: obs_dim must be at least 1", who);
+  if (!repr_w || !repr_b) return fail(h, MZS_E_INVALID, "%s: null weight array", who);
+  h->stoch_obs_dim = obs_dim;
+  h->stoch_repr_w = repr_w;
+  h->stoch_repr_b = repr_b;
+  return MZS_OK;
+}
+
+// what the two entries that run root inference open with: the policy and the family's limits, weights and representation bound
+static int stoch_root_refusal(mzs_handle* h, const char* who) {
   const mzs_config& c = h->cfg;
   if (c.policy == 2 && !h->have_stochastic_weights) return fail(h, MZS_E_INVALID, "%s: call mzs_mlp_set_stochastic_weights first", who);
   if (int rc = stoch_mlp_refusal(h, who, h->sw.support_size)) return rc;
+  if (h->stoch_obs_dim < 1) return fail(h, MZS_E_INVALID, "%s: call mzs_mlp_set_stochastic_representation first", who);
+  return MZS_OK;
+}
+
+int mzs_mlp_stochastic_root(mzs_handle* h, const float* obs, float* prior_logits_out, float* value_out, float* embedding_out,
+                            void* stream_) {
+  if (!h) return MZS_E_INVALID;
+  const char* who = "mzs_mlp_stochastic_root";
+  const mzs_config& c = h->cfg;
+  if (int rc = stoch_root_refusal(h, who)) return rc;
+  if (!obs) return fail(h, MZS_E_INVALID, "%s: null obs", who);
+  if (!prior_logits_out || !value_out || !embedding_out) return fail(h, MZS_E_INVALID, "%s: null output", who);
+  if (c.embed_dim > 64) return fail(h, MZS_E_UNSUPPORTED, "%s: embed_dim must be 1..64", who);
+  MZS_HIP(h, hipSetDevice(c.device));
+  const mzs_stochastic_mlp_weights& s = h->sw;
+  mz::StochRootParams p = {};
+  p.obs = obs; p.repr_w = h->stoch_repr_w; p.repr_b = h->stoch_repr_b;
+  p.pv = {s.pv_w1, s.pv_b1, s.pv_w2, s.pv_b2}; p.pp = {s.pp_w1, s.pp_b1, s.pp_w2, s.pp_b2};
+  p.prior_logits = prior_logits_out; p.value = value_out; p.embedding = embedding_out;
+  p.B = c.batch; p.obs_dim = h->stoch_obs_dim; p.E = c.embed_dim; p.A = c.num_actions; p.F = 2 * s.support_size + 1;
+  p.support = s.support_size;
+  std::string err;
+  if (int rc = mz::stoch_root_launch(p, static_cast<hipStream_t>(stream_), &err))
+    return fail(h, rc, "%s", (std::string(who) + ": " + err).c_str());
+  return MZS_OK;
+}
+
+// ---- the whole stochastic search of the bound family in ONE launch, the tree in LDS (mz_stoch_wide.cuh) ----
+// obs: null for mzs_mlp_stochastic_search (the RootFnOutput arrays of `a`), else root inference inside the launch
+static int stoch_search(mzs_handle* h, const char* who, const mzs_stochastic_search_args* a, const float* obs,
+                        float* root_value_out, bool with_obs, void* stream_) {
+  const mzs_config& c = h->cfg;
+  if (with_obs) {
+    if (int rc = stoch_root_refusal(h, who)) return rc;
+  } else {
+    if (c.policy == 2 && !h->have_stochastic_weights) return fail(h, MZS_E_INVALID, "%s: call mzs_mlp_set_stochastic_weights first", who);
+    if (int rc = stoch_mlp_refusal(h, who, h->sw.support_size)) return rc;
+  }
   if (!a || a->struct_size != (int32_t)sizeof(mzs_stochastic_search_args)) return fail(h, MZS_E_INVALID, "%s: null or size mismatch (ABI)", who);
-  if (!a->prior_logits || !a->value || !a->embedding) return fail(h, MZS_E_INVALID, "%s: null input", who);
+  if (with_obs) {
+    if (!obs) return fail(h, MZS_E_INVALID, "%s: null obs", who);
+    if (!root_value_out) return fail(h, MZS_E_INVALID, "%s: null root_value_out", who);
+    if (a->prior_logits || a->value || a->embedding)
+      return fail(h, MZS_E_INVALID, "%s: prior_logits, value and embedding must be NULL (the kernel computes them from obs)", who);
+  } else if (!a->prior_logits || !a->value || !a->embedding) {
+    return fail(h, MZS_E_INVALID, "%s: null input", who);
+  }
   if (!a->action || !a->action_weights) return fail(h, MZS_E_INVALID, "%s: null output", who);
   if (!a->dirichlet_noise && a->dirichlet_fraction != 0.0f && !a->device_block)
     return fail(h, MZS_E_INVALID, "%s: dirichlet_fraction != 0 needs dirichlet_noise", who);
@@ -413,6 +469,10 @@ int mzs_mlp_stochastic_search(mzs_handle* h, const mzs_stochastic_search_args* a
     MZS_HIP(h, hipMalloc(reinterpret_cast<void**>(&h->fused_emb), BN * c.embed_dim * sizeof(float)));
   mz::StochWideParams p = {};
   p.prior_logits = a->prior_logits; p.value = a->value; p.embedding = a->embedding;
+  if (with_obs) {
+    p.obs = obs; p.repr_w = h->stoch_repr_w; p.repr_b = h->stoch_repr_b; p.obs_dim = h->stoch_obs_dim;
+    p.root_value_out = root_value_out;
+  }
   p.invalid = a->invalid_actions; p.dirichlet_noise = a->dirichlet_noise; p.gumbel = a->gumbel;
   memcpy(p.w, &s.ad_w1, sizeof p.w);
   p.action = a->action; p.action_weights = a->action_weights; p.search_value = a->search_value; p.depth_sum = a->depth_sum;
@@ -435,10 +495,21 @@ int mzs_mlp_stochastic_search(mzs_handle* h, const mzs_stochastic_search_args* a
   p.global_batch = (uint64_t)c.global_batch; p.root_offset = (uint64_t)c.root_offset;
   mzh::derive_keys(a->key, c.num_simulations, p.k_sample, &p.sim_keys[0][0]);  // num_simulations <= 255 (the plan)
   std::string err;
-  if (int rc = mz::stoch_wide_launch(c.tiebreak != 0, c.device, p, pl, static_cast<hipStream_t>(stream_), &err))
+  if (int rc = mz::stoch_wide_launch(c.tiebreak != 0, with_obs, c.device, p, pl, static_cast<hipStream_t>(stream_), &err))
     return fail(h, rc, "%s", (std::string(who) + ": " + err).c_str());
   if (ex) h->step.rooted = true;  // the HBM tree is that of a finished step-wise search: mzs_tree_export serves it
   return MZS_OK;
+}
+
+int mzs_mlp_stochastic_search(mzs_handle* h, const mzs_stochastic_search_args* a, void* stream_) {
+  if (!h) return MZS_E_INVALID;
+  return stoch_search(h, "mzs_mlp_stochastic_search", a, nullptr, nullptr, false, stream_);
+}
+
+int mzs_mlp_stochastic_search_obs(mzs_handle* h, const mzs_stochastic_search_args* a, const float* obs, float* root_value_out,
+                                  void* stream_) {
+  if (!h) return MZS_E_INVALID;
+  return stoch_search(h, "mzs_mlp_stochastic_search_obs", a, obs, root_value_out, true, stream_);
 }
 
 int mzs_tree_export(mzs_handle* h, const mzs_tree_view* out, void* stream_) {

@@ -1,7 +1,10 @@
 // mz_stoch_wide.cuh -- the WHOLE stochastic search of the default stochastic MLP family (mctx stochastic_muzero_policy,
 // DESIGN.md 4.7) in ONE launch, the root's tree in LDS: the root set-up of mzs_root_stochastic, every simulation (select
 // -> decision or chance function -> expand -> backward), the summary and the sampling of mzs_finish_stochastic.  Root
-// inference stays with the caller: the kernel takes the RootFnOutput arrays.  The mapping, the tree record and the rules
+// inference is the caller's (the kernel takes the RootFnOutput arrays) or, in the ROOT instantiations, the kernel's own:
+// the representation (mz_wave_tree.cuh wave_root_state, its weights read from HBM once per root) and the prediction heads
+// on the observation row, as mz_wide.cuh does it; mz_stoch_root_kernel is that root inference alone, for the
+// three-launch route.  The mapping, the tree record and the rules
 // both one-launch kernels follow (pUCT score, tie-break noise, expansion, backup, summary and sampling, tree export) are
 // mz_wave_tree.cuh's:
 //
@@ -24,7 +27,8 @@
 // function, the outcome of the chance function) only the one whose input is 1 is evaluated -- fma(0, w, acc) == acc for
 // finite w unless acc is -0, and an accumulator that starts at +0 and adds products of non-negative inputs is not -0.
 // The condition holds for both functions: the state embedding (the caller's root inference and the chance function's
-// output) and the afterstate embedding are min-max normalised, hence non-negative.
+// output) and the afterstate embedding are min-max normalised, hence non-negative.  It holds for the ROOT instantiations
+// as well: the root state they compute leaves wave_min_max_normalize, (s - min) / scale with scale > 0.
 //
 // No atomics, nothing that depends on the launch geometry: a root's bits are the same whichever wavefront of whichever
 // workgroup ran it.
@@ -40,8 +44,37 @@ struct StochWideShape {
   int rec_words, root_words, wg_words, weight_words, emb_lds, waves;
 };
 
-// MODE 0 / 1: without / with mctx's tie-break noise at the decision nodes (the handle's `tiebreak`)
-template <int MODE>
+// Prediction (muax/nn.py:73-90) on the state whose element k is in lane k of `s`, as the chance function evaluates it:
+// the two hidden layers side by side (`grp`: 0 value, 1 policy; `u`: this lane's hidden unit), action logit a in lane a
+// (al = min(lane, A - 1)), the decoded value in every lane.  pv, pp: the heads in LDS or in HBM
+MZ_DEV void stoch_prediction(float s, const Mlp2& pv, const Mlp2& pp, int E, int F, int A, int support, int lane, float& logit,
+                             float& value) {
+  const int u = lane & 15, grp = (lane >> 4) & 1;
+  const int fc = lane < F ? lane : 0, al = lane < A ? lane : 0;
+  const float h = elu(wide_chain(s, E, (grp ? pp.w1 : pv.w1) + u) + (grp ? pp.b1 : pv.b1)[u]);
+  const float vl = wide_out<0>(h, pv.w2, pv.b2, F, fc);
+  logit = wide_out<16>(h, pp.w2, pp.b2, A, al);
+  value = wave_decode(vl, F, support, lane);
+}
+
+// Root inference of the family on its own (mzs_mlp_stochastic_root): RootFnOutput for B observations, one root per
+// wavefront, the representation by wave_root_state, the prediction heads read from HBM.  No LDS, no barrier
+__global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_root_kernel(const StochRootParams p) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * kWideMaxWaves + (threadIdx.x >> 6);
+  if (r >= p.B) return;  // (wavefront-uniform)
+  const float s = wave_root_state(p.obs + (size_t)r * p.obs_dim, p.repr_w, p.repr_b, p.obs_dim, p.E, lane);
+  float logit, value;
+  stoch_prediction(s, p.pv, p.pp, p.E, p.F, p.A, p.support, lane, logit, value);
+  if (lane < p.E) p.embedding[(size_t)r * p.E + lane] = s;
+  if (lane < p.A) p.prior_logits[(size_t)r * p.A + lane] = logit;
+  if (lane == 0) p.value[r] = value;
+}
+
+// MODE 0 / 1: without / with mctx's tie-break noise at the decision nodes (the handle's `tiebreak`); ROOT: root
+// inference inside the launch -- the kernel reads p.obs and the representation's weights (HBM, once per root) instead of
+// the RootFnOutput arrays and writes p.root_value_out
+template <int MODE, bool ROOT = false>
 __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const StochWideParams p, const StochWideShape sh) {
   static_assert(MODE == 0 || MODE == 1, "tie-break setting");
   constexpr bool TIEBREAK = MODE == 1;
@@ -99,7 +132,16 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
   // ---- the root (mz_step_kernels.cuh root_row with AD = A): Dirichlet mix, log, mask over the actions, -inf on the
   // chance slots, the softmax over all slots ----
   {
-    const float x = act ? p.prior_logits[(size_t)r * A + al] : 0.0f;
+    float x;
+    [[maybe_unused]] float root_v = 0.0f;
+    if constexpr (ROOT) {
+      // root inference (MuZero._root_inference_eager on the default modules): node 0's state, its logits and value
+      const float s = wave_root_state(p.obs + (size_t)r * p.obs_dim, p.repr_w, p.repr_b, p.obs_dim, E, lane);
+      if (lane < E) emb[lane] = s;
+      stoch_prediction(s, pv, pp, E, F, A, p.support, lane, x, root_v);
+    } else {
+      x = act ? p.prior_logits[(size_t)r * A + al] : 0.0f;
+    }
     const float pr = wave_softmax(x, A, lane);
     const float nz = (p.dirichlet_noise != nullptr && act) ? p.dirichlet_noise[(size_t)r * A + al] : 0.0f;
     const float noisy = (1.0f - fraction) * pr + fraction * nz;
@@ -110,13 +152,16 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
     }
     lg = act ? lg : -INFINITY;
     const float prob = wave_softmax(lg, AC, lane);
-    if (lane < E) emb[lane] = p.embedding[(size_t)r * E + ec];
+    if constexpr (!ROOT)
+      if (lane < E) emb[lane] = p.embedding[(size_t)r * E + ec];
     if (ok) {
       tree[rec_child(kChildProb, AC, sl)] = __float_as_int(prob);
       if (ex) p.t_children_prior_logits[tn0 * AC + sl] = lg;
     }
     if (lane == 0) {
-      const float v = p.value[r];
+      float v;
+      if constexpr (ROOT) p.root_value_out[r] = v = root_v;
+      else v = p.value[r];
       tree[kRecVisits] = 1;
       tree[kRecValue] = __float_as_int(v);
       tree[kRecRaw] = __float_as_int(v);

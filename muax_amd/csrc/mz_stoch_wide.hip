@@ -10,12 +10,27 @@
 
 namespace mz {
 
-int stoch_wide_launch(bool tiebreak, int device, const StochWideParams& p, const WidePlan& pl, hipStream_t stream,
+int stoch_wide_launch(bool tiebreak, bool root, int device, const StochWideParams& p, const WidePlan& pl, hipStream_t stream,
                       std::string* err) {
   const StochWideShape sh = {pl.rec_words, pl.root_words, pl.wg_words, pl.weight_words, pl.emb_lds, pl.waves};
   const char* what = "stochastic search kernel launch: ";
-  return tiebreak ? launch_wave_per_root<mz_stoch_wide_kernel<1>>(what, device, p, sh, (size_t)pl.lds_bytes, stream, err)
-                  : launch_wave_per_root<mz_stoch_wide_kernel<0>>(what, device, p, sh, (size_t)pl.lds_bytes, stream, err);
+  const size_t lds = (size_t)pl.lds_bytes;
+  if (root)
+    return tiebreak ? launch_wave_per_root<mz_stoch_wide_kernel<1, true>>(what, device, p, sh, lds, stream, err)
+                    : launch_wave_per_root<mz_stoch_wide_kernel<0, true>>(what, device, p, sh, lds, stream, err);
+  return tiebreak ? launch_wave_per_root<mz_stoch_wide_kernel<1>>(what, device, p, sh, lds, stream, err)
+                  : launch_wave_per_root<mz_stoch_wide_kernel<0>>(what, device, p, sh, lds, stream, err);
+}
+
+int stoch_root_launch(const StochRootParams& p, hipStream_t stream, std::string* err) {
+  const int grid = (p.B + kWideMaxWaves - 1) / kWideMaxWaves;
+  hipLaunchKernelGGL(mz_stoch_root_kernel, dim3(grid), dim3(64 * kWideMaxWaves), 0, stream, p);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    *err = std::string("stochastic root kernel launch: ") + hipGetErrorString(e);
+    return MZS_E_RUNTIME;
+  }
+  return MZS_OK;
 }
 
 }  // namespace mz

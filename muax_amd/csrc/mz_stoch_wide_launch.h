@@ -58,10 +58,25 @@ struct StochWideParams {
   uint64_t global_batch, root_offset;
   uint32_t k_sample[2];
   uint32_t sim_keys[kMaxSims][2];
+  // root inference inside the launch (the kernel's ROOT instantiations; prior_logits, value, embedding are then null):
+  // obs [B, obs_dim], the representation's repr_w [obs_dim, E] and repr_b [E] in HBM, the root's network value out [B]
+  const float *obs, *repr_w, *repr_b;
+  float* root_value_out;
+  int32_t obs_dim;
 };
 
-// tiebreak: the handle's (the kernel's mode 1).  MZS_OK after the launch, or a negative MZS_E_* with *err set.
-int stoch_wide_launch(bool tiebreak, int device, const StochWideParams& p, const WidePlan& pl, hipStream_t stream,
+// tiebreak: the handle's (the kernel's mode 1); root: p.obs set, root inference inside the launch.  MZS_OK after the
+// launch, or a negative MZS_E_* with *err set.
+int stoch_wide_launch(bool tiebreak, bool root, int device, const StochWideParams& p, const WidePlan& pl, hipStream_t stream,
                       std::string* err);
+
+// Root inference of the family on its own (mz_stoch_root_kernel): one wavefront per root, no LDS.  E, A <= 64, F <= 63.
+struct StochRootParams {
+  const float *obs, *repr_w, *repr_b;  // [B, obs_dim], [obs_dim, E], [E]
+  Mlp2 pv, pp;                         // the prediction heads in HBM
+  float *prior_logits, *value, *embedding;  // out [B, A], [B], [B, E]
+  int32_t B, obs_dim, E, A, F, support;
+};
+int stoch_root_launch(const StochRootParams& p, hipStream_t stream, std::string* err);
 
 }  // namespace mz

@@ -74,6 +74,26 @@ MZ_DEV float wave_min_max_normalize(float s, int E, int lane) {
   scale = scale < 1e-5f ? scale + 1e-5f : scale;
   return (s - mn) / scale;
 }
+// Representation (muax/nn.py:59-70) of one root: element k of the normalised state in lane k (lanes past E hold nothing
+// of use).  ob: the root's observation row [obs_dim]; repr_w [obs_dim][E], repr_b [E] in global memory, read once per
+// root.  An fma chain over the observation in index order from 0, the bias added last (oracle mzo_root_inference)
+MZ_DEV float wave_root_state(const float* ob, const float* repr_w, const float* repr_b, int obs_dim, int E, int lane) {
+  const int ec = lane < E ? lane : 0;
+  float acc = 0.0f;
+  int i = 0;
+  for (; i + 4 <= obs_dim; i += 4) {
+    float o4[4], w4[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      o4[q] = ob[i + q];
+      w4[q] = repr_w[(size_t)(i + q) * E + ec];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc = __builtin_fmaf(o4[q], w4[q], acc);
+  }
+  for (; i < obs_dim; ++i) acc = __builtin_fmaf(ob[i], repr_w[(size_t)i * E + ec], acc);
+  return wave_min_max_normalize(acc + repr_b[ec], E, lane);
+}
 // links [0, n) of a hidden layer's chain: input k in lane k of x, this lane's weights w[k * 16]
 MZ_DEV float wide_chain(float x, int n, const float* w) {
   float acc = 0.0f;

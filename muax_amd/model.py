@@ -72,7 +72,8 @@ class MuZero:
                  policy: Optional[str] = None, optimizer=None, loss_fn=None, discount: float = 0.99,
                  support_size: int = 10, recurrent_pred_on: str = "child", device=None,
                  representation_fn=None, capture_graph: bool = False, root_graph_cache: int = 2,
-                 stochastic_one_launch: bool = False, stochastic_fused_update: bool = False):
+                 stochastic_one_launch: bool = False, stochastic_fused_update: bool = False,
+                 stochastic_root_in_kernel: bool = False):
         self._stochastic = isinstance(network, SMZNetwork)
         if self._stochastic:
             if policy not in (None, "stochastic"):
@@ -100,7 +101,8 @@ class MuZero:
             self.dy_func = None
         else:
             self.repr_func, self.pred_func, self.dy_func = self.network
-        # of the last act(): "fused_host", "fused", "stepwise"; "hip_stochastic_mlp", "hip_stochastic_one_launch", "callables"
+        # of the last act(): "fused_host", "fused", "stepwise"; "hip_stochastic_mlp", "hip_stochastic_one_launch", their
+        # "..._root" twins (stochastic_root_in_kernel), "callables"
         self._last_route = None
         self._policy = policy_class()
         self._optimizer = optimizer
@@ -117,6 +119,9 @@ class MuZero:
         # default stochastic MLP family: the whole search in one launch wherever search.stochastic_plan admits the shape
         # (off by default: the two routes give the same bits, the speed is measured on one shape only -- README)
         self.stochastic_one_launch = bool(stochastic_one_launch)
+        # default stochastic MLP family on the library route: root inference by the library too (in the one launch, or
+        # one launch in front of the three-launch loop) instead of the torch modules (off by default: README)
+        self.stochastic_root_in_kernel = bool(stochastic_root_in_kernel)
         # default stochastic MLP family: update() takes loss and gradients from the fused training kernel
         # (loss.StochasticFusedLossGrad) instead of torch autograd (off by default: timed on two shapes only -- README)
         self.stochastic_fused_update = bool(stochastic_fused_update)
@@ -463,6 +468,12 @@ class MuZero:
     def _bind_stochastic(self, handle):
         w = {k: v.detach() for k, v in mz_nn.stochastic_mlp_weights(self.network).items()}
         handle.set_stochastic_mlp_weights(w, self._support_size, self._discount)
+        if self._stochastic_root_served(handle.cfg.embed_dim):
+            handle.set_stochastic_representation(*[t.detach() for t in mz_nn.stochastic_root_weights(self.network)])
+
+    def _stochastic_root_served(self, E):
+        """Whether the library route runs root inference itself: the flag, and an embedding a wavefront holds."""
+        return self.stochastic_root_in_kernel and E <= 64
 
     def _plan_stochastic(self, key, obs, num_simulations, temperature, invalid_actions, max_depth, qtransform,
                          dirichlet_fraction, dirichlet_alpha, pb_c_init, pb_c_base, dirichlet_noise, gumbel, tiebreak,
@@ -471,32 +482,40 @@ class MuZero:
         chance function evaluated by the library (the default stochastic MLP family on a GPU, support_size 8..31:
         MuZeroSearch.search_stochastic_mlp, as one launch with `stochastic_one_launch` where search.stochastic_plan admits
         the shape; MUAX_AMD_STOCHASTIC_MLP=0 switches the library route off) or, for plugin modules, by
-        StochasticMuZeroPolicy on callables built from them."""
+        StochasticMuZeroPolicy on callables built from them.  With `stochastic_root_in_kernel` the library route (embeddings
+        up to 64 wide) runs root inference too and no torch module is called: the widths come from the modules, the
+        observations go to search_stochastic_mlp(None, obs=...), the root value is the kernel's."""
         qt = getattr(qtransform, "__name__", qtransform)
         if qt not in (None, "qtransform_by_parent_and_siblings"):
             raise ValueError(f"qtransform {qt!r} is not implemented for this policy")
-        root = self._root_inference_eager(self._device_obs(obs))
-        B, A = root[0].shape
-        Cn = getattr(self.after_pred_func, "num_actions", None)
-        dirichlet_noise = self._root_noise(key, dirichlet_noise, dirichlet_fraction, dirichlet_alpha, obs, A, global_batch,
-                                           root_offset)
         hip = (mz_nn.is_default_stochastic_mlp(self.network) and self.device.type == "cuda"
                and 8 <= self._support_size <= 31 and os.environ.get("MUAX_AMD_STOCHASTIC_MLP", "1") != "0")
+        Cn = getattr(self.after_pred_func, "num_actions", None)
+        in_kernel = hip and obs.ndim == 2 and self._stochastic_root_served(self.repr_func.embedding_dim)
+        if in_kernel:
+            root, B, A, E = None, obs.shape[0], self.pred_func.num_actions, self.repr_func.embedding_dim
+        else:
+            root = self._root_inference_eager(self._device_obs(obs))
+            (B, A), E = root[0].shape, root[2].shape[1]
+        dirichlet_noise = self._root_noise(key, dirichlet_noise, dirichlet_fraction, dirichlet_alpha, obs, A, global_batch,
+                                           root_offset)
         if hip:
-            h = self._handle(B, (A, num_simulations, root[2].shape[1], max_depth, tiebreak, pb_c_init, float(pb_c_base),
+            h = self._handle(B, (A, num_simulations, E, max_depth, tiebreak, pb_c_init, float(pb_c_base),
                                  global_batch, root_offset, "stochastic", "qtransform_by_parent_and_siblings", 16, 1.0, Cn),
                              self._bind_stochastic)
-            one_launch = self.stochastic_one_launch and stochastic_plan(A, Cn, root[2].shape[1], self._support_size,
+            one_launch = self.stochastic_one_launch and stochastic_plan(A, Cn, E, self._support_size,
                                                                         num_simulations) is not None
             out = h.search_stochastic_mlp(root, key=key, invalid_actions=invalid_actions, dirichlet_noise=dirichlet_noise,
                                           dirichlet_fraction=dirichlet_fraction, temperature=temperature, gumbel=gumbel,
                                           with_tree=with_tree, graph=self.capture_graph, graph_version=self._weights_version,
-                                          one_launch=one_launch)
+                                          one_launch=one_launch, obs=self._device_obs(obs) if in_kernel else None)
             t = out.search_tree
             if t is not None:  # the decision slice, as StochasticMuZeroPolicy returns it (mctx _mask_tree)
                 t = t._replace(**{f: getattr(t, f)[..., :A] for f in t._fields if f.startswith("children_")})
-            return (PolicyOutput(out.action, out.action_weights, t), root[1], None,
-                    "hip_stochastic_one_launch" if one_launch else "hip_stochastic_mlp")
+            route = "hip_stochastic_one_launch" if one_launch else "hip_stochastic_mlp"
+            if in_kernel:  # (action, weights and root value then share the handle's one output allocation)
+                return PolicyOutput(out.action, out.action_weights, t), h.root_value, h, route + "_root"
+            return PolicyOutput(out.action, out.action_weights, t), root[1], None, route
         shapes = {} if Cn is None else dict(num_chance_outcomes=Cn, afterstate_shape=tuple(root[2].shape[1:]))
         out = self._policy(self._params, key, root, decision_recurrent_fn=self._decision_inference,
                            chance_recurrent_fn=self._chance_inference, num_simulations=num_simulations,

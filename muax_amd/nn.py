@@ -295,6 +295,16 @@ def stochastic_mlp_weights(network: SMZNetwork) -> dict:
     return {f"{h}_{n}{i + 1}": getattr(m[i], n) for h, m in heads.items() for i in (0, 1) for n in ("w", "b")}
 
 
+def stochastic_root_weights(network: SMZNetwork) -> tuple:
+    """(repr_w [obs_dim, embedding_dim], repr_b [embedding_dim]) of the family's Representation, haiku layout: what
+    mzs_mlp_set_stochastic_representation (MuZeroSearch.set_stochastic_representation) takes.  The module must have
+    seen an observation (MuZero.init) or been made with obs_dim."""
+    r = network[0]
+    if r.repr_func is None:
+        raise ValueError("the Representation has no weights yet: call MuZero.init() or give it obs_dim")
+    return r.repr_func.w, r.repr_func.b
+
+
 def stochastic_train_weights(network: SMZNetwork) -> dict:
     """All 34 arrays of the family in the order of mzs_stochastic_train_weights: the representation's two, the 28 above,
     the encoder's four."""

@@ -174,6 +174,7 @@ class MuZeroSearch:
         self._h = h
         self._weights = None
         self._stochastic_weights = self._stochastic_out = None  # set_stochastic_mlp_weights; its recurrent step's outputs
+        self._stochastic_repr = self._stochastic_root = None  # set_stochastic_representation; stochastic_mlp_root's outputs
         B, A = self.batch, cfg.num_actions
         with torch.cuda.device(self.device):
             # action | action_weights | root_value in ONE allocation: a NumPy caller gets them with one copy
@@ -615,6 +616,41 @@ class MuZeroSearch:
         _lib.check(self._L.mzs_mlp_set_stochastic_weights(self._h, C.byref(w)), self._h)
         self._stochastic_weights = keep  # keep the device buffers alive
 
+    def set_stochastic_representation(self, repr_w, repr_b):
+        """The default Representation's weights (nn.stochastic_root_weights: repr_w [obs_dim, embed_dim], repr_b
+        [embed_dim], haiku layout) for the library's own root inference: stochastic_mlp_root and
+        search_stochastic_mlp(None, obs=...).  obs_dim is repr_w's first dimension."""
+        E = self.cfg.embed_dim
+        w = torch.as_tensor(repr_w, device=self.device)
+        if w.ndim != 2 or w.shape[0] < 1:
+            raise ValueError(f"repr_w: expected shape (obs_dim >= 1, {E}), got {tuple(w.shape)}")
+        keep = (self._f32(w, (w.shape[0], E), "repr_w"), self._f32(repr_b, (E,), "repr_b"))
+        _lib.check(self._L.mzs_mlp_set_stochastic_representation(self._h, int(w.shape[0]), _ptr(keep[0]), _ptr(keep[1])), self._h)
+        self._stochastic_repr = keep  # keep the device buffers alive
+
+    def _stochastic_obs(self, obs):
+        if self._stochastic_weights is None:
+            raise ValueError("set_stochastic_mlp_weights() first")
+        if self._stochastic_repr is None:
+            raise ValueError("set_stochastic_representation() first")
+        return self._f32(obs, (self.batch, self._stochastic_repr[0].shape[0]), "obs")
+
+    def stochastic_mlp_root(self, obs):
+        """Root inference of the bound default family on obs [B, obs_dim] in ONE launch (mzs_mlp_stochastic_root), no torch
+        module -> (prior_logits [B, A], value [B], embedding [B, embed_dim]): RootFnOutput in persistent buffers of the
+        handle (value is `root_value`), overwritten by the next call."""
+        obs = self._stochastic_obs(obs)
+        if self._stochastic_root is None:
+            B, A, E = self.batch, self.cfg.num_actions, self.cfg.embed_dim
+            with torch.cuda.device(self.device):
+                self._stochastic_root = (torch.empty(B, A, dtype=torch.float32, device=self.device),
+                                         torch.empty(B, E, dtype=torch.float32, device=self.device))
+        logits, emb = self._stochastic_root
+        _lib.check(self._L.mzs_mlp_stochastic_root(self._h, _ptr(obs), _ptr(logits), _ptr(self.root_value), _ptr(emb),
+                                                   self._stream()), self._h)
+        self._keep = (obs,)
+        return logits, self.root_value, emb
+
     def stochastic_mlp_recurrent(self, slot, parent_is_decision, parent_embedding):
         """The decision or the chance function of the bound default family for every root, by its parent's kind, in ONE
         launch (mzs_mlp_stochastic_recurrent) -> the MzsStochasticOutputs block of the handle's persistent output arrays,
@@ -654,16 +690,21 @@ class MuZeroSearch:
         return self.finish_stochastic(temperature, gumbel, with_tree)
 
     def _search_stochastic_one_launch(self, root_fn_output, gkey, key, invalid_actions, dirichlet_noise, dirichlet_fraction,
-                                      temperature, gumbel, with_tree, graph, graph_version) -> PolicyOutput:
-        """The whole search as ONE launch (mzs_mlp_stochastic_search).  graph: that launch captured as a one-node graph
-        per (gkey, which optional inputs are there, with_tree, graph_version) -- the inputs then travel through persistent
-        buffers and key, temperature and dirichlet_fraction through the entry's device block, so a replay sees this
-        call's values."""
+                                      temperature, gumbel, with_tree, graph, graph_version, obs=None) -> PolicyOutput:
+        """The whole search as ONE launch (mzs_mlp_stochastic_search; with `obs` instead of root_fn_output
+        mzs_mlp_stochastic_search_obs: root inference inside it, the root's value into `root_value`).  graph: that launch
+        captured as a one-node graph per (gkey, which optional inputs are there, with_tree, graph_version) -- the inputs
+        then travel through persistent buffers and key, temperature and dirichlet_fraction through the entry's device
+        block, so a replay sees this call's values."""
         B, A, S = self.batch, self.cfg.num_actions, self.cfg.num_simulations
-        prior_logits, value, embedding = root_fn_output
-        ins = dict(prior_logits=self._f32(prior_logits, (B, A), "prior_logits"), value=self._f32(value, (B,), "value"),
-                   embedding=self._f32(torch.as_tensor(embedding, device=self.device).reshape(B, -1), (B, self._es), "embedding"),
-                   invalid_actions=self._u8(invalid_actions, (B, A), "invalid_actions"),
+        if obs is not None:
+            ins = dict(obs=self._stochastic_obs(obs))
+        else:
+            prior_logits, value, embedding = root_fn_output
+            ins = dict(prior_logits=self._f32(prior_logits, (B, A), "prior_logits"), value=self._f32(value, (B,), "value"),
+                       embedding=self._f32(torch.as_tensor(embedding, device=self.device).reshape(B, -1), (B, self._es),
+                                           "embedding"))
+        ins.update(invalid_actions=self._u8(invalid_actions, (B, A), "invalid_actions"),
                    dirichlet_noise=self._f32(dirichlet_noise, (B, A), "dirichlet_noise"),
                    gumbel=self._f32(gumbel, (B, A), "gumbel"))
         fraction = dirichlet_fraction if ins["dirichlet_noise"] is not None else 0.0
@@ -674,14 +715,18 @@ class MuZeroSearch:
                           temperature=temperature, device_block=None if block is None else block.data_ptr(),
                           action=self.action.data_ptr(), action_weights=self.action_weights.data_ptr(),
                           search_value=self.search_value.data_ptr(), depth_sum=self.depth_sum.data_ptr(),
-                          **{n: None if t is None else t.data_ptr() for n, t in tensors.items()})
-            _lib.check(self._L.mzs_mlp_stochastic_search(self._h, C.byref(a), self._stream()), self._h)
+                          **{n: None if t is None else t.data_ptr() for n, t in tensors.items() if n != "obs"})
+            if obs is None:
+                _lib.check(self._L.mzs_mlp_stochastic_search(self._h, C.byref(a), self._stream()), self._h)
+            else:
+                _lib.check(self._L.mzs_mlp_stochastic_search_obs(self._h, C.byref(a), _ptr(tensors["obs"]), _ptr(self.root_value),
+                                                                 self._stream()), self._h)
 
         if not graph:
             launch(ins, None)
             self._keep = tuple(ins.values())
         else:
-            gk = (gkey, "one_launch", tuple(t is not None for t in ins.values()), bool(with_tree))
+            gk = (gkey, "one_launch", tuple(t is not None for t in ins.values()), bool(with_tree)) + (("obs",) if obs is not None else ())
             entry = self._graphs.get(gk)
             if entry is not None and entry[3] != graph_version:
                 entry = None
@@ -712,13 +757,13 @@ class MuZeroSearch:
                 g = torch.cuda.CUDAGraph()
                 with capture(g):
                     launch(bufs, block)
-                entry = self._graphs[gk] = (g, stage, self._stochastic_weights, graph_version)
+                entry = self._graphs[gk] = (g, stage, (self._stochastic_weights, self._stochastic_repr), graph_version)
             entry[0].replay()
         return PolicyOutput(self.action, self.action_weights, self._export_tree() if with_tree else None)
 
-    def search_stochastic_mlp(self, root_fn_output, key=0, invalid_actions=None, dirichlet_noise=None, dirichlet_fraction=0.25,
+    def search_stochastic_mlp(self, root_fn_output=None, key=0, invalid_actions=None, dirichlet_noise=None, dirichlet_fraction=0.25,
                               temperature=1.0, gumbel=None, with_tree=False, graph=False, graph_key=None,
-                              graph_version=0, one_launch=False) -> PolicyOutput:
+                              graph_version=0, one_launch=False, obs=None) -> PolicyOutput:
         """search_stochastic with the two callables replaced by the library's own evaluation of the default stochastic MLP
         family (set_stochastic_mlp_weights): three launches per simulation -- select, the function of each root's parent
         kind, expand + backward -- and no torch op.  Arguments as search_stochastic; the kernel reads the bound weight
@@ -726,13 +771,25 @@ class MuZeroSearch:
 
         one_launch=True: root set-up, every simulation and the finish in ONE launch with the tree in LDS
         (mzs_mlp_stochastic_search) -- the same arguments, the same return value, the same bits; a captured graph is one
-        kernel node.  A shape `stochastic_plan` declines is then a ValueError naming the limit."""
+        kernel node.  A shape `stochastic_plan` declines is then a ValueError naming the limit.
+
+        `obs` [B, obs_dim] INSTEAD of root_fn_output (pass None for it): root inference by the library as well
+        (set_stochastic_representation; embed_dim <= 64) -- inside the one launch with one_launch=True
+        (mzs_mlp_stochastic_search_obs), else one more launch in front of the loop (stochastic_mlp_root).  The root's
+        network value is then in `root_value`.  graph=True as before: a captured launch reads `obs` from a persistent
+        buffer, a replay sees the call's own observations."""
+        if (root_fn_output is None) == (obs is None):
+            raise ValueError("search_stochastic_mlp takes either root_fn_output or obs=, not both and not neither")
         if self._stochastic_weights is None:
             raise ValueError("set_stochastic_mlp_weights() first")
+        if obs is not None and self._stochastic_repr is None:
+            raise ValueError("set_stochastic_representation() first")
         if one_launch:
             return self._search_stochastic_one_launch(root_fn_output, graph_key if graph_key is not None else "stochastic_mlp",
                                                       key, invalid_actions, dirichlet_noise, dirichlet_fraction, temperature,
-                                                      gumbel, with_tree, graph, graph_version)
+                                                      gumbel, with_tree, graph, graph_version, obs)
+        if obs is not None:
+            root_fn_output = self.stochastic_mlp_root(obs)
 
         def recurrent_expand(sim, slot, kind, pemb):
             self.expand_backup_stochastic_outputs(sim, self.stochastic_mlp_recurrent(slot, kind, pemb))

@@ -17,6 +17,13 @@ whole update() (MuZero(stochastic_fused_update=True) under backend="hip" against
 alternating in one process after warm_runtime().  Host wall time around a synchronised call, in microseconds: the
 torch route is launch-bound, so its figure is mostly host time and moves with the load of the machine; median, min
 and max over `--repeats` (at least 15).
+
+--act: the whole MuZero.act() of the default family on device observations at 2048's shape (4 actions + 32 outcomes,
+E = 16, support 10, obs_dim 16, `--sims` simulations, root noise drawn from the key, device outputs) at 64, 1024 and
+4096 roots, on the one-launch route with the root inference on the torch modules (stochastic_root_in_kernel=False) and
+inside the launch (True): two models of the same weights alternating in one process after warm_runtime() and five
+warm-up acts each.  A sample is the host wall time around ten consecutive acts and one synchronisation, per act, in
+microseconds (the torch root is launch-bound: its cost is host time); median, min and max over `--repeats` (at least 15).
 """
 import argparse
 import json
@@ -182,6 +189,49 @@ def main_train(args):
             json.dump(rows, f, indent=1)
 
 
+def main_act(args):
+    import numpy as np
+
+    import muax_amd as mx
+    from muax_amd.utils import warm_runtime
+    warm_runtime()
+    repeats, inner, od, e = max(15, args.repeats), 10, 16, 16
+    routes = {False: "hip_stochastic_one_launch", True: "hip_stochastic_one_launch_root"}
+    rows = []
+    for batch in (64, 1024, 4096):
+        obs = torch.rand(batch, od, generator=torch.Generator().manual_seed(batch)).cuda()
+        models = {}
+        for flag in routes:
+            net = mx.create_stochastic_muzero_network(e, A, C, 21, generator=torch.Generator().manual_seed(1))
+            m = models[flag] = mx.MuZero(net, policy="stochastic", stochastic_one_launch=True, stochastic_root_in_kernel=flag)
+            m.init(0, np.zeros((1, od), np.float32))
+
+        def acts(m, n):
+            for i in range(n):
+                m.act([7, i], obs, with_pi=True, with_value=True, obs_from_batch=True, num_simulations=args.sims,
+                      device_outputs=True)
+        for flag, m in models.items():
+            acts(m, 5)
+            assert m._last_route == routes[flag], m._last_route
+        t = {flag: [] for flag in routes}
+        for _ in range(repeats):  # alternating
+            for flag, m in models.items():
+                t[flag].append(wall(lambda: acts(m, inner)) / inner)
+        a = {flag: m.act([7, 0], obs, obs_from_batch=True, num_simulations=args.sims, device_outputs=True)
+             for flag, m in models.items()}
+        row = {"roots": batch, "sims": args.sims, "repeats": repeats, "acts_per_sample": inner,
+               "same_actions": round(float((a[False] == a[True]).float().mean()), 4)}
+        for flag, name in ((False, "torch_root"), (True, "root_in_kernel")):
+            v = t[flag]
+            row[name] = {"median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1)}
+        row["torch_root_over_in_kernel_median"] = round(row["torch_root"]["median_us"] / row["root_in_kernel"]["median_us"], 2)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sims", type=int, default=50)
@@ -189,7 +239,10 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--mlp", action="store_true")
     ap.add_argument("--train", action="store_true")
+    ap.add_argument("--act", action="store_true")
     args = ap.parse_args()
+    if args.act:
+        return main_act(args)
     if args.train:
         return main_train(args)
     if args.mlp:
