@@ -16,7 +16,11 @@ iteration's stream comes down once, is cut into finished episodes (`episode_traj
 Nothing here has been run to a result: whether this recipe learns 2048 is not known.
 
     python examples/fit_2048_stochastic.py [--envs 256] [--steps 64] [--iterations 3] [--updates 20] [--one-launch]
-                                           [--root-in-kernel] [--fused-update] [--host-buffer]
+                                           [--root-in-kernel] [--fused-update] [--priority-steps K] [--host-buffer]
+
+--priority-steps K (the device route): after every update() the value errors of the first K transitions of every sampled
+window are written back as priorities (`fit_vector(priority_update=True, priority_steps=K)`), from
+`MuZero(stochastic_unroll_values=True).unroll_values`: one launch for this family.
 """
 import argparse
 import functools
@@ -105,7 +109,7 @@ def fit_on_device(model, venv, args, discount, k_steps):
                     steps_per_iteration=args.steps, num_simulations=args.sims, k_steps=k_steps, num_trajectory=32,
                     num_update_per_iteration=args.updates, test_interval=max(args.iterations, 1), random_seed=args.seed,
                     trajectory_weight="sum", metrics=_Report(model, buffer, 2 ** args.reward_shift), device_collect=True,
-                    device_plan=True)
+                    device_plan=True, priority_update=args.priority_steps is not None, priority_steps=args.priority_steps)
 
 
 def main():
@@ -125,6 +129,10 @@ def main():
                          "module in an act(); with --one-launch an act() is one launch")
     ap.add_argument("--fused-update", action="store_true",
                     help="update() on the fused training kernel (MuZero(stochastic_fused_update=True)) instead of autograd")
+    ap.add_argument("--priority-steps", type=int, default=None, metavar="K",
+                    help="write the value errors of the first K transitions of every window back as priorities "
+                         "(MuZero(stochastic_unroll_values=True), fit_vector(priority_update=True, priority_steps=K)); "
+                         "the device route only")
     ap.add_argument("--host-buffer", action="store_true",
                     help="this file's own loop on a host TrajectoryReplayBuffer instead of fit_vector on the device buffer")
     ap.add_argument("--test-envs", type=int, default=16, help="greedy test episodes after the first iteration (fit_vector)")
@@ -135,7 +143,10 @@ def main():
     net = muax.create_stochastic_muzero_network(E, venv.num_actions, Cn, 2 * support_size + 1)
     model = muax.MuZero(net, policy="stochastic", discount=discount, support_size=support_size,
                         optimizer=muax.optimizers.create_optimizer("adam", 2e-3), stochastic_one_launch=args.one_launch,
-                        stochastic_fused_update=args.fused_update, stochastic_root_in_kernel=args.root_in_kernel)
+                        stochastic_fused_update=args.fused_update, stochastic_root_in_kernel=args.root_in_kernel,
+                        stochastic_unroll_values=args.priority_steps is not None)
+    if args.priority_steps is not None and args.host_buffer:
+        ap.error("--priority-steps needs the device route (fit_vector on a DeviceReplayBuffer), not --host-buffer")
     if not args.host_buffer:
         fit_on_device(model, venv, args, discount, k_steps)
         return

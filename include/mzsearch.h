@@ -473,7 +473,7 @@ int mzs_mlp_loss_grad_weighted(const mzs_mlp_weights *w, const mzs_train_args *a
  * LDS ("too large for the LDS", the limit named) (MZS_E_UNSUPPORTED). */
 typedef struct mzs_stochastic_train_weights {
   int32_t struct_size;        /* = sizeof(mzs_stochastic_train_weights) */
-  int32_t obs_dim;            /* 1 .. 32 */
+  int32_t obs_dim;            /* 1 .. 32 (the training entry's limit; mzs_stochastic_mlp_unroll_values: 1 .. 128) */
   int32_t support_size;       /* 8 .. 31 */
   int32_t reserved0;
   const float *repr_w, *repr_b;               /* representation      [obs_dim,E] [E] */
@@ -1193,6 +1193,47 @@ typedef struct mzs_unroll_args {
   float *prio;              /* out [B, kp] or NULL */
 } mzs_unroll_args;
 int mzs_mlp_unroll_values(const mzs_mlp_weights *w, const mzs_unroll_args *a, void *stream);
+
+/* ---- the same unroll of the default stochastic MLP family (mz_stoch_unroll_kernel, muax_amd/csrc/mz_unroll.cuh) ----
+ * For every window j < batch and step i < k_prio, with s_0 = Representation(obs[j][0]):
+ *   values[j][i] = support_to_scalar(softmax(value head pv(s_i)))     prio[j][i] = |values[j][i] - returns[j][i]|
+ * and, while i + 1 < k_prio,
+ *   after_i = min_max(ad([s_i | onehot(actions[j][i], A)]))           the afterstate dynamics
+ *   c_{i+1} = argmax_k en(obs[j][i+1])[k]                             the chance encoder on the raw observation row,
+ *                                                                     the lowest index among equal maxima
+ *   s_{i+1} = min_max(cn([after_i | onehot(c_{i+1}, C)]))             the chance dynamics' next state, an exact one-hot
+ * -- the chain and the code rule of mzs_stochastic_mlp_loss_grad.  codes[j][0] = -1 (step 0 has no transition),
+ * codes[j][i] = c_i behind it.  One launch, one wavefront per window; the afterstate value, the chance logits, the
+ * policy head and the reward head are not evaluated.  The arithmetic is the spec's ("MZ-F32"): values has the bits of the
+ * oracle's inference chain for any widths, prio is one fp32 subtraction with the sign cleared.  No atomics: the same
+ * bits on every run.  No allocation, no synchronisation, no copy to the host; capturable.  obs rows, `actions` and
+ * `returns` are read with the row stride row_steps, of which the first k_prio are used; an action outside
+ * 0..num_actions - 1 is the all-zero one-hot (nothing is indexed by it).
+ * The weights are the 34 arrays of mzs_stochastic_train_weights; of its scalar fields this entry reads obs_dim, here
+ * 1..128 (the 1..32 of that struct's comment is the training entry's own limit), and support_size.
+ * Limits, checked before the device is selected, the message naming the entry and the limit: MZS_E_UNSUPPORTED for
+ * obs_dim outside 1..128, embed_dim outside 1..64, num_actions < 1, num_chance_outcomes < 1,
+ * num_actions + num_chance_outcomes > 64, support_size outside 8..31; MZS_E_INVALID for struct sizes, a null weight /
+ * input pointer, batch < 1, k_prio outside 1..row_steps, values, prio and codes all NULL.
+ * errors: mzs_last_error(NULL) */
+typedef struct mzs_stochastic_unroll_args {
+  int32_t struct_size;          /* = sizeof(mzs_stochastic_unroll_args) */
+  int32_t device;
+  int32_t batch;                /* B windows */
+  int32_t row_steps;            /* L: row stride of obs rows, actions and returns */
+  int32_t k_prio;               /* kp <= L steps evaluated */
+  int32_t num_actions;          /* A */
+  int32_t num_chance_outcomes;  /* C */
+  int32_t embed_dim;            /* E */
+  const float *obs;             /* [B, L, obs_dim] */
+  const int32_t *actions;       /* [B, L] */
+  const float *returns;         /* [B, L] */
+  float *values;                /* out [B, kp] or NULL */
+  float *prio;                  /* out [B, kp] or NULL */
+  int32_t *codes;               /* out [B, kp] or NULL */
+} mzs_stochastic_unroll_args;
+int mzs_stochastic_mlp_unroll_values(const mzs_stochastic_train_weights *w, const mzs_stochastic_unroll_args *a,
+                                     void *stream);
 
 #ifdef __cplusplus
 }

@@ -274,6 +274,13 @@ class MzsUnrollArgs(C.Structure):
                 + [(n, _vp) for n in ("obs", "actions", "returns", "values", "prio")])
 
 
+class MzsStochasticUnrollArgs(C.Structure):
+    _fields_ = ([("struct_size", C.c_int32), ("device", C.c_int32), ("batch", C.c_int32), ("row_steps", C.c_int32),
+                 ("k_prio", C.c_int32), ("num_actions", C.c_int32), ("num_chance_outcomes", C.c_int32),
+                 ("embed_dim", C.c_int32)]
+                + [(n, _vp) for n in ("obs", "actions", "returns", "values", "prio", "codes")])
+
+
 def args(cls, **fields):
     """A `cls` argument struct with `struct_size` set and the given fields assigned (a tuple fills an array field)."""
     a = cls()
@@ -321,6 +328,7 @@ STRUCTS = {
     "mzs_env_classic": MzsEnvClassic,
     "mzs_env_2048": MzsEnv2048,
     "mzs_unroll_args": MzsUnrollArgs,
+    "mzs_stochastic_unroll_args": MzsStochasticUnrollArgs,
 }
 
 _P, _i32, _i64, _f32 = C.POINTER, C.c_int32, C.c_int64, C.c_float
@@ -426,6 +434,8 @@ ENTRIES = {
     "mzs_env_2048_mask": (C.c_int, [_i32, _vp, _vp, _i32, _vp]),
     # forward value unroll of the default MLP trio
     "mzs_mlp_unroll_values": (C.c_int, [_P(MzsMlpWeights), _P(MzsUnrollArgs), _vp]),
+    # ... and of the default stochastic MLP family
+    "mzs_stochastic_mlp_unroll_values": (C.c_int, [_P(MzsStochasticTrainWeights), _P(MzsStochasticUnrollArgs), _vp]),
 }
 EXPORTED_SYMBOLS = list(ENTRIES)
 

@@ -73,7 +73,7 @@ class MuZero:
                  support_size: int = 10, recurrent_pred_on: str = "child", device=None,
                  representation_fn=None, capture_graph: bool = False, root_graph_cache: int = 2,
                  stochastic_one_launch: bool = False, stochastic_fused_update: bool = False,
-                 stochastic_root_in_kernel: bool = False):
+                 stochastic_root_in_kernel: bool = False, stochastic_unroll_values: bool = False):
         self._stochastic = isinstance(network, SMZNetwork)
         if self._stochastic:
             if policy not in (None, "stochastic"):
@@ -125,6 +125,10 @@ class MuZero:
         # default stochastic MLP family: update() takes loss and gradients from the fused training kernel
         # (loss.StochasticFusedLossGrad) instead of torch autograd (off by default: timed on two shapes only -- README)
         self.stochastic_fused_update = bool(stochastic_fused_update)
+        # an SMZNetwork: unroll_values() unrolls through the afterstate and chance dynamics, the codes from the encoder --
+        # one launch for the default stochastic MLP family (unroll.StochasticFusedUnrollValues), else the modules; with it
+        # fit_vector takes priority_steps (off by default: unroll_values() then raises NotImplementedError as before -- README)
+        self.stochastic_unroll_values = bool(stochastic_unroll_values)
         self._last_update_route = None  # of the last update(): "hip_stochastic_fused", "hip_fused", "torch"
         # captured root-inference graphs kept per weights version (one per observation shape; each pins its static
         # input and a private memory pool: hundreds of MB for Atari-shaped batches -- INTEGRATION.md)
@@ -747,6 +751,12 @@ class MuZero:
         for every step of a window, `DeviceReplayBuffer.sample(all_obs=True)`."""
         return self._stochastic
 
+    @property
+    def unrolls_stochastic(self):
+        """Whether unroll_values() unrolls this model's SMZNetwork (made with `stochastic_unroll_values=True`): what
+        `fit_vector(priority_update=True, priority_steps=)` asks of a model that trains stochastically."""
+        return self._stochastic and self.stochastic_unroll_values
+
     def unroll_values(self, batch, k_prio=None, backend: str = "auto"):
         """The forward unroll of a sampled batch with the CURRENT network: `(values, priorities)`, both [B, kp] float32
         on the model's device, with v_i = value(s_i), s_0 = repr(obs[:, 0]), s_{i+1} = dynamics(s_i, a[:, i]) and
@@ -755,15 +765,31 @@ class MuZero:
         (mzs_mlp_unroll_values, muax_amd/csrc/mz_unroll.cuh) for the default MLP trio on a GPU, obs_dim 1..128,
         embedding 1..64, 1..64 actions, support_size 8..31; values then have the bits of act()'s root value.  "torch": the
         model's modules under no_grad, any nets, any device.  "auto": the kernel where it applies, else torch.  No
-        synchronisation either way."""
+        synchronisation either way.
+        An SMZNetwork raises NotImplementedError unless the model was made with `stochastic_unroll_values=True`
+        (`unrolls_stochastic`).  Then s_{i+1} = the next state of chance_dynamic(afterstate_dynamic(s_i, a[:, i]), c_{i+1})
+        with c_{i+1} the encoder's argmax code of obs[:, i + 1], so `batch.obs` must be [B, L, obs_dim], an observation
+        for every step (a ValueError otherwise).  "hip": ONE launch (mzs_stochastic_mlp_unroll_values, mz_unroll.cuh) for
+        the default stochastic MLP family on a GPU, obs_dim 1..128, embedding 1..64, actions + chance outcomes up to 64,
+        support_size 8..31; "torch" and "auto" as above."""
         from . import unroll as mz_unroll
         if backend not in ("auto", "hip", "torch"):
             raise ValueError(f"backend must be 'auto', 'hip' or 'torch', got {backend!r}")
         if self._params is None:
             raise ValueError("call init() first")
-        if self._stochastic:
+        if self._stochastic and not self.stochastic_unroll_values:
             raise NotImplementedError("unroll_values is not built for an SMZNetwork (its unroll needs every step's chance code)")
-        _, _, kp = mz_unroll.batch_window(batch, k_prio)
+        B, L, kp = mz_unroll.batch_window(batch, k_prio)
+        if self._stochastic:
+            mz_unroll.check_every_observation(tuple(np.shape(batch.obs)), B, L)  # (before anything runs)
+            family = self.device.type == "cuda" and mz_nn.is_default_stochastic_mlp(self.network)
+            if backend == "hip" and not family:
+                raise ValueError("backend='hip' needs the default stochastic MLP family on a GPU")
+            if backend == "torch" or not family or (backend == "auto" and not mz_unroll.within_stochastic_limits(self)):
+                return mz_unroll.torch_stochastic_unroll_values(self, batch, kp)
+            if self._fused_unroll is None:
+                self._fused_unroll = mz_unroll.StochasticFusedUnrollValues(self)
+            return self._fused_unroll(batch, kp)  # (backend="hip" beyond the limits: the library's error, the limit named)
         trio = self.device.type == "cuda" and mz_nn.is_default_mlp_trio(self.network)
         if backend == "hip" and not trio:
             raise ValueError("backend='hip' needs the default MLP trio on a GPU")

@@ -534,8 +534,9 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     `TrajectoryReplayBuffer` returns every row anyway and is left alone.  True / False force it; True with a buffer
     whose `sample` takes no `all_obs` is a ValueError.  So a stochastic model trains through this loop on a
     `DeviceReplayBuffer` and a device environment, with `reanalyse_every`, `priority_update` and `is_beta` as for the
-    deterministic model; `priority_steps` with such a model is a ValueError (`MuZero.unroll_values` unrolls the
-    deterministic dynamics and is not built for an `SMZNetwork`).  For any other model None changes nothing."""
+    deterministic model; `priority_steps` with such a model is a ValueError unless the model unrolls its `SMZNetwork`
+    (`MuZero(..., stochastic_unroll_values=True)`, `MuZero.unrolls_stochastic`: the afterstate and chance dynamics with
+    the encoder's codes, from the observations `all_obs` hands out).  For any other model None changes nothing."""
     if priority_steps is not None and int(priority_steps) < 1:
         raise ValueError("priority_steps must be None or >= 1")
     if trajectory_weight not in ("mean", "sum"):
@@ -562,7 +563,7 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                          f"{type(buffer).__name__}.sample does not")
     all_obs = (stochastic and "all_obs" in sample_takes) if all_obs is None else bool(all_obs)
     prioritise = bool(priority_update) and hasattr(buffer, "update_priorities")
-    if prioritise and priority_steps is not None and stochastic:
+    if prioritise and priority_steps is not None and stochastic and not getattr(model, "unrolls_stochastic", False):
         raise ValueError("fit_vector: priority_update with priority_steps needs MuZero.unroll_values, which is not built "
                          "for an SMZNetwork (a stochastic model); use priority_steps=None (value_priorities)")
     on_device = hasattr(venv, "step_device")

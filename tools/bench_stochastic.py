@@ -24,6 +24,13 @@ E = 16, support 10, obs_dim 16, `--sims` simulations, root noise drawn from the 
 inside the launch (True): two models of the same weights alternating in one process after warm_runtime() and five
 warm-up acts each.  A sample is the host wall time around ten consecutive acts and one synchronisation, per act, in
 microseconds (the torch root is launch-bound: its cost is host time); median, min and max over `--repeats` (at least 15).
+
+--unroll: the value priorities of the default family at (A, C, E, support) = (4, 32, 16, 10), obs_dim 16, for 32 and 4096
+windows of 10 steps: MuZero(stochastic_unroll_values=True).unroll_values on the kernel route (backend="hip", one launch)
+and on the torch modules (backend="torch"), and beside them vector.value_priorities, the ONE priority per window that
+fit_vector writes back with priority_steps=None -- the three alternating in one process after warm_runtime() and ten
+warm-up calls each.  A sample is the host wall time around ten consecutive calls and one synchronisation, per call, in
+microseconds; median, min and max over `--repeats` (at least 15).
 """
 import argparse
 import json
@@ -232,6 +239,50 @@ def main_act(args):
             json.dump(rows, f, indent=1)
 
 
+def main_unroll(args):
+    import numpy as np
+
+    import muax_amd as mx
+    from muax_amd.utils import warm_runtime
+    from muax_amd.vector import value_priorities
+    warm_runtime()
+    repeats, inner, od, e, support, L = max(15, args.repeats), 10, 16, 16, 10, 10
+    rows = []
+    for batch in (32, 4096):
+        rng = np.random.default_rng(batch)
+        b = mx.Transition(obs=torch.from_numpy(rng.uniform(0, 1, (batch, L, od)).astype(np.float32)).cuda(),
+                          a=torch.from_numpy(rng.integers(0, A, (batch, L)).astype(np.int32)).cuda(),
+                          r=torch.from_numpy(rng.uniform(-1, 2, (batch, L)).astype(np.float32)).cuda(),
+                          Rn=torch.from_numpy(rng.uniform(-5, 9, (batch, L)).astype(np.float32)).cuda(),
+                          pi=torch.from_numpy(rng.dirichlet(np.ones(A), (batch, L)).astype(np.float32)).cuda())
+        net = mx.create_stochastic_muzero_network(e, A, C, 2 * support + 1, generator=torch.Generator().manual_seed(1))
+        m = mx.MuZero(net, policy="stochastic", support_size=support, stochastic_unroll_values=True)
+        m.init(0, np.zeros((1, od), np.float32))
+        calls = {"kernel": lambda: m.unroll_values(b, backend="hip"), "torch": lambda: m.unroll_values(b, backend="torch"),
+                 "one_priority_torch": lambda: value_priorities(m, b)}  # (fit_vector's step with priority_steps=None)
+
+        def many(fn):
+            for _ in range(inner):
+                fn()
+        for fn in calls.values():
+            many(fn)
+        t = {k: [] for k in calls}
+        for _ in range(repeats):  # alternating
+            for k, fn in calls.items():
+                t[k].append(wall(lambda: many(fn)) / inner)
+        pk, pt = calls["kernel"]()[1], calls["torch"]()[1]
+        row = {"A": A, "C": C, "E": e, "F": 2 * support + 1, "obs_dim": od, "windows": batch, "k_prio": L, "repeats": repeats,
+               "calls_per_sample": inner, "kernel_against_torch_of_largest": float((pk - pt).abs().max() / pt.max())}
+        for k, v in t.items():
+            row[k] = {"median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1)}
+        row["torch_over_kernel_median"] = round(row["torch"]["median_us"] / row["kernel"]["median_us"], 2)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sims", type=int, default=50)
@@ -240,7 +291,10 @@ def main():
     ap.add_argument("--mlp", action="store_true")
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--act", action="store_true")
+    ap.add_argument("--unroll", action="store_true")
     args = ap.parse_args()
+    if args.unroll:
+        return main_unroll(args)
     if args.act:
         return main_act(args)
     if args.train:
