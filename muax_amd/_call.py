@@ -1,6 +1,7 @@
-"""The torch side of a call into libmzsearch.so, stated once: which device, which stream, how an argument struct is
-launched, how a loop of such calls is captured into a graph, and the weight struct of the default MLP trio.  (`_lib`
-itself stays free of torch.)"""
+"""The torch side of a call into libmzsearch.so, stated once: which device, which stream, what a kernel reads in
+place, how an argument struct is launched, how a loop of such calls is captured into a graph, the weight struct of the
+default MLP trio, and the base of the per-model objects that keep one (`FusedCall`).  (`_lib` itself stays free of
+torch.)"""
 from __future__ import annotations
 
 import contextlib
@@ -26,6 +27,14 @@ if _raw is not None:
 else:
     def raw_stream(dev_index: int) -> C.c_void_p:
         return C.c_void_p(torch.cuda.current_stream(dev_index).cuda_stream)
+
+
+def as_device(x, dtype, device) -> torch.Tensor:
+    """`x` as a contiguous tensor of `dtype` on `device`; one that already is all of that passes through untouched (the
+    kernel reads the caller's own storage)."""
+    if isinstance(x, torch.Tensor) and x.dtype == dtype and x.device == device and x.is_contiguous():
+        return x
+    return torch.as_tensor(x, device=device).to(dtype).contiguous()
 
 
 def launch(entry: str, cls, device, *extra, handle=None, **fields):
@@ -82,3 +91,19 @@ class MlpWeights:
             # a contiguous copy is not cached: it would go stale under an in-place update of its original
             self._ptrs = ptrs if all(k.data_ptr() == q for k, q in zip(keep, ptrs)) else None
         return self._w, self._keep
+
+
+class FusedCall:
+    """What the per-model objects that put one C entry on the current stream share (the fused training steps of loss.py,
+    the value unrolls of unroll.py): the model, the library, `params` in the C ABI's order (`names`), the device they lie
+    on -- a GPU, or the constructor refuses --, the support size, and the kept weight struct (`MlpWeights`)."""
+
+    def __init__(self, muzero_instance, params, names, weight_struct):
+        self.m = muzero_instance
+        self.params = [params[n] for n in names]
+        self.dev = self.params[0].device
+        if self.dev.type != "cuda":
+            raise RuntimeError("muax_amd needs a ROCm GPU (gfx950); there is no CPU fallback")
+        self._L = _lib.load()
+        self.S = muzero_instance._support_size
+        self._weights = MlpWeights(self.params, weight_struct, names)

@@ -19,7 +19,8 @@ muax/loss.py:60-61).  Reference quirks handled explicitly:
 
 Beyond the reference: `sample_weight` [B], the importance-sampling weights of prioritised replay
 (`DeviceReplayBuffer.sample(is_beta=)`), turns every mean_B CE(...) into mean_B (sample_weight * CE(...)) on both
-routes; the L2 term is not weighted.
+routes; the L2 term is not weighted.  Its [B] check (`check_sample_weight`) and the refusal of a batch without an
+observation for every step (`check_every_observation`) are stated once here, for update(), both fused steps and unroll.py.
 
 `stochastic_loss_fn` is the Stochastic MuZero loss of the reference's acme agent
 (muax/frameworks/acme/jax/stochastic_muzero/learning.py:200-277) in the conventions above -- a sum over steps, support
@@ -50,6 +51,21 @@ def softmax_cross_entropy(logits, labels):
     return -(labels * torch.log_softmax(logits, dim=-1)).sum(dim=-1)
 
 
+def check_every_observation(shape, B, L, what="loss"):
+    """The refusal of a batch whose obs (`shape`) is not [B, >= L, ...], by whoever reads an observation for every step
+    of a window: the stochastic `what` -- "loss" (both routes) or "unroll" (unroll.py)."""
+    if len(shape) < 3 or shape[0] != B or shape[1] < L:
+        raise ValueError(f"the stochastic {what} needs every step's observation: batch.obs must be [B, L, ...] with L = {L} "
+                         f"rows per window, got {tuple(shape)} (DeviceReplayBuffer.sample hands them out with all_obs=True)")
+
+
+def check_sample_weight(sample_weight, B):
+    """`sample_weight` must be [B]: update() and the fused steps ask before any launch, the two loss functions of the tensor
+    they converted.  The shape alone: looking at the values would synchronise."""
+    if tuple(getattr(sample_weight, "shape", ())) != (B,):
+        raise ValueError(f"sample_weight must be [B] with B = {B}, got {tuple(getattr(sample_weight, 'shape', ()))}")
+
+
 def default_loss_fn(muzero_instance, batch: Transition, divide_by_length: bool = False,
                     pi_all_pairs: bool = False, sample_weight=None):
     """muax/loss.py:10-88.  `batch` fields are tensors/arrays of shape [B, L, ...].  `sample_weight` [B]: row b's three
@@ -75,8 +91,7 @@ def default_loss_fn(muzero_instance, batch: Transition, divide_by_length: bool =
     sw = None
     if sample_weight is not None:
         sw = torch.as_tensor(sample_weight, device=dev).detach().to(s.dtype)
-        if tuple(sw.shape) != (B,):
-            raise ValueError(f"sample_weight must be [B] with B = {B}, got {tuple(sw.shape)}")
+        check_sample_weight(sw, B)
     for i in range(L):
         v, logits = muzero_instance.pred_func(s)
         s = mx_utils.scale_gradient(s, 0.5)  # Appendix G
@@ -111,9 +126,7 @@ def stochastic_loss_fn(muzero_instance, batch: Transition, vqvae_beta: float = 0
     B, L = a.shape[:2]
     a = a.reshape(B, L)
     obs = t(batch.obs)
-    if obs.dim() < 3 or obs.shape[0] != B or obs.shape[1] < L:
-        raise ValueError(f"the stochastic loss needs every step's observation: batch.obs must be [B, L, ...] with L = {L} "
-                         f"rows per window, got {tuple(obs.shape)} (DeviceReplayBuffer.sample hands them out with all_obs=True)")
+    check_every_observation(obs.shape, B, L)
     S = m._support_size
     r_t = mx_utils.scalar_to_support(t(batch.r).reshape(B, L), S).detach()
     Rn_t = mx_utils.scalar_to_support(t(batch.Rn).reshape(B, L), S).detach()
@@ -121,8 +134,7 @@ def stochastic_loss_fn(muzero_instance, batch: Transition, vqvae_beta: float = 0
     sw = None
     if sample_weight is not None:
         sw = torch.as_tensor(sample_weight, device=dev).detach().to(fdt)
-        if tuple(sw.shape) != (B,):
-            raise ValueError(f"sample_weight must be [B] with B = {B}, got {tuple(sw.shape)}")
+        check_sample_weight(sw, B)
     mean = (lambda x: x.mean()) if sw is None else (lambda x: (x * sw).mean())
     s = rep(obs[:, 0])
     v, logits = pred(s)
@@ -154,54 +166,36 @@ def _straight_through(encoded):
 # HIP path: loss and gradients in one fused forward+backward kernel and its fixed-order reduction, for the default MLP
 # trio (muax_amd/csrc/mz_train.cuh through mzs_mlp_loss_grad) and the default stochastic MLP family
 # (mz_stoch_train.cuh through mzs_stochastic_mlp_loss_grad).  The two kernels are built from the same blocks
-# (mz_train_blocks.cuh) and the two wrappers from `_FusedStep`.
+# (mz_train_blocks.cuh) and the two wrappers from `_FusedStep`, which stands on `_call.FusedCall` beside the unrolls.
 # ---------------------------------------------------------------------------------------------------
-class _FusedStep:
-    """What the two fused training steps share: the parameter list in the C ABI's order, the flat gradient with its
-    `views`, the workspace, the weight struct, the batch plumbing and the keep-alive of what the launch reads.  A
-    subclass sets obs_dim / E / A (/ C), names its weights and states `_num_params`, `_workspace_bytes`, `_obs` and
-    `_launch`."""
+class _FusedStep(_call.FusedCall):
+    """What the two fused training steps have on top of `_call.FusedCall`: the flat gradient with its `views`, the loss,
+    the workspace, the batch plumbing and the keep-alive of what the launch reads.  A subclass sets obs_dim / E / A
+    (/ C), names its weights and states `_num_params`, `_workspace_bytes`, `_obs` and `_launch`."""
 
     def __init__(self, muzero_instance, params, names, weight_struct):
-        self.m = muzero_instance
-        self._L = _lib.load()
-        self.params = [params[n] for n in names]
-        dev = self.params[0].device
-        if dev.type != "cuda":
-            raise RuntimeError("muax_amd needs a ROCm GPU (gfx950); there is no CPU fallback")
-        self.S = muzero_instance._support_size
+        super().__init__(muzero_instance, params, names, weight_struct)
         n = int(self._num_params())
         assert n == sum(x.numel() for x in self.params)
-        self.grads = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.views, off = [], 0
-        for x in self.params:
-            self.views.append(self.grads[off:off + x.numel()].view_as(x))
-            off += x.numel()
+        self.grads = torch.zeros(n, dtype=torch.float32, device=self.dev)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=self.dev)
+        self.views = [g.view_as(x) for g, x in zip(self.grads.split([x.numel() for x in self.params]), self.params)]
         self._ws = None
-        self._weights = _call.MlpWeights(self.params, weight_struct, names)
 
     def _step(self, batch, divide_by_length, sample_weight, **extra):
-        dev = self.grads.device
-
-        def t(x, dt):  # (tensors that already are what the kernel reads pass through untouched)
-            if isinstance(x, torch.Tensor) and x.dtype == dt and x.device == dev and x.is_contiguous():
-                return x
-            return torch.as_tensor(x, device=dev).to(dt).contiguous()
-        a = t(batch.a, torch.int32)
+        dev, t, f32 = self.dev, _call.as_device, torch.float32
+        a = t(batch.a, torch.int32, dev)
         B, L = a.shape[:2]
         a = a.reshape(B, L)
-        obs = self._obs(t(batch.obs, torch.float32), B, L)
+        obs = self._obs(t(batch.obs, f32, dev), B, L)
         if obs.shape[-1] != self.obs_dim:
             raise ValueError(f"batch.obs has {obs.shape[-1]} features, the network takes {self.obs_dim}")
-        r, Rn = t(batch.r, torch.float32).reshape(B, L), t(batch.Rn, torch.float32).reshape(B, L)
-        pi = t(batch.pi, torch.float32).reshape(B, L, self.A)
+        r, Rn = t(batch.r, f32, dev).reshape(B, L), t(batch.Rn, f32, dev).reshape(B, L)
+        pi = t(batch.pi, f32, dev).reshape(B, L, self.A)
         sw = None
-        if sample_weight is not None:  # (the shape alone: looking at the values would synchronise)
-            if tuple(getattr(sample_weight, "shape", ())) != (B,):
-                raise ValueError(f"sample_weight must be [B] with B = {B}, got "
-                                 f"{tuple(getattr(sample_weight, 'shape', ()))}")
-            sw = t(sample_weight.detach() if isinstance(sample_weight, torch.Tensor) else sample_weight, torch.float32)
+        if sample_weight is not None:
+            check_sample_weight(sample_weight, B)
+            sw = t(sample_weight.detach() if isinstance(sample_weight, torch.Tensor) else sample_weight, f32, dev)
         need = int(self._workspace_bytes(B))
         if self._ws is None or self._ws.numel() * 4 < need:
             self._ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
@@ -280,9 +274,7 @@ class StochasticFusedLossGrad(_FusedStep):
         return self._L.mzs_stochastic_mlp_train_workspace_bytes(B, self.obs_dim, self.E, self.A, self.C, self.S)
 
     def _obs(self, obs, B, L):  # a row for every step
-        if obs.dim() < 3 or obs.shape[0] != B or obs.shape[1] < L:
-            raise ValueError(f"the stochastic loss needs every step's observation: batch.obs must be [B, L, ...] with L = {L} "
-                             f"rows per window, got {tuple(obs.shape)} (DeviceReplayBuffer.sample hands them out with all_obs=True)")
+        check_every_observation(obs.shape, B, L)
         return obs[:, :L].reshape(B, L, -1).contiguous()
 
     def __call__(self, batch: Transition, vqvae_beta: float = 0.25, divide_by_length: bool = False, sample_weight=None):

@@ -19,8 +19,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import loss as mz_loss
 from . import nn as mz_nn
 from . import prng
+from . import sharding
+from . import unroll as mz_unroll
 from . import utils as mx_utils
 from ._call import capture, device_index, raw_stream
 from .nn import MZNetwork, MZNetworkParams, SMZNetwork, SMZNetworkParams
@@ -54,6 +57,9 @@ def _dirichlet(key_words, alpha: float, shape, device, global_batch=None, root_o
 def _jit_tail():
     from . import _jit
     return _jit.build_log_tail(3)
+
+
+_NO_KEYWORDS = {}  # (of update()'s fused call for the trio: one shared object, none built per update)
 
 
 class MuZero:
@@ -136,7 +142,6 @@ class MuZero:
         self._params = None
         self._opt_state_saved = None  # what init() / a checkpoint produced before an optimiser was bound
         self._loaded_opt_state = None
-        self._param_list = None
         self._fused_train = None
         self._fused_stoch_train = None
         self._fused_unroll = None
@@ -655,95 +660,93 @@ class MuZero:
         step -- the fused kernel (mzs_mlp_loss_grad_weighted), its on-demand retry, the torch route -- and a custom
         loss_fn as the keyword `sample_weight`, only when given.  A shape other than [B] is a ValueError before any
         launch; the values are not inspected (that would synchronise)."""
-        from . import loss as mz_loss
-        from . import optimizers as mz_opt
-        from .sharding import allreduce_mean_flat
         if self._params is None:
             raise ValueError("call init() first")
         if sample_weight is not None:
-            B = int(np.shape(batch.a)[0]) if not isinstance(batch.a, torch.Tensor) else int(batch.a.shape[0])
-            if tuple(getattr(sample_weight, "shape", ())) != (B,):
-                raise ValueError(f"sample_weight must be [B] with B = {B}, got "
-                                 f"{tuple(getattr(sample_weight, 'shape', ()))}")
+            mz_loss.check_sample_weight(sample_weight, int(np.shape(batch.a)[0]))  # (np.shape reads a tensor's .shape)
             kwargs["sample_weight"] = sample_weight
-        def all_params():
-            return [p for m in self.network if isinstance(m, torch.nn.Module) for p in m.parameters()]
-        if self._optimizer is None:
-            self._optimizer = mz_opt.create_optimizer()
-        if self._optimizer.opt is None:
-            loaded = self._loaded_opt_state
-            self._opt_state = self._optimizer.init(all_params())
-            if loaded is not None:
-                # a checkpoint was loaded before the optimiser was bound to parameters: resume its moments,
-                # step counts and schedule position (the reference restores opt_state, muax/model.py:210-212)
-                self._optimizer.load_state_dict(loaded)
-                self._loaded_opt_state = None
-        fused = backend != "torch" and self.loss_fn is None and self.device.type == "cuda" \
-            and mz_nn.is_default_mlp_trio(self.network) and (self.repr_func.obs_dim or 999) <= 128 \
-            and not kwargs.get("pi_all_pairs", False)
-        # ... and, with `stochastic_fused_update`, the default stochastic family under its own loss and that loss's keywords
-        stoch_fused = self.stochastic_fused_update and backend != "torch" and self.loss_fn is None \
-            and self.device.type == "cuda" and mz_nn.is_default_stochastic_mlp(self.network) \
-            and (self.repr_func.obs_dim or 999) <= 32 and not args \
-            and set(kwargs) <= {"vqvae_beta", "divide_by_length", "sample_weight"}
-        if stoch_fused:
-            try:
-                if self._fused_stoch_train is None:
-                    self._fused_stoch_train = mz_loss.StochasticFusedLossGrad(self)
-                loss, flat = self._fused_stoch_train(batch, vqvae_beta=kwargs.get("vqvae_beta", 0.25),
-                                                     divide_by_length=kwargs.get("divide_by_length", False),
-                                                     sample_weight=sample_weight)
-                if dp_mean:
-                    allreduce_mean_flat([flat])
-                for p, g in zip(self._fused_stoch_train.params, self._fused_stoch_train.views):
-                    p.grad = g
-            except (_lib.NoKernelInstance, _lib.TooLargeForLds):  # (refused on the host, before any launch)
-                if backend == "hip":
-                    raise
-                stoch_fused = False
-        if backend == "hip" and not (fused or stoch_fused):
+        if self._optimizer is None or self._optimizer.opt is None:
+            self._bind_optimizer()
+        fused = None if backend == "torch" else self._fused_update(args, kwargs)
+        if backend == "hip" and fused is None:
             raise ValueError("backend='hip' needs the default MLP trio on a GPU and the default loss"
                              + (" (the stochastic loss of an SMZNetwork runs on torch autograd only, unless the model was made with "
                                 "stochastic_fused_update=True: the default stochastic MLP family on a GPU, obs_dim up to 32)"
                                 if self._stochastic else ""))
-        if fused:
+        if fused is not None:
+            cache, cls, route, on_demand, extra = fused
             try:
-                if self._fused_train is None:
-                    self._fused_train = mz_loss.FusedLossGrad(self)
+                step = getattr(self, cache)
+                if step is None:
+                    step = cls(self)
+                    setattr(self, cache, step)  # (it stays after a refusal)
+                divide = kwargs.get("divide_by_length", False)
                 try:
-                    loss, flat = self._fused_train(batch, divide_by_length=kwargs.get("divide_by_length", False),
-                                                   sample_weight=sample_weight)
+                    loss, flat = step(batch, divide_by_length=divide, sample_weight=sample_weight, **extra)
                 except _lib.NoKernelInstance:
                     # a shape of the default trio the library lists no training instance for: build one on demand
                     # (muax_amd/_jit.py::ensure_train_instance, or ensure_wide_train_instance for 17 to 64 actions; once
                     # per shape, cached on disk) and call again
                     from . import _jit
-                    ft = self._fused_train
-                    shape = (ft.A, ft.E, 2 * ft.S + 1)
-                    if not (_jit.ensure_train_instance(*shape) or _jit.ensure_wide_train_instance(*shape)):
+                    shape = (step.A, step.E, 2 * step.S + 1)
+                    if not (on_demand and (_jit.ensure_train_instance(*shape) or _jit.ensure_wide_train_instance(*shape))):
                         raise
-                    loss, flat = ft(batch, divide_by_length=kwargs.get("divide_by_length", False),
-                                    sample_weight=sample_weight)
+                    loss, flat = step(batch, divide_by_length=divide, sample_weight=sample_weight, **extra)
                 if dp_mean:
-                    allreduce_mean_flat([flat])
-                for p, g in zip(self._fused_train.params, self._fused_train.views):
+                    sharding.allreduce_mean_flat([flat])
+                for p, g in zip(step.params, step.views):
                     p.grad = g
             except (_lib.NoKernelInstance, _lib.TooLargeForLds):
                 # shapes the kernel cannot serve (no instance, or an unroll longer than its LDS keeps) take the
                 # torch route under backend="auto"; the kernel refuses them on the host, before any launch
                 if backend == "hip":
                     raise
-                fused = False
-        if not (fused or stoch_fused):
+                fused = None
+        if fused is None:
             loss_fn = self.loss_fn or (mz_loss.stochastic_loss_fn if self.trains_stochastic else mz_loss.default_loss_fn)
             loss = loss_fn(self, batch, *args, **kwargs)
             loss.backward()
             if dp_mean:
-                allreduce_mean_flat([p.grad for p in all_params()])
-        self._last_update_route = "hip_stochastic_fused" if stoch_fused else "hip_fused" if fused else "torch"
+                sharding.allreduce_mean_flat([p.grad for p in self._all_params()])
+            route = "torch"
+        self._last_update_route = route
         self._optimizer.step()
         self._weights_version += 1
         return {"loss": float(loss.item())}
+
+    def _all_params(self):
+        return [p for m in self.network if isinstance(m, torch.nn.Module) for p in m.parameters()]
+
+    def _bind_optimizer(self):
+        """The optimiser (the default one when none was given) bound to the parameters, on the first update()."""
+        from . import optimizers as mz_opt
+        if self._optimizer is None:
+            self._optimizer = mz_opt.create_optimizer()
+        loaded = self._loaded_opt_state
+        self._opt_state = self._optimizer.init(self._all_params())
+        if loaded is not None:
+            # a checkpoint was loaded before the optimiser was bound to parameters: resume its moments,
+            # step counts and schedule position (the reference restores opt_state, muax/model.py:210-212)
+            self._optimizer.load_state_dict(loaded)
+            self._loaded_opt_state = None
+
+    def _fused_update(self, args, kwargs):
+        """The fused training step that may serve this update(), or None: (the attribute that keeps the step object, its
+        class, the route's name, whether a missing instance is built on demand, its keywords beyond divide_by_length and
+        sample_weight).  At most one: is_default_mlp_trio wants an MZNetwork of three modules, is_default_stochastic_mlp
+        an SMZNetwork of six, so the two families' conditions never hold together.  The stochastic family is served only
+        with `stochastic_fused_update`, under its own loss and that loss's keywords."""
+        if self.loss_fn is not None or self.device.type != "cuda":
+            return None
+        if mz_nn.is_default_mlp_trio(self.network):
+            if (self.repr_func.obs_dim or 999) <= 128 and not kwargs.get("pi_all_pairs", False):
+                return "_fused_train", mz_loss.FusedLossGrad, "hip_fused", True, _NO_KEYWORDS
+        elif self.stochastic_fused_update and mz_nn.is_default_stochastic_mlp(self.network):
+            if (self.repr_func.obs_dim or 999) <= 32 and not args \
+                    and set(kwargs) <= {"vqvae_beta", "divide_by_length", "sample_weight"}:
+                return ("_fused_stoch_train", mz_loss.StochasticFusedLossGrad, "hip_stochastic_fused", False,
+                        {"vqvae_beta": kwargs.get("vqvae_beta", 0.25)})
+        return None
 
     @property
     def trains_stochastic(self):
@@ -772,7 +775,6 @@ class MuZero:
         for every step (a ValueError otherwise).  "hip": ONE launch (mzs_stochastic_mlp_unroll_values, mz_unroll.cuh) for
         the default stochastic MLP family on a GPU, obs_dim 1..128, embedding 1..64, actions + chance outcomes up to 64,
         support_size 8..31; "torch" and "auto" as above."""
-        from . import unroll as mz_unroll
         if backend not in ("auto", "hip", "torch"):
             raise ValueError(f"backend must be 'auto', 'hip' or 'torch', got {backend!r}")
         if self._params is None:
@@ -781,22 +783,15 @@ class MuZero:
             raise NotImplementedError("unroll_values is not built for an SMZNetwork (its unroll needs every step's chance code)")
         B, L, kp = mz_unroll.batch_window(batch, k_prio)
         if self._stochastic:
-            mz_unroll.check_every_observation(tuple(np.shape(batch.obs)), B, L)  # (before anything runs)
-            family = self.device.type == "cuda" and mz_nn.is_default_stochastic_mlp(self.network)
-            if backend == "hip" and not family:
-                raise ValueError("backend='hip' needs the default stochastic MLP family on a GPU")
-            if backend == "torch" or not family or (backend == "auto" and not mz_unroll.within_stochastic_limits(self)):
-                return mz_unroll.torch_stochastic_unroll_values(self, batch, kp)
-            if self._fused_unroll is None:
-                self._fused_unroll = mz_unroll.StochasticFusedUnrollValues(self)
-            return self._fused_unroll(batch, kp)  # (backend="hip" beyond the limits: the library's error, the limit named)
-        trio = self.device.type == "cuda" and mz_nn.is_default_mlp_trio(self.network)
-        if backend == "hip" and not trio:
-            raise ValueError("backend='hip' needs the default MLP trio on a GPU")
-        if backend == "torch" or not trio or (backend == "auto" and not mz_unroll.within_limits(self)):
-            return mz_unroll.torch_unroll_values(self, batch, kp)
+            mz_loss.check_every_observation(tuple(np.shape(batch.obs)), B, L, "unroll")  # (before anything runs)
+        family = mz_unroll.STOCHASTIC if self._stochastic else mz_unroll.TRIO
+        served = self.device.type == "cuda" and family.is_family(self.network)
+        if backend == "hip" and not served:
+            raise ValueError(f"backend='hip' needs {family.name} on a GPU")
+        if backend == "torch" or not served or (backend == "auto" and not mz_unroll.within(family, self)):
+            return family.torch_unroll(self, batch, kp)
         if self._fused_unroll is None:
-            self._fused_unroll = mz_unroll.FusedUnrollValues(self)
+            self._fused_unroll = family.fused(self)
         return self._fused_unroll(batch, kp)  # (backend="hip" beyond the limits: the library's error, the limit named)
 
     def save_load(self, file, save=True):
