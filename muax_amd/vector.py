@@ -14,12 +14,62 @@ first observation of its next episode (auto-reset).
 """
 from __future__ import annotations
 
+import ctypes as C
+import inspect
 import time
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
+import torch
 
-from . import prng
-from .replay_buffer import Trajectory
+from . import _lib, prng  # (_lib.load() is lazy: importing this module needs no built library)
+from . import utils as mx_utils
+from .replay_buffer import Trajectory, TrajectoryReplayBuffer
+from .train import _temperature_fn, test
+
+
+# ---- Capabilities.  What an environment or a buffer may offer beyond the protocol above, each asked in one place. ----
+def _is_device_env(venv):
+    """The device-environment protocol of muax_amd/envs.py: `reset_device` / `step_device` on device tensors."""
+    return hasattr(venv, "step_device")
+
+
+def _is_gym_env(env):
+    """A gym-style single environment (`observation_space`, the five-tuple `step`): what `train.test` evaluates."""
+    return hasattr(env, "observation_space")
+
+
+def _device_mask_of(venv):
+    """The mask extension of muax_amd/envs.py on the device: act()'s `invalid_actions` keyword with the environment's
+    own uint8 [N, A] tensor (`invalid_actions_device()`, overwritten in place by its launches), or nothing."""
+    return {"invalid_actions": venv.invalid_actions_device()} if hasattr(venv, "invalid_actions_device") else {}
+
+
+def _has_host_mask(venv):
+    """The same extension through the host protocol: `invalid_actions()` -> uint8 [N, A] as NumPy, asked every step."""
+    return hasattr(venv, "invalid_actions")
+
+
+def _mask_fn_of(venv):
+    """The same extension for stored observations: reanalyse's `mask_fn` keyword (`invalid_actions_of`), or nothing."""
+    return {"mask_fn": venv.invalid_actions_of} if hasattr(venv, "invalid_actions_of") else {}
+
+
+def _has_device_store(buffer):
+    """`add_steps` of muax_amd/replay_device.py: episodes cut out of a collection ring on the device."""
+    return hasattr(buffer, "add_steps")
+
+
+def _offers(buffer, method):
+    """An optional method of muax_amd/replay_device.py that the host buffer lacks: `add_many` (a collection in one
+    launch), `reanalyse` (with `stalest`), `update_priorities`."""
+    return hasattr(buffer, method)
+
+
+def _sample_takes(buffer):
+    """The parameters of the buffer's `sample`: `is_beta` and `all_obs` are replay_device.py's, the host buffer has
+    neither."""
+    return inspect.signature(buffer.sample).parameters
 
 
 def nstep_returns(r, v, n: int, gamma: float):
@@ -79,9 +129,19 @@ class VectorCollector:
             d_l.append(np.asarray(done, bool)), v_l.append(np.asarray(v, np.float64)), pi_l.append(np.asarray(pi))
             obs = np.asarray(nxt)
         self._obs = obs
-        # env-major flat streams: for every environment its carried-over open episode, then the new steps
         fields = [np.stack(x) for x in (obs_l, a_l, r_l, v_l, pi_l)]  # [T, N, ...]
-        D = np.stack(d_l)
+        (O, A, R, V, P), first, carried = self._flat_streams(fields, steps)
+        ends, env_of_end, last_end, left = self._episode_ends(np.stack(d_l), first, carried, steps)
+        Rn, nb, W = self._returns_and_priorities(R, V, left)
+        if P.ndim == 2:
+            P = P[:, None, :]
+        streams = (O, A.astype(np.int64), R, nb, Rn, V, P, W)
+        return self._cut_and_carry(streams, first, ends, env_of_end, last_end), key, steps * N
+
+    def _flat_streams(self, fields, steps):
+        """Env-major flat streams: for every environment its carried-over open episode, then the call's steps.
+        Returns (the streams of `fields`, the stream offset of every environment [N + 1], the carried steps [N])."""
+        N = len(self._pending)
         carried = np.array([0 if p is None else len(p[0]) for p in self._pending])
         flat = []
         for k, f in enumerate(fields):
@@ -92,20 +152,30 @@ class VectorCollector:
             else:
                 f = f.reshape((N * steps,) + f.shape[2:])
             flat.append(f)
-        O, A, R, V, P = flat
-        first = np.concatenate([[0], np.cumsum(carried + steps)])  # stream offsets per environment
-        done = np.zeros(first[-1], bool)  # carried steps are never episode ends
+        return flat, np.concatenate([[0], np.cumsum(carried + steps)]), carried
+
+    @staticmethod
+    def _episode_ends(D, first, carried, steps):
+        """From the call's flags D [T, N]: the stream positions that end an episode, the environment of each, every
+        environment's last one (-1: none; the stream up to it is closed, the rest is carried over), and `left`, the
+        steps from every position to the end of its episode, that one included (garbage on open tails)."""
+        N, M = len(carried), first[-1]
+        done = np.zeros(M, bool)  # carried steps are never episode ends
         done[(first[:-1] + carried)[:, None] + np.arange(steps)[None, :]] = D.T
         ends = np.flatnonzero(done)
-        # closed part of every stream = up to its last episode end; the rest is carried over
         last_end = np.full(N, -1)
         env_of_end = np.searchsorted(first, ends, side="right") - 1
         last_end[env_of_end] = ends  # ends ascend, so the last one per environment stays
-        M = first[-1]
         pos = np.arange(M)
         nxt = ends[np.minimum(np.searchsorted(ends, pos), max(len(ends) - 1, 0))] if len(ends) else pos
-        left = nxt - pos + 1  # steps to the end of the episode, this one included (garbage on open tails)
-        n, g = self.n, self.gamma
+        return ends, env_of_end, last_end, nxt - pos + 1
+
+    def _returns_and_priorities(self, R, V, left):
+        """`nstep_returns` and the priority weights over the whole flat stream at once, `left` keeping every sum inside
+        its episode.  (`nstep_returns` states the same arithmetic for ONE episode -- `episode_trajectory`, the tests and
+        the reference comparison use it; calling it per episode here would be a Python loop over the thousands of
+        episodes a wide collection finishes.)  Returns (Rn, the flags of the transitions that could not bootstrap, w)."""
+        n, g, M = self.n, self.gamma, len(R)
         Rp, Vp = np.concatenate([R, np.zeros(n)]), np.concatenate([V, np.zeros(n)])
         Rn = np.zeros(M)
         for i in range(n):
@@ -113,21 +183,23 @@ class VectorCollector:
         boot = left > n
         Rn = Rn + np.where(boot, Vp[n:n + M] * (g ** n), 0.0)
         W = np.ones(M) if self.alpha is None else np.abs(V - Rn) ** self.alpha
-        if P.ndim == 2:
-            P = P[:, None, :]
-        A = A.astype(np.int64)
-        nb = ~boot
-        out = []
+        return Rn, ~boot, W
+
+    def _cut_and_carry(self, streams, first, ends, env_of_end, last_end):
+        """Cut the closed part of the streams (obs, a, r, done, Rn, v, pi, w) into one Trajectory per episode and keep
+        every environment's open tail for the next call."""
+        O, A, R, nb, Rn, V, P, W = streams
         starts = np.concatenate([[0], ends[:-1] + 1]) if len(ends) else np.zeros(0, int)
         starts = np.maximum(starts, first[env_of_end]) if len(ends) else starts
+        out = []
         for s0, e0 in zip(starts.tolist(), (ends + 1).tolist()):
             out.append(Trajectory.from_arrays(O[s0:e0], A[s0:e0], R[s0:e0], nb[s0:e0], Rn[s0:e0], V[s0:e0],
                                               P[s0:e0], W[s0:e0], _checked=True))
-        for e in range(N):
+        for e in range(len(self._pending)):
             s0 = first[e] if last_end[e] < 0 else last_end[e] + 1
             e0 = first[e + 1]
             self._pending[e] = (O[s0:e0], A[s0:e0], R[s0:e0], V[s0:e0], P[s0:e0, 0]) if s0 < e0 else None
-        return out, key, steps * N
+        return out
 
 
 def ring_plan(done, open_start, step0, min_length=1):
@@ -181,9 +253,11 @@ class DeviceVectorCollector:
     `np.sum`'s pairwise sum; for rewards that are small integers (every environment of the project) the two are equal
     bit for bit, for other rewards they may differ in the last bits."""
 
+    store_s = 0.0  # (fit_vector's `collect_s`: storing is part of this collection, nothing is taken out of its time)
+
     def __init__(self, venv, buffer, n: int, gamma: float, alpha=0.5, weight: str = "mean", min_length: int = 1,
                  ring_steps=None, device_plan: bool = False):
-        if not hasattr(buffer, "add_steps"):
+        if not _has_device_store(buffer):
             raise ValueError(f"DeviceVectorCollector needs a buffer with the device store (DeviceReplayBuffer); "
                              f"{type(buffer).__name__} has none")
         if weight not in ("mean", "sum"):
@@ -192,7 +266,7 @@ class DeviceVectorCollector:
             raise ValueError("n must be at least 1")
         if ring_steps is not None and int(ring_steps) < 1:
             raise ValueError("ring_steps must be positive")
-        if device_plan and not hasattr(venv, "step_device"):
+        if device_plan and not _is_device_env(venv):
             raise ValueError(f"DeviceVectorCollector: device_plan needs a device environment (one with step_device, "
                              f"e.g. DeviceCartPole): the plan kernel reads the rewards and flags the environment wrote "
                              f"on the device; {type(venv).__name__} has no step_device")
@@ -210,9 +284,6 @@ class DeviceVectorCollector:
         self._plan_held = 0      # device_plan: the longest open episode after the previous call (counts[2])
 
     def _alloc(self, N, obs_dim, A):
-        import torch
-
-        from . import _lib
         buf = self.buffer
         buf._check_dims(obs_dim, A)  # (allocates the arenas on first use; a mismatch is the buffer's ValueError)
         dev, S = buf._device, self.ring_steps
@@ -221,16 +292,11 @@ class DeviceVectorCollector:
         self._fields = {k: torch.zeros(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
         self._ring = _lib.args(_lib.MzsReplayRing, device=buf._arena.device, ring_steps=S, num_envs=N, obs_dim=obs_dim,
                                num_actions=A, **{k: x.data_ptr() for k, x in self._fields.items()})
-        if hasattr(self.venv, "step_device"):  # the flags a device environment writes, beside the ring fields
+        if _is_device_env(self.venv):  # the flags a device environment writes, beside the ring fields
             self._done_rows = torch.zeros((S, N), dtype=torch.uint8, device=dev)
 
     def _stage(self, i, obs_d, a, pi, v):
         """One `mzs_replay_stage`: step i of the call into its ring row.  Returns the actions as int32 on the device."""
-        import ctypes as C
-
-        import torch
-
-        from . import _lib
         N = self._ring.num_envs
         flat = obs_d.reshape(N, -1).contiguous()
         a32 = a.to(torch.int32).contiguous()
@@ -262,11 +328,10 @@ class DeviceVectorCollector:
         uint8 [N, A] mask of the observation act() is given, the same object every step.  The same stream order holds
         for it: the environment's overwrite of the mask comes after the search that read it.  An environment without
         the method gets exactly the act() calls it always got."""
-        import torch
         venv, S = self.venv, self.ring_steps
-        on_device = hasattr(venv, "step_device")
-        if on_device and hasattr(venv, "invalid_actions_device"):
-            act_kwargs = {"invalid_actions": venv.invalid_actions_device(), **act_kwargs}  # (a caller's own wins)
+        on_device = _is_device_env(venv)
+        if on_device:
+            act_kwargs = {**_device_mask_of(venv), **act_kwargs}  # (a caller's own wins)
         dev, first = self.buffer._device, self._obs is None
         if first:
             if on_device and dev is not None and dev.index is not None and torch.device(venv.device) != dev:
@@ -308,17 +373,31 @@ class DeviceVectorCollector:
                 at += hi - lo
         return key, R, D
 
-    def _collect_device_plan(self, model, key, steps, num_simulations, temperature, act_kwargs):
-        """collect() with the plan on the device: the step loop without its download, `mzs_replay_plan_steps` on the
-        call's rows, then the counts (the first synchronisation) and the episode rows come down."""
-        import ctypes as C
+    def _plan_on_host(self, R, D, step0):
+        """The call's episodes from its flags (`ring_plan`) and their returns from the host's rewards R [T, N]: the
+        carried part of an episode, then the call's.  Returns ([(environment, first ring row, length, stored)], returns)
+        and moves `_open_start` / `_open_r` on."""
+        finished, dropped, new_open = ring_plan(D, self._open_start, step0, self.min_length)
+        Rt = np.ascontiguousarray(R.T)
+        stored = set(finished)
+        every = sorted(finished + dropped, key=lambda x: (x[0], x[1])) if dropped else finished
+        G = []
+        for env, first, T in every:
+            seg = Rt[env, max(first - step0, 0):first + T - step0]
+            G.append(float(np.sum(np.concatenate(self._open_r[env] + [seg]) if first < step0 else seg)))
+        for env in range(R.shape[1]):
+            if new_open[env] <= step0:  # no episode of this environment ended: the open one grows
+                self._open_r[env].append(Rt[env].copy())
+            else:
+                tail = Rt[env, new_open[env] - step0:]
+                self._open_r[env] = [tail.copy()] if len(tail) else []
+        self._open_start = new_open
+        return [(env, first % self.ring_steps, T, (env, first, T) in stored) for env, first, T in every], G
 
-        import torch
-
-        from . import _lib
-        if int(self.venv.n) * steps >= 2 ** 31:
-            raise ValueError("collect: device_plan needs num_envs * steps below 2^31")
-        key, _, _ = self._steps(model, key, steps, num_simulations, temperature, act_kwargs)
+    def _plan_on_device(self, steps):
+        """`mzs_replay_plan_steps` on the call's rows, then the counts (the call's first synchronisation) and one
+        episode row and one return per finished episode come down.  Returns what `_plan_on_host` returns and moves
+        `_plan_held` on (the launch itself has advanced the device's open_len / open_ret)."""
         N, S = int(self._ring.num_envs), self.ring_steps
         dev = self._fields["r"].device
         if self._plan is None:
@@ -340,14 +419,8 @@ class DeviceVectorCollector:
             raise RuntimeError(f"collect: the plan reports {episodes} episodes, more than its {max_out} output rows")
         rows = pl["ep"][:episodes].cpu().numpy().tolist() if episodes else []
         G = pl["ret"][:episodes].cpu().numpy().tolist() if episodes else []
-        # (as on the default route the collector's state moves on before add_steps: the launch has already advanced
-        # open_len / open_ret, so if add_steps raises -- an episode longer than the buffer's max_steps -- the call's
-        # episodes are lost, not collected twice)
-        self._plan_held, self._step0 = int(counts[2]), self._step0 + steps
-        serials = iter(self.buffer.add_steps(self._ring, [(env, first, T) for env, first, T, kept in rows if kept],
-                                             self.n, self.gamma, self.alpha, weight=self.weight))
-        out = [(T, g, next(serials) if kept else None) for (_, _, T, kept), g in zip(rows, G)]
-        return out, key, steps * N
+        self._plan_held = int(counts[2])
+        return rows, G
 
     def collect(self, model, key, steps: int, num_simulations: int = 50, temperature: float = 1.0, **act_kwargs):
         """`steps` lock-step environment steps.  Returns (finished, advanced key, env steps): `finished` lists, in
@@ -369,31 +442,18 @@ class DeviceVectorCollector:
         if held + steps > S:
             raise ValueError(f"collect: an open episode of {held} steps plus {steps} more does not fit the ring of "
                              f"{S} steps (ring_steps)")
-        if self.device_plan:
-            return self._collect_device_plan(model, key, steps, num_simulations, temperature, act_kwargs)
+        if self.device_plan and int(self.venv.n) * steps >= 2 ** 31:
+            raise ValueError("collect: device_plan needs num_envs * steps below 2^31")
         step0 = self._step0
         key, R, D = self._steps(model, key, steps, num_simulations, temperature, act_kwargs)
-        N = R.shape[1]
-        finished, dropped, new_open = ring_plan(D, self._open_start, step0, self.min_length)
-        # the returns, from the host's rewards: the carried part of an episode, then the call's
-        Rt = np.ascontiguousarray(R.T)
-        stored = set(finished)
-        every = sorted(finished + dropped, key=lambda x: (x[0], x[1])) if dropped else finished
-        G = []
-        for env, first, T in every:
-            seg = Rt[env, max(first - step0, 0):first + T - step0]
-            G.append(float(np.sum(np.concatenate(self._open_r[env] + [seg]) if first < step0 else seg)))
-        for env in range(N):
-            if new_open[env] <= step0:  # no episode of this environment ended: the open one grows
-                self._open_r[env].append(Rt[env].copy())
-            else:
-                tail = Rt[env, new_open[env] - step0:]
-                self._open_r[env] = [tail.copy()] if len(tail) else []
-        self._open_start, self._step0 = new_open, step0 + steps
-        serials = iter(self.buffer.add_steps(self._ring, [(env, first % S, T) for env, first, T in finished], self.n,
-                                             self.gamma, self.alpha, weight=self.weight))
-        out = [(T, g, next(serials) if (env, first, T) in stored else None) for (env, first, T), g in zip(every, G)]
-        return out, key, steps * N
+        rows, G = self._plan_on_device(steps) if self.device_plan else self._plan_on_host(R, D, step0)
+        # the collector's state moves on before add_steps on both routes: if add_steps raises -- an episode longer than
+        # the buffer's max_steps -- the call's episodes are lost, not collected twice
+        self._step0 = step0 + steps
+        serials = iter(self.buffer.add_steps(self._ring, [(env, first, T) for env, first, T, kept in rows if kept],
+                                             self.n, self.gamma, self.alpha, weight=self.weight))
+        out = [(T, g, next(serials) if kept else None) for (_, _, T, kept), g in zip(rows, G)]
+        return out, key, steps * int(self._ring.num_envs)
 
 
 def test_vector(model, venv, key, num_simulations: int, max_steps=None):
@@ -405,7 +465,7 @@ def test_vector(model, venv, key, num_simulations: int, max_steps=None):
     N = obs.shape[0]
     G, live = np.zeros(N), np.ones(N, bool)
     steps = max_steps if max_steps is not None else venv.spec.max_episode_steps
-    masked = hasattr(venv, "invalid_actions")
+    masked = _has_host_mask(venv)
     for _ in range(steps):
         key, subkey = prng.split(key)
         mask = {"invalid_actions": venv.invalid_actions()} if masked else {}
@@ -430,11 +490,10 @@ def test_vector_device(model, venv, key, num_simulations: int, max_steps=None):
     An environment with `invalid_actions_device` (looked for once per call) has that tensor -- its own mask of the
     observation act() is given, overwritten in place by its launches -- passed to every act() as `invalid_actions`;
     the stream orders the environment's overwrite after the search that read it.  Any other is evaluated as before."""
-    import torch
-    if not hasattr(venv, "step_device"):
+    if not _is_device_env(venv):
         raise ValueError(f"test_vector_device needs a device environment (one with step_device); "
                          f"{type(venv).__name__} has none: use test_vector")
-    mask = {"invalid_actions": venv.invalid_actions_device()} if hasattr(venv, "invalid_actions_device") else {}
+    mask = _device_mask_of(venv)
     obs = venv.reset_device()
     N, dev = int(venv.n), obs.device
     G = torch.zeros(N, dtype=torch.float64, device=dev)
@@ -460,9 +519,6 @@ def value_priorities(model, batch):
     on the model's device -- the value error of every window's first transition, the one whose weight decided the
     draw of the start.  The model's torch modules under no_grad, the scalar value decoded from the support logits as
     in root inference; no synchronisation."""
-    import torch
-
-    from . import utils as mx_utils
     dev = model.device
     with torch.no_grad():
         obs = torch.as_tensor(batch.obs, dtype=torch.float32, device=dev)
@@ -480,6 +536,150 @@ def unroll_value_priorities(model, batch, k_prio=None, backend: str = "auto"):
     return model.unroll_values(batch, k_prio=k_prio, backend=backend)[1]
 
 
+class _HostCollect:
+    """`VectorCollector` behind `DeviceVectorCollector.collect`'s result, for fit_vector: the finished episodes of at
+    least `k_steps` steps go into the buffer -- `add_many` where it has one (the device buffer: one upload and one
+    launch for the collection), else `add` per trajectory -- with the "mean" or "sum" of their priority weights, and
+    every finished episode, kept or not, comes back as a (length, undiscounted return, None) row in the collector's
+    order.  `store_s`: the seconds the last call spent after the collection itself, which `collect_s` leaves out."""
+
+    def __init__(self, collector, buffer, k_steps, weight):
+        self.collector, self.buffer, self.k_steps, self.weight = collector, buffer, k_steps, weight
+        self.add_many = _offers(buffer, "add_many")
+        self.store_s = 0.0
+
+    def collect(self, model, key, steps, num_simulations, temperature):
+        trajs, key, env_steps = self.collector.collect(model, key, steps, num_simulations, temperature)
+        t0 = time.perf_counter()
+        keep = [tr for tr in trajs if len(tr) >= self.k_steps]
+        weights = [tr.weights.mean() if self.weight == "mean" else tr.weights.sum() for tr in keep]
+        if self.add_many:
+            self.buffer.add_many(keep, weights)
+        else:
+            for tr, w in zip(keep, weights):
+                self.buffer.add(tr, w)
+        rows = [(len(tr), float(np.sum(tr.rewards)), None) for tr in trajs]
+        self.store_s = time.perf_counter() - t0
+        return rows, key, env_steps
+
+
+def _tester(test_env, num_simulations, num_test_episodes):
+    """(model, key) -> mean greedy return on `test_env`: the reference's `test` for a gym-style environment, else all
+    the vector environment's first episodes in lock step, where it lives.  The value is the same either way."""
+    if _is_gym_env(test_env):
+        return lambda model, key: test(model, test_env, key, num_simulations=num_simulations,
+                                       num_test_episodes=num_test_episodes)
+    if _is_device_env(test_env):
+        return lambda model, key: test_vector_device(model, test_env, key, num_simulations)
+    return lambda model, key: test_vector(model, test_env, key, num_simulations)
+
+
+def _unpack_sample(got, with_indices, with_isw):
+    """What `sample` returned -- a batch alone, or (batch[, indices][, isw]) -- as (batch, indices or None, update()'s
+    keywords: the weights as `sample_weight`, or none)."""
+    if not (with_indices or with_isw):
+        return got, None, {}
+    return got[0], got[1] if with_indices else None, {"sample_weight": got[-1]} if with_isw else {}
+
+
+class _FitPlan(NamedTuple):
+    """What fit_vector's loop runs with, settled by `_fit_plan` before anything else happens."""
+    buffer: object
+    collector: object              # .collect(model, key, steps, num_simulations, temperature) -> (rows, key, env steps)
+    sample_kw: dict                # the keywords every sample() gets (is_beta, where scheduled, is added per batch)
+    prioritise: bool               # sample with indices and write priorities back after every update
+    priorities: Callable           # (model, batch) -> the priorities to write back
+    beta: Optional[Callable]       # training_step -> is_beta of the next batch, or None: no importance weights
+    reanalyse_kw: Optional[dict]   # reanalyse()'s fixed keywords, or None: never reanalyse
+    tester: Callable               # (model, key) -> test_G
+
+
+def _fit_plan(model, venv, test_env, buffer, *, n_step, gamma, alpha, num_simulations, k_steps, num_trajectory,
+              sample_per_trajectory, max_training_steps, num_test_episodes, trajectory_weight, reanalyse_every,
+              priority_update, priority_steps, is_beta, device_collect, device_plan, all_obs) -> _FitPlan:
+    """Every check of fit_vector's arguments against each other, the buffer, the environments and the model, and what
+    follows from them.  Touches neither the model nor an environment; the first refusal that applies is raised:
+      1. priority_steps below 1
+      2. trajectory_weight neither "mean" nor "sum"
+      3. device_plan without device_collect and a device environment
+         (from here on `buffer` is the default host buffer where none was given)
+      4. is_beta with a buffer whose sample() takes none
+      5. is_beta neither a callable nor within 0..1
+      6. all_obs=True with a buffer whose sample() takes none
+      7. priority_steps written back (priority_update, a buffer with update_priorities) for a stochastic model that
+         does not unroll its SMZNetwork
+      8. a device environment without device_collect
+      9. device_collect with a buffer without the device store
+     10. what `DeviceVectorCollector` itself refuses (n_step below 1; k_steps below 1 under device_plan)."""
+    on_device = _is_device_env(venv)
+    if priority_steps is not None and int(priority_steps) < 1:
+        raise ValueError("priority_steps must be None or >= 1")
+    if trajectory_weight not in ("mean", "sum"):
+        raise ValueError("trajectory_weight must be 'mean' or 'sum'")
+    if device_plan and not (device_collect and on_device):
+        raise ValueError(f"fit_vector: device_plan needs device_collect=True and a device environment (one with "
+                         f"step_device); device_collect is {bool(device_collect)} and {type(venv).__name__} has "
+                         f"{'a' if on_device else 'no'} step_device")
+    buffer = buffer if buffer is not None else TrajectoryReplayBuffer(500)
+    takes = _sample_takes(buffer)
+    if is_beta is not None:
+        if "is_beta" not in takes:
+            raise ValueError(f"fit_vector: is_beta needs a buffer whose sample() takes is_beta (DeviceReplayBuffer); "
+                             f"{type(buffer).__name__}.sample does not")
+        if not callable(is_beta) and not 0.0 <= float(is_beta) <= 1.0:
+            raise ValueError("fit_vector: is_beta must be None, a number in 0..1 or a callable")
+    stochastic = bool(getattr(model, "trains_stochastic", False))  # (update()'s own predicate for stochastic_loss_fn)
+    if all_obs and "all_obs" not in takes:
+        raise ValueError(f"fit_vector: all_obs needs a buffer whose sample() takes all_obs (DeviceReplayBuffer); "
+                         f"{type(buffer).__name__}.sample does not")
+    all_obs = (stochastic and "all_obs" in takes) if all_obs is None else bool(all_obs)
+    prioritise = bool(priority_update) and _offers(buffer, "update_priorities")
+    if prioritise and priority_steps is not None and stochastic and not getattr(model, "unrolls_stochastic", False):
+        raise ValueError("fit_vector: priority_update with priority_steps needs MuZero.unroll_values, which is not built "
+                         "for an SMZNetwork (a stochastic model); use priority_steps=None (value_priorities)")
+    if on_device and not device_collect:
+        raise ValueError(f"fit_vector: {type(venv).__name__} is a device environment (it has step_device) and needs "
+                         f"device_collect=True; device_collect is False")
+    if device_collect and not _has_device_store(buffer):
+        if on_device:
+            needs = (f"{type(venv).__name__} is a device environment (it has step_device) and needs a buffer with "
+                     f"the device store, add_steps (DeviceReplayBuffer)")
+        else:
+            needs = "device_collect needs a buffer with the device store (DeviceReplayBuffer)"
+        raise ValueError(f"fit_vector: {needs}; {type(buffer).__name__} has none")
+    if device_collect:  # the episodes are in the buffer when its collect() returns
+        collector = DeviceVectorCollector(venv, buffer, n_step, gamma, alpha, weight=trajectory_weight,
+                                          min_length=k_steps, device_plan=device_plan)
+    else:
+        collector = _HostCollect(VectorCollector(venv, n_step, gamma, alpha), buffer, k_steps, trajectory_weight)
+
+    sample_kw = dict(num_trajectory=num_trajectory, k_steps=k_steps, sample_per_trajectory=sample_per_trajectory)
+    if prioritise:
+        sample_kw["with_indices"] = True
+    if all_obs:
+        sample_kw["all_obs"] = True
+    # (both priority functions are looked up in this module when they are called)
+    if priority_steps is None:
+        def priorities(model, batch):
+            return value_priorities(model, batch)
+    else:
+        def priorities(model, batch):
+            return unroll_value_priorities(model, batch, min(int(priority_steps), k_steps))
+    if is_beta is None:
+        beta = None
+    elif callable(is_beta):
+        def beta(training_step):
+            return float(is_beta(training_steps=training_step, max_training_steps=max_training_steps))
+    else:
+        def beta(training_step):
+            return float(is_beta)
+    reanalyse_kw = None
+    if reanalyse_every > 0 and _offers(buffer, "reanalyse"):
+        reanalyse_kw = dict(weight=trajectory_weight, num_simulations=num_simulations, **_mask_fn_of(venv))
+    return _FitPlan(buffer, collector, sample_kw, prioritise, priorities, beta, reanalyse_kw,
+                    _tester(test_env, num_simulations, num_test_episodes))
+
+
 def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, alpha=0.5, buffer=None,
                iterations: int = 100, steps_per_iteration: int = 64, num_simulations: int = 50, k_steps: int = 10,
                num_trajectory: int = 32, sample_per_trajectory: int = 1, num_update_per_iteration: int = 50,
@@ -488,105 +688,79 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
                reanalyse_every: int = 0, reanalyse_episodes=None, priority_update: bool = False,
                priority_steps=None, is_beta=None, device_collect: bool = False, device_plan: bool = False,
                all_obs=None):
-    """The reference's fit() loop (muax/train.py:175-241: temperature schedule, buffer sampling, update,
-    greedy test) with the acting half on a vector environment: per iteration `steps_per_iteration`
-    batched act() calls -> finished episodes -> buffer, then `num_update_per_iteration` updates.
-    `trajectory_weight`: "mean" is the reference's buffer weight (mean priority of the episode,
-    muax/train.py:171,203); "sum" weights an episode by its total priority, which undoes the bias of a
-    fixed collection window towards short episodes (many short episodes finish while one long one runs).
-    `reanalyse_every` > 0 (a buffer with `reanalyse`, i.e. the device buffer): before the updates of every
-    `reanalyse_every`-th iteration the `reanalyse_episodes` episodes (default: all) whose targets are the oldest are
-    searched again with the current network (`DeviceReplayBuffer.reanalyse`, `num_simulations` simulations, act()'s
-    other defaults), its key one extra split of the running key; 0: the key stream and every result are unchanged.
-    A `venv` with `invalid_actions_of` (the mask extension of muax_amd/envs.py, e.g. `Device2048`) hands it over as
-    `mask_fn`, so that no reanalysed search policy puts weight on a move that is illegal in its stored observation;
-    the collector passes such an environment's own mask to every act() of the collection (`DeviceVectorCollector`).
-    `priority_update` (a buffer with `update_priorities`, i.e. the device buffer): every batch is sampled with its
-    indices and, after its `update()`, `value_priorities` of the updated network are written back to the window starts
-    with the loop's `alpha` (exponent 1 when `alpha` is None) and `weight=trajectory_weight`.  False, or a buffer
-    without the method: the key stream and every result are unchanged.
-    `priority_steps`: None writes `value_priorities` back (one transition per window); an integer kp >= 1 writes
-    `unroll_value_priorities(model, batch, min(kp, k_steps))` instead, one priority for each of the first kp transitions
-    of every window.  Ignored where `priority_update` is off or the buffer has no `update_priorities`.
-    `is_beta`: importance-sampling correction of the prioritised draws -- a float in 0..1, or a schedule called as
-    `is_beta(training_steps=, max_training_steps=)` before every batch (as `temperature_fn` is) -- every batch is
-    sampled with `sample(is_beta=)` and its `update()` takes the returned weights as `sample_weight`; composes with
-    `priority_update` / `priority_steps`.  The weights are normalised by the largest one of the batch, so under data
-    parallelism by each rank's own batch maximum, not a global one.  A buffer whose `sample` takes no `is_beta` (the
-    host `TrajectoryReplayBuffer`) is a ValueError: dropping a correction that was asked for would change what is
-    learned.  None: the key stream and every result are unchanged.
-    `device_collect=True` (a buffer with the device store, `DeviceReplayBuffer`; any other is a ValueError) collects
-    with `DeviceVectorCollector` (`min_length=k_steps`, `weight=trajectory_weight`): the search results stay on the
-    device and the episodes are cut into the buffer in one launch; `episodes` and `G` of the metrics row come from the
-    host's rewards.  The same key stream and the same episodes as the host collector.  False: the key stream and every
-    result are unchanged.
-    A `venv` with `step_device` (a device environment, muax_amd/envs.py) is stepped on the device by that collector;
-    it needs `device_collect=True` and a buffer with the device store, and is a ValueError otherwise: stepping it
-    through host copies would hide the cost it exists to avoid.  A `test_env` with `step_device` is evaluated by
-    `test_vector_device` (no host hop per step), any other vector environment by `test_vector`; the value is the same.
-    `device_plan=True` (needs `device_collect=True` and a device environment; a ValueError otherwise) hands the flag to
-    that collector: the episodes are cut and their returns summed on the device (`DeviceVectorCollector`), `G` of the
-    metrics row is then the mean of sequential fp64 sums -- equal to the host's for integer rewards.  False: the key
-    stream and every result are unchanged.
-    `all_obs`: whether every batch is sampled with `sample(all_obs=True)`, an observation for every step of a window
-    (`DeviceReplayBuffer.sample`).  None asks for them exactly when `update()` trains with `loss.stochastic_loss_fn` (a
-    model on an `SMZNetwork`, `MuZero.trains_stochastic`) and the buffer's `sample` takes `all_obs`; the host
-    `TrajectoryReplayBuffer` returns every row anyway and is left alone.  True / False force it; True with a buffer
-    whose `sample` takes no `all_obs` is a ValueError.  So a stochastic model trains through this loop on a
-    `DeviceReplayBuffer` and a device environment, with `reanalyse_every`, `priority_update` and `is_beta` as for the
-    deterministic model; `priority_steps` with such a model is a ValueError unless the model unrolls its `SMZNetwork`
-    (`MuZero(..., stochastic_unroll_values=True)`, `MuZero.unrolls_stochastic`: the afterstate and chance dynamics with
-    the encoder's codes, from the observations `all_obs` hands out).  For any other model None changes nothing."""
-    if priority_steps is not None and int(priority_steps) < 1:
-        raise ValueError("priority_steps must be None or >= 1")
-    if trajectory_weight not in ("mean", "sum"):
-        raise ValueError("trajectory_weight must be 'mean' or 'sum'")
-    if device_plan and not (device_collect and hasattr(venv, "step_device")):
-        raise ValueError(f"fit_vector: device_plan needs device_collect=True and a device environment (one with "
-                         f"step_device); device_collect is {bool(device_collect)} and {type(venv).__name__} has "
-                         f"{'a' if hasattr(venv, 'step_device') else 'no'} step_device")
-    from .replay_buffer import TrajectoryReplayBuffer
-    from .train import _temperature_fn, test
+    """The reference's fit() loop (muax/train.py:175-241: temperature schedule, buffer sampling, update, greedy
+    test) with the acting half on a vector environment.  Per iteration: `steps_per_iteration` batched act() calls, the
+    finished episodes of at least `k_steps` steps into the buffer, an optional reanalysis, `num_update_per_iteration`
+    times sample -> update() -> optional priority write-back, every `test_interval`-th iteration a greedy test, one
+    metrics row; it stops after `iterations` or once `max_training_steps` updates are done.  All arguments are checked
+    against each other, the buffer, the environments and the model before `model.init` (`_fit_plan` lists the order);
+    what is refused is a ValueError.  Every option below at its default leaves the key stream and every result as they
+    are without it.  Returns the model.
+
+    venv: the vector environment that is collected from.  One with `step_device` (a device environment,
+        muax_amd/envs.py) is stepped on the device by `DeviceVectorCollector`; it needs `device_collect=True` and a
+        buffer with the device store and is refused otherwise: stepping it through host copies would hide the cost it
+        exists to avoid.  One with the mask extension of envs.py (e.g. `Device2048`) has its own mask passed to every
+        act() of the collection by that collector, and see `reanalyse_every`.
+    test_env: a gym-style environment (one with `observation_space`) is evaluated by the reference's `test` with
+        `num_test_episodes` episodes; a vector environment with `step_device` by `test_vector_device` (no host hop per
+        step), any other by `test_vector`; the value of the two is the same.
+    n_step, gamma, alpha: the n-step return and the priority exponent of `NStep` / `PNStep` (alpha None: weights 1).
+    buffer: default `TrajectoryReplayBuffer(500)`.  A buffer with `add_many` (the device buffer) gets a collection in
+        one call, any other one `add` per episode.
+    temperature_fn: called as `temperature_fn(max_training_steps=, training_steps=)` before every iteration; default
+        the reference's schedule.
+    metrics: a list that gets one dict per iteration: iteration, env_steps, episodes (all that finished), collect_s
+        (the collection alone, without the host route's buffer adds), G (the mean undiscounted return of all finished
+        episodes, NaN when none finished), loss (when the buffer held something), training_step, test_G (when tested).
+    trajectory_weight: "mean" is the reference's buffer weight (mean priority of the episode, muax/train.py:171,203);
+        "sum" weights an episode by its total priority, which undoes the bias of a fixed collection window towards
+        short episodes (many short episodes finish while one long one runs).  Anything else is refused.
+    reanalyse_every: > 0 with a buffer with `reanalyse` (the device buffer): before the updates of every
+        `reanalyse_every`-th iteration the `reanalyse_episodes` episodes (default: all) whose targets are the oldest are
+        searched again with the current network (`DeviceReplayBuffer.reanalyse`, `num_simulations` simulations, act()'s
+        other defaults), its key one extra split of the running key.  A `venv` with `invalid_actions_of` hands it over
+        as `mask_fn`, so that no reanalysed search policy puts weight on a move that is illegal in its stored
+        observation.  Ignored for a buffer without the method and while the buffer is empty.
+    priority_update: with a buffer with `update_priorities` (the device buffer) every batch is sampled with its
+        indices and, after its `update()`, new priorities from the updated network are written back to the window
+        starts with the loop's `alpha` (exponent 1 when `alpha` is None) and `weight=trajectory_weight`.  Ignored for a
+        buffer without the method.
+    priority_steps: which priorities are written back.  None: `value_priorities` (one transition per window); an
+        integer kp >= 1: `unroll_value_priorities(model, batch, min(kp, k_steps))`, one priority for each of the first
+        kp transitions of every window.  Below 1 is refused.  Ignored where nothing is written back; where something
+        is, a stochastic model (`MuZero.trains_stochastic`) is refused unless it unrolls its `SMZNetwork`
+        (`MuZero(..., stochastic_unroll_values=True)`, `MuZero.unrolls_stochastic`: the afterstate and chance dynamics
+        with the encoder's codes, from the observations `all_obs` hands out).
+    is_beta: importance-sampling correction of the prioritised draws: a float in 0..1, or a schedule called as
+        `is_beta(training_steps=, max_training_steps=)` before every batch (as `temperature_fn` is).  Every batch is
+        sampled with `sample(is_beta=)` and its `update()` takes the returned weights as `sample_weight`; composes with
+        `priority_update` / `priority_steps`.  The weights are normalised by the largest one of the batch, so under
+        data parallelism by each rank's own batch maximum, not a global one.  A buffer whose `sample` takes no
+        `is_beta` (the host `TrajectoryReplayBuffer`) is refused: dropping a correction that was asked for would change
+        what is learned.  A number outside 0..1 is refused.
+    device_collect: True collects with `DeviceVectorCollector` (`min_length=k_steps`, `weight=trajectory_weight`): the
+        search results stay on the device and the episodes are cut into the buffer in one launch; `episodes` and `G`
+        come from the host's rewards.  The same key stream and the same episodes as the host collector.  Needs a buffer
+        with the device store (`DeviceReplayBuffer`); any other is refused.
+    device_plan: True hands the flag to that collector: the episodes are cut and their returns summed on the device,
+        `G` is then the mean of sequential fp64 sums -- equal to the host's for integer rewards.  Needs
+        `device_collect=True` and a device environment; refused otherwise.
+    all_obs: whether every batch is sampled with `sample(all_obs=True)`, an observation for every step of a window
+        (`DeviceReplayBuffer.sample`).  None asks for them exactly when `update()` trains with
+        `loss.stochastic_loss_fn` (a model on an `SMZNetwork`, `MuZero.trains_stochastic`) and the buffer's `sample`
+        takes `all_obs`; the host `TrajectoryReplayBuffer` returns every row anyway and is left alone; for any other
+        model None changes nothing.  True / False force it; True with a buffer whose `sample` takes no `all_obs` is
+        refused.  So a stochastic model trains through this loop on a `DeviceReplayBuffer` and a device environment,
+        with `reanalyse_every`, `priority_update` and `is_beta` as for the deterministic model."""
+    plan = _fit_plan(model, venv, test_env, buffer, n_step=n_step, gamma=gamma, alpha=alpha,
+                     num_simulations=num_simulations, k_steps=k_steps, num_trajectory=num_trajectory,
+                     sample_per_trajectory=sample_per_trajectory, max_training_steps=max_training_steps,
+                     num_test_episodes=num_test_episodes, trajectory_weight=trajectory_weight,
+                     reanalyse_every=reanalyse_every, priority_update=priority_update, priority_steps=priority_steps,
+                     is_beta=is_beta, device_collect=device_collect, device_plan=device_plan, all_obs=all_obs)
+    buffer, collector = plan.buffer, plan.collector
     temperature_fn = temperature_fn or _temperature_fn
-    buffer = buffer if buffer is not None else TrajectoryReplayBuffer(500)
-    import inspect
-    sample_takes = inspect.signature(buffer.sample).parameters
-    if is_beta is not None:
-        if "is_beta" not in sample_takes:
-            raise ValueError(f"fit_vector: is_beta needs a buffer whose sample() takes is_beta (DeviceReplayBuffer); "
-                             f"{type(buffer).__name__}.sample does not")
-        if not callable(is_beta) and not 0.0 <= float(is_beta) <= 1.0:
-            raise ValueError("fit_vector: is_beta must be None, a number in 0..1 or a callable")
-    stochastic = bool(getattr(model, "trains_stochastic", False))  # (update()'s own predicate for stochastic_loss_fn)
-    if all_obs and "all_obs" not in sample_takes:
-        raise ValueError(f"fit_vector: all_obs needs a buffer whose sample() takes all_obs (DeviceReplayBuffer); "
-                         f"{type(buffer).__name__}.sample does not")
-    all_obs = (stochastic and "all_obs" in sample_takes) if all_obs is None else bool(all_obs)
-    prioritise = bool(priority_update) and hasattr(buffer, "update_priorities")
-    if prioritise and priority_steps is not None and stochastic and not getattr(model, "unrolls_stochastic", False):
-        raise ValueError("fit_vector: priority_update with priority_steps needs MuZero.unroll_values, which is not built "
-                         "for an SMZNetwork (a stochastic model); use priority_steps=None (value_priorities)")
-    on_device = hasattr(venv, "step_device")
-    if on_device and not device_collect:
-        raise ValueError(f"fit_vector: {type(venv).__name__} is a device environment (it has step_device) and needs "
-                         f"device_collect=True; device_collect is False")
-    if device_collect:
-        if not hasattr(buffer, "add_steps"):
-            if on_device:
-                needs = (f"{type(venv).__name__} is a device environment (it has step_device) and needs a buffer with "
-                         f"the device store, add_steps (DeviceReplayBuffer)")
-            else:
-                needs = "device_collect needs a buffer with the device store (DeviceReplayBuffer)"
-            raise ValueError(f"fit_vector: {needs}; {type(buffer).__name__} has none")
-        collector = DeviceVectorCollector(venv, buffer, n_step, gamma, alpha, weight=trajectory_weight,
-                                          min_length=k_steps, device_plan=device_plan)
-    else:
-        collector = VectorCollector(venv, n_step, gamma, alpha)
-    sample_kw = dict(num_trajectory=num_trajectory, k_steps=k_steps, sample_per_trajectory=sample_per_trajectory)
-    if prioritise:
-        sample_kw["with_indices"] = True
-    if all_obs:
-        sample_kw["all_obs"] = True
     key = prng.PRNGKey(random_seed)
     key, test_key, subkey = prng.split(key, 3)
     model.init(subkey, np.asarray(venv.reset())[:1].astype(float))
@@ -594,56 +768,29 @@ def fit_vector(model, venv, test_env, n_step: int = 10, gamma: float = 0.997, al
     for it in range(iterations):
         temperature = temperature_fn(max_training_steps=max_training_steps, training_steps=training_step)
         t0 = time.perf_counter()
-        if device_collect:  # the episodes are in the buffer when collect() returns
-            finished, key, env_steps = collector.collect(model, key, steps_per_iteration, num_simulations, temperature)
-            row = {"iteration": it, "env_steps": env_steps, "episodes": len(finished),
-                   "collect_s": time.perf_counter() - t0,
-                   "G": float(np.mean([g for _, g, _ in finished])) if finished else float("nan")}
-        else:
-            trajs, key, env_steps = collector.collect(model, key, steps_per_iteration, num_simulations, temperature)
-            collect_s = time.perf_counter() - t0
-            keep = [tr for tr in trajs if len(tr) >= k_steps]
-            weights = [tr.weights.mean() if trajectory_weight == "mean" else tr.weights.sum() for tr in keep]
-            if hasattr(buffer, "add_many"):  # (the device buffer: one upload and one launch for the collection)
-                buffer.add_many(keep, weights)
-            else:
-                for tr, w in zip(keep, weights):
-                    buffer.add(tr, w)
-            row = {"iteration": it, "env_steps": env_steps, "episodes": len(trajs), "collect_s": collect_s,
-                   "G": float(np.mean([float(np.sum(t.rewards)) for t in trajs])) if trajs else float("nan")}
-        if reanalyse_every > 0 and hasattr(buffer, "reanalyse") and len(buffer) and (it + 1) % reanalyse_every == 0:
+        finished, key, env_steps = collector.collect(model, key, steps_per_iteration, num_simulations, temperature)
+        row = {"iteration": it, "env_steps": env_steps, "episodes": len(finished),
+               "collect_s": time.perf_counter() - t0 - collector.store_s,
+               "G": float(np.mean([g for _, g, _ in finished])) if finished else float("nan")}
+        if plan.reanalyse_kw is not None and len(buffer) and (it + 1) % reanalyse_every == 0:
             key, subkey = prng.split(key)
-            masks = {"mask_fn": venv.invalid_actions_of} if hasattr(venv, "invalid_actions_of") else {}
-            buffer.reanalyse(model, subkey, n_step, gamma, alpha, weight=trajectory_weight,
-                             serials=buffer.stalest(reanalyse_episodes or len(buffer)), num_simulations=num_simulations,
-                             **masks)
+            buffer.reanalyse(model, subkey, n_step, gamma, alpha,
+                             serials=buffer.stalest(reanalyse_episodes or len(buffer)), **plan.reanalyse_kw)
         if len(buffer):
             loss = 0.0
             for _ in range(num_update_per_iteration):
-                if is_beta is not None:
-                    beta = is_beta(training_steps=training_step, max_training_steps=max_training_steps) \
-                        if callable(is_beta) else is_beta
-                    sample_kw["is_beta"] = float(beta)
-                got = buffer.sample(**sample_kw)  # batch[, indices][, isw]
-                got = got if prioritise or is_beta is not None else (got,)
-                batch, indices = got[0], got[1] if prioritise else None
-                loss += model.update(batch, **({} if is_beta is None else {"sample_weight": got[-1]}))["loss"]
-                if prioritise:
-                    prio = value_priorities(model, batch) if priority_steps is None else \
-                        unroll_value_priorities(model, batch, min(int(priority_steps), k_steps))
-                    buffer.update_priorities(indices, prio,
+                sample_kw = plan.sample_kw if plan.beta is None else dict(plan.sample_kw, is_beta=plan.beta(training_step))
+                batch, indices, update_kw = _unpack_sample(buffer.sample(**sample_kw), plan.prioritise,
+                                                           plan.beta is not None)
+                loss += model.update(batch, **update_kw)["loss"]
+                if plan.prioritise:
+                    buffer.update_priorities(indices, plan.priorities(model, batch),
                                              alpha=1.0 if alpha is None else alpha, weight=trajectory_weight)
                 training_step += 1
             row["loss"] = loss / num_update_per_iteration
         row["training_step"] = training_step
         if it % test_interval == 0:
-            if hasattr(test_env, "observation_space"):  # a gym-style environment: the reference's test()
-                row["test_G"] = test(model, test_env, test_key, num_simulations=num_simulations,
-                                     num_test_episodes=num_test_episodes)
-            elif hasattr(test_env, "step_device"):  # a device environment: evaluated where it lives, the same value
-                row["test_G"] = test_vector_device(model, test_env, test_key, num_simulations)
-            else:  # a vector environment: all its episodes in lock step
-                row["test_G"] = test_vector(model, test_env, test_key, num_simulations)
+            row["test_G"] = plan.tester(model, test_key)
         if metrics is not None:
             metrics.append(row)
         if training_step >= max_training_steps:
