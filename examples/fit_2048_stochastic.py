@@ -127,6 +127,9 @@ def main():
     ap.add_argument("--root-in-kernel", action="store_true",
                     help="act() with root inference by the library too (MuZero(stochastic_root_in_kernel=True)): no torch "
                          "module in an act(); with --one-launch an act() is one launch")
+    ap.add_argument("--train-on-demand", action="store_true",
+                    help="with --fused-update: build an instance of the training kernel for a shape the library does not list "
+                         "(MuZero(stochastic_train_on_demand=True)); a shape whose instance would spill stays on autograd")
     ap.add_argument("--fused-update", action="store_true",
                     help="update() on the fused training kernel (MuZero(stochastic_fused_update=True)) instead of autograd")
     ap.add_argument("--priority-steps", type=int, default=None, metavar="K",
@@ -143,7 +146,7 @@ def main():
     net = muax.create_stochastic_muzero_network(E, venv.num_actions, Cn, 2 * support_size + 1)
     model = muax.MuZero(net, policy="stochastic", discount=discount, support_size=support_size,
                         optimizer=muax.optimizers.create_optimizer("adam", 2e-3), stochastic_one_launch=args.one_launch,
-                        stochastic_fused_update=args.fused_update, stochastic_root_in_kernel=args.root_in_kernel,
+                        stochastic_fused_update=args.fused_update, stochastic_train_on_demand=args.train_on_demand, stochastic_root_in_kernel=args.root_in_kernel,
                         stochastic_unroll_values=args.priority_steps is not None)
     if args.priority_steps is not None and args.host_buffer:
         ap.error("--priority-steps needs the device route (fit_vector on a DeviceReplayBuffer), not --host-buffer")

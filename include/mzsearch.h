@@ -470,10 +470,12 @@ int mzs_mlp_loss_grad_weighted(const mzs_mlp_weights *w, const mzs_train_args *a
  * Refusals, all before any launch: a null pointer or a struct size mismatch, a workspace below
  * mzs_stochastic_mlp_train_workspace_bytes (MZS_E_INVALID); obs_dim beyond 32, support_size outside 8 .. 31, an
  * (A, C, E, F) without a listed kernel instance ("no kernel instance"), unroll_steps beyond what the instance keeps in
- * LDS ("too large for the LDS", the limit named) (MZS_E_UNSUPPORTED). */
+ * LDS ("too large for the LDS", the limit named) (MZS_E_UNSUPPORTED).  An instance registered with
+ * mzs_register_stochastic_train_dispatch serves its own (A, C, E, F) up to its own observation cap (at most 128); the
+ * lookup comes before the obs_dim refusal, and with nothing registered every answer is the one above. */
 typedef struct mzs_stochastic_train_weights {
   int32_t struct_size;        /* = sizeof(mzs_stochastic_train_weights) */
-  int32_t obs_dim;            /* 1 .. 32 (the training entry's limit; mzs_stochastic_mlp_unroll_values: 1 .. 128) */
+  int32_t obs_dim;            /* 1 .. 32 (the training entry's listed instances; on-demand ones and mzs_stochastic_mlp_unroll_values: 1 .. 128) */
   int32_t support_size;       /* 8 .. 31 */
   int32_t reserved0;
   const float *repr_w, *repr_b;               /* representation      [obs_dim,E] [E] */
@@ -683,6 +685,19 @@ int mzs_fused_jit_abi(void);
  * Wide shapes exist as on-demand instances only: the library lists none. */
 int mzs_register_train_dispatch(void *launch, int32_t num_actions, int32_t embed_dim, int32_t full_support_size, int32_t jit_abi);
 int mzs_train_jit_abi(void);
+/* ... and for the training step of the default stochastic MLP family: mzs_stochastic_mlp_loss_grad lists four
+ * (A, C, E, F = 2 support_size + 1) tuples at an observation cap of 32.  muax_amd/csrc/mz_stoch_train_jit.hip compiled
+ * for another tuple and an observation cap of 32, 64, 96 or 128 gives a side library whose `mzs_jit_stoch_train_launch`
+ * is passed here with its `mzs_jit_stoch_train_shape` values and the value of its `mzs_jit_stoch_train_abi` (must equal
+ * mzs_stochastic_train_jit_abi(): the argument block over 34 arrays).  Later mzs_stochastic_mlp_loss_grad calls of that
+ * tuple with obs_dim <= obs_cap take it (the smallest sufficient cap when several are registered), after the listed
+ * instances; an unroll beyond the instance's own LDS plan is still refused ("too large for the LDS", its limit named).
+ * The kernel's limits bound what can be built: num_actions 1..16, num_actions + num_chance_outcomes <= 64,
+ * embed_dim 1..64, F in 17..63 (muax_amd/_jit.py::stochastic_train_plan).  MZS_E_INVALID for a null launcher, another
+ * ABI word or an obs_cap that is none of the four. */
+int mzs_register_stochastic_train_dispatch(void *launch, int32_t num_actions, int32_t num_chance_outcomes, int32_t embed_dim,
+                                           int32_t full_support_size, int32_t obs_cap, int32_t jit_abi);
+int mzs_stochastic_train_jit_abi(void);
 /* Shapes the fused kernel cannot be instantiated for at all (more than 16 actions, more than 255 simulations, embeddings
  * wider than 64): allow != 0 lets mzs_act_mlp / mzs_act_mlp_host serve them through the generic route instead of
  * returning MZS_E_UNSUPPORTED -- the trio with run-time shapes (num_actions <= 64, support_size 8..31), tree in HBM with

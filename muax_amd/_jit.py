@@ -12,6 +12,7 @@ step-wise path.  MUAX_AMD_JIT=0 turns the on-demand build off.
 from __future__ import annotations
 
 import ctypes as C
+import ctypes as C_  # (where a function's own argument is named C: the stochastic family's chance outcomes)
 import hashlib
 import os
 import subprocess
@@ -96,9 +97,9 @@ def _source_hash() -> str:
     return h.hexdigest()[:12]
 
 
-def _run_compiler(cmd, log, verbose) -> bool:
+def _run_compiler(cmd, log, verbose, keep_log: bool = False) -> bool:
     """hipcc with its output kept: `log` holds the command and everything the compiler said (a failed on-demand build
-    used to be silent); the file stays after a failure and is removed after a success."""
+    used to be silent); the file stays after a failure and is removed after a success, unless `keep_log`."""
     global last_build_log
     with open(log, "w") as lf:
         lf.write(" ".join(cmd) + "\n")
@@ -109,7 +110,8 @@ def _run_compiler(cmd, log, verbose) -> bool:
     if rc != 0:
         last_build_log = log
         return False
-    os.remove(log)
+    if not keep_log:
+        os.remove(log)
     return True
 
 
@@ -206,15 +208,63 @@ def ensure_instance(A: int, E: int, F: int, S: int, verbose: bool = False, gumbe
     return True
 
 
-def _train_hash() -> str:
+def _train_hash(sources=None, salt: str = "") -> str:
     h = hashlib.sha256()
-    for f in _TRAIN_SOURCES + [_build._ABI]:
+    for f in (_TRAIN_SOURCES if sources is None else sources) + [_build._ABI]:
         with open(os.path.join(_build.CSRC, f), "rb") as fh:
             h.update(fh.read())
     with open(os.path.abspath(__file__), "rb") as fh:
         h.update(fh.read())
     h.update("\0".join(_build.FLAGS).encode())
+    h.update(salt.encode())
     return h.hexdigest()[:12]
+
+
+def _ensure_side_library(shape, so, unit, defines, verbose, accept=None) -> bool:
+    """THE body of every on-demand training instance: build `unit` with `defines` into `so` once (under the cache
+    directory's file lock, through a temporary file), compiler output in the .log beside it.  `shape`: the key in
+    _loaded / _failed.  `accept(log_text)`: called on the compiler's output of a build that succeeded; a string is a
+    reason to decline the instance -- it is written to the log, which then stays, nothing is installed and the answer is
+    False.  True when `so` exists afterwards; False (shape noted in _failed) without a compiler, without a writable cache
+    directory, or when the build fails or is declined."""
+    global last_build_log
+    try:
+        cc = _build.hipcc()
+    except RuntimeError:
+        return False
+    try:
+        os.makedirs(JIT_DIR, exist_ok=True)
+        if not os.path.exists(so):
+            import fcntl
+            with open(os.path.join(JIT_DIR, ".jit.lock"), "w") as lock:
+                fcntl.flock(lock, fcntl.LOCK_EX)  # ranks that miss the same shape build it once
+                if not os.path.exists(so):
+                    tmp = so + f".tmp{os.getpid()}"
+                    log = so[:-3] + ".log"
+                    cmd = [cc] + _build.FLAGS + list(defines) + ["-shared", os.path.join(_build.CSRC, unit), "-o", tmp]
+                    try:
+                        if accept is None:
+                            ok = _run_compiler(cmd, log, verbose)
+                        else:
+                            ok = _run_compiler(cmd, log, verbose, keep_log=True)
+                            if ok:
+                                with open(log, errors="replace") as f:
+                                    why = accept(f.read())
+                                if why:
+                                    with open(log, "a") as f:
+                                        f.write(f"\nnot registered: {why}\n")
+                                    last_build_log, ok = log, False
+                        if not ok:
+                            _failed.add(shape)
+                            return False
+                        os.replace(tmp, so)
+                    finally:
+                        if os.path.exists(tmp):
+                            os.remove(tmp)
+    except OSError:
+        _failed.add(shape)
+        return False
+    return True
 
 
 def _ensure_train(kind: str, prefix: str, defines, A: int, E: int, F: int, verbose: bool) -> bool:
@@ -227,31 +277,9 @@ def _ensure_train(kind: str, prefix: str, defines, A: int, E: int, F: int, verbo
         return True
     if shape in _failed:
         return False
-    try:
-        cc = _build.hipcc()
-    except RuntimeError:
-        return False
     so = os.path.join(JIT_DIR, f"{prefix}_a{A}_e{E}_f{F}-{_train_hash()}.so")
-    try:
-        os.makedirs(JIT_DIR, exist_ok=True)
-        if not os.path.exists(so):
-            import fcntl
-            with open(os.path.join(JIT_DIR, ".jit.lock"), "w") as lock:
-                fcntl.flock(lock, fcntl.LOCK_EX)  # ranks that miss the same shape build it once
-                if not os.path.exists(so):
-                    tmp = so + f".tmp{os.getpid()}"
-                    cmd = [cc] + _build.FLAGS + [f"-DMZ_TRAIN_A={A}", f"-DMZ_TRAIN_E={E}", f"-DMZ_TRAIN_F={F}"] + \
-                        list(defines) + ["-shared", os.path.join(_build.CSRC, "mz_train_jit.hip"), "-o", tmp]
-                    try:
-                        if not _run_compiler(cmd, so[:-3] + ".log", verbose):
-                            _failed.add(shape)
-                            return False
-                        os.replace(tmp, so)
-                    finally:
-                        if os.path.exists(tmp):
-                            os.remove(tmp)
-    except OSError:
-        _failed.add(shape)
+    if not _ensure_side_library(shape, so, "mz_train_jit.hip",
+                                [f"-DMZ_TRAIN_A={A}", f"-DMZ_TRAIN_E={E}", f"-DMZ_TRAIN_F={F}"] + list(defines), verbose):
         return False
     from . import _lib
     L = _lib.load()
@@ -296,3 +324,138 @@ def ensure_wide_train_instance(A: int, E: int, F: int, verbose: bool = False) ->
     if not (17 <= A <= 64 and 1 <= E <= 64 and 17 <= F <= 63):
         return False
     return _ensure_train("train_wide", "mztrainwide", WIDE_TRAIN_DEFINES, A, E, F, verbose)
+
+
+# ---- the stochastic family's training step (muax_amd/csrc/mz_stoch_train_jit.hip) ----
+_STOCH_TRAIN_SOURCES = ["mz_stoch_train_jit.hip", "mz_train_launch.h", "mz_stoch_train.cuh", "mz_train_blocks.cuh", "mz_spec.cuh",
+                        "mz_host.h"]
+STOCH_TRAIN_LDS_BYTES = 160 * 1024  # mz_train_blocks.cuh: TRAIN_LDS_BYTES
+# What one lane's 512 registers (256 VGPRs + 256 AGPRs, one wavefront per SIMD) leave for gradient tiles.  A 16 x 16
+# tile is four registers that live through the whole backward sweep.  The listed (4, 32, 32, 63) instance has 42 tiles and
+# takes 256 + 206 = 462 registers, so 294 are the rest of the kernel; 512 - 294 = 218 registers hold 54 tiles.  A shape
+# beyond that cannot be built without scratch.  (Necessary, not sufficient: the build's own scratch figure decides --
+# profiles/stochastic_train.txt has shapes of 37 to 48 tiles that spill.)
+STOCH_TRAIN_MAX_TILES = 54
+_RESOURCE_USAGE = ["-Rpass-analysis=kernel-resource-usage"]
+
+
+def _slots(n: int) -> int:
+    return (n + 15) // 16
+
+
+def stochastic_train_tiles(A: int, C: int, E: int, F: int, obs_cap: int) -> int:
+    """Number of 16 x 16 weight-gradient tiles mz_stoch_train_kernel keeps in registers across the unroll."""
+    ES, FS, CS, XAS, XCS = _slots(E), _slots(F), _slots(C), _slots(E + A), _slots(E + C)
+    # ad1, ad2 | av1, av2 | ac1, ac2 | cr1, cr2 | cn1, cn2 | pv1, pv2 | pp1, pp2 | en1, en2
+    return XAS + ES + ES + FS + ES + CS + XCS + FS + XCS + ES + ES + FS + ES + 1 + obs_cap // 16 + CS
+
+
+def stochastic_train_plan(A: int, C: int, E: int, F: int, obs_dim: int):
+    """StochTrainCfg's arithmetic (muax_amd/csrc/mz_stoch_train.cuh) for an on-demand instance that serves the shape:
+    (obs_cap, weight_words, max_unroll) -- obs_dim rounded up to 32 / 64 / 96 / 128, the words of LDS the weights take,
+    the longest unroll the rest of the 160 KiB keeps -- or None when no instance can exist: outside 1 <= A <= 16, 1 <= C,
+    A + C <= 64, 1 <= E <= 64, 17 <= F <= 63, 1 <= obs_dim <= 128; where not even L = 2 fits in LDS; beyond
+    STOCH_TRAIN_MAX_TILES gradient tiles (the register file)."""
+    if not (1 <= A <= 16 and 1 <= C and A + C <= 64 and 1 <= E <= 64 and 17 <= F <= 63 and 1 <= obs_dim <= 128):
+        return None
+    OB, H, XA, XC = 32 * ((obs_dim + 31) // 32), 16, E + A, E + C
+
+    def blk(k, n):
+        return k * (16 * _slots(n) + 1) + 16 * _slots(n)
+
+    words = sum(blk(k, n) for k, n in ((XA, H), (H, E), (E, H), (H, F), (E, H), (H, C), (XC, H), (H, F), (XC, H), (H, E),
+                                       (E, H), (H, F), (E, H), (H, A), (OB, H), (H, C)))
+    words = ((words + 3) // 4) * 4
+    max_unroll = (STOCH_TRAIN_LDS_BYTES // 4 - words) // (2 * 16 * 16 * _slots(E) + 16)
+    if max_unroll < 2 or stochastic_train_tiles(A, C, E, F, OB) > STOCH_TRAIN_MAX_TILES:
+        return None
+    return OB, words, max_unroll
+
+
+def parse_resource_usage(log_text: str, kernel: str):
+    """The compiler's -Rpass-analysis=kernel-resource-usage remarks for the first function whose name contains `kernel`:
+    {'vgprs', 'agprs', 'scratch_bytes' (per lane), 'lds_bytes' (static)}, or None when the log has no such remarks."""
+    import re
+    for m in re.finditer(r"Function Name: (\S+)(.*?)LDS Size \[bytes/block\]: (\d+)", log_text, re.S):
+        if kernel in m.group(1):
+            body = m.group(2)
+            v, a, s = (re.search(p + r": (\d+)", body) for p in (r" VGPRs", r"AGPRs", r"ScratchSize \[bytes/lane\]"))
+            if v and a and s:
+                return {"vgprs": int(v.group(1)), "agprs": int(a.group(1)), "scratch_bytes": int(s.group(1)),
+                        "lds_bytes": int(m.group(3))}
+    return None
+
+
+def _stochastic_train_file(A, C, E, F, OB) -> str:
+    tag = _train_hash(_STOCH_TRAIN_SOURCES, "\0".join(_RESOURCE_USAGE))
+    return os.path.join(JIT_DIR, f"mzstochtrain_a{A}_c{C}_e{E}_f{F}_o{OB}-{tag}.so")
+
+
+def stochastic_train_instance_info(A: int, C: int, E: int, F: int, obs_dim: int):
+    """Figures of the on-demand instance for the shape, from its build's own compiler remarks (kept beside the side
+    library as <file>.log): {'vgprs', 'agprs', 'scratch_bytes', 'lds_bytes', 'max_unroll', 'obs_cap'} -- `lds_bytes` the
+    dynamic LDS of a launch at max_unroll -- or None when the plan declines the shape or nothing has been built."""
+    pl = stochastic_train_plan(A, C, E, F, obs_dim)
+    if pl is None:
+        return None
+    OB, words, max_unroll = pl
+    log = _stochastic_train_file(A, C, E, F, OB)[:-3] + ".log"
+    if not os.path.exists(log):
+        return None
+    with open(log, errors="replace") as f:
+        info = parse_resource_usage(f.read(), "mz_stoch_train_kernel")
+    if info is None:
+        return None
+    info.update(max_unroll=max_unroll, obs_cap=OB, lds_bytes=4 * (words + max_unroll * (2 * 16 * 16 * _slots(E) + 16)))
+    return info
+
+
+def _no_scratch(log_text: str):
+    info = parse_resource_usage(log_text, "mz_stoch_train_kernel")
+    if info is None:
+        return "the compiler reported no resource usage for mz_stoch_train_kernel"
+    if info["scratch_bytes"]:
+        return (f"the instance spills {info['scratch_bytes']} bytes of scratch per lane ({info['vgprs']} VGPRs + "
+                f"{info['agprs']} AGPRs): the shape is beyond the register file")
+    return None
+
+
+def ensure_stochastic_train_instance(A: int, C: int, E: int, F: int, obs_dim: int, verbose: bool = False) -> bool:
+    """Make sure mzs_stochastic_mlp_loss_grad can serve (num_actions, num_chance_outcomes, embedding_dim,
+    F = 2 support_size + 1) with observations `obs_dim` wide: True when an on-demand instance of the stochastic family's
+    fused training-step kernel (muax_amd/csrc/mz_stoch_train_jit.hip at the plan's observation cap) is registered -- built
+    now (one translation unit, cached as muax_amd/lib/jit/mzstochtrain_<shape>-<source hash>.so with its compiler remarks
+    in the .log beside it) or earlier.  False when stochastic_train_plan declines the shape, there is no compiler, the
+    build fails, the build reports scratch (such an instance is never registered; the .log says so, build_log_tail()), or
+    MUAX_AMD_JIT=0."""
+    if os.environ.get("MUAX_AMD_JIT", "1") == "0":
+        return False
+    pl = stochastic_train_plan(A, C, E, F, obs_dim)
+    if pl is None:
+        return False
+    OB, words, max_unroll = pl
+    shape = ("stoch_train", A, C, E, F, OB)
+    if shape in _loaded:
+        return True
+    if shape in _failed:
+        return False
+    so = _stochastic_train_file(A, C, E, F, OB)
+    defines = [f"-DMZ_STOCH_A={A}", f"-DMZ_STOCH_C={C}", f"-DMZ_STOCH_E={E}", f"-DMZ_STOCH_F={F}", f"-DMZ_STOCH_OB={OB}"]
+    if not _ensure_side_library(shape, so, "mz_stoch_train_jit.hip", defines + _RESOURCE_USAGE, verbose, accept=_no_scratch):
+        return False
+    from . import _lib
+    L = _lib.load()
+    side = C_.CDLL(so)
+    side.mzs_jit_stoch_train_abi.restype = C_.c_int
+    got = tuple(C_.c_int32() for _ in range(5))
+    side.mzs_jit_stoch_train_shape(*(C_.byref(x) for x in got))
+    if tuple(x.value for x in got) != (A, C, E, F, OB):  # the file name said so; the code inside must agree
+        raise RuntimeError(f"{so}: built for shape {tuple(x.value for x in got)}, asked for {(A, C, E, F, OB)}")
+    words3 = (C_.c_int32 * 3)()
+    side.mzs_jit_stoch_train_plan(words3)
+    if (words3[0], words3[2]) != (words, max_unroll):
+        raise RuntimeError(f"{so}: its LDS plan {tuple(words3)} is not stochastic_train_plan's {(words, max_unroll)}")
+    fn = C_.cast(side.mzs_jit_stoch_train_launch, C_.c_void_p)
+    _lib.check(L.mzs_register_stochastic_train_dispatch(fn, A, C, E, F, OB, side.mzs_jit_stoch_train_abi()))
+    _loaded[shape] = side
+    return True

@@ -405,6 +405,8 @@ ENTRIES = {
     "mzs_fused_jit_abi": (C.c_int, []),
     "mzs_register_train_dispatch": (C.c_int, [_vp, _i32, _i32, _i32, _i32]),
     "mzs_train_jit_abi": (C.c_int, []),
+    "mzs_register_stochastic_train_dispatch": (C.c_int, [_vp] + [_i32] * 6),
+    "mzs_stochastic_train_jit_abi": (C.c_int, []),
     "mzs_mlp_allow_generic": (C.c_int, [_vp, _i32]),
     "mzs_mlp_allow_wide": (C.c_int, [_vp, _i32]),
     "mzs_mlp_allow_wide_gumbel": (C.c_int, [_vp, _i32]),

@@ -20,6 +20,9 @@ std::vector<mz::FusedDispatch> g_jit_dispatch_muzero;  // MuZero-policy-only ins
 // training-step instances built on demand (mz_train_jit.hip): launcher of one (A, E, F = 2 support + 1) each
 struct JitTrain { int A, E, F; mzh::JitTrainLaunch launch; };
 std::vector<JitTrain> g_jit_train;
+// ... of the stochastic family (mz_stoch_train_jit.hip): one (A, C, E, F) at one observation cap each
+struct JitStochTrain { int A, C, E, F, OB; mzh::JitTrainLaunch launch; };
+std::vector<JitStochTrain> g_jit_stoch_train;
 
 }  // namespace
 
@@ -34,6 +37,13 @@ mzh::JitTrainLaunch mzh::jit_train_instance(int A, int E, int F) {
   for (const JitTrain& t : g_jit_train)
     if (t.A == A && t.E == E && t.F == F) return t.launch;
   return nullptr;
+}
+mzh::JitTrainLaunch mzh::jit_stochastic_train_instance(int A, int C, int E, int F, int obs_dim) {
+  std::lock_guard<std::mutex> lock(g_jit_mutex);
+  const JitStochTrain* best = nullptr;
+  for (const JitStochTrain& t : g_jit_stoch_train)
+    if (t.A == A && t.C == C && t.E == E && t.F == F && obs_dim >= 1 && obs_dim <= t.OB && (!best || t.OB < best->OB)) best = &t;
+  return best ? best->launch : nullptr;
 }
 void mz::jit_dispatchers(int mode, std::vector<FusedDispatch>* out) {
   std::lock_guard<std::mutex> lock(g_jit_mutex);
@@ -55,6 +65,23 @@ int mzs_register_train_dispatch(void* launch, int32_t num_actions, int32_t embed
   for (const JitTrain& t : g_jit_train)
     if (t.A == num_actions && t.E == embed_dim && t.F == full_support) return MZS_OK;
   g_jit_train.push_back({num_actions, embed_dim, full_support, reinterpret_cast<mzh::JitTrainLaunch>(launch)});
+  return MZS_OK;
+}
+
+int mzs_register_stochastic_train_dispatch(void* launch, int32_t num_actions, int32_t num_chance_outcomes, int32_t embed_dim,
+                                           int32_t full_support, int32_t obs_cap, int32_t jit_abi) {
+  if (!launch) return fail(nullptr, MZS_E_INVALID, "mzs_register_stochastic_train_dispatch: null");
+  if (jit_abi != mzs_stochastic_train_jit_abi())
+    return fail(nullptr, MZS_E_INVALID,
+                "mzs_register_stochastic_train_dispatch: the side library was built from other sources (ABI)");
+  if (obs_cap != 32 && obs_cap != 64 && obs_cap != 96 && obs_cap != 128)
+    return fail(nullptr, MZS_E_INVALID, "mzs_register_stochastic_train_dispatch: obs_cap must be 32, 64, 96 or 128");
+  std::lock_guard<std::mutex> lock(g_jit_mutex);
+  for (const JitStochTrain& t : g_jit_stoch_train)
+    if (t.A == num_actions && t.C == num_chance_outcomes && t.E == embed_dim && t.F == full_support && t.OB == obs_cap)
+      return MZS_OK;
+  g_jit_stoch_train.push_back({num_actions, num_chance_outcomes, embed_dim, full_support, obs_cap,
+                               reinterpret_cast<mzh::JitTrainLaunch>(launch)});
   return MZS_OK;
 }
 

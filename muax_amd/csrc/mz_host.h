@@ -30,6 +30,9 @@ int fail(mzs_handle* h, int code, const char* fmt, const char* a = "");
 // kept in mz_api.hip): the instance for (A, E, F = 2 support + 1), or nullptr
 using JitTrainLaunch = int (*)(const void* train_params, void* stream, char* err, int errlen);
 JitTrainLaunch jit_train_instance(int A, int E, int F);
+// ... of the stochastic family's training step (mz_stoch_train_jit.hip; mzs_register_stochastic_train_dispatch): the
+// instance for (A, C, E, F) whose observation cap is the smallest that holds obs_dim, or nullptr
+JitTrainLaunch jit_stochastic_train_instance(int A, int C, int E, int F, int obs_dim);
 // per-device record of what hipFuncSetAttribute(MaxDynamicSharedMemorySize) has already granted ONE kernel (one static
 // LdsGrant per kernel instance).  Atomic: host threads that race can at worst both set the attribute (idempotent);
 // device ordinals beyond the table are never recorded, so the attribute is then set on every call (no aliasing)

@@ -24,19 +24,23 @@
 namespace mz {
 
 constexpr int STOCH_TRAIN_ARRAYS = 34;
-constexpr int STOCH_TRAIN_MAX_OBS = 32;  // two slots of encoder-layer tiles; mzs_stochastic_mlp_loss_grad names it
+constexpr int STOCH_TRAIN_MAX_OBS = 32;  // the listed instances' observation cap; mzs_stochastic_mlp_loss_grad names it
 // repr_w, repr_b; ad, av, ac, cr, cn, pv, pp each w1, b1, w2, b2 (mzs_stochastic_mlp_weights' order); en_w1 .. en_b2
 using StochTrainParams = TrainParamsT<STOCH_TRAIN_ARRAYS>;
 
-template <int A_, int C_, int E_, int F_>
+// OB_: the observation cap of the instance -- OS = OB / 16 slots of first-layer gradient tiles for the chance encoder
+// (the representation's go out 16 rows at a time), OB rows of the encoder's first layer in LDS.  32 for the listed
+// instances; an instance built on demand (mz_stoch_train_jit.hip) takes obs_dim rounded up to 32 / 64 / 96 / 128.
+template <int A_, int C_, int E_, int F_, int OB_ = STOCH_TRAIN_MAX_OBS>
 struct StochTrainCfg {
-  static constexpr int A = A_, C = C_, E = E_, F = F_, H = 16, XA = E_ + A_, XC = E_ + C_;
+  static constexpr int A = A_, C = C_, E = E_, F = F_, OB = OB_, H = 16, XA = E_ + A_, XC = E_ + C_;
   static constexpr int ES = (E + 15) / 16, FS = (F + 15) / 16, CS = (C + 15) / 16, AS = 1;
-  static constexpr int XAS = (XA + 15) / 16, XCS = (XC + 15) / 16, OS = STOCH_TRAIN_MAX_OBS / 16;
+  static constexpr int XAS = (XA + 15) / 16, XCS = (XC + 15) / 16, OS = OB / 16;
   static constexpr int NA = STOCH_TRAIN_ARRAYS;
   static constexpr const char* DIMS = "(A, C, E, F)";
   static_assert(A <= 16, "policy head in one slot");
   static_assert(C <= 64 && E <= 64 && F <= 63, "at most four slots per vector");
+  static_assert(OB == 32 || OB == 64 || OB == 96 || OB == 128, "observation cap: 32, 64, 96 or 128");
   static constexpr int ld(int n) { return 16 * ((n + 15) / 16) + 1; }
   static constexpr int blk(int k, int n) { return k * ld(n) + 16 * ((n + 15) / 16); }
   // LDS blocks in the order of the arrays 2 .. 33
@@ -55,7 +59,7 @@ struct StochTrainCfg {
   static constexpr int PP1 = PV2 + blk(H, F);
   static constexpr int PP2 = PP1 + blk(E, H);
   static constexpr int EN1 = PP2 + blk(H, A);  // [obs_dim][17], the bias behind row obs_dim - 1
-  static constexpr int EN2 = EN1 + blk(STOCH_TRAIN_MAX_OBS, H);
+  static constexpr int EN2 = EN1 + blk(OB, H);
   static constexpr int WEIGHT_WORDS = ((EN2 + blk(H, C) + 3) / 4) * 4;
   // per step and sample: s_i, after_i (16 ES words each); per step and workgroup 16 more words hold c_i
   static constexpr int CK_STATE = 0, CK_AFTER = 16 * 16 * ES, CK_CODE = 2 * 16 * 16 * ES;

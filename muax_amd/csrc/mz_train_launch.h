@@ -20,6 +20,9 @@ namespace mz {
 // against another block is refused at registration; a cached file from other sources is never loaded in the first place,
 // since the file name carries the hash of the kernel's headers (muax_amd/_jit.py::_train_hash).
 inline int train_jit_abi() { return MZS_ABI_VERSION * 1000 + (int)(sizeof(TrainParamsT<18>) % 1000); }
+// ... and mzs_stochastic_train_jit_abi() with a side library's mzs_jit_stoch_train_abi() (mz_stoch_train_jit.hip): the
+// block over the stochastic family's 34 arrays
+inline int stoch_train_jit_abi() { return MZS_ABI_VERSION * 1000 + (int)(sizeof(TrainParamsT<34>) % 1000); }
 
 // Both launches of one training step: `kern`, the main kernel of instance C (one kernel per C: the grant below is that
 // kernel's), then the reduction over C::NA arrays.  The caller has validated `p` and selected the device.  MZS_OK, or an

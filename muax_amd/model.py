@@ -62,6 +62,28 @@ def _jit_tail():
 _NO_KEYWORDS = {}  # (of update()'s fused call for the trio: one shared object, none built per update)
 
 
+# What update() calls after an Unsupported from a fused step (`on_demand` of _fused_update's record): True when an
+# instance for the step's shape is now registered, False when none can be had, None when the refusal is not about one.
+# (The builders are looked up in _jit at call time.)
+def _trio_train_on_demand(step, refusal):
+    """muax_amd/_jit.py::ensure_train_instance, or ensure_wide_train_instance for 17 to 64 actions."""
+    from . import _jit
+    if not isinstance(refusal, _lib.NoKernelInstance):
+        return None
+    shape = (step.A, step.E, 2 * step.S + 1)
+    return _jit.ensure_train_instance(*shape) or _jit.ensure_wide_train_instance(*shape)
+
+
+def _stochastic_train_on_demand(step, refusal):
+    """muax_amd/_jit.py::ensure_stochastic_train_instance for the step's (A, C, E, F) and observation width.  Beyond 32
+    observations the library's refusal, with nothing registered, is its plain "obs_dim must be 1..32": an instance at a
+    wider cap lifts that one too."""
+    from . import _jit
+    if not (isinstance(refusal, _lib.NoKernelInstance) or (step.obs_dim > 32 and "obs_dim" in str(refusal))):
+        return None
+    return _jit.ensure_stochastic_train_instance(step.A, step.C, step.E, 2 * step.S + 1, step.obs_dim)
+
+
 class MuZero:
     r"""MuZero algorithm (muax/model.py:16-50).
 
@@ -79,7 +101,8 @@ class MuZero:
                  support_size: int = 10, recurrent_pred_on: str = "child", device=None,
                  representation_fn=None, capture_graph: bool = False, root_graph_cache: int = 2,
                  stochastic_one_launch: bool = False, stochastic_fused_update: bool = False,
-                 stochastic_root_in_kernel: bool = False, stochastic_unroll_values: bool = False):
+                 stochastic_root_in_kernel: bool = False, stochastic_unroll_values: bool = False,
+                 stochastic_train_on_demand: bool = False):
         self._stochastic = isinstance(network, SMZNetwork)
         if self._stochastic:
             if policy not in (None, "stochastic"):
@@ -131,6 +154,10 @@ class MuZero:
         # default stochastic MLP family: update() takes loss and gradients from the fused training kernel
         # (loss.StochasticFusedLossGrad) instead of torch autograd (off by default: timed on two shapes only -- README)
         self.stochastic_fused_update = bool(stochastic_fused_update)
+        # ... and a shape without a listed instance of that kernel, or observations 33 to 128 wide, gets an instance built
+        # on demand (_jit.ensure_stochastic_train_instance) instead of autograd; only together with the flag above (off
+        # by default: README)
+        self.stochastic_train_on_demand = bool(stochastic_train_on_demand)
         # an SMZNetwork: unroll_values() unrolls through the afterstate and chance dynamics, the codes from the encoder --
         # one launch for the default stochastic MLP family (unroll.StochasticFusedUnrollValues), else the modules; with it
         # fit_vector takes priority_steps (off by default: unroll_values() then raises NotImplementedError as before -- README)
@@ -652,7 +679,9 @@ class MuZero:
         default stochastic MLP family's step (obs_dim up to 32, no custom loss_fn) from its own fused kernel instead
         (mzs_stochastic_mlp_loss_grad, muax_amd/csrc/mz_stoch_train.cuh; `vqvae_beta`, `divide_by_length` and
         `sample_weight` reach it), "auto" falling to autograd for a shape without a listed instance or an unroll beyond
-        the kernel's LDS.  `_last_update_route` names the route taken: "hip_stochastic_fused", "hip_fused" or "torch".
+        the kernel's LDS.  With `stochastic_train_on_demand=True` as well, a shape without a listed instance (obs_dim up
+        to 128) gets one built on demand (muax_amd/_jit.py::ensure_stochastic_train_instance, once per shape, cached on
+        disk) and the step is called again; where no instance can be built, "auto" falls to autograd and "hip" raises.  `_last_update_route` names the route taken: "hip_stochastic_fused", "hip_fused" or "torch".
         `dp_mean=False` skips the gradient mean over the ranks of an initialised process group (a rank-local step:
         bench.py times update() with and without its collective).
         `sample_weight` [B]: importance-sampling weights (`DeviceReplayBuffer.sample(is_beta=)`); row b's cross
@@ -683,14 +712,15 @@ class MuZero:
                 divide = kwargs.get("divide_by_length", False)
                 try:
                     loss, flat = step(batch, divide_by_length=divide, sample_weight=sample_weight, **extra)
-                except _lib.NoKernelInstance:
-                    # a shape of the default trio the library lists no training instance for: build one on demand
-                    # (muax_amd/_jit.py::ensure_train_instance, or ensure_wide_train_instance for 17 to 64 actions; once
-                    # per shape, cached on disk) and call again
-                    from . import _jit
-                    shape = (step.A, step.E, 2 * step.S + 1)
-                    if not (on_demand and (_jit.ensure_train_instance(*shape) or _jit.ensure_wide_train_instance(*shape))):
+                except _lib.Unsupported as e:
+                    # a shape the library lists no training instance for: build one on demand (`on_demand`, once per
+                    # shape, cached on disk) and call again.  `on_demand` answers None for a refusal that no instance
+                    # would lift (it propagates as it is), False when no instance can be had
+                    built = on_demand(step, e) if on_demand and not isinstance(e, _lib.TooLargeForLds) else None
+                    if built is None or (not built and isinstance(e, _lib.NoKernelInstance)):
                         raise
+                    if not built:
+                        raise _lib.NoKernelInstance(f"{e} (and no kernel instance could be built on demand)") from e
                     loss, flat = step(batch, divide_by_length=divide, sample_weight=sample_weight, **extra)
                 if dp_mean:
                     sharding.allreduce_mean_flat([flat])
@@ -732,19 +762,21 @@ class MuZero:
 
     def _fused_update(self, args, kwargs):
         """The fused training step that may serve this update(), or None: (the attribute that keeps the step object, its
-        class, the route's name, whether a missing instance is built on demand, its keywords beyond divide_by_length and
-        sample_weight).  At most one: is_default_mlp_trio wants an MZNetwork of three modules, is_default_stochastic_mlp
+        class, the route's name, what builds a missing instance on demand -- a function of the step object, or None --, its
+        keywords beyond divide_by_length and sample_weight).  At most one: is_default_mlp_trio wants an MZNetwork of three modules, is_default_stochastic_mlp
         an SMZNetwork of six, so the two families' conditions never hold together.  The stochastic family is served only
-        with `stochastic_fused_update`, under its own loss and that loss's keywords."""
+        with `stochastic_fused_update`, under its own loss and that loss's keywords; with `stochastic_train_on_demand`
+        on top it builds missing instances and takes observations up to 128 wide instead of 32."""
         if self.loss_fn is not None or self.device.type != "cuda":
             return None
         if mz_nn.is_default_mlp_trio(self.network):
             if (self.repr_func.obs_dim or 999) <= 128 and not kwargs.get("pi_all_pairs", False):
-                return "_fused_train", mz_loss.FusedLossGrad, "hip_fused", True, _NO_KEYWORDS
+                return "_fused_train", mz_loss.FusedLossGrad, "hip_fused", _trio_train_on_demand, _NO_KEYWORDS
         elif self.stochastic_fused_update and mz_nn.is_default_stochastic_mlp(self.network):
-            if (self.repr_func.obs_dim or 999) <= 32 and not args \
+            on_demand = _stochastic_train_on_demand if self.stochastic_train_on_demand else None
+            if (self.repr_func.obs_dim or 999) <= (128 if on_demand else 32) and not args \
                     and set(kwargs) <= {"vqvae_beta", "divide_by_length", "sample_weight"}:
-                return ("_fused_stoch_train", mz_loss.StochasticFusedLossGrad, "hip_stochastic_fused", False,
+                return ("_fused_stoch_train", mz_loss.StochasticFusedLossGrad, "hip_stochastic_fused", on_demand,
                         {"vqvae_beta": kwargs.get("vqvae_beta", 0.25)})
         return None
 

@@ -146,6 +146,8 @@ def wall(fn):
 
 
 def main_train(args):
+    import time
+
     import numpy as np
 
     import muax_amd as mx
@@ -153,8 +155,10 @@ def main_train(args):
     warm_runtime()
     repeats = max(15, args.repeats)
     rows = []
-    od, L = 16, 5
-    for e, support in ((16, 10), (32, 31)):
+    L = 5
+    # (A, C, E, support, obs_dim): 2048's two listed shapes, or --shape (an unlisted one gets an instance built on demand)
+    shapes = [tuple(args.shape)] if args.shape else [(4, 32, 16, 10, 16), (4, 32, 32, 31, 16)]
+    for A, C, e, support, od in shapes:  # (A, C: the module's 2048 constants, shadowed by the row's)
         for batch in (32, 1024):
             rng = np.random.default_rng(batch)
             b = mx.Transition(obs=torch.from_numpy(rng.uniform(0, 1, (batch, L, od)).astype(np.float32)).cuda(),
@@ -166,9 +170,16 @@ def main_train(args):
             for route in ("fused", "torch"):
                 net = mx.create_stochastic_muzero_network(e, A, C, 2 * support + 1, generator=torch.Generator().manual_seed(1))
                 m = models[route] = mx.MuZero(net, policy="stochastic", support_size=support, stochastic_fused_update=True,
+                                              stochastic_train_on_demand=bool(args.shape),
                                               optimizer=mx.optimizers.create_optimizer("adam", 1e-3))
                 m.init(0, np.zeros((1, od), np.float32))
             fused = mx.loss.StochasticFusedLossGrad(models["fused"])
+            if args.shape:
+                from muax_amd import _jit
+                t0 = time.perf_counter()
+                built = _jit.ensure_stochastic_train_instance(A, C, e, 2 * support + 1, od)
+                print(json.dumps({"ensure_s": round(time.perf_counter() - t0, 2), "registered": built,
+                                  "info": _jit.stochastic_train_instance_info(A, C, e, 2 * support + 1, od)}), flush=True)
 
             def grad_torch(m=models["torch"]):
                 for mod in m.network:
@@ -290,6 +301,8 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--mlp", action="store_true")
     ap.add_argument("--train", action="store_true")
+    ap.add_argument("--shape", type=int, nargs=5, metavar=("A", "C", "E", "SUPPORT", "OBS"),
+                    help="--train: time this shape instead of 2048's two (built on demand where the library lists none)")
     ap.add_argument("--act", action="store_true")
     ap.add_argument("--unroll", action="store_true")
     args = ap.parse_args()
