@@ -127,6 +127,9 @@ def main():
     ap.add_argument("--root-in-kernel", action="store_true",
                     help="act() with root inference by the library too (MuZero(stochastic_root_in_kernel=True)): no torch "
                          "module in an act(); with --one-launch an act() is one launch")
+    ap.add_argument("--noise-in-kernel", action="store_true",
+                    help="with --one-launch: the root's Dirichlet noise drawn inside that launch "
+                         "(MuZero(stochastic_noise_in_kernel=True)) instead of by a launch of its own: the same bits")
     ap.add_argument("--train-on-demand", action="store_true",
                     help="with --fused-update: build an instance of the training kernel for a shape the library does not list "
                          "(MuZero(stochastic_train_on_demand=True)); a shape whose instance would spill stays on autograd")
@@ -147,7 +150,8 @@ def main():
     model = muax.MuZero(net, policy="stochastic", discount=discount, support_size=support_size,
                         optimizer=muax.optimizers.create_optimizer("adam", 2e-3), stochastic_one_launch=args.one_launch,
                         stochastic_fused_update=args.fused_update, stochastic_train_on_demand=args.train_on_demand, stochastic_root_in_kernel=args.root_in_kernel,
-                        stochastic_unroll_values=args.priority_steps is not None)
+                        stochastic_unroll_values=args.priority_steps is not None,
+                        stochastic_noise_in_kernel=args.noise_in_kernel)
     if args.priority_steps is not None and args.host_buffer:
         ap.error("--priority-steps needs the device route (fit_vector on a DeviceReplayBuffer), not --host-buffer")
     if not args.host_buffer:

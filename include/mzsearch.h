@@ -288,7 +288,8 @@ typedef struct mzs_stochastic_search_args {
   float dirichlet_fraction;
   float temperature;
   /* NULL, or a DEVICE array of 4 + 2 num_simulations words that REPLACES key, temperature and dirichlet_fraction: a
-   * captured launch freezes this struct's values, not the array's contents (mzs_stochastic_search_block fills a host copy) */
+   * captured launch freezes this struct's values, not the array's contents (mzs_stochastic_search_block fills a host copy;
+   * mzs_mlp_stochastic_search_draw reads three words more: mzs_stochastic_search_block_draw) */
   const uint32_t *device_block;
   int32_t *action;                 /* out [B] */
   float *action_weights;           /* out [B, A] */
@@ -330,6 +331,27 @@ int mzs_mlp_stochastic_root(mzs_handle *h, const float *obs, float *prior_logits
  * MZS_E_UNSUPPORTED for a shape the plan declines. */
 int mzs_mlp_stochastic_search_obs(mzs_handle *h, const mzs_stochastic_search_args *args, const float *obs,
                                   float *root_value_out, void *stream);
+
+/* ---- the root exploration noise drawn INSIDE the one launch: each root's wavefront draws its own row of
+ *   jax.random.dirichlet(split(args->key, 3)[1], full([num_actions], dirichlet_alpha), (global_batch,))
+ * in front of its search, bit for bit the row mzs_dirichlet writes (rows indexed by the GLOBAL root: shards draw their
+ * own), mixes it in with args->dirichlet_fraction and, when noise_out [B, A] (device) is not NULL, stores it there.  No
+ * separate launch, no [B, A] input array: args->dirichlet_noise must be NULL.
+ * obs == NULL: the root comes from the RootFnOutput arrays of `args`, as in mzs_mlp_stochastic_search.  obs != NULL: as
+ * mzs_mlp_stochastic_search_obs, the root arrays must be NULL and root_value_out is required.
+ * args->device_block, when not NULL, is read in the longer layout of mzs_stochastic_search_block_draw: a captured launch
+ * then freezes none of key, temperature, dirichlet_fraction or dirichlet_alpha.  One launch, capturable, the same plan.
+ * Refused before any launch, the message naming the cause: MZS_E_INVALID for a non-null dirichlet_noise, dirichlet_alpha
+ * <= 0 or not finite, and what the two entries above refuse (another policy, unbound weights or representation, a null
+ * or mis-sized struct, a null required pointer, a root array beside obs); MZS_E_UNSUPPORTED for a shape the plan
+ * declines. */
+int mzs_mlp_stochastic_search_draw(mzs_handle *h, const mzs_stochastic_search_args *args, const float *obs,
+                                   float *root_value_out, float dirichlet_alpha, float *noise_out, void *stream);
+/* HOST arithmetic: the 7 + 2 num_simulations words of that device_block -- the 4 + 2 num_simulations words of
+ * mzs_stochastic_search_block for the same arguments, then the Dirichlet key split(key, 3)[1] (two words) and the bits of
+ * dirichlet_alpha.  key NULL: zero. */
+int mzs_stochastic_search_block_draw(const uint32_t key[2], int32_t num_simulations, float temperature,
+                                     float dirichlet_fraction, float dirichlet_alpha, uint32_t *out_words);
 
 /* ---- recurrent_fn of the EfficientZero-style nets ----
  * mzs_ez_recurrent evaluates, for a batch of 6x6xC hidden states (NHWC, C = 32 or 64) and actions, the whole

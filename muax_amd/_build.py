@@ -39,7 +39,7 @@ UNITS = {
     "mz_fused_g4.hip": _FUSED,
     "mz_wide.hip": ["mz_wide.cuh", "mz_wave_tree.cuh", "mz_wide_launch.h", "mz_fused_launch.h", "mz_fused.cuh", "mz_spec.cuh",
                     "mz_host.h", _ABI],
-    "mz_stoch_wide.hip": ["mz_stoch_wide.cuh", "mz_stoch_wide_launch.h", "mz_wide.cuh", "mz_wave_tree.cuh", "mz_wide_launch.h",
+    "mz_stoch_wide.hip": ["mz_stoch_wide.cuh", "mz_stoch_wide_launch.h", "mz_dirichlet.cuh", "mz_wide.cuh", "mz_wave_tree.cuh", "mz_wide_launch.h",
                           "mz_fused_launch.h", "mz_fused.cuh", "mz_spec.cuh", "mz_host.h", "mz_keys.h", _ABI],
     "mz_conv.hip": ["mz_host.h", "mz_conv_host.h", "mz_conv.cuh", "mz_spec.cuh", _ABI],
     "mz_search_conv.hip": ["mz_host.h", "mz_conv_host.h", "mz_conv.cuh", "mz_step.cuh", "mz_step_jump.cuh", "mz_spec.cuh", _ABI],

@@ -370,6 +370,9 @@ ENTRIES = {
     "mzs_mlp_set_stochastic_representation": (C.c_int, [_vp, _i32, _vp, _vp]),
     "mzs_mlp_stochastic_root": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mzs_mlp_stochastic_search_obs": (C.c_int, [_vp, _P(MzsStochasticSearchArgs), _vp, _vp, _vp]),
+    # the root exploration noise drawn inside the one launch
+    "mzs_mlp_stochastic_search_draw": (C.c_int, [_vp, _P(MzsStochasticSearchArgs), _vp, _vp, _f32, _vp, _vp]),
+    "mzs_stochastic_search_block_draw": (C.c_int, [_key, _i32, _f32, _f32, _f32, _vp]),
     # recurrent_fn of the EfficientZero-style nets
     "mzs_ez_recurrent": (C.c_int, [_P(MzsEzArgs), _vp]),
     # fused LayerNorm of the convolutional plugin nets

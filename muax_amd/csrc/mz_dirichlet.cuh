@@ -6,6 +6,8 @@
 // the same restatement line by line and the caveat: SPEC-TO-CONFIRM against a real jax; act(dirichlet_noise = ...)
 // stays the bit-pinned route).  Four lanes per (root, action) element walk the rejection loop speculatively
 // (loggamma_group), then one thread per root does the softmax.  Rows are indexed by the GLOBAL root, so a shard draws exactly its rows of the whole batch.
+// Two drivers of that draw: dirichlet_kernel (mzs_dirichlet, a launch of its own) and wave_dirichlet_row, one row by one
+// wavefront inside a kernel that runs a root per wavefront (mz_stoch_wide.cuh's DRAW instantiations) -- the same bits.
 #pragma once
 #include "mz_spec.cuh"
 
@@ -138,6 +140,40 @@ MZ_DEV float loggamma_group(uint32_t ki0, uint32_t ki1, float alpha_orig, int t,
   return (log_pos(d) + log_pos(V)) + log_boost;
 }
 
+// ONE row of the draw by ONE wavefront, for a kernel that runs a root per wavefront (mz_stoch_wide.cuh): lane a < A
+// returns element a of row `global_root` of jax.random.dirichlet(key, full([A], alpha), (global_batch,)), lanes >= A
+// return 0 -- bit for bit what dirichlet_kernel writes for that row.  A <= 64; every lane of the wavefront must call.
+// Sixteen elements per pass (kSpec lanes each, loggamma_group as it stands), ceil(A / 16) passes; a group whose element
+// is past A shadows the pass's first element, so every lane takes part in the ballot and the shuffles.  After pass q
+// lane a in [16 q, 16 q + 16) takes its value from lane kSpec (a - 16 q).  The softmax is dirichlet_kernel's tail in its
+// order: the maximum and the sum run over the elements from 0 upwards, each broadcast in turn, every lane computing the
+// same two numbers (a tree reduction would round the sum differently).  No LDS, no barrier.
+MZ_DEV float wave_dirichlet_row(uint32_t k0, uint32_t k1, float alpha, int A, uint64_t global_batch, uint64_t global_root,
+                                int lane) {
+  constexpr int kPass = 64 / kSpec;  // elements per pass
+  const int grp = lane / kSpec, t = lane % kSpec;
+  const uint64_t n = global_batch * (uint64_t)A, row0 = global_root * (uint64_t)A;
+  auto bcast = [](float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); };
+  float v = 0.0f;
+  for (int q = 0; q * kPass < A; ++q) {  // (wavefront-uniform)
+    const int el = q * kPass + grp;
+    uint32_t e0, e1;
+    jax_split(k0, k1, n, row0 + (uint64_t)(el < A ? el : q * kPass), e0, e1);
+    const float g = __shfl(loggamma_group(e0, e1, alpha, t, lane), kSpec * (lane % kPass));
+    v = lane / kPass == q ? g : v;
+  }
+  float mx = bcast(v, 0);
+  for (int i = 1; i < A; ++i) {
+    const float vi = bcast(v, i);
+    mx = vi > mx ? vi : mx;
+  }
+  const float e = exp_neg((lane < A ? v : mx) - mx);
+  float sum = bcast(e, 0);
+  for (int i = 1; i < A; ++i) sum = sum + bcast(e, i);
+  return lane < A ? e / sum : 0.0f;
+}
+
+#ifndef MZ_DIRICHLET_NO_KERNEL  // (a second unit that wants the device functions alone defines it: one dirichlet_kernel per library)
 // block = 256 threads = R = 64 / A roots x A actions x kSpec lanes (A <= 64); dynamic LDS: R * A floats
 __global__ __launch_bounds__(256) void dirichlet_kernel(uint32_t k0, uint32_t k1, float alpha, int B, int A,
                                                         uint64_t global_batch, uint64_t root_offset, float* out) {
@@ -170,5 +206,6 @@ __global__ __launch_bounds__(256) void dirichlet_kernel(uint32_t k0, uint32_t k1
     for (int i = 0; i < A; ++i) out[(size_t)b2 * A + i] = rowp[i] / sum;
   }
 }
+#endif
 
 }  // namespace mz

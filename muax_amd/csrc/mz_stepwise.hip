@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -433,9 +434,10 @@ int mzs_mlp_stochastic_root(mzs_handle* h, const float* obs, float* prior_logits
 }
 
 // ---- the whole stochastic search of the bound family in ONE launch, the tree in LDS (mz_stoch_wide.cuh) ----
-// obs: null for mzs_mlp_stochastic_search (the RootFnOutput arrays of `a`), else root inference inside the launch
+// with_obs: root inference inside the launch on `obs`, else the RootFnOutput arrays of `a`; draw_alpha: null, or the root
+// noise drawn inside the launch with this alpha (mzs_mlp_stochastic_search_draw), its rows into noise_out when set
 static int stoch_search(mzs_handle* h, const char* who, const mzs_stochastic_search_args* a, const float* obs,
-                        float* root_value_out, bool with_obs, void* stream_) {
+                        float* root_value_out, bool with_obs, const float* draw_alpha, float* noise_out, void* stream_) {
   const mzs_config& c = h->cfg;
   if (with_obs) {
     if (int rc = stoch_root_refusal(h, who)) return rc;
@@ -453,8 +455,13 @@ static int stoch_search(mzs_handle* h, const char* who, const mzs_stochastic_sea
     return fail(h, MZS_E_INVALID, "%s: null input", who);
   }
   if (!a->action || !a->action_weights) return fail(h, MZS_E_INVALID, "%s: null output", who);
-  if (!a->dirichlet_noise && a->dirichlet_fraction != 0.0f && !a->device_block)
+  if (draw_alpha) {
+    if (a->dirichlet_noise) return fail(h, MZS_E_INVALID, "%s: dirichlet_noise must be NULL (the kernel draws the noise)", who);
+    if (!(*draw_alpha > 0.0f) || std::isinf(*draw_alpha))
+      return fail(h, MZS_E_INVALID, "%s: dirichlet_alpha must be positive and finite", who);
+  } else if (!a->dirichlet_noise && a->dirichlet_fraction != 0.0f && !a->device_block) {
     return fail(h, MZS_E_INVALID, "%s: dirichlet_fraction != 0 needs dirichlet_noise", who);
+  }
   const mzs_stochastic_mlp_weights& s = h->sw;
   mz::WidePlan pl;
   if (const char* limit = mz::stoch_wide_plan(c.num_actions, c.num_chance_outcomes, c.embed_dim, 2 * s.support_size + 1,
@@ -494,8 +501,14 @@ static int stoch_search(mzs_handle* h, const char* who, const mzs_stochastic_sea
   p.discount = s.discount; p.temperature = a->temperature;
   p.global_batch = (uint64_t)c.global_batch; p.root_offset = (uint64_t)c.root_offset;
   mzh::derive_keys(a->key, c.num_simulations, p.k_sample, &p.sim_keys[0][0]);  // num_simulations <= 255 (the plan)
+  if (draw_alpha) {
+    mzh::h_split(a->key, 3, 1, p.k_dirichlet);  // mctx: rng_key, dirichlet_rng_key, search_rng_key = split(rng_key, 3)
+    p.dirichlet_alpha = *draw_alpha;
+    p.noise_out = noise_out;
+  }
   std::string err;
-  if (int rc = mz::stoch_wide_launch(c.tiebreak != 0, with_obs, c.device, p, pl, static_cast<hipStream_t>(stream_), &err))
+  if (int rc = mz::stoch_wide_launch(c.tiebreak != 0, with_obs, draw_alpha != nullptr, c.device, p, pl,
+                                     static_cast<hipStream_t>(stream_), &err))
     return fail(h, rc, "%s", (std::string(who) + ": " + err).c_str());
   if (ex) h->step.rooted = true;  // the HBM tree is that of a finished step-wise search: mzs_tree_export serves it
   return MZS_OK;
@@ -503,13 +516,20 @@ static int stoch_search(mzs_handle* h, const char* who, const mzs_stochastic_sea
 
 int mzs_mlp_stochastic_search(mzs_handle* h, const mzs_stochastic_search_args* a, void* stream_) {
   if (!h) return MZS_E_INVALID;
-  return stoch_search(h, "mzs_mlp_stochastic_search", a, nullptr, nullptr, false, stream_);
+  return stoch_search(h, "mzs_mlp_stochastic_search", a, nullptr, nullptr, false, nullptr, nullptr, stream_);
 }
 
 int mzs_mlp_stochastic_search_obs(mzs_handle* h, const mzs_stochastic_search_args* a, const float* obs, float* root_value_out,
                                   void* stream_) {
   if (!h) return MZS_E_INVALID;
-  return stoch_search(h, "mzs_mlp_stochastic_search_obs", a, obs, root_value_out, true, stream_);
+  return stoch_search(h, "mzs_mlp_stochastic_search_obs", a, obs, root_value_out, true, nullptr, nullptr, stream_);
+}
+
+int mzs_mlp_stochastic_search_draw(mzs_handle* h, const mzs_stochastic_search_args* a, const float* obs, float* root_value_out,
+                                   float dirichlet_alpha, float* noise_out, void* stream_) {
+  if (!h) return MZS_E_INVALID;
+  return stoch_search(h, "mzs_mlp_stochastic_search_draw", a, obs, root_value_out, obs != nullptr, &dirichlet_alpha, noise_out,
+                      stream_);
 }
 
 int mzs_tree_export(mzs_handle* h, const mzs_tree_view* out, void* stream_) {

@@ -4,7 +4,8 @@
 // inference is the caller's (the kernel takes the RootFnOutput arrays) or, in the ROOT instantiations, the kernel's own:
 // the representation (mz_wave_tree.cuh wave_root_state, its weights read from HBM once per root) and the prediction heads
 // on the observation row, as mz_wide.cuh does it; mz_stoch_root_kernel is that root inference alone, for the
-// three-launch route.  The mapping, the tree record and the rules
+// three-launch route.  The root's Dirichlet noise is an input array or, in the DRAW instantiations, drawn by the root's own
+// wavefront in front of its search (mz_dirichlet.cuh wave_dirichlet_row: the bits of mzs_dirichlet).  The mapping, the tree record and the rules
 // both one-launch kernels follow (pUCT score, tie-break noise, expansion, backup, summary and sampling, tree export) are
 // mz_wave_tree.cuh's:
 //
@@ -33,6 +34,8 @@
 // No atomics, nothing that depends on the launch geometry: a root's bits are the same whichever wavefront of whichever
 // workgroup ran it.
 #pragma once
+#define MZ_DIRICHLET_NO_KERNEL  // (dirichlet_kernel is mz_selftest.hip's; this unit takes wave_dirichlet_row)
+#include "mz_dirichlet.cuh"
 #include "mz_stoch_wide_launch.h"
 #include "mz_wide.cuh"
 
@@ -73,8 +76,10 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_root_kernel(const
 
 // MODE 0 / 1: without / with mctx's tie-break noise at the decision nodes (the handle's `tiebreak`); ROOT: root
 // inference inside the launch -- the kernel reads p.obs and the representation's weights (HBM, once per root) instead of
-// the RootFnOutput arrays and writes p.root_value_out
-template <int MODE, bool ROOT = false>
+// the RootFnOutput arrays and writes p.root_value_out; DRAW: the root's Dirichlet row drawn inside the launch
+// (mz_dirichlet.cuh wave_dirichlet_row on the call's Dirichlet key, the bits of mzs_dirichlet) instead of read from
+// p.dirichlet_noise, and written to p.noise_out when that is set
+template <int MODE, bool ROOT = false, bool DRAW = false>
 __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const StochWideParams p, const StochWideShape sh) {
   static_assert(MODE == 0 || MODE == 1, "tie-break setting");
   constexpr bool TIEBREAK = MODE == 1;
@@ -132,6 +137,16 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
   // ---- the root (mz_step_kernels.cuh root_row with AD = A): Dirichlet mix, log, mask over the actions, -inf on the
   // chance slots, the softmax over all slots ----
   {
+    [[maybe_unused]] float drawn = 0.0f;
+    if constexpr (DRAW) {
+      // the root's row of the global batch's draw, first: one float is all that stays live across root inference.  Key
+      // and alpha behind the simulation keys of the device block when there is one
+      const int tail = kStochBlockHead + 2 * S;
+      const uint32_t kd0 = p.dyn ? p.dyn[tail] : p.k_dirichlet[0], kd1 = p.dyn ? p.dyn[tail + 1] : p.k_dirichlet[1];
+      const float alpha = p.dyn ? __uint_as_float(p.dyn[tail + 2]) : p.dirichlet_alpha;
+      drawn = wave_dirichlet_row(kd0, kd1, alpha, A, p.global_batch, rg, lane);
+      if (p.noise_out != nullptr && act) p.noise_out[(size_t)r * A + al] = drawn;
+    }
     float x;
     [[maybe_unused]] float root_v = 0.0f;
     if constexpr (ROOT) {
@@ -143,7 +158,9 @@ __global__ __launch_bounds__(64 * kWideMaxWaves) void mz_stoch_wide_kernel(const
       x = act ? p.prior_logits[(size_t)r * A + al] : 0.0f;
     }
     const float pr = wave_softmax(x, A, lane);
-    const float nz = (p.dirichlet_noise != nullptr && act) ? p.dirichlet_noise[(size_t)r * A + al] : 0.0f;
+    float nz;
+    if constexpr (DRAW) nz = drawn;
+    else nz = (p.dirichlet_noise != nullptr && act) ? p.dirichlet_noise[(size_t)r * A + al] : 0.0f;
     const float noisy = (1.0f - fraction) * pr + fraction * nz;
     float lg = log_pos(fmaxf(noisy, kFltTiny));
     if (p.invalid != nullptr) {

@@ -10,16 +10,24 @@
 
 namespace mz {
 
-int stoch_wide_launch(bool tiebreak, bool root, int device, const StochWideParams& p, const WidePlan& pl, hipStream_t stream,
-                      std::string* err) {
-  const StochWideShape sh = {pl.rec_words, pl.root_words, pl.wg_words, pl.weight_words, pl.emb_lds, pl.waves};
+// the kernel's instantiation for (tie-break mode, ROOT, DRAW)
+template <bool ROOT, bool DRAW>
+static int launch_instance(bool tiebreak, int device, const StochWideParams& p, const StochWideShape& sh, size_t lds,
+                           hipStream_t stream, std::string* err) {
   const char* what = "stochastic search kernel launch: ";
+  return tiebreak ? launch_wave_per_root<mz_stoch_wide_kernel<1, ROOT, DRAW>>(what, device, p, sh, lds, stream, err)
+                  : launch_wave_per_root<mz_stoch_wide_kernel<0, ROOT, DRAW>>(what, device, p, sh, lds, stream, err);
+}
+
+int stoch_wide_launch(bool tiebreak, bool root, bool draw, int device, const StochWideParams& p, const WidePlan& pl,
+                      hipStream_t stream, std::string* err) {
+  const StochWideShape sh = {pl.rec_words, pl.root_words, pl.wg_words, pl.weight_words, pl.emb_lds, pl.waves};
   const size_t lds = (size_t)pl.lds_bytes;
-  if (root)
-    return tiebreak ? launch_wave_per_root<mz_stoch_wide_kernel<1, true>>(what, device, p, sh, lds, stream, err)
-                    : launch_wave_per_root<mz_stoch_wide_kernel<0, true>>(what, device, p, sh, lds, stream, err);
-  return tiebreak ? launch_wave_per_root<mz_stoch_wide_kernel<1>>(what, device, p, sh, lds, stream, err)
-                  : launch_wave_per_root<mz_stoch_wide_kernel<0>>(what, device, p, sh, lds, stream, err);
+  if (draw)
+    return root ? launch_instance<true, true>(tiebreak, device, p, sh, lds, stream, err)
+                : launch_instance<false, true>(tiebreak, device, p, sh, lds, stream, err);
+  return root ? launch_instance<true, false>(tiebreak, device, p, sh, lds, stream, err)
+              : launch_instance<false, false>(tiebreak, device, p, sh, lds, stream, err);
 }
 
 int stoch_root_launch(const StochRootParams& p, hipStream_t stream, std::string* err) {
@@ -46,12 +54,22 @@ extern "C" int mzs_mlp_stochastic_plan(int32_t num_actions, int32_t num_chance_o
   return MZS_OK;
 }
 
+static const uint32_t kZeroKey[2] = {0, 0};
+
 extern "C" int mzs_stochastic_search_block(const uint32_t key[2], int32_t num_simulations, float temperature,
                                            float dirichlet_fraction, uint32_t* out_words) {
   if (!out_words || num_simulations < 1) return MZS_E_INVALID;
-  const uint32_t zero[2] = {0, 0};
-  mzh::derive_keys(key ? key : zero, num_simulations, out_words, out_words + mz::kStochBlockHead);
+  mzh::derive_keys(key ? key : kZeroKey, num_simulations, out_words, out_words + mz::kStochBlockHead);
   memcpy(out_words + 2, &temperature, sizeof(float));
   memcpy(out_words + 3, &dirichlet_fraction, sizeof(float));
+  return MZS_OK;
+}
+
+extern "C" int mzs_stochastic_search_block_draw(const uint32_t key[2], int32_t num_simulations, float temperature,
+                                                float dirichlet_fraction, float dirichlet_alpha, uint32_t* out_words) {
+  if (int rc = mzs_stochastic_search_block(key, num_simulations, temperature, dirichlet_fraction, out_words)) return rc;
+  uint32_t* tail = out_words + mz::kStochBlockHead + 2 * (size_t)num_simulations;
+  mzh::h_split(key ? key : kZeroKey, 3, 1, tail);  // mctx: rng_key, dirichlet_rng_key, search_rng_key = split(rng_key, 3)
+  memcpy(tail + 2, &dirichlet_alpha, sizeof(float));
   return MZS_OK;
 }

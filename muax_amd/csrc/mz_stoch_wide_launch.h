@@ -29,8 +29,10 @@ inline const char* stoch_wide_plan(int A, int C, int E, int F, int S, WidePlan* 
 }
 
 // Per-call values a captured launch must not freeze, as a DEVICE block of 4 + 2 S words (mzs_stochastic_search_block
-// fills the host copy): k_sample[2], the bits of temperature and dirichlet_fraction, every simulation's key
-constexpr int kStochBlockHead = 4;
+// fills the host copy): k_sample[2], the bits of temperature and dirichlet_fraction, every simulation's key.  The DRAW
+// instantiations read kStochBlockDrawTail more words behind them (mzs_stochastic_search_block_draw): the Dirichlet key's
+// two words and the bits of dirichlet_alpha
+constexpr int kStochBlockHead = 4, kStochBlockDrawTail = 3;
 
 struct StochWideParams {
   // RootFnOutput and the root's options ([B, A]; invalid, dirichlet_noise, gumbel may be null)
@@ -63,12 +65,18 @@ struct StochWideParams {
   const float *obs, *repr_w, *repr_b;
   float* root_value_out;
   int32_t obs_dim;
+  // the root noise drawn inside the launch (the kernel's DRAW instantiations; dirichlet_noise is then null): the call's
+  // Dirichlet key split(key, 3)[1] and alpha -- both from the device block's tail when there is one --, the drawn rows
+  // out [B, A] or null
+  float dirichlet_alpha;
+  uint32_t k_dirichlet[2];
+  float* noise_out;
 };
 
-// tiebreak: the handle's (the kernel's mode 1); root: p.obs set, root inference inside the launch.  MZS_OK after the
-// launch, or a negative MZS_E_* with *err set.
-int stoch_wide_launch(bool tiebreak, bool root, int device, const StochWideParams& p, const WidePlan& pl, hipStream_t stream,
-                      std::string* err);
+// tiebreak: the handle's (the kernel's mode 1); root: p.obs set, root inference inside the launch; draw: the root noise
+// drawn inside the launch.  MZS_OK after the launch, or a negative MZS_E_* with *err set.
+int stoch_wide_launch(bool tiebreak, bool root, bool draw, int device, const StochWideParams& p, const WidePlan& pl,
+                      hipStream_t stream, std::string* err);
 
 // Root inference of the family on its own (mz_stoch_root_kernel): one wavefront per root, no LDS.  E, A <= 64, F <= 63.
 struct StochRootParams {

@@ -102,7 +102,7 @@ class MuZero:
                  representation_fn=None, capture_graph: bool = False, root_graph_cache: int = 2,
                  stochastic_one_launch: bool = False, stochastic_fused_update: bool = False,
                  stochastic_root_in_kernel: bool = False, stochastic_unroll_values: bool = False,
-                 stochastic_train_on_demand: bool = False):
+                 stochastic_train_on_demand: bool = False, stochastic_noise_in_kernel: bool = False):
         self._stochastic = isinstance(network, SMZNetwork)
         if self._stochastic:
             if policy not in (None, "stochastic"):
@@ -131,7 +131,7 @@ class MuZero:
         else:
             self.repr_func, self.pred_func, self.dy_func = self.network
         # of the last act(): "fused_host", "fused", "stepwise"; "hip_stochastic_mlp", "hip_stochastic_one_launch", their
-        # "..._root" twins (stochastic_root_in_kernel), "callables"
+        # "..._root" twins (stochastic_root_in_kernel), the one-launch names + "_noise" (stochastic_noise_in_kernel), "callables"
         self._last_route = None
         self._policy = policy_class()
         self._optimizer = optimizer
@@ -151,6 +151,9 @@ class MuZero:
         # default stochastic MLP family on the library route: root inference by the library too (in the one launch, or
         # one launch in front of the three-launch loop) instead of the torch modules (off by default: README)
         self.stochastic_root_in_kernel = bool(stochastic_root_in_kernel)
+        # default stochastic MLP family on the one-launch route: act() draws the root's Dirichlet noise inside that launch
+        # instead of by a launch of its own (off by default: the same bits, the speed is measured on one shape -- README)
+        self.stochastic_noise_in_kernel = bool(stochastic_noise_in_kernel)
         # default stochastic MLP family: update() takes loss and gradients from the fused training kernel
         # (loss.StochasticFusedLossGrad) instead of torch autograd (off by default: timed on two shapes only -- README)
         self.stochastic_fused_update = bool(stochastic_fused_update)
@@ -520,7 +523,9 @@ class MuZero:
         the shape; MUAX_AMD_STOCHASTIC_MLP=0 switches the library route off) or, for plugin modules, by
         StochasticMuZeroPolicy on callables built from them.  With `stochastic_root_in_kernel` the library route (embeddings
         up to 64 wide) runs root inference too and no torch module is called: the widths come from the modules, the
-        observations go to search_stochastic_mlp(None, obs=...), the root value is the kernel's."""
+        observations go to search_stochastic_mlp(None, obs=...), the root value is the kernel's.  With
+        `stochastic_noise_in_kernel` the one-launch route draws the root noise too (draw_dirichlet=dirichlet_alpha) when the
+        caller gave none and dirichlet_fraction is not 0: `_root_noise` is skipped, the route's name ends in "_noise"."""
         qt = getattr(qtransform, "__name__", qtransform)
         if qt not in (None, "qtransform_by_parent_and_siblings"):
             raise ValueError(f"qtransform {qt!r} is not implemented for this policy")
@@ -533,25 +538,30 @@ class MuZero:
         else:
             root = self._root_inference_eager(self._device_obs(obs))
             (B, A), E = root[0].shape, root[2].shape[1]
-        dirichlet_noise = self._root_noise(key, dirichlet_noise, dirichlet_fraction, dirichlet_alpha, obs, A, global_batch,
-                                           root_offset)
+        one_launch = hip and self.stochastic_one_launch and stochastic_plan(A, Cn, E, self._support_size,
+                                                                            num_simulations) is not None
+        # the noise act() would draw itself (_root_noise), drawn by the one launch instead: the same rows, the same bits
+        draw = one_launch and self.stochastic_noise_in_kernel and dirichlet_noise is None and bool(dirichlet_fraction)
+        if not draw:
+            dirichlet_noise = self._root_noise(key, dirichlet_noise, dirichlet_fraction, dirichlet_alpha, obs, A, global_batch,
+                                               root_offset)
         if hip:
             h = self._handle(B, (A, num_simulations, E, max_depth, tiebreak, pb_c_init, float(pb_c_base),
                                  global_batch, root_offset, "stochastic", "qtransform_by_parent_and_siblings", 16, 1.0, Cn),
                              self._bind_stochastic)
-            one_launch = self.stochastic_one_launch and stochastic_plan(A, Cn, E, self._support_size,
-                                                                        num_simulations) is not None
             out = h.search_stochastic_mlp(root, key=key, invalid_actions=invalid_actions, dirichlet_noise=dirichlet_noise,
                                           dirichlet_fraction=dirichlet_fraction, temperature=temperature, gumbel=gumbel,
                                           with_tree=with_tree, graph=self.capture_graph, graph_version=self._weights_version,
-                                          one_launch=one_launch, obs=self._device_obs(obs) if in_kernel else None)
+                                          one_launch=one_launch, obs=self._device_obs(obs) if in_kernel else None,
+                                          draw_dirichlet=dirichlet_alpha if draw else None)
             t = out.search_tree
             if t is not None:  # the decision slice, as StochasticMuZeroPolicy returns it (mctx _mask_tree)
                 t = t._replace(**{f: getattr(t, f)[..., :A] for f in t._fields if f.startswith("children_")})
             route = "hip_stochastic_one_launch" if one_launch else "hip_stochastic_mlp"
+            suffix = "_noise" if draw else ""
             if in_kernel:  # (action, weights and root value then share the handle's one output allocation)
-                return PolicyOutput(out.action, out.action_weights, t), h.root_value, h, route + "_root"
-            return PolicyOutput(out.action, out.action_weights, t), root[1], None, route
+                return PolicyOutput(out.action, out.action_weights, t), h.root_value, h, route + "_root" + suffix
+            return PolicyOutput(out.action, out.action_weights, t), root[1], None, route + suffix
         shapes = {} if Cn is None else dict(num_chance_outcomes=Cn, afterstate_shape=tuple(root[2].shape[1:]))
         out = self._policy(self._params, key, root, decision_recurrent_fn=self._decision_inference,
                            chance_recurrent_fn=self._chance_inference, num_simulations=num_simulations,

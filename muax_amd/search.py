@@ -175,6 +175,7 @@ class MuZeroSearch:
         self._weights = None
         self._stochastic_weights = self._stochastic_out = None  # set_stochastic_mlp_weights; its recurrent step's outputs
         self._stochastic_repr = self._stochastic_root = None  # set_stochastic_representation; stochastic_mlp_root's outputs
+        self._root_noise = self.root_noise = None  # search_stochastic_mlp(draw_dirichlet=): the handle's buffer; the last call's rows
         B, A = self.batch, cfg.num_actions
         with torch.cuda.device(self.device):
             # action | action_weights | root_value in ONE allocation: a NumPy caller gets them with one copy
@@ -690,13 +691,31 @@ class MuZeroSearch:
         return self.finish_stochastic(temperature, gumbel, with_tree)
 
     def _search_stochastic_one_launch(self, root_fn_output, gkey, key, invalid_actions, dirichlet_noise, dirichlet_fraction,
-                                      temperature, gumbel, with_tree, graph, graph_version, obs=None) -> PolicyOutput:
+                                      temperature, gumbel, with_tree, graph, graph_version, obs=None, draw=None,
+                                      noise_out=None) -> PolicyOutput:
         """The whole search as ONE launch (mzs_mlp_stochastic_search; with `obs` instead of root_fn_output
         mzs_mlp_stochastic_search_obs: root inference inside it, the root's value into `root_value`).  graph: that launch
         captured as a one-node graph per (gkey, which optional inputs are there, with_tree, graph_version) -- the inputs
         then travel through persistent buffers and key, temperature and dirichlet_fraction through the entry's device
-        block, so a replay sees this call's values."""
+        block, so a replay sees this call's values.
+
+        draw: the Dirichlet alpha of a root noise drawn inside the launch (mzs_mlp_stochastic_search_draw; no
+        dirichlet_noise then); noise_out: None, True (the handle's own buffer) or the caller's float32 [B, A] tensor for
+        the drawn rows, `root_noise` afterwards.  A captured launch of this variant has its own graph, reads alpha from
+        the device block too and writes the rows to the handle's buffer (a caller's tensor is filled from it)."""
         B, A, S = self.batch, self.cfg.num_actions, self.cfg.num_simulations
+        noise = None
+        if draw is not None and noise_out is not None:
+            if noise_out is True or graph:
+                if self._root_noise is None:
+                    with torch.cuda.device(self.device):
+                        self._root_noise = torch.empty(B, A, dtype=torch.float32, device=self.device)
+                noise = self._root_noise
+            if noise_out is not True:
+                if not (isinstance(noise_out, torch.Tensor) and noise_out.dtype == torch.float32 and noise_out.is_contiguous()
+                        and tuple(noise_out.shape) == (B, A) and noise_out.device == self.action.device):
+                    raise ValueError(f"noise_out: expected True or a contiguous float32 tensor of shape {(B, A)} on {self.device}")
+                noise = noise if graph else noise_out
         if obs is not None:
             ins = dict(obs=self._stochastic_obs(obs))
         else:
@@ -707,8 +726,9 @@ class MuZeroSearch:
         ins.update(invalid_actions=self._u8(invalid_actions, (B, A), "invalid_actions"),
                    dirichlet_noise=self._f32(dirichlet_noise, (B, A), "dirichlet_noise"),
                    gumbel=self._f32(gumbel, (B, A), "gumbel"))
-        fraction = dirichlet_fraction if ins["dirichlet_noise"] is not None else 0.0
+        fraction = dirichlet_fraction if ins["dirichlet_noise"] is not None or draw is not None else 0.0
         kw = (C.c_uint32 * 2)(*key_words(key))
+        words = 4 + 2 * S + (3 if draw is not None else 0)  # the device block of the entry taken
 
         def launch(tensors, block):
             a = _lib.args(MzsStochasticSearchArgs, export_tree=int(bool(with_tree)), key=tuple(kw), dirichlet_fraction=fraction,
@@ -716,7 +736,11 @@ class MuZeroSearch:
                           action=self.action.data_ptr(), action_weights=self.action_weights.data_ptr(),
                           search_value=self.search_value.data_ptr(), depth_sum=self.depth_sum.data_ptr(),
                           **{n: None if t is None else t.data_ptr() for n, t in tensors.items() if n != "obs"})
-            if obs is None:
+            if draw is not None:
+                _lib.check(self._L.mzs_mlp_stochastic_search_draw(self._h, C.byref(a), _ptr(tensors.get("obs")),
+                                                                  _ptr(self.root_value), draw, _ptr(noise), self._stream()),
+                           self._h)
+            elif obs is None:
                 _lib.check(self._L.mzs_mlp_stochastic_search(self._h, C.byref(a), self._stream()), self._h)
             else:
                 _lib.check(self._L.mzs_mlp_stochastic_search_obs(self._h, C.byref(a), _ptr(tensors["obs"]), _ptr(self.root_value),
@@ -726,15 +750,16 @@ class MuZeroSearch:
             launch(ins, None)
             self._keep = tuple(ins.values())
         else:
-            gk = (gkey, "one_launch", tuple(t is not None for t in ins.values()), bool(with_tree)) + (("obs",) if obs is not None else ())
+            gk = ((gkey, "one_launch", tuple(t is not None for t in ins.values()), bool(with_tree))
+                  + (("obs",) if obs is not None else ()) + (("draw", noise is not None) if draw is not None else ()))
             entry = self._graphs.get(gk)
             if entry is not None and entry[3] != graph_version:
                 entry = None
             if entry is None:
                 with torch.cuda.device(self.device):
                     bufs = {n: None if t is None else torch.empty_like(t) for n, t in ins.items()}
-                    host = torch.empty(4 + 2 * S, dtype=torch.int32).pin_memory()
-                    block = torch.empty(4 + 2 * S, dtype=torch.int32, device=self.device)
+                    host = torch.empty(words, dtype=torch.int32).pin_memory()
+                    block = torch.empty(words, dtype=torch.int32, device=self.device)
                 stage = (bufs, host, block, torch.cuda.Event())
             else:
                 stage = entry[1]
@@ -743,7 +768,10 @@ class MuZeroSearch:
                 if t is not None:
                     bufs[n].copy_(t)
             ev.synchronize()  # the previous upload has left the pinned block (no-op when it has, or never ran)
-            _lib.check(self._L.mzs_stochastic_search_block(C.byref(kw), S, temperature, fraction, host.data_ptr()))
+            if draw is not None:
+                _lib.check(self._L.mzs_stochastic_search_block_draw(C.byref(kw), S, temperature, fraction, draw, host.data_ptr()))
+            else:
+                _lib.check(self._L.mzs_stochastic_search_block(C.byref(kw), S, temperature, fraction, host.data_ptr()))
             with torch.cuda.device(self.device):
                 block.copy_(host, non_blocking=True)
                 ev.record(torch.cuda.current_stream(self.device))
@@ -759,11 +787,15 @@ class MuZeroSearch:
                     launch(bufs, block)
                 entry = self._graphs[gk] = (g, stage, (self._stochastic_weights, self._stochastic_repr), graph_version)
             entry[0].replay()
+            if noise is not None and noise_out is not True:
+                noise_out.copy_(noise)
+                noise = noise_out
+        self.root_noise = noise
         return PolicyOutput(self.action, self.action_weights, self._export_tree() if with_tree else None)
 
     def search_stochastic_mlp(self, root_fn_output=None, key=0, invalid_actions=None, dirichlet_noise=None, dirichlet_fraction=0.25,
                               temperature=1.0, gumbel=None, with_tree=False, graph=False, graph_key=None,
-                              graph_version=0, one_launch=False, obs=None) -> PolicyOutput:
+                              graph_version=0, one_launch=False, obs=None, draw_dirichlet=None, noise_out=None) -> PolicyOutput:
         """search_stochastic with the two callables replaced by the library's own evaluation of the default stochastic MLP
         family (set_stochastic_mlp_weights): three launches per simulation -- select, the function of each root's parent
         kind, expand + backward -- and no torch op.  Arguments as search_stochastic; the kernel reads the bound weight
@@ -777,9 +809,27 @@ class MuZeroSearch:
         (set_stochastic_representation; embed_dim <= 64) -- inside the one launch with one_launch=True
         (mzs_mlp_stochastic_search_obs), else one more launch in front of the loop (stochastic_mlp_root).  The root's
         network value is then in `root_value`.  graph=True as before: a captured launch reads `obs` from a persistent
-        buffer, a replay sees the call's own observations."""
+        buffer, a replay sees the call's own observations.
+
+        draw_dirichlet=alpha (one_launch=True only, no dirichlet_noise): the root noise is drawn INSIDE that launch
+        (mzs_mlp_stochastic_search_draw) -- every root's wavefront draws its row of jax.random.dirichlet(split(key, 3)[1],
+        full([A], alpha), (global_batch,)), the bits of model._dirichlet / mzs_dirichlet, and mixes it in with
+        dirichlet_fraction: the results are those of passing that array as dirichlet_noise.  noise_out: a float32 [B, A]
+        device tensor that receives the drawn rows, or True for a buffer of the handle; either way they are in
+        `root_noise` afterwards (None when not asked for).  graph=True: still one kernel node, no noise staged; alpha
+        travels through the device block like the key."""
         if (root_fn_output is None) == (obs is None):
             raise ValueError("search_stochastic_mlp takes either root_fn_output or obs=, not both and not neither")
+        if draw_dirichlet is not None:
+            if not one_launch:
+                raise ValueError("draw_dirichlet needs one_launch=True: the noise is drawn inside the one-launch kernel")
+            if dirichlet_noise is not None:
+                raise ValueError("draw_dirichlet and dirichlet_noise exclude each other: the kernel draws the noise or reads it")
+            draw_dirichlet = float(draw_dirichlet)
+            if not (0.0 < draw_dirichlet < float("inf")):
+                raise ValueError(f"draw_dirichlet: alpha must be positive and finite, got {draw_dirichlet}")
+        elif noise_out is not None:
+            raise ValueError("noise_out needs draw_dirichlet=alpha")
         if self._stochastic_weights is None:
             raise ValueError("set_stochastic_mlp_weights() first")
         if obs is not None and self._stochastic_repr is None:
@@ -787,7 +837,7 @@ class MuZeroSearch:
         if one_launch:
             return self._search_stochastic_one_launch(root_fn_output, graph_key if graph_key is not None else "stochastic_mlp",
                                                       key, invalid_actions, dirichlet_noise, dirichlet_fraction, temperature,
-                                                      gumbel, with_tree, graph, graph_version, obs)
+                                                      gumbel, with_tree, graph, graph_version, obs, draw_dirichlet, noise_out)
         if obs is not None:
             root_fn_output = self.stochastic_mlp_root(obs)
 

@@ -20,10 +20,13 @@ and max over `--repeats` (at least 15).
 
 --act: the whole MuZero.act() of the default family on device observations at 2048's shape (4 actions + 32 outcomes,
 E = 16, support 10, obs_dim 16, `--sims` simulations, root noise drawn from the key, device outputs) at 64, 1024 and
-4096 roots, on the one-launch route with the root inference on the torch modules (stochastic_root_in_kernel=False) and
-inside the launch (True): two models of the same weights alternating in one process after warm_runtime() and five
-warm-up acts each.  A sample is the host wall time around ten consecutive acts and one synchronisation, per act, in
+4096 roots, on the one-launch route with the root inference on the torch modules (stochastic_root_in_kernel=False),
+inside the launch (True), and with the root noise drawn inside the launch as well (stochastic_noise_in_kernel=True): three
+models of the same weights alternating in one process after warm_runtime() and five warm-up acts each; --graph: all three
+with capture_graph=True.  A sample is the host wall time around ten consecutive acts and one synchronisation, per act, in
 microseconds (the torch root is launch-bound: its cost is host time); median, min and max over `--repeats` (at least 15).
+`dirichlet_launch` is the separate draw the third setting removes (model._dirichlet: mzs_dirichlet's launch and its
+output allocation), timed the same way.
 
 --unroll: the value priorities of the default family at (A, C, E, support) = (4, 32, 16, 10), obs_dim 16, for 32 and 4096
 windows of 10 steps: MuZero(stochastic_unroll_values=True).unroll_values on the kernel route (backend="hip", one launch)
@@ -214,35 +217,48 @@ def main_act(args):
     from muax_amd.utils import warm_runtime
     warm_runtime()
     repeats, inner, od, e = max(15, args.repeats), 10, 16, 16
-    routes = {False: "hip_stochastic_one_launch", True: "hip_stochastic_one_launch_root"}
+    # setting -> (the model's flags, the route its acts must take)
+    settings = {"torch_root": ({}, "hip_stochastic_one_launch"),
+                "root_in_kernel": (dict(stochastic_root_in_kernel=True), "hip_stochastic_one_launch_root"),
+                "noise_in_kernel": (dict(stochastic_root_in_kernel=True, stochastic_noise_in_kernel=True),
+                                    "hip_stochastic_one_launch_root_noise")}
     rows = []
     for batch in (64, 1024, 4096):
         obs = torch.rand(batch, od, generator=torch.Generator().manual_seed(batch)).cuda()
         models = {}
-        for flag in routes:
+        for name, (flags, _) in settings.items():
             net = mx.create_stochastic_muzero_network(e, A, C, 21, generator=torch.Generator().manual_seed(1))
-            m = models[flag] = mx.MuZero(net, policy="stochastic", stochastic_one_launch=True, stochastic_root_in_kernel=flag)
+            m = models[name] = mx.MuZero(net, policy="stochastic", stochastic_one_launch=True, capture_graph=args.graph, **flags)
             m.init(0, np.zeros((1, od), np.float32))
 
         def acts(m, n):
             for i in range(n):
                 m.act([7, i], obs, with_pi=True, with_value=True, obs_from_batch=True, num_simulations=args.sims,
                       device_outputs=True)
-        for flag, m in models.items():
+
+        def draws(n):
+            for i in range(n):
+                mx.model._dirichlet((7, i), 0.3, (batch, A), "cuda")
+        for name, m in models.items():
             acts(m, 5)
-            assert m._last_route == routes[flag], m._last_route
-        t = {flag: [] for flag in routes}
+            assert m._last_route == settings[name][1], m._last_route
+        draws(5)
+        t = {name: [] for name in list(settings) + ["dirichlet_launch"]}
         for _ in range(repeats):  # alternating
-            for flag, m in models.items():
-                t[flag].append(wall(lambda: acts(m, inner)) / inner)
-        a = {flag: m.act([7, 0], obs, obs_from_batch=True, num_simulations=args.sims, device_outputs=True)
-             for flag, m in models.items()}
-        row = {"roots": batch, "sims": args.sims, "repeats": repeats, "acts_per_sample": inner,
-               "same_actions": round(float((a[False] == a[True]).float().mean()), 4)}
-        for flag, name in ((False, "torch_root"), (True, "root_in_kernel")):
-            v = t[flag]
+            for name, m in models.items():
+                t[name].append(wall(lambda: acts(m, inner)) / inner)
+            t["dirichlet_launch"].append(wall(lambda: draws(inner)) / inner)
+        a = {name: [x.clone() for x in m.act([7, 0], obs, with_pi=True, obs_from_batch=True, num_simulations=args.sims,
+                                             device_outputs=True)] for name, m in models.items()}
+        row = {"roots": batch, "sims": args.sims, "graph": bool(args.graph), "repeats": repeats, "acts_per_sample": inner,
+               "same_actions": round(float((a["torch_root"][0] == a["root_in_kernel"][0]).float().mean()), 4),
+               "noise_in_kernel_same_bits": all(torch.equal(x.view(torch.int32), y.view(torch.int32))
+                                                for x, y in zip(a["root_in_kernel"], a["noise_in_kernel"]))}
+        for name, v in t.items():
             row[name] = {"median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1)}
         row["torch_root_over_in_kernel_median"] = round(row["torch_root"]["median_us"] / row["root_in_kernel"]["median_us"], 2)
+        row["root_in_kernel_over_noise_in_kernel_median"] = round(row["root_in_kernel"]["median_us"]
+                                                                  / row["noise_in_kernel"]["median_us"], 3)
         rows.append(row)
         print(json.dumps(row), flush=True)
     if args.out:
@@ -304,6 +320,7 @@ def main():
     ap.add_argument("--shape", type=int, nargs=5, metavar=("A", "C", "E", "SUPPORT", "OBS"),
                     help="--train: time this shape instead of 2048's two (built on demand where the library lists none)")
     ap.add_argument("--act", action="store_true")
+    ap.add_argument("--graph", action="store_true", help="--act: the models run with capture_graph=True")
     ap.add_argument("--unroll", action="store_true")
     args = ap.parse_args()
     if args.unroll:
