@@ -261,6 +261,11 @@ struct FusedCfg {
   static_assert(E <= 32 * 16, "row-distributed vectors");
 };
 
+// two actions, MuZero policy, plain record: the two children's value scores are computed as one packed pair
+// (puct_scores_pair); every other instance keeps the per-action code
+template <class C>
+constexpr bool kPairScores = C::A == 2 && !C::GUMBEL && !C::PH;
+
 // y = x . W + b for row-distributed vectors; W column(s) of this lane in VGPRs.
 template <int NIN, int NOUT>
 struct RowLinear {
@@ -769,6 +774,38 @@ MZ_DEV void puct_scores(float nval, float tn, const float (&prob)[A], const floa
     score[a] = vs[a] + policy_score;
   }
 }
+// puct_scores for a node with TWO children, its per-action values carried as (action 0, action 1) pairs: q, the
+// numerators and the sum with the policy scores are one v_pk_mul_f32 / v_pk_add_f32 each instead of two scalar ops
+// (a packed op rounds each half like the scalar one, and a lone wave issues it for 0.56 - 0.77 of the two:
+// tools/ubench_pk_issue.hip); min / max / selects have no packed form and stay scalar.  Every float operation and its
+// order are those of puct_scores<2, true, PRE>.  `pre`: the policy scores when PRE.
+template <bool PRE>
+MZ_DEV f32x2 puct_scores_pair(float nval, float tn, f32x2 prob, f32x2 val, const int (&vis)[2], f32x2 rew, float dis,
+                              f32x2 rcp1, f32x2 pre) {
+  const f32x2 q = rew + splat2(dis) * val;
+  const bool seen0 = vis[0] > 0, seen1 = vis[1] > 0;
+  const float safe0 = seen0 ? q.x : nval, safe1 = seen1 ? q.y : nval;
+  const float lo = fminf(fminf(nval, safe0), safe1), hi = fmaxf(fmaxf(nval, safe0), safe1);
+  const float span = fmaxf(hi - lo, 1e-8f);
+  const f32x2 num = (f32x2){seen0 ? q.x : lo, seen1 ? q.y : lo} - splat2(lo);
+  f32x2 vs;
+  const uint32_t low = min(f2u(num.x) - 1u, f2u(num.y) - 1u);  // 0 wraps to the top: only (0, 2^-100) fails the test
+  const bool risky = low < f2u(0x1p-100f) - 1u || span >= 0x1p100f;
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(risky) == 0, 1)) {
+    const float y0 = __builtin_amdgcn_rcpf(span);
+    const float y = __builtin_fmaf(__builtin_fmaf(-span, y0, 1.0f), y0, y0);
+    vs = div_newton2(num, splat2(span), splat2(y));
+  } else {
+    vs = (f32x2){num.x / span, num.y / span};
+  }
+  f32x2 policy = pre;
+  if constexpr (!PRE) {  // div_small on both halves
+    const f32x2 x = splat2(tn) * prob, d = (f32x2){(float)(vis[0] + 1), (float)(vis[1] + 1)};
+    const f32x2 q0 = x * rcp1;
+    policy = fma2(fma2(-q0, d, x), rcp1, q0);
+  }
+  return vs + policy;
+}
 
 // First-max argmax of the cached scores and the noise-independence test: mctx adds
 // 1e-7 * uniform[0,1) to every score; if fl(score_a + 1e-7) < score_best for every other
@@ -1095,7 +1132,14 @@ __global__ __launch_bounds__(C::THREADS, (C::PH && !C::LONG) ? 2 : 1) void mz_ac
       float rcp1[A];
 #pragma unroll
       for (int a = 0; a < A; ++a) rcp1[a] = 1.0f;  // no child visited yet
-      puct_scores<A>(v0, tbl[2], prob, val, vis, rew, dis, rcp1, sc);
+      if constexpr (kPairScores<C>) {
+        const f32x2 s2 = puct_scores_pair<false>(v0, tbl[2], (f32x2){prob[0], prob[1]}, (f32x2){val[0], val[1]}, vis,
+                                                 (f32x2){rew[0], rew[1]}, p.discount, (f32x2){rcp1[0], rcp1[1]}, splat2(0.0f));
+        sc[0] = s2.x;
+        sc[A - 1] = s2.y;
+      } else {
+        puct_scores<A>(v0, tbl[2], prob, val, vis, rew, dis, rcp1, sc);
+      }
     } else {
       float logit[A], gum[A];
 #pragma unroll
@@ -1481,7 +1525,15 @@ __global__ __launch_bounds__(C::THREADS, (C::PH && !C::LONG) ? 2 : 1) void mz_ac
         for (int a = 0; a < A; ++a) val[a] = (edge && pa == a) ? childv : val[a];
         const float nval = edge ? newv : pv;
         MZ_TICKW(9);  // value update
-        if constexpr (!C::GUMBEL) {
+        if constexpr (kPairScores<C>) {
+          static_assert(kFill, "the pair's policy scores come from the chain's wait slots");
+          const f32x2 s2 = puct_scores_pair<true>(nval, tn_rc.x, (f32x2){prob[0], prob[1]}, (f32x2){val[0], val[1]}, vis,
+                                                  (f32x2){rew[0], rew[1]}, p.discount, (f32x2){rcp1[0], rcp1[1]},
+                                                  (f32x2){sc[0], sc[A - 1]});
+          // root_invalid_actions: the root is only ever selected at depth 0
+          sc[0] = (pn == 0 && (inv_bits & 1u)) ? -INFINITY : s2.x;
+          sc[A - 1] = (pn == 0 && ((inv_bits >> 1) & 1u)) ? -INFINITY : s2.y;
+        } else if constexpr (!C::GUMBEL) {
           puct_scores<A, true, kFill>(nval, tn_rc.x, prob, val, vis, rew, dis, rcp1, sc);
 #pragma unroll
           for (int a = 0; a < A; ++a)  // root_invalid_actions: the root is only ever selected at depth 0
